@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: features tracked / s and ms per frame pair (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]     # the headline alone
+    python bench.py --gpus N --steps K --warmup W --full                   # + checks, roofline, CPU baseline, secondary figures, the other configs
+
+A plain run (no `--full`) does only what the headline needs: it sets up the resident pairs, warms up, times exactly K steps in one
+region (barrier + synchronise on both sides, MAX over ranks), optionally writes the records of the last timed step (`--dump-outputs
+DIR`: x.npy, y.npy, val.npy, float32, [pairs x features], pairs in seed order, pair.npy = the pair of each row; N > 1: every rank's
+pairs as rank 0 received them; a fixed, evenly spread sample of the pairs where all of them would exceed 64 MB) and
+prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (= region / K).  Everything described below
+from "The K-step timed region is repeated ..." on -- repeated regions, the oracle check, `roofline`, `cpu_baseline`, the secondary
+figures in `extra` and the config sweep -- is what `--full` adds.
 
 Workload at every N = BASELINE cfg-2 (1920x1080 synthetic pairs, 5000 features each, 7x7 window, 3 pyramid levels / subsampling 4,
 translation only).  `--resident-pairs` (default 72) DISTINCT pairs per GPU (seeds rank * 72 + 1 ...) are resident in HBM with their
@@ -24,12 +33,13 @@ N ...`) the same variables are already set and every process is a rank.  The RCC
 Consecutive groups of `--batch` pairs (default 8) go round-robin to `--inflight` contexts (default 3; one HIP stream each, nothing
 ordering them): frame pairs are independent, so the pairs of a group share every launch of their context (one batched pyramid build,
 one tracker launch -- the reference's workload for a stereo rig or two cameras) and the GPU overlaps the kernels of different groups.
-Every pair gets the full work of one KLTTrackFeatures call.  `ms_per_frame_pair` (= `extra.single_stream_ms_per_pair`) is one pair
-at a time on one stream, rotating through the resident pairs.  The K-step timed region (barrier + synchronise on both sides, MAX
-over ranks) is repeated until at least `--repeats` regions AND 6 s of timed work are in (never fewer than 5 regions); `ms_per_step`
-is the median region, the spread is in `extra.region_ms_per_step`.
+Every pair gets the full work of one KLTTrackFeatures call.  `ms_per_frame_pair` (= `extra.single_stream_ms_per_pair`, `--full`) is
+one pair at a time on one stream, rotating through the resident pairs; a plain run does not measure it and leaves it null (the
+throughput per pair is `config.ms_per_pair` = ms_per_step / pairs per step).  With `--full` the K-step timed region (barrier + synchronise on both
+sides, MAX over ranks) is repeated until at least `--repeats` regions AND 6 s of timed work are in (never fewer than 5 regions);
+`ms_per_step` is then the median region, the spread is in `extra.region_ms_per_step`.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  With `--full`, besides the contract fields it carries
   parity_checked -- the records of the last timed step of EVERY resident pair equal the CPU oracle's (the run fails otherwise);
   roofline     -- the dominant kernel of the step (largest share of device time), timed by its dispatches' own start / stop
                   timestamps in a second pass over the same pairs (events on every launch would distort the un-instrumented
@@ -38,8 +48,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline -- the CPU oracle (oracle/klt_oracle.c, a bit-exact port of the reference's Python/Cython/SciPy path) on the same
                   workload, 1 thread, rank 0, N = 1 only.
 `--config cfg1|cfg3|cfg4|cfg5` run the other BASELINE configs the same way: timed regions, records checked against the oracle,
-`roofline` with the per-kernel table, `cpu_baseline`.  The default run (cfg-2, one GPU) runs all four at their BASELINE counts as child
-processes of its own after the headline and keeps a compact record of each in `extra.configs` (benchlib/sweep.py); a config whose
+`roofline` with the per-kernel table, `cpu_baseline` (with or without `--full`).  `--full` on cfg-2 with one GPU runs all four at their
+BASELINE counts as child processes of its own after the headline and keeps a compact record of each in `extra.configs` (benchlib/sweep.py); a config whose
 records differ from the oracle's makes the whole run exit non-zero.
 """
 import argparse
@@ -81,7 +91,7 @@ def main():
                          "the launches of the timed regions and of the roofline pass, all of the headline's size")
     ap.add_argument("--no-api", action="store_true", help="skip the reference-shaped Python API figures in `extra`")
     ap.add_argument("--no-config-sweep", action="store_true",
-                    help="skip extra.configs (the default cfg-2 run otherwise runs --config cfg1, cfg3, cfg4 --pairs 256 and cfg5 --frames 512, each in a "
+                    help="skip extra.configs (a --full cfg-2 run otherwise runs --config cfg1, cfg3, cfg4 --pairs 256 and cfg5 --frames 512, each in a "
                          "child process of its own, after the headline, and folds a compact record of each into its line); --no-extras implies it")
     ap.add_argument("--no-sequences", action="store_true", help="skip extra.sequence_from_host (a 1080p and a 4K sequence fed from pinned host memory)")
     ap.add_argument("--config", choices=["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"], default="cfg2",
@@ -104,7 +114,16 @@ def main():
                          "its ramp and tail once per launch: 11.7 us per frame in a 4-frame launch, 9.8 in a 16-frame launch)")
     ap.add_argument("--min-timed-s", type=float, default=MIN_TIMED_S,
                     help="the timed regions of a run add up to at least this many seconds (0 for profiler passes, which replay every kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2: everything besides the headline -- repeated timed regions (--repeats, --min-timed-s), the records checked "
+                         "against the CPU oracle, roofline, CPU baseline, secondary figures and the config sweep (each still subject to the "
+                         "--no-* options above).  Without it a cfg2 run times exactly --steps steps in one region and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="cfg2: write the records of the last timed step to DIR/x.npy, y.npy, val.npy (float32, [pairs x features]) and "
+                         "pair.npy (the pair of each row)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config != "cfg2":
+        ap.error("--dump-outputs is implemented for the headline config (cfg2)")
     common.MIN_TIMED_S = args.min_timed_s
 
     # N > 1 without a launcher: start the ranks ourselves.  Nothing above or below this point has touched the GPU yet

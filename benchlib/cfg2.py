@@ -102,12 +102,18 @@ def run_cfg2(args, json_fd):
         for _ in range(args.steps):
             one_step()
 
-    elapsed, regions, enqueue_s = timed_regions(ranks, region, args.repeats)
+    steps_before = step_no[0]
+    if args.full:
+        elapsed, regions, enqueue_s = timed_regions(ranks, region, args.repeats)
+    else:                                               # a plain run: exactly --steps timed steps, in one region
+        elapsed, enqueue_s = ranks.timed(region)
+        regions = [elapsed]
+    timed_steps = step_no[0] - steps_before             # steps run inside the timed regions, all of them
     t_last = (step_no[0] - 1) % 2
-    rccl = ranks.validation(args.steps)                 # (collective: every rank, right behind the timed regions)
+    rccl = ranks.validation(args.steps) if args.full else {}     # (collective: every rank, right behind the timed regions)
 
     # correctness of what was timed: the last step's records of EVERY resident pair (and, N > 1, what the gather delivered of them)
-    outs = {}
+    outs, gathered = {}, []
     for c, cx in enumerate(ctxs):
         tab = cx.featbuf_download((T_OUT0, T_OUT1)[t_last], PL * NFEAT).reshape(PL, NFEAT)
         for lp in range(PL):
@@ -115,13 +121,30 @@ def run_cfg2(args, json_fd):
         if distributed:                 # what this rank received from itself equals what it produced
             got = cx.featbuf_download((T_GATH0, T_GATH1)[t_last], world * PL * NFEAT).reshape(world, PL, NFEAT)
             assert np.array_equal(got[rank], tab), "gathered records differ"
+            gathered.append(got)
+    if rank == 0 and args.dump_outputs:
+        # the records of the last timed step, pairs in seed order (N > 1: every rank's pairs as this rank received them)
+        if distributed:
+            recs = np.empty((world * NP, NFEAT), gathered[0].dtype)
+            for c, got in enumerate(gathered):
+                for lp in range(PL):
+                    recs[np.arange(world) * NP + pair_index(c, lp)] = got[:, lp]
+        else:
+            recs = np.stack([outs[i] for i in range(NP)])
+        keep = np.arange(len(recs))
+        fit = DUMP_LIMIT_BYTES // (NFEAT * 3 * 4 + 8)
+        if len(keep) > fit:                             # more pairs than the limit holds: a fixed sample, spread evenly over them
+            keep = np.unique(np.linspace(0, len(recs) - 1, fit).astype(np.int64))
+        dumped = {k: recs[k][keep].astype(np.float32) for k in ("x", "y", "val")}
+        dumped["pair"] = keep.astype(np.float64)
+        dump_outputs(args.dump_outputs, dumped)
     out, fl = outs[0], lists[0]
     tracked = int(np.count_nonzero(out["val"] >= 0))
     live = out["val"] == 0
     shift = (float(np.median(out["x"][live] - fl["x"][live])), float(np.median(out["y"][live] - fl["y"][live])))
-    ko = load_oracle() if rank == 0 else None
+    ko = load_oracle() if rank == 0 and args.full else None
     parity = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         checks = []
         if ko:
             nthreads = usable_cores()
@@ -145,7 +168,7 @@ def run_cfg2(args, json_fd):
     # second pass: per-kernel timing + iteration counters for the roofline, on context 0 over its own pairs
     roofline = None
     ms_per_pair = elapsed / (args.steps * NP) * 1e3
-    if rank == 0:
+    if rank == 0 and args.full:
         passes = max(1, min(args.steps, 4))
 
         def ctx0_passes(n=passes):
@@ -213,9 +236,12 @@ def run_cfg2(args, json_fd):
     # secondary figures (never `value`): selection time, the one-stream figure, the cache-resident figure and the PCIe-inclusive pair time
     extra = None
     ms_single = None
-    reg = region_stats(regions, args.steps, elapsed)
-    if rank == 0 and args.no_extras:
-        extra = {"region_ms_per_step": reg, "host_enqueue_ms_per_step": enqueue_s / args.steps * 1e3, "note": "--no-extras: secondary figures skipped"}
+    reg = dict(region_stats(regions, args.steps, elapsed), timed_steps=timed_steps)
+    if rank == 0 and (args.no_extras or not args.full):
+        extra = {"region_ms_per_step": reg, "host_enqueue_ms_per_step": enqueue_s / args.steps * 1e3,
+                 "note": "--no-extras: secondary figures skipped" if args.full else
+                         "plain run: ONE timed region of exactly --steps steps; repeated regions, the oracle check, roofline, CPU baseline, "
+                         "secondary figures and the other configs come with --full"}
     elif rank == 0:
         reps = 10
         ctx.sync()
@@ -356,7 +382,7 @@ def run_cfg2(args, json_fd):
             extra["pcie_pipelined_frac_of_link_next_to_a_kernel"] = min(1.0, extra["pcie_pipelined_GBps"] / link["1080p_next_to_a_kernel"])
 
     cpu = None
-    if rank == 0 and not distributed and not args.no_cpu_baseline and ko:
+    if rank == 0 and args.full and not distributed and not args.no_cpu_baseline and ko:
         a0, a1 = frames[0][0].astype(np.float32), frames[0][1].astype(np.float32)
         cpu = cpu_baseline_of(ko, lambda: ko.track_features(p, ko.Pyramids(p, a0), ko.Pyramids(p, a1), lists[0].copy()), NFEAT,
                               "pyramids of both frames + track 5000 features of ONE pair of cfg-2 (1920x1080, seed %d)" % seeds[0],
@@ -368,7 +394,7 @@ def run_cfg2(args, json_fd):
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         line = base_line(world * NP * NFEAT * args.steps / elapsed, world, args.steps, args.warmup, ms_per_step,
-                         ms_single if ms_single is not None else ms_per_pair,
+                         ms_single if ms_single is not None else (ms_per_pair if args.full else None),     # (plain run: not measured)
                          ("THROUGHPUT over %d independent pairs in flight (%d contexts x %d pairs per launch); the literal single-pair figure is "
                           "`single_pair`.  " % (nctx * B, nctx, B) if nctx * B > 1 else "ONE pair at a time on one stream.  ") +
                          "cfg-2: %d DISTINCT 1920x1080 synthetic pairs resident per GPU (seeds %d..%d; own frame slots, pyramids and "
@@ -387,7 +413,7 @@ def run_cfg2(args, json_fd):
                              "pairs_in_flight": nctx * B, "contexts": nctx, "pairs_per_launch": B, "resident_pairs": NP,
                              "features_per_pair": NFEAT, "pairs_per_step": NP * world, "ms_per_pair": ms_per_pair, "tracked": tracked,
                              "recovered_shift_px": shift, "imposed_shift_px": list(synth.DEFAULT_SHIFT),
-                             "rccl_ranks": rccl.get("rccl_ranks", 0),
+                             "rccl_ranks": rccl.get("rccl_ranks", None if distributed else 0),     # (None: not validated, plain run)
                              "parallelism": "%d pairs per GPU" % NP + (", one RCCL all-gather (libkltgpu side stream) of each context's [%d pairs x "
                                                                       "5000] record table per step" % PL if distributed else "")})
         line.update(parity)
@@ -408,7 +434,7 @@ def run_cfg2(args, json_fd):
     # (twelve HIP streams, 4.2 GB of slots) are closed first -- with them open the same calls read 5-15 % slower (more queues than the
     # hardware schedules side by side).  One-GPU secondary figures: with N > 1 the other ranks are done by now and must not be kept
     # waiting for rank 0's extras.
-    if line is not None and isinstance(extra, dict) and not args.no_extras and not distributed:
+    if line is not None and isinstance(extra, dict) and args.full and not args.no_extras and not distributed:
         if not args.no_api:
             extra.update(api_figures_in_a_child_process())
             # ... and once more with the child confined to eight CPUs of the GPU's NUMA node, as a deployment would pin it: the host part of a
@@ -425,7 +451,7 @@ def run_cfg2(args, json_fd):
                                            "4k": sequence_from_host(ranks.local_rank, 3840, 2160, 20000, 128, link.get("4k")),
                                            "note": sequence_from_host.__doc__.split("  Secondary")[0].replace("\n    ", " ")}
     sweep_failed = []
-    if line is not None and isinstance(extra, dict) and not args.no_extras and not distributed and not args.no_config_sweep:
+    if line is not None and isinstance(extra, dict) and args.full and not args.no_extras and not distributed and not args.no_config_sweep:
         # the other four BASELINE configs, each in a child process of its own (benchlib/sweep.py): compact records in extra.configs
         from .sweep import config_sweep
         extra["configs"], sweep_failed = config_sweep(["--no-cpu-baseline"] if args.no_cpu_baseline else [])

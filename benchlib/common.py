@@ -461,6 +461,22 @@ def emit(json_fd, line):
     os.write(json_fd, (json.dumps(line) + "\n").encode())      # the ONE JSON line on the real stdout
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy (float32 / float64 only, 64 MB at most in all)"""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), "%s: %s" % (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+
+
 def base_line(value, n_gpus, steps, warmup, ms_step, ms_pair, workload, scaling="weak", extra_cfg=None):
     cfg = {"workload": workload}
     cfg.update(extra_cfg or {})

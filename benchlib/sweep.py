@@ -1,5 +1,5 @@
-"""The other four BASELINE configs next to the headline: after the cfg-2 line's contexts are closed, `bench.py --gpus 1`
-runs `bench.py --config cfg1 | cfg3 | cfg4 | cfg5` at the BASELINE counts (cfg-4: 256 pairs on the one GPU; cfg-5: the 512-frame clip), each
+"""The other four BASELINE configs next to the headline: after the cfg-2 line's contexts are closed, `bench.py --gpus 1
+--full` runs `bench.py --config cfg1 | cfg3 | cfg4 | cfg5` at the BASELINE counts (cfg-4: 256 pairs on the one GPU; cfg-5: the 512-frame clip), each
 in a fresh child process that opens the GPU itself (started as a child and waited for -- never an exec: this process has initialised the GPU),
 and folds a compact record of each child's line into `extra.configs`.  A child that fails -- its records differ from the oracle's, a
 fraction of peak above 1, a crash, a timeout -- leaves an `error` record and makes the parent exit non-zero AFTER it has printed its line."""

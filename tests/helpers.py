@@ -122,3 +122,21 @@ def colour_of(grey):
     in tests/golden/gen_colour_images.py (three different functions of the frame, so that the luma is not the frame itself)"""
     g = np.asarray(grey, np.uint8)
     return np.dstack([g, np.roll(g, 3, axis=1), (255 - g // 2).astype(np.uint8)])
+
+
+def assert_dumped_cfg2_pair(dump_dir, row, seed):
+    """row `row` of what `bench.py --dump-outputs DIR` wrote (x.npy, y.npy, val.npy) = the CPU oracle's selection + tracking of the cfg-2
+    pair of seed `seed`"""
+    from benchlib.common import NFEAT, TOL_PX, cfg2_context, oracle_track, records_equal
+    from oracle import klt_oracle as ko
+    p = params_from_tc(cfg2_context())
+    f0, f1 = synth.synth_pair(1920, 1080, seed=seed)
+    ko.set_threads(8)
+    sel = ko.select_good_features(p, f0.astype(np.float32), NFEAT)
+    ko.set_threads(1)
+    want = oracle_track(ko, p, f0, f1, sel, threads=8)
+    got = np.zeros(NFEAT, want.dtype)
+    for k in ("x", "y", "val"):
+        got[k] = np.load(_os.path.join(dump_dir, k + ".npy"))[row]
+    same, dx = records_equal(got, want)
+    assert same and dx <= TOL_PX, (row, seed, dx)

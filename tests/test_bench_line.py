@@ -1,8 +1,12 @@
-"""CPU-side checks of bench.py's line plumbing: the config sweep (benchlib/sweep.py) that folds cfg-1 / 3 / 4 / 5 into the default line."""
+"""CPU-side checks of bench.py's line plumbing: the config sweep (benchlib/sweep.py) that folds cfg-1 / 3 / 4 / 5 into the --full line,
+rank validation, --dump-outputs."""
 import json
+import os
 import subprocess
+import sys
 import types
 
+import numpy as np
 import pytest
 
 from benchlib import sweep
@@ -129,3 +133,27 @@ def test_rank_validation_fails_the_run_when_a_rank_saw_fewer_peers_than_asked(mo
     r.ctxs = [_FakeCtx(4, 0, [_peer(4, 1, 2.0), _peer(4, 1, 2.0), _peer(4, 3, 2.0)])]
     v = r.validation(1)
     assert v["rccl_rank_ids_seen"] == 3 and "different rank numbers" in v["rccl_validation_failed"]
+
+
+# ---------------------------------------------------------------------------------------------------------------- --dump-outputs
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    from benchlib import common
+    x = np.arange(12, dtype=np.float32).reshape(3, 4)
+    common.dump_outputs(str(tmp_path / "out"), {"x": x, "val": np.full((3, 4), -1.0, np.float64)})
+    assert sorted(os.listdir(tmp_path / "out")) == ["val.npy", "x.npy"]
+    got = np.load(tmp_path / "out" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x) and np.load(tmp_path / "out" / "val.npy").dtype == np.float64
+    with pytest.raises(AssertionError):
+        common.dump_outputs(str(tmp_path / "ints"), {"val": np.zeros(4, np.int32)})
+    monkeypatch.setattr(common, "DUMP_LIMIT_BYTES", 40)
+    with pytest.raises(SystemExit):
+        common.dump_outputs(str(tmp_path / "big"), {"x": x})
+    assert not (tmp_path / "ints").exists() and not (tmp_path / "big").exists()
+
+
+def test_dump_outputs_is_refused_where_it_is_not_implemented(tmp_path):
+    """the option is checked with the arguments, before anything is set up"""
+    from conftest import REPO
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "cfg4", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not (tmp_path / "out").exists()

@@ -32,10 +32,10 @@ def run_bench(extra_args, timeout=1500, **env_kw):
 
 
 def test_the_drivers_command_line_prints_a_clean_record():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- exactly what the driver runs at round end: no figure above its roof,
-    iteration counters that describe the launches they are divided by, 72 distinct pairs all checked against the oracle, a timed
-    phase long enough to be seen from outside the process, and a value that does not depend on K."""
-    line = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's command line with everything besides the headline: no
+    figure above its roof, iteration counters that describe the launches they are divided by, 72 distinct pairs all checked against the
+    oracle, a timed phase long enough to be seen from outside the process, and a value that does not depend on K."""
+    line = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
     roof = line["roofline"]
     assert line["parity_checked"] is True and line["parity_cases"] == 72 and line["max_abs_dx"] <= 1e-3
     assert line["config"]["resident_pairs"] == 72 and line["config"]["pairs_per_step"] == 72 and line["config"]["contexts"] == 3
@@ -62,9 +62,42 @@ def test_the_drivers_command_line_prints_a_clean_record():
     assert "api_error" not in x and x["api_ms_per_KLTTrackFeatures_pil"] < 1.5 * x["api_ms_per_KLTTrackFeatures"], (x.get("api_error"), x.get("api_pil_note"))
     assert x["sequence_from_host"]["4k"]["arrangement"] == "one_copy_stream"
     # the same figures from a run with five times the steps per region
-    long = run_bench(["--gpus", "1", "--steps", "100", "--warmup", "5", "--repeats", "8", "--no-cpu-baseline", "--no-extras"])
+    long = run_bench(["--gpus", "1", "--steps", "100", "--warmup", "5", "--repeats", "8", "--no-cpu-baseline", "--no-extras", "--full"])
     assert abs(long["roofline"]["step_algorithmic_bytes"] / roof["step_algorithmic_bytes"] - 1) < 0.05
     assert abs(long["value"] / line["value"] - 1) < 0.08, (long["value"], line["value"])     # (seen: 0.3-1.7 %)
+
+
+def test_a_plain_run_times_its_steps_and_dumps_what_it_computed(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline alone -- ONE timed region of exactly K
+    steps (counted, and its time grows with K), the contract fields, none of --full's figures -- and DIR holds the records of the last
+    timed step of every resident pair: the same from run to run, and the CPU oracle's."""
+    from benchlib.common import NFEAT
+    from helpers import assert_dumped_cfg2_pair
+    args = ["--gpus", "1", "--warmup", "1", "--resident-pairs", "6", "--inflight", "3", "--batch", "2"]
+    line = run_bench(args + ["--steps", "20", "--dump-outputs", str(tmp_path / "a")])
+    reg = line["extra"]["region_ms_per_step"]
+    assert line["metric"] == "features tracked/sec" and line["unit"] == "features/s" and line["higher_is_better"] is True and line["dtype"]
+    assert line["steps"] == 20 and line["warmup"] == 1 and reg["regions"] == 1 and reg["timed_steps"] == 20
+    assert abs(reg["timed_s_total"] * 1e3 / 20 / line["ms_per_step"] - 1) < 1e-9
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / (6 * NFEAT) - 1) < 1e-9
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "parity_checked" not in line and "configs" not in line["extra"]
+    assert line["ms_per_frame_pair"] is None                  # (one pair at a time on one stream is a --full figure)
+    again = run_bench(args + ["--steps", "20", "--dump-outputs", str(tmp_path / "b")])
+    assert again["extra"]["region_ms_per_step"]["timed_steps"] == 20
+    # four times the steps: four times the steps counted and about four times the timed region
+    longer = run_bench(args + ["--steps", "80", "--dump-outputs", str(tmp_path / "c")])
+    reg4 = longer["extra"]["region_ms_per_step"]
+    assert longer["steps"] == 80 and reg4["regions"] == 1 and reg4["timed_steps"] == 80
+    assert 2.5 < reg4["timed_s_total"] / reg["timed_s_total"] < 6.0, (reg4["timed_s_total"], reg["timed_s_total"])
+    rec = {}
+    for k in ("x", "y", "val"):
+        a, b, c = (np.load(tmp_path / d / (k + ".npy")) for d in ("a", "b", "c"))
+        assert a.dtype == np.float32 and a.shape == (6, NFEAT) and np.array_equal(a, b) and np.array_equal(a, c), k
+        rec[k] = a
+    assert np.array_equal(np.load(tmp_path / "a" / "pair.npy"), np.arange(6.0))
+    assert ((rec["val"] >= 0).sum(axis=1) > 4500).all()
+    for i in (0, 5):                                    # pair i = seed i + 1; pairs 0 and 5 sit on different contexts
+        assert_dumped_cfg2_pair(tmp_path / "a", i, i + 1)
 
 
 def test_bench_refuses_figures_above_the_roof():

@@ -45,7 +45,7 @@ def test_cfg2_ranks_with_their_own_pairs_and_the_all_gather(world, tmp_path, stu
     """`bench.py --gpus N`: every rank runs its own distinct pairs (seeds rank * NP + 1 ...), each context's record table is all-gathered
     every step; rank 0 checks all of its own pairs against the oracle AND pair 0 of the last rank as it arrived through the gather."""
     line = run_ranks(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--repeats", "5", "--resident-pairs", "4", "--inflight", "2", "--batch", "2",
-                      "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0"], tmp_path, stub_rccl)
+                      "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0", "--full", "--dump-outputs", str(tmp_path / "dump")], tmp_path, stub_rccl)
     assert line["n_gpus"] == world and line["config"]["rccl_ranks"] == world and line["config"]["pairs_per_step"] == 4 * world
     assert line["parity_checked"] is True and line["parity_cases"] == 5 and line["max_abs_dx"] <= 1e-3
     assert "as received through the all-gather" in line["parity_what"]
@@ -54,15 +54,35 @@ def test_cfg2_ranks_with_their_own_pairs_and_the_all_gather(world, tmp_path, stu
     assert val["rccl_ranks"] == val["rccl_ranks_largest_communicator"] == val["rccl_rank_ids_seen"] == val["world_size"] == world
     assert 0 < val["per_rank_ms_per_step"]["min"] <= val["per_rank_ms_per_step"]["max"] <= line["ms_per_step"] * 1.0001
     assert "rccl_validation_failed" not in val
+    # --dump-outputs: rank 0 writes every rank's records of the last timed step as the all-gather delivered them, pairs in seed order
+    from helpers import assert_dumped_cfg2_pair
+    for k in ("x", "y", "val"):
+        a = np.load(tmp_path / "dump" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (4 * world, 5000), k
+    assert np.array_equal(np.load(tmp_path / "dump" / "pair.npy"), np.arange(4.0 * world))
+    assert ((np.load(tmp_path / "dump" / "val.npy") >= 0).sum(axis=1) > 4500).all()
+    assert_dumped_cfg2_pair(tmp_path / "dump", 4 * world - 1, 4 * world)       # the last rank's last pair, on its second context
 
 
 def test_cfg2_three_contexts_per_rank_as_in_the_default_arrangement(tmp_path, stub_rccl):
     """The default line runs three contexts per rank (three record tables, three all-gathers per step through one communicator each,
     chained in issue order): the same at a small size, two ranks."""
     line = run_ranks(["--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "5", "--resident-pairs", "6", "--inflight", "3", "--batch", "2",
-                      "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0"], tmp_path, stub_rccl)
+                      "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0", "--full"], tmp_path, stub_rccl)
     assert line["n_gpus"] == 2 and line["config"]["rccl_ranks"] == 2 and line["config"]["contexts"] == 3 and line["config"]["pairs_per_step"] == 12
     assert line["parity_checked"] is True and line["parity_cases"] == 7 and line["max_abs_dx"] <= 1e-3
+    # ... and a plain run of the same arrangement (no --full): one region of exactly --steps steps, nothing validated, and rank 0 dumps
+    # both ranks' records of the last timed step as the all-gathers delivered them
+    from helpers import assert_dumped_cfg2_pair
+    plain = run_ranks(["--gpus", "2", "--steps", "3", "--warmup", "1", "--resident-pairs", "6", "--inflight", "3", "--batch", "2",
+                       "--dump-outputs", str(tmp_path / "dump")], tmp_path / "plain", stub_rccl)
+    assert plain["n_gpus"] == 2 and plain["config"]["pairs_per_step"] == 12 and plain["config"]["rccl_ranks"] is None
+    assert "parity_checked" not in plain and plain["roofline"] is None and plain["extra"]["region_ms_per_step"]["timed_steps"] == 3
+    for k in ("x", "y", "val"):
+        a = np.load(tmp_path / "dump" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (12, 5000), k
+    assert np.array_equal(np.load(tmp_path / "dump" / "pair.npy"), np.arange(12.0))
+    assert_dumped_cfg2_pair(tmp_path / "dump", 11, 12)                         # rank 1's last pair, on its third context
 
 
 def test_cfg4_shards_of_unequal_size_through_the_gather_with_counts(tmp_path, stub_rccl):
@@ -147,8 +167,8 @@ def test_the_drivers_multi_gpu_launch_line(tmp_path, stub_rccl):
     os.makedirs(env["KLT_STUB_RCCL_DIR"], exist_ok=True)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--repeats", "5", "--resident-pairs", "4", "--inflight", "2", "--batch", "2", "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0"],
-                       env=env, capture_output=True, text=True, timeout=900)
+                        "--repeats", "5", "--resident-pairs", "4", "--inflight", "2", "--batch", "2", "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -165,7 +185,8 @@ def test_ordering_stress_with_four_and_eight_ranks(world, tmp_path, stub_rccl):
     gather with a count per rank; (c) cfg-5's baton through all ranks.  50 steps of (a) and (b), 5 passes of the baton through every rank;
     rank 0 checks its own records AND what the last rank contributed against the oracle every time."""
     steps = ["--steps", "10", "--warmup", "1", "--repeats", "5", "--min-timed-s", "0", "--no-cpu-baseline"]
-    a = run_ranks(["--gpus", str(world), "--resident-pairs", "6", "--inflight", "3", "--batch", "2", "--no-extras"] + steps, tmp_path / "a", stub_rccl)
+    a = run_ranks(["--gpus", str(world), "--resident-pairs", "6", "--inflight", "3", "--batch", "2", "--no-extras", "--full"] + steps, tmp_path / "a",
+                  stub_rccl)
     assert a["n_gpus"] == world and a["config"]["rccl_ranks"] == world and a["config"]["contexts"] == 3
     assert a["config"]["pairs_per_step"] == 6 * world and a["parity_checked"] is True and a["parity_cases"] == 7 and a["max_abs_dx"] <= 1e-3
     b = run_ranks(["--config", "cfg4", "--gpus", str(world), "--pairs", "257"] + steps, tmp_path / "b", stub_rccl)

@@ -7,7 +7,7 @@ mkdir -p $O
 for rep in 1 2; do
   for which in tree other; do
     if [ $which = other ]; then export KLT_GPU_LIB=$OTHER; else unset KLT_GPU_LIB; fi
-    timeout 400 python3 bench.py --no-extras --no-cpu-baseline --no-api "$@" > $O/ab_${which}_$rep.json 2> $O/ab_${which}_$rep.err
+    timeout 400 python3 bench.py --full --no-extras --no-cpu-baseline --no-api "$@" > $O/ab_${which}_$rep.json 2> $O/ab_${which}_$rep.err
     python3 - <<PY
 import json
 d = json.loads(open("$O/ab_${which}_$rep.json").read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ export KLT_PROFILE_TAG=r04_$TAG
 export KLT_PROFILE_BATCH=8
 O=gpurun_out
 mkdir -p $O
-PMC="--inflight 1 --resident-pairs 8 --steps 3 --warmup 1 --min-timed-s 0 --repeats 5 --no-cpu-baseline --no-extras"
+PMC="--inflight 1 --resident-pairs 8 --steps 3 --warmup 1 --min-timed-s 0 --repeats 5 --no-cpu-baseline --no-extras --full"
 i=0
 dirs=""
 for set in "TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum" "TA_DATA_STALLED_BY_TC_CYCLES_sum TA_BUFFER_READ_WAVEFRONTS_sum" \
