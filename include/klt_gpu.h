@@ -112,6 +112,9 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
 /* test hook: >= 0: the library's (value + 1)-th device / pinned-host allocation from now is refused as if memory had run out (KLT_ERR_NOMEM; the
  * context stays usable, the call can be repeated); -1 (default): off.  Lets the tests walk every allocation site of a call sequence. */
 #define KLT_OPT_FAIL_ALLOC_AFTER 19
+/* 1 (default): the level-0 kernel with the fused first reduction walks each 64-column strip down in bands and computes every row of every
+ * stage once (frames of >= 128 columns); 0: the tiled kernel, which computes each tile's vertical halo again.  Same results bit for bit. */
+#define KLT_OPT_L0_STREAM 21
 int klt_set_option(klt_ctx *ctx, int option, int value);
 
 /* ---- parameters and taps ------------------------------------------------------------------- */

@@ -180,7 +180,7 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     // launch also consumes the reduction stage's input (4 per pixel of level 0 -- the part of 4 (N0 + N1) that no longer
     // touches HBM); pyr_vreduce is charged the stage's output, so the step total is unchanged
     TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + N * 12 + (hred ? 4.0 * N : 0.0));
-    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred))
+    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream))
         return fail(c, KLT_ERR_DEVICE, std::string("smooth_grad launch: ") + hipGetErrorString((hipError_t)e));
     return 0;
 }

@@ -156,6 +156,7 @@ struct klt_ctx {
     float *h1 = nullptr;                      // H1 planes of the fused first reduction (one per frame of a batch)
     size_t h1_cap = 0;
     bool fuse_hreduce = true;                 // KLT_OPT_FUSED_HREDUCE
+    bool l0_stream = true;                    // KLT_OPT_L0_STREAM
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
     // selection scratch

@@ -18,7 +18,10 @@
 // commutatively before multiplying.  So the smoothed value computed at a virtual position equals the smoothed
 // image at the reflected position, which is what the differentiation must see.  The host only takes this
 // path when the smoothing taps are symmetric (they are Gaussians) and the tile fits in LDS.
+#include <cmath>
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 
 #include "klt_internal.h"
 
@@ -43,8 +46,22 @@ __device__ unsigned g_block_hw[8192];
             }                                                                                            \
         }                                                                                                \
     } while (0)
+// streaming kernel: ticks of each stage summed over the bands of segment 1 of frame 0 (stage 0 includes the barrier after the previous
+// band's stage 4)
+__device__ long long g_stream_clk[64 * 8];
+#define STREAM_CLK_START long long stream_t_ = wall_clock64()
+#define STREAM_MARK(n)                                                                                  \
+    do {                                                                                                \
+        if (threadIdx.x == 0 && blockIdx.y == 1 && blockIdx.z == 0 && blockIdx.x < 64) {               \
+            const long long now_ = wall_clock64();                                                      \
+            g_stream_clk[blockIdx.x * 8 + (n)] += now_ - stream_t_;                                     \
+            stream_t_ = now_;                                                                           \
+        }                                                                                               \
+    } while (0)
 #else
 #define STAGE_MARK(n) do { } while (0)
+#define STREAM_CLK_START do { } while (0)
+#define STREAM_MARK(n) do { } while (0)
 #endif
 
 namespace {
@@ -234,13 +251,16 @@ __device__ __forceinline__ void load_taps(TapRegs<NT> &r, const Taps &t)
 // four outputs.  The per-output FP64 expression and its operation order are unchanged.
 // Column frames (relative to the tile's first output column): A (raw) starts at -8, B / C at -4, D / E at 0,
 // all row strides are multiples of 4 floats.  Needs tap radii <= 4.
-template <int NT, int SYM>
+// ZC (antisymmetric taps only): the centre tap is +0.0 and the centre sample is >= +0 and finite, so the first product c[0] * k[H]
+// is +0 and the first addition +0 + p equals p + 0.0 bit for bit (-0 included): the multiply is dropped, the addition kept.
+template <int NT, int SYM, bool ZC = false>
 __device__ __forceinline__ float corr_regs(const double *c /* centre */, const TapRegs<NT> &t)
 {
     constexpr int H = NT / 2;
-    double acc = c[0] * t.k[H];
+    static_assert(!ZC || SYM < 0, "centre-tap elision is for the derivative taps");
+    double acc = ZC ? (c[-H] - c[H]) * t.k[0] + 0.0 : c[0] * t.k[H];
 #pragma unroll
-    for (int jj = -H; jj < 0; jj++) {
+    for (int jj = ZC ? -H + 1 : -H; jj < 0; jj++) {
         const double pr = SYM > 0 ? c[jj] + c[-jj] : c[jj] - c[-jj];
         acc = acc + pr * t.k[H + jj];
     }
@@ -577,6 +597,374 @@ __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradA
     else smooth_grad_rb_tile<TIn, SMOOTH, NS, NG, ND, TH_, NTHR, HRED, true>(a, lds, nc, nr);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Streaming level-0 kernel: the stages of smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>, but a workgroup walks a segment of
+// `seg_h` rows of a 64-column strip in bands of SB output rows and computes every row of every stage once.  The tiled kernel computes
+// its vertical halo again in every tile (42 / 38 / 38 rows of stages 1 / 2 / 3 for 32 output rows); here the last NS - 1 horizontally
+// smoothed rows and the last 6 rows of the two gradient intermediates are carried to the next band, and the halo is paid once per
+// segment.  Same expressions, same operation order, same virtual coordinates as the tiled kernel (header of this file).
+//
+// Band with output rows [y, y + SB), cbase = y + 3 (frame row of C row 0):
+//   A  raw rows (f32)           A row i  = frame row cbase + rs + i        SB rows x AW      (region 1)
+//   B  H-smoothed               B row j  = frame row cbase - rs + j        SB + 2 rs rows    rows [0, 2 rs) carried (Bc)
+//   C  smoothed image           C row i  = frame row cbase + i             SB rows x BW      (region 1, over A)
+//   DE gradient intermediates   DE row k = frame row cbase - 6 + k         SB + 6 rows       rows [0, 6) carried
+// A DE row holds the D row (derivative taps along x) in floats [0, 64) and the E row (Gaussian taps) in [64, 128).  B lives in the DE
+// rows past the carried six (dead once stage 2 has run; its last 2 rs rows are saved to Bc first).  The prologue band of a segment
+// (PRO) fills the carries: C rows [SB - 6, SB) = frame rows [s0 - 3, s0 + 3), no gradient output.
+// The image and the H1 plane are stored from the C rows of [s0, s0 + seg_h); the gradients of [y, y + SB) from each steady band.
+constexpr int SB = 32;
+
+template <int NS>
+struct StreamLds {
+    static constexpr int HB = 12, rs = NS / 2;
+    static constexpr int AW = TW + 2 * HB + 8, BW = TW + 2 * HB, DEW = 2 * TW;
+    static constexpr int R1 = SB * AW;                           // A, then C
+    static constexpr int NDE = (SB + 6) * DEW;                   // DE (B over its rows >= 6)
+    static constexpr int NBC = 2 * rs * BW;                      // Bc
+    static constexpr int total = R1 + NDE + NBC;
+    static_assert((SB + 2 * rs) * BW <= SB * DEW, "B must fit in the DE rows past the carried ones");
+};
+
+// Taps read from the kernel argument (the SmoothGradArgs at offset 0 of the kernarg segment) where they are used: the address goes through
+// an empty asm statement so that the compiler cannot hoist the scalar loads out of the band loop (the four tap sets held across it spill)
+// (smooth_grad_stream keeps its SmoothGradArgs as its first parameter for this.)
+template <int NT>
+__device__ __forceinline__ void load_taps_here(TapRegs<NT> &r, const size_t arg_offset)
+{
+    typedef const __attribute__((address_space(4))) char *kptr;
+    kptr p = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + arg_offset;
+    asm volatile("" : "+s"(p));
+#pragma unroll
+    for (int i = 0; i < NT; i++) r.k[i] = ((const __attribute__((address_space(4))) double *)p)[i];
+}
+
+// u8 frames: the raw rows of a steady band (A rows [0, SB), 4 bytes per quad) are requested one band ahead and stay in flight in three
+// registers while the band before runs its stages 1-4.  Edge bands read element by element through the reflect map (and wait for it).
+template <int NS>
+__device__ __forceinline__ void l0_fetch_u8(const uint8_t *raw, const int nc, const int nr, const int tx0, const int cbase, uint32_t (&w)[SB * (TW + 32) / 4 / 256])
+{
+    constexpr int AQ = (TW + 32) / 4, N0 = SB * AQ, U0 = N0 / 256;
+    static_assert(N0 % 256 == 0, "a steady band's quads are whole rounds of the workgroup");
+    const int ya = cbase + NS / 2, xa = tx0 - 16, tid = threadIdx.x;
+    if ((nc & 3) == 0 && xa >= 0 && xa + 4 * AQ <= nc && ya >= 0 && ya + SB <= nr) {
+        const plane_rsrc rawp = plane_of(raw);
+        const unsigned raw_b0 = (unsigned)ya * (unsigned)nc + (unsigned)xa;
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            const int i = tid + u * 256;
+            w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, raw_b0 + __umul24((unsigned)(i / AQ), (unsigned)nc) + 4u * (unsigned)(i % AQ), 0, 0);
+        }
+    } else {
+        uint8_t e[U0][4];
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            const int i = tid + u * 256;
+            const int y = ya + i / AQ, x = xa + 4 * (i % AQ);
+            const uint8_t *row = raw + (size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int xx = x + k;
+                e[u][k] = row[xx < 0 ? -1 - xx : xx >= nc ? 2 * nc - 1 - xx : xx];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U0; u++) w[u] = e[u][0] | (uint32_t)e[u][1] << 8 | (uint32_t)e[u][2] << 16 | (uint32_t)e[u][3] << 24;
+    }
+}
+
+template <typename TIn, int NS, bool ZC, bool EDGE, bool PRO>
+__device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
+                                               const int cbase, const int s0, const int ylim, const bool vec2_ok, const bool vec4_ok,
+                                               uint32_t (&pre)[SB * (TW + 32) / 4 / 256])
+{
+    constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead (l0_fetch_u8)
+    STREAM_CLK_START;
+    constexpr int NTHR = 256, NG = 7, ND = 7;
+    using L = StreamLds<NS>;
+    constexpr int HB = L::HB, rs = L::rs, AW = L::AW, BW = L::BW, DEW = L::DEW, DW = TW;
+    constexpr int AQ = AW / 4, BQ = BW / 4, DQ = DW / 4;
+    constexpr int CLO = PRO ? SB - 6 : 0;                        // C / DE rows made by this band: C [CLO, SB), DE [CLO + 6, SB + 6)
+    constexpr int BLO = PRO ? CLO : 2 * rs;                      // B rows made: [BLO, SB + 2 rs)
+    constexpr int ALO = BLO - 2 * rs;                            // A rows loaded: [ALO, SB)
+    static_assert(ALO >= 0, "prologue rows");
+    float *const A = lds, *const C = lds, *const DE = lds + L::R1, *const B = DE + 6 * DEW, *const Bc = DE + L::NDE;
+    // tid goes through an empty asm statement once per band: the per-thread index math of the stages is then recomputed in each band
+    // instead of being hoisted out of the band loop and held in registers across all stages
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int b = blockIdx.z;
+    const TIn *__restrict__ raw = (const TIn *)a.raw[b];
+    const unsigned row_bytes = 4u * (unsigned)nc;
+    const unsigned band_b0 = (unsigned)cbase * row_bytes + 4u * (unsigned)tx0;   // byte offset of (cbase, tx0) in the f32 planes, mod 2^32
+
+    // ---- stage 0: raw rows -> registers; (after the previous band's stage 4) -> A, carried rows into place
+    {
+        constexpr int NA = SB - ALO, N0 = NA * AQ, U0 = (N0 + NTHR - 1) / NTHR, X0 = -(HB + 4);
+        const int ya = cbase + rs + ALO, xa = tx0 + X0;          // frame position of A (ALO, 0)
+        float4 v[U0];
+        const bool interior = (nc & 3) == 0 && xa >= 0 && xa + AW <= nc && ya >= 0 && ya + NA <= nr;
+        if (PF && !PRO) {
+            static_assert(!PF || PRO || U0 == sizeof(pre) / 4, "prefetched quads");
+#pragma unroll
+            for (int u = 0; u < U0; u++) {
+                const uint32_t w = pre[u < int(sizeof(pre) / 4) ? u : 0];
+                v[u].x = (float)(w & 0xffu); v[u].y = (float)((w >> 8) & 0xffu);
+                v[u].z = (float)((w >> 16) & 0xffu); v[u].w = (float)(w >> 24);
+            }
+        } else if (interior) {
+            const plane_rsrc rawp = plane_of(raw);
+            const unsigned raw_b0 = ((unsigned)ya * (unsigned)nc + (unsigned)xa) * (unsigned)sizeof(TIn);
+            if (sizeof(TIn) == 1) {
+                uint32_t w[U0];
+#pragma unroll
+                for (int u = 0; u < U0; u++) {
+                    const int i = min(tid + u * NTHR, N0 - 1);
+                    w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, raw_b0 + __umul24((unsigned)(i / AQ), (unsigned)nc) + 4u * (unsigned)(i % AQ), 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < U0; u++) {
+                    v[u].x = (float)(w[u] & 0xffu); v[u].y = (float)((w[u] >> 8) & 0xffu);
+                    v[u].z = (float)((w[u] >> 16) & 0xffu); v[u].w = (float)(w[u] >> 24);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U0; u++) {
+                    const int i = min(tid + u * NTHR, N0 - 1);
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rawp, raw_b0 + __umul24((unsigned)(i / AQ), row_bytes) + 16u * (unsigned)(i % AQ), 0, 0);
+                    v[u] = __builtin_bit_cast(float4, q);
+                }
+            }
+        } else {
+            // bands at the frame's edges (the host takes this kernel for frames of >= 2 strips and >= 64 rows: one reflection
+            // brings every index inside)
+            TIn e[U0][4];
+#pragma unroll
+            for (int u = 0; u < U0; u++) {
+                const int i = min(tid + u * NTHR, N0 - 1);
+                const int y = ya + i / AQ, x = xa + 4 * (i % AQ);
+                const TIn *row = raw + (size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int xx = x + k;
+                    e[u][k] = row[xx < 0 ? -1 - xx : xx >= nc ? 2 * nc - 1 - xx : xx];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U0; u++) {
+                v[u].x = (float)e[u][0]; v[u].y = (float)e[u][1]; v[u].z = (float)e[u][2]; v[u].w = (float)e[u][3];
+            }
+        }
+        if (!PRO) __syncthreads();                               // the previous band's stage 4 has read DE
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            const int i = tid + u * NTHR;
+            if (i < N0) *reinterpret_cast<float4 *>(A + ALO * AW + i * 4) = v[u];
+        }
+        if (!PRO) {
+            // B rows [0, 2 rs) from Bc; DE rows [SB, SB + 6) -> [0, 6)
+            constexpr int NB = 2 * rs * BQ, NDQ = 6 * (DEW / 4);
+            for (int i = NTHR - 1 - tid; i < NB + NDQ; i += NTHR) {
+                if (i < NB) *reinterpret_cast<float4 *>(B + 4 * i) = *reinterpret_cast<const float4 *>(Bc + 4 * i);
+                else *reinterpret_cast<float4 *>(DE + 4 * (i - NB)) = *reinterpret_cast<const float4 *>(DE + SB * DEW + 4 * (i - NB));
+            }
+        }
+    }
+    __syncthreads();
+    STREAM_MARK(0);
+    if (PF && (PRO || cbase - 3 + SB < ylim)) l0_fetch_u8<NS>((const uint8_t *)raw, nc, nr, tx0, PRO ? s0 + 3 : cbase + SB, pre);
+    {
+        TapRegs<NS> ks;
+        load_taps_here(ks, offsetof(SmoothGradArgs, smooth.k));
+        // ---- stage 1: horizontal smoothing, A -> B rows [BLO, SB + 2 rs)
+        for (int i = tid; i < (SB + 2 * rs - BLO) * BQ; i += NTHR) {
+            const int j = BLO + i / BQ, q = i % BQ;
+            double v[12];
+            widen12(A + (j - 2 * rs) * AW + 4 * q, v);
+            float4 o;
+            o.x = corr_regs<NS, 1>(v + 4, ks); o.y = corr_regs<NS, 1>(v + 5, ks);
+            o.z = corr_regs<NS, 1>(v + 6, ks); o.w = corr_regs<NS, 1>(v + 7, ks);
+            *reinterpret_cast<float4 *>(B + j * BW + 4 * q) = o;
+        }
+        __syncthreads();
+        STREAM_MARK(1);
+        // ---- stage 2: vertical smoothing, B -> C rows [CLO, SB) (+ store the strip's columns of the rows of the segment)
+        const plane_rsrc img = plane_of(a.img[b]);
+        constexpr int BH = BW / 2, G2 = (SB - CLO + 3) / 4;
+        for (int i = (tid + NTHR / 4) & (NTHR - 1); i < G2 * BH; i += NTHR) {
+            const int r = CLO + 4 * (i / BH), h = i % BH;
+            const unsigned img_b0 = band_b0 + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h) - (unsigned)(4 * HB);   // (cbase + r, tx0 - HB + 2 h)
+            double v[2][NS + 3];
+#pragma unroll
+            for (int j = 0; j < NS + 3; j++) {
+                const int rj = min(r + j, SB + 2 * rs - 1);      // rows past the band only feed outputs that are not made
+                const float2 t = *reinterpret_cast<const float2 *>(B + rj * BW + 2 * h);
+                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
+            }
+#pragma unroll
+            for (int dr = 0; dr < 4; dr++) {
+                const int rr = r + dr;
+                if (rr >= SB) break;
+                float2 o;
+                o.x = corr_regs<NS, 1>(v[0] + rs + dr, ks); o.y = corr_regs<NS, 1>(v[1] + rs + dr, ks);
+                *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = o;
+                const int y = cbase + rr, x = tx0 - HB + 2 * h;
+                if (h >= HB / 2 && h < HB / 2 + DW / 2 && (!PRO || y >= s0) && y < ylim) {
+                    const unsigned ob = img_b0 + (unsigned)dr * row_bytes;
+                    if (!EDGE && vec2_ok) plane_store2(img, ob, o);
+                    else if (!EDGE) { plane_store(img, ob, o.x); plane_store(img, ob + 4, o.y); }
+                    else {
+                        if (x < nc) plane_store(img, ob, o.x);
+                        if (x + 1 < nc) plane_store(img, ob + 4, o.y);
+                    }
+                }
+            }
+        }
+        // the last 2 rs rows of B are the next band's first ones
+        for (int i = NTHR - 1 - tid; i < 2 * rs * BQ; i += NTHR)
+            *reinterpret_cast<float4 *>(Bc + 4 * i) = *reinterpret_cast<const float4 *>(B + SB * BW + 4 * i);
+    }
+    __syncthreads();
+    STREAM_MARK(2);
+    // ---- stage 3: horizontal pass of both gradients, C rows [CLO, SB) -> DE rows [CLO + 6, SB + 6)
+    {
+        TapRegs<NG> kg;
+        TapRegs<ND> kd;
+        load_taps_here(kg, offsetof(SmoothGradArgs, ggauss.k));
+        load_taps_here(kd, offsetof(SmoothGradArgs, gderiv.k));
+        for (int i = (tid + NTHR / 2) & (NTHR - 1); i < (SB - CLO) * DQ; i += NTHR) {
+            const int r = CLO + i / DQ, q = i % DQ;
+            double v[12];
+            widen12(C + r * BW + 4 * q + (HB - 4), v);
+            float4 d, e;
+            d.x = corr_regs<ND, -1, ZC>(v + 4, kd); d.y = corr_regs<ND, -1, ZC>(v + 5, kd);
+            d.z = corr_regs<ND, -1, ZC>(v + 6, kd); d.w = corr_regs<ND, -1, ZC>(v + 7, kd);
+            e.x = corr_regs<NG, 1>(v + 4, kg); e.y = corr_regs<NG, 1>(v + 5, kg);
+            e.z = corr_regs<NG, 1>(v + 6, kg); e.w = corr_regs<NG, 1>(v + 7, kg);
+            *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + 4 * q) = d;
+            *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + DW + 4 * q) = e;
+        }
+    }
+    {
+        // ---- stage 3b: horizontal pass of the pyramid reduction at the columns 4x + 2 of the C rows of the segment (as in the tiled kernel)
+        constexpr int NR = 21, HR = NR / 2;
+        TapRegs<HR + 1> kr;                                     // k[0..HR] (symmetric)
+        load_taps_here(kr, offsetof(SmoothGradArgs, reduce.k));
+        const plane_rsrc h1 = plane_of(a.h1[b]);
+        const int h1_nc = a.h1_nc;
+        const unsigned h1_row_bytes = 4u * (unsigned)h1_nc, h1_b0 = (unsigned)cbase * h1_row_bytes + (unsigned)tx0;   // (cbase, tx0 / 4)
+        for (int i = tid; i < (SB - CLO) * (DQ / 2); i += NTHR) {
+            const int r = CLO + i / (DQ / 2), xs = 2 * (i % (DQ / 2));
+            const int y = cbase + r;
+            typedef const volatile __attribute__((address_space(3))) f32x4 *lds_quad_ptr;
+            const lds_quad_ptr p = (lds_quad_ptr)(C + r * BW + 4 * xs + (HB - 8));
+            double v[28];
+#pragma unroll
+            for (int u = 0; u < 7; u++) {
+                const f32x4 t = p[u];
+                v[4 * u] = (double)t.x; v[4 * u + 1] = (double)t.y; v[4 * u + 2] = (double)t.z; v[4 * u + 3] = (double)t.w;
+            }
+#pragma unroll
+            for (int o = 0; o < 2; o++) {
+                const double *c = v + HR + 4 * o;
+                double acc = c[0] * kr.k[HR];
+#pragma unroll
+                for (int jj = -HR; jj < 0; jj++) acc = acc + (c[jj] + c[-jj]) * kr.k[HR + jj];
+                const int xg = tx0 / 4 + xs + o;
+                if ((!PRO || y >= s0) && y < ylim && (!EDGE || xg < h1_nc))
+                    plane_store(h1, h1_b0 + __umul24((unsigned)r, h1_row_bytes) + 4u * (unsigned)(xs + o), (float)acc);
+            }
+        }
+    }
+    if (PRO) return;
+    __syncthreads();
+    STREAM_MARK(3);
+    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29): D -> gradx (Gaussian taps), E -> grady (derivative taps)
+    TapRegs<NG> kg;
+    TapRegs<ND> kd;
+    load_taps_here(kg, offsetof(SmoothGradArgs, ggauss.k));
+    load_taps_here(kd, offsetof(SmoothGradArgs, gderiv.k));
+    const plane_rsrc gxy = plane_of(a.gx[b]);
+    constexpr int DH = DW / 2;
+    const int y0 = cbase - 3;
+    const bool full = y0 + SB <= ylim;
+    for (int i = tid; i < (SB / 4) * DH; i += NTHR) {
+        const int r = 4 * (i / DH), h = i % DH;
+        const int x = tx0 + 2 * h;
+        if ((EDGE && x >= nc) || (!full && y0 + r >= ylim)) continue;
+        float2 ox[4], oy[4];
+        {
+            double v[2][NG + 3];
+#pragma unroll
+            for (int j = 0; j < NG + 3; j++) {
+                const float2 t = *reinterpret_cast<const float2 *>(DE + (r + j) * DEW + 2 * h);
+                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
+            }
+#pragma unroll
+            for (int dr = 0; dr < 4; dr++) {
+                ox[dr].x = corr_regs<NG, 1>(v[0] + NG / 2 + dr, kg); ox[dr].y = corr_regs<NG, 1>(v[1] + NG / 2 + dr, kg);
+            }
+        }
+        {
+            double v[2][ND + 3];
+#pragma unroll
+            for (int j = 0; j < ND + 3; j++) {
+                const float2 t = *reinterpret_cast<const float2 *>(DE + (r + j) * DEW + DW + 2 * h);
+                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
+            }
+#pragma unroll
+            for (int dr = 0; dr < 4; dr++) {
+                oy[dr].x = corr_regs<ND, -1, ZC>(v[0] + ND / 2 + dr, kd); oy[dr].y = corr_regs<ND, -1, ZC>(v[1] + ND / 2 + dr, kd);
+            }
+        }
+        const unsigned g_b0 = 2u * (band_b0 - 3u * row_bytes + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // (y0 + r, x), interleaved
+#pragma unroll
+        for (int dr = 0; dr < 4; dr++) {
+            if (!full && y0 + r + dr >= ylim) break;
+            const unsigned ob = g_b0 + (unsigned)dr * 2u * row_bytes;
+            float2 p0, p1;
+            p0.x = ox[dr].x; p0.y = oy[dr].x; p1.x = ox[dr].y; p1.y = oy[dr].y;
+            if (!EDGE && vec4_ok) plane_store4(gxy, ob, p0, p1);
+            else {
+                plane_store2(gxy, ob, p0);
+                if (!EDGE || x + 1 < nc) plane_store2(gxy, ob + 8, p1);
+            }
+        }
+    }
+    STREAM_MARK(4);
+}
+
+template <typename TIn, int NS, bool ZC, bool EDGE>
+__device__ __forceinline__ void l0_stream_segment(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
+                                                  const int s0, const int ylim)
+{
+    const int b = blockIdx.z;
+    const bool vec2_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.img[b]) & 7) == 0;
+    const bool vec4_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.gx[b]) & 15) == 0;
+    uint32_t pre[SB * (TW + 32) / 4 / 256];
+    l0_stream_band<TIn, NS, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, vec2_ok, vec4_ok, pre);
+    for (int y = s0; y < ylim; y += SB) l0_stream_band<TIn, NS, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, vec2_ok, vec4_ok, pre);
+}
+
+// grid = (ceil(ncols / 64), ceil(nrows / seg_h), batch); seg_h a multiple of SB.
+// `a` must stay the FIRST parameter: load_taps_here reads the taps at kernarg offset offsetof(SmoothGradArgs, ...).
+template <typename TIn, int NS, bool ZC>
+__global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGradArgs a, int seg_h)
+{
+    __shared__ __attribute__((aligned(16))) float lds[StreamLds<NS>::total];
+    const int b = blockIdx.z;
+    const int tx0 = blockIdx.x * TW, s0 = blockIdx.y * seg_h;
+    const int nc = a.dim_c[b] ? a.dim_c[b] : a.ncols, nr = a.dim_r[b] ? a.dim_r[b] : a.nrows;
+    if (tx0 >= nc || s0 >= nr) return;
+    const int ylim = min(s0 + seg_h, nr);
+    const bool inside = tx0 + TW <= nc && tx0 / 4 + TW / 4 <= a.h1_nc;
+    STAGE_MARK(0);
+    if (inside) l0_stream_segment<TIn, NS, ZC, false>(a, lds, nc, nr, tx0, s0, ylim);
+    else l0_stream_segment<TIn, NS, ZC, true>(a, lds, nc, nr, tx0, s0, ylim);
+    STAGE_MARK(5);
+}
+
 // The f32-rounded horizontal result is kept in LDS as the double it widens to (one widening per sample instead of one
 // per tap of the vertical pass); the source tile stays f32 (an f64 tile was measured slower: half the LDS matters more).
 template <int NT, int STRIDE>
@@ -830,7 +1218,29 @@ int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch)
     return 0;
 }
 
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred)
+// Segment height of the streaming level-0 kernel: 160 rows, the fastest of the cfg-2 sweep (profiles/README.md).  KLT_L0_SEG (a multiple of 32)
+// overrides it: experiment hook.
+static int l0_stream_seg()
+{
+    static const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0;
+    return force > 0 && force % SB == 0 ? force : 160;
+}
+
+// The derivative taps' centre is +0.0 and every sample the two derivative passes see is >= +0 (a u8 frame, smoothing and Gaussian
+// taps without sign bits): corr_regs<..., ZC> may drop the centre product
+static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
+{
+    auto sign_free = [](const Taps &t) {
+        for (int i = 0; i < t.n; i++)
+            if (std::signbit(t.k[i]) || !std::isfinite(t.k[i])) return false;
+        return true;
+    };
+    uint64_t centre;
+    std::memcpy(&centre, &a.gderiv.k[a.gderiv.n / 2], sizeof(centre));
+    return kind == 0 && centre == 0 && sign_free(a.smooth) && sign_free(a.ggauss);
+}
+
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream)
 {
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
@@ -852,6 +1262,27 @@ int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int ki
             // round 2: 29.9 / 29.9 / 30.4 us event-timed against 28.1 for the 32-row tile: the extra halo work outweighs the occupancy)
             // (three / two workgroups per CU instead of four -- dynamic LDS padding, same kernel -- read 0.0379 / 0.0382 ms per pair with
             // three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
+            // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
+            // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
+            // frame, 1080p batches below 8) keep the tiled kernel, whose 32-row tiles fill the chip
+            const int sh = l0_stream_seg();
+            const dim3 gs((a.ncols + TW - 1) / TW, (a.nrows + sh - 1) / sh, batch);
+            if (stream && a.ncols >= 2 * TW && (long long)gs.x * gs.y * gs.z >= 2048) {
+                const bool zc = deriv_centre_elidable(a, kind);
+#define KLT_L0S(T, NSV, ZCOK)                                                                                                      \
+    do {                                                                                                                       \
+        if (ZCOK && zc) klt_launch((smooth_grad_stream<T, NSV, ZCOK>), gs, blk, 0, s, a, sh);                                 \
+        else klt_launch((smooth_grad_stream<T, NSV, false>), gs, blk, 0, s, a, sh);                                           \
+        return 0;                                                                                                              \
+    } while (0)
+                // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
+                if (kind == 0 && a.smooth.n == 5) KLT_L0S(uint8_t, 5, true);
+                if (kind == 1 && a.smooth.n == 5) KLT_L0S(float, 5, false);
+                if (kind == 0 && a.smooth.n == 9) KLT_L0S(uint8_t, 9, true);
+                if (kind == 1 && a.smooth.n == 9) KLT_L0S(float, 9, false);
+#undef KLT_L0S
+                return -1;
+            }
             if (kind == 0 && a.smooth.n == 5) { klt_launch((smooth_grad_rb<uint8_t, true, 5, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
             if (kind == 1 && a.smooth.n == 5) { klt_launch((smooth_grad_rb<float, true, 5, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
             if (kind == 0 && a.smooth.n == 9) { klt_launch((smooth_grad_rb<uint8_t, true, 9, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }

@@ -1,10 +1,14 @@
 // Stage timing of the level-0 kernel: includes the product source with KLT_STAGE_CLOCKS and prints, for 64 workgroups of one
-// tile row, the wall-clock ticks (100 MHz) spent between the stage marks.  Build (from the repo root):
+// tile row, the wall-clock ticks (100 MHz) spent between the stage marks.  `T`: the tiled kernel with the fused reduction, `s`: the
+// streaming kernel (per-stage ticks summed over the bands of one segment), both on 16 1080p u8 frames with interleaved gradient planes
+// as at cfg-2.  Build (from the repo root):
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DKLT_STAGE_CLOCKS -Iinclude -Ipyfeaturetrack_amd/csrc tools/mb/l0_stages.hip -o tools/mb/l0_stages
 #include "../../pyfeaturetrack_amd/csrc/pyramid_kernels.hip"
 #include <cstdio>
 #include <cmath>
 #include <vector>
+
+thread_local hipEvent_t g_klt_stamp_start, g_klt_stamp_stop;      // (defined by the library's api_context.hip; klt_launch reads them)
 
 static void gauss_taps(Taps &g, Taps &d, double sigma, int n)
 {
@@ -27,11 +31,14 @@ int main(int argc, char **argv)
     a.ncols = nc; a.nrows = nr; a.R = 3;
     std::vector<uint8_t> h((size_t)nc * nr);
     for (size_t i = 0; i < h.size(); i++) h[i] = (uint8_t)((i * 2654435761u) >> 24);
-    for (int b = 0; b < 2; b++) {
+    const bool tiled16 = argc > 1 && argv[1][0] == 'T', stream = argc > 1 && argv[1][0] == 's';
+    const int B = tiled16 || stream ? 16 : 2;
+    if (B == 16) a.gstride = 2;
+    for (int b = 0; b < B; b++) {
         uint8_t *raw; float *img, *gx, *gy;
-        hipMalloc(&raw, h.size()); hipMalloc(&img, 4 * h.size()); hipMalloc(&gx, 4 * h.size()); hipMalloc(&gy, 4 * h.size());
+        hipMalloc(&raw, h.size()); hipMalloc(&img, 4 * h.size()); hipMalloc(&gx, 8 * h.size()); hipMalloc(&gy, 4 * h.size());
         hipMemcpy(raw, h.data(), h.size(), hipMemcpyHostToDevice);
-        a.raw[b] = raw; a.img[b] = img; a.gx[b] = gx; a.gy[b] = gy;
+        a.raw[b] = raw; a.img[b] = img; a.gx[b] = gx; a.gy[b] = B == 16 ? gx + 1 : gy;
     }
     PyrReduceArgs pr = {};
     gauss_taps(pr.taps, dummy, 3.6, 21);
@@ -40,8 +47,8 @@ int main(int argc, char **argv)
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     const bool plain = argc > 1 && argv[1][0] == 'p';      // the kernel without the fused horizontal reduction
     a.reduce = pr.taps; a.h1_nc = nc / 4;
-    for (int b = 0; b < 2; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
-    auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, 2, 0, !plain); };
+    for (int b = 0; b < B; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
+    auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, B, 0, !plain, stream); };
     for (int rep = 0; rep < 3; rep++) go();
     hipDeviceSynchronize();
     hipEventRecord(e0);
@@ -50,16 +57,35 @@ int main(int argc, char **argv)
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("kernel: %.2f us per launch\n", ms * 1000 / 20);
     long long clk[64 * 8];
+    if (stream) {
+        // g_stream_clk accumulated over every launch of this run (3 + 20): per launch, per band of 32 rows (4 bands + the prologue)
+        hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_stream_clk), sizeof(clk));
+        printf("ticks of 10 ns per 32-row band (segment 1 of frame 0, prologue share included)\nblock | load  hsm  vsm  hgrad vgrad | total\n");
+        double sum[5] = {};
+        for (int b = 0; b < 30; b++) {
+            const long long *c = clk + b * 8;
+            double t = 0;
+            for (int k = 0; k < 5; k++) { sum[k] += c[k] / 23.0 / 4; t += c[k] / 23.0 / 4; }
+            printf("%4d | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", b, c[0] / 92.0, c[1] / 92.0, c[2] / 92.0, c[3] / 92.0, c[4] / 92.0, t);
+        }
+        printf("mean | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", sum[0] / 30, sum[1] / 30, sum[2] / 30, sum[3] / 30, sum[4] / 30,
+               (sum[0] + sum[1] + sum[2] + sum[3] + sum[4]) / 30);
+        return 0;
+    }
     hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_stage_clk), sizeof(clk));
     long long t0 = clk[0];
     const int nrow = level ? 8 : reduce ? 15 : 30;
     for (int b = 0; b < nrow; b++) t0 = clk[b * 8] < t0 ? clk[b * 8] : t0;
     printf("ticks of 10 ns; tile row 8 of frame 0\nblock  start | load  hsm  vsm  hgrad vgrad | total\n");
+    double tsum[5] = {};
     for (int b = 0; b < nrow; b++) {
         const long long *c = clk + b * 8;
+        for (int k = 0; k < 5; k++) tsum[k] += c[k + 1] - c[k];
         if (reduce) printf("%4d %6lld | load %4lld  hpass %4lld  vpass %4lld | %5lld\n", b, c[0] - t0, c[1] - c[0], c[2] - c[1], c[5] - c[2], c[5] - c[0]);
         else printf("%4d %6lld | %4lld %4lld %4lld %4lld %4lld | %5lld\n", b, c[0] - t0, c[1] - c[0], c[2] - c[1], c[3] - c[2], c[4] - c[3], c[5] - c[4], c[5] - c[0]);
     }
+    if (!reduce) printf("mean | %5.0f %5.0f %5.0f %5.0f %5.0f\n", tsum[0] / nrow, tsum[1] / nrow, tsum[2] / nrow, tsum[3] / nrow, tsum[4] / nrow);
+    if (tiled16) return 0;
     static long long bc[8192 * 2];
     static unsigned hw[8192];
     hipMemcpyFromSymbol(bc, HIP_SYMBOL(g_block_clk), sizeof(bc));
