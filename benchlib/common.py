@@ -353,7 +353,7 @@ def timed_pass(ctx, run, mode):
 KLT_OPT_TRACK_TREE_SUMS = 18
 # VGPRs of the two forms of the quad tracker kernels, from the compiler's metadata (tools/kernel_regs.py prints them from a fresh
 # compile of track_kernels.hip; a CPU test compares)
-TRACKER_VGPRS = {7: {"exact": 124, "tree": 94}, 15: {"exact": 96, "tree": 96}}
+TRACKER_VGPRS = {7: {"exact": 120, "tree": 90}, 15: {"exact": 96, "tree": 96}}
 
 
 def tree_sums_probe(ctx, launch, read, bytes_per_launch, window, reps=6):

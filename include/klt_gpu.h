@@ -126,8 +126,8 @@ int klt_set_kernels(klt_ctx *ctx, int which, const double *gauss, int ng, const 
 /* ---- frames (slots) ------------------------------------------------------------------------ */
 /* replaces `np.array(img.convert("F"))`, trackFeatures.py:165,176 / selectGoodFeatures.py:190.
  * pitch is in elements.  The upload is enqueued; the host buffer may be reused on return.
- * Limits: 1 <= ncols, nrows <= 65535 and ncols * nrows < 2^28 (the kernels address a plane with 32-bit byte offsets below 2 GB, and
- * the interleaved gradient plane of level 0 has 8 bytes per pixel); a frame
+ * Limits: 1 <= ncols, nrows <= 65535 and ncols * nrows < 2^27 (the kernels address a plane with 32-bit byte offsets below 2 GB, and
+ * the pixel-record plane of level 0 has 12 bytes per pixel); a frame
  * beyond them is KLT_ERR_ARG here, at klt_upload_u8_async and at the stand-alone convolution / pyramid calls. */
 int klt_upload_u8(klt_ctx *ctx, int slot, const uint8_t *px, int ncols, int nrows, int pitch);
 int klt_upload_f32(klt_ctx *ctx, int slot, const float *px, int ncols, int nrows, int pitch);
@@ -352,8 +352,9 @@ int klt_comm_set_timeout(klt_ctx *ctx, double ms);
 int klt_comm_allreduce_max(klt_ctx *ctx, double *inout, int n);
 
 /* ---- test / inspection hooks --------------------------------------------------------------- */
-/* pyramid: 0 = image, 1 = gradx, 2 = grady; dst holds level_ncols*level_nrows floats.  (On the device the two gradient planes of a level are
- * stored interleaved -- gradx, grady of a pixel side by side, DESIGN.md section 4 --; this call and klt_download_select_f32 hand out separate planes.) */
+/* pyramid: 0 = image, 1 = gradx, 2 = grady; dst holds level_ncols*level_nrows floats.  (On the device the three planes of a level are
+ * stored as pixel records -- image, gradx, grady of a pixel side by side, DESIGN.md section 5 --; this call and klt_download_select_f32 hand
+ * out separate planes.) */
 int klt_level_dims(klt_ctx *ctx, int slot, int level, int *ncols, int *nrows);
 int klt_download_f32(klt_ctx *ctx, int slot, int pyramid, int level, float *dst);
 /* selection intermediates of the last klt_select*: 0 = smoothed image, 1 = gradx, 2 = grady (full frame),

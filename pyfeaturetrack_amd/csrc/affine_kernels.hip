@@ -19,8 +19,8 @@
 
 namespace {
 
-// ST = element stride of the plane: 1 (image planes, the kernel's own template copies) or KLT_GRAD_STRIDE (one of the two interleaved
-// gradient planes of a frame; `img` is then the plane's own first element)
+// ST = element stride of the plane: 1 (the kernel's own template copies) or KLT_PIX_STRIDE (one of the three planes of a frame's pixel
+// records; `img` is then the plane's own first element)
 template <int ST = 1>
 __device__ __forceinline__ float bilinear_at(const float *__restrict__ img, int nc, float x, float y)
 {
@@ -165,9 +165,9 @@ __global__ __launch_bounds__(64) void affine_kernel(AffineArgs a)
         if (x0 - thw < 0 || y0 - thh < 0 || x0 + thw >= nc || y0 + thh >= nr) return;     // upstream asserts; stay template-less
         for (int k = lane; k < tn; k += 64) {
             const size_t o = (size_t)(y0 - thh + k / tw) * nc + (x0 - thw + k % tw);
-            tpl[k] = a.i1[o];
-            tpl[tn + k] = a.gx1[KLT_GRAD_STRIDE * o];                 // interleaved gradient planes (klt_internal.h)
-            tpl[2 * tn + k] = a.gy1[KLT_GRAD_STRIDE * o];
+            tpl[k] = a.i1[KLT_PIX_STRIDE * o];                        // pixel records (klt_internal.h)
+            tpl[tn + k] = a.gx1[KLT_PIX_STRIDE * o];
+            tpl[2 * tn + k] = a.gy1[KLT_PIX_STRIDE * o];
         }
         if (lane == 0) {
             st.aff_x = before.x - (float)x0 + (float)thw;
@@ -224,9 +224,9 @@ __global__ __launch_bounds__(64) void affine_kernel(AffineArgs a)
             }
             float gxx = 0.f, gxy = 0.f, gyy = 0.f, ex = 0.f, ey = 0.f;
             for_samples([&](float fi, float fj, float ti, float tgx, float tgy) {
-                const float d = ti - bilinear_at(a.i2, nc, x2 + fi, y2 + fj);
-                const float g1 = tgx + bilinear_at<KLT_GRAD_STRIDE>(a.gx2, nc, x2 + fi, y2 + fj);
-                const float g2 = tgy + bilinear_at<KLT_GRAD_STRIDE>(a.gy2, nc, x2 + fi, y2 + fj);
+                const float d = ti - bilinear_at<KLT_PIX_STRIDE>(a.i2, nc, x2 + fi, y2 + fj);
+                const float g1 = tgx + bilinear_at<KLT_PIX_STRIDE>(a.gx2, nc, x2 + fi, y2 + fj);
+                const float g2 = tgy + bilinear_at<KLT_PIX_STRIDE>(a.gy2, nc, x2 + fi, y2 + fj);
                 gxx = gxx + g1 * g1; gxy = gxy + g1 * g2; gyy = gyy + g2 * g2;
                 ex = ex + d * g1; ey = ey + d * g2;
             });
@@ -252,9 +252,9 @@ __global__ __launch_bounds__(64) void affine_kernel(AffineArgs a)
             const int nn = MODE == 1 ? 4 : 6;
             for_samples([&](float x, float y, float ti, float, float) {
                 const float mi = Axx * x + Axy * y, mj = Ayx * x + Ayy * y;
-                const float d = ti - bilinear_at(a.i2, nc, x2 + mi, y2 + mj);
-                const float g1 = bilinear_at<KLT_GRAD_STRIDE>(a.gx2, nc, x2 + mi, y2 + mj);
-                const float g2 = bilinear_at<KLT_GRAD_STRIDE>(a.gy2, nc, x2 + mi, y2 + mj);
+                const float d = ti - bilinear_at<KLT_PIX_STRIDE>(a.i2, nc, x2 + mi, y2 + mj);
+                const float g1 = bilinear_at<KLT_PIX_STRIDE>(a.gx2, nc, x2 + mi, y2 + mj);
+                const float g2 = bilinear_at<KLT_PIX_STRIDE>(a.gy2, nc, x2 + mi, y2 + mj);
                 if (MODE == 1) {
                     const float u = x * g1 + y * g2, v = x * g2 - y * g1;
                     e[0] = e[0] + (d * g1 * x + d * g2 * y); e[1] = e[1] + (d * g2 * x - d * g1 * y);
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(64) void affine_kernel(AffineArgs a)
         float s = 0.f;
         for_samples([&](float x, float y, float ti, float, float) {
             const float mi = MODE ? Axx * x + Axy * y : x, mj = MODE ? Ayx * x + Ayy * y : y;
-            s = s + fabsf(ti - bilinear_at(a.i2, nc, x2 + mi, y2 + mj));
+            s = s + fabsf(ti - bilinear_at<KLT_PIX_STRIDE>(a.i2, nc, x2 + mi, y2 + mj));
         });
         s = wave_sum(s);
         if (s / (float)n > a.max_residue) status = KLT_LARGE_RESIDUE;

@@ -27,29 +27,29 @@ int klt_scan_good_features_f32(klt_ctx *c, const float *gradx, const float *grad
     const size_t N = (size_t)ncols * nrows;
     long long npow2 = 2048;
     while (npow2 < ncand) npow2 <<= 1;
-    // gradx / grady interleaved, as the table kernels read a slot's planes
-    std::vector<float> inter(2 * N);
-    for (size_t i = 0; i < N; i++) { inter[2 * i] = gradx[i]; inter[2 * i + 1] = grady[i]; }
-    float *d = nullptr;                         // [2N] gradients | [3N] tables | [ncand] eigenvalues
+    // pixel records (image unused, gradx, grady), as the table kernels read a slot's levels
+    std::vector<float> inter(KLT_PIX_STRIDE * N, 0.f);
+    for (size_t i = 0; i < N; i++) { inter[3 * i + 1] = gradx[i]; inter[3 * i + 2] = grady[i]; }
+    float *d = nullptr;                         // [3N] records | [3N] tables | [ncand] eigenvalues
     unsigned long long *keys = nullptr;
-    DEVALLOC(c, d, (5 * N + (size_t)ncand) * sizeof(float));
+    DEVALLOC(c, d, (6 * N + (size_t)ncand) * sizeof(float));
     if (int rc_keys = dev_alloc(c, (void **)&keys, (size_t)npow2 * sizeof(unsigned long long), "candidate keys")) { hipFree(d); return rc_keys; }
     hipError_t e = hipSuccess;
     int rc = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(d, inter.data(), 2 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, inter.data(), 3 * N * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         c->work = c->stream;
-        rc = enqueue_sat(c, c->stream, d, d + 1, d + 2 * N, ncols, nrows);
+        rc = enqueue_sat(c, c->stream, d + 1, d + 2, d + 3 * N, ncols, nrows);
     }
     if (e == hipSuccess && rc == 0) {
         SelectArgs sa;
         std::memset(&sa, 0, sizeof(sa));
-        sa.sat = d + 2 * N; sa.valmap = d + 5 * N; sa.keys = keys;
+        sa.sat = d + 3 * N; sa.valmap = d + 6 * N; sa.keys = keys;
         sa.min_eig = 1.0;
         sa.ncols = ncols; sa.nrows = nrows; sa.bx = borderx; sa.by = bordery; sa.step = step; sa.nx = nx; sa.ny = ny;
         sa.hw = window_hw; sa.hh = window_hh; sa.npow2 = (int)npow2;
         launch_eigen(c->stream, sa);
-        e = hipMemcpyAsync(val, d + 5 * N, (size_t)ncand * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(val, d + 6 * N, (size_t)ncand * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     hipFree(d);

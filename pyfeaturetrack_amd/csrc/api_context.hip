@@ -103,6 +103,15 @@ int ensure_h1(klt_ctx *c, size_t floats)
     return 0;
 }
 
+int ensure_cimg(klt_ctx *c, size_t floats)
+{
+    if (floats <= c->cimg_cap && c->cimg) return 0;
+    if (c->cimg) { if (int rc = sync_all(c)) return rc; hipFree(c->cimg); c->cimg = nullptr; c->cimg_cap = 0; }
+    DEVALLOC(c, c->cimg, floats * sizeof(float));
+    c->cimg_cap = floats;
+    return 0;
+}
+
 int get_slot(klt_ctx *c, int slot, Slot **out, bool create)
 {
     if (slot < 0 || slot > 65535) return fail(c, KLT_ERR_ARG, "slot index out of range");
@@ -291,8 +300,8 @@ void klt_destroy(klt_ctx *c)
     for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); }
     for (FeatBuf &b : c->fbs)
         if (!b.view) hipFree(b.d);
-    hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1);
-    hipFree(c->sel_img); hipFree(c->sel_gx); hipFree(c->sat); hipFree(c->valmap);      // (sel_gy points into sel_gx's allocation)
+    hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg);
+    hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap);
     for (auto &e : c->pre) hipFree(e.keys);
     hipFree(c->sat_pre);
     hipFree(c->keys); hipFree(c->seedmap); hipFree(c->grid); hipFree(c->nms_slots); for (auto &bt : c->batch_tables) hipFree(bt.dev); for (auto &bo : c->batch_orders) hipFree(bo.order); hipFree(c->shared_order.order); hipFree(c->keys2); hipFree(c->topk_hist); hipFree(c->fl_snapshot); hipFree(c->mis_st); hipFree(c->mis_list); hipFree(c->mis_cnt); hipFree(c->score_override); hipFree(c->mis_tile_keys);

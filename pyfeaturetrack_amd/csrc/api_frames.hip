@@ -31,7 +31,7 @@ int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int p
     if (!c || !px) return fail(c, KLT_ERR_ARG, "null argument");
     if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols)
         return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^28 pixels or more: a plane must stay below 2 GB)");
+    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s;
     if (int rc = get_slot(c, slot, &s, true)) return rc;
@@ -63,7 +63,7 @@ int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int p
 int layout_pyramid(klt_ctx *c, Slot *s)
 {
     const int L = c->p.nPyramidLevels, ss = c->p.subsampling;
-    // [image planes of all levels][interleaved gradient planes of all levels]; every level starts on a 16-byte boundary
+    // one plane of pixel records (image, gradx, grady: KLT_PIX_STRIDE floats) per level; every level starts on a 16-byte boundary
     auto padded = [](int nc_, int nr_) { return ((size_t)nc_ * nr_ + 3) & ~(size_t)3; };
     size_t total = 0;
     int nc = s->nc, nr = s->nr;
@@ -85,9 +85,9 @@ int layout_pyramid(klt_ctx *c, Slot *s)
     for (int l = 0; l < L; l++) {
         s->lv[l].nc = nc;
         s->lv[l].nr = nr;
-        s->lv[l].img = s->planes + off;
-        s->lv[l].gx = s->planes + total + KLT_GRAD_STRIDE * off;      // gradx and grady of a pixel side by side (klt_internal.h)
-        s->lv[l].gy = s->lv[l].gx + 1;
+        s->lv[l].img = s->planes + KLT_PIX_STRIDE * off;           // the three values of a pixel side by side (klt_internal.h)
+        s->lv[l].gx = s->lv[l].img + 1;
+        s->lv[l].gy = s->lv[l].img + 2;
         off += padded(nc, nr);
         nc /= ss;
         nr /= ss;
@@ -114,8 +114,9 @@ int enqueue_smooth_raw(klt_ctx *c, Slot *s, float *dst)
     return 0;
 }
 
-// KLTComputeGradients, convolve.py:226-248: gx = (deriv horizontally, gauss vertically), gy = (gauss, deriv)
-int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *gx, float *gy)
+// KLTComputeGradients, convolve.py:226-248: gx = (deriv horizontally, gauss vertically), gy = (gauss, deriv); the compact image `img`
+// and its gradients into the pixel records `rec`
+int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *rec)
 {
     const double N = (double)nc * nr;
     {
@@ -124,7 +125,8 @@ int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *gx, f
     }
     {
         TimerScope t(c, F_GRAD_V, N * 16);
-        launch_vconv(c->work, c->tmpA, c->tmpB, nc, nr, gx, gy, nr, 1, 0, c->gauss[2], &c->deriv[2], KLT_GRAD_STRIDE);   // a level's interleaved planes
+        launch_vconv(c->work, c->tmpA, c->tmpB, nc, nr, rec + 1, rec + 2, nr, 1, 0, c->gauss[2], &c->deriv[2], KLT_PIX_STRIDE);
+        launch_put_strided(c->work, img, rec, (size_t)nc * nr, KLT_PIX_STRIDE);
     }
     return 0;
 }
@@ -145,28 +147,31 @@ bool merged_grad_ok(const klt_ctx *c)
 bool fused_grad_ok(const klt_ctx *c) { return c->use_fused && smooth_grad_lds_bytes(-1, grad_radius(c)) <= kMaxLds; }
 bool fused_reduce_ok(const klt_ctx *c) { return c->use_fused && pyr_reduce_lds_bytes(c->p.subsampling, c->gauss[1].n) <= kMaxLds; }
 
-// 2 when every entry's grady plane starts one element behind its gradx plane (the interleaved planes of slots and of the selection), else 1
-static int grad_stride_of(float *const *gx, float *const *gy, int batch)
-{
-    for (int b = 0; b < batch; b++)
-        if (gy[b] != gx[b] + 1) return 1;
-    return KLT_GRAD_STRIDE;
-}
-
-// smooth(raw frame) + gradients for up to KLT_MAX_BATCH same-sized frames in one launch
-// *fused_h1 (optional, in/out): in = the caller wants the horizontal pass of the first reduction fused into this launch; out =
-// whether it was (then c->h1 holds one H1 plane of nr x (nc / ss) floats per frame)
-int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *img,
-                              float *const *gx, float *const *gy, int nc, int nr, bool *fused_h1 /* = nullptr */)
+// Would a level-0 launch of `batch` frames that wants the first reduction's horizontal pass get it (enqueue_fused_smooth_grad)?
+static bool l0_hred(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
 {
     SmoothGradArgs a;
     std::memset(&a, 0, sizeof(a));
-    for (int b = 0; b < batch; b++) { a.raw[b] = raw[b]; a.img[b] = img[b]; a.gx[b] = gx[b]; a.gy[b] = gy[b]; }
-    a.gstride = grad_stride_of(gx, gy, batch);
+    a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
+    a.ncols = nc; a.nrows = nr;
+    return c->fuse_hreduce && smooth_grad_hred_ok(a, batch, raw_kind == 1 ? 0 : 1, c->gauss[1], c->p.subsampling);
+}
+
+// smooth(raw frame) + gradients for up to KLT_MAX_BATCH same-sized frames in one launch: pixel records `rec`, and (cimg, optional,
+// not with the fused reduction) the smoothed image as compact planes as well
+// *fused_h1 (optional, in/out): in = the caller wants the horizontal pass of the first reduction fused into this launch; out =
+// whether it was (then c->h1 holds one H1 plane of nr x (nc / ss) floats per frame)
+int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
+                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */)
+{
+    SmoothGradArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (int b = 0; b < batch; b++) { a.raw[b] = raw[b]; a.rec[b] = rec[b]; a.cimg[b] = cimg ? cimg[b] : nullptr; }
     a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
     a.ncols = nc; a.nrows = nr; a.R = grad_radius(c);
     const int kind = raw_kind == 1 ? 0 : 1;
-    bool hred = fused_h1 && *fused_h1 && c->fuse_hreduce && smooth_grad_hred_ok(a, batch, kind, c->gauss[1], c->p.subsampling);
+    bool hred = fused_h1 && *fused_h1 && l0_hred(c, batch, raw_kind, nc, nr);
+    if (hred && cimg) return fail(c, KLT_ERR_STATE, "level-0 launch: a compact image copy with the fused reduction");
     if (hred) {
         const size_t plane = (size_t)nr * (nc / c->p.subsampling);
         if (int rc = ensure_h1(c, plane * batch)) return rc;
@@ -185,14 +190,12 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     return 0;
 }
 
-// gradients of up to KLT_MAX_BATCH same-sized f32 images in one launch
-int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *gx, float *const *gy, int nc, int nr,
-                       bool u8_input /* = false */)
+// gradients of up to KLT_MAX_BATCH same-sized compact f32 images in one launch, into pixel records (the image copied through)
+int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input /* = false */)
 {
     SmoothGradArgs a;
     std::memset(&a, 0, sizeof(a));
-    for (int b = 0; b < batch; b++) { a.raw[b] = img[b]; a.gx[b] = gx[b]; a.gy[b] = gy[b]; }
-    a.gstride = grad_stride_of(gx, gy, batch);
+    for (int b = 0; b < batch; b++) { a.raw[b] = img[b]; a.rec[b] = rec[b]; }
     a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
     a.ncols = nc; a.nrows = nr; a.R = grad_radius(c);
     TimerScope t(c, F_GRAD, (double)nc * nr * batch * 12);
@@ -270,22 +273,38 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         Slot *s0 = g[0];
         const void *raw[KLT_MAX_BATCH];
         const float *src[KLT_MAX_BATCH];
-        float *img[KLT_MAX_BATCH], *gx[KLT_MAX_BATCH], *gy[KLT_MAX_BATCH];
+        float *rec[KLT_MAX_BATCH], *cim[KLT_MAX_BATCH];
         if (int rc = ensure_tmp(c, (size_t)s0->nc * s0->nr)) return rc;
 
+        // level 1 comes from the H1 planes written by the level-0 kernel, or from a compact copy of level 0
+        const bool fused0 = fused_smooth_ok(c);
+        const bool h1_want = fused0 && s0->nlev > 1 && fused_reduce_ok(c) && l0_hred(c, B, s0->raw_kind, s0->nc, s0->nr);
+        // The reductions read and write compact image planes, and the gradient launches of levels >= 1 read them: scratch for the levels
+        // of every frame of the group (level 0 only where something reads it), 16-byte aligned
+        size_t coff[KLT_MAX_LEVELS], cper = 0;
+        for (int l = 0; l < s0->nlev; l++) {
+            coff[l] = cper;
+            if (l > 0 || (!h1_want && (!fused0 || s0->nlev > 1))) cper += ((size_t)s0->lv[l].nc * s0->lv[l].nr + 3) & ~(size_t)3;
+        }
+        if (cper) { if (int rc = ensure_cimg(c, cper * B)) return rc; }
+        auto cimg_of = [&](int l, int b) { return c->cimg + cper * b + coff[l]; };
+
         // level 0: smoothed frame (trackFeatures.py:165-166) and its gradients (:171-172)
-        bool h1_fused = false;              // level 1 comes from the H1 planes written by the level-0 kernel
-        if (fused_smooth_ok(c)) {
+        bool h1_fused = false;
+        if (fused0) {
             for (int b = 0; b < B; b++) {
                 raw[b] = g[b]->raw_kind == 1 ? (const void *)raw8(g[b]) : (const void *)rawf(g[b]);
-                img[b] = g[b]->lv[0].img; gx[b] = g[b]->lv[0].gx; gy[b] = g[b]->lv[0].gy;
+                rec[b] = g[b]->lv[0].img;
+                cim[b] = cimg_of(0, b);
             }
-            h1_fused = s0->nlev > 1 && fused_reduce_ok(c);
-            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, img, gx, gy, s0->nc, s0->nr, &h1_fused)) return rc;
+            h1_fused = h1_want;
+            const bool copy0 = !h1_want && s0->nlev > 1;
+            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 ? cim : nullptr, s0->nc, s0->nr, &h1_fused)) return rc;
+            if (h1_fused != h1_want) return fail(c, KLT_ERR_STATE, "level-0 launch: fused reduction not as planned");
         } else {
             for (int b = 0; b < B; b++) {
-                enqueue_smooth_raw(c, g[b], g[b]->lv[0].img);
-                enqueue_gradients(c, g[b]->lv[0].img, g[b]->nc, g[b]->nr, g[b]->lv[0].gx, g[b]->lv[0].gy);
+                enqueue_smooth_raw(c, g[b], cimg_of(0, b));
+                enqueue_gradients(c, cimg_of(0, b), g[b]->nc, g[b]->nr, g[b]->lv[0].img);
             }
         }
         // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
@@ -296,7 +315,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
             if (fused_reduce_ok(c)) {
                 PyrReduceArgs a;
                 std::memset(&a, 0, sizeof(a));
-                for (int b = 0; b < B; b++) { a.src[b] = g[b]->lv[l - 1].img; a.dst[b] = g[b]->lv[l].img; }
+                for (int b = 0; b < B; b++) { a.src[b] = cimg_of(l - 1, b); a.dst[b] = cimg_of(l, b); }
                 a.taps = c->gauss[1];
                 a.src_nc = ls.nc; a.src_nr = ls.nr; a.dst_nc = ld.nc; a.dst_nr = ld.nr; a.ss = ss;
                 a.log2ss = 0;
@@ -317,36 +336,36 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
                 for (int b = 0; b < B; b++) {
                     {
                         TimerScope t(c, F_PYR_H, 4.0 * ((double)ls.nc * ls.nr + (double)ld.nc * ls.nr));
-                        launch_hconv_f32(c->work, g[b]->lv[l - 1].img, ls.nc, ls.nr, c->tmpA, nullptr, ld.nc, ss, ss / 2, c->gauss[1], nullptr);
+                        launch_hconv_f32(c->work, cimg_of(l - 1, b), ls.nc, ls.nr, c->tmpA, nullptr, ld.nc, ss, ss / 2, c->gauss[1], nullptr);
                     }
                     {
                         TimerScope t(c, F_PYR_V, 4.0 * ((double)ld.nc * ls.nr + (double)ld.nc * ld.nr));
-                        launch_vconv(c->work, c->tmpA, nullptr, ld.nc, ls.nr, g[b]->lv[l].img, nullptr, ld.nr, ss, ss / 2, c->gauss[1], nullptr);
+                        launch_vconv(c->work, c->tmpA, nullptr, ld.nc, ls.nr, cimg_of(l, b), nullptr, ld.nr, ss, ss / 2, c->gauss[1], nullptr);
                     }
                 }
             }
             const bool merged = fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767;
             if (merged) continue;          // gradients of all levels >= 1 go out in one launch below
             if (fused_grad_ok(c)) {
-                for (int b = 0; b < B; b++) { src[b] = g[b]->lv[l].img; gx[b] = g[b]->lv[l].gx; gy[b] = g[b]->lv[l].gy; }
-                if (int rc = enqueue_fused_grad(c, B, src, gx, gy, ld.nc, ld.nr)) return rc;
+                for (int b = 0; b < B; b++) { src[b] = cimg_of(l, b); rec[b] = g[b]->lv[l].img; }
+                if (int rc = enqueue_fused_grad(c, B, src, rec, ld.nc, ld.nr)) return rc;
             } else {
-                for (int b = 0; b < B; b++) enqueue_gradients(c, g[b]->lv[l].img, ld.nc, ld.nr, g[b]->lv[l].gx, g[b]->lv[l].gy);
+                for (int b = 0; b < B; b++) enqueue_gradients(c, cimg_of(l, b), ld.nc, ld.nr, g[b]->lv[l].img);
             }
         }
         if (s0->nlev > 1 && fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767) {
-            // one launch for the gradients of every level >= 1 of every frame: entry = (frame, level), per-entry geometry
+            // one launch for the gradients of every level >= 1 of every frame: entry = (frame, level), per-entry geometry; each reads its
+            // compact level image and writes the level's records
             SmoothGradArgs a;
             std::memset(&a, 0, sizeof(a));
             int e = 0;
             double bytes = 0;
             for (int l = 1; l < s0->nlev; l++)
                 for (int b = 0; b < B; b++, e++) {
-                    a.raw[e] = g[b]->lv[l].img; a.gx[e] = g[b]->lv[l].gx; a.gy[e] = g[b]->lv[l].gy;
+                    a.raw[e] = cimg_of(l, b); a.rec[e] = g[b]->lv[l].img;
                     a.dim_c[e] = (short)g[b]->lv[l].nc; a.dim_r[e] = (short)g[b]->lv[l].nr;
                     bytes += 12.0 * g[b]->lv[l].nc * g[b]->lv[l].nr;
                 }
-            a.gstride = KLT_GRAD_STRIDE;                              // slot planes: gradx / grady interleaved
             a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
             a.ncols = s0->lv[1].nc; a.nrows = s0->lv[1].nr; a.R = grad_radius(c);
             TimerScope t(c, F_GRAD, bytes);
@@ -452,7 +471,7 @@ static int upload_async(klt_ctx *c, int slot, const void *px, int ncols, int nro
 {
     if (!c || !px) return fail(c, KLT_ERR_ARG, "null argument");
     if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols) return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^28 pixels or more: a plane must stay below 2 GB)");
+    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t attr;                           // the source must be pinned: a pageable copy would be staged synchronously
     if (hipPointerGetAttributes(&attr, px) != hipSuccess || attr.type != hipMemoryTypeHost) {
@@ -582,7 +601,7 @@ int klt_slot_adopt_u8(klt_ctx *c, int slot, const uint8_t *dev_px, int ncols, in
     if (!c || !dev_px) return fail(c, KLT_ERR_ARG, "null argument");
     if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535) return fail(c, KLT_ERR_ARG, "bad image geometry");
     if (pitch != ncols) return fail(c, KLT_ERR_ARG, "an adopted frame must have contiguous rows (pitch == ncols): it is read in place");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^28 pixels or more: a plane must stay below 2 GB)");
+    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, dev_px) != hipSuccess || attr.type != hipMemoryTypeDevice) {
@@ -639,7 +658,7 @@ int klt_download_f32(klt_ctx *c, int slot, int pyramid, int level, float *dst)
     const float *src = pyramid == 0 ? l.img : (pyramid == 1 ? l.gx : l.gy);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = wait_built(c, s)) return rc;
-    return download_plane(c, src, pyramid == 0 ? 1 : KLT_GRAD_STRIDE, (size_t)l.nc * l.nr, dst);
+    return download_plane(c, src, KLT_PIX_STRIDE, (size_t)l.nc * l.nr, dst);
 }
 
 

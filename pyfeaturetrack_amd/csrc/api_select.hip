@@ -276,19 +276,18 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
 
     // scratch
     if (N > c->sel_cap) {
-        if (c->sel_img) { if (int rc = sync_all(c)) return rc; hipFree(c->sel_img); hipFree(c->sel_gx); hipFree(c->sat); hipFree(c->valmap); }
-        c->sel_img = c->sel_gx = c->sel_gy = c->sat = c->valmap = nullptr;
+        if (c->sel_img) { if (int rc = sync_all(c)) return rc; hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap); }
+        c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
         c->sel_cap = 0;                                       // (nothing is held until all four planes are: a failure below frees what it got)
         int rc_alloc = dev_alloc(c, (void **)&c->sel_img, N * sizeof(float), "selection scratch: image");
-        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sel_gx, KLT_GRAD_STRIDE * N * sizeof(float), "selection scratch: gradients");      // gradx / grady interleaved, like a slot's planes
+        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sel_rec, KLT_PIX_STRIDE * N * sizeof(float), "selection scratch: pixel records");      // image, gradx, grady, like a slot's levels
         if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sat, 3 * N * sizeof(float), "selection scratch: summed-area tables");
         if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->valmap, N * sizeof(float), "selection scratch: eigenvalue map");
         if (rc_alloc) {
-            hipFree(c->sel_img); hipFree(c->sel_gx); hipFree(c->sat); hipFree(c->valmap);
-            c->sel_img = c->sel_gx = c->sel_gy = c->sat = c->valmap = nullptr;
+            hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap);
+            c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
             return rc_alloc;
         }
-        c->sel_gy = c->sel_gx + 1;
         c->sel_cap = N;
     }
     if (int rc = ensure(c, c->keys, c->keys_cap, (size_t)npow2)) return rc;
@@ -307,8 +306,7 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
         bool grads_done = false;
         if (p.smoothBeforeSelecting && fused_smooth_ok(c)) {
             const void *raw = s->raw_kind == 1 ? (const void *)raw8(s) : (const void *)rawf(s);
-            if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_img, &c->sel_gx, &c->sel_gy, nc, nr)) return rc;
-            img = c->sel_img;
+            if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr)) return rc;
             grads_done = true;
         } else if (p.smoothBeforeSelecting) {
             enqueue_smooth_raw(c, s, c->sel_img);
@@ -324,10 +322,11 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
             img = c->sel_img;
         }
         if (!grads_done) {
-            if (fused_grad_ok(c)) { if (int rc = enqueue_fused_grad(c, 1, &img, &c->sel_gx, &c->sel_gy, nc, nr)) return rc; }
-            else enqueue_gradients(c, img, nc, nr, c->sel_gx, c->sel_gy);
+            // the compact image (a raw f32 frame or sel_img) -> the records, image copied through
+            if (fused_grad_ok(c)) { if (int rc = enqueue_fused_grad(c, 1, &img, &c->sel_rec, nc, nr)) return rc; }
+            else enqueue_gradients(c, img, nc, nr, c->sel_rec);
         }
-        gx = c->sel_gx; gy = c->sel_gy;
+        img = c->sel_rec; gx = c->sel_rec + 1; gy = c->sel_rec + 2;
         // the kernels above read the raw frame: the second-next asynchronous copy into this slot (its raw buffers alternate) waits
         if (int rc = mark_consumed(c, &s, 1, c->stream)) return rc;
     }
@@ -619,7 +618,7 @@ int klt_download_select_f32(klt_ctx *c, int what, float *dst)
     const float *src = what == 3 ? c->valmap : c->last_sel[what];
     const size_t cnt = what == 3 ? (size_t)c->sel_nx * c->sel_ny : (size_t)c->sel_nc * c->sel_nr;
     HIPCHK(c, hipSetDevice(c->device));
-    return download_plane(c, src, (what == 1 || what == 2) ? KLT_GRAD_STRIDE : 1, cnt, dst);
+    return download_plane(c, src, what == 3 ? 1 : KLT_PIX_STRIDE, cnt, dst);     // image, gradx, grady: planes of pixel records
 }
 
 int klt_set_score_override(klt_ctx *c, const float *val, int count)

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void vconv_kernel(const float *__restrict__ in
     const int ys = blockIdx.y * 4 + threadIdx.y;
     if (x >= ncols || ys >= out_rows) return;
     const int y = ys * ystride + yoff;
-    const size_t o = ((size_t)ys * ncols + x) * ostride;          // ostride 2: outB == outA + 1, interleaved gradient planes
+    const size_t o = ((size_t)ys * ncols + x) * ostride;          // ostride 3: outA, outB = gradx, grady planes of pixel records
     outA[o] = correlate_at(inA + x, (size_t)ncols, y, nrows, ta);
     if (NOUT == 2) outB[o] = correlate_at(inB + x, (size_t)ncols, y, nrows, tb);
 }
@@ -138,7 +138,7 @@ void launch_hconv_f32(hipStream_t s, const float *in, int ncols, int nrows, floa
     launch_hconv_t<float>(s, in, ncols, nrows, outA, outB, out_cols, xstride, xoff, ta, tb);
 }
 
-// dst[i] = src[i * stride]: one of the two interleaved gradient planes as a plane of its own (the ABI's plane downloads)
+// dst[i] = src[i * stride]: one of the three planes of a level's pixel records as a plane of its own (the ABI's plane downloads)
 __global__ __launch_bounds__(256) void take_strided_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t n, int stride)
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src[i * stride];
@@ -148,6 +148,18 @@ void launch_take_strided(hipStream_t s, const float *src, float *dst, size_t n, 
 {
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(take_strided_kernel, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, s, src, dst, n, stride);
+}
+
+// dst[i * stride] = src[i]: a compact image into the image plane of pixel records (the generic gradient path)
+__global__ __launch_bounds__(256) void put_strided_kernel(const float *__restrict__ src, float *__restrict__ dst, size_t n, int stride)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i * stride] = src[i];
+}
+
+void launch_put_strided(hipStream_t s, const float *src, float *dst, size_t n, int stride)
+{
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(put_strided_kernel, dim3((unsigned)(blocks < 4096 ? (blocks ? blocks : 1) : 4096)), dim3(256), 0, s, src, dst, n, stride);
 }
 
 void launch_vconv(hipStream_t s, const float *inA, const float *inB, int ncols, int nrows, float *outA, float *outB,

@@ -155,12 +155,14 @@ struct klt_ctx {
     size_t tmp_cap = 0;
     float *h1 = nullptr;                      // H1 planes of the fused first reduction (one per frame of a batch)
     size_t h1_cap = 0;
+    float *cimg = nullptr;                    // compact image planes of a pyramid build's levels (what the reductions read and write)
+    size_t cimg_cap = 0;
     bool fuse_hreduce = true;                 // KLT_OPT_FUSED_HREDUCE
     bool l0_stream = true;                    // KLT_OPT_L0_STREAM
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
     // selection scratch
-    float *sel_img = nullptr, *sel_gx = nullptr, *sel_gy = nullptr, *sat = nullptr, *valmap = nullptr;
+    float *sel_img = nullptr, *sel_rec = nullptr, *sat = nullptr, *valmap = nullptr;   // compact image, pixel records (KLT_PIX_STRIDE)
     size_t sel_cap = 0;               // pixels
     unsigned long long *keys = nullptr;
     size_t keys_cap = 0;
@@ -320,6 +322,7 @@ int drain_timers(klt_ctx *c);
 int sync_all(klt_ctx *c);
 int ensure_tmp(klt_ctx *c, size_t pixels);
 int ensure_h1(klt_ctx *c, size_t floats);
+int ensure_cimg(klt_ctx *c, size_t floats);
 int get_slot(klt_ctx *c, int slot, Slot **out, bool create);
 int get_fb(klt_ctx *c, int fb, int n, FeatBuf **out);
 int fresh_event(klt_ctx *c, hipEvent_t *out, uint64_t *serial = nullptr);
@@ -343,20 +346,19 @@ int ensure(klt_ctx *c, T *&ptr, size_t &cap, size_t want)
 
 // ---- api_frames.hip
 // The kernels address a plane with 32-bit BYTE offsets into a buffer descriptor of 2 GB (raw buffer operations, klt_internal.h), and the
-// largest plane is the interleaved gradient plane of level 0 with 8 bytes per pixel: a frame must stay below 2^28 pixels.
-// 2^28 - 1 pixels is a 16 384 x 16 383 frame; the largest frame of the test suite is 7680 x 4320.
-constexpr long long kMaxFramePixels = (1LL << 28) - 1;
+// largest plane is the record plane of level 0 with 12 bytes per pixel: a frame must stay below 2^27 pixels (1.5 GB of records).
+// 2^27 - 1 pixels is a 16 384 x 8 191 frame; the largest frame of the test suite is 7680 x 4320.
+constexpr long long kMaxFramePixels = (1LL << 27) - 1;
 void make_taps(const double *k, int n, Taps &t);
 int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int pitch, int kind);
 int layout_pyramid(klt_ctx *c, Slot *s);
 int enqueue_smooth_raw(klt_ctx *c, Slot *s, float *dst);
-int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *gx, float *gy);
+int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *rec);      // compact image -> pixel records
 bool fused_smooth_ok(const klt_ctx *c);
 bool fused_grad_ok(const klt_ctx *c);
-int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *img,
-                              float *const *gx, float *const *gy, int nc, int nr, bool *fused_h1 = nullptr);
-int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *gx, float *const *gy, int nc, int nr,
-                       bool u8_input = false);
+int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
+                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr);
+int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
 int download_plane(klt_ctx *c, const float *src, int stride, size_t cnt, float *dst);      // every stride-th float of a device plane to the host
 

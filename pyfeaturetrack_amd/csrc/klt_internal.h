@@ -18,10 +18,9 @@ struct Taps {
 constexpr int KLT_MAX_BATCH = 32;   // frames per fused pyramid launch (pointer tables travel in the kernarg segment)
 
 struct SmoothGradArgs {
-    const void *raw[KLT_MAX_BATCH];   // u8 or f32 frame (or, for gradients only, the level image)
-    float *img[KLT_MAX_BATCH];        // smoothed image out (unused for gradients only)
-    float *gx[KLT_MAX_BATCH], *gy[KLT_MAX_BATCH];   // gradient planes; gstride == 2: ONE interleaved plane per entry, gy[b] == gx[b] + 1
-    int gstride;                      // element stride of a gradient plane: 2 for the planes of slots / the selection (KLT_GRAD_STRIDE), 1 for separate planes
+    const void *raw[KLT_MAX_BATCH];   // u8 or f32 frame (or, for gradients only, the compact level image)
+    float *rec[KLT_MAX_BATCH];        // pixel records out (KLT_PIX_STRIDE): image, gradx, grady; gradients only: the image is copied through
+    float *cimg[KLT_MAX_BATCH];       // optional (smoothing kinds, not with HRED): the smoothed image as a compact plane as well
     Taps smooth, ggauss, gderiv;
     int ncols, nrows, R;              // R = max gradient tap radius; ncols/nrows = largest entry (grid extent)
     short dim_c[KLT_MAX_BATCH], dim_r[KLT_MAX_BATCH];   // per-entry geometry when entries differ (0 = use ncols/nrows)
@@ -38,15 +37,17 @@ struct PyrReduceArgs {
     int src_nc, src_nr, dst_nc, dst_nr, ss, log2ss;
 };
 
-// The two gradient planes of a pyramid level are stored INTERLEAVED: pixel (y, x) holds gradx at element 2 (y nc + x) and grady right
-// behind it, so gy == gx + 1 and a row of a tracking window's footprint is one contiguous piece (64 bytes for an 8-pixel row) instead of
-// two 32-byte pieces in two planes -- the tracker is bound by the cache lines its footprints touch.  Producers
-// (level-0 kernel, gradient kernels) write both values of a pixel together, consumers (tracker, affine check, summed-area row pass)
-// read them together; only the plane download of the ABI separates them again.
-constexpr int KLT_GRAD_STRIDE = 2;
+// A pyramid level is ONE plane of 12-byte pixel records: pixel (y, x) holds the image at element 3 (y nc + x), gradx right behind it
+// and grady behind that, so img, gx = img + 1 and gy = img + 2 are three planes of element stride KLT_PIX_STRIDE.  A row of a tracking
+// window's footprint is then one contiguous piece (96 bytes for an 8-pixel row) instead of a 32-byte piece of an image plane and a
+// 64-byte piece of a gradient plane -- the tracker is bound by the cache lines its footprints touch.  Producers
+// (level-0 kernels, gradient kernels) write the records, consumers (tracker, affine check, summed-area row pass) read them; only the
+// plane download of the ABI separates the three planes again.  The pyramid reductions work on compact image planes in scratch
+// (api_frames.hip).  The selection's own scratch uses the same records.
+constexpr int KLT_PIX_STRIDE = 3;
 
 struct TrackLevel {
-    const float *i1, *gx1, *gy1, *i2, *gx2, *gy2;   // gy == gx + 1 (interleaved gradient planes)
+    const float *i1, *gx1, *gy1, *i2, *gx2, *gy2;   // records: gx == i + 1, gy == i + 2 (KLT_PIX_STRIDE)
     int nc, nr;
 };
 
@@ -155,8 +156,9 @@ void launch_hconv_u8(hipStream_t s, const uint8_t *in, int ncols, int nrows, flo
 void launch_hconv_f32(hipStream_t s, const float *in, int ncols, int nrows, float *outA, float *outB,
                       int out_cols, int xstride, int xoff, const Taps &ta, const Taps *tb);
 void launch_take_strided(hipStream_t s, const float *src, float *dst, size_t n, int stride);
-// ostride: element stride of the output plane(s) -- KLT_GRAD_STRIDE when outA / outB are the two interleaved gradient planes of a
-// level (outB == outA + 1), 1 for separate planes (stated by the caller, never inferred from the pointers)
+void launch_put_strided(hipStream_t s, const float *src, float *dst, size_t n, int stride);     // dst[i * stride] = src[i]
+// ostride: element stride of the output plane(s) -- KLT_PIX_STRIDE when outA / outB are planes of a level's pixel records, 1 for
+// separate planes (stated by the caller, never inferred from the pointers)
 void launch_vconv(hipStream_t s, const float *inA, const float *inB, int ncols, int nrows, float *outA, float *outB,
                   int out_rows, int ystride, int yoff, const Taps &ta, const Taps *tb, int ostride = 1);
 

@@ -132,13 +132,13 @@ __global__ __launch_bounds__(256) void smooth_grad_kernel(SmoothGradArgs a)
             B[i] = correlate_lds(A + r * RW + c + rs, 1, a.smooth);
         }
         __syncthreads();
-        float *__restrict__ img = a.img[b];
+        float *__restrict__ img = a.cimg[b];             // the optional compact copy (the records get the image below)
         for (int i = tid; i < IH * IW; i += 256) {       // vertical smoothing -> image tile (+ store the interior)
             const int r = i / IW, c = i - r * IW;
             const float v = correlate_lds(B + (r + rs) * IW + c, IW, a.smooth);
             C[i] = v;
             const int y = ty0 - R + r, x = tx0 - R + c;
-            if (r >= R && r < R + TH && c >= R && c < R + TW && y < nr && x < nc) img[(size_t)y * nc + x] = v;
+            if (img && r >= R && r < R + TH && c >= R && c < R + TW && y < nr && x < nc) img[(size_t)y * nc + x] = v;
         }
     } else {
         for (int i = tid; i < IH * IW; i += 256) {
@@ -155,15 +155,15 @@ __global__ __launch_bounds__(256) void smooth_grad_kernel(SmoothGradArgs a)
         E[i] = correlate_lds(c, 1, a.ggauss);            // grady: Gaussian taps along x
     }
     __syncthreads();
-    float *__restrict__ gxo = a.gx[b];
-    float *__restrict__ gyo = a.gy[b];
-    for (int i = tid; i < TH * TW; i += 256) {           // vertical pass -> coalesced stores
+    float *__restrict__ rec = a.rec[b];
+    for (int i = tid; i < TH * TW; i += 256) {           // vertical pass -> the pixel records (image copied from the tile)
         const int r = i / TW, x = i - r * TW;
         const int y = ty0 + r, xx = tx0 + x;
         if (y < nr && xx < nc) {
-            const size_t o = ((size_t)y * nc + xx) * a.gstride;      // gstride 2: gyo == gxo + 1 (interleaved planes)
-            gxo[o] = correlate_lds(D + (r + R) * TW + x, TW, a.ggauss);
-            gyo[o] = correlate_lds(E + (r + R) * TW + x, TW, a.gderiv);
+            const size_t o = ((size_t)y * nc + xx) * KLT_PIX_STRIDE;
+            rec[o] = C[(r + R) * IW + x + R];
+            rec[o + 1] = correlate_lds(D + (r + R) * TW + x, TW, a.ggauss);
+            rec[o + 2] = correlate_lds(E + (r + R) * TW + x, TW, a.gderiv);
         }
     }
 }
@@ -286,6 +286,23 @@ __device__ __forceinline__ void widen12(const float *row, double *d)
     d[8] = (double)c.x; d[9] = (double)c.y; d[10] = (double)c.z; d[11] = (double)c.w;
 }
 
+// The pixel records of two horizontally adjacent pixels at byte offset `ob` (8-byte aligned): image, gradx, grady of the first, then
+// of the second (`second` = false: the first only)
+__device__ __forceinline__ void store_records(plane_rsrc r, unsigned ob, float2 im, float2 gx, float2 gy, bool second)
+{
+    float2 p;
+    p.x = im.x; p.y = gx.x;
+    plane_store2(r, ob, p);
+    if (second) {
+        p.x = gy.x; p.y = im.y;
+        plane_store2(r, ob + 8, p);
+        p.x = gx.y; p.y = gy.y;
+        plane_store2(r, ob + 16, p);
+    } else {
+        plane_store(r, ob + 8, gy.x);
+    }
+}
+
 #ifndef KLT_L0_WAVES
 #define KLT_L0_WAVES 4
 #endif
@@ -317,8 +334,8 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
     float *const A = lds, *const C = lds, *const B = lds + AC, *const D = lds + AC, *const E = lds + AC + IH * DW;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH_;
-    // two adjacent outputs go out as one 8-byte store where every row of the planes keeps them aligned (block-uniform)
-    const bool vec2_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.img[b]) & 7) == 0;
+    // two adjacent outputs of the compact image copy go out as one 8-byte store where every row keeps them aligned (block-uniform)
+    const bool vec2_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.cimg[b]) & 7) == 0;
     const TIn *__restrict__ raw = (const TIn *)a.raw[b];
     const unsigned row_bytes = 4u * (unsigned)nc;                // of the f32 planes
     const unsigned tile_b0 = (unsigned)ty0 * row_bytes + 4u * (unsigned)tx0;   // byte offset of the tile's first output in them
@@ -432,10 +449,12 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
         }
         __syncthreads();
         STAGE_MARK(2);
-        // ---- stage 2: vertical smoothing, B -> C (+ store the tile interior of the smoothed image).
+        // ---- stage 2: vertical smoothing, B -> C (+ store the tile interior of the compact image copy, if one is asked for; the
+        // records take the image from C in stage 4).
         // A thread produces two adjacent columns on FOUR consecutive rows: NS + 3 rows of two samples are read (ds_read_b64) and
         // widened for 8 outputs -- 2 widenings per output (a quad on two rows: 3).
-        const plane_rsrc img = plane_of(a.img[b]);
+        const bool cimg_out = a.cimg[b] != nullptr;
+        const plane_rsrc img = plane_of(a.cimg[b]);
         constexpr int BH = BW / 2, G2 = (IH + 3) / 4;           // half-quads per row, groups of four rows (the last one may be partial)
         for (int i = tid; i < G2 * BH; i += NTHR) {
             const int r = 4 * (i / BH), h = i % BH;
@@ -456,7 +475,7 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
                 o.x = corr_regs<NS, 1>(v[0] + rs + dr, ks); o.y = corr_regs<NS, 1>(v[1] + rs + dr, ks);
                 *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = o;
                 const int y = ty0 - R + rr, x = tx0 - HB + 2 * h;
-                if (rr >= R && rr < R + TH_ && h >= HB / 2 && h < HB / 2 + DW / 2 && (!EDGE || y < nr)) {
+                if (cimg_out && rr >= R && rr < R + TH_ && h >= HB / 2 && h < HB / 2 + DW / 2 && (!EDGE || y < nr)) {
                     const unsigned ob = img_b0 + (unsigned)dr * row_bytes;          // byte offset of (y, x)
                     if (!EDGE && vec2_ok) plane_store2(img, ob, o);                  // x is even
                     else if (!EDGE) { plane_store(img, ob, o.x); plane_store(img, ob + 4, o.y); }
@@ -527,8 +546,8 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
     // ---- stage 4: vertical pass, D -> gradx (Gaussian taps), E -> grady (derivative taps).  A thread makes two adjacent columns on
     // FOUR consecutive rows: NG + 3 rows of two samples are read (ds_read_b64) and widened once for 8 outputs per plane -- 2.5
     // widenings per output where a quad on two rows needs 4 (the widening is an FP64-rate instruction like the adds and multiplies).
-    const plane_rsrc gxy = plane_of(a.gx[b]);                    // the interleaved gradient plane: gradx, grady of a pixel side by side
-    const bool vec4_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.gx[b]) & 15) == 0;    // both pixels of a pair as one 16-byte store
+    // The two pixel records (image from C, gradx, grady) go out together: 24 contiguous bytes.
+    const plane_rsrc recp = plane_of(a.rec[b]);
     static_assert(TH_ % 4 == 0, "tile height must be a multiple of four");
     static_assert(NG == ND, "the vertical pass shares its row window between the two planes");
     constexpr int DH = DW / 2;                                   // half-quads per row
@@ -561,19 +580,14 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
                 oy[dr].x = corr_regs<ND, -1>(v[0] + ND / 2 + dr, kd); oy[dr].y = corr_regs<ND, -1>(v[1] + ND / 2 + dr, kd);
             }
         }
-        const unsigned g_b0 = 2u * (tile_b0 + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // byte offset of (ty0 + r, x) in the interleaved plane
+        const unsigned r_b0 = 3u * (tile_b0 + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // byte offset of (ty0 + r, x) in the records
 #pragma unroll
         for (int dr = 0; dr < 4; dr++) {
             const int y = ty0 + r + dr;
             if (EDGE && y >= nr) break;
-            const unsigned ob = g_b0 + (unsigned)dr * 2u * row_bytes;
-            float2 p0, p1;
-            p0.x = ox[dr].x; p0.y = oy[dr].x; p1.x = ox[dr].y; p1.y = oy[dr].y;
-            if (!EDGE && vec4_ok) plane_store4(gxy, ob, p0, p1);
-            else {
-                plane_store2(gxy, ob, p0);
-                if (!EDGE || x + 1 < nc) plane_store2(gxy, ob + 8, p1);
-            }
+            const unsigned ob = r_b0 + (unsigned)dr * 3u * row_bytes;
+            const float2 im = *reinterpret_cast<const float2 *>(C + (r + dr + R) * BW + HB + 2 * h);
+            store_records(recp, ob, im, ox[dr], oy[dr], !EDGE || x + 1 < nc);
         }
     }
     STAGE_MARK(5);
@@ -612,7 +626,9 @@ __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradA
 // A DE row holds the D row (derivative taps along x) in floats [0, 64) and the E row (Gaussian taps) in [64, 128).  B lives in the DE
 // rows past the carried six (dead once stage 2 has run; its last 2 rs rows are saved to Bc first).  The prologue band of a segment
 // (PRO) fills the carries: C rows [SB - 6, SB) = frame rows [s0 - 3, s0 + 3), no gradient output.
-// The image and the H1 plane are stored from the C rows of [s0, s0 + seg_h); the gradients of [y, y + SB) from each steady band.
+// The H1 plane is stored from the C rows of [s0, s0 + seg_h); the pixel records of [y, y + SB) from each steady band's stage 4, the image
+// taken from C -- its first three rows from Cc, the interior columns of the last three C rows of the band before (two slots, by band
+// parity: a band reads one and fills the other).
 constexpr int SB = 32;
 
 template <int NS>
@@ -622,7 +638,8 @@ struct StreamLds {
     static constexpr int R1 = SB * AW;                           // A, then C
     static constexpr int NDE = (SB + 6) * DEW;                   // DE (B over its rows >= 6)
     static constexpr int NBC = 2 * rs * BW;                      // Bc
-    static constexpr int total = R1 + NDE + NBC;
+    static constexpr int NCC = 2 * 3 * TW;                       // Cc: two slots of three C rows' interior columns
+    static constexpr int total = R1 + NDE + NBC + NCC;
     static_assert((SB + 2 * rs) * BW <= SB * DEW, "B must fit in the DE rows past the carried ones");
 };
 
@@ -675,8 +692,7 @@ __device__ __forceinline__ void l0_fetch_u8(const uint8_t *raw, const int nc, co
 
 template <typename TIn, int NS, bool ZC, bool EDGE, bool PRO>
 __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
-                                               const int cbase, const int s0, const int ylim, const bool vec2_ok, const bool vec4_ok,
-                                               uint32_t (&pre)[SB * (TW + 32) / 4 / 256])
+                                               const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[SB * (TW + 32) / 4 / 256])
 {
     constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead (l0_fetch_u8)
     STREAM_CLK_START;
@@ -689,6 +705,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     constexpr int ALO = BLO - 2 * rs;                            // A rows loaded: [ALO, SB)
     static_assert(ALO >= 0, "prologue rows");
     float *const A = lds, *const C = lds, *const DE = lds + L::R1, *const B = DE + 6 * DEW, *const Bc = DE + L::NDE;
+    float *const Ccr = Bc + L::NBC + par * 3 * TW, *const Ccw = Bc + L::NBC + (par ^ 1) * 3 * TW;   // Cc slot read / filled by this band
     // tid goes through an empty asm statement once per band: the per-thread index math of the stages is then recomputed in each band
     // instead of being hoisted out of the band loop and held in registers across all stages
     int tid = threadIdx.x;
@@ -789,12 +806,10 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         }
         __syncthreads();
         STREAM_MARK(1);
-        // ---- stage 2: vertical smoothing, B -> C rows [CLO, SB) (+ store the strip's columns of the rows of the segment)
-        const plane_rsrc img = plane_of(a.img[b]);
+        // ---- stage 2: vertical smoothing, B -> C rows [CLO, SB)
         constexpr int BH = BW / 2, G2 = (SB - CLO + 3) / 4;
         for (int i = (tid + NTHR / 4) & (NTHR - 1); i < G2 * BH; i += NTHR) {
             const int r = CLO + 4 * (i / BH), h = i % BH;
-            const unsigned img_b0 = band_b0 + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h) - (unsigned)(4 * HB);   // (cbase + r, tx0 - HB + 2 h)
             double v[2][NS + 3];
 #pragma unroll
             for (int j = 0; j < NS + 3; j++) {
@@ -809,16 +824,6 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
                 float2 o;
                 o.x = corr_regs<NS, 1>(v[0] + rs + dr, ks); o.y = corr_regs<NS, 1>(v[1] + rs + dr, ks);
                 *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = o;
-                const int y = cbase + rr, x = tx0 - HB + 2 * h;
-                if (h >= HB / 2 && h < HB / 2 + DW / 2 && (!PRO || y >= s0) && y < ylim) {
-                    const unsigned ob = img_b0 + (unsigned)dr * row_bytes;
-                    if (!EDGE && vec2_ok) plane_store2(img, ob, o);
-                    else if (!EDGE) { plane_store(img, ob, o.x); plane_store(img, ob + 4, o.y); }
-                    else {
-                        if (x < nc) plane_store(img, ob, o.x);
-                        if (x + 1 < nc) plane_store(img, ob + 4, o.y);
-                    }
-                }
             }
         }
         // the last 2 rs rows of B are the next band's first ones
@@ -845,6 +850,9 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
             *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + 4 * q) = d;
             *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + DW + 4 * q) = e;
         }
+        // the interior columns of C rows [SB - 3, SB): the first three image rows of the next band's stage 4
+        for (int i = NTHR - 1 - tid; i < 3 * DQ; i += NTHR)
+            *reinterpret_cast<float4 *>(Ccw + 4 * i) = *reinterpret_cast<const float4 *>(C + (SB - 3 + i / DQ) * BW + HB + 4 * (i % DQ));
     }
     {
         // ---- stage 3b: horizontal pass of the pyramid reduction at the columns 4x + 2 of the C rows of the segment (as in the tiled kernel)
@@ -880,12 +888,13 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     if (PRO) return;
     __syncthreads();
     STREAM_MARK(3);
-    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29): D -> gradx (Gaussian taps), E -> grady (derivative taps)
+    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29): D -> gradx (Gaussian taps), E -> grady (derivative taps); the
+    // pixel records (image from C / Cc, gradx, grady) of two adjacent pixels go out together: 24 contiguous bytes
     TapRegs<NG> kg;
     TapRegs<ND> kd;
     load_taps_here(kg, offsetof(SmoothGradArgs, ggauss.k));
     load_taps_here(kd, offsetof(SmoothGradArgs, gderiv.k));
-    const plane_rsrc gxy = plane_of(a.gx[b]);
+    const plane_rsrc recp = plane_of(a.rec[b]);
     constexpr int DH = DW / 2;
     const int y0 = cbase - 3;
     const bool full = y0 + SB <= ylim;
@@ -918,18 +927,14 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
                 oy[dr].x = corr_regs<ND, -1, ZC>(v[0] + ND / 2 + dr, kd); oy[dr].y = corr_regs<ND, -1, ZC>(v[1] + ND / 2 + dr, kd);
             }
         }
-        const unsigned g_b0 = 2u * (band_b0 - 3u * row_bytes + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // (y0 + r, x), interleaved
+        const unsigned r_b0 = 3u * (band_b0 - 3u * row_bytes + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // record of (y0 + r, x)
 #pragma unroll
         for (int dr = 0; dr < 4; dr++) {
             if (!full && y0 + r + dr >= ylim) break;
-            const unsigned ob = g_b0 + (unsigned)dr * 2u * row_bytes;
-            float2 p0, p1;
-            p0.x = ox[dr].x; p0.y = oy[dr].x; p1.x = ox[dr].y; p1.y = oy[dr].y;
-            if (!EDGE && vec4_ok) plane_store4(gxy, ob, p0, p1);
-            else {
-                plane_store2(gxy, ob, p0);
-                if (!EDGE || x + 1 < nc) plane_store2(gxy, ob + 8, p1);
-            }
+            const int k = r + dr;                                // frame row y0 + k = C row k - 3
+            const float *const im_row = k >= 3 ? C + (k - 3) * BW + HB : Ccr + k * TW;
+            const float2 im = *reinterpret_cast<const float2 *>(im_row + 2 * h);
+            store_records(recp, r_b0 + (unsigned)dr * 3u * row_bytes, im, ox[dr], oy[dr], !EDGE || x + 1 < nc);
         }
     }
     STREAM_MARK(4);
@@ -939,12 +944,9 @@ template <typename TIn, int NS, bool ZC, bool EDGE>
 __device__ __forceinline__ void l0_stream_segment(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
                                                   const int s0, const int ylim)
 {
-    const int b = blockIdx.z;
-    const bool vec2_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.img[b]) & 7) == 0;
-    const bool vec4_ok = (nc & 1) == 0 && (reinterpret_cast<uintptr_t>(a.gx[b]) & 15) == 0;
     uint32_t pre[SB * (TW + 32) / 4 / 256];
-    l0_stream_band<TIn, NS, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, vec2_ok, vec4_ok, pre);
-    for (int y = s0; y < ylim; y += SB) l0_stream_band<TIn, NS, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, vec2_ok, vec4_ok, pre);
+    l0_stream_band<TIn, NS, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, 1, pre);          // (fills Cc slot 0)
+    for (int y = s0, par = 0; y < ylim; y += SB, par ^= 1) l0_stream_band<TIn, NS, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, par, pre);
 }
 
 // grid = (ceil(ncols / 64), ceil(nrows / seg_h), batch); seg_h a multiple of SB.
@@ -1206,7 +1208,7 @@ bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Tap
 {
     static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;
     const bool tall = force_th ? force_th == 32 : (long long)a.ncols * a.nrows * batch >= 1000000;
-    return tall && kind < 2 && a.gstride == 2 && a.smooth.sym == 1 && (a.smooth.n == 5 || a.smooth.n == 9) &&
+    return tall && kind < 2 && a.smooth.sym == 1 && (a.smooth.n == 5 || a.smooth.n == 9) &&
            a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && ss == 4 && reduce.sym == 1 && reduce.n == 21 &&
            a.nrows >= 64 && a.ncols >= 64;
 }
@@ -1244,7 +1246,7 @@ int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int ki
 {
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
-    if (a.gstride == 2 && a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
+    if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
         const dim3 blk(256);
         // register-blocked kernels; small frames take the shorter tile so that the grid still covers the chip
         static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;   // experiment hook

@@ -80,19 +80,26 @@ __global__ __launch_bounds__(PIPE_THREADS) __attribute__((amdgpu_waves_per_eu(1,
             SAT_MARK(0, s, 2);
         }
     } else if (wave <= NLW) {                                   // ---- loaders: lane = (row parity, pixel pair of each half of the tile row)
-        // The gradient planes are interleaved (klt_internal.h): a tile row is RT x 8 = 1024 contiguous bytes behind gx.  Lane q takes
-        // the 16 bytes at 16 q of each 512-byte half -- pixels 2 q, 2 q + 1 and RT / 2 + 2 q, RT / 2 + 2 q + 1 with gradx and grady side
-        // by side -- so every load instruction of a row reads one contiguous 512-byte piece.
+        // The gradients are planes of pixel records (klt_internal.h): a tile row is RT x 12 = 1536 contiguous bytes.  Lane q takes the
+        // gradx, grady of pixels 2 q, 2 q + 1 and RT / 2 + 2 q, RT / 2 + 2 q + 1 (four dword loads per pair), so every load instruction of
+        // a row reads within one contiguous 768-byte piece.
         const int j = wave - 1;
         const int half = lane >> 5, q = lane & 31;
+        const plane_rsrc recp = plane_of(gx - 1);               // the records: image, gradx, grady of pixel p at byte 12 p
         float4 va[RB / 2], vb[RB / 2];                          // {gx, gy, gx, gy} of the lane's pixel pair in the first / second half
+        auto pair_at = [&](unsigned p) {
+            float4 v;
+            v.x = plane_load(recp, 12u * p + 4u); v.y = plane_load(recp, 12u * p + 8u);
+            v.z = plane_load(recp, 12u * p + 16u); v.w = plane_load(recp, 12u * p + 20u);
+            return v;
+        };
         auto request = [&](int t) {
             const int c0 = min(t * RT + 2 * q, ncols - 2), c1 = min(t * RT + RT / 2 + 2 * q, ncols - 2);    // clamped, unconditional (ncols % 4 == 0)
 #pragma unroll
             for (int rp = 0; rp < RB / 2; rp++) {
-                const size_t o = (size_t)min(row0 + 2 * rp + half, nrows - 1) * ncols;
-                va[rp] = *reinterpret_cast<const float4 *>(gx + KLT_GRAD_STRIDE * (o + c0));
-                vb[rp] = *reinterpret_cast<const float4 *>(gx + KLT_GRAD_STRIDE * (o + c1));
+                const unsigned o = __umul24((unsigned)min(row0 + 2 * rp + half, nrows - 1), (unsigned)ncols);
+                va[rp] = pair_at(o + (unsigned)c0);
+                vb[rp] = pair_at(o + (unsigned)c1);
             }
         };
         for (int s = -NLW; s < nsteps; s++) {                   // (steps -NLW .. -1: the first requests only; one request site)
@@ -404,7 +411,7 @@ static bool quads_ok(const void *a, const void *b, const void *c, int ncols, int
 
 int launch_sat_rows_pipe(hipStream_t s, const float *gx, const float *gy, float *sat, int ncols, int nrows)
 {
-    if (gy != gx + 1 || !quads_ok(gx, gx, sat, ncols, nrows)) return -1;      // the interleaved gradient planes (klt_internal.h)
+    if (gy != gx + 1 || !quads_ok(gx - 1, gx - 1, sat, ncols, nrows)) return -1;      // planes of pixel records (klt_internal.h)
     constexpr size_t lds = sizeof(float) * NSLOT * RSLOT;
     static bool set = false;
     if (!set) {

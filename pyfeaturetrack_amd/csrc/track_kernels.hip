@@ -61,8 +61,8 @@ __device__ __forceinline__ Bilinear make_bilinear(float x, float y)
     return b;
 }
 
-// ST = element stride of the plane: 1 for an image plane, KLT_GRAD_STRIDE for one of the two interleaved gradient planes (qg then
-// points at the plane's own first element: gradx at +0, grady at +1)
+// ST = element stride of the plane: 1 for a plane of its own, KLT_PIX_STRIDE for one of the three planes of a level's pixel records (qg
+// then points at the plane's own element of the pixel: image at +0, gradx at +1, grady at +2)
 template <int ST = 1>
 __device__ __forceinline__ float sample(const float *__restrict__ qg, int nc, const Bilinear &b)
 {
@@ -159,9 +159,9 @@ __device__ int track_level(const TrackArgs &a, const TrackLevel &lv, float x1, f
         if (k < n) {
             off[kk] = (k / w) * nc + (k % w);
             const size_t q = (size_t)(b1.iy - hw) * nc + (b1.ix - hw) + off[kk];
-            t_i[kk] = sample(lv.i1 + q, nc, b1);
-            t_gx[kk] = sample<KLT_GRAD_STRIDE>(lv.gx1 + KLT_GRAD_STRIDE * q, nc, b1);
-            t_gy[kk] = sample<KLT_GRAD_STRIDE>(lv.gy1 + KLT_GRAD_STRIDE * q, nc, b1);
+            t_i[kk] = sample<KLT_PIX_STRIDE>(lv.i1 + KLT_PIX_STRIDE * q, nc, b1);
+            t_gx[kk] = sample<KLT_PIX_STRIDE>(lv.gx1 + KLT_PIX_STRIDE * q, nc, b1);
+            t_gy[kk] = sample<KLT_PIX_STRIDE>(lv.gy1 + KLT_PIX_STRIDE * q, nc, b1);
         }
     }
 
@@ -185,9 +185,9 @@ __device__ int track_level(const TrackArgs &a, const TrackLevel &lv, float x1, f
             const int k = lane + 64 * kk;
             if (k < n) {
                 const size_t q = base + off[kk];
-                const float diff = t_i[kk] - sample(lv.i2 + q, nc, b2);          // :82-85
-                const float sx = t_gx[kk] + sample<KLT_GRAD_STRIDE>(lv.gx2 + KLT_GRAD_STRIDE * q, nc, b2);          // -( -g1 - g2 ), :128 and :297
-                const float sy = t_gy[kk] + sample<KLT_GRAD_STRIDE>(lv.gy2 + KLT_GRAD_STRIDE * q, nc, b2);
+                const float diff = t_i[kk] - sample<KLT_PIX_STRIDE>(lv.i2 + KLT_PIX_STRIDE * q, nc, b2);          // :82-85
+                const float sx = t_gx[kk] + sample<KLT_PIX_STRIDE>(lv.gx2 + KLT_PIX_STRIDE * q, nc, b2);          // -( -g1 - g2 ), :128 and :297
+                const float sy = t_gy[kk] + sample<KLT_PIX_STRIDE>(lv.gy2 + KLT_PIX_STRIDE * q, nc, b2);
                 lds[k] = sx * sx;                  // gxx terms, :299
                 lds[npad + k] = sx * sy;           // gxy terms, :300
                 lds[2 * npad + k] = sy * sy;       // gyy terms, :301
@@ -248,7 +248,7 @@ __device__ int track_level(const TrackArgs &a, const TrackLevel &lv, float x1, f
 #pragma unroll
         for (int kk = 0; kk < MAXK; kk++) {
             const int k = lane + 64 * kk;
-            if (k < n) l_diff[k] = fabsf(t_i[kk] - sample(lv.i2 + base + off[kk], nc, b2));
+            if (k < n) l_diff[k] = fabsf(t_i[kk] - sample<KLT_PIX_STRIDE>(lv.i2 + KLT_PIX_STRIDE * (base + off[kk]), nc, b2));
         }
         __syncthreads();
         float s = pairwise_sum<3>(l_diff, n, lane);
@@ -324,9 +324,10 @@ __global__ __launch_bounds__(64) void track_kernel(TrackArgs a)
 //   7x7   the 8x8 footprint is 16 quads -> a feature owns 16 lanes and a wavefront tracks FOUR features in lock step under
 //         per-feature predicates (a finished feature keeps its state and idles);
 //   15x15 the 16x16 footprint is exactly 64 quads -> one feature per wavefront.
-// Lane (row r, quad h) of a feature loads pixels (r, 4h .. 4h + 3) and computes the window samples (r, 4h .. 4h + 3) from its own
-// quad, the quad below (lane + quads-per-row) and the first pixels of the quads to the right (lane + 1, lane + quads-per-row + 1):
-// 3 vector loads per footprint and wavefront, where the one-sample-per-lane kernel issues 12 (7x7) or 48 (15x15).  The bounds test
+// Lane (row r, quad h) of a feature loads the records of pixels (r, 4h .. 4h + 3) -- 48 contiguous bytes, three 16-byte loads -- and
+// computes the window samples (r, 4h .. 4h + 3) from its own quad, the quad below (lane + quads-per-row) and the first pixels of the
+// quads to the right (lane + 1, lane + quads-per-row + 1): 3 vector loads per footprint and wavefront, where the one-sample-per-lane
+// kernel issues 12 (7x7) or 48 (15x15).  A footprint row is one contiguous run of (w + 1) records.  The bounds test
 // and the footprint of the NEXT Newton iteration are issued as soon as the position is known -- for the first iteration of a
 // level together with the template's loads -- so a level costs one memory round trip per iteration instead of one more.
 // Every feature's arithmetic is track_level's, operation for operation: same bilinear expression, the five product arrays in
@@ -371,25 +372,35 @@ __device__ __forceinline__ float pairwise_group<0>(const float *a, int n, int s)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// 4-byte aligned 16-byte load of elements q .. q + 3 of a plane, as a raw buffer load: the plane pointer is wavefront-uniform, so the
-// descriptor sits in four SGPRs and the lane's 32-bit byte offset is the whole vector address (a plane is far below 2 GB).  A global
-// load of plane + q costs a 64-bit vector add per load and a register pair for the address; a flat load (what a pointer read from
-// generic memory gives) also counts as an LDS operation.  Word 3 of the descriptor: data format 32 bits, nothing else (raw dwords).
-__device__ __forceinline__ f32x4 load_quad(const float *plane, unsigned q)
+// The records of pixels q .. q + 3 of a level (klt_internal.h: image, gradx, grady per pixel): 48 contiguous bytes at byte offset 12 q,
+// three 4-byte aligned 16-byte loads as raw buffer loads -- the record pointer is wavefront-uniform, so the descriptor sits in four
+// SGPRs and the lane's 32-bit byte offset is the whole vector address (a plane is below 2 GB).  A global load of plane + q costs a
+// 64-bit vector add per load and a register pair for the address; a flat load (what a pointer read from generic memory gives) also
+// counts as an LDS operation.  Word 3 of the descriptor: data format 32 bits, nothing else (raw dwords).  The twelve values are
+// unpacked in registers into the quads of the three planes.
+__device__ __forceinline__ void load_records(const float *rec, unsigned q, f32x4 &im, f32x4 &gx, f32x4 &gy)
 {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)plane, 0, 0x7fffffff, 0x00020000);
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, q << 2, 0, 0));
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)rec, 0, 0x7fffffff, 0x00020000);
+    const unsigned o = 12u * q;
+    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));          // i0 x0 y0 i1
+    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));    // x1 y1 i2 x2
+    const f32x4 c = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 32u, 0, 0));    // y2 i3 x3 y3
+    im.x = a.x; im.y = a.w; im.z = b.z; im.w = c.y;
+    gx.x = a.y; gx.y = b.x; gx.z = b.w; gx.w = c.z;
+    gy.x = a.z; gy.y = b.y; gy.z = c.x; gy.w = c.w;
 }
 
-// the gradient quads of pixels q .. q + 3: the two planes are interleaved (gxy = the gradx plane's pointer, grady one element behind),
-// so the eight values are 32 contiguous bytes -- two 16-byte loads, as for two separate planes, but ONE piece of memory per footprint row
-__device__ __forceinline__ void load_grad_quads(const float *gxy, unsigned q, f32x4 &gx, f32x4 &gy)
+// the image values alone of pixels q .. q + 3 (the residue): four 4-byte loads
+__device__ __forceinline__ f32x4 load_record_images(const float *rec, unsigned q)
 {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)gxy, 0, 0x7fffffff, 0x00020000);
-    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, q << 3, 0, 0));
-    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (q << 3) + 16u, 0, 0));
-    gx.x = a.x; gx.y = a.z; gx.z = b.x; gx.w = b.z;
-    gy.x = a.y; gy.y = a.w; gy.z = b.y; gy.w = b.w;
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)rec, 0, 0x7fffffff, 0x00020000);
+    const unsigned o = 12u * q;
+    f32x4 im;
+    im.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0));
+    im.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 12u, 0, 0));
+    im.z = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 24u, 0, 0));
+    im.w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 36u, 0, 0));
+    return im;
 }
 
 // the four window samples of a lane from its quad `a`: pairs (a.x,a.y), (a.y,a.z), (a.z,a.w), (a.w, right neighbour) and the same
@@ -484,9 +495,8 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
         const bool run = alive && t_ok;
         // (row * nc as a 24-bit multiply: both are far below 2^24, and the 32-bit integer multiply is a quarter-rate instruction)
         const unsigned q1 = run ? __umul24((unsigned)(b1.iy - hw + qr), (unsigned)nc) + (unsigned)(b1.ix - hw + 4 * qh) : 0u;   // 32-bit element offsets: scalar base + vector offset loads
-        const f32x4 t_qi = load_quad(lv.i1, q1);
-        f32x4 t_qgx, t_qgy;
-        load_grad_quads(lv.gx1, q1, t_qgx, t_qgy);
+        f32x4 t_qi, t_qgx, t_qgy;
+        load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
 
         // the first Newton iteration starts from a position that is already known: its bounds test (trackFeaturesUtils.pyx:428-431)
         // and its footprint loads go out now, behind the template's
@@ -510,12 +520,12 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
             if (REUSE) {
                 const unsigned q = __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh);
                 if (iterating && q != q_held) {
-                    s_qi = load_quad(lv.i2, q); load_grad_quads(lv.gx2, q, s_qgx, s_qgy);
+                    load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
                     q_held = q;
                 }
             } else {
                 const unsigned q = iterating ? __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh) : 0u;
-                s_qi = load_quad(lv.i2, q); load_grad_quads(lv.gx2, q, s_qgx, s_qgy);
+                load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
             }
         };
         request_footprint();
@@ -627,10 +637,10 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
             if (REUSE) {
                 const unsigned q = __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh);
                 r_qi = s_qi;                                 // the last footprint, if the final position has the same integer corner
-                if (need_res && q != q_held) r_qi = load_quad(lv.i2, q);
+                if (need_res && q != q_held) r_qi = load_record_images(lv.i2, q);
             } else {
                 const unsigned q = need_res ? __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh) : 0u;
-                r_qi = load_quad(lv.i2, q);
+                r_qi = load_record_images(lv.i2, q);
             }
             float s_i[4];
             sample_quad<QPR>(r_qi, br, s_i);

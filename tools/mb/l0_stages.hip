@@ -1,7 +1,7 @@
 // Stage timing of the level-0 kernel: includes the product source with KLT_STAGE_CLOCKS and prints, for 64 workgroups of one
 // tile row, the wall-clock ticks (100 MHz) spent between the stage marks.  `T`: the tiled kernel with the fused reduction, `s`: the
-// streaming kernel (per-stage ticks summed over the bands of one segment), both on 16 1080p u8 frames with interleaved gradient planes
-// as at cfg-2.  Build (from the repo root):
+// streaming kernel (per-stage ticks summed over the bands of one segment), both on 16 1080p u8 frames into planes of pixel records
+// as at cfg-2 (`p`, the tiled kernel without the fused reduction, also writes the compact image copy the build then asks for).  Build (from the repo root):
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DKLT_STAGE_CLOCKS -Iinclude -Ipyfeaturetrack_amd/csrc tools/mb/l0_stages.hip -o tools/mb/l0_stages
 #include "../../pyfeaturetrack_amd/csrc/pyramid_kernels.hip"
 #include <cstdio>
@@ -33,19 +33,19 @@ int main(int argc, char **argv)
     for (size_t i = 0; i < h.size(); i++) h[i] = (uint8_t)((i * 2654435761u) >> 24);
     const bool tiled16 = argc > 1 && argv[1][0] == 'T', stream = argc > 1 && argv[1][0] == 's';
     const int B = tiled16 || stream ? 16 : 2;
-    if (B == 16) a.gstride = 2;
+    const bool plain = argc > 1 && argv[1][0] == 'p';      // the kernel without the fused horizontal reduction
+    float *cimg[KLT_MAX_BATCH], *dst[KLT_MAX_BATCH];
     for (int b = 0; b < B; b++) {
-        uint8_t *raw; float *img, *gx, *gy;
-        hipMalloc(&raw, h.size()); hipMalloc(&img, 4 * h.size()); hipMalloc(&gx, 8 * h.size()); hipMalloc(&gy, 4 * h.size());
+        uint8_t *raw; float *rec;
+        hipMalloc(&raw, h.size()); hipMalloc(&rec, 4 * KLT_PIX_STRIDE * h.size()); hipMalloc(&cimg[b], 4 * h.size()); hipMalloc(&dst[b], 4 * h.size());
         hipMemcpy(raw, h.data(), h.size(), hipMemcpyHostToDevice);
-        a.raw[b] = raw; a.img[b] = img; a.gx[b] = gx; a.gy[b] = B == 16 ? gx + 1 : gy;
+        a.raw[b] = raw; a.rec[b] = rec; a.cimg[b] = plain ? cimg[b] : nullptr;
     }
     PyrReduceArgs pr = {};
     gauss_taps(pr.taps, dummy, 3.6, 21);
     pr.src_nc = nc; pr.src_nr = nr; pr.dst_nc = nc / 4; pr.dst_nr = nr / 4; pr.ss = 4; pr.log2ss = 2;
-    for (int b = 0; b < 2; b++) { pr.src[b] = a.img[b]; pr.dst[b] = a.gx[b]; }
+    for (int b = 0; b < 2; b++) { pr.src[b] = cimg[b]; pr.dst[b] = dst[b]; }
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    const bool plain = argc > 1 && argv[1][0] == 'p';      // the kernel without the fused horizontal reduction
     a.reduce = pr.taps; a.h1_nc = nc / 4;
     for (int b = 0; b < B; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
     auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, B, 0, !plain, stream); };

@@ -9,12 +9,12 @@ thread_local hipEvent_t g_klt_stamp_start = nullptr, g_klt_stamp_stop = nullptr;
 int main(int argc, char **argv)
 {
     const int nc = argc > 2 ? atoi(argv[1]) : 1920, nr = argc > 2 ? atoi(argv[2]) : 1080;
-    float *gx, *gy, *sat;
-    hipMalloc(&gx, 8ull * nc * nr); gy = gx + 1;                    // the interleaved gradient planes (klt_internal.h)
+    float *rec, *gx, *gy, *sat;
+    hipMalloc(&rec, 12ull * nc * nr); gx = rec + 1; gy = rec + 2;   // the gradient planes of pixel records (klt_internal.h)
     hipMalloc(&sat, 12ull * nc * nr);
-    std::vector<float> h(2 * (size_t)nc * nr);
+    std::vector<float> h(3 * (size_t)nc * nr);
     for (size_t i = 0; i < h.size(); i++) h[i] = (float)((i * 2654435761u) >> 20) * 1e-3f;
-    hipMemcpy(gx, h.data(), 4 * h.size(), hipMemcpyHostToDevice);
+    hipMemcpy(rec, h.data(), 4 * h.size(), hipMemcpyHostToDevice);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int i = 0; i < 3; i++) launch_sat_rows_pipe(0, gx, gy, sat, nc, nr);
     hipDeviceSynchronize();
