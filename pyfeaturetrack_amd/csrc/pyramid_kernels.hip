@@ -227,10 +227,15 @@ __global__ __launch_bounds__(256) void pyr_reduce_kernel(PyrReduceArgs a)
 // in scalar registers for the whole kernel and the correlate loops are fully unrolled (same operation order).
 // The runtime-sized kernels above remain the fallback for unusual sigmas.
 
+// The reflect map for indices at most n beyond either end (frames at least as large as the halo): branch-free
+__device__ __forceinline__ int reflect_once(int i, int n)
+{
+    return i < 0 ? -1 - i : i >= n ? 2 * n - 1 - i : i;
+}
+
 __device__ __forceinline__ int reflect_fast(int i, int n)
 {
-    if (i < 0) i = -1 - i;
-    else if (i >= n) i = 2 * n - 1 - i;
+    i = reflect_once(i, n);
     if ((unsigned)i >= (unsigned)n) i = reflect_idx(i, n);      // frames smaller than the halo
     return i;
 }
@@ -267,11 +272,6 @@ __device__ __forceinline__ float corr_regs(const double *c /* centre */, const T
     return (float)acc;
 }
 
-__device__ __forceinline__ void widen4(const float4 v, double *d)
-{
-    d[0] = (double)v.x; d[1] = (double)v.y; d[2] = (double)v.z; d[3] = (double)v.w;
-}
-
 // Three aligned quads of an LDS row, widened.  The loads are volatile so that they stay three ds_read_b128: when only 8 or
 // 10 of the 12 samples are used the compiler otherwise narrows them to ds_read2_b32 pairs, and dword reads at a lane stride
 // of 16 bytes are 4-way bank conflicts.
@@ -303,6 +303,179 @@ __device__ __forceinline__ void store_records(plane_rsrc r, unsigned ob, float2 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Stage primitives of the two level-0 kernels (smooth_grad_rb and smooth_grad_stream): one thread's work item of a stage, on the LDS
+// pointers it is given.  The kernels keep what differs between them: the work-item loops and their thread rotation, the rows and columns
+// an item maps to, the barriers, the carries between bands, the store predicates and the stage marks.
+
+__device__ __forceinline__ float4 unpack_u8x4(uint32_t w)
+{
+    float4 v;
+    v.x = (float)(w & 0xffu); v.y = (float)((w >> 8) & 0xffu);
+    v.z = (float)((w >> 16) & 0xffu); v.w = (float)(w >> 24);
+    return v;
+}
+
+// Four adjacent raw samples in registers: the packed word of a u8 frame (the streaming kernel keeps a band of them in flight in three
+// registers), a float4 of an f32 frame
+template <typename TIn> struct RawQuad;
+template <> struct RawQuad<uint8_t> { typedef uint32_t reg; };
+template <> struct RawQuad<float> { typedef float4 reg; };
+__device__ __forceinline__ float4 quad_f32(uint32_t w) { return unpack_u8x4(w); }
+__device__ __forceinline__ float4 quad_f32(float4 v) { return v; }
+
+// Is the block of H rows x WQ quads at frame position (y0, x0) inside the frame, its quads aligned?
+template <int H, int WQ>
+__device__ __forceinline__ bool raw_block_interior(int nc, int nr, int y0, int x0)
+{
+    return (nc & 3) == 0 && x0 >= 0 && x0 + 4 * WQ <= nc && y0 >= 0 && y0 + H <= nr;
+}
+
+// Stage 0: the raw block of H rows x WQ quads at frame position (y0, x0) -> registers; w[u] = quad tid + u NTHR of the block, row-major
+// (clamped: the last threads repeat the last quad).  Converting to f32 and storing to LDS is the caller's.  The frame must be large
+// enough that one reflection brings every index of the block inside.
+template <typename TIn, int H, int WQ, int NTHR>
+__device__ __forceinline__ void load_raw_block(const TIn *raw, int nc, int nr, int y0, int x0, int tid,
+                                               typename RawQuad<TIn>::reg (&w)[(H * WQ + NTHR - 1) / NTHR])
+{
+    constexpr int N0 = H * WQ, U0 = (N0 + NTHR - 1) / NTHR;
+    if (raw_block_interior<H, WQ>(nc, nr, y0, x0)) {
+        // Blocks inside the frame (most of them): every load of the thread is issued before the first one is used.  A loop
+        // that waits for each of its 3-4 loads in turn costs 2.2 of the 9 us a workgroup of the tiled kernel lives.
+        const plane_rsrc rawp = plane_of(raw);
+        const unsigned row_b = (unsigned)nc * (unsigned)sizeof(TIn), raw_b0 = (unsigned)y0 * row_b + (unsigned)x0 * (unsigned)sizeof(TIn);
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            const int i = N0 % NTHR ? min(tid + u * NTHR, N0 - 1) : tid + u * NTHR;
+            const unsigned off = raw_b0 + __umul24((unsigned)(i / WQ), row_b) + 4u * (unsigned)sizeof(TIn) * (unsigned)(i % WQ);
+            if constexpr (sizeof(TIn) == 1) {
+                w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, off, 0, 0);
+            } else {
+                w[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rawp, off, 0, 0));
+            }
+        }
+    } else {
+        // blocks at the frame's edges: branch-free index map, all element loads of the thread in flight together
+        TIn e[U0][4];
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            const int i = N0 % NTHR ? min(tid + u * NTHR, N0 - 1) : tid + u * NTHR;
+            const TIn *row = raw + (size_t)reflect_once(y0 + i / WQ, nr) * nc;
+            const int x = x0 + 4 * (i % WQ);
+#pragma unroll
+            for (int k = 0; k < 4; k++) e[u][k] = row[reflect_once(x + k, nc)];
+        }
+#pragma unroll
+        for (int u = 0; u < U0; u++) {
+            if constexpr (sizeof(TIn) == 1) {
+                w[u] = e[u][0] | (uint32_t)e[u][1] << 8 | (uint32_t)e[u][2] << 16 | (uint32_t)e[u][3] << 24;
+            } else {
+                w[u].x = e[u][0]; w[u].y = e[u][1]; w[u].z = e[u][2]; w[u].w = e[u][3];
+            }
+        }
+    }
+}
+
+// Four adjacent outputs of a horizontal pass from the twelve widened samples of their row (the outputs sit at v[4..7])
+template <int NT, int SYM, bool ZC = false>
+__device__ __forceinline__ float4 corr_quad(const double *v, const TapRegs<NT> &t)
+{
+    float4 o;
+    o.x = corr_regs<NT, SYM, ZC>(v + 4, t); o.y = corr_regs<NT, SYM, ZC>(v + 5, t);
+    o.z = corr_regs<NT, SYM, ZC>(v + 6, t); o.w = corr_regs<NT, SYM, ZC>(v + 7, t);
+    return o;
+}
+
+// Stage 1: horizontal smoothing of the four samples that start at a[4] (a: a quad of an A row)
+template <int NS>
+__device__ __forceinline__ float4 hsmooth_quad(const float *a, const TapRegs<NS> &ks)
+{
+    double v[12];
+    widen12(a, v);
+    return corr_quad<NS, 1>(v, ks);
+}
+
+// Stage 3: horizontal pass of both gradients at the four samples that start at c[4] (c: a quad of a C row): d = derivative taps
+// along x (gradx after stage 4), e = Gaussian taps along x (grady)
+template <int NG, int ND, bool ZC>
+__device__ __forceinline__ void hgrad_quad(const float *c, const TapRegs<NG> &kg, const TapRegs<ND> &kd, float4 &d, float4 &e)
+{
+    double v[12];
+    widen12(c, v);
+    d = corr_quad<ND, -1, ZC>(v, kd);
+    e = corr_quad<NG, 1>(v, kg);
+}
+
+// Stage 3b: horizontal pass of the first pyramid reduction (pyramid.py:59-72 -> correlate1d along x, symmetric branch; f32 result, as
+// between the reference's two passes) at TWO adjacent surviving columns (four samples apart): their 21-sample windows share 17 samples, so
+// 28 samples are read and widened for two outputs instead of 24 for each.  c: the quad of a C row that starts at the first output's
+// leftmost sample.  kr.k[0..NR/2]: the taps left of and at the centre (symmetric).
+template <int NR>
+__device__ __forceinline__ void hreduce_pair(const float *c, const TapRegs<NR / 2 + 1> &kr, float (&o)[2])
+{
+    constexpr int HR = NR / 2;
+    static_assert(2 * HR + 4 < 28, "both windows inside the seven quads");
+    typedef const volatile __attribute__((address_space(3))) f32x4 *lds_quad_ptr;      // (volatile: as in widen12)
+    const lds_quad_ptr p = (lds_quad_ptr)c;
+    double v[28];
+#pragma unroll
+    for (int u = 0; u < 7; u++) {
+        const f32x4 t = p[u];
+        v[4 * u] = (double)t.x; v[4 * u + 1] = (double)t.y; v[4 * u + 2] = (double)t.z; v[4 * u + 3] = (double)t.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const double *m = v + HR + 4 * i;                        // centre sample of output i
+        double acc = m[0] * kr.k[HR];
+#pragma unroll
+        for (int jj = -HR; jj < 0; jj++) acc = acc + (m[jj] + m[-jj]) * kr.k[HR + jj];
+        o[i] = (float)acc;
+    }
+}
+
+// The vertical passes (stages 2 and 4).  A thread makes two adjacent columns on FOUR consecutive rows: the NT + 3 rows of two samples
+// they need are read (ds_read_b64) and widened once for 8 outputs -- with 7 taps 2.5 widenings per output where a quad on two rows
+// needs 4, with 5 taps 2 against 3 (the widening is an FP64-rate instruction like the adds and multiplies).
+// p: the two samples of the first row, rows STRIDE floats apart; rows past jlast are read as row jlast (they only feed outputs that
+// the caller does not make).
+template <int NROWS, int STRIDE>
+__device__ __forceinline__ void widen_col_pair(const float *p, int jlast, double (&v)[2][NROWS])
+{
+#pragma unroll
+    for (int j = 0; j < NROWS; j++) {
+        const float2 t = *reinterpret_cast<const float2 *>(p + min(j, jlast) * STRIDE);
+        v[0][j] = (double)t.x; v[1][j] = (double)t.y;
+    }
+}
+
+// ... and output row dr (0..3) of the two columns
+template <int NT, int SYM, bool ZC = false>
+__device__ __forceinline__ float2 corr_pair(const double (&v)[2][NT + 3], int dr, const TapRegs<NT> &t)
+{
+    float2 o;
+    o.x = corr_regs<NT, SYM, ZC>(v[0] + NT / 2 + dr, t); o.y = corr_regs<NT, SYM, ZC>(v[1] + NT / 2 + dr, t);
+    return o;
+}
+
+// Stage 4: vertical pass of both gradients, two columns x four rows: D -> gradx (Gaussian taps), E -> grady (derivative taps).
+// d, e: the two samples of the first of the NG + 3 rows of D and of E.
+template <int NG, int ND, int STRIDE, bool ZC>
+__device__ __forceinline__ void vgrad_2x4(const float *d, const float *e, const TapRegs<NG> &kg, const TapRegs<ND> &kd, float2 (&ox)[4], float2 (&oy)[4])
+{
+    {
+        double v[2][NG + 3];
+        widen_col_pair<NG + 3, STRIDE>(d, NG + 2, v);
+#pragma unroll
+        for (int dr = 0; dr < 4; dr++) ox[dr] = corr_pair<NG, 1>(v, dr, kg);
+    }
+    {
+        double v[2][ND + 3];
+        widen_col_pair<ND + 3, STRIDE>(e, ND + 2, v);
+#pragma unroll
+        for (int dr = 0; dr < 4; dr++) oy[dr] = corr_pair<ND, -1, ZC>(v, dr, kd);
+    }
+}
+
 #ifndef KLT_L0_WAVES
 #define KLT_L0_WAVES 4
 #endif
@@ -314,24 +487,32 @@ __device__ __forceinline__ void store_records(plane_rsrc r, unsigned ob, float2 
 // the reflected ones (header of this file), which is what the reference's reduction reads beyond the frame edge.
 // EDGE = false: the instantiation for tiles whose outputs all land inside the frame (every tile but the last row / column of tiles of
 // a frame whose size is not a multiple of the tile): the per-row and per-column store predicates fold away.
-template <typename TIn, bool SMOOTH, int NS, int NG, int ND, int TH_, int NTHR, bool HRED, bool EDGE>
-__device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, float *const lds, const int nc, const int nr)
-{
+// LDS layout of the tiled kernel: floats per row, rows and region sizes, for the kernel (array size) and the tile body (offsets)
+template <bool SMOOTH, int NS, int NG, int ND, int TH_, bool HRED>
+struct TileLds {
     static_assert(!HRED || SMOOTH, "the fused horizontal reduction needs the smoothing stages");
-    constexpr int HB = HRED ? 12 : 4;                           // halo columns of the image tile (B, C) on each side
-    constexpr int rs = SMOOTH ? NS / 2 : 0;
-    constexpr int R = (NG > ND ? NG : ND) / 2;
+    static constexpr int HB = HRED ? 12 : 4;                    // halo columns of the image tile (B, C) on each side
+    static constexpr int rs = SMOOTH ? NS / 2 : 0, R = (NG > ND ? NG : ND) / 2;
     static_assert(rs <= 4 && R <= 4, "register-blocked kernel needs tap radii <= 4");
-    constexpr int AW = TW + 2 * HB + 8, BW = TW + 2 * HB, DW = TW;   // floats per row (A starts at column -HB-4, B / C at -HB, D / E at 0)
-    constexpr int AQ = AW / 4, BQ = BW / 4, DQ = DW / 4;        // quads per row
-    constexpr int IH = TH_ + 2 * R, RH = IH + 2 * rs;
+    static constexpr int AW = TW + 2 * HB + 8, BW = TW + 2 * HB, DW = TW;   // floats per row (A starts at column -HB-4, B / C at -HB, D / E at 0)
+    static constexpr int IH = TH_ + 2 * R, RH = IH + 2 * rs;
     // LDS regions.  With smoothing: [A | C] then [B | D E] -- the raw tile A is dead once B exists and the smoothed tile C takes its
     // place; B is dead once C exists and the two gradient intermediates D, E take its place (they are written while C is read,
     // so they cannot share C's region).  35.6 KB for the 32-row tile with the fused reduction: four workgroups per CU, and the
     // 2040 tiles of a 1080p pair are two full rounds of the 1024 slots (44 KB / three per CU before: 2.66 rounds).
     // Without smoothing (gradients of levels >= 1): C, then D E.
-    constexpr int AC = SMOOTH ? (RH * AW > IH * BW ? RH * AW : IH * BW) : IH * BW;
-    float *const A = lds, *const C = lds, *const B = lds + AC, *const D = lds + AC, *const E = lds + AC + IH * DW;
+    static constexpr int AC = SMOOTH ? (RH * AW > IH * BW ? RH * AW : IH * BW) : IH * BW;
+    static constexpr int BDE = SMOOTH ? (RH * BW > 2 * IH * DW ? RH * BW : 2 * IH * DW) : 2 * IH * DW;
+    static constexpr int total = AC + BDE;
+};
+
+template <typename TIn, bool SMOOTH, int NS, int NG, int ND, int TH_, int NTHR, bool HRED, bool EDGE>
+__device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, float *const lds, const int nc, const int nr)
+{
+    using L = TileLds<SMOOTH, NS, NG, ND, TH_, HRED>;
+    constexpr int HB = L::HB, rs = L::rs, R = L::R, AW = L::AW, BW = L::BW, DW = L::DW, IH = L::IH, RH = L::RH;
+    constexpr int AQ = AW / 4, BQ = BW / 4, DQ = DW / 4;        // quads per row
+    float *const A = lds, *const C = lds, *const B = lds + L::AC, *const D = lds + L::AC, *const E = lds + L::AC + IH * DW;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH_;
     // two adjacent outputs of the compact image copy go out as one 8-byte store where every row keeps them aligned (block-uniform)
@@ -350,79 +531,25 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
         constexpr int W0 = SMOOTH ? AQ : BQ, H0 = SMOOTH ? RH : IH, X0 = SMOOTH ? -(HB + 4) : -HB, Y0 = -(R + rs);
         float *const dst = SMOOTH ? A : C;
         constexpr int N0 = H0 * W0, U0 = (N0 + NTHR - 1) / NTHR;
-        // Tiles whose halo lies inside the frame (most of them): every load of the thread is issued before the first one
-        // is used.  The general loop below waits for each of its 3-4 loads in turn -- 2.2 of the 9 us a workgroup lives.
-        const bool interior = (nc & 3) == 0 && tx0 + X0 >= 0 && tx0 + X0 + 4 * W0 <= nc && ty0 + Y0 >= 0 && ty0 + Y0 + H0 <= nr;
-        if (interior) {
-            const plane_rsrc rawp = plane_of(raw);
-            const unsigned raw_b0 = ((unsigned)(ty0 + Y0) * (unsigned)nc + (unsigned)(tx0 + X0)) * (unsigned)sizeof(TIn);
-            if (sizeof(TIn) == 1) {
-                uint32_t w[U0];
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = min(tid + u * NTHR, N0 - 1);          // clamped, unconditional (the last threads repeat a quad)
-                    w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, raw_b0 + __umul24((unsigned)(i / W0), (unsigned)nc) + 4u * (unsigned)(i % W0), 0, 0);
-                }
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = tid + u * NTHR;
-                    float4 v;
-                    v.x = (float)(w[u] & 0xffu); v.y = (float)((w[u] >> 8) & 0xffu);
-                    v.z = (float)((w[u] >> 16) & 0xffu); v.w = (float)(w[u] >> 24);
-                    if (i < N0) *reinterpret_cast<float4 *>(dst + (size_t)i * 4) = v;
-                }
-            } else {
-                float4 w[U0];
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = min(tid + u * NTHR, N0 - 1);
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rawp, raw_b0 + __umul24((unsigned)(i / W0), row_bytes) + 16u * (unsigned)(i % W0), 0, 0);
-                    w[u] = __builtin_bit_cast(float4, q);
-                }
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = tid + u * NTHR;
-                    if (i < N0) *reinterpret_cast<float4 *>(dst + (size_t)i * 4) = w[u];
-                }
-            }
-        } else if (nc >= 2 * TW && nr >= 2 * TH_) {
-            // frame-edge tiles of frames large enough that one reflection brings every index inside: branch-free index
-            // map, all element loads of the thread in flight together
-            TIn e[U0][4];
-#pragma unroll
-            for (int u = 0; u < U0; u++) {
-                const int i = min(tid + u * NTHR, N0 - 1);
-                const int y = ty0 + Y0 + i / W0, x = tx0 + X0 + 4 * (i % W0);
-                const TIn *row = raw + (size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int xx = x + k;
-                    e[u][k] = row[xx < 0 ? -1 - xx : xx >= nc ? 2 * nc - 1 - xx : xx];
-                }
-            }
+        // tiles whose halo lies inside the frame, and frame-edge tiles of frames large enough that one reflection brings every index inside
+        if (raw_block_interior<H0, W0>(nc, nr, ty0 + Y0, tx0 + X0) || (nc >= 2 * TW && nr >= 2 * TH_)) {
+            typename RawQuad<TIn>::reg w[U0];
+            load_raw_block<TIn, H0, W0, NTHR>(raw, nc, nr, ty0 + Y0, tx0 + X0, tid, w);
 #pragma unroll
             for (int u = 0; u < U0; u++) {
                 const int i = tid + u * NTHR;
-                float4 v;
-                v.x = (float)e[u][0]; v.y = (float)e[u][1]; v.z = (float)e[u][2]; v.w = (float)e[u][3];
-                if (i < N0) *reinterpret_cast<float4 *>(dst + (size_t)i * 4) = v;
+                if (i < N0) *reinterpret_cast<float4 *>(dst + (size_t)i * 4) = quad_f32(w[u]);
             }
         } else
-        for (int i = tid; i < H0 * W0; i += NTHR) {
+        for (int i = tid; i < H0 * W0; i += NTHR) {              // frames smaller than the halo
             const int r = i / W0, q = i % W0;
             const int gy = reflect_fast(ty0 + Y0 + r, nr);
             const int x = tx0 + X0 + 4 * q;
             const TIn *row = raw + (size_t)gy * nc;
             float4 v;
             if (x >= 0 && x + 3 < nc && (nc & 3) == 0) {          // aligned quad: one 4- or 16-byte load
-                if (sizeof(TIn) == 1) {
-                    const uint32_t wq = *reinterpret_cast<const uint32_t *>(row + x);
-                    v.x = (float)(wq & 0xffu); v.y = (float)((wq >> 8) & 0xffu);
-                    v.z = (float)((wq >> 16) & 0xffu); v.w = (float)(wq >> 24);
-                } else {
-                    v = *reinterpret_cast<const float4 *>(row + x);
-                }
+                if constexpr (sizeof(TIn) == 1) v = unpack_u8x4(*reinterpret_cast<const uint32_t *>(row + x));
+                else v = *reinterpret_cast<const float4 *>(row + x);
             } else if (x >= 0 && x + 3 < nc) {
                 v.x = (float)row[x]; v.y = (float)row[x + 1]; v.z = (float)row[x + 2]; v.w = (float)row[x + 3];
             } else {
@@ -440,19 +567,12 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
         // ---- stage 1: horizontal smoothing, A -> B (B column c = A column c + 4)
         for (int i = tid; i < RH * BQ; i += NTHR) {
             const int r = i / BQ, q = i % BQ;
-            double v[12];
-            widen12(A + r * AW + 4 * q, v);
-            float4 o;
-            o.x = corr_regs<NS, 1>(v + 4, ks); o.y = corr_regs<NS, 1>(v + 5, ks);
-            o.z = corr_regs<NS, 1>(v + 6, ks); o.w = corr_regs<NS, 1>(v + 7, ks);
-            *reinterpret_cast<float4 *>(B + r * BW + 4 * q) = o;
+            *reinterpret_cast<float4 *>(B + r * BW + 4 * q) = hsmooth_quad<NS>(A + r * AW + 4 * q, ks);
         }
         __syncthreads();
         STAGE_MARK(2);
         // ---- stage 2: vertical smoothing, B -> C (+ store the tile interior of the compact image copy, if one is asked for; the
-        // records take the image from C in stage 4).
-        // A thread produces two adjacent columns on FOUR consecutive rows: NS + 3 rows of two samples are read (ds_read_b64) and
-        // widened for 8 outputs -- 2 widenings per output (a quad on two rows: 3).
+        // records take the image from C in stage 4)
         const bool cimg_out = a.cimg[b] != nullptr;
         const plane_rsrc img = plane_of(a.cimg[b]);
         constexpr int BH = BW / 2, G2 = (IH + 3) / 4;           // half-quads per row, groups of four rows (the last one may be partial)
@@ -461,18 +581,12 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
             // byte offset of (ty0 - R + r, tx0 - HB + 2 h) modulo 2^32 (rows above the frame are never stored)
             const unsigned img_b0 = tile_b0 + __umul24((unsigned)r, row_bytes) - (unsigned)R * row_bytes + (unsigned)(8 * h) - (unsigned)(4 * HB);
             double v[2][NS + 3];
-#pragma unroll
-            for (int j = 0; j < NS + 3; j++) {
-                const int rj = min(r + j, RH - 1);              // rows past the tile only feed outputs that are not stored
-                const float2 t = *reinterpret_cast<const float2 *>(B + rj * BW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
+            widen_col_pair<NS + 3, BW>(B + r * BW + 2 * h, RH - 1 - r, v);
 #pragma unroll
             for (int dr = 0; dr < 4; dr++) {
                 const int rr = r + dr;
                 if (rr >= IH) break;
-                float2 o;
-                o.x = corr_regs<NS, 1>(v[0] + rs + dr, ks); o.y = corr_regs<NS, 1>(v[1] + rs + dr, ks);
+                const float2 o = corr_pair<NS, 1>(v, dr, ks);
                 *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = o;
                 const int y = ty0 - R + rr, x = tx0 - HB + 2 * h;
                 if (cimg_out && rr >= R && rr < R + TH_ && h >= HB / 2 && h < HB / 2 + DW / 2 && (!EDGE || y < nr)) {
@@ -494,59 +608,39 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
     // and 1, and wavefront w of every workgroup of a CU sits on SIMD w -- the rotation evens out the SIMDs)
     for (int i = (tid + NTHR / 2) & (NTHR - 1); i < IH * DQ; i += NTHR) {
         const int r = i / DQ, q = i % DQ;
-        double v[12];
-        widen12(C + r * BW + 4 * q + (HB - 4), v);
         float4 d, e;
-        d.x = corr_regs<ND, -1>(v + 4, kd); d.y = corr_regs<ND, -1>(v + 5, kd);
-        d.z = corr_regs<ND, -1>(v + 6, kd); d.w = corr_regs<ND, -1>(v + 7, kd);
-        e.x = corr_regs<NG, 1>(v + 4, kg); e.y = corr_regs<NG, 1>(v + 5, kg);
-        e.z = corr_regs<NG, 1>(v + 6, kg); e.w = corr_regs<NG, 1>(v + 7, kg);
+        hgrad_quad<NG, ND, false>(C + r * BW + 4 * q + (HB - 4), kg, kd, d, e);
         *reinterpret_cast<float4 *>(D + r * DW + 4 * q) = d;
         *reinterpret_cast<float4 *>(E + r * DW + 4 * q) = e;
     }
     if (HRED) {
         // ---- stage 3b: horizontal pass of the pyramid reduction at the surviving columns 4x + 2 of the tile's own rows
-        // (pyramid.py:59-72 -> correlate1d along x, symmetric branch; f32 result, as between the reference's two passes)
         constexpr int NR = 21, HR = NR / 2;
-        TapRegs<HR + 1> kr;                                     // k[0..HR]: the taps left of and at the centre (symmetric)
+        TapRegs<HR + 1> kr;
 #pragma unroll
         for (int t = 0; t <= HR; t++) kr.k[t] = a.reduce.k[t];
         const plane_rsrc h1 = plane_of(a.h1[b]);
         const int h1_nc = a.h1_nc;
         const unsigned h1_row_bytes = 4u * (unsigned)h1_nc, h1_b0 = (unsigned)ty0 * h1_row_bytes + (unsigned)tx0;   // (ty0, tx0 / 4); tx0 % 4 == 0
-        // a thread makes TWO adjacent outputs (columns 4 xs + 2 and 4 xs + 6 of the tile): their 21-sample windows share 17
-        // samples, so 28 samples are read and widened for two outputs instead of 24 for each
         static_assert(DQ % 2 == 0, "tile width must be a multiple of eight");
         for (int i = tid; i < TH_ * (DQ / 2); i += NTHR) {
-            const int r = i / (DQ / 2), xs = 2 * (i % (DQ / 2));
+            const int r = i / (DQ / 2), xs = 2 * (i % (DQ / 2));     // outputs at columns 4 xs + 2 and 4 xs + 6 of the tile
             // centre = image column 4 xs + 2 = C index HB + 4 xs + 2; samples -10 .. +10 start at C index 4 xs + HB - 8 (a quad)
-            typedef const volatile __attribute__((address_space(3))) f32x4 *lds_quad_ptr;
-            const lds_quad_ptr p = (lds_quad_ptr)(C + (r + R) * BW + 4 * xs + (HB - 8));
-            double v[28];
-#pragma unroll
-            for (int u = 0; u < 7; u++) {
-                const f32x4 t = p[u];
-                v[4 * u] = (double)t.x; v[4 * u + 1] = (double)t.y; v[4 * u + 2] = (double)t.z; v[4 * u + 3] = (double)t.w;
-            }
+            float o[2];
+            hreduce_pair<NR>(C + (r + R) * BW + 4 * xs + (HB - 8), kr, o);
             const int y = ty0 + r;
 #pragma unroll
-            for (int o = 0; o < 2; o++) {
-                const double *c = v + HR + 4 * o;                    // centre sample of output o
-                double acc = c[0] * kr.k[HR];
-#pragma unroll
-                for (int jj = -HR; jj < 0; jj++) acc = acc + (c[jj] + c[-jj]) * kr.k[HR + jj];
-                const int xg = tx0 / 4 + xs + o;
+            for (int k = 0; k < 2; k++) {
+                const int xg = tx0 / 4 + xs + k;
                 if (!EDGE || (y < nr && xg < h1_nc))
-                    plane_store(h1, h1_b0 + __umul24((unsigned)r, h1_row_bytes) + 4u * (unsigned)(xs + o), (float)acc);
+                    plane_store(h1, h1_b0 + __umul24((unsigned)r, h1_row_bytes) + 4u * (unsigned)(xs + k), o[k]);
             }
         }
     }
     __syncthreads();
     STAGE_MARK(4);
-    // ---- stage 4: vertical pass, D -> gradx (Gaussian taps), E -> grady (derivative taps).  A thread makes two adjacent columns on
-    // FOUR consecutive rows: NG + 3 rows of two samples are read (ds_read_b64) and widened once for 8 outputs per plane -- 2.5
-    // widenings per output where a quad on two rows needs 4 (the widening is an FP64-rate instruction like the adds and multiplies).
-    // The two pixel records (image from C, gradx, grady) go out together: 24 contiguous bytes.
+    // ---- stage 4: vertical pass, D -> gradx, E -> grady.  The two pixel records (image from C, gradx, grady) of a row go out
+    // together: 24 contiguous bytes.
     const plane_rsrc recp = plane_of(a.rec[b]);
     static_assert(TH_ % 4 == 0, "tile height must be a multiple of four");
     static_assert(NG == ND, "the vertical pass shares its row window between the two planes");
@@ -556,30 +650,7 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
         const int x = tx0 + 2 * h;
         if (EDGE && (ty0 + r >= nr || x >= nc)) continue;
         float2 ox[4], oy[4];
-        {
-            double v[2][NG + 3];
-#pragma unroll
-            for (int j = 0; j < NG + 3; j++) {
-                const float2 t = *reinterpret_cast<const float2 *>(D + (r + R - NG / 2 + j) * DW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
-#pragma unroll
-            for (int dr = 0; dr < 4; dr++) {
-                ox[dr].x = corr_regs<NG, 1>(v[0] + NG / 2 + dr, kg); ox[dr].y = corr_regs<NG, 1>(v[1] + NG / 2 + dr, kg);
-            }
-        }
-        {
-            double v[2][ND + 3];
-#pragma unroll
-            for (int j = 0; j < ND + 3; j++) {
-                const float2 t = *reinterpret_cast<const float2 *>(E + (r + R - ND / 2 + j) * DW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
-#pragma unroll
-            for (int dr = 0; dr < 4; dr++) {
-                oy[dr].x = corr_regs<ND, -1>(v[0] + ND / 2 + dr, kd); oy[dr].y = corr_regs<ND, -1>(v[1] + ND / 2 + dr, kd);
-            }
-        }
+        vgrad_2x4<NG, ND, DW, false>(D + (r + R - NG / 2) * DW + 2 * h, E + (r + R - ND / 2) * DW + 2 * h, kg, kd, ox, oy);
         const unsigned r_b0 = 3u * (tile_b0 + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // byte offset of (ty0 + r, x) in the records
 #pragma unroll
         for (int dr = 0; dr < 4; dr++) {
@@ -596,11 +667,7 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
 template <typename TIn, bool SMOOTH, int NS, int NG, int ND, int TH_, int NTHR = 256, bool HRED = false>
 __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradArgs a)
 {
-    constexpr int HB = HRED ? 12 : 4, rs = SMOOTH ? NS / 2 : 0, R = (NG > ND ? NG : ND) / 2;
-    constexpr int AW = TW + 2 * HB + 8, BW = TW + 2 * HB, DW = TW, IH = TH_ + 2 * R, RH = IH + 2 * rs;
-    constexpr int AC = SMOOTH ? (RH * AW > IH * BW ? RH * AW : IH * BW) : IH * BW;
-    constexpr int BDE = SMOOTH ? (RH * BW > 2 * IH * DW ? RH * BW : 2 * IH * DW) : 2 * IH * DW;
-    __shared__ __attribute__((aligned(16))) float lds[AC + BDE];
+    __shared__ __attribute__((aligned(16))) float lds[TileLds<SMOOTH, NS, NG, ND, TH_, HRED>::total];
     const int b = blockIdx.z;
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH_;
     const int nc = a.dim_c[b] ? a.dim_c[b] : a.ncols, nr = a.dim_r[b] ? a.dim_r[b] : a.nrows;
@@ -616,7 +683,8 @@ __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradA
 // `seg_h` rows of a 64-column strip in bands of SB output rows and computes every row of every stage once.  The tiled kernel computes
 // its vertical halo again in every tile (42 / 38 / 38 rows of stages 1 / 2 / 3 for 32 output rows); here the last NS - 1 horizontally
 // smoothed rows and the last 6 rows of the two gradient intermediates are carried to the next band, and the halo is paid once per
-// segment.  Same expressions, same operation order, same virtual coordinates as the tiled kernel (header of this file).
+// segment.  Same expressions and operation order as the tiled kernel (both call the stage primitives above), same virtual coordinates
+// (header of this file).
 //
 // Band with output rows [y, y + SB), cbase = y + 3 (frame row of C row 0):
 //   A  raw rows (f32)           A row i  = frame row cbase + rs + i        SB rows x AW      (region 1)
@@ -657,44 +725,12 @@ __device__ __forceinline__ void load_taps_here(TapRegs<NT> &r, const size_t arg_
 }
 
 // u8 frames: the raw rows of a steady band (A rows [0, SB), 4 bytes per quad) are requested one band ahead and stay in flight in three
-// registers while the band before runs its stages 1-4.  Edge bands read element by element through the reflect map (and wait for it).
-template <int NS>
-__device__ __forceinline__ void l0_fetch_u8(const uint8_t *raw, const int nc, const int nr, const int tx0, const int cbase, uint32_t (&w)[SB * (TW + 32) / 4 / 256])
-{
-    constexpr int AQ = (TW + 32) / 4, N0 = SB * AQ, U0 = N0 / 256;
-    static_assert(N0 % 256 == 0, "a steady band's quads are whole rounds of the workgroup");
-    const int ya = cbase + NS / 2, xa = tx0 - 16, tid = threadIdx.x;
-    if ((nc & 3) == 0 && xa >= 0 && xa + 4 * AQ <= nc && ya >= 0 && ya + SB <= nr) {
-        const plane_rsrc rawp = plane_of(raw);
-        const unsigned raw_b0 = (unsigned)ya * (unsigned)nc + (unsigned)xa;
-#pragma unroll
-        for (int u = 0; u < U0; u++) {
-            const int i = tid + u * 256;
-            w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, raw_b0 + __umul24((unsigned)(i / AQ), (unsigned)nc) + 4u * (unsigned)(i % AQ), 0, 0);
-        }
-    } else {
-        uint8_t e[U0][4];
-#pragma unroll
-        for (int u = 0; u < U0; u++) {
-            const int i = tid + u * 256;
-            const int y = ya + i / AQ, x = xa + 4 * (i % AQ);
-            const uint8_t *row = raw + (size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int xx = x + k;
-                e[u][k] = row[xx < 0 ? -1 - xx : xx >= nc ? 2 * nc - 1 - xx : xx];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U0; u++) w[u] = e[u][0] | (uint32_t)e[u][1] << 8 | (uint32_t)e[u][2] << 16 | (uint32_t)e[u][3] << 24;
-    }
-}
-
+// registers (`pre`) while the band before runs its stages 1-4.  Edge bands read element by element through the reflect map (and wait for it).
 template <typename TIn, int NS, bool ZC, bool EDGE, bool PRO>
 __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
                                                const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[SB * (TW + 32) / 4 / 256])
 {
-    constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead (l0_fetch_u8)
+    constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead
     STREAM_CLK_START;
     constexpr int NTHR = 256, NG = 7, ND = 7;
     using L = StreamLds<NS>;
@@ -714,70 +750,25 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     const TIn *__restrict__ raw = (const TIn *)a.raw[b];
     const unsigned row_bytes = 4u * (unsigned)nc;
     const unsigned band_b0 = (unsigned)cbase * row_bytes + 4u * (unsigned)tx0;   // byte offset of (cbase, tx0) in the f32 planes, mod 2^32
+    constexpr int X0 = -(HB + 4);                                // frame column of A column 0, relative to the strip
 
     // ---- stage 0: raw rows -> registers; (after the previous band's stage 4) -> A, carried rows into place
+    // (the host takes this kernel for frames of >= 2 strips and >= 64 rows: one reflection brings every index inside)
     {
-        constexpr int NA = SB - ALO, N0 = NA * AQ, U0 = (N0 + NTHR - 1) / NTHR, X0 = -(HB + 4);
-        const int ya = cbase + rs + ALO, xa = tx0 + X0;          // frame position of A (ALO, 0)
-        float4 v[U0];
-        const bool interior = (nc & 3) == 0 && xa >= 0 && xa + AW <= nc && ya >= 0 && ya + NA <= nr;
-        if (PF && !PRO) {
-            static_assert(!PF || PRO || U0 == sizeof(pre) / 4, "prefetched quads");
+        constexpr int NA = SB - ALO, N0 = NA * AQ, U0 = (N0 + NTHR - 1) / NTHR;
+        typename RawQuad<TIn>::reg w[U0];
+        if constexpr (PF && !PRO) {
+            static_assert(U0 == sizeof(pre) / 4, "prefetched quads");
 #pragma unroll
-            for (int u = 0; u < U0; u++) {
-                const uint32_t w = pre[u < int(sizeof(pre) / 4) ? u : 0];
-                v[u].x = (float)(w & 0xffu); v[u].y = (float)((w >> 8) & 0xffu);
-                v[u].z = (float)((w >> 16) & 0xffu); v[u].w = (float)(w >> 24);
-            }
-        } else if (interior) {
-            const plane_rsrc rawp = plane_of(raw);
-            const unsigned raw_b0 = ((unsigned)ya * (unsigned)nc + (unsigned)xa) * (unsigned)sizeof(TIn);
-            if (sizeof(TIn) == 1) {
-                uint32_t w[U0];
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = min(tid + u * NTHR, N0 - 1);
-                    w[u] = __builtin_amdgcn_raw_buffer_load_b32(rawp, raw_b0 + __umul24((unsigned)(i / AQ), (unsigned)nc) + 4u * (unsigned)(i % AQ), 0, 0);
-                }
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    v[u].x = (float)(w[u] & 0xffu); v[u].y = (float)((w[u] >> 8) & 0xffu);
-                    v[u].z = (float)((w[u] >> 16) & 0xffu); v[u].w = (float)(w[u] >> 24);
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < U0; u++) {
-                    const int i = min(tid + u * NTHR, N0 - 1);
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rawp, raw_b0 + __umul24((unsigned)(i / AQ), row_bytes) + 16u * (unsigned)(i % AQ), 0, 0);
-                    v[u] = __builtin_bit_cast(float4, q);
-                }
-            }
+            for (int u = 0; u < U0; u++) w[u] = pre[u];
         } else {
-            // bands at the frame's edges (the host takes this kernel for frames of >= 2 strips and >= 64 rows: one reflection
-            // brings every index inside)
-            TIn e[U0][4];
-#pragma unroll
-            for (int u = 0; u < U0; u++) {
-                const int i = min(tid + u * NTHR, N0 - 1);
-                const int y = ya + i / AQ, x = xa + 4 * (i % AQ);
-                const TIn *row = raw + (size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int xx = x + k;
-                    e[u][k] = row[xx < 0 ? -1 - xx : xx >= nc ? 2 * nc - 1 - xx : xx];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U0; u++) {
-                v[u].x = (float)e[u][0]; v[u].y = (float)e[u][1]; v[u].z = (float)e[u][2]; v[u].w = (float)e[u][3];
-            }
+            load_raw_block<TIn, NA, AQ, NTHR>(raw, nc, nr, cbase + rs + ALO, tx0 + X0, tid, w);
         }
         if (!PRO) __syncthreads();                               // the previous band's stage 4 has read DE
 #pragma unroll
         for (int u = 0; u < U0; u++) {
             const int i = tid + u * NTHR;
-            if (i < N0) *reinterpret_cast<float4 *>(A + ALO * AW + i * 4) = v[u];
+            if (i < N0) *reinterpret_cast<float4 *>(A + ALO * AW + i * 4) = quad_f32(w[u]);
         }
         if (!PRO) {
             // B rows [0, 2 rs) from Bc; DE rows [SB, SB + 6) -> [0, 6)
@@ -790,19 +781,18 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     }
     __syncthreads();
     STREAM_MARK(0);
-    if (PF && (PRO || cbase - 3 + SB < ylim)) l0_fetch_u8<NS>((const uint8_t *)raw, nc, nr, tx0, PRO ? s0 + 3 : cbase + SB, pre);
+    if constexpr (PF) {
+        static_assert((SB * AQ) % NTHR == 0, "a steady band's quads are whole rounds of the workgroup");
+        if (PRO || cbase - 3 + SB < ylim)                        // the A rows of the next steady band
+            load_raw_block<uint8_t, SB, AQ, NTHR>(raw, nc, nr, (PRO ? s0 + 3 : cbase + SB) + rs, tx0 + X0, threadIdx.x, pre);
+    }
     {
         TapRegs<NS> ks;
         load_taps_here(ks, offsetof(SmoothGradArgs, smooth.k));
         // ---- stage 1: horizontal smoothing, A -> B rows [BLO, SB + 2 rs)
         for (int i = tid; i < (SB + 2 * rs - BLO) * BQ; i += NTHR) {
             const int j = BLO + i / BQ, q = i % BQ;
-            double v[12];
-            widen12(A + (j - 2 * rs) * AW + 4 * q, v);
-            float4 o;
-            o.x = corr_regs<NS, 1>(v + 4, ks); o.y = corr_regs<NS, 1>(v + 5, ks);
-            o.z = corr_regs<NS, 1>(v + 6, ks); o.w = corr_regs<NS, 1>(v + 7, ks);
-            *reinterpret_cast<float4 *>(B + j * BW + 4 * q) = o;
+            *reinterpret_cast<float4 *>(B + j * BW + 4 * q) = hsmooth_quad<NS>(A + (j - 2 * rs) * AW + 4 * q, ks);
         }
         __syncthreads();
         STREAM_MARK(1);
@@ -811,19 +801,12 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         for (int i = (tid + NTHR / 4) & (NTHR - 1); i < G2 * BH; i += NTHR) {
             const int r = CLO + 4 * (i / BH), h = i % BH;
             double v[2][NS + 3];
-#pragma unroll
-            for (int j = 0; j < NS + 3; j++) {
-                const int rj = min(r + j, SB + 2 * rs - 1);      // rows past the band only feed outputs that are not made
-                const float2 t = *reinterpret_cast<const float2 *>(B + rj * BW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
+            widen_col_pair<NS + 3, BW>(B + r * BW + 2 * h, SB + 2 * rs - 1 - r, v);
 #pragma unroll
             for (int dr = 0; dr < 4; dr++) {
                 const int rr = r + dr;
                 if (rr >= SB) break;
-                float2 o;
-                o.x = corr_regs<NS, 1>(v[0] + rs + dr, ks); o.y = corr_regs<NS, 1>(v[1] + rs + dr, ks);
-                *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = o;
+                *reinterpret_cast<float2 *>(C + rr * BW + 2 * h) = corr_pair<NS, 1>(v, dr, ks);
             }
         }
         // the last 2 rs rows of B are the next band's first ones
@@ -840,13 +823,8 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         load_taps_here(kd, offsetof(SmoothGradArgs, gderiv.k));
         for (int i = (tid + NTHR / 2) & (NTHR - 1); i < (SB - CLO) * DQ; i += NTHR) {
             const int r = CLO + i / DQ, q = i % DQ;
-            double v[12];
-            widen12(C + r * BW + 4 * q + (HB - 4), v);
             float4 d, e;
-            d.x = corr_regs<ND, -1, ZC>(v + 4, kd); d.y = corr_regs<ND, -1, ZC>(v + 5, kd);
-            d.z = corr_regs<ND, -1, ZC>(v + 6, kd); d.w = corr_regs<ND, -1, ZC>(v + 7, kd);
-            e.x = corr_regs<NG, 1>(v + 4, kg); e.y = corr_regs<NG, 1>(v + 5, kg);
-            e.z = corr_regs<NG, 1>(v + 6, kg); e.w = corr_regs<NG, 1>(v + 7, kg);
+            hgrad_quad<NG, ND, ZC>(C + r * BW + 4 * q + (HB - 4), kg, kd, d, e);
             *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + 4 * q) = d;
             *reinterpret_cast<float4 *>(DE + (r + 6) * DEW + DW + 4 * q) = e;
         }
@@ -857,7 +835,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     {
         // ---- stage 3b: horizontal pass of the pyramid reduction at the columns 4x + 2 of the C rows of the segment (as in the tiled kernel)
         constexpr int NR = 21, HR = NR / 2;
-        TapRegs<HR + 1> kr;                                     // k[0..HR] (symmetric)
+        TapRegs<HR + 1> kr;
         load_taps_here(kr, offsetof(SmoothGradArgs, reduce.k));
         const plane_rsrc h1 = plane_of(a.h1[b]);
         const int h1_nc = a.h1_nc;
@@ -865,31 +843,21 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         for (int i = tid; i < (SB - CLO) * (DQ / 2); i += NTHR) {
             const int r = CLO + i / (DQ / 2), xs = 2 * (i % (DQ / 2));
             const int y = cbase + r;
-            typedef const volatile __attribute__((address_space(3))) f32x4 *lds_quad_ptr;
-            const lds_quad_ptr p = (lds_quad_ptr)(C + r * BW + 4 * xs + (HB - 8));
-            double v[28];
+            float o[2];
+            hreduce_pair<NR>(C + r * BW + 4 * xs + (HB - 8), kr, o);
 #pragma unroll
-            for (int u = 0; u < 7; u++) {
-                const f32x4 t = p[u];
-                v[4 * u] = (double)t.x; v[4 * u + 1] = (double)t.y; v[4 * u + 2] = (double)t.z; v[4 * u + 3] = (double)t.w;
-            }
-#pragma unroll
-            for (int o = 0; o < 2; o++) {
-                const double *c = v + HR + 4 * o;
-                double acc = c[0] * kr.k[HR];
-#pragma unroll
-                for (int jj = -HR; jj < 0; jj++) acc = acc + (c[jj] + c[-jj]) * kr.k[HR + jj];
-                const int xg = tx0 / 4 + xs + o;
+            for (int k = 0; k < 2; k++) {
+                const int xg = tx0 / 4 + xs + k;
                 if ((!PRO || y >= s0) && y < ylim && (!EDGE || xg < h1_nc))
-                    plane_store(h1, h1_b0 + __umul24((unsigned)r, h1_row_bytes) + 4u * (unsigned)(xs + o), (float)acc);
+                    plane_store(h1, h1_b0 + __umul24((unsigned)r, h1_row_bytes) + 4u * (unsigned)(xs + k), o[k]);
             }
         }
     }
     if (PRO) return;
     __syncthreads();
     STREAM_MARK(3);
-    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29): D -> gradx (Gaussian taps), E -> grady (derivative taps); the
-    // pixel records (image from C / Cc, gradx, grady) of two adjacent pixels go out together: 24 contiguous bytes
+    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29); the pixel records (image from C / Cc, gradx, grady) of two
+    // adjacent pixels go out together: 24 contiguous bytes
     TapRegs<NG> kg;
     TapRegs<ND> kd;
     load_taps_here(kg, offsetof(SmoothGradArgs, ggauss.k));
@@ -903,30 +871,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         const int x = tx0 + 2 * h;
         if ((EDGE && x >= nc) || (!full && y0 + r >= ylim)) continue;
         float2 ox[4], oy[4];
-        {
-            double v[2][NG + 3];
-#pragma unroll
-            for (int j = 0; j < NG + 3; j++) {
-                const float2 t = *reinterpret_cast<const float2 *>(DE + (r + j) * DEW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
-#pragma unroll
-            for (int dr = 0; dr < 4; dr++) {
-                ox[dr].x = corr_regs<NG, 1>(v[0] + NG / 2 + dr, kg); ox[dr].y = corr_regs<NG, 1>(v[1] + NG / 2 + dr, kg);
-            }
-        }
-        {
-            double v[2][ND + 3];
-#pragma unroll
-            for (int j = 0; j < ND + 3; j++) {
-                const float2 t = *reinterpret_cast<const float2 *>(DE + (r + j) * DEW + DW + 2 * h);
-                v[0][j] = (double)t.x; v[1][j] = (double)t.y;
-            }
-#pragma unroll
-            for (int dr = 0; dr < 4; dr++) {
-                oy[dr].x = corr_regs<ND, -1, ZC>(v[0] + ND / 2 + dr, kd); oy[dr].y = corr_regs<ND, -1, ZC>(v[1] + ND / 2 + dr, kd);
-            }
-        }
+        vgrad_2x4<NG, ND, DEW, ZC>(DE + r * DEW + 2 * h, DE + r * DEW + DW + 2 * h, kg, kd, ox, oy);
         const unsigned r_b0 = 3u * (band_b0 - 3u * row_bytes + __umul24((unsigned)r, row_bytes) + (unsigned)(8 * h));   // record of (y0 + r, x)
 #pragma unroll
         for (int dr = 0; dr < 4; dr++) {
@@ -1040,7 +985,7 @@ __global__ __launch_bounds__(NTHR) void pyr_reduce_fast(PyrReduceArgs a)
         for (int u = 0; u < EPT; u++) {
             const int i = min(tid + u * NTHR, NE - 1);
             const int y = gy0 + i / SW, x = gx0 + i % SW;
-            e[u] = src[(size_t)(y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y) * nc + (x < 0 ? -1 - x : x >= nc ? 2 * nc - 1 - x : x)];
+            e[u] = src[(size_t)reflect_once(y, nr) * nc + reflect_once(x, nc)];
         }
 #pragma unroll
         for (int u = 0; u < EPT; u++) {
@@ -1137,9 +1082,7 @@ __global__ __launch_bounds__(256) void pyr_vreduce_kernel(PyrReduceArgs a)
 #pragma unroll
         for (int u = 0; u < U; u++) {                            // clamped, unconditional; all loads in flight together
             const int rr = min((tid >> 6) + 4 * u, SH - 1);
-            int y = gy0 + rr;
-            y = y < 0 ? -1 - y : y >= nr ? 2 * nr - 1 - y : y;
-            y = min(max(y, 0), nr - 1);                          // (frames shorter than the halo never take this kernel)
+            const int y = min(max(reflect_once(gy0 + rr, nr), 0), nr - 1);   // (frames shorter than the halo never take this kernel)
             v[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(src, 4u * (__umul24((unsigned)y, (unsigned)nc) + (unsigned)col), 0, 0));
         }
 #pragma unroll
@@ -1201,14 +1144,20 @@ static int set_lds(K kernel, size_t lds)
     return 0;
 }
 
+// Do the register-blocked kernels take the 32-row tile for this launch?  Small launches take the 16-row tile so that the grid still covers
+// the chip.  KLT_RB_TH (16 or 32) overrides the choice: experiment hook.
+static bool rb_tall_tiles(const SmoothGradArgs &a, int batch)
+{
+    static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;
+    return force_th ? force_th == 32 : (long long)a.ncols * a.nrows * batch >= 1000000;
+}
+
 // kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image, gradients only, 3 = u8 image, gradients only
 // Is the fused horizontal reduction available for this launch?  (specialised taps, tall tiles, subsampling 4 with 21 taps,
 // frames tall enough that the vertical pass needs a single reflection)
 bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss)
 {
-    static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;
-    const bool tall = force_th ? force_th == 32 : (long long)a.ncols * a.nrows * batch >= 1000000;
-    return tall && kind < 2 && a.smooth.sym == 1 && (a.smooth.n == 5 || a.smooth.n == 9) &&
+    return rb_tall_tiles(a, batch) && kind < 2 && a.smooth.sym == 1 && (a.smooth.n == 5 || a.smooth.n == 9) &&
            a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && ss == 4 && reduce.sym == 1 && reduce.n == 21 &&
            a.nrows >= 64 && a.ncols >= 64;
 }
@@ -1242,62 +1191,54 @@ static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
     return kind == 0 && centre == 0 && sign_free(a.smooth) && sign_free(a.ggauss);
 }
 
+// The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
+template <typename TIn, bool SMOOTH, int NS>
+static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream)
+{
+    const dim3 blk(256);
+    const bool tall = rb_tall_tiles(a, batch);
+    const int th = tall ? 32 : 16;
+    const dim3 g((a.ncols + TW - 1) / TW, (a.nrows + th - 1) / th, batch);
+    if constexpr (SMOOTH) if (hred) {
+        // (28- / 24- / 20-row tiles -- 32.0 / 28.4 / 24.8 KB of LDS, five / five / six workgroups per CU -- were measured in
+        // round 2: 29.9 / 29.9 / 30.4 us event-timed against 28.1 for the 32-row tile: the extra halo work outweighs the occupancy)
+        // (three / two workgroups per CU instead of four -- dynamic LDS padding, same kernel -- read 0.0379 / 0.0382 ms per pair with
+        // three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
+        // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
+        // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
+        // frame, 1080p batches below 8) keep the tiled kernel, whose 32-row tiles fill the chip
+        const int sh = l0_stream_seg();
+        const dim3 gs((a.ncols + TW - 1) / TW, (a.nrows + sh - 1) / sh, batch);
+        if (stream && a.ncols >= 2 * TW && (long long)gs.x * gs.y * gs.z >= 2048) {
+            // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
+            if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
+                klt_launch((smooth_grad_stream<TIn, NS, true>), gs, blk, 0, s, a, sh);
+                return 0;
+            }
+            klt_launch((smooth_grad_stream<TIn, NS, false>), gs, blk, 0, s, a, sh);
+            return 0;
+        }
+        klt_launch((smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>), g, blk, 0, s, a);
+        return 0;
+    }
+    if (tall) klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 32>), g, blk, 0, s, a);
+    else klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 16>), g, blk, 0, s, a);
+    return 0;
+}
+
 int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream)
 {
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
     if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
-        const dim3 blk(256);
-        // register-blocked kernels; small frames take the shorter tile so that the grid still covers the chip
-        static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;   // experiment hook
-        const bool tall = force_th ? force_th == 32 : (long long)a.ncols * a.nrows * batch >= 1000000;
-        const int th = tall ? 32 : 16;
-        const dim3 g((a.ncols + TW - 1) / TW, (a.nrows + th - 1) / th, batch);
-#define KLT_RB(T, SM, NSV)                                                                                        \
-    do {                                                                                                          \
-        if (tall) klt_launch((smooth_grad_rb<T, SM, NSV, 7, 7, 32>), g, blk, 0, s, a);                   \
-        else klt_launch((smooth_grad_rb<T, SM, NSV, 7, 7, 16>), g, blk, 0, s, a);                        \
-        return 0;                                                                                                 \
-    } while (0)
-        if (hred) {
-            // (28- / 24- / 20-row tiles -- 32.0 / 28.4 / 24.8 KB of LDS, five / five / six workgroups per CU -- were measured in
-            // round 2: 29.9 / 29.9 / 30.4 us event-timed against 28.1 for the 32-row tile: the extra halo work outweighs the occupancy)
-            // (three / two workgroups per CU instead of four -- dynamic LDS padding, same kernel -- read 0.0379 / 0.0382 ms per pair with
-            // three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
-            // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
-            // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
-            // frame, 1080p batches below 8) keep the tiled kernel, whose 32-row tiles fill the chip
-            const int sh = l0_stream_seg();
-            const dim3 gs((a.ncols + TW - 1) / TW, (a.nrows + sh - 1) / sh, batch);
-            if (stream && a.ncols >= 2 * TW && (long long)gs.x * gs.y * gs.z >= 2048) {
-                const bool zc = deriv_centre_elidable(a, kind);
-#define KLT_L0S(T, NSV, ZCOK)                                                                                                      \
-    do {                                                                                                                       \
-        if (ZCOK && zc) klt_launch((smooth_grad_stream<T, NSV, ZCOK>), gs, blk, 0, s, a, sh);                                 \
-        else klt_launch((smooth_grad_stream<T, NSV, false>), gs, blk, 0, s, a, sh);                                           \
-        return 0;                                                                                                              \
-    } while (0)
-                // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
-                if (kind == 0 && a.smooth.n == 5) KLT_L0S(uint8_t, 5, true);
-                if (kind == 1 && a.smooth.n == 5) KLT_L0S(float, 5, false);
-                if (kind == 0 && a.smooth.n == 9) KLT_L0S(uint8_t, 9, true);
-                if (kind == 1 && a.smooth.n == 9) KLT_L0S(float, 9, false);
-#undef KLT_L0S
-                return -1;
-            }
-            if (kind == 0 && a.smooth.n == 5) { klt_launch((smooth_grad_rb<uint8_t, true, 5, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
-            if (kind == 1 && a.smooth.n == 5) { klt_launch((smooth_grad_rb<float, true, 5, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
-            if (kind == 0 && a.smooth.n == 9) { klt_launch((smooth_grad_rb<uint8_t, true, 9, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
-            if (kind == 1 && a.smooth.n == 9) { klt_launch((smooth_grad_rb<float, true, 9, 7, 7, 32, 256, true>), g, blk, 0, s, a); return 0; }
-            return -1;
-        }
-        if (kind == 0 && a.smooth.n == 5) KLT_RB(uint8_t, true, 5);
-        if (kind == 1 && a.smooth.n == 5) KLT_RB(float, true, 5);
-        if (kind == 0 && a.smooth.n == 9) KLT_RB(uint8_t, true, 9);
-        if (kind == 1 && a.smooth.n == 9) KLT_RB(float, true, 9);
-        if (kind == 2) KLT_RB(float, false, 1);
-        if (kind == 3) KLT_RB(uint8_t, false, 1);
-#undef KLT_RB
+        const int ns = smooth ? a.smooth.n : 1;
+        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream);
+        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream);
+        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream);
+        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream);
+        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream);
+        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream);
+        if (hred) return -1;                                     // (smooth_grad_hred_ok admits 5 and 9 smoothing taps only)
     }
     const size_t lds = smooth_grad_lds_bytes(smooth ? a.smooth.n / 2 : -1, a.R);
     const dim3 grid((a.ncols + TW - 1) / TW, (a.nrows + TH - 1) / TH, batch), block(256);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / SGPR / scratch of the kernels of one source file of csrc/, from the compiler's metadata of a fresh device-only compile
+"""VGPR / SGPR / scratch / static LDS of the kernels of one source file of csrc/, from the compiler's metadata of a fresh device-only compile
 (hipcc cross-compiles gfx950 without a GPU): `python tools/kernel_regs.py track_kernels.hip [name-filter]`."""
 import os
 import re
@@ -19,8 +19,11 @@ def kernel_regs(source, name_filter=""):
                         os.path.join(CSRC, source)], check=True, stderr=subprocess.DEVNULL)
         text = open(asm).read()
     out = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S):
-        name, body = m.group(1), m.group(2)
+    # one metadata entry per kernel, "  - .agpr_count: ..." up to the next one; the fields of an entry are in alphabetical order
+    # (.group_segment_fixed_size comes before .name)
+    kernels = text.split("amdhsa.kernels:", 1)[1].split("\namdhsa.", 1)[0]
+    for body in re.split(r"\n  - ", kernels)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", body).group(1)
         if name_filter not in name:
             continue
 
