@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define KLT_ABI_VERSION 11
+#define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points: klt_set_fb_params / klt_track_fb* are purely additive, no
+                                   * existing struct or signature moved; klt_params stays as it is) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
 
@@ -47,7 +48,8 @@ typedef enum {
 
 /* feature status codes, klt.py:23-29 (kltState) */
 enum { KLT_TRACKED = 0, KLT_NOT_FOUND = -1, KLT_SMALL_DET = -2, KLT_MAX_ITERATIONS = -3,
-       KLT_OOB = -4, KLT_LARGE_RESIDUE = -5 };
+       KLT_OOB = -4, KLT_LARGE_RESIDUE = -5,
+       KLT_FB_INCONSISTENT = -6 /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */ };
 
 /* selection modes, selectGoodFeatures.py:11-13 */
 enum { KLT_SELECTING_ALL = 1, KLT_REPLACING_SOME = 2 };
@@ -102,7 +104,7 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
  * them (one event each way per frame).  0 (default): one stream.  The caller must give frame t+1 a slot that no call still to be
  * enqueued reads (a ring of three slots for a sequence). */
 #define KLT_OPT_BUILD_STREAM 15
-#define KLT_OPT_TRACK_TREE_SUMS 18        /* 0 (default): the tracker adds its five window sums (and the residue) in the reference's order -- records identical to the reference's bit for bit; 1: butterfly sums in registers (7x7 / 15x15 quad kernels; same precision, other order of the additions): positions agree to 1e-3 px, a status word can differ where a feature sits on a threshold */
+#define KLT_OPT_TRACK_TREE_SUMS 18        /* (does not apply to klt_track_fb*, which always add in the reference's order) 0 (default): the tracker adds its five window sums (and the residue) in the reference's order -- records identical to the reference's bit for bit; 1: butterfly sums in registers (7x7 / 15x15 quad kernels; same precision, other order of the additions): positions agree to 1e-3 px, a status word can differ where a feature sits on a threshold */
 #define KLT_OPT_SCORE_SETS 16            /* how many sets of prepared selection scores (klt_select_prepare_async) the context keeps: 2 (default) .. 256; a selection frees the set it uses */
 /* 1 .. 8 (default 2; KLT_COPY_STREAMS in the environment sets the initial value): the copy streams consecutive klt_upload_u8_async calls
  * alternate between.  Two let the frames of a PAIR travel side by side (45 GB/s against 28-39 on one or three); a SEQUENCE loop -- one new
@@ -273,6 +275,26 @@ int klt_track(klt_ctx *ctx, int slot1, int slot2, klt_feat *inout, int n, int *n
  * pair i tracks feature buffer fb_in[i] (n records) from slot1[i] to slot2[i] into fb_out[i] */
 int klt_track_batch_async(klt_ctx *ctx, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out,
                           int npairs, int n);
+
+/* ---- forward-backward consistency check (not in the reference) ------------------------------------------ */
+/* Let T(a, b, list) be what klt_track_async(slot_a, slot_b, ...) gives for `list`.  fwd = T(1, 2, in); back = T(2, 1, fwd) (records of
+ * fwd with val < 0 pass through, as always).  A feature that was live in `in` and has fwd.val == KLT_TRACKED is CONSISTENT iff
+ * back.val == KLT_TRACKED and (double)dx*(double)dx + (double)dy*(double)dy <= (double)max_error*(double)max_error with the f32 differences
+ * dx = back.x - in.x, dy = back.y - in.y (exact products, one rounding in the sum).  out = fwd for a consistent feature (the whole record),
+ * (-1, -1, KLT_FB_INCONSISTENT, fwd.aux) for an inconsistent one, and exactly T(1, 2, in) for every other record.  One kernel launch does
+ * both descents of a feature; it always uses the reference-order window sums (KLT_OPT_TRACK_TREE_SUMS is not looked at), so `out` and
+ * `back` equal the composition of two default klt_track_async calls bit for bit, for every window and KLT_OPT_TRACK_VARIANT.
+ * Stateless; not offered together with the affine check (klt_track_affine_async is untouched). */
+typedef struct { int32_t enabled; float max_error; } klt_fb_params;
+/* max_error in pixels (default 1.0), negative or NaN: KLT_ERR_ARG.  `enabled` is kept for the host layer (the Python API reads the
+ * tracking context's flag); the klt_track_fb* calls below run the check whenever they are called. */
+int klt_set_fb_params(klt_ctx *ctx, const klt_fb_params *p);
+/* fb_back: feature buffer that receives `back` (n records), or -1.  fb_in, fb_out and fb_back must be pairwise distinct. */
+int klt_track_fb_async(klt_ctx *ctx, int slot1, int slot2, int fb_in, int fb_out, int n, int fb_back);
+int klt_track_fb(klt_ctx *ctx, int slot1, int slot2, klt_feat *inout, klt_feat *back_or_NULL, int n, int *n_tracked);
+/* npairs pairs in one launch (cf. klt_track_batch_async); fb_back may be NULL (no pair's backward records are kept) and single entries -1 */
+int klt_track_fb_batch_async(klt_ctx *ctx, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_back,
+                             int npairs, int n);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

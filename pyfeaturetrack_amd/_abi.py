@@ -35,6 +35,10 @@ class KltAffineParams(C.Structure):
                 ("max_residue", C.c_float), ("min_displacement", C.c_float), ("max_displacement_differ", C.c_float)]
 
 
+class KltFbParams(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("max_error", C.c_float)]
+
+
 class KltAffineRec(C.Structure):
     _fields_ = [("aff_x", C.c_float), ("aff_y", C.c_float), ("Axx", C.c_float), ("Ayx", C.c_float), ("Axy", C.c_float),
                 ("Ayy", C.c_float), ("valid", C.c_int32), ("pad", C.c_int32)]
@@ -110,6 +114,10 @@ SYMBOLS = {
     "klt_track_async": (_I, [_P, _I, _I, _I, _I, _I]),
     "klt_track": (_I, [_P, _I, _I, _P, _I, _PI]),
     "klt_track_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _I, _I]),
+    "klt_set_fb_params": (_I, [_P, C.POINTER(KltFbParams)]),
+    "klt_track_fb_async": (_I, [_P, _I, _I, _I, _I, _I, _I]),
+    "klt_track_fb": (_I, [_P, _I, _I, _P, _P, _I, _PI]),
+    "klt_track_fb_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

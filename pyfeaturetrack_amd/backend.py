@@ -11,9 +11,9 @@ import threading
 
 import numpy as np
 
-from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
+from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
                    KltTrackStats, load_library)
-from .params import affine_params_from_tc, params_from_tc, taps_from_params
+from .params import affine_params_from_tc, fb_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
 assert FEAT_DTYPE.itemsize == C.sizeof(KltFeat)
@@ -29,6 +29,7 @@ MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
 # feature buffers of the reference-shaped API (65534 / 65535 are the staging buffers of the synchronous klt_track / klt_select entry
 # points, 65533 the API's selection list, 60000 .. 65524 KLTTrackSequence's table rows)
 _FB_API_IN, _FB_API_OUT = 65526, 65527
+_FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
 
 
 def _dp(a):
@@ -101,6 +102,40 @@ class Context:
     def configure(self, tc):
         self.set_params(params_from_tc(tc))
         self.set_affine_params(affine_params_from_tc(tc))
+        fb = fb_params_from_tc(tc)
+        if fb.enabled:
+            self.set_fb_params(fb)
+
+    # ------------------------------------------- forward-backward consistency check
+    def set_fb_params(self, fb=None, max_error=None):
+        """klt_set_fb_params: `fb` a KltFbParams, or max_error alone"""
+        if fb is None:
+            fb = KltFbParams(1, float(max_error))
+        key = bytes(fb)
+        if key != getattr(self, "_fb_key", None):
+            self._check(self._lib.klt_set_fb_params(self._h, C.byref(fb)))
+            self._fb_key = key
+
+    def track_fb(self, slot1, slot2, fl, want_back=False):
+        """klt_track_fb on a copy: (records after the check, number still tracked[, backward records])."""
+        fl = np.ascontiguousarray(fl, FEAT_DTYPE).copy()
+        back = np.empty(len(fl), FEAT_DTYPE) if want_back else None
+        k = C.c_int()
+        self._check(self._lib.klt_track_fb(self._h, slot1, slot2, fl.ctypes.data, back.ctypes.data if want_back else None, len(fl),
+                                           C.byref(k)))
+        return (fl, k.value, back) if want_back else (fl, k.value)
+
+    def track_fb_async(self, slot1, slot2, fb_in, fb_out, n, fb_back=-1):
+        self._check(self._lib.klt_track_fb_async(self._h, slot1, slot2, fb_in, fb_out, n, fb_back))
+
+    def track_fb_batch_async(self, pairs, n):
+        """pairs: [(slot1, slot2, fb_in, fb_out[, fb_back]), ...] -- one forward-backward launch for all of them; without any fb_back
+        no backward records are kept."""
+        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(4)]
+        back = None
+        if any(len(p) > 4 for p in pairs):
+            back = (C.c_int * len(pairs))(*[p[4] if len(p) > 4 else -1 for p in pairs])
+        self._check(self._lib.klt_track_fb_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], back, len(pairs), n))
 
     # ------------------------------------------------ affine consistency check
     def set_affine_params(self, ap):
@@ -442,7 +477,7 @@ class Context:
             self._check(self._lib.klt_featbuf_map_host(self._h, fb_out, rout.ctypes.data, len(rout)))
             self._mapped_records = key
 
-    def track_enqueue(self, slot1, slot2, n, state=None, upload=True, fb_in=_FB_API_IN, fb_out=_FB_API_OUT):
+    def track_enqueue(self, slot1, slot2, n, state=None, upload=True, fb_in=_FB_API_IN, fb_out=_FB_API_OUT, fb_check=False):
         """The tracker is enqueued on the list in host_records(n)[0]; nothing is waited for.  With MAP_RECORDS (the default) the two
         feature buffers are those pinned arrays themselves and no copy is enqueued; otherwise the list goes up first (`upload`; not
         again when the tracker is only repeated on other pyramids)."""
@@ -450,7 +485,9 @@ class Context:
             self._map_records(n, fb_in, fb_out)
         elif upload:
             self._check(self._lib.klt_featbuf_upload_async(self._h, fb_in, self.host_records(n)[0].ctypes.data, n))
-        if state is None:
+        if fb_check:                       # forward-backward check (never with an affine state); the backward records stay on the device
+            self._check(self._lib.klt_track_fb_async(self._h, slot1, slot2, fb_in, fb_out, n, _FB_API_BACK))
+        elif state is None:
             self._check(self._lib.klt_track_async(self._h, slot1, slot2, fb_in, fb_out, n))
         else:
             self._check(self._lib.klt_track_affine_async(self._h, slot1, slot2, fb_in, fb_out, n, state))

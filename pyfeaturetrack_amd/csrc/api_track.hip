@@ -17,6 +17,13 @@ static void fill_track_params(const klt_ctx *c, const Slot *s1, TrackArgs &a, in
     a.tree_sums = c->track_tree_sums ? 1 : 0;
 }
 
+// the forward-backward launch on top (klt_track_fb*): the squared threshold as the kernels compare it
+static void fill_fb_params(const klt_ctx *c, TrackArgs &a)
+{
+    a.fb = 1;
+    a.fb_max_e2 = (double)c->fbp.max_error * (double)c->fbp.max_error;
+}
+
 // XCD-aware feature order (KLT_OPT_TRACK_XCD_ORDER): one permutation of 0..n-1 per pair of the launch.  It is only a locality
 // hint (any permutation tracks every feature exactly once), so it is recomputed when the shape of the launch changes and every
 // 64th launch (a sequence's features drift, and its lists alternate between two buffers); in between the stored one is reused.
@@ -87,21 +94,31 @@ static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv)
     }
 }
 
-int klt_track_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n)
+// klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1)
+static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, bool fb, int fb_back)
 {
     if (int rc = check_ready(c)) return rc;
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
+    if (fb && (fb_in == fb_out || (fb_back >= 0 && (fb_back == fb_in || fb_back == fb_out))))
+        return fail(c, KLT_ERR_ARG, "the forward-backward check needs fb_in, fb_out and fb_back pairwise distinct");
+    if (fb && fb_back < -1) return fail(c, KLT_ERR_ARG, "fb_back must be a feature buffer or -1");
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s1, *s2;
     if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
     if (fb_in < 0 || (size_t)fb_in >= c->fbs.size() || c->fbs[fb_in].cap < n) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
     FeatBuf *bo;
+    if (fb && fb_back >= 0)                                  // (may grow c->fbs: before any pointer into it is taken)
+        if (int rc = get_fb(c, fb_back, n > 0 ? n : 1, &bo)) return rc;
     if (int rc = get_fb(c, fb_out, n > 0 ? n : 1, &bo)) return rc;
     TrackArgs a;
     std::memset(&a, 0, sizeof(a));
     fill_levels(s1, s2, a.lv);
     a.in = c->fbs[fb_in].d; a.out = bo->d;
     fill_track_params(c, s1, a, n);
+    if (fb) {
+        fill_fb_params(c, a);
+        a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
+    }
     if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
     {
         const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
@@ -117,10 +134,36 @@ int klt_track_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int
     return KLT_OK;
 }
 
-int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, int npairs, int n)
+int klt_track_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n)
+{
+    return track_single(c, slot1, slot2, fb_in, fb_out, n, false, -1);
+}
+
+int klt_track_fb_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, int fb_back)
+{
+    return track_single(c, slot1, slot2, fb_in, fb_out, n, true, fb_back);
+}
+
+int klt_set_fb_params(klt_ctx *c, const klt_fb_params *p)
+{
+    if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
+    if (!(p->max_error >= 0.f)) return fail(c, KLT_ERR_ARG, "fb max_error must be a number >= 0");      // (NaN fails the comparison)
+    c->fbp = *p;
+    return KLT_OK;
+}
+
+// klt_track_batch_async (fb == false) and klt_track_fb_batch_async (fb == true; fb_back may be null)
+static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_back, int npairs,
+                       int n, bool fb)
 {
     if (int rc = check_ready(c)) return rc;
     if (!slot1 || !slot2 || !fb_in || !fb_out || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
+    if (fb)
+        for (int i = 0; i < npairs; i++) {
+            const int b = fb_back ? fb_back[i] : -1;
+            if (b < -1 || fb_in[i] == fb_out[i] || (b >= 0 && (b == fb_in[i] || b == fb_out[i])))
+                return fail(c, KLT_ERR_ARG, "the forward-backward check needs fb_in, fb_out and fb_back pairwise distinct");
+        }
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<TrackPairDesc> table((size_t)npairs);
     std::vector<Slot *> used;
@@ -128,6 +171,8 @@ int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const 
     for (int i = 0; i < npairs; i++) {
         FeatBuf *bo;                      // may grow c->fbs: do it before taking pointers into it
         if (int rc = get_fb(c, fb_out[i], n > 0 ? n : 1, &bo)) return rc;
+        if (fb && fb_back && fb_back[i] >= 0)
+            if (int rc = get_fb(c, fb_back[i], n > 0 ? n : 1, &bo)) return rc;
     }
     for (int i = 0; i < npairs; i++) {
         Slot *s1, *s2;
@@ -143,6 +188,7 @@ int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const 
         fill_levels(s1, s2, table[i].lv);
         table[i].in = c->fbs[fb_in[i]].d;
         table[i].out = c->fbs[fb_out[i]].d;
+        if (fb && fb_back && fb_back[i] >= 0) table[i].back = c->fbs[fb_back[i]].d;
     }
     // the descriptor table is uploaded only when none of the tables kept on the device holds it (found by hash; at most 256 tables,
     // the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order protects the
@@ -175,6 +221,7 @@ int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const 
     a.pairs = bt->dev;
     a.npairs = npairs;
     fill_track_params(c, first, a, n);
+    if (fb) fill_fb_params(c, a);
     {
         // one permutation per pair, kept with the set of input lists (see set_track_order)
         std::vector<const klt_feat *> ins((size_t)npairs);
@@ -193,12 +240,40 @@ int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const 
     return KLT_OK;
 }
 
+int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, int npairs, int n)
+{
+    return track_batch(c, slot1, slot2, fb_in, fb_out, nullptr, npairs, n, false);
+}
+
+int klt_track_fb_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_back,
+                             int npairs, int n)
+{
+    return track_batch(c, slot1, slot2, fb_in, fb_out, fb_back, npairs, n, true);
+}
+
 int klt_track(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int *n_tracked)
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
     const int fi = 65534, fo = 65535;
     if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: `inout` is ours until then)
     if (int rc = klt_track_async(c, slot1, slot2, fi, fo, n)) return rc;
+    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
+    if (n_tracked) {
+        int k = 0;
+        for (int i = 0; i < n; i++) k += inout[i].val >= 0;
+        *n_tracked = k;
+    }
+    return KLT_OK;
+}
+
+int klt_track_fb(klt_ctx *c, int slot1, int slot2, klt_feat *inout, klt_feat *back, int n, int *n_tracked)
+{
+    if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
+    const int fi = 65534, fo = 65535, fbk = 65532;
+    if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;
+    if (int rc = klt_track_fb_async(c, slot1, slot2, fi, fo, n, back ? fbk : -1)) return rc;
+    if (back)
+        if (int rc = klt_featbuf_download(c, fbk, back, n)) return rc;
     if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
     if (n_tracked) {
         int k = 0;

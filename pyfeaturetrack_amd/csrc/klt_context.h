@@ -234,6 +234,7 @@ struct klt_ctx {
     uint64_t batch_clock = 0;
     static constexpr size_t kBatchTables = 256, kBatchOrders = 128;
     klt_affine_params ap{-1, 15, 15, 10, 10.f, 0.02f, 1.5f};      // klt.py:67-73 defaults
+    klt_fb_params fbp{0, 1.0f};                                    // forward-backward check (klt_set_fb_params)
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;

@@ -56,9 +56,13 @@ struct TrackPairDesc {
     TrackLevel lv[KLT_MAX_LEVELS];
     const klt_feat *in;
     klt_feat *out;
+    klt_feat *back;                     // forward-backward launches: the backward records of the pair, or null (last: the offsets above stay)
 };
 
-struct TrackArgs {
+// The kernel argument of the plain tracker kernels.  Its layout is what their register allocation was measured with (the compiler widens
+// scalar loads up to the end of the kernarg segment: a longer struct moved SGPR counts, a VGPR and 12 bytes of scratch), so what the
+// forward-backward kernels need on top lives in TrackArgs below and the plain kernels never see it.
+struct TrackArgsBase {
     TrackLevel lv[KLT_MAX_LEVELS];      // single-pair launch: levels travel in the kernarg segment
     const klt_feat *in;
     klt_feat *out;
@@ -73,6 +77,14 @@ struct TrackArgs {
     int n, nlevels, window, max_iterations, use_max_residue, retain, ncols, nrows;
     float small, th, step, max_residue, ss, inv_ss;
     int tree_sums;               // KLT_OPT_TRACK_TREE_SUMS: the quad kernels add the five sums (and the residue) by a butterfly in registers
+};
+
+// A tracker launch as the API describes it, and the kernel argument of the forward-backward kernels (klt_track_fb_async; DESIGN.md
+// section 9a)
+struct TrackArgs : TrackArgsBase {
+    int fb;                      // 1: the fused forward-backward kernels (always the reference-order sums: tree_sums is not looked at)
+    klt_feat *back;              // single-pair launch: the backward records, or null
+    double fb_max_e2;            // (double)max_error * (double)max_error: a feature is consistent when its round trip ends within it
 };
 
 struct AffineArgs {

@@ -18,6 +18,7 @@
 // position updates, the in-loop bounds test with the integer half-window and the post-loop one with
 // the Python-3 float half-window.
 #include <cstdlib>
+#include <type_traits>
 
 #include "klt_internal.h"
 
@@ -130,13 +131,23 @@ __device__ __forceinline__ TrackLevel load_level(const TrackLevel *p)
     return lv;
 }
 
+// the level with the two frames in each other's place
+__device__ __forceinline__ TrackLevel exchanged(const TrackLevel &l)
+{
+    TrackLevel e;
+    e.i1 = l.i2; e.gx1 = l.gx2; e.gy1 = l.gy2;
+    e.i2 = l.i1; e.gx2 = l.gx1; e.gy2 = l.gy1;
+    e.nc = l.nc; e.nr = l.nr;
+    return e;
+}
+
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // _trackFeature for one level.  Returns the status; x2/y2 updated in place; `iters` = Newton iterations.
 // WCT > 0: window size known at compile time (index math folds, the summation loops unroll and read LDS
 // 16 bytes at a time); WCT == 0: any odd window up to 31.
 template <int MAXK, int WCT>
-__device__ int track_level(const TrackArgs &a, const TrackLevel &lv, float x1, float y1, float &x2r, float &y2r,
+__device__ int track_level(const TrackArgsBase &a, const TrackLevel &lv, float x1, float y1, float &x2r, float &y2r,
                            float *lds, int lane, int &iters, int clk0 = 0)
 {
     const int w = WCT > 0 ? WCT : a.window, n = w * w, hw = w / 2;
@@ -264,8 +275,42 @@ __device__ int track_level(const TrackArgs &a, const TrackLevel &lv, float x1, f
     return KLT_TRACKED;
 }
 
-template <int MAXK, int WCT, bool BATCH>
-__global__ __launch_bounds__(64) void track_kernel(TrackArgs a)
+// The record a feature ends with, from the status of the last level it visited and its level-0 position (trackFeatures.py:288-308)
+__device__ __forceinline__ klt_feat track_record(const TrackArgsBase &a, int val, float xout, float yout, uint32_t aux)
+{
+    klt_feat o;
+    o.aux = (int32_t)aux;
+    const double xd = (double)xout, yd = (double)yout;
+    const bool oob = val == KLT_OOB ||
+                     xd < a.borderx || xd > (double)(a.ncols - 1) - a.borderx ||
+                     yd < a.bordery || yd > (double)(a.nrows - 1) - a.bordery;   // :288-308
+    if (oob) { o.x = -1.f; o.y = -1.f; o.val = KLT_OOB; }
+    else if (val == KLT_SMALL_DET || val == KLT_LARGE_RESIDUE || val == KLT_MAX_ITERATIONS) {
+        o.x = -1.f; o.y = -1.f; o.val = val;
+    } else { o.x = xout; o.y = yout; o.val = KLT_TRACKED; }
+    return o;
+}
+
+// Forward-backward rule (klt_gpu.h, klt_track_fb_async) for a feature that the forward pass tracked: `ft` the input record, `fwd` the
+// forward record, `back` what the tracker gives for `fwd` with the two frames exchanged.  The round trip's error is formed from the f32
+// differences; their squares are exact in FP64 and the sum rounds once (explicit round-to-nearest operations: nothing to contract).
+__device__ __forceinline__ klt_feat fb_record(double max_e2, const klt_feat &ft, const klt_feat &fwd, const klt_feat &back)
+{
+    const float dx = back.x - ft.x, dy = back.y - ft.y;
+    const double e2 = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy));
+    if (back.val == KLT_TRACKED && e2 <= max_e2) return fwd;
+    klt_feat o;
+    o.x = -1.f; o.y = -1.f; o.val = KLT_FB_INCONSISTENT; o.aux = fwd.aux;
+    return o;
+}
+
+// FB: the forward-backward check in the same launch -- the feature's wavefront descends the pyramids from frame 1 into frame 2 and, if
+// that tracked it, once more from there with the two frames exchanged; one `out` record (and one `back` record if asked) per feature.
+template <bool FB>
+using TrackKernArgs = std::conditional_t<FB, TrackArgs, TrackArgsBase>;
+
+template <int MAXK, int WCT, bool BATCH, bool FB = false>
+__global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB> a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int f = blockIdx.x;
@@ -282,40 +327,59 @@ __global__ __launch_bounds__(64) void track_kernel(TrackArgs a)
     const TrackLevel *levels = BATCH ? a.pairs[blockIdx.y].lv : a.lv;
     const klt_feat *fin = BATCH ? a.pairs[blockIdx.y].in : a.in;
     klt_feat *fout = BATCH ? a.pairs[blockIdx.y].out : a.out;
+    klt_feat *fback = nullptr;
+    if constexpr (FB) fback = BATCH ? a.pairs[blockIdx.y].back : a.back;
     const klt_feat ft = fin[f];
     if (ft.val < 0) {                       // only live features are tracked, trackFeatures.py:253
-        if (lane == 0) fout[f] = ft;
+        if (lane == 0) {
+            fout[f] = ft;
+            if (FB && fback) fback[f] = ft;
+        }
         return;
     }
     const int L = a.nlevels;
     TCLK(0);
-    // trackFeatures.py:255-265: position at the coarsest resolution (divisions by a power of two: exact)
-    float xloc = ft.x, yloc = ft.y;
-    for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }   // power of two: exact
-    float xout = xloc, yout = yloc;
-    int val = KLT_TRACKED;
-    uint32_t aux = 0;       // 4 bits per level: 0 = level not visited, v = v-1 Newton iterations (saturating at 14)
-    for (int r = L - 1; r >= 0; r--) {
-        xloc = xloc * a.ss; yloc = yloc * a.ss; xout = xout * a.ss; yout = yout * a.ss;
-        int it = 0;
-        const TrackLevel lv = BATCH ? load_level(levels + r) : levels[r];
-        val = track_level<MAXK, WCT>(a, lv, xloc, yloc, xout, yout, lds, lane, it, 1 + 9 * (L - 1 - r));
-        aux |= (uint32_t)(it < 14 ? it + 1 : 15) << (4 * r);      // visited level r with `it` Newton iterations
-        if (val == KLT_SMALL_DET || val == KLT_OOB) break;             // :284-285
-    }
-    if (lane == 0) {
-        klt_feat o;
-        o.aux = (int32_t)aux;
-        const double xd = (double)xout, yd = (double)yout;
-        const bool oob = val == KLT_OOB ||
-                         xd < a.borderx || xd > (double)(a.ncols - 1) - a.borderx ||
-                         yd < a.bordery || yd > (double)(a.nrows - 1) - a.bordery;   // :288-308
-        if (oob) { o.x = -1.f; o.y = -1.f; o.val = KLT_OOB; }
-        else if (val == KLT_SMALL_DET || val == KLT_LARGE_RESIDUE || val == KLT_MAX_ITERATIONS) {
-            o.x = -1.f; o.y = -1.f; o.val = val;
-        } else { o.x = xout; o.y = yout; o.val = KLT_TRACKED; }
-        fout[f] = o;
-    }
+    float xstart = ft.x, ystart = ft.y;     // FB, second pass: the forward result
+    klt_feat fwd = ft;
+    // (a do-while whose condition is constant false without FB: the plain kernels are compiled with no loop here at all -- as a counted
+    // loop of one round it moved their register figures)
+    int pass = 0;
+    do {
+        // trackFeatures.py:255-265: position at the coarsest resolution (divisions by a power of two: exact)
+        float xloc = xstart, yloc = ystart;
+        for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }   // power of two: exact
+        float xout = xloc, yout = yloc;
+        int val = KLT_TRACKED;
+        uint32_t aux = 0;       // 4 bits per level: 0 = level not visited, v = v-1 Newton iterations (saturating at 14)
+        for (int r = L - 1; r >= 0; r--) {
+            xloc = xloc * a.ss; yloc = yloc * a.ss; xout = xout * a.ss; yout = yout * a.ss;
+            int it = 0;
+            const TrackLevel lvf = BATCH ? load_level(levels + r) : levels[r];
+            const TrackLevel lv = FB && pass ? exchanged(lvf) : lvf;       // backward: frame 2 holds the template, frame 1 is searched
+            val = track_level<MAXK, WCT>(a, lv, xloc, yloc, xout, yout, lds, lane, it, 1 + 9 * (L - 1 - r));
+            aux |= (uint32_t)(it < 14 ? it + 1 : 15) << (4 * r);      // visited level r with `it` Newton iterations
+            if (val == KLT_SMALL_DET || val == KLT_OOB) break;             // :284-285
+        }
+        if constexpr (!FB) {
+            if (lane == 0) fout[f] = track_record(a, val, xout, yout, aux);
+        } else {
+            const klt_feat o = track_record(a, val, xout, yout, aux);      // wavefront-uniform
+            if (pass == 0) {
+                fwd = o;
+                if (o.val != KLT_TRACKED) {                                // lost on the way forward: the plain tracker's record, both ways
+                    if (lane == 0) {
+                        fout[f] = o;
+                        if (fback) fback[f] = o;
+                    }
+                    return;
+                }
+                xstart = o.x; ystart = o.y;
+            } else if (lane == 0) {
+                fout[f] = fb_record(a.fb_max_e2, ft, fwd, o);
+                if (fback) fback[f] = o;
+            }
+        }
+    } while (FB && ++pass < 2);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -440,10 +504,13 @@ __device__ __forceinline__ float group_tree_sum(float v)
     return v;
 }
 
-template <bool BATCH, int W, int WAVES = 1, bool TREE = false>
-__global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
+// FB: the forward-backward check in the same launch (see track_kernel).  A lane group whose feature is not tracked back -- not live, or
+// lost on the way forward -- idles through the second pass under the predicate that masks a finished feature in the first.
+template <bool BATCH, int W, int WAVES = 1, bool TREE = false, bool FB = false>
+__global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB> a)
 {
     static_assert(W == 7 || W == 15, "quad kernels exist for 7x7 and 15x15 windows");
+    static_assert(!(FB && TREE), "the forward-backward check uses the reference-order sums");
     constexpr int FPW = W == 7 ? 4 : 1;                      // features per wavefront
     constexpr int LPF = 64 / FPW;                            // lanes per feature = quads of its footprint
     constexpr int QPR = (W + 1) / 4;                         // quads per footprint row
@@ -464,10 +531,15 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
     const TrackLevel *levels = BATCH ? a.pairs[blockIdx.y].lv : a.lv;
     const klt_feat *fin = BATCH ? a.pairs[blockIdx.y].in : a.in;
     klt_feat *fout = BATCH ? a.pairs[blockIdx.y].out : a.out;
+    klt_feat *fback = nullptr;
+    if constexpr (FB) fback = BATCH ? a.pairs[blockIdx.y].back : a.back;
     const bool valid = f < a.n;
     const klt_feat ft = fin[valid ? f : a.n - 1];
     const bool tracked_feature = valid && ft.val >= 0;       // only live features are tracked, trackFeatures.py:253
-    if (valid && ft.val < 0 && s == 0) fout[f] = ft;
+    if (valid && ft.val < 0 && s == 0) {
+        fout[f] = ft;
+        if (FB && fback) fback[f] = ft;
+    }
     if (!__any(tracked_feature)) return;
     const int L = a.nlevels;
     float *const gl = lds + g * 5 * npad;                    // this feature's five product arrays
@@ -475,218 +547,246 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackArgs a)
     const int k0 = qr * w + 4 * qh;                          // window index of my first sample (qr, 4 qh)
     const float one_plus_eps = 1.001f;
 
-    // trackFeatures.py:255-265
-    float xloc = ft.x, yloc = ft.y;
-    for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }
-    float xout = xloc, yout = yloc;
-    int val = KLT_TRACKED;
-    uint32_t aux = 0;
-    bool alive = tracked_feature;                            // still descending the pyramid
+    bool go = tracked_feature;                               // the feature takes part in the pass
+    float xstart = ft.x, ystart = ft.y;                      // FB, second pass: the forward result
+    klt_feat fwd = ft, bwd = ft;
+    // (a do-while whose condition is constant false without FB: the plain kernels are compiled with no loop here at all -- as a counted
+    // loop of one round it moved their register figures)
+    int pass = 0;
+    do {
+        // trackFeatures.py:255-265
+        float xloc = xstart, yloc = ystart;
+        for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }
+        float xout = xloc, yout = yloc;
+        int val = KLT_TRACKED;
+        uint32_t aux = 0;
+        bool alive = go;                                         // still descending the pyramid
 
-    for (int r = L - 1; r >= 0; r--) {
-        if (!__any(alive)) break;
-        const TrackLevel lv = BATCH ? load_level(levels + r) : levels[r];
-        const int nc = lv.nc, nr = lv.nr;
-        if (alive) { xloc = xloc * a.ss; yloc = yloc * a.ss; xout = xout * a.ss; yout = yout * a.ss; }
+        for (int r = L - 1; r >= 0; r--) {
+            if (!__any(alive)) break;
+            const TrackLevel lvf = BATCH ? load_level(levels + r) : levels[r];
+            const TrackLevel lv = FB && pass ? exchanged(lvf) : lvf;       // backward: frame 2 holds the template, frame 1 is searched
+            const int nc = lv.nc, nr = lv.nr;
+            if (alive) { xloc = xloc * a.ss; yloc = yloc * a.ss; xout = xout * a.ss; yout = yout * a.ss; }
 
-        // image-1 template (trackFeatures.py:102-104); a window that leaves image 1 ends the feature
-        const Bilinear b1 = make_bilinear(xloc, yloc);
-        const bool t_ok = b1.ix - hw >= 0 && b1.iy - hw >= 0 && b1.ix + hw + 2 <= nc && b1.iy + hw + 2 <= nr;
-        const bool run = alive && t_ok;
-        // (row * nc as a 24-bit multiply: both are far below 2^24, and the 32-bit integer multiply is a quarter-rate instruction)
-        const unsigned q1 = run ? __umul24((unsigned)(b1.iy - hw + qr), (unsigned)nc) + (unsigned)(b1.ix - hw + 4 * qh) : 0u;   // 32-bit element offsets: scalar base + vector offset loads
-        f32x4 t_qi, t_qgx, t_qgy;
-        load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
+            // image-1 template (trackFeatures.py:102-104); a window that leaves image 1 ends the feature
+            const Bilinear b1 = make_bilinear(xloc, yloc);
+            const bool t_ok = b1.ix - hw >= 0 && b1.iy - hw >= 0 && b1.ix + hw + 2 <= nc && b1.iy + hw + 2 <= nr;
+            const bool run = alive && t_ok;
+            // (row * nc as a 24-bit multiply: both are far below 2^24, and the 32-bit integer multiply is a quarter-rate instruction)
+            const unsigned q1 = run ? __umul24((unsigned)(b1.iy - hw + qr), (unsigned)nc) + (unsigned)(b1.ix - hw + 4 * qh) : 0u;   // 32-bit element offsets: scalar base + vector offset loads
+            f32x4 t_qi, t_qgx, t_qgy;
+            load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
 
-        // the first Newton iteration starts from a position that is already known: its bounds test (trackFeaturesUtils.pyx:428-431)
-        // and its footprint loads go out now, behind the template's
-        int it = 0, status = KLT_OOB;
-        float x2 = xout, y2 = yout;
-        bool iterating = run;
-        Bilinear b2;
-        f32x4 s_qi = {0.f, 0.f, 0.f, 0.f}, s_qgx = s_qi, s_qgy = s_qi;
-        unsigned q_held = ~0u;                               // element offset of the footprint quads in s_q*: none of this level yet
-        // A Newton step usually moves the window by less than a pixel: when its integer corner stays where it was, the footprint is
-        // the one already in registers (only the bilinear weights change) and nothing is requested; neither is anything for a
-        // feature that has stopped.  The launch is bound by the L1's requests to the L2 in flight (tools/pmc_mem.sh: ~78 per CU
-        // all the time at ~750 clocks each), so a request not made is time saved: 89.2 -> 86.6 us per eight-pair launch of cfg-2,
-        // 131.6 -> 125.7 us at cfg-4.  7x7 only: the 15x15 kernel, at its occupancy target of five, pays for the held offset and the
-        // conditional loads with 16 more bytes of scratch and goes from 38.9 to 42.4 us at cfg-3.
-        auto request_footprint = [&]() {
-            const bool oob = (double)(x2 - (float)hw) < 0. || (float)nc - (x2 + (float)hw) < one_plus_eps ||
-                             (double)(y2 - (float)hw) < 0. || (float)nr - (y2 + (float)hw) < one_plus_eps;
-            if (iterating && oob) { status = KLT_OOB; iterating = false; }
-            b2 = make_bilinear(x2, y2);
-            if (REUSE) {
-                const unsigned q = __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh);
-                if (iterating && q != q_held) {
-                    load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
-                    q_held = q;
-                }
-            } else {
-                const unsigned q = iterating ? __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh) : 0u;
-                load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
-            }
-        };
-        request_footprint();
-
-        float t_i[4], t_gx[4], t_gy[4];
-        sample_quad<QPR>(t_qi, b1, t_i);
-        sample_quad<QPR>(t_qgx, b1, t_gx);
-        sample_quad<QPR>(t_qgy, b1, t_gy);
-
-        while (__any(iterating)) {
-            const bool act = iterating;
-            float s_i[4], s_gx[4], s_gy[4];
-            sample_quad<QPR>(s_qi, b2, s_i);
-            sample_quad<QPR>(s_qgx, b2, s_gx);
-            sample_quad<QPR>(s_qgy, b2, s_gy);
-            float tree[5] = {0.f, 0.f, 0.f, 0.f, 0.f};     // TREE: this lane's share of the five sums (its samples inside the window)
-#pragma unroll
-            for (int m = 0; m < 4; m++) {
-                if (qr < w && 4 * qh + m < w) {
-                    const int k = k0 + m;
-                    const float diff = t_i[m] - s_i[m];
-                    const float sx = t_gx[m] + s_gx[m];
-                    const float sy = t_gy[m] + s_gy[m];
-                    if (TREE) {
-                        tree[0] = tree[0] + sx * sx;
-                        tree[1] = tree[1] + sx * sy;
-                        tree[2] = tree[2] + sy * sy;
-                        tree[3] = tree[3] + diff * sx;
-                        tree[4] = tree[4] + diff * sy;
-                    } else {
-                        gl[k] = sx * sx;
-                        gl[npad + k] = sx * sy;
-                        gl[2 * npad + k] = sy * sy;
-                        gl[3 * npad + k] = diff * sx;
-                        gl[4 * npad + k] = diff * sy;
-                    }
-                }
-            }
-            if (!TREE) wave_lds_sync();
-            float acc = 0.f;
-            if (!TREE && s < 5) {
-                const float4 *T4 = reinterpret_cast<const float4 *>(gl + s * npad);
-                if (W > 8) {
-                    // 15x15: whole quads without a test, the n % 4 tail on its own -- with the tests inside the partly unrolled loop every
-                    // quad paid three scalar compares and branches (13 M scalar next to 20 M vector instructions per launch): 49.0 -> 38.5 us
-#pragma unroll 8
-                    for (int q = 0; q < n / 4; q++) {
-                        const float4 v = T4[q];
-                        acc = acc + v.x;
-                        acc = acc + v.y;
-                        acc = acc + v.z;
-                        acc = acc + v.w;
-                    }
-                    if (n % 4) {
-                        const float4 v = T4[n / 4];
-                        acc = acc + v.x;
-                        if (n % 4 > 1) acc = acc + v.y;
-                        if (n % 4 > 2) acc = acc + v.z;
+            // the first Newton iteration starts from a position that is already known: its bounds test (trackFeaturesUtils.pyx:428-431)
+            // and its footprint loads go out now, behind the template's
+            int it = 0, status = KLT_OOB;
+            float x2 = xout, y2 = yout;
+            bool iterating = run;
+            Bilinear b2;
+            f32x4 s_qi = {0.f, 0.f, 0.f, 0.f}, s_qgx = s_qi, s_qgy = s_qi;
+            unsigned q_held = ~0u;                               // element offset of the footprint quads in s_q*: none of this level yet
+            // A Newton step usually moves the window by less than a pixel: when its integer corner stays where it was, the footprint is
+            // the one already in registers (only the bilinear weights change) and nothing is requested; neither is anything for a
+            // feature that has stopped.  The launch is bound by the L1's requests to the L2 in flight (tools/pmc_mem.sh: ~78 per CU
+            // all the time at ~750 clocks each), so a request not made is time saved: 89.2 -> 86.6 us per eight-pair launch of cfg-2,
+            // 131.6 -> 125.7 us at cfg-4.  7x7 only: the 15x15 kernel, at its occupancy target of five, pays for the held offset and the
+            // conditional loads with 16 more bytes of scratch and goes from 38.9 to 42.4 us at cfg-3.
+            auto request_footprint = [&]() {
+                const bool oob = (double)(x2 - (float)hw) < 0. || (float)nc - (x2 + (float)hw) < one_plus_eps ||
+                                 (double)(y2 - (float)hw) < 0. || (float)nr - (y2 + (float)hw) < one_plus_eps;
+                if (iterating && oob) { status = KLT_OOB; iterating = false; }
+                b2 = make_bilinear(x2, y2);
+                if (REUSE) {
+                    const unsigned q = __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh);
+                    if (iterating && q != q_held) {
+                        load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
+                        q_held = q;
                     }
                 } else {
-                    // 7x7: the 13 quads are unrolled completely and the tests fold (the peeled form measured 0.4 us slower here)
-#pragma unroll 16
-                    for (int q = 0; q < (n + 3) / 4; q++) {
-                        const float4 v = T4[q];
-                        acc = acc + v.x;
-                        if (4 * q + 1 < n) acc = acc + v.y;
-                        if (4 * q + 2 < n) acc = acc + v.z;
-                        if (4 * q + 3 < n) acc = acc + v.w;
+                    const unsigned q = iterating ? __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh) : 0u;
+                    load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
+                }
+            };
+            request_footprint();
+
+            float t_i[4], t_gx[4], t_gy[4];
+            sample_quad<QPR>(t_qi, b1, t_i);
+            sample_quad<QPR>(t_qgx, b1, t_gx);
+            sample_quad<QPR>(t_qgy, b1, t_gy);
+
+            while (__any(iterating)) {
+                const bool act = iterating;
+                float s_i[4], s_gx[4], s_gy[4];
+                sample_quad<QPR>(s_qi, b2, s_i);
+                sample_quad<QPR>(s_qgx, b2, s_gx);
+                sample_quad<QPR>(s_qgy, b2, s_gy);
+                float tree[5] = {0.f, 0.f, 0.f, 0.f, 0.f};     // TREE: this lane's share of the five sums (its samples inside the window)
+    #pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    if (qr < w && 4 * qh + m < w) {
+                        const int k = k0 + m;
+                        const float diff = t_i[m] - s_i[m];
+                        const float sx = t_gx[m] + s_gx[m];
+                        const float sy = t_gy[m] + s_gy[m];
+                        if (TREE) {
+                            tree[0] = tree[0] + sx * sx;
+                            tree[1] = tree[1] + sx * sy;
+                            tree[2] = tree[2] + sy * sy;
+                            tree[3] = tree[3] + diff * sx;
+                            tree[4] = tree[4] + diff * sy;
+                        } else {
+                            gl[k] = sx * sx;
+                            gl[npad + k] = sx * sy;
+                            gl[2 * npad + k] = sy * sy;
+                            gl[3 * npad + k] = diff * sx;
+                            gl[4 * npad + k] = diff * sy;
+                        }
                     }
                 }
+                if (!TREE) wave_lds_sync();
+                float acc = 0.f;
+                if (!TREE && s < 5) {
+                    const float4 *T4 = reinterpret_cast<const float4 *>(gl + s * npad);
+                    if (W > 8) {
+                        // 15x15: whole quads without a test, the n % 4 tail on its own -- with the tests inside the partly unrolled loop every
+                        // quad paid three scalar compares and branches (13 M scalar next to 20 M vector instructions per launch): 49.0 -> 38.5 us
+    #pragma unroll 8
+                        for (int q = 0; q < n / 4; q++) {
+                            const float4 v = T4[q];
+                            acc = acc + v.x;
+                            acc = acc + v.y;
+                            acc = acc + v.z;
+                            acc = acc + v.w;
+                        }
+                        if (n % 4) {
+                            const float4 v = T4[n / 4];
+                            acc = acc + v.x;
+                            if (n % 4 > 1) acc = acc + v.y;
+                            if (n % 4 > 2) acc = acc + v.z;
+                        }
+                    } else {
+                        // 7x7: the 13 quads are unrolled completely and the tests fold (the peeled form measured 0.4 us slower here)
+    #pragma unroll 16
+                        for (int q = 0; q < (n + 3) / 4; q++) {
+                            const float4 v = T4[q];
+                            acc = acc + v.x;
+                            if (4 * q + 1 < n) acc = acc + v.y;
+                            if (4 * q + 2 < n) acc = acc + v.z;
+                            if (4 * q + 3 < n) acc = acc + v.w;
+                        }
+                    }
+                }
+                if (!TREE) wave_lds_sync();
+                float gxx, gxy, gyy, ex, ey;
+                if (TREE) {
+                    gxx = group_tree_sum<LPF>(tree[0]); gxy = group_tree_sum<LPF>(tree[1]); gyy = group_tree_sum<LPF>(tree[2]);
+                    ex = group_tree_sum<LPF>(tree[3]) * a.step; ey = group_tree_sum<LPF>(tree[4]) * a.step;
+                } else {
+                    gxx = __shfl(acc, glead); gxy = __shfl(acc, glead + 1); gyy = __shfl(acc, glead + 2);
+                    ex = __shfl(acc, glead + 3) * a.step; ey = __shfl(acc, glead + 4) * a.step;
+                }
+                const float p1 = gxx * gyy, p2 = gxy * gxy;
+                const float det = p1 - p2;
+                const bool small_det = det < a.small;
+                if (act && small_det) { status = KLT_SMALL_DET; iterating = false; }
+                const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
+                const float dx = (n1 - n2) / det;
+                const float dy = (n3 - n4) / det;
+                if (act && !small_det) {
+                    status = KLT_TRACKED;
+                    x2 = x2 + dx;
+                    y2 = y2 + dy;
+                    it++;
+                    iterating = (fabsf(dx) >= a.th || fabsf(dy) >= a.th) && it < a.max_iterations;
+                }
+                if (__any(iterating)) request_footprint();
             }
-            if (!TREE) wave_lds_sync();
-            float gxx, gxy, gyy, ex, ey;
-            if (TREE) {
-                gxx = group_tree_sum<LPF>(tree[0]); gxy = group_tree_sum<LPF>(tree[1]); gyy = group_tree_sum<LPF>(tree[2]);
-                ex = group_tree_sum<LPF>(tree[3]) * a.step; ey = group_tree_sum<LPF>(tree[4]) * a.step;
-            } else {
-                gxx = __shfl(acc, glead); gxy = __shfl(acc, glead + 1); gyy = __shfl(acc, glead + 2);
-                ex = __shfl(acc, glead + 3) * a.step; ey = __shfl(acc, glead + 4) * a.step;
-            }
-            const float p1 = gxx * gyy, p2 = gxy * gxy;
-            const float det = p1 - p2;
-            const bool small_det = det < a.small;
-            if (act && small_det) { status = KLT_SMALL_DET; iterating = false; }
-            const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
-            const float dx = (n1 - n2) / det;
-            const float dy = (n3 - n4) / det;
-            if (act && !small_det) {
-                status = KLT_TRACKED;
-                x2 = x2 + dx;
-                y2 = y2 + dy;
-                it++;
-                iterating = (fabsf(dx) >= a.th || fabsf(dy) >= a.th) && it < a.max_iterations;
-            }
-            if (__any(iterating)) request_footprint();
-        }
-        if (run) { xout = x2; yout = y2; }
+            if (run) { xout = x2; yout = y2; }
 
-        // trackFeatures.py:110 -- Python floats: half-window 3.5, eps 1.001 as doubles
-        const double x2d = (double)x2, y2d = (double)y2, hwd = a.half_window;
-        if (run && (x2d - hwd < 0.0 || (double)nc - (x2d + hwd) < 1.001 || y2d - hwd < 0.0 || (double)nr - (y2d + hwd) < 1.001))
-            status = KLT_OOB;
+            // trackFeatures.py:110 -- Python floats: half-window 3.5, eps 1.001 as doubles
+            const double x2d = (double)x2, y2d = (double)y2, hwd = a.half_window;
+            if (run && (x2d - hwd < 0.0 || (double)nc - (x2d + hwd) < 1.001 || y2d - hwd < 0.0 || (double)nr - (y2d + hwd) < 1.001))
+                status = KLT_OOB;
 
-        // residue, trackFeatures.py:118-125
-        const bool need_res = run && status == KLT_TRACKED && a.use_max_residue;
-        if (__any(need_res)) {
-            const Bilinear br = make_bilinear(x2, y2);
-            f32x4 r_qi;
-            if (REUSE) {
-                const unsigned q = __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh);
-                r_qi = s_qi;                                 // the last footprint, if the final position has the same integer corner
-                if (need_res && q != q_held) r_qi = load_record_images(lv.i2, q);
-            } else {
-                const unsigned q = need_res ? __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh) : 0u;
-                r_qi = load_record_images(lv.i2, q);
+            // residue, trackFeatures.py:118-125
+            const bool need_res = run && status == KLT_TRACKED && a.use_max_residue;
+            if (__any(need_res)) {
+                const Bilinear br = make_bilinear(x2, y2);
+                f32x4 r_qi;
+                if (REUSE) {
+                    const unsigned q = __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh);
+                    r_qi = s_qi;                                 // the last footprint, if the final position has the same integer corner
+                    if (need_res && q != q_held) r_qi = load_record_images(lv.i2, q);
+                } else {
+                    const unsigned q = need_res ? __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh) : 0u;
+                    r_qi = load_record_images(lv.i2, q);
+                }
+                float s_i[4];
+                sample_quad<QPR>(r_qi, br, s_i);
+                float sres;
+                if (TREE) {
+                    float part = 0.f;
+    #pragma unroll
+                    for (int m = 0; m < 4; m++)
+                        if (qr < w && 4 * qh + m < w) part = part + fabsf(t_i[m] - s_i[m]);
+                    sres = group_tree_sum<LPF>(part);
+                } else {
+    #pragma unroll
+                    for (int m = 0; m < 4; m++)
+                        if (qr < w && 4 * qh + m < w) gl[k0 + m] = fabsf(t_i[m] - s_i[m]);
+                    wave_lds_sync();
+                    sres = pairwise_group<3>(gl, n, s);
+                    wave_lds_sync();
+                    sres = __shfl(sres, glead);
+                }
+                if (need_res && sres / (float)n > a.max_residue) status = KLT_LARGE_RESIDUE;
             }
-            float s_i[4];
-            sample_quad<QPR>(r_qi, br, s_i);
-            float sres;
-            if (TREE) {
-                float part = 0.f;
-#pragma unroll
-                for (int m = 0; m < 4; m++)
-                    if (qr < w && 4 * qh + m < w) part = part + fabsf(t_i[m] - s_i[m]);
-                sres = group_tree_sum<LPF>(part);
-            } else {
-#pragma unroll
-                for (int m = 0; m < 4; m++)
-                    if (qr < w && 4 * qh + m < w) gl[k0 + m] = fabsf(t_i[m] - s_i[m]);
-                wave_lds_sync();
-                sres = pairwise_group<3>(gl, n, s);
-                wave_lds_sync();
-                sres = __shfl(sres, glead);
-            }
-            if (need_res && sres / (float)n > a.max_residue) status = KLT_LARGE_RESIDUE;
-        }
 
-        int lvl_val;
-        if (!t_ok) lvl_val = KLT_OOB;
-        else if (a.retain) lvl_val = KLT_TRACKED;                                               // :127-129
-        else if (status == KLT_SMALL_DET || status == KLT_OOB || status == KLT_LARGE_RESIDUE) lvl_val = status;
-        else if (it >= a.max_iterations) lvl_val = KLT_MAX_ITERATIONS;
-        else lvl_val = KLT_TRACKED;
-        if (alive) {
-            val = lvl_val;
-            aux |= (uint32_t)(it < 14 ? it + 1 : 15) << (4 * r);
-            alive = !(val == KLT_SMALL_DET || val == KLT_OOB);                                  // :284-285
+            int lvl_val;
+            if (!t_ok) lvl_val = KLT_OOB;
+            else if (a.retain) lvl_val = KLT_TRACKED;                                               // :127-129
+            else if (status == KLT_SMALL_DET || status == KLT_OOB || status == KLT_LARGE_RESIDUE) lvl_val = status;
+            else if (it >= a.max_iterations) lvl_val = KLT_MAX_ITERATIONS;
+            else lvl_val = KLT_TRACKED;
+            if (alive) {
+                val = lvl_val;
+                aux |= (uint32_t)(it < 14 ? it + 1 : 15) << (4 * r);
+                alive = !(val == KLT_SMALL_DET || val == KLT_OOB);                                  // :284-285
+            }
         }
-    }
-    if (tracked_feature && s == 0) {
-        klt_feat o;
-        o.aux = (int32_t)aux;
-        const double xd = (double)xout, yd = (double)yout;
-        const bool oob = val == KLT_OOB ||
-                         xd < a.borderx || xd > (double)(a.ncols - 1) - a.borderx ||
-                         yd < a.bordery || yd > (double)(a.nrows - 1) - a.bordery;   // :288-308
-        if (oob) { o.x = -1.f; o.y = -1.f; o.val = KLT_OOB; }
-        else if (val == KLT_SMALL_DET || val == KLT_LARGE_RESIDUE || val == KLT_MAX_ITERATIONS) {
-            o.x = -1.f; o.y = -1.f; o.val = val;
-        } else { o.x = xout; o.y = yout; o.val = KLT_TRACKED; }
-        fout[f] = o;
+        if constexpr (!FB) {
+            // (track_record's text, in place: through the function the tree-sum 7x7 instantiations came out two SGPRs apart)
+            if (tracked_feature && s == 0) {
+                klt_feat o;
+                o.aux = (int32_t)aux;
+                const double xd = (double)xout, yd = (double)yout;
+                const bool oob = val == KLT_OOB ||
+                                 xd < a.borderx || xd > (double)(a.ncols - 1) - a.borderx ||
+                                 yd < a.bordery || yd > (double)(a.nrows - 1) - a.bordery;   // :288-308
+                if (oob) { o.x = -1.f; o.y = -1.f; o.val = KLT_OOB; }
+                else if (val == KLT_SMALL_DET || val == KLT_LARGE_RESIDUE || val == KLT_MAX_ITERATIONS) {
+                    o.x = -1.f; o.y = -1.f; o.val = val;
+                } else { o.x = xout; o.y = yout; o.val = KLT_TRACKED; }
+                fout[f] = o;
+            }
+        } else {
+            const klt_feat o = track_record(a, val, xout, yout, aux);          // uniform within the feature's lane group
+            if (pass == 0) {
+                fwd = o;
+                go = go && o.val == KLT_TRACKED;                               // lost on the way forward: the plain tracker's record, both ways
+                xstart = o.x; ystart = o.y;
+                if (!__any(go)) break;
+            } else {
+                bwd = o;
+            }
+        }
+    } while (FB && ++pass < 2);
+    if constexpr (FB) {
+        if (tracked_feature && s == 0) {
+            fout[f] = go ? fb_record(a.fb_max_e2, ft, fwd, bwd) : fwd;
+            if (fback) fback[f] = go ? bwd : fwd;
+        }
     }
 }
 
@@ -778,9 +878,11 @@ void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, 
 // features per wavefront, one pixel per lane) are recorded in profiles/README.md and live in the git history.
 int g_track_variant = getenv("KLT_TRACK_VARIANT") ? atoi(getenv("KLT_TRACK_VARIANT")) : 4;
 
-template <bool BATCH>
+// FB: the forward-backward kernels (klt_track_fb_async), chosen by the same rules; they have no tree-sum form
+template <bool BATCH, bool FB>
 static int launch_track_t(hipStream_t s, const TrackArgs &a)
 {
+    const TrackKernArgs<FB> &ka = a;                     // what the kernels take: the plain ones not the forward-backward fields
     const int n = a.window * a.window;
     if (n > 1024) return -1;
     const size_t lds = 5 * (size_t)((n + 3) & ~3) * sizeof(float);
@@ -798,26 +900,31 @@ static int launch_track_t(hipStream_t s, const TrackArgs &a)
         // latency: 112 / 199 us per launch against 87.5, cfg-4's 32-pair shard 0.535 / 0.687 ms against 0.495.  A scratch reload is a
         // vector memory operation and those return in order: it waits behind the footprint loads in flight, i.e. for the round trip
         // the extra wavefront was meant to hide.)
-        if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 7, 1, true>), gq, block, 0u, s, a);
-        else klt_launch((track_kernel_quad<BATCH, 7>), gq, block, (unsigned)(4 * lds), s, a);
+        // (the forward-backward instantiation is left without a cap as well -- an occupancy target of two is none for a kernel of 138
+        // VGPRs, which three wavefronts per SIMD fit; its registers and scratch are in DESIGN.md section 9a)
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 7, 2, false, true>), gq, block, (unsigned)(4 * lds), s, ka);
+        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 7, 1, true>), gq, block, 0u, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 7>), gq, block, (unsigned)(4 * lds), s, ka);
         return 0;
     }
     if (g_track_variant != 0 && a.window == 15) {
         const dim3 gq(a.order ? 8 * a.order_chunk : a.n, ny);
         // occupancy target 5 (96 VGPRs, 40 bytes of scratch per lane instead of 107 VGPRs): the 5000 wavefronts of cfg-3 are then
         // resident at once instead of in two rounds -- 57.9 -> 49.3 us.  (The 7x7 kernel loses from the same cap, see above.)
-        if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 15, 5, true>), gq, block, 0u, s, a);
-        else klt_launch((track_kernel_quad<BATCH, 15, 5>), gq, block, (unsigned)lds, s, a);
+        // (forward-backward: occupancy target 4 -- 123 VGPRs, 36 bytes of scratch; at 5 the two passes' state costs 152 bytes of scratch per lane)
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 15, 4, false, true>), gq, block, (unsigned)lds, s, ka);
+        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 15, 5, true>), gq, block, 0u, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 15, 5>), gq, block, (unsigned)lds, s, ka);
         return 0;
     }
     const dim3 grid(a.order ? 8 * a.order_chunk : a.n, ny);
-    if (a.window == 7) klt_launch((track_kernel<1, 7, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (a.window == 15) klt_launch((track_kernel<4, 15, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 64) klt_launch((track_kernel<1, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 128) klt_launch((track_kernel<2, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 256) klt_launch((track_kernel<4, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 512) klt_launch((track_kernel<8, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else klt_launch((track_kernel<16, 0, BATCH>), grid, block, (unsigned)lds, s, a);
+    if (a.window == 7) klt_launch((track_kernel<1, 7, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else if (a.window == 15) klt_launch((track_kernel<4, 15, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 64) klt_launch((track_kernel<1, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 128) klt_launch((track_kernel<2, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 256) klt_launch((track_kernel<4, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 512) klt_launch((track_kernel<8, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    else klt_launch((track_kernel<16, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
     return 0;
 }
 
@@ -919,6 +1026,10 @@ void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, c
 int launch_track(hipStream_t s, const TrackArgs &a)
 {
     if (a.n <= 0) return 0;
-    if (a.pairs) return a.npairs > 0 ? launch_track_t<true>(s, a) : 0;
-    return launch_track_t<false>(s, a);
+    if (a.fb) {
+        if (a.pairs) return a.npairs > 0 ? launch_track_t<true, true>(s, a) : 0;
+        return launch_track_t<false, true>(s, a);
+    }
+    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false>(s, a) : 0;
+    return launch_track_t<false, false>(s, a);
 }

@@ -36,6 +36,7 @@ class kltState:
     KLT_MAX_ITERATIONS = -3
     KLT_OOB = -4
     KLT_LARGE_RESIDUE = -5
+    KLT_FB_INCONSISTENT = -6          # not in the reference: rejected by the forward-backward check (tc.forwardBackwardCheck)
 
 
 def _pyramidSigma(tc):
@@ -76,6 +77,10 @@ class KLT_TrackingContext:
         self.affine_max_residue = 10.0
         self.affine_min_displacement = 0.02
         self.affine_max_displacement_differ = 1.5
+        # forward-backward consistency check (not in the reference): a feature tracked into frame 2 is tracked back into frame 1 and
+        # rejected (KLT_FB_INCONSISTENT) when it does not land within fb_max_error pixels of where it started
+        self.forwardBackwardCheck = False
+        self.fb_max_error = 1.0
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

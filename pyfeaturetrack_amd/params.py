@@ -1,5 +1,5 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
-from ._abi import KltAffineParams, KltParams
+from ._abi import KltAffineParams, KltFbParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -45,6 +45,19 @@ def params_from_tc(tc):
 def taps_from_params(p):
     """[(gauss, deriv)] for smoothing, pyramid and gradient sigma (klt_set_kernels `which` 0, 1, 2)."""
     return [_computeKernels(p.smooth_sigma), _computeKernels(p.pyramid_sigma), _computeKernels(p.grad_sigma)]
+
+
+def fb_params_from_tc(tc):
+    """tc.forwardBackwardCheck / tc.fb_max_error -> klt_fb_params.  Both are read with defaults: a tracking context made elsewhere (the
+    reference's own class) has neither.  The check is not offered together with the affine consistency check."""
+    f = KltFbParams()
+    f.enabled = int(bool(getattr(tc, "forwardBackwardCheck", False)))
+    f.max_error = float(getattr(tc, "fb_max_error", 1.0))
+    if f.enabled and tc.affineConsistencyCheck >= 0:
+        raise ValueError("forwardBackwardCheck and affineConsistencyCheck cannot both be switched on")
+    if f.enabled and not f.max_error >= 0.0:
+        raise ValueError("fb_max_error must be a number >= 0")
+    return f
 
 
 def affine_params_from_tc(tc):

@@ -11,6 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
+from .params import fb_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -157,6 +158,36 @@ def _affine_state_of(tc, ctx, featurelist):
             else:
                 weakref.finalize(anchor, _drop)
     return entry[1]
+
+
+class _BackRecords:
+    """tc.fb_back after a KLTTrackFeatures call with tc.forwardBackwardCheck: the backward records of that call (what tracking the
+    forward result back into frame 1 gave) as a structured array (x, y, val, aux).  They stay in a device buffer and are downloaded when
+    first looked at -- np.asarray(tc.fb_back), tc.fb_back["x"], tc.fb_back[i] --, which must happen before the next call with the check
+    (that call's records replace them: a late look raises)."""
+
+    def __init__(self, ctx, n):
+        self._ctx, self._n, self._rec = ctx, n, None
+        self._serial = ctx.__dict__["_fb_back_serial"] = ctx.__dict__.get("_fb_back_serial", 0) + 1
+
+    def _records(self):
+        if self._rec is None:
+            from .backend import _FB_API_BACK
+            if self._ctx.__dict__.get("_fb_back_serial") != self._serial:
+                raise KltBackendError("the backward records of this call were replaced by a later call with forwardBackwardCheck")
+            with self._ctx.lock:
+                self._rec = self._ctx.featbuf_download(_FB_API_BACK, self._n)
+        return self._rec
+
+    def __array__(self, dtype=None, copy=None):
+        rec = self._records()
+        return rec if dtype is None else rec.astype(dtype)
+
+    def __getitem__(self, key):
+        return self._records()[key]
+
+    def __len__(self):
+        return self._n
 
 
 def _trackFeature(x1, y1, x2, y2, img1, gradx1, grady1, img2, gradx2, grady2, tc):
@@ -332,6 +363,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist):
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
             KLTCountRemainingFeatures(featurelist), ncols, nrows))
+    fb_params_from_tc(tc)                             # (ValueError for the forward-backward and the affine check together, before any device work)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -342,6 +374,9 @@ def KLTTrackFeatures(tc, img1, img2, featurelist):
 
 def _track_locked(ctx, tc, img1, img2, featurelist):
     affine = tc.affineConsistencyCheck >= 0
+    # forward-backward check: one fused launch (klt_track_fb_async), stateless -- it can be repeated like the plain tracker's.  A rejected
+    # feature comes back as (-1, -1, KLT_FB_INCONSISTENT) and goes through the branches below like any other lost one.
+    fb_check = bool(fb_params_from_tc(tc).enabled)
     # The affine check updates its per-feature state in place, so its launch cannot be repeated: nothing is taken on trust there.
     s1, s2, ncols, nrows, doubts = _prepare_pair(tc, ctx, img1, img2, speculate=not affine)
 
@@ -354,7 +389,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist):
         # follows upstream KLT 1.3.4.  The per-feature templates / A matrices live on the device, keyed
         # by the feature list object.
         state = _affine_state_of(tc, ctx, featurelist)
-    ctx.track_enqueue(s1, s2, nfeat, state)
+    ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check)
     # The device is tracking; now every byte of the frames that were taken as resident is compared with what their slots were
     # filled from.  One that differs (the same array edited in place off the lattice, ...) is sent and built now and the tracker
     # runs again on the same input records: the records that come back are those of the last launch.
@@ -364,7 +399,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist):
             _resend(tc, ctx, slot, key)
             again = True
     if again:
-        ctx.track_enqueue(s1, s2, nfeat, state, upload=False)
+        ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
     # list-independent half of that replacement -- summed-area tables and eigenvalue keys of frame 2's level 0, 50 us at 1080p -- is
     # enqueued now, behind the tracker, and runs while the host moves the columns and finds its way into the replacement call
@@ -379,6 +414,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist):
             except KltBackendError:                         # (an optimisation only: the replacement scores the frame itself then)
                 pass
     fl_out = ctx.track_complete(nfeat, marked=marked)
+    if fb_check:
+        tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:
         rec = ctx.affine_download(state, nfeat)
     if store is not None:

@@ -139,9 +139,12 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     """Track `nFeatures` features through `frames` (an iterable of equally sized 8-bit images) and return the
     KLT_FeatureTable: row 0 = the selected features, row k = the features after tracking frame k-1 -> k (and, with
     `replace_lost`, after replacing the lost ones on frame k: new features carry their eigenvalue in `val`, as after
-    KLTReplaceLostFeatures).  tc.affineConsistencyCheck >= 0 runs the affine check on every step.
+    KLTReplaceLostFeatures).  tc.affineConsistencyCheck >= 0 runs the affine check on every step,
+    tc.forwardBackwardCheck the forward-backward check (rejected features are lost ones: the replacement pass fills their slots).
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
+    from .params import fb_params_from_tc
+    fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -162,6 +165,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     rows = [first]
     nrows, ncols = first.shape
     affine = tc.affineConsistencyCheck >= 0
+    from .params import fb_params_from_tc
+    fb_check = bool(fb_params_from_tc(tc).enabled) and not affine       # forward-backward check in every tracker step
 
     # frames are consumed lazily; the table grows in chunks so that a generator of unknown length works
     chunk = 64
@@ -244,6 +249,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                 cur, prev = s[j % ring], s[(j - 1) % ring]
                 if affine:
                     ctx.track_affine_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures, state)
+                elif fb_check:                       # stateless like the plain tracker: may be enqueued ahead and repeated
+                    ctx.track_fb_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
                 else:
                     ctx.track_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
 
