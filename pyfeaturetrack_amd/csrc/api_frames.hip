@@ -212,10 +212,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     // KLT_OPT_BUILD_STREAM: the whole build goes to the build stream, behind everything enqueued on the main stream so far (the
     // earlier readers of these slots, synchronous uploads) -- one event each way per build.  The generic two-pass kernels share
     // scratch with the selection, so they stay on the main stream.
-    struct WorkScope {
-        klt_ctx *c;
-        ~WorkScope() { c->work = c->stream; }
-    } work_scope{c};
+    WorkScope work_scope{c};
     // (Round 3 measured the level-0 kernel alone on the build stream, levels >= 1 and the tracker on the main stream -- "KLT_OPT_L0_STREAM",
     // commit 72f1f4e: bit-identical, and no faster: one context 0.0452 ms per pair against 0.0462 on one stream with two pairs per launch.
     // The level-0 kernel and the tracker are both bound by VALU issue: running side by side they take 70 us where they take 48 + 26 one

@@ -4,26 +4,41 @@
 #include "klt_context.h"
 
 namespace kltapi {
+// summed-area tables of the gradient products (goodFeaturesUtils.pyx:49-51): step-synchronous wavefront pipelines (sat_pipeline.hip)
+// where whole aligned quads can be moved, else the barrier-coupled kernels of select_kernels.hip
+
+// the tables' column pass: the pipeline kernel where it takes the geometry (a positive code is a device error), else the barrier kernel
+static int enqueue_sat_cols(klt_ctx *c, hipStream_t st, float *sat, int nc, int nr)
+{
+    TimerScope t(c, F_SAT_COLS, (double)nc * nr * 24);
+    const int e = c->sat_variant == 1 ? launch_sat_cols_pipe(st, sat, nc, nr) : -1;
+    if (e > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e));
+    if (e < 0) launch_sat_cols(st, sat, nc, nr);
+    return 0;
+}
 
 int enqueue_sat(klt_ctx *c, hipStream_t st, const float *gx, const float *gy, float *sat, int nc, int nr, bool rows_only)
 {
-    const bool pipe = c->sat_variant == 1;
-    const double N = (double)nc * nr;
-    { TimerScope t(c, F_SAT_ROWS, N * (8 + 12));
-      const int e = pipe ? launch_sat_rows_pipe(st, gx, gy, sat, nc, nr) : -1;
+    { TimerScope t(c, F_SAT_ROWS, (double)nc * nr * (8 + 12));
+      const int e = c->sat_variant == 1 ? launch_sat_rows_pipe(st, gx, gy, sat, nc, nr) : -1;
       if (e > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e));
       if (e < 0) launch_sat_rows(st, gx, gy, sat, nc, nr); }
-    if (rows_only) return 0;
-    { TimerScope t(c, F_SAT_COLS, N * 24);
-      const int e = pipe ? launch_sat_cols_pipe(st, sat, nc, nr) : -1;
-      if (e > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e));
-      if (e < 0) launch_sat_cols(st, sat, nc, nr); }
-    return 0;
+    return rows_only ? 0 : enqueue_sat_cols(c, st, sat, nc, nr);
 }
 
 }  // namespace kltapi
 
 namespace {
+// smallest power of two >= x, at least 2048 (the sort takes whole 2048-key chunks)
+long long pow2_at_least_2048(long long x) { long long p = 2048; while (p < x) p <<= 1; return p; }
+
+// the list as select_job_start / serial_selection found it, back from the snapshot
+int restore_list(klt_ctx *c, klt_feat *fl, int n)
+{
+    HIPCHK(c, hipMemcpyAsync(fl, c->fl_snapshot, (size_t)n * sizeof(klt_feat), hipMemcpyDefault /* the list may be pinned host memory (klt_featbuf_map_host) */, c->stream));
+    return 0;
+}
+
 // start of an attempt: free slots + snapshot of the list, scores / histogram / cut (attempt 0) or "every candidate" (attempt 1), tile lists
 int select_job_start(klt_ctx *c, SelectJob &j)
 {
@@ -100,7 +115,7 @@ int select_job_finish(klt_ctx *c, SelectJob &j)
         if (rem[j.look - 1] != 0u) {
             // a dependency chain longer than the passes run so far: put the list back and keep going
             if (j.round + j.rounds_per_look > SelectJob::kMaxRounds) return fail(c, KLT_ERR_DEVICE, "minimum-distance passes did not settle");
-            HIPCHK(c, hipMemcpyAsync(j.fl, c->fl_snapshot, (size_t)j.n * sizeof(klt_feat), hipMemcpyDefault /* the list may be pinned host memory (klt_featbuf_map_host) */, c->stream));
+            if (int rc = restore_list(c, j.fl, j.n)) return rc;
             if (j.by_rank) launch_zero_words(c->stream, j.rank_d, (size_t)j.bound);
             else HIPCHK(c, hipMemsetAsync(c->keys2, 0, (size_t)j.np2 * sizeof(unsigned long long), c->stream));
             if (int rc = select_job_rounds(c, j)) return rc;
@@ -116,7 +131,7 @@ int select_job_finish(klt_ctx *c, SelectJob &j)
         c->sorted_keys = j.by_rank ? nullptr : c->keys2; c->sorted_count = j.by_rank ? 0 : (int)j.np2;
         // ran out of accepted candidates although the prefilter dropped some: repeat with every candidate
         if (j.filtered && res[1] && info[1] < info[2]) {
-            HIPCHK(c, hipMemcpyAsync(j.fl, c->fl_snapshot, (size_t)j.n * sizeof(klt_feat), hipMemcpyDefault, c->stream));
+            if (int rc = restore_list(c, j.fl, j.n)) return rc;
             j.attempt = 1;
             if (int rc = select_job_start(c, j)) return rc;
             if (int rc = select_job_rounds(c, j)) return rc;
@@ -128,9 +143,7 @@ int select_job_finish(klt_ctx *c, SelectJob &j)
     HIPCHK(c, hipGetLastError());
     return looks > 1 ? 1 : KLT_OK;
 }
-}  // namespace
 
-namespace {
 // borders / half-windows as ScanImageForGoodFeatures receives them: Python floats truncated to C ints
 // (selectGoodFeatures.py:168-169, :215-221, goodFeaturesUtils.pyx:35-37)
 struct SelGeom { int bx, by, hw, hh, step, nx, ny; long long ncand, npow2; };
@@ -147,14 +160,52 @@ int select_geometry(klt_ctx *c, int nc, int nr, SelGeom *g)
     g->nx = (nc - g->bx > g->bx) ? (nc - 2 * g->bx + g->step - 1) / g->step : 0;
     g->ny = (nr - g->by > g->by) ? (nr - 2 * g->by + g->step - 1) / g->step : 0;
     g->ncand = (long long)g->nx * g->ny;
-    g->npow2 = 2048;
-    while (g->npow2 < g->ncand) g->npow2 <<= 1;
+    g->npow2 = pow2_at_least_2048(g->ncand);
     if (g->npow2 > (1LL << 30)) return fail(c, KLT_ERR_ARG, "too many candidates");
     return 0;
 }
 
-// summed-area tables of the gradient products (goodFeaturesUtils.pyx:49-51): step-synchronous wavefront pipelines (sat_pipeline.hip)
-// where whole aligned quads can be moved, else the barrier-coupled kernels of select_kernels.hip
+double select_min_eig(const klt_params &p) { return p.min_eigenvalue < 1 ? 1.0 : p.min_eigenvalue; }      // selectGoodFeatures.py:53
+
+// the frame, the candidate lattice and the eigenvalue floor of a zeroed SelectArgs; the buffers are the caller's
+void fill_select_geometry(SelectArgs &sa, int nc, int nr, const SelGeom &g, double min_eig)
+{
+    sa.min_eig = min_eig;
+    sa.ncols = nc; sa.nrows = nr; sa.bx = g.bx; sa.by = g.by; sa.step = g.step; sa.nx = g.nx; sa.ny = g.ny;
+    sa.hw = g.hw; sa.hh = g.hh; sa.npow2 = (int)g.npow2;
+}
+
+// the greedy walk's arguments over list `fl` with exclusion distance d (mindist - 1) on an ncols x nrows frame: slot scratch and cell grid
+// are there when this returns, the grid NOT cleared; keys, nkeys and aff_rec are the caller's
+int make_nms_args(klt_ctx *c, klt_feat *fl, int n, bool overwrite_all, int d, int ncols, int nrows, NmsArgs &na)
+{
+    std::memset(&na, 0, sizeof(na));
+    na.fl = fl; na.placed_out = c->placed_d;
+    na.nfeat = n; na.overwrite_all = overwrite_all;
+    na.d = d; na.cell = d >= 0 ? d + 1 : 1;
+    na.cell_magic = na.cell == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)na.cell) + 1u;
+    if (int rc = ensure(c, c->nms_slots, c->nms_slots_cap, (size_t)n)) return rc;
+    na.slots = c->nms_slots;
+    na.gw = d >= 0 ? (ncols + na.cell - 1) / na.cell : 1;
+    na.gh = d >= 0 ? (nrows + na.cell - 1) / na.cell : 1;
+    na.grid_in_lds = (size_t)na.gw * na.gh * sizeof(uint32_t) <= 128 * 1024;     // + 12.4 KiB of static LDS in the kernel
+    if (!na.grid_in_lds) {
+        if (int rc = ensure(c, c->grid, c->grid_cap, (size_t)na.gw * na.gh)) return rc;
+        na.grid_global = c->grid;
+    }
+    return 0;
+}
+
+// The counters of the parallel passes, one allocation: [tiles] list lengths | [kMaxRounds] "undecided left after pass r" | accepted count |
+// workgroup ticket | [tiles] accepted per tile | 8192 histogram bins + 4 words of prefilter info | [bound] ranks (when ranking by counting)
+struct MisCounters {
+    size_t lists = 0, remaining, accepted, ticket, tile_accepted, hist, info, rank, total;      // where each part starts, in words
+    MisCounters(int tiles, long long bound, bool by_rank)
+        : remaining((size_t)tiles), accepted(remaining + SelectJob::kMaxRounds), ticket(accepted + 1), tile_accepted(ticket + 1),
+          hist(tile_accepted + tiles), info(hist + 8192), rank(info + 4), total(rank + (by_rank ? (size_t)bound : 0)) {}
+    size_t zero_from() const { return remaining; }      // an attempt starts with everything behind the list lengths zeroed
+    size_t zero_n() const { return total - remaining; }
+};
 
 ScoreCache *find_scores(klt_ctx *c, const Slot *s, const SelGeom &g, double min_eig)
 {
@@ -165,10 +216,236 @@ ScoreCache *find_scores(klt_ctx *c, const Slot *s, const SelGeom &g, double min_
             return &e;
     return nullptr;
 }
+
+// ---- the steps of klt_select_begin_async, in the order it takes them
+// leaves the four scratch planes of an N-pixel frame (all of them or none), the key buffer and the convolution scratch
+int ensure_select_scratch(klt_ctx *c, size_t N, long long npow2)
+{
+    if (N > c->sel_cap) {
+        if (c->sel_img) { if (int rc = sync_all(c)) return rc; hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap); }
+        c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
+        c->sel_cap = 0;                                       // (nothing is held until all four planes are: a failure below frees what it got)
+        int rc_alloc = dev_alloc(c, (void **)&c->sel_img, N * sizeof(float), "selection scratch: image");
+        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sel_rec, KLT_PIX_STRIDE * N * sizeof(float), "selection scratch: pixel records");      // image, gradx, grady, like a slot's levels
+        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sat, 3 * N * sizeof(float), "selection scratch: summed-area tables");
+        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->valmap, N * sizeof(float), "selection scratch: eigenvalue map");
+        if (rc_alloc) {
+            hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap);
+            c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
+            return rc_alloc;
+        }
+        c->sel_cap = N;
+    }
+    if (int rc = ensure(c, c->keys, c->keys_cap, (size_t)npow2)) return rc;
+    return ensure_tmp(c, N);
+}
+
+// leaves the image and gradient planes the selection scores, enqueued on the stream: the slot's level-0 pyramid reused
+// (selectGoodFeatures.py:176-181) or computed afresh from the raw frame (:183-197)
+int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, const float **gx, const float **gy)
+{
+    const int nc = s->nc, nr = s->nr;
+    const float *img = nullptr;
+    if (use_pyramid) {
+        if (!s->pyr_valid) return fail(c, KLT_ERR_STATE, "use_pyramid requested but the slot's pyramids are not built");
+        if (int rc = wait_built(c, s)) return rc;
+        *img_out = s->lv[0].img; *gx = s->lv[0].gx; *gy = s->lv[0].gy;
+        return 0;
+    }
+    if (s->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
+    if (int rc = wait_upload(c, s, c->stream)) return rc;
+    if (int rc = wait_built(c, s)) return rc;              // a build of this slot may still read the raw frame's buffers
+    bool grads_done = false;
+    if (c->p.smoothBeforeSelecting && fused_smooth_ok(c)) {
+        const void *raw = s->raw_kind == 1 ? (const void *)raw8(s) : (const void *)rawf(s);
+        if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr)) return rc;
+        grads_done = true;
+    } else if (c->p.smoothBeforeSelecting) {
+        enqueue_smooth_raw(c, s, c->sel_img);
+        img = c->sel_img;
+    } else if (s->raw_kind == 2) {
+        img = rawf(s);
+    } else {
+        // u8 -> f32 with a 1-tap identity kernel is overkill; widen with a 1-tap correlate (exact)
+        Taps one;
+        std::memset(&one, 0, sizeof(one));
+        one.n = 1; one.sym = 1; one.k[0] = 1.0;
+        launch_hconv_u8(c->stream, raw8(s), nc, nr, c->sel_img, nullptr, nc, 1, 0, one, nullptr);
+        img = c->sel_img;
+    }
+    if (!grads_done) {
+        // the compact image (a raw f32 frame or sel_img) -> the records, image copied through
+        if (fused_grad_ok(c)) { if (int rc = enqueue_fused_grad(c, 1, &img, &c->sel_rec, nc, nr)) return rc; }
+        else enqueue_gradients(c, img, nc, nr, c->sel_rec);
+    }
+    *img_out = c->sel_rec; *gx = c->sel_rec + 1; *gy = c->sel_rec + 2;
+    // the kernels above read the raw frame: the second-next asynchronous copy into this slot (its raw buffers alternate) waits
+    return mark_consumed(c, &s, 1, c->stream);
+}
+
+// what a selection of n features in `mode` will do, decided from the geometry and the options alone; nothing is enqueued
+struct SelPlan {
+    int d, R;                     // mindist - 1; exclusion radius in candidate cells (-1: none)
+    bool parallel_nms, prefilter;
+    long long target;             // candidates the prefilter aims to keep
+    double min_eig;
+    ScoreCache *pre;              // scores prepared ahead of time that this selection uses, or null
+};
+SelPlan plan_selection(klt_ctx *c, const Slot *s, const SelGeom &g, int mode, int use_pyramid, int n)
+{
+    SelPlan pl;
+    const int mindist = c->p.mindist < 0 ? 0 : c->p.mindist;          // selectGoodFeatures.py:241-243
+    pl.d = mindist - 1;                                               // :61
+    pl.R = pl.d >= 0 ? pl.d / g.step : -1;
+    pl.parallel_nms = c->use_mis && g.ncand > 0 && mis_stage_bytes(pl.R) <= 120 * 1024;
+    pl.target = 64LL * n;
+    if (pl.target < 65536) pl.target = 65536;
+    pl.prefilter = c->use_topk && g.ncand > 262144 && pl.target < g.ncand / 2;
+    pl.min_eig = select_min_eig(c->p);
+    // scores prepared ahead of time (klt_select_prepare_async) are used by the replacement pass of the parallel path; everything else
+    // computes them here
+    pl.pre = nullptr;
+    if (mode == KLT_REPLACING_SOME && use_pyramid && pl.parallel_nms && pl.prefilter && pl.d >= 0 && !c->score_override_n)
+        pl.pre = find_scores(c, s, g, pl.min_eig);
+    return pl;
+}
+
+struct Consume {                                           // a set is used once: the selection frees it when it is through with it
+    ScoreCache *e;
+    ~Consume() { if (e) e->gen = 0; }
+};
+
+// REPLACING_SOME: the squares of the live features are marked first; the eigenvalue kernels skip marked pixels, so neither the
+// scoring nor the minimum-distance stage ever sees them.  Leaves the seed map stamped with c->seed_stamp.
+int mark_live_squares(klt_ctx *c, const klt_feat *fl, int n, int nc, int nr, int d, const uint8_t **seed)
+{
+    const size_t N = (size_t)nc * nr;
+    const uint8_t *before = c->seedmap;
+    if (int rc = ensure(c, c->seedmap, c->seed_cap, N)) return rc;
+    if (c->seedmap != before || c->seed_n != N || c->seed_stamp == 255) {       // new map, other frame size, or the stamps wrapped
+        HIPCHK(c, hipMemsetAsync(c->seedmap, 0, N, c->stream));
+        c->seed_n = N;
+        c->seed_stamp = 0;
+    }
+    c->seed_stamp++;
+    TimerScope t(c, F_SEED, (double)n * 16);
+    launch_seed_fill(c->stream, fl, n, c->seedmap, nc, nr, d, c->seed_stamp);
+    *seed = c->seedmap;
+    return 0;
+}
+
+// ---- parallel minimum distance (default): decide every candidate in a few passes, rank the accepted ones, and
+// fill the free slots with the best of them (same result as the sorted serial walk below).  Leaves the first batch of passes
+// enqueued and the job with the context, for klt_select_finish.
+int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, const NmsArgs &na, int mode, Consume &consume)
+{
+    const int nx = sa.nx, ny = sa.ny, R = pl.R, n = na.nfeat;
+    const long long ncand = (long long)nx * ny;
+    auto job = std::make_unique<SelectJob>();
+    SelectJob &j = *job;
+    // passes enqueued before the host looks at the outcome: what the previous selection needed (frames of a sequence
+    // behave alike); an idle pass costs 5 us, a second look costs a host round trip
+    j.rounds_per_look = c->mis_rounds_hint;
+    const int tiles = mis_tiles(nx, ny);
+    // two accepted candidates are more than R cells apart in x or in y: at most one per (R+1)x(R+1) block of cells
+    j.bound = R < 0 ? ncand : (long long)((nx + R) / (R + 1)) * ((ny + R) / (R + 1));
+    j.by_rank = j.bound <= 98304;                       // rank by counting; beyond that sort the accepted keys
+    j.np2 = pow2_at_least_2048(j.bound);
+    const MisCounters cnt(tiles, j.bound, j.by_rank);
+    const int tile_cap = mis_tile_capacity(R);
+    if (int rc = ensure(c, c->keys2, c->keys2_cap, (size_t)(j.np2 > sa.npow2 ? j.np2 : sa.npow2))) return rc;
+    if (int rc = ensure(c, c->mis_st, c->mis_st_cap, (size_t)ncand)) return rc;
+    if (int rc = ensure(c, c->mis_list, c->mis_list_cap, (size_t)tiles * 1024)) return rc;
+    if (int rc = ensure(c, c->mis_cnt, c->mis_cnt_cap, cnt.total)) return rc;
+    if (int rc = ensure(c, c->mis_tile_keys, c->mis_tile_keys_cap, (size_t)tiles * tile_cap)) return rc;
+    if (int rc = ensure(c, c->fl_snapshot, c->fl_snapshot_cap, (size_t)n)) return rc;
+    // results come back through pinned host memory the kernels write to directly
+    if (!c->readback) {
+        void *hp = nullptr;
+        if (int rc = host_alloc(c, &hp, 128 * sizeof(unsigned), "selection read-back words")) return rc;
+        c->readback = (unsigned *)hp;
+        c->pinned.push_back(hp);
+    }
+    unsigned *const base = c->mis_cnt;
+    j.fl = na.fl; j.n = n; j.ncand = ncand; j.mode = mode; j.prefilter = pl.prefilter; j.target = pl.target; j.pre = pl.pre;
+    j.zero_from = base + cnt.zero_from(); j.zero_n = cnt.zero_n();
+    j.hist_d = base + cnt.hist; j.ticket_d = base + cnt.ticket; j.info_d = base + cnt.info; j.rank_d = base + cnt.rank;
+    j.acc_count_d = base + cnt.accepted;
+    j.nfill_d = c->placed_d + 2;
+    MisArgs &ma = j.ma;
+    ma.keys = pl.pre ? pl.pre->keys : c->keys; ma.seed = pl.pre ? sa.seedmap : nullptr; ma.seed_stamp = c->seed_stamp; ma.ncols = sa.ncols;
+    ma.st = c->mis_st; ma.list = c->mis_list; ma.cnt = base + cnt.lists;
+    ma.remaining = base + cnt.remaining; ma.acc_cnt = base + cnt.tile_accepted; ma.acc_cap = tile_cap;
+    ma.acc_keys = c->mis_tile_keys; ma.info = j.info_d;
+    ma.nx = nx; ma.ny = ny; ma.R = R; ma.stage = 1; ma.bx = sa.bx; ma.by = sa.by; ma.step = sa.step;
+    ma.sparse = mode == KLT_REPLACING_SOME && pl.prefilter ? 1 : 0;
+    j.pa = na;                                          // placement: the accepted candidates never exclude each other
+    j.pa.d = -1; j.pa.cell = 1; j.pa.cell_magic = 0u; j.pa.gw = j.pa.gh = 1; j.pa.grid_in_lds = 1; j.pa.grid_global = nullptr;
+    j.pa.keys = c->keys2; j.pa.nkeys = (int)j.np2;
+    j.sa = sa;
+    consume.e = nullptr;                                // the job frees the score set when it is through with it
+    if (int rc = select_job_start(c, j)) return rc;
+    if (int rc = select_job_rounds(c, j)) return rc;
+    c->sel_job = std::move(job);
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
+// the greedy walk over sorted `keys`, the cell grid cleared first where it lives in global memory
+int run_nms(klt_ctx *c, NmsArgs &na, const unsigned long long *keys, int nkeys)
+{
+    na.keys = keys;
+    na.nkeys = nkeys;
+    if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
+    TimerScope t(c, F_NMS, (double)na.nfeat * 16);
+    const int e = launch_nms(c->stream, na);
+    if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
+    return 0;
+}
+
+// ---- sorted serial walk (KLT_OPT_SELECT_PARALLEL_NMS = 0, or an exclusion square too large for the LDS tile).  Leaves the
+// selection enqueued in full (or, behind the prefilter, complete) and the sorted keys it walked in sorted_keys / sorted_count.
+int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArgs &na)
+{
+    const int n = na.nfeat;
+    const long long ncand = (long long)sa.nx * sa.ny, npow2 = sa.npow2;
+    // top-K prefilter: sort only the candidates the greedy walk can plausibly reach (one small D2H read-back)
+    if (pl.prefilter) {
+        if (int rc = ensure(c, c->keys2, c->keys2_cap, (size_t)npow2)) return rc;
+        size_t hcap = c->topk_hist ? 8192 + 4 : 0;
+        if (int rc = ensure(c, c->topk_hist, hcap, (size_t)8192 + 4)) return rc;
+        if (int rc = ensure(c, c->fl_snapshot, c->fl_snapshot_cap, (size_t)n)) return rc;
+        HIPCHK(c, hipMemsetAsync(c->topk_hist, 0, (8192 + 4) * sizeof(unsigned), c->stream));
+        unsigned info[4] = {0, 0, 0, 0};
+        {
+            TimerScope t(c, F_SORT, (double)ncand * 16);
+            launch_topk_prefilter(c->stream, c->keys, (int)ncand, (unsigned)pl.target, c->topk_hist, c->topk_hist + 8192, c->keys2);
+        }
+        HIPCHK(c, hipMemcpyAsync(info, c->topk_hist + 8192, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const long long kept = info[3], valid = info[2];
+        const long long np2 = pow2_at_least_2048(kept);
+        if (kept < np2) HIPCHK(c, hipMemsetAsync(c->keys2 + kept, 0, (size_t)(np2 - kept) * sizeof(unsigned long long), c->stream));
+        { TimerScope t(c, F_SORT, (double)np2 * 16); launch_sort_desc(c->stream, c->keys2, (int)np2); }
+        HIPCHK(c, hipMemcpyAsync(c->fl_snapshot, na.fl, (size_t)n * sizeof(klt_feat), hipMemcpyDefault, c->stream));
+        if (int rc = run_nms(c, na, c->keys2, (int)kept)) return rc;
+        c->sorted_keys = c->keys2; c->sorted_count = (int)kept;
+        int res[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(res, c->placed_d, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!(res[1] && kept < valid)) { HIPCHK(c, hipGetLastError()); return KLT_OK; }
+        // the kept candidates ran out before the list was full: restore the list and take the full sort
+        if (int rc = restore_list(c, na.fl, n)) return rc;
+    }
+    { TimerScope t(c, F_SORT, (double)npow2 * 16); launch_sort_desc(c->stream, c->keys, (int)npow2); }
+    if (int rc = run_nms(c, na, c->keys, (int)(ncand < npow2 ? ncand : npow2))) return rc;
+    c->sorted_keys = c->keys; c->sorted_count = (int)(ncand < npow2 ? ncand : npow2);
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
 }  // namespace
 
 extern "C" {
-
 
 // The half of a selection that depends on the pixels only -- summed-area tables and the eigenvalue of every candidate window
 // (goodFeaturesUtils.pyx:17-73) -- for the level-0 images of `slot`, ahead of the selection itself: on the build stream when
@@ -185,10 +462,7 @@ int klt_select_prepare_async(klt_ctx *c, int slot)
     SelGeom g;
     if (int rc = select_geometry(c, nc, nr, &g)) return rc;
     if (g.ncand <= 0) return KLT_OK;
-    struct WorkScope {
-        klt_ctx *c;
-        ~WorkScope() { c->work = c->stream; }
-    } work_scope{c};
+    WorkScope work_scope{c};
     if (c->build_stream_on) {
         if (!c->bstream) HIPCHK(c, hipStreamCreateWithFlags(&c->bstream, hipStreamNonBlocking));
         if (!s->built_on_bstream) {             // built on the main stream: behind everything there
@@ -218,9 +492,7 @@ int klt_select_prepare_async(klt_ctx *c, int slot)
     SelectArgs sa;
     std::memset(&sa, 0, sizeof(sa));
     sa.sat = c->sat_pre; sa.keys = e->keys;
-    sa.min_eig = c->p.min_eigenvalue < 1 ? 1.0 : c->p.min_eigenvalue;          // selectGoodFeatures.py:53
-    sa.ncols = nc; sa.nrows = nr; sa.bx = g.bx; sa.by = g.by; sa.step = g.step; sa.nx = g.nx; sa.ny = g.ny;
-    sa.hw = g.hw; sa.hh = g.hh; sa.npow2 = (int)g.npow2;
+    fill_select_geometry(sa, nc, nr, g, select_min_eig(c->p));
     // the tables' column pass and the eigenvalue keys in one launch where that applies (sat_pipeline.hip: the column-summed tables never
     // reach HBM); KLT_FUSED_COLS_EIGEN=0: the two separate kernels
     static const bool fused_cols_eigen = !(getenv("KLT_FUSED_COLS_EIGEN") && atoi(getenv("KLT_FUSED_COLS_EIGEN")) == 0);
@@ -233,10 +505,7 @@ int klt_select_prepare_async(klt_ctx *c, int slot)
         if (e2 < 0) {
             // the fused kernel does not take this geometry after all: the column pass and the keys as two launches (no keys were written,
             // and the score set is only stamped below, after a launch that did write them)
-            { TimerScope t(c, F_SAT_COLS, N * 24);
-              const int e3 = launch_sat_cols_pipe(c->work, c->sat_pre, nc, nr);
-              if (e3 > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e3));
-              if (e3 < 0) launch_sat_cols(c->work, c->sat_pre, nc, nr); }
+            if (int rc = enqueue_sat_cols(c, c->work, c->sat_pre, nc, nr)) return rc;
             TimerScope t(c, F_EIGEN, 12.0 * N + (double)g.ncand * 8);
             launch_eigen_hist(c->work, sa);
         }
@@ -264,258 +533,51 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
     Slot *s;
     if (int rc = get_slot(c, slot, &s, false)) return rc;
     const int nc = s->nc, nr = s->nr;
-    const size_t N = (size_t)nc * nr;
     FeatBuf *b;
     if (int rc = get_fb(c, fb, n, &b)) return rc;
-
-    const klt_params &p = c->p;
     SelGeom geom;
     if (int rc = select_geometry(c, nc, nr, &geom)) return rc;
-    const int bx = geom.bx, by = geom.by, hw = geom.hw, hh = geom.hh, step = geom.step, nx = geom.nx, ny = geom.ny;
-    const long long ncand = geom.ncand, npow2 = geom.npow2;
 
-    // scratch
-    if (N > c->sel_cap) {
-        if (c->sel_img) { if (int rc = sync_all(c)) return rc; hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap); }
-        c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
-        c->sel_cap = 0;                                       // (nothing is held until all four planes are: a failure below frees what it got)
-        int rc_alloc = dev_alloc(c, (void **)&c->sel_img, N * sizeof(float), "selection scratch: image");
-        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sel_rec, KLT_PIX_STRIDE * N * sizeof(float), "selection scratch: pixel records");      // image, gradx, grady, like a slot's levels
-        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->sat, 3 * N * sizeof(float), "selection scratch: summed-area tables");
-        if (!rc_alloc) rc_alloc = dev_alloc(c, (void **)&c->valmap, N * sizeof(float), "selection scratch: eigenvalue map");
-        if (rc_alloc) {
-            hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap);
-            c->sel_img = c->sel_rec = c->sat = c->valmap = nullptr;
-            return rc_alloc;
-        }
-        c->sel_cap = N;
-    }
-    if (int rc = ensure(c, c->keys, c->keys_cap, (size_t)npow2)) return rc;
-    if (int rc = ensure_tmp(c, N)) return rc;
-
-    // images: reuse the slot's level-0 pyramid (selectGoodFeatures.py:176-181) or compute afresh (:183-197)
+    if (int rc = ensure_select_scratch(c, (size_t)nc * nr, geom.npow2)) return rc;
     const float *img, *gx, *gy;
-    if (use_pyramid) {
-        if (!s->pyr_valid) return fail(c, KLT_ERR_STATE, "use_pyramid requested but the slot's pyramids are not built");
-        if (int rc = wait_built(c, s)) return rc;
-        img = s->lv[0].img; gx = s->lv[0].gx; gy = s->lv[0].gy;
-    } else {
-        if (s->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
-        if (int rc = wait_upload(c, s, c->stream)) return rc;
-        if (int rc = wait_built(c, s)) return rc;              // a build of this slot may still read the raw frame's buffers
-        bool grads_done = false;
-        if (p.smoothBeforeSelecting && fused_smooth_ok(c)) {
-            const void *raw = s->raw_kind == 1 ? (const void *)raw8(s) : (const void *)rawf(s);
-            if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr)) return rc;
-            grads_done = true;
-        } else if (p.smoothBeforeSelecting) {
-            enqueue_smooth_raw(c, s, c->sel_img);
-            img = c->sel_img;
-        } else if (s->raw_kind == 2) {
-            img = rawf(s);
-        } else {
-            // u8 -> f32 with a 1-tap identity kernel is overkill; widen with a 1-tap correlate (exact)
-            Taps one;
-            std::memset(&one, 0, sizeof(one));
-            one.n = 1; one.sym = 1; one.k[0] = 1.0;
-            launch_hconv_u8(c->stream, raw8(s), nc, nr, c->sel_img, nullptr, nc, 1, 0, one, nullptr);
-            img = c->sel_img;
-        }
-        if (!grads_done) {
-            // the compact image (a raw f32 frame or sel_img) -> the records, image copied through
-            if (fused_grad_ok(c)) { if (int rc = enqueue_fused_grad(c, 1, &img, &c->sel_rec, nc, nr)) return rc; }
-            else enqueue_gradients(c, img, nc, nr, c->sel_rec);
-        }
-        img = c->sel_rec; gx = c->sel_rec + 1; gy = c->sel_rec + 2;
-        // the kernels above read the raw frame: the second-next asynchronous copy into this slot (its raw buffers alternate) waits
-        if (int rc = mark_consumed(c, &s, 1, c->stream)) return rc;
-    }
+    if (int rc = select_planes(c, s, use_pyramid, &img, &gx, &gy)) return rc;
     c->last_sel[0] = img; c->last_sel[1] = gx; c->last_sel[2] = gy;
-    c->sel_nc = nc; c->sel_nr = nr; c->sel_nx = nx; c->sel_ny = ny; c->sel_npow2 = (int)npow2;
+    c->sel_nc = nc; c->sel_nr = nr; c->sel_nx = geom.nx; c->sel_ny = geom.ny; c->sel_npow2 = (int)geom.npow2;
 
-    int mindist = p.mindist < 0 ? 0 : p.mindist;          // selectGoodFeatures.py:241-243
-    const int d = mindist - 1;                            // :61
-    const int R = d >= 0 ? d / step : -1;                 // exclusion radius in candidate cells
-    const bool parallel_nms = c->use_mis && ncand > 0 && mis_stage_bytes(R) <= 120 * 1024;
-    long long target = 64LL * n;
-    if (target < 65536) target = 65536;
-    const bool prefilter = c->use_topk && ncand > 262144 && target < ncand / 2;
-    const double min_eig = p.min_eigenvalue < 1 ? 1.0 : p.min_eigenvalue;          // :53
-
-    // scores prepared ahead of time (klt_select_prepare_async) are used by the replacement pass of the parallel path; everything else
-    // computes them here
-    ScoreCache *pre = nullptr;
-    if (mode == KLT_REPLACING_SOME && use_pyramid && parallel_nms && prefilter && d >= 0 && !c->score_override_n)
-        pre = find_scores(c, s, geom, min_eig);
-    c->sel_valmap = !pre;
-    struct Consume {                                       // a set is used once: the selection frees it when it is through with it
-        ScoreCache *e;
-        ~Consume() { if (e) e->gen = 0; }
-    } consume{pre};
-    if (pre) {
-        if (event_live(c, pre->ev_serial)) HIPCHK(c, hipStreamWaitEvent(c->stream, pre->ev, 0));
+    const SelPlan plan = plan_selection(c, s, geom, mode, use_pyramid, n);
+    c->sel_valmap = !plan.pre;
+    Consume consume{plan.pre};
+    if (plan.pre) {
+        if (event_live(c, plan.pre->ev_serial)) HIPCHK(c, hipStreamWaitEvent(c->stream, plan.pre->ev, 0));
         else if (c->bstream && !c->capturing) HIPCHK(c, hipStreamSynchronize(c->bstream));
     } else {
         // summed-area tables (goodFeaturesUtils.pyx:49-51)
         if (int rc = enqueue_sat(c, c->stream, gx, gy, c->sat, nc, nr)) return rc;
     }
-
     const uint8_t *seed = nullptr;
-    // REPLACING_SOME: the squares of the live features are marked first; the eigenvalue kernels skip marked pixels, so neither the
-    // scoring nor the minimum-distance stage ever sees them
-    if (mode == KLT_REPLACING_SOME && d >= 0) {
-        const uint8_t *before = c->seedmap;
-        if (int rc = ensure(c, c->seedmap, c->seed_cap, N)) return rc;
-        if (c->seedmap != before || c->seed_n != N || c->seed_stamp == 255) {       // new map, other frame size, or the stamps wrapped
-            HIPCHK(c, hipMemsetAsync(c->seedmap, 0, N, c->stream));
-            c->seed_n = N;
-            c->seed_stamp = 0;
-        }
-        c->seed_stamp++;
-        TimerScope t(c, F_SEED, (double)n * 16);
-        launch_seed_fill(c->stream, b->d, n, c->seedmap, nc, nr, d, c->seed_stamp);
-        seed = c->seedmap;
-    }
+    if (mode == KLT_REPLACING_SOME && plan.d >= 0)
+        if (int rc = mark_live_squares(c, b->d, n, nc, nr, plan.d, &seed)) return rc;
 
     SelectArgs sa;
+    std::memset(&sa, 0, sizeof(sa));
     sa.sat = c->sat; sa.valmap = c->valmap; sa.keys = c->keys; sa.seedmap = seed; sa.seed_stamp = c->seed_stamp;
-    sa.val_in = nullptr;
-    sa.hist = sa.ticket = sa.info = nullptr; sa.hist_target = 0; sa.hist_slots = nullptr; sa.hist_per_slot = 0;
+    fill_select_geometry(sa, nc, nr, geom, plan.min_eig);
     if (c->score_override_n) {
         const int given = c->score_override_n;
         c->score_override_n = 0;
-        if (given != ncand) return fail(c, KLT_ERR_ARG, "score override does not match the candidate grid");
+        if (given != geom.ncand) return fail(c, KLT_ERR_ARG, "score override does not match the candidate grid");
         sa.val_in = c->score_override;
     }
-    sa.min_eig = min_eig;
-    sa.ncols = nc; sa.nrows = nr; sa.bx = bx; sa.by = by; sa.step = step; sa.nx = nx; sa.ny = ny;
-    sa.hw = hw; sa.hh = hh; sa.npow2 = (int)npow2;
-    if (!parallel_nms) { TimerScope t(c, F_EIGEN, 12.0 * N + (double)ncand * (4 + 8)); launch_eigen(c->stream, sa); }
+    if (!plan.parallel_nms) { TimerScope t(c, F_EIGEN, 12.0 * nc * nr + (double)geom.ncand * (4 + 8)); launch_eigen(c->stream, sa); }
     NmsArgs na;
-    std::memset(&na, 0, sizeof(na));
-    na.fl = b->d; na.placed_out = c->placed_d;
-    na.nfeat = n; na.overwrite_all = (mode == KLT_SELECTING_ALL);
-    na.d = d; na.cell = d >= 0 ? d + 1 : 1;
-    na.cell_magic = na.cell == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)na.cell) + 1u;
-    if (int rc = ensure(c, c->nms_slots, c->nms_slots_cap, (size_t)n)) return rc;
-    na.slots = c->nms_slots;
-    na.aff_rec = nullptr;
+    if (int rc = make_nms_args(c, b->d, n, mode == KLT_SELECTING_ALL, plan.d, nc, nr, na)) return rc;
     if (c->select_aff_state >= 0) {
         AffState &as = c->aff[c->select_aff_state];
         if (as.n < n) return fail(c, KLT_ERR_STATE, "affine state smaller than the feature list");
         na.aff_rec = as.rec;
     }
-    na.gw = (nc + na.cell - 1) / na.cell; na.gh = (nr + na.cell - 1) / na.cell;
-    if (d < 0) { na.gw = na.gh = 1; }
-    const size_t grid_bytes = (size_t)na.gw * na.gh * sizeof(uint32_t);
-    na.grid_in_lds = grid_bytes <= 128 * 1024;     // + 12.4 KiB of static LDS in the kernel
-    na.grid_global = nullptr;
-    if (!na.grid_in_lds) {
-        if (int rc = ensure(c, c->grid, c->grid_cap, (size_t)na.gw * na.gh)) return rc;
-        na.grid_global = c->grid;
-    }
-    auto run_nms = [&](const unsigned long long *keys, int nkeys) -> int {
-        na.keys = keys;
-        na.nkeys = nkeys;
-        if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, grid_bytes, c->stream));
-        TimerScope t(c, F_NMS, (double)n * 16);
-        const int e = launch_nms(c->stream, na);
-        if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
-        return 0;
-    };
-
-    // ---- parallel minimum distance (default): decide every candidate in a few passes, rank the accepted ones, and
-    // fill the free slots with the best of them (same result as the sorted serial walk below)
-    if (parallel_nms) {
-        auto job = std::make_unique<SelectJob>();
-        SelectJob &j = *job;
-        // passes enqueued before the host looks at the outcome: what the previous selection needed (frames of a sequence
-        // behave alike); an idle pass costs 5 us, a second look costs a host round trip
-        j.rounds_per_look = c->mis_rounds_hint;
-        const int tiles = mis_tiles(nx, ny);
-        // two accepted candidates are more than R cells apart in x or in y: at most one per (R+1)x(R+1) block of cells
-        j.bound = R < 0 ? ncand : (long long)((nx + R) / (R + 1)) * ((ny + R) / (R + 1));
-        j.by_rank = j.bound <= 98304;                       // rank by counting; beyond that sort the accepted keys
-        j.np2 = 2048;
-        while (j.np2 < j.bound) j.np2 <<= 1;
-        // one allocation of counters: [tiles] list lengths | [kMaxRounds] "undecided left after pass r" | accepted count |
-        // workgroup ticket | [tiles] accepted per tile | 8192 histogram bins + 4 words of prefilter info | [bound] ranks
-        const size_t off_rem = (size_t)tiles, off_acc = off_rem + SelectJob::kMaxRounds, off_ticket = off_acc + 1, off_tacc = off_ticket + 1,
-                     off_hist = off_tacc + tiles, off_rank = off_hist + 8192 + 4;
-        const int tile_cap = mis_tile_capacity(R);
-        const size_t n_cnt = off_rank + (j.by_rank ? (size_t)j.bound : 0);
-        if (int rc = ensure(c, c->keys2, c->keys2_cap, (size_t)(j.np2 > npow2 ? j.np2 : npow2))) return rc;
-        if (int rc = ensure(c, c->mis_st, c->mis_st_cap, (size_t)ncand)) return rc;
-        if (int rc = ensure(c, c->mis_list, c->mis_list_cap, (size_t)tiles * 1024)) return rc;
-        if (int rc = ensure(c, c->mis_cnt, c->mis_cnt_cap, n_cnt)) return rc;
-        if (int rc = ensure(c, c->mis_tile_keys, c->mis_tile_keys_cap, (size_t)tiles * tile_cap)) return rc;
-        if (int rc = ensure(c, c->fl_snapshot, c->fl_snapshot_cap, (size_t)n)) return rc;
-        // results come back through pinned host memory the kernels write to directly
-        if (!c->readback) {
-            void *hp = nullptr;
-            if (int rc = host_alloc(c, &hp, 128 * sizeof(unsigned), "selection read-back words")) return rc;
-            c->readback = (unsigned *)hp;
-            c->pinned.push_back(hp);
-        }
-        j.fl = b->d; j.n = n; j.ncand = ncand; j.mode = mode; j.prefilter = prefilter; j.target = target; j.pre = pre;
-        j.zero_from = c->mis_cnt + off_rem; j.zero_n = n_cnt - off_rem;
-        j.hist_d = c->mis_cnt + off_hist; j.ticket_d = c->mis_cnt + off_ticket;
-        j.info_d = c->mis_cnt + off_hist + 8192; j.rank_d = c->mis_cnt + off_rank;
-        j.acc_count_d = c->mis_cnt + off_acc;
-        j.nfill_d = c->placed_d + 2;
-        MisArgs &ma = j.ma;
-        ma.keys = pre ? pre->keys : c->keys; ma.seed = pre ? seed : nullptr; ma.seed_stamp = c->seed_stamp; ma.ncols = nc; ma.st = c->mis_st; ma.list = c->mis_list; ma.cnt = c->mis_cnt;
-        ma.remaining = c->mis_cnt + off_rem; ma.acc_cnt = c->mis_cnt + off_tacc; ma.acc_cap = tile_cap;
-        ma.acc_keys = c->mis_tile_keys; ma.info = j.info_d;
-        ma.nx = nx; ma.ny = ny; ma.R = R; ma.stage = 1; ma.bx = bx; ma.by = by; ma.step = step;
-        ma.sparse = mode == KLT_REPLACING_SOME && prefilter ? 1 : 0;
-        j.pa = na;                                          // placement: the accepted candidates never exclude each other
-        j.pa.d = -1; j.pa.cell = 1; j.pa.cell_magic = 0u; j.pa.gw = j.pa.gh = 1; j.pa.grid_in_lds = 1; j.pa.grid_global = nullptr;
-        j.pa.keys = c->keys2; j.pa.nkeys = (int)j.np2;
-        j.sa = sa;
-        consume.e = nullptr;                                // the job frees the score set when it is through with it
-        if (int rc = select_job_start(c, j)) return rc;
-        if (int rc = select_job_rounds(c, j)) return rc;
-        c->sel_job = std::move(job);
-        HIPCHK(c, hipGetLastError());
-        return KLT_OK;
-    }
-
-    // ---- sorted serial walk (KLT_OPT_SELECT_PARALLEL_NMS = 0, or an exclusion square too large for the LDS tile)
-    // top-K prefilter: sort only the candidates the greedy walk can plausibly reach (one small D2H read-back)
-    if (prefilter) {
-        if (int rc = ensure(c, c->keys2, c->keys2_cap, (size_t)npow2)) return rc;
-        size_t hcap = c->topk_hist ? 8192 + 4 : 0;
-        if (int rc = ensure(c, c->topk_hist, hcap, (size_t)8192 + 4)) return rc;
-        if (int rc = ensure(c, c->fl_snapshot, c->fl_snapshot_cap, (size_t)n)) return rc;
-        HIPCHK(c, hipMemsetAsync(c->topk_hist, 0, (8192 + 4) * sizeof(unsigned), c->stream));
-        unsigned info[4] = {0, 0, 0, 0};
-        {
-            TimerScope t(c, F_SORT, (double)ncand * 16);
-            launch_topk_prefilter(c->stream, c->keys, (int)ncand, (unsigned)target, c->topk_hist, c->topk_hist + 8192, c->keys2);
-        }
-        HIPCHK(c, hipMemcpyAsync(info, c->topk_hist + 8192, sizeof(info), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const long long kept = info[3], valid = info[2];
-        long long np2 = 2048;
-        while (np2 < kept) np2 <<= 1;
-        if (kept < np2) HIPCHK(c, hipMemsetAsync(c->keys2 + kept, 0, (size_t)(np2 - kept) * sizeof(unsigned long long), c->stream));
-        { TimerScope t(c, F_SORT, (double)np2 * 16); launch_sort_desc(c->stream, c->keys2, (int)np2); }
-        HIPCHK(c, hipMemcpyAsync(c->fl_snapshot, b->d, (size_t)n * sizeof(klt_feat), hipMemcpyDefault, c->stream));
-        if (int rc = run_nms(c->keys2, (int)kept)) return rc;
-        c->sorted_keys = c->keys2; c->sorted_count = (int)kept;
-        int res[2] = {0, 0};
-        HIPCHK(c, hipMemcpyAsync(res, c->placed_d, sizeof(res), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (!(res[1] && kept < valid)) { HIPCHK(c, hipGetLastError()); return KLT_OK; }
-        // the kept candidates ran out before the list was full: restore the list and take the full sort
-        HIPCHK(c, hipMemcpyAsync(b->d, c->fl_snapshot, (size_t)n * sizeof(klt_feat), hipMemcpyDefault, c->stream));
-    }
-    { TimerScope t(c, F_SORT, (double)npow2 * 16); launch_sort_desc(c->stream, c->keys, (int)npow2); }
-    if (int rc = run_nms(c->keys, (int)(ncand < npow2 ? ncand : npow2))) return rc;
-    c->sorted_keys = c->keys; c->sorted_count = (int)(ncand < npow2 ? ncand : npow2);
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
+    if (plan.parallel_nms) return begin_parallel_selection(c, plan, sa, na, mode, consume);
+    return serial_selection(c, plan, sa, na);
 }
 
 int klt_select_finish(klt_ctx *c)
@@ -575,23 +637,9 @@ int klt_min_distance_walk(klt_ctx *c, const uint64_t *keys, int nkeys, int ncols
     if (nkeys) HIPCHK(c, hipMemcpyAsync(c->keys2, keys, (size_t)nkeys * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->keys2 + nkeys, 0, sizeof(uint64_t), c->stream));            // a zero key ends the walk
     NmsArgs na;
-    std::memset(&na, 0, sizeof(na));
     const int d = (mindist < 0 ? 0 : mindist) - 1;        // :61 (and :241-243 for a negative minimum distance)
-    na.fl = c->fbs[fb].d; na.placed_out = c->placed_d;
-    na.nfeat = n; na.overwrite_all = overwrite_all != 0;
-    na.d = d; na.cell = d >= 0 ? d + 1 : 1;
-    na.cell_magic = na.cell == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)na.cell) + 1u;
-    if (int rc = ensure(c, c->nms_slots, c->nms_slots_cap, (size_t)n)) return rc;
-    na.slots = c->nms_slots;
-    na.gw = d >= 0 ? (ncols + na.cell - 1) / na.cell : 1;
-    na.gh = d >= 0 ? (nrows + na.cell - 1) / na.cell : 1;
-    const size_t grid_bytes = (size_t)na.gw * na.gh * sizeof(uint32_t);
-    na.grid_in_lds = grid_bytes <= 128 * 1024;
-    if (!na.grid_in_lds) {
-        if (int rc = ensure(c, c->grid, c->grid_cap, (size_t)na.gw * na.gh)) return rc;
-        na.grid_global = c->grid;
-        HIPCHK(c, hipMemsetAsync(c->grid, 0, grid_bytes, c->stream));
-    }
+    if (int rc = make_nms_args(c, c->fbs[fb].d, n, overwrite_all != 0, d, ncols, nrows, na)) return rc;
+    if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
     na.keys = c->keys2; na.nkeys = nkeys + 1;
     if (const int e = launch_nms(c->stream, na)) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
     c->sorted_keys = nullptr; c->sorted_count = 0;
@@ -599,7 +647,6 @@ int klt_min_distance_walk(klt_ctx *c, const uint64_t *keys, int nkeys, int ncols
     if (n_placed) HIPCHK(c, hipMemcpy(n_placed, c->placed_d, sizeof(int), hipMemcpyDeviceToHost));
     return KLT_OK;
 }
-
 
 int klt_select_dims(klt_ctx *c, int what, int *ncols, int *nrows)
 {
@@ -652,6 +699,5 @@ int klt_download_sorted_candidates(klt_ctx *c, float *val, int32_t *x, int32_t *
     if (n_valid) *n_valid = k;
     return KLT_OK;
 }
-
 
 }  // extern "C"

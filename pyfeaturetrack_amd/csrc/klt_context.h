@@ -318,6 +318,12 @@ struct TimerScope {
     }
 };
 
+// whoever points c->work at the build stream holds one of these: the helpers enqueue on the main stream again on every way out
+struct WorkScope {
+    klt_ctx *c;
+    ~WorkScope() { c->work = c->stream; }
+};
+
 // ---- api_context.hip
 int drain_timers(klt_ctx *c);
 int sync_all(klt_ctx *c);

@@ -951,6 +951,31 @@ def test_topk_prefilter_and_its_fallback(ctx, ko):
         assert_feats(fl2, *oracle_feats(ofl), what="full-sort select mindist=%d n=%d" % (mindist, n))
 
 
+def test_serial_walk_behind_the_prefilter_and_its_fallback(ctx, ko):
+    """The sorted serial walk (KLT_OPT_SELECT_PARALLEL_NMS = 0) behind the top-K prefilter on the smallest frame that takes it
+    (720x480 at the default border: 277 200 candidates, the prefilter starts above 262 144).  Small minimum distance: the kept
+    candidates fill the list (prefilter + one sort).  Minimum distance 25 and more features than fit: they run out, the list is
+    put back and the full sort takes over (a third sort launch).  Either way the oracle's list."""
+    from pyfeaturetrack_amd import synth
+    f0 = synth.synth_frame(720, 480, 6, 0)
+    try:
+        ctx.set_option(8, 0)
+        for mindist, n, sorts in ((10, 500, 2), (25, 1500, 3)):
+            tc = make_tc(levels=2, ss=4, mindist=mindist)
+            ctx.configure(tc)
+            ctx.upload(0, f0)
+            ofl = ko.select_good_features(params_from_tc(tc), f0.astype(np.float32), n)
+            ctx.timing_enable(1)
+            fl, placed = ctx.select(0, n)
+            launches = {t["name"]: t["launches"] for t in ctx.timing_read()}
+            assert placed == int(np.count_nonzero(ofl["val"] >= 0))
+            assert_feats(fl, *oracle_feats(ofl), what="serial walk behind the prefilter mindist=%d n=%d" % (mindist, n))
+            assert launches["sort"] == sorts, launches
+    finally:
+        ctx.timing_enable(0)
+        ctx.set_option(8, 1)
+
+
 def test_replacement_cut_and_its_repeat(ctx, ko):
     """REPLACING_SOME at 1080p keeps 64 candidates per LOST feature (at least 4096).  Few lost features: the cut holds.  Many lost
     features under a large minimum distance: the kept candidates run out and the selection repeats with every candidate.  Either way
