@@ -31,7 +31,8 @@
 extern "C" {
 #endif
 
-#define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points: klt_set_fb_params / klt_track_fb* are purely additive, no
+#define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points and by the selection mask: klt_set_fb_params / klt_track_fb* /
+                                   * klt_set_select_mask* are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
@@ -255,6 +256,30 @@ int klt_select_finish(klt_ctx *ctx);
  * squares, cuts and runs the minimum-distance passes.  Same result with or without this call. */
 int klt_select_prepare_async(klt_ctx *ctx, int slot);
 int klt_select(klt_ctx *ctx, int slot, int mode, int use_pyramid, klt_feat *inout, int n, int *n_placed);
+/* Selection mask: where klt_select* may NOT place features (a vehicle's bonnet, a burnt-in timestamp, the sky, moving objects found by a
+ * segmentation network).  [nrows][ncols] bytes, state of the context like the parameters: a pixel whose byte is 0 is never a candidate,
+ * any other value leaves it eligible.  The selection is exactly what it would be had ScanImageForGoodFeatures never put the masked
+ * positions on the point list _enforceMinimumDistance walks (selectGoodFeatures.py:45-135, :230-236); nothing else changes: in
+ * KLT_REPLACING_SOME live features inside masked areas are kept and still block their squares; the tracker, klt_min_distance_walk,
+ * klt_scan_good_features_f32 and klt_select_prepare_async ignore the mask (prepared scores depend on neither list nor mask: the selection
+ * that uses them applies it); with klt_set_score_override both apply and the mask wins; in klt_download_select_f32(what = 3) masked
+ * candidates read 0.  A context without a mask enqueues nothing for it.
+ * klt_set_select_mask copies a HOST mask (pitch in bytes >= ncols) into a device plane the context owns before it returns.
+ * klt_set_select_mask_device takes a mask that is ALREADY in device memory (a network's output; klt_device_alloc / klt_device_write for
+ * callers without a HIP binding): rows without padding (pitch == ncols, cf. klt_slot_adopt_u8), the address a multiple of 16
+ * (KLT_ERR_ARG otherwise); it is read in place -- never a byte behind ncols * nrows -- and never written or freed by the library.
+ * mask == NULL / dev_mask == NULL removes the mask (the sizes are not looked at).
+ * When it is read: once per selection, in stream order, by a kernel klt_select_begin_async enqueues (klt_select_async and klt_select
+ * go through it); a repeat inside klt_select_finish (more passes, the fallback to every candidate) does not read it again.  The
+ * contents of a device mask may therefore be changed as soon as klt_select_begin_async has returned and the stream has passed that
+ * point (klt_device_write, or a kernel enqueued behind it on klt_stream_handle).  The mask ITSELF cannot be set or removed while a
+ * selection is pending: KLT_ERR_STATE between klt_select_begin_async and klt_select_finish.
+ * A mask whose size differs from the frame of the slot a selection is asked for makes that klt_select* call return KLT_ERR_ARG (the
+ * message names both sizes) before it enqueues anything; the mask stays set and the context usable.  A klt_set_select_mask that fails
+ * (KLT_ERR_NOMEM for the plane) leaves the context WITHOUT a mask, and so does klt_device_free of the allocation a device mask
+ * lives in. */
+int klt_set_select_mask(klt_ctx *ctx, const uint8_t *mask, int ncols, int nrows, int pitch);
+int klt_set_select_mask_device(klt_ctx *ctx, const uint8_t *dev_mask, int ncols, int nrows);
 /* replaces _enforceMinimumDistance(pointlist, featurelist, ncols, nrows, mindist, min_eigenvalue, overwriteAllFeatures) called on its own
  * (selectGoodFeatures.py:45-135): the greedy walk over a GIVEN candidate list in the GIVEN order.  keys[i] = f32 bits of val << 32 |
  * x << 16 | y (what klt_download_sorted_candidates returns, re-packed); the caller has dropped the candidates the walk skips without
@@ -381,7 +406,7 @@ int klt_level_dims(klt_ctx *ctx, int slot, int level, int *ncols, int *nrows);
 int klt_download_f32(klt_ctx *ctx, int slot, int pyramid, int level, float *dst);
 /* selection intermediates of the last klt_select*: 0 = smoothed image, 1 = gradx, 2 = grady (full frame),
  * 3 = eigenvalue map [ny][nx] (scan order, goodFeaturesUtils.pyx:53-54; after a KLT_REPLACING_SOME selection the pixels inside
- * the exclusion squares of the live features read 0: they can never be placed and are not scored; a selection that used the
+ * the exclusion squares of the live features read 0, as do the candidates a selection mask excludes: they can never be placed and are not scored; a selection that used the
  * scores of klt_select_prepare_async writes no map, and 3 is refused after it).  dims via klt_select_dims. */
 int klt_select_dims(klt_ctx *ctx, int what, int *ncols, int *nrows);
 int klt_download_select_f32(klt_ctx *ctx, int what, float *dst);

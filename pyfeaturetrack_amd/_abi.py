@@ -110,6 +110,8 @@ SYMBOLS = {
     "klt_select_finish": (_I, [_P]),
     "klt_select_prepare_async": (_I, [_P, _I]),
     "klt_select": (_I, [_P, _I, _I, _I, _P, _I, _PI]),
+    "klt_set_select_mask": (_I, [_P, _P, _I, _I, _I]),
+    "klt_set_select_mask_device": (_I, [_P, _P, _I, _I]),
     "klt_min_distance_walk": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _PI]),
     "klt_track_async": (_I, [_P, _I, _I, _I, _I, _I]),
     "klt_track": (_I, [_P, _I, _I, _P, _I, _PI]),

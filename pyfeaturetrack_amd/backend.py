@@ -528,6 +528,47 @@ class Context:
         """Scores of the slot's level-0 images ahead of a REPLACING_SOME selection on it (klt_select_prepare_async); asynchronous."""
         self._check(self._lib.klt_select_prepare_async(self._h, slot))
 
+    # ------------------------------------------------------------- selection mask
+    # `_mask_state`: what the host layer knows of the context's mask -- None: there is none; an array: the copy of the bytes
+    # sync_select_mask sent; "direct": set by a caller of the two methods below (or a call that failed half way): unknown bytes
+    def set_select_mask(self, mask):
+        """klt_set_select_mask: `mask` a 2-D uint8 array (a byte of 0 = never a candidate; rows may be strided), copied to the device
+        before this returns; None removes the mask.  What every later selection of this context honours, until it is set again."""
+        self._mask_state = "direct"
+        if mask is None:
+            self._check(self._lib.klt_set_select_mask(self._h, None, 0, 0, 0))
+            self._mask_state = None
+            return
+        a = np.asarray(mask)
+        if a.ndim != 2 or a.dtype != np.uint8:
+            raise ValueError("set_select_mask takes a 2-D uint8 array")
+        if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            a = np.ascontiguousarray(a)
+        self._check(self._lib.klt_set_select_mask(self._h, a.ctypes.data, a.shape[1], a.shape[0], a.strides[0]))
+
+    def set_select_mask_device(self, dev, ncols, nrows):
+        """klt_set_select_mask_device: the mask IS the [nrows][ncols] bytes at device address `dev` (device_alloc / device_write, or
+        another library's buffer; a multiple of 16), read in place by every selection; None removes the mask."""
+        self._mask_state = "direct"
+        self._check(self._lib.klt_set_select_mask_device(self._h, None if dev is None else C.c_void_p(dev), int(ncols), int(nrows)))
+        if dev is None:
+            self._mask_state = None
+
+    def sync_select_mask(self, mask):
+        """The reference-shaped API's mask (params.selection_mask_from_tc: None or a C-contiguous 2-D uint8 array): sent only when its
+        bytes differ from the copy kept of what the context holds (klt_host_compare), so an array changed in place takes effect and
+        an unchanged one costs one pass over it."""
+        state = self.__dict__.get("_mask_state")
+        if mask is None:
+            if state is not None:
+                self.set_select_mask(None)
+            return
+        from ._frames import same_pixels
+        if isinstance(state, np.ndarray) and same_pixels(state, mask):
+            return
+        self.set_select_mask(mask)
+        self._mask_state = mask.copy()
+
     def select_intermediate(self, what):
         nc, nr = C.c_int(), C.c_int()
         self._check(self._lib.klt_select_dims(self._h, what, C.byref(nc), C.byref(nr)))

@@ -576,6 +576,8 @@ int klt_device_free(klt_ctx *c, void *p)
                 if (s.u8_ext && s.u8_ext >= lo && s.u8_ext < hi) {
                     s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.gen = 0; s.nc = s.nr = 0;
                 }
+            // likewise a selection mask that lives inside it (klt_set_select_mask_device): the context has no mask any more
+            if (c->mask && c->mask >= lo && c->mask < hi) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }
             hipFree(p);
             c->dev_allocs.erase(c->dev_allocs.begin() + (long)i);
             c->dev_alloc_bytes.erase(c->dev_alloc_bytes.begin() + (long)i);

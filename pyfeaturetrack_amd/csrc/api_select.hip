@@ -315,23 +315,50 @@ struct Consume {                                           // a set is used once
     ~Consume() { if (e) e->gen = 0; }
 };
 
-// REPLACING_SOME: the squares of the live features are marked first; the eigenvalue kernels skip marked pixels, so neither the
-// scoring nor the minimum-distance stage ever sees them.  Leaves the seed map stamped with c->seed_stamp.
-int mark_live_squares(klt_ctx *c, const klt_feat *fl, int n, int nc, int nr, int d, const uint8_t **seed)
+// ---- the seed map: per-pixel "never a candidate" marks, read by the scoring kernels (eigen_key, mask_hist_kernel) and by mis_init.  It is
+// stamped, not cleared: a pixel is blocked when it carries THIS selection's stamp.  One step begins the map, two steps fill it.
+
+// Leaves a map for an nc x nr frame in which no pixel carries the stamp c->seed_stamp (a new one): allocated (whole 16-byte pieces, which
+// fill_select_mask stores), cleared when it is new, when the frame size changed or when the stamps wrapped at 255.
+int begin_seed_map(klt_ctx *c, int nc, int nr, const uint8_t **seed)
 {
-    const size_t N = (size_t)nc * nr;
+    const size_t N = (size_t)nc * nr, padded = (N + 15) & ~(size_t)15;
     const uint8_t *before = c->seedmap;
-    if (int rc = ensure(c, c->seedmap, c->seed_cap, N)) return rc;
+    if (int rc = ensure(c, c->seedmap, c->seed_cap, padded)) return rc;
     if (c->seedmap != before || c->seed_n != N || c->seed_stamp == 255) {       // new map, other frame size, or the stamps wrapped
-        HIPCHK(c, hipMemsetAsync(c->seedmap, 0, N, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->seedmap, 0, padded, c->stream));
         c->seed_n = N;
         c->seed_stamp = 0;
     }
     c->seed_stamp++;
-    TimerScope t(c, F_SEED, (double)n * 16);
-    launch_seed_fill(c->stream, fl, n, c->seedmap, nc, nr, d, c->seed_stamp);
     *seed = c->seedmap;
     return 0;
+}
+
+// REPLACING_SOME: the squares of the live features are marked; the eigenvalue kernels skip marked pixels, so neither the
+// scoring nor the minimum-distance stage ever sees them.
+void fill_live_squares(klt_ctx *c, const klt_feat *fl, int n, int nc, int nr, int d)
+{
+    TimerScope t(c, F_SEED, (double)n * 16);
+    launch_seed_fill(c->stream, fl, n, c->seedmap, nc, nr, d, c->seed_stamp);
+}
+
+// klt_set_select_mask*: the pixels whose mask byte is 0 are marked the same way.  The mask is read here, once per selection: a repeat inside
+// klt_select_finish reuses the stamped map.
+void fill_select_mask(klt_ctx *c, int nc, int nr)
+{
+    const size_t N = (size_t)nc * nr;
+    TimerScope t(c, F_SEED, 2.0 * N);
+    launch_seed_mask(c->stream, c->mask, c->seedmap, N, c->seed_stamp);
+}
+
+// a mask belongs to frames of one size: another one is the caller's mistake, found before anything is enqueued
+int check_select_mask(klt_ctx *c, int nc, int nr)
+{
+    if (!c->mask || (c->mask_nc == nc && c->mask_nr == nr)) return 0;
+    char msg[160];
+    snprintf(msg, sizeof msg, "the selection mask is %d x %d, the slot's frame %d x %d (klt_set_select_mask)", c->mask_nc, c->mask_nr, nc, nr);
+    return fail(c, KLT_ERR_ARG, msg);
 }
 
 // ---- parallel minimum distance (default): decide every candidate in a few passes, rank the accepted ones, and
@@ -537,6 +564,7 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
     if (int rc = get_fb(c, fb, n, &b)) return rc;
     SelGeom geom;
     if (int rc = select_geometry(c, nc, nr, &geom)) return rc;
+    if (int rc = check_select_mask(c, nc, nr)) return rc;
 
     if (int rc = ensure_select_scratch(c, (size_t)nc * nr, geom.npow2)) return rc;
     const float *img, *gx, *gy;
@@ -555,8 +583,12 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
         if (int rc = enqueue_sat(c, c->stream, gx, gy, c->sat, nc, nr)) return rc;
     }
     const uint8_t *seed = nullptr;
-    if (mode == KLT_REPLACING_SOME && plan.d >= 0)
-        if (int rc = mark_live_squares(c, b->d, n, nc, nr, plan.d, &seed)) return rc;
+    const bool live_squares = mode == KLT_REPLACING_SOME && plan.d >= 0;
+    if (live_squares || c->mask) {
+        if (int rc = begin_seed_map(c, nc, nr, &seed)) return rc;
+        if (live_squares) fill_live_squares(c, b->d, n, nc, nr, plan.d);
+        if (c->mask) fill_select_mask(c, nc, nr);
+    }
 
     SelectArgs sa;
     std::memset(&sa, 0, sizeof(sa));
@@ -676,6 +708,45 @@ int klt_set_score_override(klt_ctx *c, const float *val, int count)
     HIPCHK(c, hipMemcpyAsync(c->score_override, val, (size_t)count * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->score_override_n = count;
+    return KLT_OK;
+}
+
+// the context has no mask from here on (what a failed klt_set_select_mask* leaves as well)
+static void drop_select_mask(klt_ctx *c) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }
+
+static int select_mask_args(klt_ctx *c, int ncols, int nrows)
+{
+    if (ncols <= 0 || nrows <= 0 || (long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "bad selection mask size");
+    return 0;
+}
+
+int klt_set_select_mask(klt_ctx *c, const uint8_t *mask, int ncols, int nrows, int pitch)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (c->sel_job) return fail(c, KLT_ERR_STATE, "a selection is pending: klt_select_finish first");
+    if (!mask) { drop_select_mask(c); return KLT_OK; }
+    if (int rc = select_mask_args(c, ncols, nrows)) return rc;
+    if (pitch < ncols) return fail(c, KLT_ERR_ARG, "selection mask: pitch smaller than ncols");
+    HIPCHK(c, hipSetDevice(c->device));
+    drop_select_mask(c);
+    const size_t N = (size_t)ncols * nrows;
+    if (int rc = ensure(c, c->mask_own, c->mask_own_cap, (N + 15) & ~(size_t)15)) return rc;
+    // rows packed on the way (the plane is the library's: the kernel then reads a host mask and a device mask alike); behind whatever
+    // still reads the plane's previous contents on the stream
+    HIPCHK(c, hipMemcpy2DAsync(c->mask_own, (size_t)ncols, mask, (size_t)pitch, (size_t)ncols, (size_t)nrows, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mask = c->mask_own; c->mask_nc = ncols; c->mask_nr = nrows;
+    return KLT_OK;
+}
+
+int klt_set_select_mask_device(klt_ctx *c, const uint8_t *dev_mask, int ncols, int nrows)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (c->sel_job) return fail(c, KLT_ERR_STATE, "a selection is pending: klt_select_finish first");
+    if (!dev_mask) { drop_select_mask(c); return KLT_OK; }
+    if (int rc = select_mask_args(c, ncols, nrows)) return rc;
+    if ((uintptr_t)dev_mask & 15) return fail(c, KLT_ERR_ARG, "selection mask: the device address must be a multiple of 16 (it is read 16 bytes at a time)");
+    c->mask = dev_mask; c->mask_nc = ncols; c->mask_nr = nrows;
     return KLT_OK;
 }
 

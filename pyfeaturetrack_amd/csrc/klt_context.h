@@ -168,7 +168,13 @@ struct klt_ctx {
     size_t keys_cap = 0;
     uint8_t *seedmap = nullptr;
     size_t seed_cap = 0, seed_n = 0;          // pixels the stamps in the map are valid for
-    uint8_t seed_stamp = 0;                   // stamp of the latest replacement pass (1..255)
+    uint8_t seed_stamp = 0;                   // stamp of the latest selection that used the map (1..255)
+    // selection mask (klt_set_select_mask*): what the selections read -- the context's own plane (a host mask's copy) or the caller's
+    // device memory, [mask_nr][mask_nc] bytes without padding between rows; null = no mask
+    const uint8_t *mask = nullptr;
+    int mask_nc = 0, mask_nr = 0;
+    uint8_t *mask_own = nullptr;
+    size_t mask_own_cap = 0;
     uint32_t *grid = nullptr;
     size_t grid_cap = 0;
     int *nms_slots = nullptr;

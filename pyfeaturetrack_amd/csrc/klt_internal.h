@@ -101,7 +101,7 @@ struct SelectArgs {
     const float *sat;        // 3 planes (gxx, gxy, gyy), each ncols*nrows
     float *valmap;           // [ny][nx]
     unsigned long long *keys;
-    const uint8_t *seedmap;  // may be null; a pixel is blocked when it holds seed_stamp
+    const uint8_t *seedmap;  // may be null; a pixel is blocked when it holds seed_stamp (a live feature's square, or a selection mask's zero)
     uint8_t seed_stamp;
     const float *val_in;     // test hook: eigenvalues given instead of computed (may be null)
     unsigned *hist, *ticket, *info;   // eigen_hist_kernel: 8192 bins, workgroup ticket, threshold info (hist may be null)
@@ -136,7 +136,7 @@ struct MisArgs {
     const unsigned *info;             // info[0] = lowest key bin that takes part (top-K prefilter)
     int nx, ny, R /* exclusion radius in cells */, stage /* 1: stage tile + halo in LDS */;
     int bx, by, step;                 // pixel position of cell (i, j) = (bx + i * step, by + j * step)
-    const uint8_t *seed;              // optional: [nrows][ncols] squares of the live features (pixels holding seed_stamp); keys were scored WITHOUT it
+    const uint8_t *seed;              // optional: [nrows][ncols] squares of the live features and the selection mask's zeros (pixels holding seed_stamp); keys were scored WITHOUT it
     uint8_t seed_stamp;               // (klt_select_prepare_async)
     int ncols;
     int sparse;                       // 1: few candidates per tile are expected (a replacement behind the cut): later passes take several tiles per workgroup
@@ -263,6 +263,8 @@ constexpr int KLT_SAT_PAD = 64;
 bool sat_cols_eigen_ok(const SelectArgs &a);
 int  launch_sat_cols_eigen_pipe(hipStream_t s, const float *sat, const SelectArgs &a);
 void launch_seed_fill(hipStream_t s, const klt_feat *fl, int nfeat, uint8_t *seedmap, int ncols, int nrows, int d, uint8_t stamp);
+// a selection mask of n bytes (16-byte aligned; 0 = never a candidate) merged into the seed map, which has room for n rounded up to 16
+void launch_seed_mask(hipStream_t s, const uint8_t *mask, uint8_t *seedmap, size_t n, uint8_t stamp);
 void launch_eigen(hipStream_t s, const SelectArgs &a);
 void launch_sort_desc(hipStream_t s, unsigned long long *keys, int npow2);
 void launch_topk_prefilter(hipStream_t s, const unsigned long long *keys, int n, unsigned target, unsigned *hist,

@@ -217,6 +217,56 @@ __global__ void seed_fill_kernel(const klt_feat *__restrict__ fl, int nfeat, uin
     }
 }
 
+// A caller's selection mask (klt_set_select_mask*) merged into the seed map: a pixel whose mask byte is 0 gets this selection's stamp, like
+// a pixel inside a live feature's square.  Both planes are flat arrays of n = ncols * nrows bytes (a row's end is nothing special; what
+// is left is the end of the plane when n % 16 != 0).  Runs on every frame of a masked sequence, so it streams: a lane takes 16 mask bytes
+// with one load; a piece without a zero byte writes nothing (and does not read the map), a piece of zero bytes is one 16-byte store of
+// stamps, a mixed piece reads the map's 16 bytes and stores the dwords that changed.  The mask is caller memory when it was given as
+// a device pointer: its last n % 16 bytes are loaded one by one by a single lane and nothing behind byte n - 1 is read.  The seed map is
+// the library's and padded to whole 16-byte pieces (begin_seed_map), so the tail is merged and stored like any other piece.
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t w)          // 0xff in every byte of w that is 0
+{
+    const uint32_t low7 = 0x7f7f7f7fu;
+    const uint32_t t = ~(((w & low7) + low7) | w | low7);          // 0x80 in every zero byte
+    return (t >> 7) * 0xffu;
+}
+
+__device__ __forceinline__ void seed_mask_piece(uint4 m, uint8_t *__restrict__ seed16, uint32_t stamp4)
+{
+    const uint32_t z[4] = {zero_bytes(m.x), zero_bytes(m.y), zero_bytes(m.z), zero_bytes(m.w)};
+    if ((z[0] | z[1] | z[2] | z[3]) == 0u) return;
+    uint4 *const out = reinterpret_cast<uint4 *>(seed16);
+    if ((z[0] & z[1] & z[2] & z[3]) == 0xffffffffu) { *out = make_uint4(stamp4, stamp4, stamp4, stamp4); return; }
+    const uint4 s = *out;
+    const uint32_t old[4] = {s.x, s.y, s.z, s.w};
+    uint32_t *const w = reinterpret_cast<uint32_t *>(seed16);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (z[k]) w[k] = (old[k] & ~z[k]) | (stamp4 & z[k]);
+}
+
+__global__ __launch_bounds__(256) void seed_mask_kernel(const uint8_t *__restrict__ mask, uint8_t *__restrict__ seedmap, size_t n, uint8_t stamp)
+{
+    const uint32_t stamp4 = 0x01010101u * stamp;
+    const size_t pieces = n / 16;
+    const uint4 *const m16 = reinterpret_cast<const uint4 *>(mask);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < pieces; i += (size_t)gridDim.x * 256)
+        seed_mask_piece(m16[i], seedmap + 16 * i, stamp4);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255 && (n & 15)) {      // the plane's last n % 16 bytes: bytes behind the end count as "allowed"
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            w[k] = ~0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const size_t b = 16 * pieces + 4 * k + j;
+                if (b < n && mask[b] == 0) w[k] &= ~(0xffu << (8 * j));
+            }
+        }
+        seed_mask_piece(make_uint4(w[0], w[1], w[2], w[3]), seedmap + 16 * pieces, stamp4);
+    }
+}
+
 // ------------------------------------------------------------------ eigenvalue map + sort keys
 __device__ __forceinline__ float window_sum(const float *__restrict__ s, int ncols, int x, int y, int hw, int hh)
 {
@@ -1240,6 +1290,14 @@ void launch_seed_fill(hipStream_t s, const klt_feat *fl, int nfeat, uint8_t *see
 {
     if (nfeat <= 0 || d < 0) return;
     hipLaunchKernelGGL(seed_fill_kernel, dim3(nfeat), dim3(64), 0, s, fl, nfeat, seedmap, ncols, nrows, d, stamp);
+}
+
+// mask: 16-byte aligned, n bytes; seedmap: room for n rounded up to whole 16-byte pieces
+void launch_seed_mask(hipStream_t s, const uint8_t *mask, uint8_t *seedmap, size_t n, uint8_t stamp)
+{
+    if (n == 0) return;
+    const size_t blocks = (n / 16 + 255) / 256;
+    hipLaunchKernelGGL(seed_mask_kernel, dim3((unsigned)(blocks < 2048 ? (blocks ? blocks : 1) : 2048)), dim3(256), 0, s, mask, seedmap, n, stamp);
 }
 
 void launch_eigen(hipStream_t s, const SelectArgs &a)

@@ -81,6 +81,9 @@ class KLT_TrackingContext:
         # rejected (KLT_FB_INCONSISTENT) when it does not land within fb_max_error pixels of where it started
         self.forwardBackwardCheck = False
         self.fb_max_error = 1.0
+        # selection mask (not in the reference): None, or a [nrows][ncols] array of bool / integers (or a Pillow "L" / "1" image) in
+        # which zero marks the pixels KLTSelectGoodFeatures / KLTReplaceLostFeatures / KLTTrackSequence never place a feature on
+        self.selectionMask = None
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

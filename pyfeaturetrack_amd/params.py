@@ -1,4 +1,6 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
+import numpy as np
+
 from ._abi import KltAffineParams, KltFbParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
@@ -58,6 +60,31 @@ def fb_params_from_tc(tc):
     if f.enabled and not f.max_error >= 0.0:
         raise ValueError("fb_max_error must be a number >= 0")
     return f
+
+
+def selection_mask_from_tc(tc, ncols=None, nrows=None):
+    """tc.selectionMask -> None, or the [nrows][ncols] uint8 array klt_set_select_mask takes (0 = never a candidate).  Read with a default:
+    a tracking context made elsewhere (the reference's own class) has no such attribute.  Accepted: a 2-D numpy array of bool or of any
+    integer type (non-zero = allowed), or a Pillow image of mode "L" or "1"; anything else is a TypeError, a shape other than the image's
+    (when `ncols` / `nrows` are given) a ValueError -- both before any device work.  A C-contiguous uint8 or bool array is used as it is
+    (no copy), so what is handed out must be looked at before the caller's next statement runs."""
+    mask = getattr(tc, "selectionMask", None)
+    if mask is None:
+        return None
+    if not isinstance(mask, np.ndarray):
+        if getattr(mask, "mode", None) not in ("L", "1") or not hasattr(mask, "size"):
+            raise TypeError("tc.selectionMask must be a 2-D numpy array of bool or integers, or a Pillow image of mode 'L' or '1' "
+                            "(got {0})".format(type(mask).__name__ if not hasattr(mask, "mode") else "an image of mode %r" % (mask.mode,)))
+        mask = np.asarray(mask)
+    if mask.dtype != np.bool_ and not np.issubdtype(mask.dtype, np.integer):
+        raise TypeError("tc.selectionMask must hold bool or integers, not {0}".format(mask.dtype))
+    if mask.ndim != 2:
+        raise ValueError("tc.selectionMask must be 2-D ({0} dimensions)".format(mask.ndim))
+    if ncols is not None and mask.shape != (nrows, ncols):
+        raise ValueError("tc.selectionMask is {0} by {1}, the image {2} by {3}".format(mask.shape[1], mask.shape[0], ncols, nrows))
+    if mask.dtype == np.bool_ or mask.dtype.itemsize == 1:
+        return np.ascontiguousarray(mask).view(np.uint8)            # (int8: a non-zero value is a non-zero byte)
+    return (mask != 0).view(np.uint8)
 
 
 def affine_params_from_tc(tc):

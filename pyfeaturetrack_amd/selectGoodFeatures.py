@@ -170,14 +170,18 @@ def _KLTSelectGoodFeatures(tc, img, nFeatures, mode, featurelist=None):
     if tc.mindist < 0:
         KLTWarning("(_KLTSelectGoodFeatures) Tracking context field tc.mindist is negative ({0}); setting to zero".format(tc.mindist))
         tc.mindist = 0
+    from .params import selection_mask_from_tc
+    ncols, nrows = _image_size(img)
+    mask = selection_mask_from_tc(tc, ncols, nrows)     # (TypeError / ValueError before any device work)
     ctx = context_of(tc)
     with ctx.lock:                                      # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
-        return _select_locked(ctx, tc, img, nFeatures, mode, featurelist)
+        return _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask)
 
 
-def _select_locked(ctx, tc, img, nFeatures, mode, featurelist):
+def _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask=None):
     from ._frames import FrameKey, cache_of, settle_frames
+    ctx.sync_select_mask(mask)                        # tc.selectionMask: sent when its bytes differ from what the context holds
     if cache_of(tc).handles and not ctx.configured_for(tc):
         cache_of(tc).keep_all_handles()               # new parameters void every pyramid of the context: kept handles fetch theirs first
     ctx.configure(tc)

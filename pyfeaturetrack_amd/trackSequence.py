@@ -141,10 +141,13 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     `replace_lost`, after replacing the lost ones on frame k: new features carry their eigenvalue in `val`, as after
     KLTReplaceLostFeatures).  tc.affineConsistencyCheck >= 0 runs the affine check on every step,
     tc.forwardBackwardCheck the forward-backward check (rejected features are lost ones: the replacement pass fills their slots).
+    tc.selectionMask (zero = no feature here) holds for the first selection and every replacement; it is read once, when the call starts.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
+    from .params import selection_mask_from_tc
+    selection_mask_from_tc(tc)           # (TypeError for a tc.selectionMask of an unknown kind, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -164,6 +167,9 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     first = pixels_of(next(frames))
     rows = [first]
     nrows, ncols = first.shape
+    from .params import selection_mask_from_tc
+    # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
+    ctx.sync_select_mask(selection_mask_from_tc(tc, ncols, nrows))
     affine = tc.affineConsistencyCheck >= 0
     from .params import fb_params_from_tc
     fb_check = bool(fb_params_from_tc(tc).enabled) and not affine       # forward-backward check in every tracker step
