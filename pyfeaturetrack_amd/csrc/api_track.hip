@@ -2,6 +2,30 @@
 // affine consistency check and its per-feature state, the iteration counters behind the roofline figures.
 #include "klt_context.h"
 
+// The caches of feature orders and descriptor tables: the entry that `match` accepts, or null ...
+template <class Entry, class Match>
+static Entry *cache_find(std::vector<Entry> &v, Match match)
+{
+    for (Entry &e : v)
+        if (match(e)) return &e;
+    return nullptr;
+}
+
+// ... and the place of a new entry: appended while the cache holds fewer than `capacity`, else the least recently used entry's (the
+// first one with the smallest `used` stamp), whose contents the caller replaces
+template <class Entry>
+static Entry *cache_place(std::vector<Entry> &v, size_t capacity)
+{
+    if (v.size() < capacity) {
+        v.emplace_back();
+        return &v.back();
+    }
+    Entry *lru = &v[0];
+    for (Entry &e : v)
+        if (e.used < lru->used) lru = &e;
+    return lru;
+}
+
 extern "C" {
 
 static void fill_track_params(const klt_ctx *c, const Slot *s1, TrackArgs &a, int n)
@@ -36,9 +60,7 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
 {
     if (!c->track_xcd_order || n < 64) return 0;
     const int npairs = (int)ins.size();
-    klt_ctx::BatchOrder *bo = nullptr;
-    for (auto &e : c->batch_orders)
-        if (e.in == ins) { bo = &e; break; }
+    klt_ctx::BatchOrder *bo = cache_find(c->batch_orders, [&](const klt_ctx::BatchOrder &e) { return e.in == ins; });
     if (npairs == 1) {
         bool seen = false;
         for (const klt_feat *p : c->seen_once) seen = seen || p == ins[0];
@@ -49,14 +71,7 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
         }
     }
     if (!bo) {
-        if (c->batch_orders.size() < klt_ctx::kBatchOrders) {
-            c->batch_orders.emplace_back();
-            bo = &c->batch_orders.back();
-        } else {
-            bo = &c->batch_orders[0];
-            for (auto &e : c->batch_orders)
-                if (e.used < bo->used) bo = &e;
-        }
+        bo = cache_place(c->batch_orders, klt_ctx::kBatchOrders);
         bo->in = ins;
         bo->n = -1;
     }
@@ -85,13 +100,45 @@ static int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2)
     return 0;
 }
 
+// the six planes of level l of a frame pair
+static void level_planes(const Slot *s1, const Slot *s2, int l, const float *&i1, const float *&gx1, const float *&gy1, const float *&i2,
+                         const float *&gx2, const float *&gy2)
+{
+    i1 = s1->lv[l].img; gx1 = s1->lv[l].gx; gy1 = s1->lv[l].gy;
+    i2 = s2->lv[l].img; gx2 = s2->lv[l].gx; gy2 = s2->lv[l].gy;
+}
+
 static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv)
 {
     for (int l = 0; l < s1->nlev; l++) {
-        lv[l].i1 = s1->lv[l].img; lv[l].gx1 = s1->lv[l].gx; lv[l].gy1 = s1->lv[l].gy;
-        lv[l].i2 = s2->lv[l].img; lv[l].gx2 = s2->lv[l].gx; lv[l].gy2 = s2->lv[l].gy;
+        level_planes(s1, s2, l, lv[l].i1, lv[l].gx1, lv[l].gy1, lv[l].i2, lv[l].gx2, lv[l].gy2);
         lv[l].nc = s1->lv[l].nc; lv[l].nr = s1->lv[l].nr;
     }
+}
+
+// what a forward-backward launch asks of a pair's three feature buffers (fb_back: a buffer or -1)
+static int check_fb_buffers(klt_ctx *c, int fb_in, int fb_out, int fb_back)
+{
+    if (fb_in == fb_out || (fb_back >= 0 && (fb_back == fb_in || fb_back == fb_out)))
+        return fail(c, KLT_ERR_ARG, "the forward-backward check needs fb_in, fb_out and fb_back pairwise distinct");
+    if (fb_back < -1) return fail(c, KLT_ERR_ARG, "fb_back must be a feature buffer or -1");
+    return 0;
+}
+
+// the tracker launch of `npairs` pairs of `nlev` levels under its timer
+static int enqueue_track(klt_ctx *c, const TrackArgs &a, int npairs, int nlev)
+{
+    const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
+    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * nlev + 32), c->stream);   // refined by the caller from klt_track_stats
+    if (launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
+    return 0;
+}
+
+static int count_live(const klt_feat *f, int n)
+{
+    int k = 0;
+    for (int i = 0; i < n; i++) k += f[i].val >= 0;
+    return k;
 }
 
 // klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1)
@@ -99,9 +146,8 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
 {
     if (int rc = check_ready(c)) return rc;
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
-    if (fb && (fb_in == fb_out || (fb_back >= 0 && (fb_back == fb_in || fb_back == fb_out))))
-        return fail(c, KLT_ERR_ARG, "the forward-backward check needs fb_in, fb_out and fb_back pairwise distinct");
-    if (fb && fb_back < -1) return fail(c, KLT_ERR_ARG, "fb_back must be a feature buffer or -1");
+    if (fb)
+        if (int rc = check_fb_buffers(c, fb_in, fb_out, fb_back)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s1, *s2;
     if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
@@ -120,11 +166,7 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
         a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
     }
     if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
-    {
-        const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
-        TimerScope t(c, F_TRACK, (double)n * (foot * 2 * s1->nlev + 32), c->stream);   // refined by the caller from klt_track_stats
-        if (launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
-    }
+    if (int rc = enqueue_track(c, a, 1, s1->nlev)) return rc;
     if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
     {
         Slot *both[2] = {s1, s2};
@@ -159,11 +201,8 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     if (int rc = check_ready(c)) return rc;
     if (!slot1 || !slot2 || !fb_in || !fb_out || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
     if (fb)
-        for (int i = 0; i < npairs; i++) {
-            const int b = fb_back ? fb_back[i] : -1;
-            if (b < -1 || fb_in[i] == fb_out[i] || (b >= 0 && (b == fb_in[i] || b == fb_out[i])))
-                return fail(c, KLT_ERR_ARG, "the forward-backward check needs fb_in, fb_out and fb_back pairwise distinct");
-        }
+        for (int i = 0; i < npairs; i++)
+            if (int rc = check_fb_buffers(c, fb_in[i], fb_out[i], fb_back ? fb_back[i] : -1)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<TrackPairDesc> table((size_t)npairs);
     std::vector<Slot *> used;
@@ -198,18 +237,11 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         const unsigned char *bytes = reinterpret_cast<const unsigned char *>(table.data());
         for (size_t i = 0; i < table.size() * sizeof(TrackPairDesc); i++) hash = (hash ^ bytes[i]) * 1099511628211ull;
     }
-    klt_ctx::BatchTable *bt = nullptr;
-    for (auto &e : c->batch_tables)
-        if (e.hash == hash && e.host.size() == table.size() && std::memcmp(e.host.data(), table.data(), table.size() * sizeof(TrackPairDesc)) == 0) { bt = &e; break; }
+    klt_ctx::BatchTable *bt = cache_find(c->batch_tables, [&](const klt_ctx::BatchTable &e) {
+        return e.hash == hash && e.host.size() == table.size() && std::memcmp(e.host.data(), table.data(), table.size() * sizeof(TrackPairDesc)) == 0;
+    });
     if (!bt) {
-        if (c->batch_tables.size() < klt_ctx::kBatchTables) {
-            c->batch_tables.emplace_back();
-            bt = &c->batch_tables.back();
-        } else {
-            bt = &c->batch_tables[0];
-            for (auto &e : c->batch_tables)
-                if (e.used < bt->used) bt = &e;
-        }
+        bt = cache_place(c->batch_tables, klt_ctx::kBatchTables);
         if (int rc = ensure(c, bt->dev, bt->cap, (size_t)npairs)) return rc;
         HIPCHK(c, hipMemcpyAsync(bt->dev, table.data(), (size_t)npairs * sizeof(TrackPairDesc), hipMemcpyHostToDevice, c->stream));
         bt->host = table;
@@ -228,11 +260,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
         if (int rc = set_track_order(c, a, n, ins)) return rc;
     }
-    {
-        const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
-        TimerScope t(c, F_TRACK, (double)npairs * n * (foot * 2 * first->nlev + 32), c->stream);
-        if (launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
-    }
+    if (int rc = enqueue_track(c, a, npairs, first->nlev)) return rc;
     if (c->collect_stats)
         for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, first->nlev, c->stats_d);
     if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
@@ -258,11 +286,7 @@ int klt_track(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int *n_t
     if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: `inout` is ours until then)
     if (int rc = klt_track_async(c, slot1, slot2, fi, fo, n)) return rc;
     if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
-    if (n_tracked) {
-        int k = 0;
-        for (int i = 0; i < n; i++) k += inout[i].val >= 0;
-        *n_tracked = k;
-    }
+    if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }
 
@@ -275,11 +299,7 @@ int klt_track_fb(klt_ctx *c, int slot1, int slot2, klt_feat *inout, klt_feat *ba
     if (back)
         if (int rc = klt_featbuf_download(c, fbk, back, n)) return rc;
     if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
-    if (n_tracked) {
-        int k = 0;
-        for (int i = 0; i < n; i++) k += inout[i].val >= 0;
-        *n_tracked = k;
-    }
+    if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }
 
@@ -377,8 +397,7 @@ int klt_track_affine_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_o
     AffineArgs a;
     std::memset(&a, 0, sizeof(a));
     a.in = c->fbs[fb_in].d; a.out = c->fbs[fb_out].d; a.rec = as.rec; a.tpl = as.tpl;
-    a.i1 = s1->lv[0].img; a.gx1 = s1->lv[0].gx; a.gy1 = s1->lv[0].gy;
-    a.i2 = s2->lv[0].img; a.gx2 = s2->lv[0].gx; a.gy2 = s2->lv[0].gy;
+    level_planes(s1, s2, 0, a.i1, a.gx1, a.gy1, a.i2, a.gx2, a.gy2);
     a.n = n; a.ncols = s1->nc; a.nrows = s1->nr; a.mode = c->ap.mode;
     a.width = c->ap.window_width; a.height = c->ap.window_height; a.max_iterations = c->ap.max_iterations;
     a.step = c->p.step_factor; a.small = c->p.min_determinant; a.th = c->p.min_displacement;
@@ -402,11 +421,7 @@ int klt_track_affine(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, i
     if (int rc = klt_featbuf_upload(c, fi, inout, n)) return rc;
     if (int rc = klt_track_affine_async(c, slot1, slot2, fi, fo, n, state)) return rc;
     if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
-    if (n_tracked) {
-        int k = 0;
-        for (int i = 0; i < n; i++) k += inout[i].val >= 0;
-        *n_tracked = k;
-    }
+    if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }
 
@@ -429,6 +444,5 @@ int klt_track_stats_read(klt_ctx *c, klt_track_stats *out)
     for (int l = 0; l < KLT_MAX_LEVELS; l++) { out->level_visits[l] = h[1 + l]; out->iterations[l] = h[1 + KLT_MAX_LEVELS + l]; }
     return KLT_OK;
 }
-
 
 }  // extern "C"

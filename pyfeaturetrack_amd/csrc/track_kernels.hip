@@ -77,12 +77,82 @@ __device__ __forceinline__ float sample(const float *__restrict__ qg, int nc, co
     return (float)v;
 }
 
-// numpy's pairwise summation of n floats in LDS (trackFeatures.py:124), computed by the whole wavefront; the result is valid in
-// lane 0.  For a block of 8 <= n <= 128 numpy keeps eight running sums r[j] = a[j] + a[8 + j] + a[16 + j] + ... (each a
+// (tried as shared functions and not kept -- each moved register figures of instantiations it was inlined into, in every form tried
+// (by value / by reference, one expression / early returns / bitwise, with and without branch hints), so these statements stay
+// written out where they are used; tools/kernel_regs.py figures, vgpr / sgpr / scratch:
+//   the in-loop bounds test (:428-431): track_kernel<1,0,false,false> 61/73 -> 63/74, track_kernel_quad<false,7,1,false,false>
+//       120/68 -> 116/70, <false,15,5,false,false> scratch 40 -> 44, track_iterate_kernel 49/64 -> 50/62;
+//   the template footprint test (:35): track_kernel<1,0,true,false> 61/83 -> 63/81, extract_patch_kernel 40 -> 38 VGPRs;
+//   the post-loop bounds test (trackFeatures.py:110) and the level status (:127-129): neutral in track_level, but
+//       track_kernel_quad<false,7,1,false,false> 68 -> 64 SGPRs resp. <false,7,1,true,false> 68 -> 66, which leaves one caller;
+//   the kernels' prologue (feature index, per-pair pointers): track_kernel<1,0,false,false> 61/73 -> 59/77,
+//       track_kernel_quad<false,7,1,true,false> 68 -> 66 SGPRs;
+//   the run-time-n sum loop shared by track_level and track_iterate_kernel: track_kernel<1,0,false,false> 73 -> 72 SGPRs.)
+
+// _solveEquation, trackFeaturesUtils.pyx:318-340: the step (dx, dy) from the five sums (ex, ey already times the step factor).
+// Returns whether the determinant is too small, in which case the step means nothing (it is formed all the same: a division
+// that nobody reads costs nothing, and the quad kernels divide before they look at the predicate).
+__device__ __forceinline__ bool solve_step(float gxx, float gxy, float gyy, float ex, float ey, float small, float &dx, float &dy)
+{
+    const float p1 = gxx * gyy, p2 = gxy * gxy;
+    const float det = p1 - p2;
+    const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
+    dx = (n1 - n2) / det;
+    dy = (n3 - n4) / det;
+    return det < small;
+}
+
+// 16-byte aligned sub-arrays: the five product arrays of a window of n samples in LDS
+__host__ __device__ constexpr int track_npad(int n) { return (n + 3) & ~3; }
+__host__ __device__ constexpr size_t track_lds_bytes(int n) { return 5 * (size_t)track_npad(n) * sizeof(float); }
+
+// One product array added in the reference's row-major order (sequential f32 adds, trackFeaturesUtils.pyx:263-267, :296-302), read
+// from LDS 16 bytes at a time: N terms, N known at compile time (a window size known at run time only: a plain loop over the terms).
+//   PEEL == false: every quad carries the tests of its last three elements.  Unrolled completely they fold (7x7: 13 quads; the
+//       peeled form measured 0.4 us slower there).
+//   PEEL == true: whole quads without a test, the N % 4 tail on its own.  15x15 quad kernel: with the tests inside the partly
+//       unrolled loop every quad paid three scalar compares and branches (13 M scalar next to 20 M vector instructions per launch):
+//       49.0 -> 38.5 us.
+template <int N, bool PEEL, int UNROLL>
+__device__ __forceinline__ float chain_sum(const float4 *T4)
+{
+    float acc = 0.f;
+    if (PEEL) {
+#pragma unroll UNROLL
+        for (int q = 0; q < N / 4; q++) {
+            const float4 v = T4[q];
+            acc = acc + v.x;
+            acc = acc + v.y;
+            acc = acc + v.z;
+            acc = acc + v.w;
+        }
+        if (N % 4) {
+            const float4 v = T4[N / 4];
+            acc = acc + v.x;
+            if (N % 4 > 1) acc = acc + v.y;
+            if (N % 4 > 2) acc = acc + v.z;
+        }
+    } else {
+#pragma unroll UNROLL
+        for (int q = 0; q < (N + 3) / 4; q++) {
+            const float4 v = T4[q];
+            acc = acc + v.x;
+            if (4 * q + 1 < N) acc = acc + v.y;
+            if (4 * q + 2 < N) acc = acc + v.z;
+            if (4 * q + 3 < N) acc = acc + v.w;
+        }
+    }
+    return acc;
+}
+
+// numpy's pairwise summation of n floats in LDS (trackFeatures.py:124), computed by a group of lanes; the result is valid in
+// its lane 0.  For a block of 8 <= n <= 128 numpy keeps eight running sums r[j] = a[j] + a[8 + j] + a[16 + j] + ... (each a
 // sequential chain, independent of the others), folds them as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) and then adds
 // the n % 8 tail one by one.  Lanes 0..7 run the eight chains side by side and three shuffles do the fold: the same
 // additions in the same order as the 1-lane loop, in 5 + 3 + tail steps instead of n.
-__device__ __forceinline__ float pairwise_block_wave(const float *a, int n, int lane)
+// `s` = the lane's index within the summing group: the wavefront, or the lane group of a feature of the quad kernels (the result
+// is then valid in the group's lane s == 0).
+__device__ __forceinline__ float pairwise_block(const float *a, int n, int s)
 {
     if (n < 8) {
         float res = 0.f;
@@ -91,9 +161,9 @@ __device__ __forceinline__ float pairwise_block_wave(const float *a, int n, int 
     }
     const int nn = n - (n % 8);
     float r = 0.f;
-    if (lane < 8) {
-        r = a[lane];
-        for (int i = 8; i < nn; i += 8) r = r + a[i + lane];
+    if (s < 8) {
+        r = a[s];
+        for (int i = 8; i < nn; i += 8) r = r + a[i + s];
     }
     r = r + __shfl_down(r, 1);          // lanes 0, 2, 4, 6: r0 + r1, r2 + r3, r4 + r5, r6 + r7
     r = r + __shfl_down(r, 2);          // lanes 0, 4
@@ -102,19 +172,23 @@ __device__ __forceinline__ float pairwise_block_wave(const float *a, int n, int 
     return res;
 }
 
+// ... of any n: numpy halves blocks of more than 128 elements (n2 = n / 2 rounded down to a multiple of 8)
 template <int DEPTH>
-__device__ float pairwise_sum(const float *a, int n, int lane)
+__device__ __forceinline__ float pairwise_sum(const float *a, int n, int s)
 {
-    if (n <= 128) return pairwise_block_wave(a, n, lane);
+    if (n <= 128) return pairwise_block(a, n, s);
     int n2 = n / 2;
     n2 -= n2 % 8;
-    return pairwise_sum<DEPTH - 1>(a, n2, lane) + pairwise_sum<DEPTH - 1>(a + n2, n - n2, lane);
+    return pairwise_sum<DEPTH - 1>(a, n2, s) + pairwise_sum<DEPTH - 1>(a + n2, n - n2, s);
 }
 template <>
-__device__ float pairwise_sum<0>(const float *a, int n, int lane)
+__device__ __forceinline__ float pairwise_sum<0>(const float *a, int n, int s)
 {
-    return pairwise_block_wave(a, n < 128 ? n : 128, lane);
+    return pairwise_block(a, n < 128 ? n : 128, s);
 }
+// (track_level's call of it stays a function: inlined there, the run-time-n tree moved every track_kernel<*, 0, *, *> figure,
+// <1, 0, false, false> from 61 to 80 VGPRs)
+__device__ float pairwise_sum_wave(const float *a, int n, int lane) { return pairwise_sum<3>(a, n, lane); }
 
 // A level of a pair's descriptor table.  The table is written by the host before the launch and never by a kernel, so it is read
 // through the constant address space: scalar loads, the six plane pointers stay in SGPRs (as they do for a single-pair launch, whose
@@ -151,7 +225,7 @@ __device__ int track_level(const TrackArgsBase &a, const TrackLevel &lv, float x
                            float *lds, int lane, int &iters, int clk0 = 0)
 {
     const int w = WCT > 0 ? WCT : a.window, n = w * w, hw = w / 2;
-    const int npad = (n + 3) & ~3;                       // 16-byte aligned sub-arrays
+    const int npad = track_npad(n);
     const int nc = lv.nc, nr = lv.nr;
     float *l_diff = lds;                                 // residue scratch (aliases product array 0)
     iters = 0;
@@ -212,30 +286,15 @@ __device__ int track_level(const TrackArgsBase &a, const TrackLevel &lv, float x
         float acc = 0.f;
         if (lane < 5) {
             const float *T = lds + lane * npad;
-            if (WCT > 0) {
-                const float4 *T4 = reinterpret_cast<const float4 *>(T);
-#pragma unroll WCT <= 8 ? 16 : 4
-                for (int q = 0; q < (WCT * WCT + 3) / 4; q++) {
-                    const float4 v = T4[q];
-                    acc = acc + v.x;
-                    if (4 * q + 1 < WCT * WCT) acc = acc + v.y;
-                    if (4 * q + 2 < WCT * WCT) acc = acc + v.z;
-                    if (4 * q + 3 < WCT * WCT) acc = acc + v.w;
-                }
-            } else {
+            if constexpr (WCT > 0) acc = chain_sum<WCT * WCT, false, (WCT <= 8 ? 16 : 4)>(reinterpret_cast<const float4 *>(T));
+            else
                 for (int k = 0; k < n; k++) acc = acc + T[k];
-            }
         }
         __syncthreads();
         const float gxx = __shfl(acc, 0), gxy = __shfl(acc, 1), gyy = __shfl(acc, 2);
         const float ex = __shfl(acc, 3) * a.step, ey = __shfl(acc, 4) * a.step;
-        // _solveEquation, :318-340
-        const float p1 = gxx * gyy, p2 = gxy * gxy;
-        const float det = p1 - p2;
-        if (det < a.small) { status = KLT_SMALL_DET; break; }
-        const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
-        const float dx = (n1 - n2) / det;
-        const float dy = (n3 - n4) / det;
+        float dx, dy;
+        if (solve_step(gxx, gxy, gyy, ex, ey, a.small, dx, dy)) { status = KLT_SMALL_DET; break; }
         status = KLT_TRACKED;
         x2 = x2 + dx;
         y2 = y2 + dy;
@@ -262,7 +321,7 @@ __device__ int track_level(const TrackArgsBase &a, const TrackLevel &lv, float x
             if (k < n) l_diff[k] = fabsf(t_i[kk] - sample<KLT_PIX_STRIDE>(lv.i2 + KLT_PIX_STRIDE * (base + off[kk]), nc, b2));
         }
         __syncthreads();
-        float s = pairwise_sum<3>(l_diff, n, lane);
+        float s = pairwise_sum_wave(l_diff, n, lane);
         __syncthreads();
         s = __shfl(s, 0);
         if (s / (float)n > a.max_residue) status = KLT_LARGE_RESIDUE;
@@ -397,43 +456,6 @@ __global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB> a)
 // Every feature's arithmetic is track_level's, operation for operation: same bilinear expression, the five product arrays in
 // LDS added by lanes 0..4 of the feature in the reference's row-major sequential f32 order, numpy's pairwise sum for the residue.
 
-// numpy's pairwise f32 sum of a block of n <= 128 floats, by the lanes s = 0..7 of a feature's lane group (pairwise_block_wave
-// with the group lane); the result is valid in the group's lane s == 0
-__device__ __forceinline__ float pairwise_block_group(const float *a, int n, int s)
-{
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; i++) res = res + a[i];
-        return res;
-    }
-    const int nn = n - (n % 8);
-    float r = 0.f;
-    if (s < 8) {
-        r = a[s];
-        for (int i = 8; i < nn; i += 8) r = r + a[i + s];
-    }
-    r = r + __shfl_down(r, 1);
-    r = r + __shfl_down(r, 2);
-    float res = r + __shfl_down(r, 4);
-    for (int i = nn; i < n; i++) res = res + a[i];
-    return res;
-}
-
-// ... of any n: numpy halves blocks of more than 128 elements (n2 = n / 2 rounded down to a multiple of 8)
-template <int DEPTH>
-__device__ __forceinline__ float pairwise_group(const float *a, int n, int s)
-{
-    if (n <= 128) return pairwise_block_group(a, n, s);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return pairwise_group<DEPTH - 1>(a, n2, s) + pairwise_group<DEPTH - 1>(a + n2, n - n2, s);
-}
-template <>
-__device__ __forceinline__ float pairwise_group<0>(const float *a, int n, int s)
-{
-    return pairwise_block_group(a, n < 128 ? n : 128, s);
-}
-
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The records of pixels q .. q + 3 of a level (klt_internal.h: image, gradx, grady per pixel): 48 contiguous bytes at byte offset 12 q,
@@ -514,7 +536,7 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
     constexpr int FPW = W == 7 ? 4 : 1;                      // features per wavefront
     constexpr int LPF = 64 / FPW;                            // lanes per feature = quads of its footprint
     constexpr int QPR = (W + 1) / 4;                         // quads per footprint row
-    constexpr int w = W, n = W * W, hw = W / 2, npad = (n + 3) & ~3;
+    constexpr int w = W, n = W * W, hw = W / 2, npad = track_npad(n);
     constexpr bool REUSE = W == 7;                           // keep a footprint whose integer corner has not moved (see request_footprint)
     static_assert((W + 1) * QPR == LPF, "one quad per lane");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -646,37 +668,7 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
                 }
                 if (!TREE) wave_lds_sync();
                 float acc = 0.f;
-                if (!TREE && s < 5) {
-                    const float4 *T4 = reinterpret_cast<const float4 *>(gl + s * npad);
-                    if (W > 8) {
-                        // 15x15: whole quads without a test, the n % 4 tail on its own -- with the tests inside the partly unrolled loop every
-                        // quad paid three scalar compares and branches (13 M scalar next to 20 M vector instructions per launch): 49.0 -> 38.5 us
-    #pragma unroll 8
-                        for (int q = 0; q < n / 4; q++) {
-                            const float4 v = T4[q];
-                            acc = acc + v.x;
-                            acc = acc + v.y;
-                            acc = acc + v.z;
-                            acc = acc + v.w;
-                        }
-                        if (n % 4) {
-                            const float4 v = T4[n / 4];
-                            acc = acc + v.x;
-                            if (n % 4 > 1) acc = acc + v.y;
-                            if (n % 4 > 2) acc = acc + v.z;
-                        }
-                    } else {
-                        // 7x7: the 13 quads are unrolled completely and the tests fold (the peeled form measured 0.4 us slower here)
-    #pragma unroll 16
-                        for (int q = 0; q < (n + 3) / 4; q++) {
-                            const float4 v = T4[q];
-                            acc = acc + v.x;
-                            if (4 * q + 1 < n) acc = acc + v.y;
-                            if (4 * q + 2 < n) acc = acc + v.z;
-                            if (4 * q + 3 < n) acc = acc + v.w;
-                        }
-                    }
-                }
+                if (!TREE && s < 5) acc = chain_sum<n, (W > 8), (W > 8 ? 8 : 16)>(reinterpret_cast<const float4 *>(gl + s * npad));
                 if (!TREE) wave_lds_sync();
                 float gxx, gxy, gyy, ex, ey;
                 if (TREE) {
@@ -686,13 +678,9 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
                     gxx = __shfl(acc, glead); gxy = __shfl(acc, glead + 1); gyy = __shfl(acc, glead + 2);
                     ex = __shfl(acc, glead + 3) * a.step; ey = __shfl(acc, glead + 4) * a.step;
                 }
-                const float p1 = gxx * gyy, p2 = gxy * gxy;
-                const float det = p1 - p2;
-                const bool small_det = det < a.small;
+                float dx, dy;
+                const bool small_det = solve_step(gxx, gxy, gyy, ex, ey, a.small, dx, dy);
                 if (act && small_det) { status = KLT_SMALL_DET; iterating = false; }
-                const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
-                const float dx = (n1 - n2) / det;
-                const float dy = (n3 - n4) / det;
                 if (act && !small_det) {
                     status = KLT_TRACKED;
                     x2 = x2 + dx;
@@ -736,7 +724,7 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
                     for (int m = 0; m < 4; m++)
                         if (qr < w && 4 * qh + m < w) gl[k0 + m] = fabsf(t_i[m] - s_i[m]);
                     wave_lds_sync();
-                    sres = pairwise_group<3>(gl, n, s);
+                    sres = pairwise_sum<3>(gl, n, s);
                     wave_lds_sync();
                     sres = __shfl(sres, glead);
                 }
@@ -885,7 +873,7 @@ static int launch_track_t(hipStream_t s, const TrackArgs &a)
     const TrackKernArgs<FB> &ka = a;                     // what the kernels take: the plain ones not the forward-backward fields
     const int n = a.window * a.window;
     if (n > 1024) return -1;
-    const size_t lds = 5 * (size_t)((n + 3) & ~3) * sizeof(float);
+    const size_t lds = track_lds_bytes(n);
     const unsigned ny = BATCH ? a.npairs : 1;
     const dim3 block(64);
     // the permutation is (re)computed here whenever the caller asks for it, whichever kernel consumes it
@@ -961,7 +949,7 @@ __global__ __launch_bounds__(64) void track_iterate_kernel(const float *__restri
                                                            int max_iterations, float *__restrict__ res)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x, n = w * w, hw = w / 2, npad = (n + 3) & ~3;
+    const int lane = threadIdx.x, n = w * w, hw = w / 2, npad = track_npad(n);
     int iters = 0, status;
     const float one_plus_eps = 1.001f;
     for (;;) {
@@ -992,12 +980,8 @@ __global__ __launch_bounds__(64) void track_iterate_kernel(const float *__restri
         __syncthreads();
         const float gxx = __shfl(acc, 0), gxy = __shfl(acc, 1), gyy = __shfl(acc, 2);
         const float ex = __shfl(acc, 3) * step, ey = __shfl(acc, 4) * step;
-        const float p1 = gxx * gyy, p2 = gxy * gxy;
-        const float det = p1 - p2;
-        if (det < small) { status = KLT_SMALL_DET; break; }
-        const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
-        const float dx = (n1 - n2) / det;
-        const float dy = (n3 - n4) / det;
+        float dx, dy;
+        if (solve_step(gxx, gxy, gyy, ex, ey, small, dx, dy)) { status = KLT_SMALL_DET; break; }
         status = KLT_TRACKED;
         x2 = x2 + dx;
         y2 = y2 + dy;
@@ -1018,8 +1002,7 @@ void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, c
                           const float *gy2, int nc, int nr, int w, float x2, float y2, float step, float small, float th,
                           int max_iterations, float *res)
 {
-    const size_t lds = 5 * (size_t)((w * w + 3) & ~3) * sizeof(float);
-    hipLaunchKernelGGL(track_iterate_kernel, dim3(1), dim3(64), (unsigned)lds, s, t_gx, t_gy, t_i, i2, gx2, gy2, nc, nr, w, x2, y2, step,
+    hipLaunchKernelGGL(track_iterate_kernel, dim3(1), dim3(64), (unsigned)track_lds_bytes(w * w), s, t_gx, t_gy, t_i, i2, gx2, gy2, nc, nr, w, x2, y2, step,
                        small, th, max_iterations, res);
 }
 

@@ -86,6 +86,23 @@ def test_occlusion_cases_and_thresholds(ctx, case, max_error):
         assert np.array_equal(kept, checked & (back["val"] == KLT_TRACKED) & (back["x"] == fl["x"]) & (back["y"] == fl["y"]))
 
 
+@pytest.mark.parametrize("window,levels,ss", [(5, 2, 4), (13, 2, 2), (21, 2, 2), (31, 1, 2)])
+def test_any_window_kernels(ctx, window, levels, ss):
+    """the forward-backward forms of the any-window kernel with 1, 4, 8 and 16 samples per lane (windows 7, 9 and 15 are the cases
+    above).  With max_error = 1.0 the CPU oracle's composition rejects 17, 17, 8 and 2 of the 123, 127, 112 and 106 features it tracks
+    forward (of 138 live ones).  Window 13 also as a batch of two pairs: the batched form of the same kernel"""
+    f0, f1 = occlusion_pair(320, 240, (70, 170, 100, 220))
+    fl = load_pair(ctx, make_tc(levels=levels, ss=ss, window=window), f0, f1, 150, lost_every=13)
+    out, back, _ = check_fused(ctx, fl, 1.0, "window %d" % window, need_rejected=True)
+    if window == 13:
+        ctx.featbuf_upload(100, fl)
+        ctx.track_fb_batch_async([(0, 1, 100, 200 + i, 300 + i) for i in range(2)], len(fl))
+        ctx.sync()
+        for i in range(2):
+            assert_records(ctx.featbuf_download(200 + i, len(fl)), out, "window 13, batch pair %d out" % i)
+            assert_records(ctx.featbuf_download(300 + i, len(fl)), back, "window 13, batch pair %d back" % i)
+
+
 @pytest.mark.parametrize("case", OCCLUSION_CASES + [("cfg-1",)], ids=[c[0] for c in OCCLUSION_CASES] + ["cfg1"])
 def test_against_the_cpu_oracle_composition(ctx, case, img0, img1):
     """the fused kernel against two runs of the CPU oracle's tracker and the rule (the oracle writes no aux word: x, y, val)"""
