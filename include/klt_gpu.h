@@ -31,8 +31,9 @@
 extern "C" {
 #endif
 
-#define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points and by the selection mask: klt_set_fb_params / klt_track_fb* /
-                                   * klt_set_select_mask* are purely additive, no
+#define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
+                                   * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
+                                   * klt_predict_cv_async are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
@@ -320,6 +321,31 @@ int klt_track_fb(klt_ctx *ctx, int slot1, int slot2, klt_feat *inout, klt_feat *
 /* npairs pairs in one launch (cf. klt_track_batch_async); fb_back may be NULL (no pair's backward records are kept) and single entries -1 */
 int klt_track_fb_batch_async(klt_ctx *ctx, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_back,
                              int npairs, int n);
+
+/* ---- motion prior: start each feature's search from a predicted position (not in the reference) ---------- */
+/* `guess` is a list of klt_feat records next to `in`, same index = same feature: x, y = the predicted position in frame 2.  For a live
+ * feature (in.val >= 0) the guess COUNTS iff guess.val >= 0 and guess.x and guess.y are both finite.  The only thing that changes is where
+ * the coarse-to-fine loop (trackFeatures.py:250-346) starts its search: with a guess that counts xlocout = guess.x / ss^L and
+ * ylocout = guess.y / ss^L (exact divisions, as for xloc), without one xlocout = xloc as in klt_track_async.  The template position, the
+ * per-level bounds tests, the status priority, the border test and the aux bits are klt_track_async's.  A finite guess outside the image
+ * is caught by the first level's bounds test: KLT_OOB, which is what the reference says about a search position outside the image.
+ * Records are identical bit for bit to klt_track_async's when every guess is the feature's own position or none counts (every window,
+ * KLT_OPT_TRACK_VARIANT, KLT_OPT_TRACK_XCD_ORDER and KLT_OPT_TRACK_TREE_SUMS value).
+ * fb_guess must hold at least n records and be distinct from fb_out (and fb_back): KLT_ERR_ARG otherwise.  It may be fb_in. */
+int klt_track_guess_async(klt_ctx *ctx, int slot1, int slot2, int fb_in, int fb_guess, int fb_out, int n);
+int klt_track_guess(klt_ctx *ctx, int slot1, int slot2, klt_feat *inout, const klt_feat *guess, int n, int *n_tracked);
+/* npairs pairs in one launch (cf. klt_track_batch_async); a fb_guess entry of -1: that pair has no guess list.  A pair's guess list must be
+ * distinct from every pair's fb_out. */
+int klt_track_guess_batch_async(klt_ctx *ctx, const int *slot1, const int *slot2, const int *fb_in, const int *fb_guess, const int *fb_out,
+                                int npairs, int n);
+/* The forward-backward check with a prior: fwd = G(1, 2, in, guess), back = T(2, 1, fwd) -- the way back starts at the forward result as
+ * in klt_track_fb_async (a prior there would bias the check) -- then the rule above.  Reference-order sums, like klt_track_fb*. */
+int klt_track_fb_guess_async(klt_ctx *ctx, int slot1, int slot2, int fb_in, int fb_guess, int fb_out, int n, int fb_back);
+/* Constant-velocity prediction from the lists of the last two frames: for a slot with cur.val == KLT_TRACKED and prev.val >= 0
+ * guess = (cur.x + (cur.x - prev.x), cur.y + (cur.y - prev.y), 0, 0), each coordinate two f32 roundings; every other slot -- lost, or
+ * refilled by a replacement pass (val > 0) -- gets (-1, -1, -1, 0): no guess.  fb_guess is allocated if needed and may be neither of the
+ * other two (KLT_ERR_ARG). */
+int klt_predict_cv_async(klt_ctx *ctx, int fb_prev, int fb_cur, int fb_guess, int n);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

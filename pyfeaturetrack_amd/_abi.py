@@ -120,6 +120,11 @@ SYMBOLS = {
     "klt_track_fb_async": (_I, [_P, _I, _I, _I, _I, _I, _I]),
     "klt_track_fb": (_I, [_P, _I, _I, _P, _P, _I, _PI]),
     "klt_track_fb_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
+    "klt_track_guess_async": (_I, [_P, _I, _I, _I, _I, _I, _I]),
+    "klt_track_guess": (_I, [_P, _I, _I, _P, _P, _I, _PI]),
+    "klt_track_guess_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
+    "klt_track_fb_guess_async": (_I, [_P, _I, _I, _I, _I, _I, _I, _I]),
+    "klt_predict_cv_async": (_I, [_P, _I, _I, _I, _I]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -30,6 +30,7 @@ MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
 # points, 65533 the API's selection list, 60000 .. 65524 KLTTrackSequence's table rows)
 _FB_API_IN, _FB_API_OUT = 65526, 65527
 _FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
+_FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
 
 
 def _dp(a):
@@ -136,6 +137,32 @@ class Context:
         if any(len(p) > 4 for p in pairs):
             back = (C.c_int * len(pairs))(*[p[4] if len(p) > 4 else -1 for p in pairs])
         self._check(self._lib.klt_track_fb_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], back, len(pairs), n))
+
+    # ------------------------------------------------ motion prior (klt_track_guess*, klt_predict_cv_async)
+    def track_guess(self, slot1, slot2, fl, guess):
+        """klt_track_guess on a copy: (records, number still tracked); `guess` a record array of the same length."""
+        fl = np.ascontiguousarray(fl, FEAT_DTYPE).copy()
+        guess = np.ascontiguousarray(guess, FEAT_DTYPE)
+        if len(guess) != len(fl):
+            raise ValueError("the guess list has %d records, the feature list %d" % (len(guess), len(fl)))
+        k = C.c_int()
+        self._check(self._lib.klt_track_guess(self._h, slot1, slot2, fl.ctypes.data, guess.ctypes.data, len(fl), C.byref(k)))
+        return fl, k.value
+
+    def track_guess_async(self, slot1, slot2, fb_in, fb_guess, fb_out, n):
+        self._check(self._lib.klt_track_guess_async(self._h, slot1, slot2, fb_in, fb_guess, fb_out, n))
+
+    def track_fb_guess_async(self, slot1, slot2, fb_in, fb_guess, fb_out, n, fb_back=-1):
+        self._check(self._lib.klt_track_fb_guess_async(self._h, slot1, slot2, fb_in, fb_guess, fb_out, n, fb_back))
+
+    def track_guess_batch_async(self, pairs, n):
+        """pairs: [(slot1, slot2, fb_in, fb_guess, fb_out), ...] -- one launch for all of them; fb_guess -1: that pair has no guess."""
+        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(5)]
+        self._check(self._lib.klt_track_guess_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], cols[4], len(pairs), n))
+
+    def predict_cv_async(self, fb_prev, fb_cur, fb_guess, n):
+        """klt_predict_cv_async: constant-velocity guesses for the list fb_cur from the list before it, fb_prev"""
+        self._check(self._lib.klt_predict_cv_async(self._h, fb_prev, fb_cur, fb_guess, n))
 
     # ------------------------------------------------ affine consistency check
     def set_affine_params(self, ap):
@@ -477,15 +504,23 @@ class Context:
             self._check(self._lib.klt_featbuf_map_host(self._h, fb_out, rout.ctypes.data, len(rout)))
             self._mapped_records = key
 
-    def track_enqueue(self, slot1, slot2, n, state=None, upload=True, fb_in=_FB_API_IN, fb_out=_FB_API_OUT, fb_check=False):
+    def track_enqueue(self, slot1, slot2, n, state=None, upload=True, fb_in=_FB_API_IN, fb_out=_FB_API_OUT, fb_check=False, guess=None):
         """The tracker is enqueued on the list in host_records(n)[0]; nothing is waited for.  With MAP_RECORDS (the default) the two
         feature buffers are those pinned arrays themselves and no copy is enqueued; otherwise the list goes up first (`upload`; not
-        again when the tracker is only repeated on other pyramids)."""
+        again when the tracker is only repeated on other pyramids).  `guess`: a record array of predicted positions (motion prior,
+        never with an affine state); it goes up with the list."""
         if MAP_RECORDS:
             self._map_records(n, fb_in, fb_out)
         elif upload:
             self._check(self._lib.klt_featbuf_upload_async(self._h, fb_in, self.host_records(n)[0].ctypes.data, n))
-        if fb_check:                       # forward-backward check (never with an affine state); the backward records stay on the device
+        if guess is not None:
+            if upload:
+                self._check(self._lib.klt_featbuf_upload(self._h, _FB_API_GUESS, guess.ctypes.data, n))
+            if fb_check:
+                self._check(self._lib.klt_track_fb_guess_async(self._h, slot1, slot2, fb_in, _FB_API_GUESS, fb_out, n, _FB_API_BACK))
+            else:
+                self._check(self._lib.klt_track_guess_async(self._h, slot1, slot2, fb_in, _FB_API_GUESS, fb_out, n))
+        elif fb_check:                       # forward-backward check (never with an affine state); the backward records stay on the device
             self._check(self._lib.klt_track_fb_async(self._h, slot1, slot2, fb_in, fb_out, n, _FB_API_BACK))
         elif state is None:
             self._check(self._lib.klt_track_async(self._h, slot1, slot2, fb_in, fb_out, n))

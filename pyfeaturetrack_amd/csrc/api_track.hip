@@ -125,12 +125,34 @@ static int check_fb_buffers(klt_ctx *c, int fb_in, int fb_out, int fb_back)
     return 0;
 }
 
-// the tracker launch of `npairs` pairs of `nlev` levels under its timer
-static int enqueue_track(klt_ctx *c, const TrackArgs &a, int npairs, int nlev)
+// what a launch with a motion prior asks of a pair's guess list (klt_track_guess*): a feature buffer of its own next to the ones the
+// launch writes -- by index and by address, a view can be a second name of the same records.  (It may be fb_in: every feature's guess
+// is then its own position.)
+static int check_guess_buffer(klt_ctx *c, int fb_guess, int fb_out, int fb_back)
+{
+    if (fb_guess < 0 || fb_guess > 65535) return fail(c, KLT_ERR_ARG, "fb_guess must be a feature buffer");
+    if (fb_guess == fb_out || fb_guess == fb_back) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
+    return 0;
+}
+
+// ... once the launch's own buffers exist: the guess list holds n records and shares no memory with them
+static int guess_records(klt_ctx *c, int fb_guess, int fb_out, int fb_back, int n, const klt_feat **guess)
+{
+    if ((size_t)fb_guess >= c->fbs.size() || !c->fbs[fb_guess].d || c->fbs[fb_guess].cap < n)
+        return fail(c, KLT_ERR_ARG, "the guess feature buffer holds fewer records than the feature list");
+    const klt_feat *g = c->fbs[fb_guess].d;
+    if (g == c->fbs[fb_out].d || (fb_back >= 0 && g == c->fbs[fb_back].d))
+        return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
+    *guess = g;
+    return 0;
+}
+
+// the tracker launch of `npairs` pairs of `nlev` levels under its timer (guess: the kernels that start from a predicted position)
+static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nlev, bool guess = false)
 {
     const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
     TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * nlev + 32), c->stream);   // refined by the caller from klt_track_stats
-    if (launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
+    if (guess ? launch_track_guess(c->stream, a) : launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
     return 0;
 }
 
@@ -141,13 +163,17 @@ static int count_live(const klt_feat *f, int n)
     return k;
 }
 
-// klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1)
-static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, bool fb, int fb_back)
+// klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1); guess == true:
+// klt_track_guess_async and klt_track_fb_guess_async, with the predicted positions in fb_guess
+static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, bool fb, int fb_back, bool guess = false,
+                        int fb_guess = -1)
 {
     if (int rc = check_ready(c)) return rc;
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
     if (fb)
         if (int rc = check_fb_buffers(c, fb_in, fb_out, fb_back)) return rc;
+    if (guess)
+        if (int rc = check_guess_buffer(c, fb_guess, fb_out, fb ? fb_back : -1)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s1, *s2;
     if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
@@ -156,8 +182,10 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
     if (fb && fb_back >= 0)                                  // (may grow c->fbs: before any pointer into it is taken)
         if (int rc = get_fb(c, fb_back, n > 0 ? n : 1, &bo)) return rc;
     if (int rc = get_fb(c, fb_out, n > 0 ? n : 1, &bo)) return rc;
-    TrackArgs a;
+    TrackGuessArgs a;
     std::memset(&a, 0, sizeof(a));
+    if (guess)
+        if (int rc = guess_records(c, fb_guess, fb_out, fb ? fb_back : -1, n, &a.guess)) return rc;
     fill_levels(s1, s2, a.lv);
     a.in = c->fbs[fb_in].d; a.out = bo->d;
     fill_track_params(c, s1, a, n);
@@ -166,7 +194,7 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
         a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
     }
     if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
-    if (int rc = enqueue_track(c, a, 1, s1->nlev)) return rc;
+    if (int rc = enqueue_track(c, a, 1, s1->nlev, guess)) return rc;
     if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
     {
         Slot *both[2] = {s1, s2};
@@ -186,6 +214,35 @@ int klt_track_fb_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, 
     return track_single(c, slot1, slot2, fb_in, fb_out, n, true, fb_back);
 }
 
+int klt_track_guess_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_guess, int fb_out, int n)
+{
+    return track_single(c, slot1, slot2, fb_in, fb_out, n, false, -1, true, fb_guess);
+}
+
+int klt_track_fb_guess_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_guess, int fb_out, int n, int fb_back)
+{
+    return track_single(c, slot1, slot2, fb_in, fb_out, n, true, fb_back, true, fb_guess);
+}
+
+// constant-velocity prediction from the lists of the last two frames (predict_cv_kernel has the rule)
+int klt_predict_cv_async(klt_ctx *c, int fb_prev, int fb_cur, int fb_guess, int n)
+{
+    if (int rc = check_ready(c)) return rc;
+    if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
+    if (fb_guess == fb_prev || fb_guess == fb_cur) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_prev and fb_cur");
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int fb : {fb_prev, fb_cur})
+        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
+            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    FeatBuf *bg;                                             // (may grow c->fbs: before any pointer into it is taken)
+    if (int rc = get_fb(c, fb_guess, n > 0 ? n : 1, &bg)) return rc;
+    if (bg->d == c->fbs[fb_prev].d || bg->d == c->fbs[fb_cur].d)
+        return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_prev and fb_cur");
+    launch_predict_cv(c->stream, c->fbs[fb_prev].d, c->fbs[fb_cur].d, bg->d, n);
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
 int klt_set_fb_params(klt_ctx *c, const klt_fb_params *p)
 {
     if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
@@ -194,12 +251,20 @@ int klt_set_fb_params(klt_ctx *c, const klt_fb_params *p)
     return KLT_OK;
 }
 
-// klt_track_batch_async (fb == false) and klt_track_fb_batch_async (fb == true; fb_back may be null)
+// klt_track_batch_async (fb == false) and klt_track_fb_batch_async (fb == true; fb_back may be null); fb_guess != null:
+// klt_track_guess_batch_async, an entry of -1 = that pair has no guess list
 static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_back, int npairs,
-                       int n, bool fb)
+                       int n, bool fb, const int *fb_guess = nullptr)
 {
     if (int rc = check_ready(c)) return rc;
     if (!slot1 || !slot2 || !fb_in || !fb_out || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
+    if (fb_guess)
+        for (int i = 0; i < npairs; i++) {
+            if (fb_guess[i] == -1) continue;
+            // (a guess list that another pair of the launch writes would be read while it changes: distinct from every pair's output)
+            for (int j = 0; j < npairs; j++)
+                if (int rc = check_guess_buffer(c, fb_guess[i], fb_out[j], -1)) return rc;
+        }
     if (fb)
         for (int i = 0; i < npairs; i++)
             if (int rc = check_fb_buffers(c, fb_in[i], fb_out[i], fb_back ? fb_back[i] : -1)) return rc;
@@ -228,6 +293,11 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         table[i].in = c->fbs[fb_in[i]].d;
         table[i].out = c->fbs[fb_out[i]].d;
         if (fb && fb_back && fb_back[i] >= 0) table[i].back = c->fbs[fb_back[i]].d;
+        if (fb_guess && fb_guess[i] >= 0) {
+            if (int rc = guess_records(c, fb_guess[i], fb_out[i], -1, n, &table[i].guess)) return rc;
+            for (int j = 0; j < npairs; j++)
+                if (table[i].guess == c->fbs[fb_out[j]].d) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
+        }
     }
     // the descriptor table is uploaded only when none of the tables kept on the device holds it (found by hash; at most 256 tables,
     // the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order protects the
@@ -248,7 +318,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         bt->hash = hash;
     }
     bt->used = ++c->batch_clock;
-    TrackArgs a;
+    TrackGuessArgs a;
     std::memset(&a, 0, sizeof(a));
     a.pairs = bt->dev;
     a.npairs = npairs;
@@ -260,7 +330,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
         if (int rc = set_track_order(c, a, n, ins)) return rc;
     }
-    if (int rc = enqueue_track(c, a, npairs, first->nlev)) return rc;
+    if (int rc = enqueue_track(c, a, npairs, first->nlev, fb_guess != nullptr)) return rc;
     if (c->collect_stats)
         for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, first->nlev, c->stats_d);
     if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
@@ -277,6 +347,25 @@ int klt_track_fb_batch_async(klt_ctx *c, const int *slot1, const int *slot2, con
                              int npairs, int n)
 {
     return track_batch(c, slot1, slot2, fb_in, fb_out, fb_back, npairs, n, true);
+}
+
+int klt_track_guess_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_guess, const int *fb_out,
+                                int npairs, int n)
+{
+    if (!fb_guess) return fail(c, KLT_ERR_ARG, "bad argument");
+    return track_batch(c, slot1, slot2, fb_in, fb_out, nullptr, npairs, n, false, fb_guess);
+}
+
+int klt_track_guess(klt_ctx *c, int slot1, int slot2, klt_feat *inout, const klt_feat *guess, int n, int *n_tracked)
+{
+    if (!c || !inout || !guess) return fail(c, KLT_ERR_ARG, "null argument");
+    const int fi = 65534, fo = 65535, fg = 65531;
+    if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: both lists are ours until then)
+    if (int rc = klt_featbuf_upload_async(c, fg, guess, n)) return rc;
+    if (int rc = klt_track_guess_async(c, slot1, slot2, fi, fg, fo, n)) return rc;
+    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
+    if (n_tracked) *n_tracked = count_live(inout, n);
+    return KLT_OK;
 }
 
 int klt_track(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int *n_tracked)

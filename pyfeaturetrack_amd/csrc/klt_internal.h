@@ -57,6 +57,7 @@ struct TrackPairDesc {
     const klt_feat *in;
     klt_feat *out;
     klt_feat *back;                     // forward-backward launches: the backward records of the pair, or null (last: the offsets above stay)
+    const klt_feat *guess;              // launches with a motion prior: the pair's predicted positions, or null (read by those kernels alone)
 };
 
 // The kernel argument of the plain tracker kernels.  Its layout is what their register allocation was measured with (the compiler widens
@@ -85,6 +86,12 @@ struct TrackArgs : TrackArgsBase {
     int fb;                      // 1: the fused forward-backward kernels (always the reference-order sums: tree_sums is not looked at)
     klt_feat *back;              // single-pair launch: the backward records, or null
     double fb_max_e2;            // (double)max_error * (double)max_error: a feature is consistent when its round trip ends within it
+};
+
+// ... and the kernel argument of the kernels that start a feature's search from a predicted position (klt_track_guess_async; DESIGN.md
+// section 9c): the plain and the forward-backward kernels never see the pointer
+struct TrackGuessArgs : TrackArgs {
+    const klt_feat *guess;       // single-pair launch: one record per feature (x, y = predicted frame-2 position; val < 0: no guess)
 };
 
 struct AffineArgs {
@@ -290,6 +297,8 @@ void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int
 
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
 int launch_track(hipStream_t s, const TrackArgs &a);
+int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
+void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,
                           const float *gy2, int nc, int nr, int w, float x2, float y2, float step, float small, float th,

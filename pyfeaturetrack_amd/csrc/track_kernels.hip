@@ -365,11 +365,21 @@ __device__ __forceinline__ klt_feat fb_record(double max_e2, const klt_feat &ft,
 
 // FB: the forward-backward check in the same launch -- the feature's wavefront descends the pyramids from frame 1 into frame 2 and, if
 // that tracked it, once more from there with the two frames exchanged; one `out` record (and one `back` record if asked) per feature.
-template <bool FB>
-using TrackKernArgs = std::conditional_t<FB, TrackArgs, TrackArgsBase>;
+// GUESS: a motion prior (klt_track_guess_async) -- the search in frame 2 starts at the feature's record in the guess
+// list instead of at its own position; the template position, and with FB the way back, are what they are without one.
+template <bool FB, bool GUESS = false>
+using TrackKernArgs = std::conditional_t<GUESS, TrackGuessArgs, std::conditional_t<FB, TrackArgs, TrackArgsBase>>;
 
-template <int MAXK, int WCT, bool BATCH, bool FB = false>
-__global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB> a)
+// Whether a guess record counts: val >= 0 and both coordinates finite, decided on the bits BEFORE anything is computed from the position
+// (a NaN passes every `<` of the bounds tests, and an address would be formed from it)
+__device__ __forceinline__ bool guess_counts(const klt_feat &gs)
+{
+    const uint32_t bx = __float_as_uint(gs.x), by = __float_as_uint(gs.y);
+    return gs.val >= 0 && (bx & 0x7f800000u) != 0x7f800000u && (by & 0x7f800000u) != 0x7f800000u;
+}
+
+template <int MAXK, int WCT, bool BATCH, bool FB = false, bool GUESS = false>
+__global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB, GUESS> a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     int f = blockIdx.x;
@@ -400,6 +410,14 @@ __global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB> a)
     TCLK(0);
     float xstart = ft.x, ystart = ft.y;     // FB, second pass: the forward result
     klt_feat fwd = ft;
+    float xguess = ft.x, yguess = ft.y;     // GUESS: where the forward search starts (without a guess that counts: at the feature itself)
+    if constexpr (GUESS) {
+        const klt_feat *fguess = BATCH ? a.pairs[blockIdx.y].guess : a.guess;
+        if (fguess) {
+            const klt_feat gs = fguess[f];
+            if (guess_counts(gs)) { xguess = gs.x; yguess = gs.y; }
+        }
+    }
     // (a do-while whose condition is constant false without FB: the plain kernels are compiled with no loop here at all -- as a counted
     // loop of one round it moved their register figures)
     int pass = 0;
@@ -408,6 +426,12 @@ __global__ __launch_bounds__(64) void track_kernel(TrackKernArgs<FB> a)
         float xloc = xstart, yloc = ystart;
         for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }   // power of two: exact
         float xout = xloc, yout = yloc;
+        if constexpr (GUESS) {
+            if (pass == 0) {                // the guess at the coarsest resolution, by the same exact divisions
+                xout = xguess; yout = yguess;
+                for (int r = 0; r < L; r++) { xout = xout * a.inv_ss; yout = yout * a.inv_ss; }
+            }
+        }
         int val = KLT_TRACKED;
         uint32_t aux = 0;       // 4 bits per level: 0 = level not visited, v = v-1 Newton iterations (saturating at 14)
         for (int r = L - 1; r >= 0; r--) {
@@ -528,9 +552,15 @@ __device__ __forceinline__ float group_tree_sum(float v)
 
 // FB: the forward-backward check in the same launch (see track_kernel).  A lane group whose feature is not tracked back -- not live, or
 // lost on the way forward -- idles through the second pass under the predicate that masks a finished feature in the first.
-template <bool BATCH, int W, int WAVES = 1, bool TREE = false, bool FB = false>
-__global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB> a)
+// (WAVES = occupancy target + GUESS_WAVES for the instantiations with a prior: the plain ones are looked up by the head of their names --
+// batch flag, window, target, sum form -- which has to stay theirs alone; as a shared body under two kernel names the 15x15 kernel took
+// 48 instead of 40 bytes of scratch and four plain instantiations two more SGPRs)
+constexpr int GUESS_WAVES = 8;
+
+template <bool BATCH, int W, int WAVES = 1, bool TREE = false, bool FB = false, bool GUESS = false>
+__global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(TrackKernArgs<FB, GUESS> a)
 {
+    static_assert(GUESS == (WAVES >= GUESS_WAVES), "instantiations with a prior carry the mark in their occupancy target");
     static_assert(W == 7 || W == 15, "quad kernels exist for 7x7 and 15x15 windows");
     static_assert(!(FB && TREE), "the forward-backward check uses the reference-order sums");
     constexpr int FPW = W == 7 ? 4 : 1;                      // features per wavefront
@@ -558,6 +588,14 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
     const bool valid = f < a.n;
     const klt_feat ft = fin[valid ? f : a.n - 1];
     const bool tracked_feature = valid && ft.val >= 0;       // only live features are tracked, trackFeatures.py:253
+    float xguess = ft.x, yguess = ft.y;                      // GUESS: where the feature's forward search starts (see track_kernel)
+    if constexpr (GUESS) {
+        const klt_feat *fguess = BATCH ? a.pairs[blockIdx.y].guess : a.guess;
+        if (fguess) {
+            const klt_feat gs = fguess[valid ? f : a.n - 1];
+            if (guess_counts(gs)) { xguess = gs.x; yguess = gs.y; }
+        }
+    }
     if (valid && ft.val < 0 && s == 0) {
         fout[f] = ft;
         if (FB && fback) fback[f] = ft;
@@ -580,6 +618,12 @@ __global__ __launch_bounds__(64, WAVES) void track_kernel_quad(TrackKernArgs<FB>
         float xloc = xstart, yloc = ystart;
         for (int r = 0; r < L; r++) { xloc = xloc * a.inv_ss; yloc = yloc * a.inv_ss; }
         float xout = xloc, yout = yloc;
+        if constexpr (GUESS) {
+            if (pass == 0) {
+                xout = xguess; yout = yguess;
+                for (int r = 0; r < L; r++) { xout = xout * a.inv_ss; yout = yout * a.inv_ss; }
+            }
+        }
         int val = KLT_TRACKED;
         uint32_t aux = 0;
         bool alive = go;                                         // still descending the pyramid
@@ -850,7 +894,33 @@ __global__ __launch_bounds__(256) void track_stats_kernel(const klt_feat *__rest
         atomicAdd(&stats[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
 }
 
+// Constant-velocity prediction (klt_predict_cv_async): one record per lane, a 16-byte load of each list and a 16-byte store.
+// guess = cur + (cur - prev), two f32 roundings per coordinate (no multiply: nothing to contract), for a feature that the last step tracked
+// (cur.val == KLT_TRACKED) from a live one (prev.val >= 0); any other slot -- lost, or refilled by a replacement pass, whose val is its
+// eigenvalue > 0 -- gets (-1, -1, -1, 0): no guess.
+__global__ __launch_bounds__(256) void predict_cv_kernel(const klt_feat *__restrict__ prev, const klt_feat *__restrict__ cur,
+                                                         klt_feat *__restrict__ guess, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int4 p = reinterpret_cast<const int4 *>(prev)[i], c = reinterpret_cast<const int4 *>(cur)[i];
+    int4 o = make_int4(__float_as_int(-1.f), __float_as_int(-1.f), -1, 0);
+    if (c.z == KLT_TRACKED && p.z >= 0) {
+        const float cx = __int_as_float(c.x), cy = __int_as_float(c.y);
+        o.x = __float_as_int(__fadd_rn(cx, __fsub_rn(cx, __int_as_float(p.x))));
+        o.y = __float_as_int(__fadd_rn(cy, __fsub_rn(cy, __int_as_float(p.y))));
+        o.z = 0;
+    }
+    reinterpret_cast<int4 *>(guess)[i] = o;
+}
+
 }  // namespace
+
+void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(predict_cv_kernel, dim3((n + 255) / 256), dim3(256), 0, s, prev, cur, guess, n);
+}
 
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats)
 {
@@ -867,10 +937,11 @@ void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, 
 int g_track_variant = getenv("KLT_TRACK_VARIANT") ? atoi(getenv("KLT_TRACK_VARIANT")) : 4;
 
 // FB: the forward-backward kernels (klt_track_fb_async), chosen by the same rules; they have no tree-sum form
-template <bool BATCH, bool FB>
-static int launch_track_t(hipStream_t s, const TrackArgs &a)
+// GUESS: the kernels with a motion prior (klt_track_guess*), chosen by the same rules again
+template <bool BATCH, bool FB, bool GUESS, class Args>
+static int launch_track_t(hipStream_t s, const Args &a)
 {
-    const TrackKernArgs<FB> &ka = a;                     // what the kernels take: the plain ones not the forward-backward fields
+    const TrackKernArgs<FB, GUESS> &ka = a;              // what the kernels take: the plain ones not the forward-backward fields, only those with a prior the guess list
     const int n = a.window * a.window;
     if (n > 1024) return -1;
     const size_t lds = track_lds_bytes(n);
@@ -890,9 +961,10 @@ static int launch_track_t(hipStream_t s, const TrackArgs &a)
         // the extra wavefront was meant to hide.)
         // (the forward-backward instantiation is left without a cap as well -- an occupancy target of two is none for a kernel of 138
         // VGPRs, which three wavefronts per SIMD fit; its registers and scratch are in DESIGN.md section 9a)
-        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 7, 2, false, true>), gq, block, (unsigned)(4 * lds), s, ka);
-        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 7, 1, true>), gq, block, 0u, s, ka);
-        else klt_launch((track_kernel_quad<BATCH, 7>), gq, block, (unsigned)(4 * lds), s, ka);
+        constexpr int GW = GUESS ? GUESS_WAVES : 0;
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 7, 2 + GW, false, true, GUESS>), gq, block, (unsigned)(4 * lds), s, ka);
+        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, true, false, GUESS>), gq, block, 0u, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, false, false, GUESS>), gq, block, (unsigned)(4 * lds), s, ka);
         return 0;
     }
     if (g_track_variant != 0 && a.window == 15) {
@@ -900,19 +972,20 @@ static int launch_track_t(hipStream_t s, const TrackArgs &a)
         // occupancy target 5 (96 VGPRs, 40 bytes of scratch per lane instead of 107 VGPRs): the 5000 wavefronts of cfg-3 are then
         // resident at once instead of in two rounds -- 57.9 -> 49.3 us.  (The 7x7 kernel loses from the same cap, see above.)
         // (forward-backward: occupancy target 4 -- 123 VGPRs, 36 bytes of scratch; at 5 the two passes' state costs 152 bytes of scratch per lane)
-        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 15, 4, false, true>), gq, block, (unsigned)lds, s, ka);
-        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 15, 5, true>), gq, block, 0u, s, ka);
-        else klt_launch((track_kernel_quad<BATCH, 15, 5>), gq, block, (unsigned)lds, s, ka);
+        constexpr int GW = GUESS ? GUESS_WAVES : 0;
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 15, 4 + GW, false, true, GUESS>), gq, block, (unsigned)lds, s, ka);
+        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, true, false, GUESS>), gq, block, 0u, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, false, false, GUESS>), gq, block, (unsigned)lds, s, ka);
         return 0;
     }
     const dim3 grid(a.order ? 8 * a.order_chunk : a.n, ny);
-    if (a.window == 7) klt_launch((track_kernel<1, 7, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else if (a.window == 15) klt_launch((track_kernel<4, 15, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else if (n <= 64) klt_launch((track_kernel<1, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else if (n <= 128) klt_launch((track_kernel<2, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else if (n <= 256) klt_launch((track_kernel<4, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else if (n <= 512) klt_launch((track_kernel<8, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
-    else klt_launch((track_kernel<16, 0, BATCH, FB>), grid, block, (unsigned)lds, s, ka);
+    if (a.window == 7) klt_launch((track_kernel<1, 7, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else if (a.window == 15) klt_launch((track_kernel<4, 15, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 64) klt_launch((track_kernel<1, 0, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 128) klt_launch((track_kernel<2, 0, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 256) klt_launch((track_kernel<4, 0, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else if (n <= 512) klt_launch((track_kernel<8, 0, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
+    else klt_launch((track_kernel<16, 0, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
     return 0;
 }
 
@@ -1010,9 +1083,17 @@ int launch_track(hipStream_t s, const TrackArgs &a)
 {
     if (a.n <= 0) return 0;
     if (a.fb) {
-        if (a.pairs) return a.npairs > 0 ? launch_track_t<true, true>(s, a) : 0;
-        return launch_track_t<false, true>(s, a);
+        if (a.pairs) return a.npairs > 0 ? launch_track_t<true, true, false>(s, a) : 0;
+        return launch_track_t<false, true, false>(s, a);
     }
-    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false>(s, a) : 0;
-    return launch_track_t<false, false>(s, a);
+    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false, false>(s, a) : 0;
+    return launch_track_t<false, false, false>(s, a);
+}
+
+int launch_track_guess(hipStream_t s, const TrackGuessArgs &a)
+{
+    if (a.n <= 0) return 0;
+    if (a.fb) return a.pairs ? -1 : launch_track_t<false, true, true>(s, a);        // (no batched entry point takes a prior and the check together)
+    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false, true>(s, a) : 0;
+    return launch_track_t<false, false, true>(s, a);
 }

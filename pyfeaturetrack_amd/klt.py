@@ -84,6 +84,9 @@ class KLT_TrackingContext:
         # selection mask (not in the reference): None, or a [nrows][ncols] array of bool / integers (or a Pillow "L" / "1" image) in
         # which zero marks the pixels KLTSelectGoodFeatures / KLTReplaceLostFeatures / KLTTrackSequence never place a feature on
         self.selectionMask = None
+        # motion prior (not in the reference): None, or "constant_velocity" -- KLTTrackSequence then starts each feature's search in
+        # frame k + 1 at its position in frame k plus its last displacement (KLTTrackFeatures takes predictions through `guess=`)
+        self.motionPrediction = None
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

@@ -62,6 +62,38 @@ def fb_params_from_tc(tc):
     return f
 
 
+MOTION_PREDICTIONS = (None, "constant_velocity")
+
+
+def motion_prediction_from_tc(tc):
+    """tc.motionPrediction -> None or "constant_velocity" (read with a default: a tracking context made elsewhere has no such attribute);
+    any other value is a ValueError, and so is a prediction together with the affine consistency check, which takes no prior."""
+    mode = getattr(tc, "motionPrediction", None)
+    if mode not in MOTION_PREDICTIONS:
+        raise ValueError("tc.motionPrediction must be None or 'constant_velocity' (got {0!r})".format(mode))
+    if mode is not None and tc.affineConsistencyCheck >= 0:
+        raise ValueError("motionPrediction and affineConsistencyCheck cannot both be switched on")
+    return mode
+
+
+def guess_records(guess, n, affine=False):
+    """The `guess=` argument of KLTTrackFeatures -> None, or n klt_feat records: an (n, 2) array-like of predicted frame-2 positions,
+    a row with a NaN = no guess for that feature (val -1; a row with an infinity is sent as it is and does not count either).  ValueError
+    for another shape, and for a guess together with the affine consistency check -- before any device work."""
+    if guess is None:
+        return None
+    if affine:
+        raise ValueError("guess= and affineConsistencyCheck cannot be used together: the affine check takes no prior")
+    g = np.asarray(guess, np.float32)
+    if g.shape != (n, 2):
+        raise ValueError("guess must be an (n, 2) array of predicted positions for the {0} features (got shape {1})".format(n, g.shape))
+    from .backend import FEAT_DTYPE
+    rec = np.zeros(n, FEAT_DTYPE)
+    rec["x"], rec["y"] = g[:, 0], g[:, 1]
+    rec["val"] = np.where(np.isnan(g).any(axis=1), -1, 0)
+    return rec
+
+
 def selection_mask_from_tc(tc, ncols=None, nrows=None):
     """tc.selectionMask -> None, or the [nrows][ncols] uint8 array klt_set_select_mask takes (0 = never a candidate).  Read with a default:
     a tracking context made elsewhere (the reference's own class) has no such attribute.  Accepted: a 2-D numpy array of bool or of any

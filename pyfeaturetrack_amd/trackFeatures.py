@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import fb_params_from_tc
+from .params import fb_params_from_tc, guess_records
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -356,23 +356,54 @@ def _compute_image_pyramids(tc, ctx, img1, img2):
     return first + _pyramid_handles(tc, ctx, s2, ncols, nrows)
 
 
-def KLTTrackFeatures(tc, img1, img2, featurelist):
+def KLTPredictConstantVelocity(prev_positions, featurelist):
+    """Constant-velocity guesses for the next KLTTrackFeatures call, for callers that run their own loop (klt_predict_cv_async's rule in
+    numpy float32).  `featurelist` is the list as it is now, `prev_positions` the same features before the last tracking call: a record
+    array or a feature list (x, y, val), or an (n, 2) array of positions in which a NaN row stands for a feature that was not live.
+    Returns an (n, 2) float32 array: row i = cur + (cur - prev), two float32 roundings per coordinate, for a feature that the last call
+    tracked (val == KLT_TRACKED) from a live one; every other row -- lost, or refilled by KLTReplaceLostFeatures (val > 0) -- is NaN:
+    no guess.  The result is what KLTTrackFeatures takes as `guess=`."""
+    cur = features_to_array(featurelist) if not isinstance(featurelist, np.ndarray) else featurelist
+    n = len(cur)
+    if isinstance(prev_positions, np.ndarray) and prev_positions.dtype.names:
+        px, py, plive = prev_positions["x"], prev_positions["y"], prev_positions["val"] >= 0
+    elif len(prev_positions) and hasattr(prev_positions[0], "val"):
+        prev = features_to_array(prev_positions)
+        px, py, plive = prev["x"], prev["y"], prev["val"] >= 0
+    else:
+        prev = np.asarray(prev_positions, np.float32).reshape(n, 2)
+        px, py, plive = prev[:, 0], prev[:, 1], ~np.isnan(prev).any(axis=1)
+    cx, cy = cur["x"].astype(np.float32), cur["y"].astype(np.float32)
+    out = np.full((n, 2), np.nan, np.float32)
+    ok = (cur["val"] == kltState.KLT_TRACKED) & plive
+    with np.errstate(invalid="ignore"):
+        gx = cx + (cx - px.astype(np.float32))
+        gy = cy + (cy - py.astype(np.float32))
+    out[ok, 0], out[ok, 1] = gx[ok], gy[ok]
+    return out
+
+
+def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     """trackFeatures.py:205-409 (translation model; the affine branch :347-399 calls functions the
-    reference never defines)."""
+    reference never defines).
+    `guess` (not in the reference): an (n, 2) array-like of predicted frame-2 positions, one row per feature; each feature's search starts
+    there instead of at its frame-1 position (a row with a NaN: no guess for that feature).  Works with tc.forwardBackwardCheck (the way
+    back takes no prior) and in sequential mode; with tc.affineConsistencyCheck >= 0 it raises ValueError."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
             KLTCountRemainingFeatures(featurelist), ncols, nrows))
     fb_params_from_tc(tc)                             # (ValueError for the forward-backward and the affine check together, before any device work)
+    guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
-        _track_locked(ctx, tc, img1, img2, featurelist)
+        _track_locked(ctx, tc, img1, img2, featurelist, guess)
     if KLT_verbose >= 1:
         print("\n\t{0} features successfully tracked.".format(KLTCountRemainingFeatures(featurelist)))
 
 
-def _track_locked(ctx, tc, img1, img2, featurelist):
+def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
     affine = tc.affineConsistencyCheck >= 0
     # forward-backward check: one fused launch (klt_track_fb_async), stateless -- it can be repeated like the plain tracker's.  A rejected
     # feature comes back as (-1, -1, KLT_FB_INCONSISTENT) and goes through the branches below like any other lost one.
@@ -389,7 +420,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist):
         # follows upstream KLT 1.3.4.  The per-feature templates / A matrices live on the device, keyed
         # by the feature list object.
         state = _affine_state_of(tc, ctx, featurelist)
-    ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check)
+    ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check, guess=guess)
     # The device is tracking; now every byte of the frames that were taken as resident is compared with what their slots were
     # filled from.  One that differs (the same array edited in place off the lattice, ...) is sent and built now and the tracker
     # runs again on the same input records: the records that come back are those of the last launch.
@@ -399,7 +430,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist):
             _resend(tc, ctx, slot, key)
             again = True
     if again:
-        ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check)
+        ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check, guess=guess)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
     # list-independent half of that replacement -- summed-area tables and eigenvalue keys of frame 2's level 0, 50 us at 1080p -- is
     # enqueued now, behind the tracker, and runs while the host moves the columns and finds its way into the replacement call

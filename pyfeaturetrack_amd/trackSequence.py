@@ -16,6 +16,7 @@ from .selectGoodFeatures import _fix_window, _slots_of
 
 _FB_TABLE = 60000            # feature-buffer ids used by this module: the table, then one view per frame
 _FB_ROW0 = 60001
+_FB_GUESS = 65525            # ... and the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -142,12 +143,17 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     KLTReplaceLostFeatures).  tc.affineConsistencyCheck >= 0 runs the affine check on every step,
     tc.forwardBackwardCheck the forward-backward check (rejected features are lost ones: the replacement pass fills their slots).
     tc.selectionMask (zero = no feature here) holds for the first selection and every replacement; it is read once, when the call starts.
+    tc.motionPrediction = "constant_velocity": from the second step on every feature's search starts at its position plus its last
+    displacement (klt_predict_cv_async on the two last rows of the table, then klt_track_guess_async: the previous list and the guesses
+    never leave the device); a feature the last step lost or replaced starts at its own position.  Not together with the affine check.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
     from .params import selection_mask_from_tc
     selection_mask_from_tc(tc)           # (TypeError for a tc.selectionMask of an unknown kind, likewise)
+    from .params import motion_prediction_from_tc
+    motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -173,6 +179,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     affine = tc.affineConsistencyCheck >= 0
     from .params import fb_params_from_tc
     fb_check = bool(fb_params_from_tc(tc).enabled) and not affine       # forward-backward check in every tracker step
+    from .params import motion_prediction_from_tc
+    predict = motion_prediction_from_tc(tc) == "constant_velocity"      # a motion prior for every tracker step but the first
 
     # frames are consumed lazily; the table grows in chunks so that a generator of unknown length works
     chunk = 64
@@ -255,6 +263,12 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                 cur, prev = s[j % ring], s[(j - 1) % ring]
                 if affine:
                     ctx.track_affine_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures, state)
+                elif predict and j >= 2:             # guesses from rows j - 2 and j - 1, on the same stream in front of the tracker that reads them
+                    ctx.predict_cv_async(row_fb(j - 2), row_fb(j - 1), _FB_GUESS, nFeatures)
+                    if fb_check:
+                        ctx.track_fb_guess_async(prev, cur, row_fb(j - 1), _FB_GUESS, row_fb(j), nFeatures)
+                    else:
+                        ctx.track_guess_async(prev, cur, row_fb(j - 1), _FB_GUESS, row_fb(j), nFeatures)
                 elif fb_check:                       # stateless like the plain tracker: may be enqueued ahead and repeated
                     ctx.track_fb_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
                 else:
