@@ -357,9 +357,7 @@ __global__ void affine_reset_kernel(klt_affine_rec *rec, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    klt_affine_rec r;
-    r.aff_x = -1.f; r.aff_y = -1.f; r.Axx = 1.f; r.Ayx = 0.f; r.Axy = 0.f; r.Ayy = 1.f; r.valid = 0; r.pad = 0;
-    rec[i] = r;
+    rec[i] = klt_affine_rec_initial();
 }
 
 }  // namespace

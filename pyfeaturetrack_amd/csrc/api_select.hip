@@ -183,7 +183,7 @@ int make_nms_args(klt_ctx *c, klt_feat *fl, int n, bool overwrite_all, int d, in
     na.fl = fl; na.placed_out = c->placed_d;
     na.nfeat = n; na.overwrite_all = overwrite_all;
     na.d = d; na.cell = d >= 0 ? d + 1 : 1;
-    na.cell_magic = na.cell == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)na.cell) + 1u;
+    na.cell_magic = na.cell == 1 ? 0u : klt_div_magic((unsigned)na.cell);
     if (int rc = ensure(c, c->nms_slots, c->nms_slots_cap, (size_t)n)) return rc;
     na.slots = c->nms_slots;
     na.gw = d >= 0 ? (ncols + na.cell - 1) / na.cell : 1;
@@ -655,7 +655,7 @@ int klt_min_distance_walk(klt_ctx *c, const uint64_t *keys, int nkeys, int ncols
     // kernel marks accepted candidates in a grid of ncols x nrows cells and checks nothing, a position outside would be a write outside it
     for (int i = 0; i < nkeys; i++) {
         if (keys[i] == 0ull) return fail(c, KLT_ERR_ARG, "a zero key (value 0.0 at (0, 0)) is the walk's end mark, not a candidate");
-        const int x = (int)((keys[i] >> 16) & 0xffffull), y = (int)(keys[i] & 0xffffull);
+        const int x = klt_key_x(keys[i]), y = klt_key_y(keys[i]);
         if (x >= ncols || y >= nrows) {
             char msg[128];
             snprintf(msg, sizeof msg, "candidate %d at (%d, %d) lies outside the %d x %d image", i, x, y, ncols, nrows);
@@ -762,10 +762,9 @@ int klt_download_sorted_candidates(klt_ctx *c, float *val, int32_t *x, int32_t *
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int k = 0;
     for (; k < n && h[k] != 0ull; k++) {
-        const uint32_t bits = (uint32_t)(h[k] >> 32);
-        std::memcpy(&val[k], &bits, 4);
-        x[k] = (int32_t)((h[k] >> 16) & 0xffffull);
-        y[k] = (int32_t)(h[k] & 0xffffull);
+        val[k] = klt_key_val(h[k]);
+        x[k] = klt_key_x(h[k]);
+        y[k] = klt_key_y(h[k]);
     }
     if (n_valid) *n_valid = k;
     return KLT_OK;

@@ -126,7 +126,7 @@ struct NmsArgs {
     int *placed_out;         // [0] features placed, [1] 1 if the candidates ran out before the list was full
     int *slots;              // scratch [nfeat]: fillable slot indices (REPLACING_SOME)
     klt_affine_rec *aff_rec; // optional: affine state reset for every slot filled (selectGoodFeatures.py:120-128)
-    unsigned cell_magic;     // floor(2^32 / cell) + 1: x / cell == __umulhi(x, cell_magic) for x < 65536
+    unsigned cell_magic;     // klt_div_magic(cell) (unused when cell == 1)
     int nkeys, nfeat, overwrite_all, d /* mindist-1 */, cell, gw, gh, grid_in_lds;
 };
 
@@ -238,9 +238,32 @@ __device__ __forceinline__ float klt_window_value(float gxx, float gxy, float gy
     return (float)((double)num / 2.0);
 }
 
-__device__ __forceinline__ unsigned long long klt_pack_key(float val, int x, int y)
+// A candidate's key: [f32 bits of val : 32 | x : 16 | y : 16], so that u64 order is (val, x, y) order for val > 0.  The split is
+// written here and nowhere else (host and device).
+__host__ __device__ __forceinline__ unsigned long long klt_pack_key_bits(uint32_t val_bits, int x, int y)
 {
-    return ((unsigned long long)__float_as_uint(val) << 32) | ((unsigned long long)x << 16) | (unsigned long long)y;
+    return ((unsigned long long)val_bits << 32) | ((unsigned long long)x << 16) | (unsigned long long)y;
+}
+__host__ __device__ __forceinline__ unsigned long long klt_pack_key(float val, int x, int y)
+{
+    return klt_pack_key_bits(__builtin_bit_cast(uint32_t, val), x, y);
+}
+__host__ __device__ __forceinline__ int klt_key_x(unsigned long long key) { return (int)((key >> 16) & 0xffffull); }
+__host__ __device__ __forceinline__ int klt_key_y(unsigned long long key) { return (int)(key & 0xffffull); }
+__host__ __device__ __forceinline__ uint32_t klt_key_bits(unsigned long long key) { return (uint32_t)(key >> 32); }
+__host__ __device__ __forceinline__ float klt_key_val(unsigned long long key) { return __builtin_bit_cast(float, klt_key_bits(key)); }
+
+// n / d without an integer division, exact for n < 65536 and 2 <= d < 65536: magic = floor(2^32 / d) + 1 (d == 1 has no magic
+// number in 32 bits: callers that allow it test for it)
+__host__ __device__ __forceinline__ unsigned klt_div_magic(unsigned d) { return (unsigned)((1ull << 32) / d) + 1u; }
+__device__ __forceinline__ unsigned klt_div_by_magic(unsigned n, unsigned magic) { return __umulhi(n, magic); }
+
+// the affine state of a freshly selected feature (selectGoodFeatures.py:120-128)
+__host__ __device__ __forceinline__ klt_affine_rec klt_affine_rec_initial()
+{
+    klt_affine_rec r;
+    r.aff_x = -1.f; r.aff_y = -1.f; r.Axx = 1.f; r.Ayx = 0.f; r.Axy = 0.f; r.Ayy = 1.f; r.valid = 0; r.pad = 0;
+    return r;
 }
 
 __device__ __forceinline__ unsigned long long klt_window_key(float gxx, float gxy, float gyy, double min_eig, int x, int y, float *val_out)

@@ -15,11 +15,48 @@
 //     form used here: a candidate is accepted iff no previously accepted feature lies within Chebyshev
 //     distance mindist-1.  With cells of side mindist at most one accepted feature fits in a cell, so
 //     the test reads the 3x3 neighbouring cells of a small grid held in LDS instead of a full-frame map.
+// Every shared primitive is defined once, ahead of its first user (key codec, division by a run-time constant and the initial affine
+// state in klt_internal.h); a kernel that keeps a copy of its own says so beside the primitive.  Launchers at the end.
 #include "klt_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+// ------------------------------------------------------------------ SAT, the barrier-coupled kernels' pipeline
+// What sat_rows_kernel and sat_cols_kernel share: wavefront 0 (`chain`) scans tile t in LDS buffer t & 1 while the loaders put tile t + 1
+// into the other buffer (registers -> LDS), fetch tile t + 1 + D into the ring slot that has just become free (global -> registers, a ring
+// of D tiles in flight per lane) and store the finished tile t - 1 (LDS -> global).  One barrier per tile.
+template <int D, class Fetch, class Put, class Store, class Scan>
+__device__ __forceinline__ void sat_tile_pipeline(bool chain, int ntiles, const Fetch &fetch, const Put &put, const Store &store, const Scan &scan)
+{
+    if (!chain) {
+#pragma unroll
+        for (int s = 0; s < D; s++) fetch(s, s);
+        put(0, 0);
+        fetch(0, D);
+    }
+    __syncthreads();
+    for (int t0 = 0; t0 < ntiles; t0 += D) {
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            const int t = t0 + k;
+            if (t < ntiles) {                                   // uniform
+                if (chain) {
+                    scan(k & 1);
+                } else {
+                    if (t + 1 < ntiles) {
+                        put((k + 1) % D, (k + 1) & 1);
+                        fetch((k + 1) % D, t + 1 + D);
+                    }
+                    if (t >= 1) store((k + 1) & 1, t - 1);
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (!chain) store((ntiles - 1) & 1, ntiles - 1);
+}
 
 // ------------------------------------------------------------------ SAT, row pass (+ products)
 // The only serial work is the chain itself: 64 dependent f32 adds per 64-column tile and row.  Everything else is kept
@@ -94,32 +131,7 @@ __global__ __launch_bounds__(SR_T) void sat_rows_kernel(const float *__restrict_
             }
         }
     };
-    if (!chain) {
-#pragma unroll
-        for (int s = 0; s < SR_D; s++) fetch(s, s);
-        put(0, 0);
-        fetch(0, SR_D);
-    }
-    __syncthreads();
-    for (int t0 = 0; t0 < ntiles; t0 += SR_D) {
-#pragma unroll
-        for (int k = 0; k < SR_D; k++) {
-            const int t = t0 + k;
-            if (t < ntiles) {                                   // uniform
-                if (chain) {
-                    scan(k & 1);
-                } else {
-                    if (t + 1 < ntiles) {
-                        put((k + 1) % SR_D, (k + 1) & 1);
-                        fetch((k + 1) % SR_D, t + 1 + SR_D);
-                    }
-                    if (t >= 1) store((k + 1) & 1, t - 1);
-                }
-                __syncthreads();
-            }
-        }
-    }
-    if (!chain) store((ntiles - 1) & 1, ntiles - 1);
+    sat_tile_pipeline<SR_D>(chain, ntiles, fetch, put, store, scan);
 }
 
 // ------------------------------------------------------------------ SAT, column pass (in place)
@@ -171,32 +183,7 @@ __global__ __launch_bounds__(SC_T) void sat_cols_kernel(float *__restrict__ sat,
             }
         }
     };
-    if (!chain) {
-#pragma unroll
-        for (int k = 0; k < SC_D; k++) fetch(k, k);
-        put(0, 0);
-        fetch(0, SC_D);
-    }
-    __syncthreads();
-    for (int t0 = 0; t0 < ntiles; t0 += SC_D) {
-#pragma unroll
-        for (int k = 0; k < SC_D; k++) {
-            const int t = t0 + k;
-            if (t < ntiles) {                                   // uniform
-                if (chain) {
-                    scan(k & 1);
-                } else {
-                    if (t + 1 < ntiles) {
-                        put((k + 1) % SC_D, (k + 1) & 1);
-                        fetch((k + 1) % SC_D, t + 1 + SC_D);
-                    }
-                    if (t >= 1) store((k + 1) & 1, t - 1);
-                }
-                __syncthreads();
-            }
-        }
-    }
-    if (!chain) store((ntiles - 1) & 1, ntiles - 1);
+    sat_tile_pipeline<SC_D>(chain, ntiles, fetch, put, store, scan);
 }
 
 // ------------------------------------------------------------------ seed map for REPLACING_SOME
@@ -277,14 +264,22 @@ __device__ __forceinline__ float window_sum(const float *__restrict__ s, int nco
     return ((c + a) - b) - d;
 }
 
+// Candidate cell (xi, yi) of the lattice -> its pixel (SelectArgs and MisArgs name the lattice alike), and "this pixel cannot be placed":
+// it carries this selection's stamp in the seed map (a live feature's square, or a selection mask's zero).
+// (mask_hist_kernel keeps its own copy of both: through these it takes 33 SGPRs instead of 32.)
+template <class Args> __device__ __forceinline__ int cell_x(const Args &a, int xi) { return a.bx + xi * a.step; }
+template <class Args> __device__ __forceinline__ int cell_y(const Args &a, int yi) { return a.by + yi * a.step; }
+template <class Args> __device__ __forceinline__ size_t cell_pixel(const Args &a, int xi, int yi) { return (size_t)cell_y(a, yi) * a.ncols + cell_x(a, xi); }
+__device__ __forceinline__ bool seed_blocked(const uint8_t *__restrict__ seed, uint8_t stamp, size_t pixel) { return seed[pixel] == stamp; }
+
 // key of candidate k (0 = not a candidate); also stores the eigenvalue
 __device__ __forceinline__ unsigned long long eigen_key(const SelectArgs &a, int k)
 {
     const int xi = k % a.nx, yi = k / a.nx;
-    const int x = a.bx + xi * a.step, y = a.by + yi * a.step;
+    const int x = cell_x(a, xi), y = cell_y(a, yi);
     // REPLACING_SOME: a pixel inside the exclusion square of a live feature can never be placed (selectGoodFeatures.py:64-69 marks
     // the feature map before the walk), so it is not scored at all -- most of the frame when few features were lost
-    if (a.seedmap && a.seedmap[(size_t)y * a.ncols + x] == a.seed_stamp) { if (a.valmap) a.valmap[k] = 0.f; return 0ull; }
+    if (a.seedmap && seed_blocked(a.seedmap, a.seed_stamp, cell_pixel(a, xi, yi))) { if (a.valmap) a.valmap[k] = 0.f; return 0ull; }
     const size_t plane = (size_t)a.ncols * a.nrows;
     const float gxx = window_sum(a.sat, a.ncols, x, y, a.hw, a.hh);
     const float gxy = window_sum(a.sat + plane, a.ncols, x, y, a.hw, a.hh);
@@ -293,7 +288,7 @@ __device__ __forceinline__ unsigned long long eigen_key(const SelectArgs &a, int
     unsigned long long key = klt_window_key(gxx, gxy, gyy, a.min_eig, x, y, &val);       // goodFeaturesUtils.pyx:17-19 (klt_internal.h)
     if (a.val_in) {                                                                      // test hook: the eigenvalue is given
         val = a.val_in[k];
-        key = (double)val >= a.min_eig ? (((unsigned long long)__float_as_uint(val) << 32) | ((unsigned long long)x << 16) | (unsigned long long)y) : 0ull;
+        key = (double)val >= a.min_eig ? klt_pack_key(val, x, y) : 0ull;
     }
     if (a.valmap) a.valmap[k] = val;
     return key;
@@ -313,21 +308,32 @@ __global__ __launch_bounds__(256) void eigen_kernel(SelectArgs a)
 // is unchanged (same keys), so the walk sees exactly the same prefix; if it ever runs off the end of the kept set
 // before the list is full, the host repeats the selection with the full sort.
 constexpr int HIST_BINS = 8192;
-__device__ __forceinline__ unsigned key_bin(unsigned long long key) { return (unsigned)(key >> 50) & (HIST_BINS - 1); }
+__device__ __forceinline__ unsigned key_bin(unsigned long long key) { return (klt_key_bits(key) >> 18) & (HIST_BINS - 1); }
+
+// a workgroup's (256 threads) histogram in LDS: cleared, counted by the kernel's own loop (LDS atomics), its non-empty bins added to the global one
+__device__ __forceinline__ void hist_clear(unsigned *h)
+{
+    for (int i = threadIdx.x; i < HIST_BINS; i += 256) h[i] = 0u;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void hist_flush(const unsigned *h, unsigned *__restrict__ hist)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < HIST_BINS; i += 256)
+        if (h[i]) atomicAdd(&hist[i], h[i]);
+}
 
 // stride > 1: every stride-th key only (an estimate is enough where the threshold is just a work-saving cut)
 __global__ __launch_bounds__(256) void key_hist_kernel(const unsigned long long *__restrict__ keys, int n, unsigned *__restrict__ hist, int stride)
 {
     __shared__ unsigned h[HIST_BINS];
-    for (int i = threadIdx.x; i < HIST_BINS; i += 256) h[i] = 0u;
-    __syncthreads();
+    hist_clear(h);
     for (int i = (blockIdx.x * 256 + threadIdx.x) * stride; i < n; i += gridDim.x * 256 * stride) {
         const unsigned long long key = keys[i];
         if (key) atomicAdd(&h[key_bin(key)], 1u);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < HIST_BINS; i += 256)
-        if (h[i]) atomicAdd(&hist[i], h[i]);
+    hist_flush(h, hist);
 }
 
 // info[0] = threshold bin, info[1] = number of keys in bins >= threshold, info[2] = number of valid keys
@@ -380,21 +386,14 @@ __global__ __launch_bounds__(256) void eigen_hist_kernel(SelectArgs a)
     // (XCD-contiguous eighths of the candidates instead of this interleaved sweep -- the table rows shared by windows 2 hh + 1 rows
     // apart then meet in one L2 -- were measured in round 2: no change, 14.6 us at 1080p either way)
     const bool sampler = a.hist != nullptr && (blockIdx.x & 3) == 0;
-    if (sampler) {
-        for (int i = tid; i < HIST_BINS; i += 256) h[i] = 0u;
-        __syncthreads();
-    }
+    if (sampler) hist_clear(h);
     for (int k = blockIdx.x * 256 + tid; k < ncand; k += gridDim.x * 256) {
         const unsigned long long key = eigen_key(a, k);
         a.keys[k] = key;
         if (sampler && key) atomicAdd(&h[key_bin(key)], 1u);
     }
     if (!a.hist) return;
-    if (sampler) {
-        __syncthreads();
-        for (int i = tid; i < HIST_BINS; i += 256)
-            if (h[i]) atomicAdd(&a.hist[i], h[i]);
-    }
+    if (sampler) hist_flush(h, a.hist);
 }
 
 // Keys scored ahead of time without the seed map (klt_select_prepare_async): the histogram behind the cut counts the keys outside
@@ -407,8 +406,7 @@ __global__ __launch_bounds__(256) void mask_hist_kernel(SelectArgs a)
 {
     __shared__ unsigned h[HIST_BINS];
     const int tid = threadIdx.x, ncand = a.nx * a.ny;
-    for (int i = tid; i < HIST_BINS; i += 256) h[i] = 0u;
-    __syncthreads();
+    hist_clear(h);
     constexpr int U = 8, S = MASK_HIST_SAMPLE;
     for (int k0 = S * U * blockIdx.x * 256 + tid; k0 < ncand; k0 += S * U * gridDim.x * 256) {
         unsigned long long key[U];
@@ -427,9 +425,18 @@ __global__ __launch_bounds__(256) void mask_hist_kernel(SelectArgs a)
         for (int u = 0; u < U; u++)
             if (!masked[u]) atomicAdd(&h[key_bin(key[u])], 1u);
     }
-    __syncthreads();
-    for (int i = tid; i < HIST_BINS; i += 256)
-        if (h[i]) atomicAdd(&a.hist[i], h[i]);
+    hist_flush(h, a.hist);
+}
+
+// Wavefront-ordered compaction: the lanes that keep their element get consecutive slots, in lane order, behind a range that lane 0
+// reserves on an LDS cursor.  Every lane calls.  (nms_kernel needs rank order ACROSS wavefronts and counts per wavefront: another algorithm.)
+__device__ __forceinline__ unsigned wave_compact_slot(bool keep, unsigned *cursor, int lane)
+{
+    const unsigned long long m = __ballot(keep);
+    unsigned wbase = 0;
+    if (lane == 0 && m) wbase = atomicAdd(cursor, (unsigned)__popcll(m));
+    wbase = __shfl(wbase, 0);
+    return wbase + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 // Order inside the kept set does not matter (it is sorted next), so every workgroup counts the keys it keeps in its
@@ -462,11 +469,8 @@ __global__ __launch_bounds__(256) void key_compact_kernel(const unsigned long lo
         const int i = i0 + threadIdx.x;
         const unsigned long long key = i < end ? keys[i] : 0ull;
         const bool keep = key != 0ull && key_bin(key) >= thr;
-        const unsigned long long m = __ballot(keep);
-        unsigned wbase = 0;
-        if (lane == 0 && m) wbase = atomicAdd(&s_cursor, (unsigned)__popcll(m));
-        wbase = __shfl(wbase, 0);
-        if (keep) out[base + wbase + __popcll(m & ((1ull << lane) - 1ull))] = key;
+        const unsigned slot = wave_compact_slot(keep, &s_cursor, lane);
+        if (keep) out[base + slot] = key;
     }
 }
 
@@ -474,10 +478,34 @@ __global__ __launch_bounds__(256) void key_compact_kernel(const unsigned long lo
 constexpr int SORT_E = 2048;      // keys per workgroup (16 KiB of LDS)
 constexpr int SORT_T = 1024;
 
-__device__ __forceinline__ void cmpx(unsigned long long &a, unsigned long long &b, bool desc)
+// compare-exchange; true when the two were swapped
+__device__ __forceinline__ bool cmpx(unsigned long long &a, unsigned long long &b, bool desc)
 {
     const bool sw = desc ? (a < b) : (a > b);
     if (sw) { const unsigned long long t = a; a = b; b = t; }
+    return sw;
+}
+
+// a workgroup's 2048-key chunk in LDS: in, one compare-exchange step with partner distance j of the stage that builds runs of length k, out
+__device__ __forceinline__ void bitonic_lds_load(unsigned long long *s, const unsigned long long *keys, size_t base, int t)
+{
+    s[t] = keys[base + t]; s[t + SORT_T] = keys[base + t + SORT_T];
+    __syncthreads();
+}
+__device__ __forceinline__ void bitonic_lds_step(unsigned long long *s, size_t base, int t, int j, int k)
+{
+    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+    const int l = i | j;
+    const bool desc = (((base + i) & (size_t)k) == 0);
+    unsigned long long a = s[i], b = s[l];
+    cmpx(a, b, desc);
+    s[i] = a;
+    s[l] = b;
+    __syncthreads();
+}
+__device__ __forceinline__ void bitonic_lds_store(const unsigned long long *s, unsigned long long *keys, size_t base, int t)
+{
+    keys[base + t] = s[t]; keys[base + t + SORT_T] = s[t + SORT_T];
 }
 
 // full sort of each 2048-key chunk; chunk direction follows the global network (bit 11 of the index)
@@ -486,23 +514,10 @@ __global__ __launch_bounds__(SORT_T) void bitonic_local_sort(unsigned long long 
     __shared__ unsigned long long s[SORT_E];
     const int t = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * SORT_E;
-    s[t] = keys[base + t];
-    s[t + SORT_T] = keys[base + t + SORT_T];
-    __syncthreads();
-    for (int k = 2; k <= SORT_E; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-            const int l = i | j;
-            const bool desc = (((base + i) & (size_t)k) == 0);
-            unsigned long long a = s[i], b = s[l];
-            cmpx(a, b, desc);
-            s[i] = a;
-            s[l] = b;
-            __syncthreads();
-        }
-    }
-    keys[base + t] = s[t];
-    keys[base + t + SORT_T] = s[t + SORT_T];
+    bitonic_lds_load(s, keys, base, t);
+    for (int k = 2; k <= SORT_E; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) bitonic_lds_step(s, base, t, j, k);
+    bitonic_lds_store(s, keys, base, t);
 }
 
 // one compare-exchange step with partner distance j >= SORT_E, inside the stage that builds runs of length k
@@ -514,8 +529,7 @@ __global__ __launch_bounds__(256) void bitonic_global_step(unsigned long long *_
     const size_t l = i | (size_t)j;
     const bool desc = ((i & (size_t)k) == 0);
     unsigned long long a = keys[i], b = keys[l];
-    const bool sw = desc ? (a < b) : (a > b);
-    if (sw) { keys[i] = b; keys[l] = a; }
+    if (cmpx(a, b, desc)) { keys[i] = a; keys[l] = b; }
 }
 
 // the remaining steps (j = 1024 .. 1) of stage k, inside LDS
@@ -524,21 +538,9 @@ __global__ __launch_bounds__(SORT_T) void bitonic_local_merge(unsigned long long
     __shared__ unsigned long long s[SORT_E];
     const int t = threadIdx.x;
     const size_t base = (size_t)blockIdx.x * SORT_E;
-    s[t] = keys[base + t];
-    s[t + SORT_T] = keys[base + t + SORT_T];
-    __syncthreads();
-    for (int j = SORT_E >> 1; j > 0; j >>= 1) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int l = i | j;
-        const bool desc = (((base + i) & (size_t)k) == 0);
-        unsigned long long a = s[i], b = s[l];
-        cmpx(a, b, desc);
-        s[i] = a;
-        s[l] = b;
-        __syncthreads();
-    }
-    keys[base + t] = s[t];
-    keys[base + t + SORT_T] = s[t + SORT_T];
+    bitonic_lds_load(s, keys, base, t);
+    for (int j = SORT_E >> 1; j > 0; j >>= 1) bitonic_lds_step(s, base, t, j, k);
+    bitonic_lds_store(s, keys, base, t);
 }
 
 // ------------------------------------------------------------------ greedy minimum-distance pass
@@ -559,10 +561,10 @@ __device__ __forceinline__ uint32_t grid_load(const uint32_t *p)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // L2-served: never a stale L1 line
 }
 
-// x / cell for x < 65536 without an integer division: cell_magic = floor(2^32 / cell) + 1
+// x / cell (klt_div_magic, klt_internal.h; coordinates are below 65536)
 __device__ __forceinline__ int cell_of(int v, const NmsArgs &a)
 {
-    return a.cell == 1 ? v : (int)__umulhi((unsigned)v, a.cell_magic);
+    return a.cell == 1 ? v : (int)klt_div_by_magic((unsigned)v, a.cell_magic);
 }
 
 template <bool LDSGRID>
@@ -583,6 +585,26 @@ __device__ __forceinline__ bool grid_free(const uint32_t *grid, const NmsArgs &a
             }
         }
     return ok;
+}
+
+// slot `slot` of the list filled from an accepted candidate's key; the slot's affine state starts over when the list has one
+__device__ __forceinline__ void fill_slot(const NmsArgs &a, int slot, unsigned long long key)
+{
+    klt_feat ft;
+    ft.x = (float)klt_key_x(key);
+    ft.y = (float)klt_key_y(key);
+    ft.val = (int32_t)klt_key_val(key);                                      // int(val), selectGoodFeatures.py:119
+    ft.aux = 0;
+    a.fl[slot] = ft;
+    if (a.aff_rec) a.aff_rec[slot] = klt_affine_rec_initial();
+}
+
+// a slot the candidates did not reach: selectGoodFeatures.py:78-94 (SELECTING_ALL only; DESIGN.md lists the deviation)
+__device__ __forceinline__ void mark_not_found(klt_feat *fl, int slot)
+{
+    klt_feat ft;
+    ft.x = -1.f; ft.y = -1.f; ft.val = KLT_NOT_FOUND; ft.aux = 0;
+    fl[slot] = ft;
 }
 
 template <bool LDSGRID>
@@ -631,7 +653,7 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
         const int nxt = pos + NMS_T + tid;
         key = nxt < a.nkeys ? a.keys[nxt] : 0ull;                 // prefetch the next super-batch
         const bool valid = cur != 0ull;
-        const int x = (int)((cur >> 16) & 0xffffull), y = (int)(cur & 0xffffull);
+        const int x = klt_key_x(cur), y = klt_key_y(cur);
         bool ok = valid;
         if (valid && a.d >= 0) ok = grid_free<LDSGRID>(grid, a, x, y);
         const unsigned long long m = __ballot(ok);
@@ -649,7 +671,7 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
         if (wave == 0) {
             for (int base = 0; base < total && !list_full; base += 64) {
                 const unsigned long long k = base + lane < total ? surv[base + lane] : 0ull;
-                const int sx = (int)((k >> 16) & 0xffffull), sy = (int)(k & 0xffffull);
+                const int sx = klt_key_x(k), sy = klt_key_y(k);
                 bool is_free = k != 0ull;
                 if (base > 0 && is_free && a.d >= 0) is_free = grid_free<LDSGRID>(grid, a, sx, sy);
                 unsigned long long mask = __ballot(is_free), accepted = 0ull;
@@ -673,17 +695,7 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
                 if ((accepted >> lane) & 1ull) {
                     const int rank = placed + __popcll(accepted & ((1ull << lane) - 1ull));
                     const int slot = a.overwrite_all ? rank : a.slots[rank];
-                    klt_feat ft;
-                    ft.x = (float)sx;
-                    ft.y = (float)sy;
-                    ft.val = (int32_t)__uint_as_float((uint32_t)(k >> 32));      // int(val), selectGoodFeatures.py:119
-                    ft.aux = 0;
-                    a.fl[slot] = ft;
-                    if (a.aff_rec) {
-                        klt_affine_rec r;
-                        r.aff_x = -1.f; r.aff_y = -1.f; r.Axx = 1.f; r.Ayx = 0.f; r.Axy = 0.f; r.Ayy = 1.f; r.valid = 0; r.pad = 0;
-                        a.aff_rec[slot] = r;
-                    }
+                    fill_slot(a, slot, k);
                     if (a.d >= 0) {
                         const uint32_t code = (((uint32_t)sx << 16) | (uint32_t)sy) + 1u;
                         uint32_t *cellp = &grid[cell_of(sy, a) * a.gw + cell_of(sx, a)];
@@ -700,18 +712,9 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
         __syncthreads();
         if (s_stop) break;
     }
-    // candidates exhausted: selectGoodFeatures.py:78-94 (SELECTING_ALL only; DESIGN.md lists the deviation)
     if (wave == 0) {
-        if (!list_full && a.overwrite_all) {
-            for (int i = placed + lane; i < a.nfeat; i += 64) {
-                klt_feat ft;
-                ft.x = -1.f;
-                ft.y = -1.f;
-                ft.val = KLT_NOT_FOUND;
-                ft.aux = 0;
-                a.fl[i] = ft;
-            }
-        }
+        if (!list_full && a.overwrite_all)                         // candidates exhausted
+            for (int i = placed + lane; i < a.nfeat; i += 64) mark_not_found(a.fl, i);
         if (lane == 0 && a.placed_out) {
             a.placed_out[0] = placed;
             a.placed_out[1] = list_full ? 0 : 1;      // 1: the walk ran out of candidates before the list was full
@@ -736,10 +739,16 @@ constexpr int MIS_TILE = 32, MIS_CAP = MIS_TILE * MIS_TILE, MIS_T = 256;
 
 // Workgroup -> tile.  Workgroup b runs on XCD b % 8: XCD k takes the k-th contiguous eighth of the (row-major) tiles, so that the
 // halo cells a tile shares with its neighbours come out of the same L2.
-__device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned g)
+__device__ __forceinline__ void xcd_range(unsigned k, unsigned g, unsigned &first, unsigned &len)     // XCD k's eighth of g tiles
 {
-    const unsigned k = b & 7u, i = b >> 3, base = g >> 3, rem = g & 7u;
-    return k * base + min(k, rem) + i;
+    const unsigned base = g >> 3, rem = g & 7u;
+    first = k * base + min(k, rem); len = base + (k < rem ? 1u : 0u);
+}
+__device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned g)          // the tile of workgroup b of g, one tile per workgroup
+{
+    unsigned first, len;
+    xcd_range(b & 7u, g, first, len);
+    return first + (b >> 3);
 }
 
 __global__ __launch_bounds__(MIS_T) void mis_init_kernel(MisArgs a)
@@ -766,7 +775,7 @@ __global__ __launch_bounds__(MIS_T) void mis_init_kernel(MisArgs a)
         inside[u] = xi < a.nx && yi < a.ny;
         pcell[u] = yi * a.nx + xi;
         key[u] = 1ull;
-        if (inside[u] && a.seed) key[u] = a.seed[(size_t)(a.by + yi * a.step) * a.ncols + a.bx + xi * a.step] == a.seed_stamp ? 0ull : 1ull;
+        if (inside[u] && a.seed) key[u] = seed_blocked(a.seed, a.seed_stamp, cell_pixel(a, xi, yi)) ? 0ull : 1ull;
     }
 #pragma unroll
     for (int u = 0; u < U; u++) key[u] = inside[u] && key[u] ? a.keys[pcell[u]] : 0ull;
@@ -774,12 +783,9 @@ __global__ __launch_bounds__(MIS_T) void mis_init_kernel(MisArgs a)
     for (int u = 0; u < U; u++) {
         const int p = pcell[u];
         const bool keep = key[u] != 0ull && key_bin(key[u]) >= thr;
-        if (inside[u]) a.st[p] = keep ? (uint32_t)(key[u] >> 32) : 0u;
-        const unsigned long long m = __ballot(keep);
-        unsigned wbase = 0;
-        if (lane == 0 && m) wbase = atomicAdd(&s_cursor, (unsigned)__popcll(m));
-        wbase = __shfl(wbase, 0);
-        if (keep) list[wbase + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)p;
+        if (inside[u]) a.st[p] = keep ? klt_key_bits(key[u]) : 0u;
+        const unsigned slot = wave_compact_slot(keep, &s_cursor, lane);
+        if (keep) list[slot] = (uint32_t)p;
     }
     __syncthreads();
     if (threadIdx.x == 0) a.cnt[tile] = s_cursor;
@@ -822,6 +828,10 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
     // (eight workgroups per CU instead of seven -- 2048 slots for the tiles of a 1080p frame -- were measured this way: no change)
     unsigned short *acc_local = reinterpret_cast<unsigned short *>(lds32 + (staged ? W * MIS_TILE + W * W : 0));
     const int ox = tx * MIS_TILE - R, oy = ty * MIS_TILE - R;
+    // a cell of the tile travels through LDS as q = ly * 32 + lx (tile-local coordinates); its index in the lattice
+    struct Local { int lx, ly; };
+    auto local_of = [](int q) { return Local{q % MIS_TILE, q / MIS_TILE}; };
+    auto cell_of_local = [&](int lx, int ly) { return (ty * MIS_TILE + ly) * a.nx + tx * MIS_TILE + lx; };
     uint32_t *list = a.list + (size_t)tile * MIS_CAP;
     unsigned next_p = threadIdx.x < n ? list[threadIdx.x] : 0u;           // first batch, in flight during the staging
     if (threadIdx.x == 0) { s_acc = 0u; s_cursor = 0u; s_top = 0u; s_left = 0u; }
@@ -947,11 +957,8 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
             acc_local[atomicAdd(&s_acc, 1u)] = q;
         }
         // the candidates that stay undecided are collected in LDS and go back to the list once this pass's accepted ones are known
-        const unsigned long long m = __ballot(wait);
-        unsigned wbase = 0;
-        if (lane == 0 && m) wbase = atomicAdd(&s_cursor, (unsigned)__popcll(m));
-        wbase = __shfl(wbase, 0);
-        if (wait) wait_local[wbase + __popcll(m & ((1ull << lane) - 1ull))] = q;
+        const unsigned slot = wave_compact_slot(wait, &s_cursor, lane);
+        if (wait) wait_local[slot] = q;
     }
     __syncthreads();
     const unsigned ntop = s_top;
@@ -959,13 +966,13 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
         // equal eigenvalues inside one window are ranked by position: a wavefront per candidate scans its window for an equal
         // neighbour of higher rank (one candidate after the other with the whole workgroup, and a barrier each, before: 1.7 of
         // the 11 us a dense tile lives)
-        const unsigned magic = (unsigned)((1ull << 32) / (unsigned)L) + 1u;      // w / L for w < 65536
+        const unsigned magic = klt_div_magic((unsigned)L);                       // w / L (L >= 3, w < L * L <= 65 * 65)
         for (unsigned e = (unsigned)wave; e < ntop; e += MIS_T / 64) {
-            const int q = (int)top_local[e], lx = q % MIS_TILE, ly = q / MIS_TILE;
+            const int q = (int)top_local[e], lx = local_of(q).lx, ly = local_of(q).ly;
             const uint32_t sp = S[(ly + R) * W + lx + R];
             bool outranked = false;
             for (int w = lane; w < L * L; w += 64) {
-                const int wy = (int)__umulhi((unsigned)w, magic), dx = w - wy * L - R, dy = wy - R;
+                const int wy = (int)klt_div_by_magic((unsigned)w, magic), dx = w - wy * L - R, dy = wy - R;
                 outranked |= S[(ly + R + dy) * W + lx + R + dx] == sp && (dx > 0 || (dx == 0 && dy > 0));
             }
             const bool any = __ballot(outranked) != 0ull;
@@ -973,7 +980,7 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
                 if (any) {
                     wait_local[atomicAdd(&s_cursor, 1u)] = (unsigned short)q;
                 } else {
-                    a.st[(ty * MIS_TILE + ly) * a.nx + tx * MIS_TILE + lx] = sp | 0x80000000u;
+                    a.st[cell_of_local(lx, ly)] = sp | 0x80000000u;
                     acc_local[atomicAdd(&s_acc, 1u)] = (unsigned short)q;
                 }
             }
@@ -991,18 +998,15 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
     // gone -- after the first pass that was 85 % of the list.)
     for (unsigned i0 = 0; i0 < nwait; i0 += MIS_T) {
         const unsigned i = i0 + threadIdx.x;
-        const int q = i < nwait ? (int)wait_local[i] : 0, lx = q % MIS_TILE, ly = q / MIS_TILE;
+        const int q = i < nwait ? (int)wait_local[i] : 0, lx = local_of(q).lx, ly = local_of(q).ly;
         bool keep = i < nwait;
         if (R > 0)
             for (unsigned k = 0; k < nacc; k++) {
-                const int qa = (int)acc_local[k];
-                keep = keep && (abs(lx - qa % MIS_TILE) > R || abs(ly - qa / MIS_TILE) > R);
+                const Local acc = local_of((int)acc_local[k]);
+                keep = keep && (abs(lx - acc.lx) > R || abs(ly - acc.ly) > R);
             }
-        const unsigned long long m = __ballot(keep);
-        unsigned wbase = 0;
-        if (lane == 0 && m) wbase = atomicAdd(&s_left, (unsigned)__popcll(m));
-        wbase = __shfl(wbase, 0);
-        if (keep) list[wbase + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)((ty * MIS_TILE + ly) * a.nx + tx * MIS_TILE + lx);
+        const unsigned slot = wave_compact_slot(keep, &s_left, lane);
+        if (keep) list[slot] = (uint32_t)cell_of_local(lx, ly);
     }
     __syncthreads();
     const unsigned left = s_left;
@@ -1015,26 +1019,24 @@ __device__ __forceinline__ void mis_round_tile(const MisArgs &a, int round, unsi
     // push: every cell within the exclusion square of a newly accepted candidate is rejected right away.  None of them
     // can be accepted (two accepted candidates never lie within each other's square), so the whole square is cleared.
     if (R > 0 && nacc) {
-        const unsigned magic = (unsigned)((1ull << 32) / (unsigned)L) + 1u;      // w / L for w < 65536
+        const unsigned magic = klt_div_magic((unsigned)L);                       // w / L (L >= 3, w < L * L <= 65 * 65)
         for (int w = threadIdx.x; w < L * L; w += MIS_T) {
-            const int wy = (int)__umulhi((unsigned)w, magic), dx = w - wy * L - R, dy = wy - R;
+            const int wy = (int)klt_div_by_magic((unsigned)w, magic), dx = w - wy * L - R, dy = wy - R;
             if ((dx | dy) == 0) continue;
             for (unsigned k = 0; k < nacc; k++) {
-                const int q = (int)acc_local[k];
-                const int gx = tx * MIS_TILE + (q % MIS_TILE) + dx, gy = ty * MIS_TILE + q / MIS_TILE + dy;
-                if (staged && S[(q / MIS_TILE + R + dy) * W + q % MIS_TILE + R + dx] == 0u) continue;
+                const Local acc = local_of((int)acc_local[k]);
+                const int gx = tx * MIS_TILE + acc.lx + dx, gy = ty * MIS_TILE + acc.ly + dy;
+                if (staged && S[(acc.ly + R + dy) * W + acc.lx + R + dx] == 0u) continue;
                 if (gx >= 0 && gy >= 0 && gx < a.nx && gy < a.ny) a.st[(size_t)gy * a.nx + gx] = 0u;
             }
         }
     }
     __syncthreads();
     for (unsigned i = threadIdx.x; i < nacc; i += MIS_T) {
-        const int q = (int)acc_local[i];
-        const int xi = tx * MIS_TILE + q % MIS_TILE, yi = ty * MIS_TILE + q / MIS_TILE;
-        const uint32_t sp = staged ? S[(q / MIS_TILE + R) * W + q % MIS_TILE + R] : a.st[(size_t)yi * a.nx + xi] & 0x7fffffffu;
-        const unsigned long long key = ((unsigned long long)sp << 32) | ((unsigned long long)(a.bx + xi * a.step) << 16) |
-                                       (unsigned long long)(a.by + yi * a.step);
-        a.acc_keys[s_base + i] = key;
+        const Local acc = local_of((int)acc_local[i]);
+        const int xi = tx * MIS_TILE + acc.lx, yi = ty * MIS_TILE + acc.ly;
+        const uint32_t sp = staged ? S[(acc.ly + R) * W + acc.lx + R] : a.st[(size_t)yi * a.nx + xi] & 0x7fffffffu;
+        a.acc_keys[s_base + i] = klt_pack_key_bits(sp, cell_x(a, xi), cell_y(a, yi));
     }
 }
 
@@ -1047,8 +1049,9 @@ template <int RC>
 __global__ __launch_bounds__(MIS_T) void mis_round_kernel(MisArgs a, int round, int tpw)
 {
     const unsigned ntile = (unsigned)(((a.nx + MIS_TILE - 1) / MIS_TILE) * ((a.ny + MIS_TILE - 1) / MIS_TILE));
-    const unsigned k = blockIdx.x & 7u, i = blockIdx.x >> 3, base = ntile >> 3, rem = ntile & 7u;
-    const unsigned first = k * base + min(k, rem), len = base + (k < rem ? 1u : 0u);      // XCD k's tiles
+    const unsigned i = blockIdx.x >> 3;
+    unsigned first, len;
+    xcd_range(blockIdx.x & 7u, ntile, first, len);
     unsigned cnt[MIS_TPW_MAX];
 #pragma unroll
     for (int sub = 0; sub < MIS_TPW_MAX; sub++) {
@@ -1092,6 +1095,30 @@ __device__ __forceinline__ unsigned block_scan_256(unsigned v, unsigned *red /* 
     return base + inc;
 }
 
+// "How many before my block": thread tid's share (i = tid, tid + 256, ...) of the sum of count(load(i)) over i in [0, t0); block_sum_256
+// makes the workgroup's total of it.  Sixteen loads in flight (the last workgroup of a 20 000-feature list walks 78 strides of 256
+// records), then the tail as one more batch of clamped, unconditional loads (a guard is a branch).
+// (mis_compact_kernel keeps its own copy: through this template, in every form tried, it takes 52 VGPRs instead of 50.)
+template <class Load, class Count>
+__device__ __forceinline__ unsigned count_before(int tid, int t0, Load load, Count count)
+{
+    unsigned before = 0;
+    int i = tid;
+    for (; i + 15 * 256 < t0; i += 16 * 256) {
+        decltype(load(0)) v[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) v[u] = load(i + u * 256);
+#pragma unroll
+        for (int u = 0; u < 16; u++) before += count(v[u]);
+    }
+    decltype(load(0)) v[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) v[u] = load(min(i + u * 256, max(t0 - 1, 0)));
+#pragma unroll
+    for (int u = 0; u < 16; u++) before += i + u * 256 < t0 ? count(v[u]) : 0u;
+    return before;
+}
+
 // accepted candidates of all tiles -> one dense array (tile order) + their number.  One thread per tile, any number of
 // workgroups: a workgroup first adds up the counts of the tiles before its own 256 (a few thousand words from L2), scans its
 // own, and every thread copies its tile's keys.  (The single-workgroup version took 10.7 us at 1080p and 30.7 us at 4K.
@@ -1105,8 +1132,8 @@ __global__ __launch_bounds__(256) void mis_compact_kernel(const unsigned long lo
     const int tid = threadIdx.x, t0 = blockIdx.x * 256, t = t0 + tid;
     unsigned before = 0;
     {
-        // sixteen loads in flight: the last workgroup of a 4K frame walks 22 strides of 256 counts, and a loop that waits for every
-        // load in turn made this kernel 22 us long (round-3 kernel trace) for 5 us of work
+        // count_before, written out.  Sixteen loads in flight: the last workgroup of a 4K frame walks 22 strides of 256 counts, and a
+        // loop that waits for every load in turn made this kernel 22 us long (round-3 kernel trace) for 5 us of work
         int i = tid;
         for (; i + 15 * 256 < t0; i += 16 * 256) {
             unsigned v[16];
@@ -1139,6 +1166,14 @@ __global__ __launch_bounds__(256) void mis_compact_kernel(const unsigned long lo
     if (blockIdx.x == gridDim.x - 1 && tid == 255) *out_count = base + incl;
 }
 
+// workgroup `block` of `nblocks` (256 threads each) takes its stride of the n words to clear
+__device__ __forceinline__ void zero_words(unsigned *__restrict__ p, size_t n, size_t block, size_t nblocks)
+{
+    for (size_t i = block * 256 + threadIdx.x; i < n; i += nblocks * 256) p[i] = 0u;
+}
+
+__global__ __launch_bounds__(256) void zero_words_kernel(unsigned *__restrict__ p, size_t n) { zero_words(p, n, blockIdx.x, gridDim.x); }
+
 // ---- placement of the accepted candidates: rank by counting, then the first `free slots` fill the list
 // free slots in list order (selectGoodFeatures.py:109-110): every slot when overwriting, else the lost features
 // one launch before the passes: the first workgroups list the free slots and keep a copy of the list (a repeated attempt
@@ -1148,8 +1183,7 @@ __global__ __launch_bounds__(256) void mis_prepare_kernel(const klt_feat *__rest
                                                           unsigned *__restrict__ zero, size_t zero_n, int feat_blocks)
 {
     if ((int)blockIdx.x >= feat_blocks) {
-        const size_t zb = blockIdx.x - feat_blocks, nz = gridDim.x - feat_blocks;
-        for (size_t i = zb * 256 + threadIdx.x; i < zero_n; i += nz * 256) zero[i] = 0u;
+        zero_words(zero, zero_n, blockIdx.x - feat_blocks, gridDim.x - feat_blocks);
         return;
     }
     // workgroup b owns features [256 b, 256 b + 256): copies them, and (REPLACING_SOME) lists the lost ones among them behind
@@ -1160,25 +1194,7 @@ __global__ __launch_bounds__(256) void mis_prepare_kernel(const klt_feat *__rest
     ft.val = 0;
     if (f < nfeat) { ft = fl[f]; snapshot[f] = ft; }
     if (overwrite_all) { if (f == 0) *nfill_out = nfeat; return; }
-    unsigned before = 0;
-    {
-        // (eight loads in flight: the last workgroup of a 20 000-feature list walks 78 strides of 256 records)
-        int i = tid;
-        for (; i + 15 * 256 < f0; i += 16 * 256) {
-            int v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = fl[i + u * 256].val;
-#pragma unroll
-            for (int u = 0; u < 16; u++) before += v[u] < 0 ? 1u : 0u;
-        }
-        {                                                       // the tail as one more batch: clamped, unconditional loads
-            int v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = fl[min(i + u * 256, max(f0 - 1, 0))].val;
-#pragma unroll
-            for (int u = 0; u < 16; u++) before += (i + u * 256 < f0 && v[u] < 0) ? 1u : 0u;
-        }
-    }
+    const unsigned before = count_before(tid, f0, [=](int i) { return fl[i].val; }, [](int val) { return val < 0 ? 1u : 0u; });
     const unsigned base = block_sum_256(before, red);
     const unsigned lost = (f < nfeat && ft.val < 0) ? 1u : 0u;
     const unsigned incl = block_scan_256(lost, red);
@@ -1236,26 +1252,11 @@ __global__ __launch_bounds__(256) void mis_place_kernel(NmsArgs a, const unsigne
         if (r < nfill) {
             const unsigned long long k = a.keys[i];
             const int slot = a.overwrite_all ? r : a.slots[r];
-            klt_feat ft;
-            ft.x = (float)(int)((k >> 16) & 0xffffull);
-            ft.y = (float)(int)(k & 0xffffull);
-            ft.val = (int32_t)__uint_as_float((uint32_t)(k >> 32));          // int(val), selectGoodFeatures.py:119
-            ft.aux = 0;
-            a.fl[slot] = ft;
-            if (a.aff_rec) {
-                klt_affine_rec rec;
-                rec.aff_x = -1.f; rec.aff_y = -1.f; rec.Axx = 1.f; rec.Ayx = 0.f; rec.Axy = 0.f; rec.Ayy = 1.f; rec.valid = 0; rec.pad = 0;
-                a.aff_rec[slot] = rec;
-            }
+            fill_slot(a, slot, k);
         }
     }
-    // candidates exhausted: selectGoodFeatures.py:78-94 (SELECTING_ALL only; DESIGN.md lists the deviation)
-    if (a.overwrite_all)
-        for (int s = placed + i; s < a.nfeat; s += gridDim.x * 256) {
-            klt_feat ft;
-            ft.x = -1.f; ft.y = -1.f; ft.val = KLT_NOT_FOUND; ft.aux = 0;
-            a.fl[s] = ft;
-        }
+    if (a.overwrite_all)                                           // candidates exhausted
+        for (int s = placed + i; s < a.nfeat; s += gridDim.x * 256) mark_not_found(a.fl, s);
     if (i == 0 && a.placed_out) {
         a.placed_out[0] = placed;
         a.placed_out[1] = placed < nfill ? 1 : 0;       // 1: the candidates ran out before the list was full
@@ -1269,12 +1270,15 @@ __global__ void unpack_candidates_kernel(const unsigned long long *__restrict__ 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned long long key = keys[i];
-    val[i] = __uint_as_float((uint32_t)(key >> 32));
-    x[i] = (int)((key >> 16) & 0xffffull);
-    y[i] = (int)(key & 0xffffull);
+    val[i] = klt_key_val(key);
+    x[i] = klt_key_x(key);
+    y[i] = klt_key_y(key);
 }
 
 }  // namespace
+
+// a grid of `blocks` workgroups, at least one and at most `cap`
+static unsigned clamp_grid(size_t blocks, unsigned cap) { return (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap); }
 
 void launch_sat_rows(hipStream_t s, const float *gx, const float *gy, float *sat, int ncols, int nrows)
 {
@@ -1297,7 +1301,7 @@ void launch_seed_mask(hipStream_t s, const uint8_t *mask, uint8_t *seedmap, size
 {
     if (n == 0) return;
     const size_t blocks = (n / 16 + 255) / 256;
-    hipLaunchKernelGGL(seed_mask_kernel, dim3((unsigned)(blocks < 2048 ? (blocks ? blocks : 1) : 2048)), dim3(256), 0, s, mask, seedmap, n, stamp);
+    hipLaunchKernelGGL(seed_mask_kernel, dim3(clamp_grid(blocks, 2048)), dim3(256), 0, s, mask, seedmap, n, stamp);
 }
 
 void launch_eigen(hipStream_t s, const SelectArgs &a)
@@ -1320,15 +1324,10 @@ void launch_key_threshold(hipStream_t s, const unsigned long long *keys, int n, 
     hipLaunchKernelGGL(key_threshold_kernel, dim3(1), dim3(1024), 0, s, hist, (target + 3u) / 4u, info, (const int *)nullptr, 0u);
 }
 
-__global__ __launch_bounds__(256) void zero_words_kernel(unsigned *__restrict__ p, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
-}
-
 void launch_zero_words(hipStream_t s, unsigned *p, size_t n)
 {
     const size_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < 1024 ? (blocks ? blocks : 1) : 1024)), dim3(256), 0, s, p, n);
+    hipLaunchKernelGGL(zero_words_kernel, dim3(clamp_grid(blocks, 1024)), dim3(256), 0, s, p, n);
 }
 
 int mis_tiles(int nx, int ny) { return ((nx + MIS_TILE - 1) / MIS_TILE) * ((ny + MIS_TILE - 1) / MIS_TILE); }
@@ -1384,14 +1383,14 @@ void launch_mis_prepare(hipStream_t s, const klt_feat *fl, int nfeat, int overwr
 {
     const size_t zb = (zero_n + 1023) / 1024;
     const int feat_blocks = nfeat > 0 ? (nfeat + 255) / 256 : 1;
-    hipLaunchKernelGGL(mis_prepare_kernel, dim3(feat_blocks + (unsigned)(zb < 1 ? 1 : (zb > 64 ? 64 : zb))), dim3(256), 0, s, fl, nfeat, overwrite_all,
+    hipLaunchKernelGGL(mis_prepare_kernel, dim3(feat_blocks + clamp_grid(zb, 64)), dim3(256), 0, s, fl, nfeat, overwrite_all,
                        slots, nfill_out, snapshot, zero, zero_n, feat_blocks);
 }
 
 void launch_eigen_hist(hipStream_t s, const SelectArgs &a)
 {
     const int blocks = (a.nx * a.ny + 255) / 256;
-    klt_launch(eigen_hist_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, a);
+    klt_launch(eigen_hist_kernel, dim3(clamp_grid(blocks, 1024)), dim3(256), 0, s, a);
     if (a.hist) hipLaunchKernelGGL(key_threshold_kernel, dim3(1), dim3(1024), 0, s, a.hist, a.hist_target, a.info, a.hist_slots, a.hist_per_slot);
 }
 
@@ -1401,7 +1400,7 @@ void launch_mask_hist(hipStream_t s, const SelectArgs &a)
     constexpr unsigned scale = MASK_HIST_SAMPLE / 4;
     const int per_wg = MASK_HIST_SAMPLE * 8 * 256;
     const int blocks = (a.nx * a.ny + per_wg - 1) / per_wg;
-    hipLaunchKernelGGL(mask_hist_kernel, dim3(blocks < 1024 ? (blocks ? blocks : 1) : 1024), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(mask_hist_kernel, dim3(clamp_grid(blocks, 1024)), dim3(256), 0, s, a);
     const unsigned per_slot = (a.hist_per_slot + scale - 1) / scale;
     hipLaunchKernelGGL(key_threshold_kernel, dim3(1), dim3(1024), 0, s, a.hist, (a.hist_target + scale - 1) / scale, a.info, a.hist_slots,
                        per_slot ? per_slot : 1u);

@@ -1525,6 +1525,48 @@ def test_min_distance_on_given_scores(ctx, ko, case):
         ctx.set_option(8, 1)
 
 
+def _long_list_replacement_case(ko, ncols, nrows, n, tc):
+    """Random given scores and a list of n slots, about half of them live at random positions (the other half lost)."""
+    p = params_from_tc(tc)
+    bx, by, _, _ = ko.scan_borders(p)
+    nx, ny = ncols - 2 * bx, nrows - 2 * by
+    rng = np.random.default_rng(23)
+    val = (rng.random((ny, nx)) * 1000.0).astype(np.float32)
+    val[rng.random((ny, nx)) < 0.3] = 0.5                                      # below min_eigenvalue
+    fl_in = ko.make_featurelist(n)
+    keep = np.flatnonzero(rng.random(n) < 0.5)
+    fl_in["x"][keep] = rng.uniform(bx, ncols - bx - 1, keep.size).astype(np.float32)
+    fl_in["y"][keep] = rng.uniform(by, nrows - by - 1, keep.size).astype(np.float32)
+    fl_in["val"][keep] = 0
+    return val, fl_in
+
+
+def test_min_distance_replacement_in_a_long_list_with_a_small_radius(ctx, ko):
+    """REPLACING_SOME on a list of 9000 slots, about half of them lost, with mindist = 2: the count of the lost slots before a
+    workgroup's own 256 runs through more than one unrolled batch of 16 x 256 records, and the parallel passes take the
+    any-radius instantiation with the narrow-window horizontal maxima (exclusion radius 1 cell).  The oracle fills every lost
+    slot (nothing is left to the exhaustion rule); both formulations must give its list."""
+    from pyfeaturetrack_amd import synth
+    ncols, nrows, n = 500, 300, 9000
+    tc = make_tc(mindist=2)
+    ctx.configure(tc)
+    val, fl_in = _long_list_replacement_case(ko, ncols, nrows, n, tc)
+    lost = int((fl_in["val"] < 0).sum())
+    assert n >= 4352 + 256 and lost > 4096
+    want = _oracle_min_distance(ko, val, ncols, nrows, tc, n, fl_in)
+    assert int((want["val"] >= 0).sum()) == n, "the oracle left %d lost slots unfilled" % int((want["val"] < 0).sum())
+    ctx.upload(2, synth.synth_frame(ncols, nrows, 3, 0))
+    try:
+        for algo in (1, 0):
+            ctx.set_option(8, algo)
+            ctx.set_score_override(val)
+            got, placed = ctx.select(2, n, mode=2, fl=fl_in)
+            assert placed == lost, "algo %d placed %d of %d" % (algo, placed, lost)
+            assert_feats(got, *oracle_feats(want), what="long list algo %d" % algo)
+    finally:
+        ctx.set_option(8, 1)
+
+
 def test_track_sequence_without_presmoothing():
     """tc.smoothBeforeSelecting = False: KLTTrackSequence's initial selection uses the raw frame, as KLTSelectGoodFeatures does
     (selectGoodFeatures.py:183-197) -- not level 0 of the pyramid, which is always smoothed."""
