@@ -5,6 +5,8 @@ per trial: pyramids of two frames, selection, tracking, replacement of the lost 
 bit for bit.
 
     python3 tests/fuzz/fuzz_parity.py [--trials 40] [--seed 1] [--max-pixels 400000] [--max-n 700] [--max-side 900]
+--fb / --guess / --mask: the forward-backward check, the motion prior and the selection mask on the draws of tests/draws_expected.py (the
+trial functions tests/test_gpu_draws.py runs on its fixed seed table), trial k on draw seed * 100000 + k.
 --sequence: KLTTrackSequence against the per-frame host API loop on short random sequences (both are the HIP path; the per-frame
 API is the one pinned to the reference).
 Prints one line per trial and exits non-zero at the first difference (with the drawn parameters, so that it can be replayed by seed).
@@ -357,6 +359,32 @@ def run_batch_trial(ctx, t):
     return None
 
 
+def run_draws_trials(a):
+    """--fb / --guess / --mask: the trial functions of tests/draws_expected.py on fresh draws"""
+    import draws_expected as de
+    ctx = Context(0)
+    t0 = time.time()
+    for k in range(a.trials):
+        seed = a.seed * 100000 + k
+        if a.mask:
+            c = de.mask_case(seed)
+            bad = de.run_mask_trial(ctx, c)
+            f = de.mask_facts(c)
+            stat = "placed %d, differs from the unmasked list %d, tail zero %d" % (f["placed"], f["differs"], f["tail_zero"])
+            de.mask_case.cache_clear()
+        else:
+            c = de.track_case(seed)
+            bad = de.run_track_trial(ctx, c, parts=("plain", "fb", "batch") if a.fb else ("plain", "guess", "batch"))
+            f = de.track_facts(c)
+            stat = "live %d, tracked %d, prior differs on %d, statuses %s" % (f["live"], f["tracked"], f["prior_differs"], sorted(f["statuses"]))
+            de.track_case.cache_clear()
+        print("trial %3d %s  %s  %s" % (k, "ok  " if not bad else "FAIL (%s)" % bad, c["t"], stat), flush=True)
+        if bad:
+            sys.exit(1)
+    print("%d trials identical in %.0f s" % (a.trials, time.time() - t0))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=40)
@@ -371,7 +399,12 @@ def main():
     ap.add_argument("--api", action="store_true", help="the reference-shaped Python API over random call sequences, against the oracle")
     ap.add_argument("--pil", action="store_true", help="with --api: the calls are handed Pillow images (owned storage and array-mapped ones), edited in place")
     ap.add_argument("--min-pixels", type=int, default=0)
+    ap.add_argument("--fb", action="store_true", help="klt_track_fb* (and with a prior) on the draws of tests/draws_expected.py, against the oracle compositions")
+    ap.add_argument("--guess", action="store_true", help="klt_track_guess* on the same draws")
+    ap.add_argument("--mask", action="store_true", help="klt_set_select_mask* on the mask draws of tests/draws_expected.py")
     a = ap.parse_args()
+    if a.fb or a.guess or a.mask:
+        return run_draws_trials(a)
     rng = np.random.default_rng(a.seed)
     ctx = None if (a.sequence or a.api) else Context(0)
     t0 = time.time()
