@@ -34,7 +34,8 @@ extern "C" {
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
                                    * klt_predict_cv_async are purely additive, no
-                                   * existing struct or signature moved; klt_params stays as it is) */
+                                   * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path, a read-only
+                                   * diagnostic entry) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
 
@@ -187,6 +188,20 @@ int klt_build_pyramids_async(klt_ctx *ctx, int slot);
  * or every pair of a batch -- BASELINE cfg-4) */
 int klt_build_pyramids_batch_async(klt_ctx *ctx, const int *slots, int n);
 int klt_build_pyramids(klt_ctx *ctx, int slot);
+/* Diagnostic, read-only: which kernel the most recent klt_build_pyramids* call launched for level 0 of its LAST group of frames (frames of
+ * one size and input type share launches, at most 32 per group) -- one of the KLT_L0_* codes, recorded where the launch decision is made;
+ * KLT_ERR_STATE before the first build.  *merged_grad (may be NULL): 1 when the gradients of that group's levels >= 1 went out as ONE
+ * launch with per-entry geometry (frames x (levels - 1) <= 32), 0 when each level had a launch of its own.  The choice depends on the
+ * launch's size, the taps, the subsampling and KLT_OPT_FUSED_KERNELS / KLT_OPT_FUSED_HREDUCE / KLT_OPT_L0_STREAM; every path gives the
+ * same planes bit for bit -- the tests use this to know that the kernel they were written for is the one that ran. */
+#define KLT_L0_TWO_PASS 0           /* generic two-pass convolution kernels (KLT_OPT_FUSED_KERNELS 0, asymmetric smoothing taps) */
+#define KLT_L0_TILED_LDS 1          /* smooth_grad_kernel: LDS-tiled, taps of any count */
+#define KLT_L0_RB16 2               /* smooth_grad_rb, 16-row tiles (launches below 1 000 000 pixels) */
+#define KLT_L0_RB32 3               /* smooth_grad_rb, 32-row tiles */
+#define KLT_L0_RB32_HRED 4          /* 32-row tiles with the first reduction's horizontal pass (KLT_OPT_FUSED_HREDUCE) */
+#define KLT_L0_STREAM 5             /* smooth_grad_stream (KLT_OPT_L0_STREAM), f32 frames */
+#define KLT_L0_STREAM_NO_CENTRE 6   /* smooth_grad_stream with the derivative taps' centre product elided (u8 frames) */
+int klt_level0_path(klt_ctx *ctx, int *merged_grad);
 /* bit 0: the slot holds a frame; bit 1: its pyramids are built and match the current parameters / taps (what
  * `tc.pyramid_last is not None` means in the reference, trackFeatures.py:152); 0 for a slot never used */
 int klt_slot_state(klt_ctx *ctx, int slot);

@@ -335,6 +335,13 @@ class Context:
         if sync:
             self.sync()
 
+    def level0_path(self):
+        """(KLT_L0_* code, merged) of the last build's last group of frames: which kernel built level 0, and whether the gradients of
+        levels >= 1 went out as one launch (klt_level0_path; a diagnostic -- every path gives the same planes)"""
+        merged = C.c_int()
+        code = self._check(self._lib.klt_level0_path(self._h, C.byref(merged)))
+        return code, bool(merged.value)
+
     def set_option(self, option, value):
         self._check(self._lib.klt_set_option(self._h, option, int(value)))
 

@@ -161,8 +161,9 @@ static bool l0_hred(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
 // not with the fused reduction) the smoothed image as compact planes as well
 // *fused_h1 (optional, in/out): in = the caller wants the horizontal pass of the first reduction fused into this launch; out =
 // whether it was (then c->h1 holds one H1 plane of nr x (nc / ss) floats per frame)
+// *path (optional, out): the KLT_L0_* code of the kernel launched
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */)
+                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */, int *path /* = nullptr */)
 {
     SmoothGradArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -185,7 +186,7 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     // launch also consumes the reduction stage's input (4 per pixel of level 0 -- the part of 4 (N0 + N1) that no longer
     // touches HBM); pyr_vreduce is charged the stage's output, so the step total is unchanged
     TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + N * 12 + (hred ? 4.0 * N : 0.0));
-    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream))
+    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path))
         return fail(c, KLT_ERR_DEVICE, std::string("smooth_grad launch: ") + hipGetErrorString((hipError_t)e));
     return 0;
 }
@@ -288,6 +289,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
 
         // level 0: smoothed frame (trackFeatures.py:165-166) and its gradients (:171-172)
         bool h1_fused = false;
+        int l0_path = KLT_L0_TWO_PASS;
         if (fused0) {
             for (int b = 0; b < B; b++) {
                 raw[b] = g[b]->raw_kind == 1 ? (const void *)raw8(g[b]) : (const void *)rawf(g[b]);
@@ -296,7 +298,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
             }
             h1_fused = h1_want;
             const bool copy0 = !h1_want && s0->nlev > 1;
-            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 ? cim : nullptr, s0->nc, s0->nr, &h1_fused)) return rc;
+            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 ? cim : nullptr, s0->nc, s0->nr, &h1_fused, &l0_path)) return rc;
             if (h1_fused != h1_want) return fail(c, KLT_ERR_STATE, "level-0 launch: fused reduction not as planned");
         } else {
             for (int b = 0; b < B; b++) {
@@ -304,6 +306,10 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
                 enqueue_gradients(c, cimg_of(0, b), g[b]->nc, g[b]->nr, g[b]->lv[0].img);
             }
         }
+        // what klt_level0_path reports: the last group's level-0 kernel, and whether its gradients of levels >= 1 are one launch
+        const bool merged_grad = s0->nlev > 1 && fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767;
+        c->l0_path = l0_path;
+        c->l0_merged_grad = merged_grad;
         // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
         // then the gradients of the new level.  Only surviving columns / rows are evaluated.
         for (int l = 1; l < s0->nlev; l++) {
@@ -341,8 +347,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
                     }
                 }
             }
-            const bool merged = fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767;
-            if (merged) continue;          // gradients of all levels >= 1 go out in one launch below
+            if (merged_grad) continue;          // gradients of all levels >= 1 go out in one launch below
             if (fused_grad_ok(c)) {
                 for (int b = 0; b < B; b++) { src[b] = cimg_of(l, b); rec[b] = g[b]->lv[l].img; }
                 if (int rc = enqueue_fused_grad(c, B, src, rec, ld.nc, ld.nr)) return rc;
@@ -350,7 +355,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
                 for (int b = 0; b < B; b++) enqueue_gradients(c, cimg_of(l, b), ld.nc, ld.nr, g[b]->lv[l].img);
             }
         }
-        if (s0->nlev > 1 && fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767) {
+        if (merged_grad) {
             // one launch for the gradients of every level >= 1 of every frame: entry = (frame, level), per-entry geometry; each reads its
             // compact level image and writes the level's records
             SmoothGradArgs a;
@@ -634,6 +639,14 @@ int klt_build_pyramids(klt_ctx *c, int slot)
 
 
 // -------------------------------------------------------------------------------------- inspection
+int klt_level0_path(klt_ctx *c, int *merged_grad)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (c->l0_path < 0) return fail(c, KLT_ERR_STATE, "no pyramid build yet");
+    if (merged_grad) *merged_grad = c->l0_merged_grad ? 1 : 0;
+    return c->l0_path;
+}
+
 int klt_level_dims(klt_ctx *c, int slot, int level, int *ncols, int *nrows)
 {
     if (!c) return KLT_ERR_ARG;

@@ -159,6 +159,8 @@ struct klt_ctx {
     size_t cimg_cap = 0;
     bool fuse_hreduce = true;                 // KLT_OPT_FUSED_HREDUCE
     bool l0_stream = true;                    // KLT_OPT_L0_STREAM
+    int l0_path = -1;                         // klt_level0_path: KLT_L0_* of the last geometry group of the last build (-1: no build yet)
+    bool l0_merged_grad = false;              // ... and whether that group's gradients of levels >= 1 went out as one launch
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
     // selection scratch
@@ -370,7 +372,7 @@ int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *rec);
 bool fused_smooth_ok(const klt_ctx *c);
 bool fused_grad_ok(const klt_ctx *c);
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr);
+                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr, int *path = nullptr);
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
 int download_plane(klt_ctx *c, const float *src, int stride, size_t cnt, float *dst);      // every stride-th float of a device plane to the host

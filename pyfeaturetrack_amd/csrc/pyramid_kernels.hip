@@ -1192,8 +1192,9 @@ static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
 }
 
 // The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
+// *path: the KLT_L0_* code of the kernel launched (klt_level0_path)
 template <typename TIn, bool SMOOTH, int NS>
-static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream)
+static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream, int *path)
 {
     const dim3 blk(256);
     const bool tall = rb_tall_tiles(a, batch);
@@ -1206,43 +1207,50 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
         // three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
         // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
         // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
-        // frame, 1080p batches below 8) keep the tiled kernel, whose 32-row tiles fill the chip
+        // frame, 1080p batches below 10) keep the tiled kernel, whose 32-row tiles fill the chip
         const int sh = l0_stream_seg();
         const dim3 gs((a.ncols + TW - 1) / TW, (a.nrows + sh - 1) / sh, batch);
         if (stream && a.ncols >= 2 * TW && (long long)gs.x * gs.y * gs.z >= 2048) {
             // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
             if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
                 klt_launch((smooth_grad_stream<TIn, NS, true>), gs, blk, 0, s, a, sh);
+                *path = KLT_L0_STREAM_NO_CENTRE;
                 return 0;
             }
             klt_launch((smooth_grad_stream<TIn, NS, false>), gs, blk, 0, s, a, sh);
+            *path = KLT_L0_STREAM;
             return 0;
         }
         klt_launch((smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>), g, blk, 0, s, a);
+        *path = KLT_L0_RB32_HRED;
         return 0;
     }
     if (tall) klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 32>), g, blk, 0, s, a);
     else klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 16>), g, blk, 0, s, a);
+    *path = tall ? KLT_L0_RB32 : KLT_L0_RB16;
     return 0;
 }
 
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream)
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream, int *path)
 {
+    int path_unused;
+    if (!path) path = &path_unused;
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
     if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
         const int ns = smooth ? a.smooth.n : 1;
-        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream);
-        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream);
-        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream);
-        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream);
-        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream);
-        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream);
+        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path);
+        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path);
+        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path);
+        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path);
+        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path);
+        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path);
         if (hred) return -1;                                     // (smooth_grad_hred_ok admits 5 and 9 smoothing taps only)
     }
     const size_t lds = smooth_grad_lds_bytes(smooth ? a.smooth.n / 2 : -1, a.R);
     const dim3 grid((a.ncols + TW - 1) / TW, (a.nrows + TH - 1) / TH, batch), block(256);
     int e = 0;
+    *path = KLT_L0_TILED_LDS;
     switch (kind) {
     case 0: if ((e = set_lds(smooth_grad_kernel<uint8_t, true>, lds))) return e;
             klt_launch((smooth_grad_kernel<uint8_t, true>), grid, block, lds, s, a); break;

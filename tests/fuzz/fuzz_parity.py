@@ -7,6 +7,8 @@ bit for bit.
     python3 tests/fuzz/fuzz_parity.py [--trials 40] [--seed 1] [--max-pixels 400000] [--max-n 700] [--max-side 900]
 --fb / --guess / --mask: the forward-backward check, the motion prior and the selection mask on the draws of tests/draws_expected.py (the
 trial functions tests/test_gpu_draws.py runs on its fixed seed table), trial k on draw seed * 100000 + k.
+--pyramid: the level-0 pyramid kernels on the draws of tests/pyramid_expected.py (the kernel first, then a batch of frames that reaches it;
+the trial function of tests/test_gpu_l0_edges.py), trial k on draw seed * 100000 + k.
 --sequence: KLTTrackSequence against the per-frame host API loop on short random sequences (both are the HIP path; the per-frame
 API is the one pinned to the reference).
 Prints one line per trial and exits non-zero at the first difference (with the drawn parameters, so that it can be replayed by seed).
@@ -385,6 +387,24 @@ def run_draws_trials(a):
     ctx.close()
 
 
+def run_pyramid_trials(a):
+    """--pyramid: run_pyramid_trial of tests/pyramid_expected.py on fresh draws"""
+    import pyramid_expected as pe
+    ctx = Context(0)
+    t0 = time.time()
+    for k in range(a.trials):
+        seed = a.seed * 100000 + k
+        c, f32 = pe.drawn_case(seed)
+        paths = []
+        bad = pe.run_pyramid_trial(ctx, c, f32, oracle_frames=pe.draw_oracle_frames(c), seed=seed, log=paths.append)
+        print("trial %3d %s  %s %s  %s" % (k, "ok  " if not bad else "FAIL (%s)" % bad, pe.case_id(c), "f32" if f32 else "u8", "; ".join(paths)), flush=True)
+        if bad:
+            print(repr(c), "seed", seed)
+            sys.exit(1)
+    print("%d trials identical in %.0f s" % (a.trials, time.time() - t0))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=40)
@@ -402,7 +422,10 @@ def main():
     ap.add_argument("--fb", action="store_true", help="klt_track_fb* (and with a prior) on the draws of tests/draws_expected.py, against the oracle compositions")
     ap.add_argument("--guess", action="store_true", help="klt_track_guess* on the same draws")
     ap.add_argument("--mask", action="store_true", help="klt_set_select_mask* on the mask draws of tests/draws_expected.py")
+    ap.add_argument("--pyramid", action="store_true", help="the level-0 pyramid kernels on the draws of tests/pyramid_expected.py, against the oracle")
     a = ap.parse_args()
+    if a.pyramid:
+        return run_pyramid_trials(a)
     if a.fb or a.guess or a.mask:
         return run_draws_trials(a)
     rng = np.random.default_rng(a.seed)

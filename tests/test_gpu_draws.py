@@ -1,9 +1,12 @@
 """The forward-backward check, the motion prior and the selection mask on seeded random draws (tests/draws_expected.py): every record of
 every call equals the composition made from the CPU oracle alone, bit for bit -- val, x, y and the aux word for the tracker, val, x, y for
 the selection.  The tables are fixed; tests/test_draws_rule.py asserts without a GPU that their entries exercise what they claim, and
-tests/fuzz/fuzz_parity.py --fb / --guess / --mask runs the same trial functions on fresh seeds."""
+tests/fuzz/fuzz_parity.py --fb / --guess / --mask runs the same trial functions on fresh seeds.
+test_pyramid_draw: the level-0 pyramid kernels on the draws of tests/pyramid_expected.py (the kernel is drawn first, then a frame size and a
+batch that reach it), every plane against the oracle bit for bit; tests/test_pyramid_rule.py and fuzz_parity.py --pyramid likewise."""
 import pytest
 
+from pyramid_expected import PYRAMID_SEEDS, draw_oracle_frames, drawn_case, run_pyramid_trial
 from draws_expected import API_SEEDS, MASK_LARGE_SEEDS, MASK_SEEDS, TRACK_SEEDS, mask_case, run_api_trial, run_mask_trial, run_track_trial, track_case
 
 pytestmark = pytest.mark.gpu
@@ -50,3 +53,13 @@ def test_features_together_through_the_python_api(seed):
     KLTTrackFeatures(guess=KLTPredictConstantVelocity(...)) over four frames with KLTReplaceLostFeatures in between"""
     bad = run_api_trial(seed)
     assert bad is None, bad
+
+
+@pytest.mark.parametrize("seed", PYRAMID_SEEDS)
+def test_pyramid_draw(ctx, seed):
+    """a drawn kernel (every klt_level0_path code occurs in the table), merged or separate gradient launches, a drawn batch, dtype, sigma,
+    depth and subsampling: the path as expected, the builds with KLT_OPT_L0_STREAM / KLT_OPT_FUSED_HREDUCE on and off equal in every plane
+    of every frame, and equal to the oracle"""
+    c, f32 = drawn_case(seed)
+    bad = run_pyramid_trial(ctx, c, f32, oracle_frames=draw_oracle_frames(c), seed=seed)
+    assert bad is None, "%s\n%r f32=%r" % (bad, c, f32)

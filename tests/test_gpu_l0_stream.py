@@ -1,7 +1,9 @@
 """KLT_OPT_L0_STREAM: the streaming level-0 kernel (a workgroup walks a column strip down in bands) and the tiled kernel build the
 same pyramids bit for bit -- level-0 image, both gradients and levels 1 and 2, u8 and f32 frames, 5- and 9-tap smoothing, frame
 sizes that are not multiples of the strip, the band or the segment, and batches of 1 to 16 frames (the launches below the
-streaming kernel's grid bound take the tiled kernel both ways)."""
+streaming kernel's grid bound take the tiled kernel both ways: 640 x 480 x 16, and 1921 x 1083 in batches of 1, 2 and 8).  Which
+kernel each build launched is asserted through klt_level0_path, so that a retuned bound cannot turn a case into "tiled both ways"
+unnoticed.  tests/test_gpu_l0_edges.py sweeps the strip, band and segment remainders with batches of small frames."""
 import os
 import re
 
@@ -42,20 +44,26 @@ def _frames(shape, n, f32, seed):
     return out
 
 
-def _build(ctx, frames, stream):
+STREAM_CODES, TILED_CODES = (5, 6), (2, 3, 4)        # klt_level0_path: KLT_L0_STREAM*, KLT_L0_RB16 / RB32 / RB32_HRED
+
+
+def _build(ctx, frames, stream, streams=True):
+    """`streams`: the launch is large enough for the streaming kernel (asserted through klt_level0_path both ways)"""
     ctx.set_option(OPT_L0_STREAM, stream)
     try:
         for i, f in enumerate(frames):
             ctx.upload(i, f)
         ctx.build_pyramids_batch(list(range(len(frames))), sync=True)
+        code = ctx.level0_path()[0]
+        assert code in (STREAM_CODES if stream and streams else TILED_CODES), "option %d, streams %d: level-0 kernel code %d" % (stream, streams, code)
         return [[ctx.download_level(i, p, l) for l in range(LEVELS) for p in range(3)] for i in range(len(frames))]
     finally:
         ctx.set_option(OPT_L0_STREAM, 1)
 
 
-def _check(ctx, frames, tc, what):
+def _check(ctx, frames, tc, what, streams=True):
     ctx.configure(tc)
-    on, off = _build(ctx, frames, 1), _build(ctx, frames, 0)
+    on, off = _build(ctx, frames, 1, streams), _build(ctx, frames, 0, streams)
     names = ["%s level %d" % (w, l) for l in range(LEVELS) for w in ("img", "gx", "gy")]
     for i, (a_planes, b_planes) in enumerate(zip(on, off)):
         for name, a, b in zip(names, a_planes, b_planes):
@@ -77,14 +85,17 @@ CASES = [((1080, 1920), 16), ((1083, 1921), 16), ((480, 640), 16), ((2160, 3840)
 @pytest.mark.parametrize("sigma_fact", [0.1, 0.2])      # 5- and 9-tap smoothing at the default window
 def test_stream_equals_tiled_shapes(ctx, shape, n, f32, sigma_fact):
     tc = make_tc(levels=LEVELS, ss=4, smooth_sigma_fact=sigma_fact)
-    _check(ctx, _frames(shape, n, f32, shape[0] + shape[1]), tc, "%dx%d x%d %s sigma %.1f" % (shape[1], shape[0], n, "f32" if f32 else "u8", sigma_fact))
+    _check(ctx, _frames(shape, n, f32, shape[0] + shape[1]), tc, "%dx%d x%d %s sigma %.1f" % (shape[1], shape[0], n, "f32" if f32 else "u8", sigma_fact),
+           streams=shape != (480, 640))
 
 
 @pytest.mark.parametrize("batch", [1, 2, 8, 16])
 @pytest.mark.parametrize("f32", [False, True])
 def test_stream_equals_tiled_batches(ctx, batch, f32):
     tc = make_tc(levels=LEVELS, ss=4)
-    _check(ctx, _frames((1083, 1921), batch, f32, batch), tc, "1921x1083 x%d %s" % (batch, "f32" if f32 else "u8"))
+    # 31 strips x 7 segments per frame: only the batch of 16 fills the grid bound of 2048 workgroups, batches of 1, 2 and 8 (1736 workgroups)
+    # take the tiled kernel both ways
+    _check(ctx, _frames((1083, 1921), batch, f32, batch), tc, "1921x1083 x%d %s" % (batch, "f32" if f32 else "u8"), streams=31 * 7 * batch >= 2048)
 
 
 @pytest.mark.parametrize("sigma_fact", [0.1, 0.2])
