@@ -34,8 +34,8 @@ extern "C" {
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
                                    * klt_predict_cv_async are purely additive, no
-                                   * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path, a read-only
-                                   * diagnostic entry) */
+                                   * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
+                                   * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
 
@@ -457,6 +457,23 @@ int klt_download_select_f32(klt_ctx *ctx, int what, float *dst);
 int klt_set_score_override(klt_ctx *ctx, const float *val, int count);
 /* first `n` sorted candidates of the last klt_select* as (val, x, y), selectGoodFeatures.py:234-236 */
 int klt_download_sorted_candidates(klt_ctx *ctx, float *val, int32_t *x, int32_t *y, int n, int *n_valid);
+/* Diagnostic, read-only: the keys of the score set that klt_select_prepare_async prepared for the slot's CURRENT contents under the current
+ * selection parameters -- nx * ny 64-bit keys in scan order (y outer, x inner: key k belongs to the candidate at x = borderx + (k % nx) *
+ * step, y = bordery + (k / nx) * step), each the f32 bits of val << 32 | x << 16 | y as klt_download_sorted_candidates describes them,
+ * or 0 where (double)val < max(min_eigenvalue, 1).  Waits (on the host) for the set's own event; the set is NOT consumed and nothing is
+ * enqueued.  KLT_ERR_STATE when no set matches (none prepared, already used by a selection, the slot rebuilt or the parameters changed
+ * since); KLT_ERR_ARG when capacity (in keys) < nx * ny -- *nx and *ny (either may be NULL) are set then as well, so a caller can size
+ * the buffer and repeat. */
+int klt_download_prepared_keys(klt_ctx *ctx, int slot, uint64_t *dst, size_t capacity, int *nx, int *ny);
+/* Diagnostic, read-only: which kernels built the summed-area tables of the most recent klt_select_prepare_async or klt_select* that built
+ * any (a selection that used prepared scores builds none and leaves the preparation's codes), recorded where the launch decisions are
+ * made, the fallback after the fused kernel declines a geometry included.  KLT_ERR_STATE before the first.  Either pointer may be NULL.
+ * The choice depends on KLT_OPT_SAT_VARIANT, ncols % 4, the window, nSkippedPixels and KLT_FUSED_COLS_EIGEN in the environment; every
+ * path gives the same tables and keys bit for bit -- the tests use this to know that the kernel they were written for is the one that ran. */
+#define KLT_SCORE_BARRIER 0         /* *rows, *cols: sat_rows_kernel / sat_cols_kernel (KLT_OPT_SAT_VARIANT 0, or ncols % 4 != 0) */
+#define KLT_SCORE_PIPELINE 1        /* *rows, *cols: sat_rows_pipe / sat_cols_pipe */
+#define KLT_SCORE_FUSED_KEYS 2      /* *cols only: cols_eigen_pipe, the column pass and the eigenvalue keys in one launch (klt_select_prepare_async) */
+int klt_select_score_path(klt_ctx *ctx, int *rows, int *cols);
 
 /* ---- standalone convolutions (host buffers in / out, synchronous) ---------------------------- */
 /* _convolveSeparate(imgin, horiz_kernel, vert_kernel), convolve.py:208-219 (SciPy branch: scipy.ndimage.convolve1d along axis 1, then

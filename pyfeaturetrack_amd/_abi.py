@@ -140,6 +140,8 @@ SYMBOLS = {
     "klt_select_dims": (_I, [_P, _I, _PI, _PI]),
     "klt_download_select_f32": (_I, [_P, _I, _P]),
     "klt_set_score_override": (_I, [_P, _P, _I]),
+    "klt_download_prepared_keys": (_I, [_P, _I, _P, C.c_size_t, _PI, _PI]),
+    "klt_select_score_path": (_I, [_P, _PI, _PI]),
     "klt_download_sorted_candidates": (_I, [_P, _P, _P, _P, _I, _PI]),
     "klt_smooth_f32": (_I, [_P, _P, _I, _I, C.POINTER(C.c_double), _I, _P]),
     "klt_convolve_separate_f32": (_I, [_P, _P, _I, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _P]),

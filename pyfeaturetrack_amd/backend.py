@@ -623,6 +623,28 @@ class Context:
         val = np.ascontiguousarray(val, np.float32)
         self._check(self._lib.klt_set_score_override(self._h, val.ctypes.data, val.size))
 
+    def prepared_keys(self, slot):
+        """The [ny][nx] uint64 keys (scan order; f32 bits of val << 32 | x << 16 | y, 0 = below the threshold) of the score set that
+        select_prepare computed for the slot's current contents (klt_download_prepared_keys; a diagnostic -- the set is not consumed)."""
+        cap = 1 << 16
+        while True:
+            out = np.empty(cap, np.uint64)
+            nx, ny = C.c_int(), C.c_int()
+            rc = self._lib.klt_download_prepared_keys(self._h, slot, out.ctypes.data, cap, C.byref(nx), C.byref(ny))
+            if rc == -1 and nx.value * ny.value > cap:           # KLT_ERR_ARG: the grid is larger than the buffer, and now known
+                cap = nx.value * ny.value
+                continue
+            self._check(rc)
+            return out[:nx.value * ny.value].reshape(ny.value, nx.value).copy()
+
+    def select_score_path(self):
+        """(rows, cols): which kernels built the summed-area tables of the last preparation or selection (klt_select_score_path) --
+        rows 0 barrier / 1 pipeline; cols 0 barrier / 1 pipeline / 2 fused with the eigenvalue keys.  A diagnostic: every path gives
+        the same tables."""
+        rows, cols = C.c_int(), C.c_int()
+        self._check(self._lib.klt_select_score_path(self._h, C.byref(rows), C.byref(cols)))
+        return rows.value, cols.value
+
     def sorted_candidates(self, n):
         val = np.empty(n, np.float32)
         x = np.empty(n, np.int32)

@@ -14,6 +14,7 @@ static int enqueue_sat_cols(klt_ctx *c, hipStream_t st, float *sat, int nc, int 
     const int e = c->sat_variant == 1 ? launch_sat_cols_pipe(st, sat, nc, nr) : -1;
     if (e > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e));
     if (e < 0) launch_sat_cols(st, sat, nc, nr);
+    c->score_cols_path = e < 0 ? KLT_SCORE_BARRIER : KLT_SCORE_PIPELINE;        // klt_select_score_path
     return 0;
 }
 
@@ -22,7 +23,8 @@ int enqueue_sat(klt_ctx *c, hipStream_t st, const float *gx, const float *gy, fl
     { TimerScope t(c, F_SAT_ROWS, (double)nc * nr * (8 + 12));
       const int e = c->sat_variant == 1 ? launch_sat_rows_pipe(st, gx, gy, sat, nc, nr) : -1;
       if (e > 0) return fail(c, KLT_ERR_DEVICE, hipGetErrorString((hipError_t)e));
-      if (e < 0) launch_sat_rows(st, gx, gy, sat, nc, nr); }
+      if (e < 0) launch_sat_rows(st, gx, gy, sat, nc, nr);
+      c->score_rows_path = e < 0 ? KLT_SCORE_BARRIER : KLT_SCORE_PIPELINE; }    // klt_select_score_path
     return rows_only ? 0 : enqueue_sat_cols(c, st, sat, nc, nr);
 }
 
@@ -535,6 +537,8 @@ int klt_select_prepare_async(klt_ctx *c, int slot)
             if (int rc = enqueue_sat_cols(c, c->work, c->sat_pre, nc, nr)) return rc;
             TimerScope t(c, F_EIGEN, 12.0 * N + (double)g.ncand * 8);
             launch_eigen_hist(c->work, sa);
+        } else {
+            c->score_cols_path = KLT_SCORE_FUSED_KEYS;
         }
     } else {
         if (int rc = enqueue_sat(c, c->work, s->lv[0].gx, s->lv[0].gy, c->sat_pre, nc, nr)) return rc;
@@ -698,6 +702,37 @@ int klt_download_select_f32(klt_ctx *c, int what, float *dst)
     const size_t cnt = what == 3 ? (size_t)c->sel_nx * c->sel_ny : (size_t)c->sel_nc * c->sel_nr;
     HIPCHK(c, hipSetDevice(c->device));
     return download_plane(c, src, what == 3 ? 1 : KLT_PIX_STRIDE, cnt, dst);     // image, gradx, grady: planes of pixel records
+}
+
+int klt_download_prepared_keys(klt_ctx *c, int slot, uint64_t *dst, size_t capacity, int *nx, int *ny)
+{
+    if (int rc = check_ready(c)) return rc;
+    if (!dst) return fail(c, KLT_ERR_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    Slot *s;
+    if (int rc = get_slot(c, slot, &s, false)) return rc;
+    SelGeom g;
+    if (int rc = select_geometry(c, s->nc, s->nr, &g)) return rc;
+    const ScoreCache *e = find_scores(c, s, g, select_min_eig(c->p));
+    if (!e) return fail(c, KLT_ERR_STATE, "no prepared scores for the slot's contents under the current parameters (klt_select_prepare_async)");
+    if (nx) *nx = e->nx;
+    if (ny) *ny = e->ny;
+    const size_t count = (size_t)e->nx * e->ny;
+    if (capacity < count) return fail(c, KLT_ERR_ARG, "klt_download_prepared_keys: capacity smaller than nx * ny");
+    // the set's own event where the ring still holds it, else whatever stream it may have been scored on
+    if (event_live(c, e->ev_serial)) HIPCHK(c, hipEventSynchronize(e->ev));
+    else { HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->bstream) HIPCHK(c, hipStreamSynchronize(c->bstream)); }
+    HIPCHK(c, hipMemcpy(dst, e->keys, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return KLT_OK;
+}
+
+int klt_select_score_path(klt_ctx *c, int *rows, int *cols)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (c->score_rows_path < 0 || c->score_cols_path < 0) return fail(c, KLT_ERR_STATE, "no summed-area tables have been built yet");
+    if (rows) *rows = c->score_rows_path;
+    if (cols) *cols = c->score_cols_path;
+    return KLT_OK;
 }
 
 int klt_set_score_override(klt_ctx *c, const float *val, int count)

@@ -191,6 +191,7 @@ struct klt_ctx {
     bool use_mis = true;                      // parallel minimum-distance passes instead of the sorted serial walk
     int mis_rounds_hint = 6;
     int sat_variant = 1;                      // 1: step-synchronous wavefront pipelines (sat_pipeline.hip), 0: barrier-coupled SAT kernels
+    int score_rows_path = -1, score_cols_path = -1;   // klt_select_score_path: KLT_SCORE_* of the tables' row / column pass last enqueued (-1: none yet)
     unsigned *readback = nullptr;             // pinned scratch for small results
     float *score_override = nullptr;          // test hook (klt_set_score_override)
     size_t score_override_cap = 0;

@@ -9,6 +9,8 @@ bit for bit.
 trial functions tests/test_gpu_draws.py runs on its fixed seed table), trial k on draw seed * 100000 + k.
 --pyramid: the level-0 pyramid kernels on the draws of tests/pyramid_expected.py (the kernel first, then a batch of frames that reaches it;
 the trial function of tests/test_gpu_l0_edges.py), trial k on draw seed * 100000 + k.
+--scores: the selection score kernels on the draws of tests/select_scores_expected.py (the path code first, then a geometry that reaches
+it; the trial function of tests/test_gpu_select_scores.py), trial k on draw seed * 100000 + k.
 --sequence: KLTTrackSequence against the per-frame host API loop on short random sequences (both are the HIP path; the per-frame
 API is the one pinned to the reference).
 Prints one line per trial and exits non-zero at the first difference (with the drawn parameters, so that it can be replayed by seed).
@@ -405,6 +407,25 @@ def run_pyramid_trials(a):
     ctx.close()
 
 
+def run_scores_trials(a):
+    """--scores: run_scores_trial of tests/select_scores_expected.py on fresh draws"""
+    import select_scores_expected as se
+    ctx = Context(0)
+    t0 = time.time()
+    for k in range(a.trials):
+        seed = a.seed * 100000 + k
+        c = se.draw_scores(seed)
+        paths = []
+        bad = se.run_scores_trial(ctx, c, log=paths.append)
+        print("trial %3d %s  %s  %s" % (k, "ok  " if not bad else "FAIL (%s)" % bad, se.case_id(c), "; ".join(paths)), flush=True)
+        se.expected.cache_clear()
+        if bad:
+            print(repr(c), "seed", seed)
+            sys.exit(1)
+    print("%d trials identical in %.0f s" % (a.trials, time.time() - t0))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=40)
@@ -423,7 +444,10 @@ def main():
     ap.add_argument("--guess", action="store_true", help="klt_track_guess* on the same draws")
     ap.add_argument("--mask", action="store_true", help="klt_set_select_mask* on the mask draws of tests/draws_expected.py")
     ap.add_argument("--pyramid", action="store_true", help="the level-0 pyramid kernels on the draws of tests/pyramid_expected.py, against the oracle")
+    ap.add_argument("--scores", action="store_true", help="the selection score kernels on the draws of tests/select_scores_expected.py, against the oracle")
     a = ap.parse_args()
+    if a.scores:
+        return run_scores_trials(a)
     if a.pyramid:
         return run_pyramid_trials(a)
     if a.fb or a.guess or a.mask:
