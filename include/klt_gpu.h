@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -361,6 +361,24 @@ int klt_track_fb_guess_async(klt_ctx *ctx, int slot1, int slot2, int fb_in, int 
  * refilled by a replacement pass (val > 0) -- gets (-1, -1, -1, 0): no guess.  fb_guess is allocated if needed and may be neither of the
  * other two (KLT_ERR_ARG). */
 int klt_predict_cv_async(klt_ctx *ctx, int fb_prev, int fb_cur, int fb_guess, int n);
+
+/* ---- gain / bias (lighting-insensitive) tracking (not in the reference as code) ------------------------------ */
+/* KLT 1.3.4's lighting-insensitive Newton step, which the reference carries as commented text (trackFeaturesUtils.pyx:152-239) and calls
+ * for at trackFeatures.py:119-120.  Per level and feature, with T / S the window samples of image 1 / of image 2 at the current position,
+ * n samples, nf = (float)n, all sums sequential f32 chains in row-major order: sum1 = SUM T, sq1 = SUM T*T, sum2 = SUM S, sq2 = SUM S*S;
+ * alpha = (float)sqrt((double)((sq1/nf) / (sq2/nf))), beta = sum1/nf - alpha*(sum2/nf), diff = (T - S*alpha) - beta;
+ * alpha_g = (float)sqrt((double)((sum1/nf) / (sum2/nf))) (the ratio of the means, as KLT 1.3.4 has it), gradient sums Tg + Sg*alpha_g;
+ * everything else -- the five product sums, the solve, step factor, bounds tests, iteration cap, status priority, retainTrackers, border
+ * rule, aux word -- is klt_track_async's; the residue is taken from |diff| with alpha and beta of the final position.  A window whose
+ * sums are not all positive and finite, or whose alpha / alpha_g (or Newton step) is not finite, ends its level with KLT_SMALL_DET at the
+ * position it has.  With mode 1 klt_track, klt_track_async and klt_track_batch_async launch these kernels (features in list order:
+ * KLT_OPT_TRACK_XCD_ORDER and KLT_OPT_TRACK_TREE_SUMS are not looked at); klt_track_fb*, klt_track_guess*, klt_track_fb_guess_async and
+ * klt_track_affine* return KLT_ERR_STATE before anything is enqueued.  With mode 0 nothing changes. */
+typedef struct { int32_t mode; } klt_light_params;   /* 0 off (default), 1 gain + bias */
+int klt_set_light_params(klt_ctx *ctx, const klt_light_params *p);          /* another mode: KLT_ERR_ARG */
+/* which kernel the last launch with mode 1 took -- 0: no such launch yet, 1: one feature per wavefront, 2: four 7x7 features per wavefront
+ * (7x7 windows, features x pairs >= 2048, KLT_OPT_TRACK_VARIANT != 0).  A diagnostic: both give the same records. */
+int klt_track_light_path(klt_ctx *ctx);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

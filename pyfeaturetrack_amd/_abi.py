@@ -39,6 +39,10 @@ class KltFbParams(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("max_error", C.c_float)]
 
 
+class KltLightParams(C.Structure):
+    _fields_ = [("mode", C.c_int32)]
+
+
 class KltAffineRec(C.Structure):
     _fields_ = [("aff_x", C.c_float), ("aff_y", C.c_float), ("Axx", C.c_float), ("Ayx", C.c_float), ("Axy", C.c_float),
                 ("Ayy", C.c_float), ("valid", C.c_int32), ("pad", C.c_int32)]
@@ -126,6 +130,8 @@ SYMBOLS = {
     "klt_track_guess_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
     "klt_track_fb_guess_async": (_I, [_P, _I, _I, _I, _I, _I, _I, _I]),
     "klt_predict_cv_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_set_light_params": (_I, [_P, C.POINTER(KltLightParams)]),
+    "klt_track_light_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

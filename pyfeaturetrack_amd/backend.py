@@ -11,9 +11,9 @@ import threading
 
 import numpy as np
 
-from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
+from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
                    KltTrackStats, load_library)
-from .params import affine_params_from_tc, fb_params_from_tc, params_from_tc, taps_from_params
+from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
 assert FEAT_DTYPE.itemsize == C.sizeof(KltFeat)
@@ -101,11 +101,28 @@ class Context:
         return bytes(params_from_tc(tc)) == self._params_key
 
     def configure(self, tc):
+        light = light_params_from_tc(tc)                 # (ValueError for a combination that is not offered, before anything is set)
         self.set_params(params_from_tc(tc))
+        self.set_light_params(light)
         self.set_affine_params(affine_params_from_tc(tc))
         fb = fb_params_from_tc(tc)
         if fb.enabled:
             self.set_fb_params(fb)
+
+    # ------------------------------------------------ gain / bias tracking (klt_set_light_params)
+    def set_light_params(self, lp=None, mode=None):
+        """klt_set_light_params: `lp` a KltLightParams, or mode alone (0 off, 1 gain + bias).  While mode 1 is set, track / track_async /
+        track_batch_async run the gain / bias kernels and every other tracker entry point is refused."""
+        if lp is None:
+            lp = KltLightParams(int(mode))
+        key = bytes(lp)
+        if key != getattr(self, "_light_key", None):
+            self._check(self._lib.klt_set_light_params(self._h, C.byref(lp)))
+            self._light_key = key
+
+    def track_light_path(self):
+        """klt_track_light_path: 0 no lighting launch yet, 1 wave kernel, 2 quad kernel (the last launch with mode 1; a diagnostic)"""
+        return self._check(self._lib.klt_track_light_path(self._h))
 
     # ------------------------------------------- forward-backward consistency check
     def set_fb_params(self, fb=None, max_error=None):

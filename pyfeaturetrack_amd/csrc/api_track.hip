@@ -152,8 +152,20 @@ static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nl
 {
     const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
     TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * nlev + 32), c->stream);   // refined by the caller from klt_track_stats
+    if (c->lightp.mode) {                                   // gain / bias tracking (klt_set_light_params): kernels of their own, features in list order
+        if (launch_track_light(c->stream, a, &c->light_path)) return fail(c, KLT_ERR_ARG, "unsupported window size");
+        return 0;
+    }
     if (guess ? launch_track_guess(c->stream, a) : launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
     return 0;
+}
+
+// gain / bias tracking is offered by klt_track, klt_track_async and klt_track_batch_async alone: every other tracker entry point is refused
+// while it is switched on, before anything is enqueued
+static int refuse_with_light(klt_ctx *c, const char *what)
+{
+    if (!c || !c->lightp.mode) return 0;
+    return fail(c, KLT_ERR_STATE, std::string(what) + " is not offered together with lighting compensation (klt_set_light_params mode 1)");
 }
 
 static int count_live(const klt_feat *f, int n)
@@ -169,6 +181,8 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
                         int fb_guess = -1)
 {
     if (int rc = check_ready(c)) return rc;
+    if (fb || guess)
+        if (int rc = refuse_with_light(c, fb ? "the forward-backward check" : "a motion prior")) return rc;
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
     if (fb)
         if (int rc = check_fb_buffers(c, fb_in, fb_out, fb_back)) return rc;
@@ -193,7 +207,8 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
         fill_fb_params(c, a);
         a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
     }
-    if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
+    if (!c->lightp.mode)
+        if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
     if (int rc = enqueue_track(c, a, 1, s1->nlev, guess)) return rc;
     if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
     {
@@ -243,6 +258,20 @@ int klt_predict_cv_async(klt_ctx *c, int fb_prev, int fb_cur, int fb_guess, int 
     return KLT_OK;
 }
 
+int klt_set_light_params(klt_ctx *c, const klt_light_params *p)
+{
+    if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
+    if (p->mode != 0 && p->mode != 1) return fail(c, KLT_ERR_ARG, "lighting compensation mode must be 0 (off) or 1 (gain + bias)");
+    c->lightp = *p;
+    return KLT_OK;
+}
+
+int klt_track_light_path(klt_ctx *c)
+{
+    if (!c) return KLT_ERR_ARG;
+    return c->light_path;
+}
+
 int klt_set_fb_params(klt_ctx *c, const klt_fb_params *p)
 {
     if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
@@ -257,6 +286,8 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
                        int n, bool fb, const int *fb_guess = nullptr)
 {
     if (int rc = check_ready(c)) return rc;
+    if (fb || fb_guess)
+        if (int rc = refuse_with_light(c, fb ? "the forward-backward check" : "a motion prior")) return rc;
     if (!slot1 || !slot2 || !fb_in || !fb_out || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
     if (fb_guess)
         for (int i = 0; i < npairs; i++) {
@@ -324,7 +355,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     a.npairs = npairs;
     fill_track_params(c, first, a, n);
     if (fb) fill_fb_params(c, a);
-    {
+    if (!c->lightp.mode) {
         // one permutation per pair, kept with the set of input lists (see set_track_order)
         std::vector<const klt_feat *> ins((size_t)npairs);
         for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
@@ -359,6 +390,7 @@ int klt_track_guess_batch_async(klt_ctx *c, const int *slot1, const int *slot2, 
 int klt_track_guess(klt_ctx *c, int slot1, int slot2, klt_feat *inout, const klt_feat *guess, int n, int *n_tracked)
 {
     if (!c || !inout || !guess) return fail(c, KLT_ERR_ARG, "null argument");
+    if (int rc = refuse_with_light(c, "a motion prior")) return rc;
     const int fi = 65534, fo = 65535, fg = 65531;
     if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: both lists are ours until then)
     if (int rc = klt_featbuf_upload_async(c, fg, guess, n)) return rc;
@@ -382,6 +414,7 @@ int klt_track(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int *n_t
 int klt_track_fb(klt_ctx *c, int slot1, int slot2, klt_feat *inout, klt_feat *back, int n, int *n_tracked)
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
+    if (int rc = refuse_with_light(c, "the forward-backward check")) return rc;
     const int fi = 65534, fo = 65535, fbk = 65532;
     if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;
     if (int rc = klt_track_fb_async(c, slot1, slot2, fi, fo, n, back ? fbk : -1)) return rc;
@@ -476,6 +509,7 @@ int klt_affine_download(klt_ctx *c, int state, klt_affine_rec *dst, int n)
 int klt_track_affine_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, int state)
 {
     if (!c) return KLT_ERR_ARG;
+    if (int rc = refuse_with_light(c, "the affine consistency check")) return rc;
     if (fb_in == fb_out) return fail(c, KLT_ERR_ARG, "the consistency check needs the records before and after: fb_in != fb_out");
     if (c->ap.mode >= 0 && (state < 0 || (size_t)state >= c->aff.size() || !c->aff[state].rec || c->aff[state].n < n))
         return fail(c, KLT_ERR_STATE, "affine state not allocated (klt_affine_alloc) or smaller than the feature list");
@@ -506,6 +540,7 @@ int klt_track_affine_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_o
 int klt_track_affine(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int state, int *n_tracked)
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
+    if (int rc = refuse_with_light(c, "the affine consistency check")) return rc;
     const int fi = 65534, fo = 65535;
     if (int rc = klt_featbuf_upload(c, fi, inout, n)) return rc;
     if (int rc = klt_track_affine_async(c, slot1, slot2, fi, fo, n, state)) return rc;

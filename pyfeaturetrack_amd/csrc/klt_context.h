@@ -244,6 +244,8 @@ struct klt_ctx {
     static constexpr size_t kBatchTables = 256, kBatchOrders = 128;
     klt_affine_params ap{-1, 15, 15, 10, 10.f, 0.02f, 1.5f};      // klt.py:67-73 defaults
     klt_fb_params fbp{0, 1.0f};                                    // forward-backward check (klt_set_fb_params)
+    klt_light_params lightp{0};                                    // gain / bias tracking (klt_set_light_params); 0 = off
+    int light_path = 0;                                            // klt_track_light_path: kernel of the last lighting launch (0: none yet)
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;

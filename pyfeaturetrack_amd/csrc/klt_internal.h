@@ -322,6 +322,8 @@ void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
 int launch_track(hipStream_t s, const TrackArgs &a);
 int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
+// the gain / bias tracker (track_light_kernels.hip; klt_set_light_params mode 1): *path = 1 wave kernel, 2 quad kernel; a.order is not looked at
+int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

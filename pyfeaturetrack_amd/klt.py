@@ -87,6 +87,10 @@ class KLT_TrackingContext:
         # motion prior (not in the reference): None, or "constant_velocity" -- KLTTrackSequence then starts each feature's search in
         # frame k + 1 at its position in frame k plus its last displacement (KLTTrackFeatures takes predictions through `guess=`)
         self.motionPrediction = None
+        # gain / bias tracking (not in the reference as code: KLT 1.3.4's lighting-insensitive step, which trackFeaturesUtils.pyx:152-239
+        # carries as commented text): None, or "gain_bias" -- KLTTrackFeatures then fits a gain and an offset between the two windows in
+        # every Newton iteration and in the residue.  (tc.lighting_insensitive, the reference's switch, raises as it does there.)
+        self.lightingCompensation = None
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

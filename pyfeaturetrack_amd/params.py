@@ -1,7 +1,7 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import numpy as np
 
-from ._abi import KltAffineParams, KltFbParams, KltParams
+from ._abi import KltAffineParams, KltFbParams, KltLightParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -14,7 +14,7 @@ def params_from_tc(tc):
     max_residue (compared against a numpy float32, trackFeatures.py:124), doubles elsewhere."""
     if tc.lighting_insensitive:
         # trackFeaturesUtils.pyx:434-435 raises the same exception inside the Newton loop
-        raise Exception("Not implemented")
+        raise Exception("Not implemented (the reference's switch; gain / bias tracking is tc.lightingCompensation = 'gain_bias')")
     if tc.window_width != tc.window_height:
         # the reference's patch loops are transposed for non-square windows (SURVEY.md A.7)
         raise ValueError("window_width must equal window_height")
@@ -74,6 +74,30 @@ def motion_prediction_from_tc(tc):
     if mode is not None and tc.affineConsistencyCheck >= 0:
         raise ValueError("motionPrediction and affineConsistencyCheck cannot both be switched on")
     return mode
+
+
+LIGHTING_COMPENSATIONS = (None, "gain_bias")
+
+
+def light_params_from_tc(tc, guess=False, sequence=False):
+    """tc.lightingCompensation -> klt_light_params: None (the default; read with one, a tracking context made elsewhere has no such
+    attribute) packs mode 0, "gain_bias" mode 1, any other value is a ValueError.  The gain / bias tracker is offered on its own: a
+    ValueError as well -- before any device work -- when it is switched on together with tc.forwardBackwardCheck, tc.motionPrediction,
+    tc.affineConsistencyCheck >= 0, a `guess=` argument (`guess`) or KLTTrackSequence (`sequence`).  tc.lighting_insensitive, the
+    reference's own switch, keeps raising "Not implemented" (params_from_tc), as the reference does."""
+    mode = getattr(tc, "lightingCompensation", None)
+    if not isinstance(mode, (str, type(None))) or mode not in LIGHTING_COMPENSATIONS:
+        raise ValueError("tc.lightingCompensation must be None or 'gain_bias' (got {0!r})".format(mode))
+    lp = KltLightParams()
+    lp.mode = 0 if mode is None else 1
+    if lp.mode:
+        for on, what in ((bool(getattr(tc, "forwardBackwardCheck", False)), "forwardBackwardCheck"),
+                         (getattr(tc, "motionPrediction", None) is not None, "motionPrediction"),
+                         (getattr(tc, "affineConsistencyCheck", -1) >= 0, "affineConsistencyCheck"),
+                         (bool(guess), "a guess= argument"), (bool(sequence), "KLTTrackSequence")):
+            if on:
+                raise ValueError("lightingCompensation and {0} cannot be used together".format(what))
+    return lp
 
 
 def guess_records(guess, n, affine=False):

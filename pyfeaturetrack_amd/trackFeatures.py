@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import fb_params_from_tc, guess_records
+from .params import fb_params_from_tc, guess_records, light_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -388,12 +388,15 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     reference never defines).
     `guess` (not in the reference): an (n, 2) array-like of predicted frame-2 positions, one row per feature; each feature's search starts
     there instead of at its frame-1 position (a row with a NaN: no guess for that feature).  Works with tc.forwardBackwardCheck (the way
-    back takes no prior) and in sequential mode; with tc.affineConsistencyCheck >= 0 it raises ValueError."""
+    back takes no prior) and in sequential mode; with tc.affineConsistencyCheck >= 0 it raises ValueError.
+    tc.lightingCompensation = "gain_bias" (not in the reference as code): the gain / bias tracker of DESIGN.md section 9d, in sequential and
+    in ping-pong mode; ValueError together with forwardBackwardCheck, motionPrediction, affineConsistencyCheck >= 0 or `guess`."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
             KLTCountRemainingFeatures(featurelist), ncols, nrows))
     fb_params_from_tc(tc)                             # (ValueError for the forward-backward and the affine check together, before any device work)
+    light_params_from_tc(tc, guess=guess is not None)      # (ValueError for lightingCompensation with a check, a prior or a guess, likewise)
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)

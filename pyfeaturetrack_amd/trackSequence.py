@@ -154,6 +154,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     selection_mask_from_tc(tc)           # (TypeError for a tc.selectionMask of an unknown kind, likewise)
     from .params import motion_prediction_from_tc
     motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
+    from .params import light_params_from_tc
+    light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
