@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -296,6 +296,31 @@ int klt_select(klt_ctx *ctx, int slot, int mode, int use_pyramid, klt_feat *inou
  * lives in. */
 int klt_set_select_mask(klt_ctx *ctx, const uint8_t *mask, int ncols, int nrows, int pitch);
 int klt_set_select_mask_device(klt_ctx *ctx, const uint8_t *dev_mask, int ncols, int nrows);
+/* Selection grid: a cap on how many features one image cell may hold (grid-balanced selection, as visual-odometry front ends bucket their
+ * features).  Cells are cell_width x cell_height PIXELS; on an ncols x nrows frame there are gw = ceil(ncols / cell_width) by
+ * gh = ceil(nrows / cell_height) of them (the last column and row may be narrower) and pixel (x, y) lies in cell
+ * (y / cell_height) * gw + x / cell_width.  State of the context like the mask and the parameters, and independent of the frame size.
+ * The rule, composed from _enforceMinimumDistance (selectGoodFeatures.py:45-135): let A = (a_1, a_2, ...) be the candidates the walk
+ * accepts, in the order it accepts them, if the list were never full (in KLT_REPLACING_SOME the squares of the live features are marked
+ * first, as always).  Without a grid the selection is the first `free slots` members of A.  With a grid, cap(c) = max_per_cell in
+ * KLT_SELECTING_ALL and max(max_per_cell - live(c), 0) in KLT_REPLACING_SOME, where live(c) counts the list's records with val >= 0 whose
+ * position passes 0 <= x < ncols && 0 <= y < nrows as f32 comparisons (a NaN fails) in the cell of ((int)x, (int)y); a_i is KEPT iff it
+ * is among the first cap(cell(a_i)) members of A in its cell, and the free slots (every slot when overwriting, else the lost ones) are
+ * filled in list order with the kept members in order, until slots or members run out.  Slots of a KLT_SELECTING_ALL the members did
+ * not reach become (-1, -1, KLT_NOT_FOUND), as without a grid.  Live features are never removed, even where a cell holds more than
+ * max_per_cell of them.  A member of A that is not kept STILL excludes its neighbours: A does not depend on the grid, and the grid never
+ * admits a weaker neighbour of a stronger corner it turned away.
+ * klt_min_distance_walk, klt_scan_good_features_f32, klt_select_prepare_async and the tracker ignore the grid; the mask and
+ * klt_set_score_override act on the point list, the grid on A, so they compose; KLT_OPT_SELECT_AFFINE_STATE resets exactly the slots that
+ * are filled.  A context without a grid enqueues nothing for it.
+ * g == NULL or g->cell_width == 0 removes the grid (the default).  KLT_ERR_ARG for cell_width or cell_height < 1 or max_per_cell outside
+ * 1 .. 65535; KLT_ERR_STATE between klt_select_begin_async and klt_select_finish.
+ * klt_select_grid_path: how the last selection under a grid applied it -- 0: none has run yet; 1: a filter kernel between the parallel
+ * minimum-distance passes and the placement by rank; 2: the quota inside the greedy walk (KLT_OPT_SELECT_PARALLEL_NMS = 0, exclusion
+ * squares too large for the passes, more accepted candidates than the ranking takes, or max_per_cell above 64). */
+typedef struct { int32_t cell_width, cell_height, max_per_cell; } klt_select_grid;
+int klt_set_select_grid(klt_ctx *ctx, const klt_select_grid *g);
+int klt_select_grid_path(klt_ctx *ctx);
 /* replaces _enforceMinimumDistance(pointlist, featurelist, ncols, nrows, mindist, min_eigenvalue, overwriteAllFeatures) called on its own
  * (selectGoodFeatures.py:45-135): the greedy walk over a GIVEN candidate list in the GIVEN order.  keys[i] = f32 bits of val << 32 |
  * x << 16 | y (what klt_download_sorted_candidates returns, re-packed); the caller has dropped the candidates the walk skips without

@@ -43,6 +43,10 @@ class KltLightParams(C.Structure):
     _fields_ = [("mode", C.c_int32)]
 
 
+class KltSelectGrid(C.Structure):
+    _fields_ = [("cell_width", C.c_int32), ("cell_height", C.c_int32), ("max_per_cell", C.c_int32)]
+
+
 class KltAffineRec(C.Structure):
     _fields_ = [("aff_x", C.c_float), ("aff_y", C.c_float), ("Axx", C.c_float), ("Ayx", C.c_float), ("Axy", C.c_float),
                 ("Ayy", C.c_float), ("valid", C.c_int32), ("pad", C.c_int32)]
@@ -117,6 +121,8 @@ SYMBOLS = {
     "klt_select": (_I, [_P, _I, _I, _I, _P, _I, _PI]),
     "klt_set_select_mask": (_I, [_P, _P, _I, _I, _I]),
     "klt_set_select_mask_device": (_I, [_P, _P, _I, _I]),
+    "klt_set_select_grid": (_I, [_P, C.POINTER(KltSelectGrid)]),
+    "klt_select_grid_path": (_I, [_P]),
     "klt_min_distance_walk": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _PI]),
     "klt_track_async": (_I, [_P, _I, _I, _I, _I, _I]),
     "klt_track": (_I, [_P, _I, _I, _P, _I, _PI]),

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
+from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
                    KltTrackStats, load_library)
 from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
@@ -627,6 +627,30 @@ class Context:
             return
         self.set_select_mask(mask)
         self._mask_state = mask.copy()
+
+    # ------------------------------------------------------------- selection grid
+    def set_select_grid(self, grid):
+        """klt_set_select_grid: `grid` = (cell_width, cell_height, max_per_cell), or None for no grid.  No cell of cell_width x cell_height
+        pixels holds more than max_per_cell features after a selection of this context, until it is set again."""
+        self._grid_state = "direct"
+        if grid is None:
+            self._check(self._lib.klt_set_select_grid(self._h, None))
+            self._grid_state = None
+            return
+        cw, ch, q = grid
+        g = KltSelectGrid(int(cw), int(ch), int(q))
+        self._check(self._lib.klt_set_select_grid(self._h, C.byref(g)))
+        self._grid_state = (int(cw), int(ch), int(q))
+
+    def select_grid_path(self):
+        """klt_select_grid_path: 0 no selection under a grid yet, 1 filter kernel before the rank placement, 2 quota inside the walk"""
+        return self._check(self._lib.klt_select_grid_path(self._h))
+
+    def sync_select_grid(self, grid):
+        """The reference-shaped API's grid (params.select_grid_from_tc: None or a tuple of three ints): sent only when it differs from
+        what the context holds."""
+        if self.__dict__.get("_grid_state") != grid:
+            self.set_select_grid(grid)
 
     def select_intermediate(self, what):
         nc, nr = C.c_int(), C.c_int()

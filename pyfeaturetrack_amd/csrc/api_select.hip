@@ -41,6 +41,32 @@ int restore_list(klt_ctx *c, klt_feat *fl, int n)
     return 0;
 }
 
+// ---- per-cell quota (klt_set_select_grid)
+// the quota's arguments on an nc x nr frame and its buffer (klt_context.h), not cleared
+int make_quota_args(klt_ctx *c, int nc, int nr, QuotaArgs &qa)
+{
+    const klt_select_grid &g = c->sel_grid;
+    const long long gw = ((long long)nc + g.cell_width - 1) / g.cell_width, gh = ((long long)nr + g.cell_height - 1) / g.cell_height;
+    const size_t cells = (size_t)(gw * gh);                        // at most one per pixel
+    if (int rc = ensure(c, c->quota_buf, c->quota_buf_cap, 3 * cells + (cells + 1) / 2 + 1)) return rc;
+    qa.live = (unsigned *)(c->quota_buf + 3 * cells);
+    qa.cw = g.cell_width; qa.ch = g.cell_height; qa.gw = (int)gw; qa.q = g.max_per_cell; qa.cells = (int)cells;
+    qa.cw_magic = g.cell_width >= 65536 ? 0u : klt_div_magic((unsigned)g.cell_width);
+    qa.ch_magic = g.cell_height >= 65536 ? 0u : klt_div_magic((unsigned)g.cell_height);
+    return 0;
+}
+unsigned *quota_nkept(const QuotaArgs &qa) { return qa.live + qa.cells; }
+
+// live(cell) of list `fl` in stream order, in front of the filter or the walk: a repeat comes through here again, with the list back from
+// its snapshot.  rounds: the filter's planes and its count are cleared as well.
+int enqueue_quota_live(klt_ctx *c, const QuotaArgs &qa, bool rounds, const klt_feat *fl, int n, bool overwrite_all, int nc, int nr)
+{
+    if (rounds) HIPCHK(c, hipMemsetAsync(c->quota_buf, 0, 3 * (size_t)qa.cells * sizeof(unsigned long long) + ((size_t)qa.cells + 1) * sizeof(unsigned), c->stream));
+    else HIPCHK(c, hipMemsetAsync(qa.live, 0, (size_t)qa.cells * sizeof(unsigned), c->stream));
+    if (!overwrite_all) launch_quota_live(c->stream, fl, n, nc, nr, qa);      // KLT_SELECTING_ALL: every slot is free, no feature counts
+    return 0;
+}
+
 // start of an attempt: free slots + snapshot of the list, scores / histogram / cut (attempt 0) or "every candidate" (attempt 1), tile lists
 int select_job_start(klt_ctx *c, SelectJob &j)
 {
@@ -54,7 +80,7 @@ int select_job_start(klt_ctx *c, SelectJob &j)
             // LOST feature (at least 4096) instead of 64 per list entry -- most of a frame's candidates never enter the passes.
             // (cfg-5, 50-95 lost of 20000 per frame: a floor of 65536 / 16384 / 4096 / 1024 candidates reads 0.424 / 0.387 /
             // 0.365 / 0.364 ms per frame; too tight a cut only costs the repeat below, never the result)
-            sa.hist_target = 4096 / 4; sa.hist_slots = j.nfill_d; sa.hist_per_slot = 64 / 4;
+            sa.hist_target = 4096 / 4 * j.cut_scale; sa.hist_slots = j.nfill_d; sa.hist_per_slot = 64 / 4 * j.cut_scale;
         }
         if (j.pre) {
             // scored ahead of time without the seed map: histogram of the keys outside it here, the mask itself in mis_init
@@ -89,13 +115,22 @@ int select_job_rounds(klt_ctx *c, SelectJob &j)
     j.look = j.round < 64 ? j.round : 64;                        // the last `look` passes
     const unsigned *rem_d = j.ma.remaining + j.round - j.look;
     launch_mis_compact(c->stream, j.ma, c->keys2, j.acc_count_d);
-    if (j.by_rank) {
+    if (j.by_rank && j.quota) {
+        // the accepted candidates beyond their cell's room leave keys2 before the rest is ranked and placed
+        TimerScope t(c, F_NMS, (double)j.n * 16 + (double)j.bound * 8 * (j.qa.q + 1));
+        if (int rc = enqueue_quota_live(c, j.qa, true, j.fl, j.n, j.pa.overwrite_all != 0, j.ncols, j.nrows)) return rc;
+        launch_quota_filter(c->stream, c->keys2, j.acc_count_d, (int)j.bound, j.qa, c->quota_buf, j.qa.cells, quota_nkept(j.qa));
+        launch_mis_place_quota(c->stream, j.pa, j.acc_count_d, quota_nkept(j.qa), j.rank_d, j.nfill_d, (int)j.bound, c->readback, rem_d, j.look,
+                               j.info_d);
+    } else if (j.by_rank) {
         TimerScope t(c, F_NMS, (double)j.n * 16);
         launch_mis_place(c->stream, j.pa, j.acc_count_d, j.rank_d, j.nfill_d, (int)j.bound, c->readback, rem_d, j.look, j.info_d);
     } else {
         { TimerScope t(c, F_SORT, (double)j.np2 * 16); launch_sort_desc(c->stream, c->keys2, (int)j.np2); }
         TimerScope t(c, F_NMS, (double)j.n * 16);
-        const int e = launch_nms(c->stream, j.pa);
+        if (j.quota)
+            if (int rc = enqueue_quota_live(c, j.qa, false, j.fl, j.n, j.pa.overwrite_all != 0, j.ncols, j.nrows)) return rc;
+        const int e = j.quota ? launch_nms_quota(c->stream, j.pa, j.qa) : launch_nms(c->stream, j.pa);
         if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
         launch_mis_results(c->stream, c->readback, rem_d, j.look, j.info_d, c->placed_d);
     }
@@ -290,6 +325,7 @@ struct SelPlan {
     int d, R;                     // mindist - 1; exclusion radius in candidate cells (-1: none)
     bool parallel_nms, prefilter;
     long long target;             // candidates the prefilter aims to keep
+    int cut_scale;                // 1, or the factor a grid widens the cuts by
     double min_eig;
     ScoreCache *pre;              // scores prepared ahead of time that this selection uses, or null
 };
@@ -302,6 +338,12 @@ SelPlan plan_selection(klt_ctx *c, const Slot *s, const SelGeom &g, int mode, in
     pl.parallel_nms = c->use_mis && g.ncand > 0 && mis_stage_bytes(pl.R) <= 120 * 1024;
     pl.target = 64LL * n;
     if (pl.target < 65536) pl.target = 65536;
+    // under a grid (klt_set_select_grid) the walk turns candidates away, so a cut sized for "best first" runs out sooner and the repeat with
+    // every candidate is likelier.  KLT_GRID_CUT_SCALE widens every cut of a selection under a grid by that factor; 1 (the default): the
+    // figures of tools/grid_probe.py did not call for more.  Too tight a cut costs the repeat, never the result.
+    static const int grid_cut_scale = getenv("KLT_GRID_CUT_SCALE") ? atoi(getenv("KLT_GRID_CUT_SCALE")) : 1;
+    pl.cut_scale = c->sel_grid.cell_width > 0 && grid_cut_scale > 1 ? (grid_cut_scale > 64 ? 64 : grid_cut_scale) : 1;
+    pl.target *= pl.cut_scale;
     pl.prefilter = c->use_topk && g.ncand > 262144 && pl.target < g.ncand / 2;
     pl.min_eig = select_min_eig(c->p);
     // scores prepared ahead of time (klt_select_prepare_async) are used by the replacement pass of the parallel path; everything else
@@ -366,7 +408,8 @@ int check_select_mask(klt_ctx *c, int nc, int nr)
 // ---- parallel minimum distance (default): decide every candidate in a few passes, rank the accepted ones, and
 // fill the free slots with the best of them (same result as the sorted serial walk below).  Leaves the first batch of passes
 // enqueued and the job with the context, for klt_select_finish.
-int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, const NmsArgs &na, int mode, Consume &consume)
+int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, const NmsArgs &na, int mode, Consume &consume,
+                             const QuotaArgs *qa)
 {
     const int nx = sa.nx, ny = sa.ny, R = pl.R, n = na.nfeat;
     const long long ncand = (long long)nx * ny;
@@ -379,6 +422,12 @@ int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa
     // two accepted candidates are more than R cells apart in x or in y: at most one per (R+1)x(R+1) block of cells
     j.bound = R < 0 ? ncand : (long long)((nx + R) / (R + 1)) * ((ny + R) / (R + 1));
     j.by_rank = j.bound <= 98304;                       // rank by counting; beyond that sort the accepted keys
+    if (qa) {
+        // the filter takes one launch per feature a cell may hold: beyond KLT_QUOTA_MAX_ROUNDS the accepted keys are sorted and walked
+        j.quota = true; j.qa = *qa; j.ncols = sa.ncols; j.nrows = sa.nrows;
+        if (qa->q > KLT_QUOTA_MAX_ROUNDS) j.by_rank = false;
+        c->grid_path = j.by_rank ? 1 : 2;
+    }
     j.np2 = pow2_at_least_2048(j.bound);
     const MisCounters cnt(tiles, j.bound, j.by_rank);
     const int tile_cap = mis_tile_capacity(R);
@@ -396,7 +445,7 @@ int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa
         c->pinned.push_back(hp);
     }
     unsigned *const base = c->mis_cnt;
-    j.fl = na.fl; j.n = n; j.ncand = ncand; j.mode = mode; j.prefilter = pl.prefilter; j.target = pl.target; j.pre = pl.pre;
+    j.fl = na.fl; j.n = n; j.ncand = ncand; j.mode = mode; j.prefilter = pl.prefilter; j.target = pl.target; j.cut_scale = pl.cut_scale; j.pre = pl.pre;
     j.zero_from = base + cnt.zero_from(); j.zero_n = cnt.zero_n();
     j.hist_d = base + cnt.hist; j.ticket_d = base + cnt.ticket; j.info_d = base + cnt.info; j.rank_d = base + cnt.rank;
     j.acc_count_d = base + cnt.accepted;
@@ -421,22 +470,25 @@ int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa
 }
 
 // the greedy walk over sorted `keys`, the cell grid cleared first where it lives in global memory
-int run_nms(klt_ctx *c, NmsArgs &na, const unsigned long long *keys, int nkeys)
+int run_nms(klt_ctx *c, NmsArgs &na, const unsigned long long *keys, int nkeys, const QuotaArgs *qa, int ncols, int nrows)
 {
     na.keys = keys;
     na.nkeys = nkeys;
     if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
     TimerScope t(c, F_NMS, (double)na.nfeat * 16);
-    const int e = launch_nms(c->stream, na);
+    if (qa)
+        if (int rc = enqueue_quota_live(c, *qa, false, na.fl, na.nfeat, na.overwrite_all != 0, ncols, nrows)) return rc;
+    const int e = qa ? launch_nms_quota(c->stream, na, *qa) : launch_nms(c->stream, na);
     if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
     return 0;
 }
 
 // ---- sorted serial walk (KLT_OPT_SELECT_PARALLEL_NMS = 0, or an exclusion square too large for the LDS tile).  Leaves the
 // selection enqueued in full (or, behind the prefilter, complete) and the sorted keys it walked in sorted_keys / sorted_count.
-int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArgs &na)
+int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArgs &na, const QuotaArgs *qa)
 {
     const int n = na.nfeat;
+    if (qa) c->grid_path = 2;
     const long long ncand = (long long)sa.nx * sa.ny, npow2 = sa.npow2;
     // top-K prefilter: sort only the candidates the greedy walk can plausibly reach (one small D2H read-back)
     if (pl.prefilter) {
@@ -457,7 +509,7 @@ int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArg
         if (kept < np2) HIPCHK(c, hipMemsetAsync(c->keys2 + kept, 0, (size_t)(np2 - kept) * sizeof(unsigned long long), c->stream));
         { TimerScope t(c, F_SORT, (double)np2 * 16); launch_sort_desc(c->stream, c->keys2, (int)np2); }
         HIPCHK(c, hipMemcpyAsync(c->fl_snapshot, na.fl, (size_t)n * sizeof(klt_feat), hipMemcpyDefault, c->stream));
-        if (int rc = run_nms(c, na, c->keys2, (int)kept)) return rc;
+        if (int rc = run_nms(c, na, c->keys2, (int)kept, qa, sa.ncols, sa.nrows)) return rc;
         c->sorted_keys = c->keys2; c->sorted_count = (int)kept;
         int res[2] = {0, 0};
         HIPCHK(c, hipMemcpyAsync(res, c->placed_d, sizeof(res), hipMemcpyDeviceToHost, c->stream));
@@ -467,7 +519,7 @@ int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArg
         if (int rc = restore_list(c, na.fl, n)) return rc;
     }
     { TimerScope t(c, F_SORT, (double)npow2 * 16); launch_sort_desc(c->stream, c->keys, (int)npow2); }
-    if (int rc = run_nms(c, na, c->keys, (int)(ncand < npow2 ? ncand : npow2))) return rc;
+    if (int rc = run_nms(c, na, c->keys, (int)(ncand < npow2 ? ncand : npow2), qa, sa.ncols, sa.nrows)) return rc;
     c->sorted_keys = c->keys; c->sorted_count = (int)(ncand < npow2 ? ncand : npow2);
     HIPCHK(c, hipGetLastError());
     return KLT_OK;
@@ -612,8 +664,12 @@ int klt_select_begin_async(klt_ctx *c, int slot, int mode, int use_pyramid, int 
         if (as.n < n) return fail(c, KLT_ERR_STATE, "affine state smaller than the feature list");
         na.aff_rec = as.rec;
     }
-    if (plan.parallel_nms) return begin_parallel_selection(c, plan, sa, na, mode, consume);
-    return serial_selection(c, plan, sa, na);
+    QuotaArgs qa;
+    const bool quota = c->sel_grid.cell_width > 0;                       // klt_set_select_grid
+    if (quota)
+        if (int rc = make_quota_args(c, nc, nr, qa)) return rc;
+    if (plan.parallel_nms) return begin_parallel_selection(c, plan, sa, na, mode, consume, quota ? &qa : nullptr);
+    return serial_selection(c, plan, sa, na, quota ? &qa : nullptr);
 }
 
 int klt_select_finish(klt_ctx *c)
@@ -745,6 +801,19 @@ int klt_set_score_override(klt_ctx *c, const float *val, int count)
     c->score_override_n = count;
     return KLT_OK;
 }
+
+int klt_set_select_grid(klt_ctx *c, const klt_select_grid *g)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (c->sel_job) return fail(c, KLT_ERR_STATE, "a selection is pending: klt_select_finish first");
+    if (!g || g->cell_width == 0) { c->sel_grid = klt_select_grid{0, 0, 0}; return KLT_OK; }
+    if (g->cell_width < 1 || g->cell_height < 1) return fail(c, KLT_ERR_ARG, "selection grid: cell_width and cell_height must be at least 1");
+    if (g->max_per_cell < 1 || g->max_per_cell > 65535) return fail(c, KLT_ERR_ARG, "selection grid: max_per_cell must lie in 1 .. 65535");
+    c->sel_grid = *g;
+    return KLT_OK;
+}
+
+int klt_select_grid_path(klt_ctx *c) { return c ? c->grid_path : KLT_ERR_ARG; }
 
 // the context has no mask from here on (what a failed klt_set_select_mask* leaves as well)
 static void drop_select_mask(klt_ctx *c) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }

@@ -114,6 +114,10 @@ struct SelectJob {
     long long bound = 0, np2 = 0, ncand = 0, target = 0;
     int n = 0, mode = 0, rounds_per_look = 0, attempt = 0, round = 0, look = 0;
     bool by_rank = false, prefilter = false, filtered = false;
+    bool quota = false;                       // a grid is set (klt_set_select_grid): qa, and the frame the cells lie on
+    QuotaArgs qa{};
+    int ncols = 0, nrows = 0;
+    int cut_scale = 1;                        // the factor a grid widens the prefilter's cuts by (KLT_GRID_CUT_SCALE)
 };
 
 
@@ -177,6 +181,12 @@ struct klt_ctx {
     int mask_nc = 0, mask_nr = 0;
     uint8_t *mask_own = nullptr;
     size_t mask_own_cap = 0;
+    // per-cell quota of the selector (klt_set_select_grid): cell_width == 0 = no grid.  quota_buf, for a frame of `cells` cells:
+    // [3 * cells] 64-bit words of the filter's rounds | [cells] live counts | the number of keys the filter kept
+    klt_select_grid sel_grid{0, 0, 0};
+    int grid_path = 0;                        // klt_select_grid_path
+    unsigned long long *quota_buf = nullptr;
+    size_t quota_buf_cap = 0;
     uint32_t *grid = nullptr;
     size_t grid_cap = 0;
     int *nms_slots = nullptr;

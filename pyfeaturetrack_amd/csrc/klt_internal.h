@@ -130,6 +130,15 @@ struct NmsArgs {
     int nkeys, nfeat, overwrite_all, d /* mindist-1 */, cell, gw, gh, grid_in_lds;
 };
 
+// per-cell quota of the selector (klt_set_select_grid): the cell of pixel (x, y) is (y / ch) * gw + x / cw.  A second kernel argument of the
+// quota kernels only: NmsArgs and the kernels that take it alone stay as they are.
+struct QuotaArgs {
+    unsigned *live;          // [gw * gh] features each cell holds: the list's live records, plus (the walk) the features placed so far
+    int cw, ch, gw, q;       // cell size in pixels, cells per row, max_per_cell
+    int cells;               // gw * gh
+    unsigned cw_magic, ch_magic;      // klt_div_magic of cw / ch; 0 for a cell of 65536 pixels or more (every coordinate is in cell 0), unused for 1
+};
+
 // parallel minimum-distance passes (select_kernels.hip)
 struct MisArgs {
     const unsigned long long *keys;   // [ny*nx] candidate keys of the eigenvalue pass (0 = no candidate)
@@ -318,6 +327,18 @@ void launch_mis_results(hipStream_t s, unsigned *host_out, const unsigned *rem, 
 void launch_mis_place(hipStream_t s, const NmsArgs &a, const unsigned *count, unsigned *rank, const int *nfill, int bound,
                       unsigned *host_out, const unsigned *rem, int look, const unsigned *info);
 void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int n, float *val, int *x, int *y);
+// ---- per-cell quota (klt_set_select_grid)
+constexpr int KLT_QUOTA_MAX_ROUNDS = 64;      // largest max_per_cell the filter in front of the rank placement takes (one launch per round)
+// g.live[cell] += the list's live records in that cell (g.live zeroed by the caller)
+void launch_quota_live(hipStream_t s, const klt_feat *fl, int nfeat, int ncols, int nrows, const QuotaArgs &g);
+// keys[0 .. *count) unsorted accepted candidates: those beyond their cell's room become 0, *nkept = how many stay.  thr: 3 planes of `ncells`
+// words, zeroed by the caller, like *nkept; g.q <= KLT_QUOTA_MAX_ROUNDS
+void launch_quota_filter(hipStream_t s, unsigned long long *keys, const unsigned *count, int bound, const QuotaArgs &g,
+                         unsigned long long *thr, int ncells, unsigned *nkept);
+// launch_mis_place over filtered keys (zero keys are skipped, *nkept of them are not zero)
+void launch_mis_place_quota(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill,
+                            int bound, unsigned *host_out, const unsigned *rem, int look, const unsigned *info);
+int  launch_nms_quota(hipStream_t s, const NmsArgs &a, const QuotaArgs &g);   // the greedy walk under a quota; returns 0 or a hipError_t
 
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
 int launch_track(hipStream_t s, const TrackArgs &a);

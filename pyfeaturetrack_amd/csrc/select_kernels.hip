@@ -1275,6 +1275,213 @@ __global__ void unpack_candidates_kernel(const unsigned long long *__restrict__ 
     y[i] = klt_key_y(key);
 }
 
+// ------------------------------------------------------------------ per-cell quota (klt_set_select_grid)
+// The members of the accepted sequence A (what the walk accepts by distance, in rank order) that are kept are the first cap(cell) of
+// each cell, cap(cell) = max(q - live(cell), 0); everything else about A -- who excludes whom -- is as without a grid.
+__device__ __forceinline__ int quota_cell(const QuotaArgs &g, int x, int y)
+{
+    const int cx = g.cw == 1 ? x : (int)klt_div_by_magic((unsigned)x, g.cw_magic);
+    const int cy = g.ch == 1 ? y : (int)klt_div_by_magic((unsigned)y, g.ch_magic);
+    return cy * g.gw + cx;
+}
+
+// room left in a cell; the count is read from L2 (the walk adds to it between two reads)
+__device__ __forceinline__ int quota_left(const QuotaArgs &g, int cell)
+{
+    const unsigned held = __hip_atomic_load(&g.live[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return held < (unsigned)g.q ? (int)((unsigned)g.q - held) : 0;
+}
+
+// live(cell): list records with val >= 0 whose position lies inside the frame (f32 comparisons: a NaN fails), counted in the cell of
+// ((int)x, (int)y).  A sum: the order the additions arrive in does not matter.
+__global__ __launch_bounds__(256) void quota_live_kernel(const klt_feat *__restrict__ fl, int nfeat, int ncols, int nrows, QuotaArgs g)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nfeat) return;
+    const klt_feat ft = fl[i];
+    if (ft.val < 0) return;
+    if (!(ft.x >= 0.f && ft.x < (float)ncols && ft.y >= 0.f && ft.y < (float)nrows)) return;
+    atomicAdd(&g.live[quota_cell(g, (int)ft.x, (int)ft.y)], 1u);
+}
+
+// The filter in front of the rank placement, one launch per round r = 0 .. q: round r < q leaves in cur[cell] the largest key of the cell
+// that is below prev[cell], the largest of round r - 1 -- the cell's (r + 1)-th accepted candidate -- for every cell with r < cap(cell).
+// A key that finds itself in prev[] was one of the first cap(cell) of its cell and sets bit 63 (the sign of a positive eigenvalue, never
+// set in a key); round q only looks, clears the bit of the keys that have it and zeroes the others.  Maxima of distinct keys: what a round
+// leaves does not depend on the order its atomics arrive in.  thr = 3 planes of ncells words: prev, cur, and the plane round r + 1
+// collects in, which round r clears.
+constexpr unsigned long long QUOTA_KEPT = 1ull << 63;
+__global__ __launch_bounds__(256) void quota_round_kernel(unsigned long long *__restrict__ keys, const unsigned *__restrict__ count, QuotaArgs g,
+                                                          unsigned long long *__restrict__ thr, int ncells, int r, unsigned *__restrict__ nkept)
+{
+    const unsigned long long *prev = thr + (size_t)(r % 3) * ncells;
+    unsigned long long *cur = thr + (size_t)((r + 1) % 3) * ncells, *next = thr + (size_t)((r + 2) % 3) * ncells;
+    const bool last = r == g.q;
+    const int n = (int)*count, stride = gridDim.x * 256, first = blockIdx.x * 256 + threadIdx.x;
+    if (!last)
+        for (int c = first; c < ncells; c += stride) next[c] = 0ull;
+    for (int i0 = blockIdx.x * 256; i0 < n; i0 += stride) {              // (whole wavefronts stay together for the ballot below)
+        const int i = i0 + threadIdx.x;
+        unsigned long long k = i < n ? keys[i] : 0ull;
+        if (k != 0ull && !(k & QUOTA_KEPT)) {
+            const int cell = quota_cell(g, klt_key_x(k), klt_key_y(k)), cap = quota_left(g, cell);
+            if (r >= 1 && r - 1 < cap && k == prev[cell]) {
+                k |= QUOTA_KEPT;
+                if (!last) keys[i] = k;
+            } else if (!last && r < cap && (r == 0 || k < prev[cell])) {
+                atomicMax(&cur[cell], k);
+            }
+        }
+        if (last) {
+            const bool kept = (k & QUOTA_KEPT) != 0ull;
+            if (i < n) keys[i] = kept ? k & ~QUOTA_KEPT : 0ull;
+            const unsigned long long m = __ballot(kept);
+            if ((threadIdx.x & 63) == 0 && m) atomicAdd(nkept, (unsigned)__popcll(m));
+        }
+    }
+}
+
+// mis_place_kernel over filtered keys: the zero keys are skipped (mis_rank_kernel counted none of them as greater than anything), and
+// *nkept keys are left
+__global__ __launch_bounds__(256) void mis_place_quota_kernel(NmsArgs a, const unsigned *__restrict__ count, const unsigned *__restrict__ nkept,
+                                                              const unsigned *__restrict__ rank, const int *__restrict__ nfill_in,
+                                                              unsigned *host_out, const unsigned *rem, int look, const unsigned *info)
+{
+    const int n = (int)*count, nfill = *nfill_in;
+    const int placed = min((int)*nkept, nfill);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const unsigned long long k = a.keys[i];
+        const int r = (int)rank[i];
+        if (k != 0ull && r < nfill) fill_slot(a, a.overwrite_all ? r : a.slots[r], k);
+    }
+    if (a.overwrite_all)                                           // the kept candidates ran out
+        for (int s = placed + i; s < a.nfeat; s += gridDim.x * 256) mark_not_found(a.fl, s);
+    if (i == 0 && a.placed_out) {
+        a.placed_out[0] = placed;
+        a.placed_out[1] = placed < nfill ? 1 : 0;
+    }
+    if (blockIdx.x == 0) write_results(host_out, rem, look, info, placed, placed < nfill ? 1 : 0);
+}
+
+// nms_kernel under a quota.  A candidate accepted by distance marks the cell grid and blocks the later lanes near it whatever its cell
+// holds; it takes a slot, and room, only while its cell has room left.  The room of a batch of 64 survivors: what the cell had when the
+// batch began (g.live, which the batch's placed features are added to behind it) minus the lanes of the same cell placed before this one.
+// Without a minimum distance (d < 0) a candidate of a full cell has no effect at all and is dropped with the first test; the one-shot
+// "first `room` free lanes" of nms_kernel becomes the same lane-by-lane loop, which stops when the list is full.
+template <bool LDSGRID>
+__global__ __launch_bounds__(NMS_T) void nms_quota_kernel(NmsArgs a, QuotaArgs g)
+{
+    extern __shared__ uint32_t lds_grid[];
+    __shared__ unsigned long long surv[NMS_T];
+    __shared__ int wave_cnt[NMS_T / 64];
+    __shared__ int scan[NMS_T];
+    __shared__ int s_stop, s_nfill;
+    uint32_t *grid = LDSGRID ? lds_grid : a.grid_global;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (LDSGRID)
+        for (int i = tid; i < a.gw * a.gh; i += NMS_T) grid[i] = 0u;
+    if (tid == 0) s_stop = 0;
+
+    // the fillable slots in list order, as in nms_kernel
+    int nfill = a.nfeat;
+    if (!a.overwrite_all) {
+        const int per = (a.nfeat + NMS_T - 1) / NMS_T, lo = min(tid * per, a.nfeat), hi = min(lo + per, a.nfeat);
+        int cnt = 0;
+        for (int i = lo; i < hi; i++) cnt += a.fl[i].val < 0;
+        scan[tid] = cnt;
+        __syncthreads();
+        for (int off = 1; off < NMS_T; off <<= 1) {
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        int k = scan[tid] - cnt;
+        for (int i = lo; i < hi; i++)
+            if (a.fl[i].val < 0) a.slots[k++] = i;
+        if (tid == NMS_T - 1) s_nfill = scan[tid];
+        __syncthreads();
+        nfill = s_nfill;
+    }
+    __syncthreads();
+
+    int placed = 0;                               // meaningful in wave 0 only
+    bool list_full = nfill == 0;
+    unsigned long long key = tid < a.nkeys ? a.keys[tid] : 0ull;
+    for (int pos = 0; pos < a.nkeys && nfill > 0; pos += NMS_T) {
+        const unsigned long long cur = key;
+        const int nxt = pos + NMS_T + tid;
+        key = nxt < a.nkeys ? a.keys[nxt] : 0ull;
+        const bool valid = cur != 0ull;
+        const int x = klt_key_x(cur), y = klt_key_y(cur);
+        bool ok = valid;
+        if (valid) ok = a.d >= 0 ? grid_free<LDSGRID>(grid, a, x, y) : quota_left(g, quota_cell(g, x, y)) > 0;
+        const unsigned long long m = __ballot(ok);
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        const int ended = __syncthreads_or(!valid);
+        int offset = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < NMS_T / 64; w++) {
+            const int c = wave_cnt[w];
+            offset += w < wave ? c : 0;
+            total += c;
+        }
+        if (ok) surv[offset + __popcll(m & ((1ull << lane) - 1ull))] = cur;
+        __syncthreads();
+        if (wave == 0) {
+            for (int base = 0; base < total && !list_full; base += 64) {
+                const unsigned long long k = base + lane < total ? surv[base + lane] : 0ull;
+                const int sx = klt_key_x(k), sy = klt_key_y(k);
+                bool is_free = k != 0ull;
+                if (base > 0 && is_free && a.d >= 0) is_free = grid_free<LDSGRID>(grid, a, sx, sy);
+                const int qc = is_free ? quota_cell(g, sx, sy) : -1;
+                const int left = is_free ? quota_left(g, qc) : 0;
+                unsigned long long mask = __ballot(is_free), accepted = 0ull, taken = 0ull;
+                int room = nfill - placed;
+                // rank order = lane order: the first free lane is accepted and blocks the later lanes near it
+                while (mask != 0ull && room > 0) {
+                    const int l = __ffsll((long long)mask) - 1;
+                    accepted |= 1ull << l;
+                    mask &= ~(1ull << l);
+                    const int cell_l = __builtin_amdgcn_readlane(qc, l), left_l = __builtin_amdgcn_readlane(left, l);
+                    const unsigned long long same = __ballot(qc == cell_l);
+                    if (__popcll(taken & same) < left_l) { taken |= 1ull << l; room--; }
+                    if (a.d >= 0) {
+                        const int ax = __builtin_amdgcn_readlane(sx, l), ay = __builtin_amdgcn_readlane(sy, l);
+                        mask &= ~__ballot(abs(sx - ax) <= a.d && abs(sy - ay) <= a.d);
+                    }
+                }
+                if (((accepted >> lane) & 1ull) && a.d >= 0) {
+                    const uint32_t code = (((uint32_t)sx << 16) | (uint32_t)sy) + 1u;
+                    uint32_t *cellp = &grid[cell_of(sy, a) * a.gw + cell_of(sx, a)];
+                    if (LDSGRID) *cellp = code;
+                    else __hip_atomic_store(cellp, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if ((taken >> lane) & 1ull) {
+                    const int rank = placed + __popcll(taken & ((1ull << lane) - 1ull));
+                    fill_slot(a, a.overwrite_all ? rank : a.slots[rank], k);
+                    __hip_atomic_fetch_add(&g.live[qc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                placed += __popcll(taken);
+                if (placed >= nfill) list_full = true;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // the next batch (and the next first test) reads g.live and the grid
+            }
+            if (lane == 0 && (list_full || ended)) s_stop = 1;
+        }
+        __syncthreads();
+        if (s_stop) break;
+    }
+    if (wave == 0) {
+        if (!list_full && a.overwrite_all)                         // candidates exhausted
+            for (int i = placed + lane; i < a.nfeat; i += 64) mark_not_found(a.fl, i);
+        if (lane == 0 && a.placed_out) {
+            a.placed_out[0] = placed;
+            a.placed_out[1] = list_full ? 0 : 1;
+        }
+    }
+}
+
 }  // namespace
 
 // a grid of `blocks` workgroups, at least one and at most `cap`
@@ -1449,4 +1656,40 @@ void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(unpack_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, s, keys, n, val, x, y);
+}
+
+void launch_quota_live(hipStream_t s, const klt_feat *fl, int nfeat, int ncols, int nrows, const QuotaArgs &g)
+{
+    if (nfeat <= 0) return;
+    hipLaunchKernelGGL(quota_live_kernel, dim3((nfeat + 255) / 256), dim3(256), 0, s, fl, nfeat, ncols, nrows, g);
+}
+
+void launch_quota_filter(hipStream_t s, unsigned long long *keys, const unsigned *count, int bound, const QuotaArgs &g,
+                         unsigned long long *thr, int ncells, unsigned *nkept)
+{
+    const size_t most = (size_t)(bound > ncells ? bound : ncells);
+    const dim3 grid(clamp_grid((most + 255) / 256, 384));
+    for (int r = 0; r <= g.q; r++) hipLaunchKernelGGL(quota_round_kernel, grid, dim3(256), 0, s, keys, count, g, thr, ncells, r, nkept);
+}
+
+void launch_mis_place_quota(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill,
+                            int bound, unsigned *host_out, const unsigned *rem, int look, const unsigned *info)
+{
+    const int chunks = (bound + RANK_T - 1) / RANK_T;
+    hipLaunchKernelGGL(mis_rank_kernel, dim3(chunks < RANK_GX ? chunks : RANK_GX, chunks < RANK_GY ? chunks : RANK_GY), dim3(RANK_T), 0, s,
+                       a.keys, count, rank);
+    hipLaunchKernelGGL(mis_place_quota_kernel, dim3((bound + 255) / 256), dim3(256), 0, s, a, count, nkept, rank, nfill, host_out, rem, look, info);
+}
+
+int launch_nms_quota(hipStream_t s, const NmsArgs &a, const QuotaArgs &g)
+{
+    if (a.grid_in_lds) {
+        const size_t lds = (size_t)a.gw * a.gh * sizeof(uint32_t);
+        hipError_t e = hipFuncSetAttribute((const void *)nms_quota_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(nms_quota_kernel<true>, dim3(1), dim3(NMS_T), lds, s, a, g);
+    } else {
+        hipLaunchKernelGGL(nms_quota_kernel<false>, dim3(1), dim3(NMS_T), 0, s, a, g);
+    }
+    return 0;
 }

@@ -84,6 +84,9 @@ class KLT_TrackingContext:
         # selection mask (not in the reference): None, or a [nrows][ncols] array of bool / integers (or a Pillow "L" / "1" image) in
         # which zero marks the pixels KLTSelectGoodFeatures / KLTReplaceLostFeatures / KLTTrackSequence never place a feature on
         self.selectionMask = None
+        # selection grid (not in the reference): None, or (cell_width, cell_height, max_per_cell) -- no cell of cell_width x cell_height
+        # pixels ends up with more than max_per_cell features after KLTSelectGoodFeatures / KLTReplaceLostFeatures / KLTTrackSequence
+        self.selectionGrid = None
         # motion prior (not in the reference): None, or "constant_velocity" -- KLTTrackSequence then starts each feature's search in
         # frame k + 1 at its position in frame k plus its last displacement (KLTTrackFeatures takes predictions through `guess=`)
         self.motionPrediction = None

@@ -143,6 +143,29 @@ def selection_mask_from_tc(tc, ncols=None, nrows=None):
     return (mask != 0).view(np.uint8)
 
 
+def select_grid_from_tc(tc):
+    """tc.selectionGrid -> None, or the (cell_width, cell_height, max_per_cell) tuple of ints klt_set_select_grid takes.  Read with a
+    default, like tc.selectionMask.  TypeError for a value that is not a sequence of three integers (a bool is not one), ValueError for a
+    cell side below 1 or max_per_cell outside 1 .. 65535 -- both before any device work."""
+    grid = getattr(tc, "selectionGrid", None)
+    if grid is None:
+        return None
+    import numbers
+    try:
+        values = tuple(grid)
+    except TypeError:
+        values = None
+    if isinstance(grid, (str, bytes)) or values is None or len(values) != 3 or not all(
+            isinstance(v, numbers.Integral) and not isinstance(v, (bool, np.bool_)) for v in values):
+        raise TypeError("tc.selectionGrid must be None or (cell_width, cell_height, max_per_cell), three integers (got {0!r})".format(grid))
+    cw, ch, q = (int(v) for v in values)
+    if cw < 1 or ch < 1 or cw > 2 ** 31 - 1 or ch > 2 ** 31 - 1:
+        raise ValueError("tc.selectionGrid: cell_width and cell_height must be at least 1 (got {0} x {1})".format(cw, ch))
+    if not 1 <= q <= 65535:
+        raise ValueError("tc.selectionGrid: max_per_cell must lie in 1 .. 65535 (got {0})".format(q))
+    return cw, ch, q
+
+
 def affine_params_from_tc(tc):
     """klt.py:67-73 -> klt_affine_params (mode -1 = consistency check off)."""
     a = KltAffineParams()

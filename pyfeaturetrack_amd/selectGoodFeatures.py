@@ -173,15 +173,18 @@ def _KLTSelectGoodFeatures(tc, img, nFeatures, mode, featurelist=None):
     from .params import selection_mask_from_tc
     ncols, nrows = _image_size(img)
     mask = selection_mask_from_tc(tc, ncols, nrows)     # (TypeError / ValueError before any device work)
+    from .params import select_grid_from_tc
+    grid = select_grid_from_tc(tc)                      # (likewise)
     ctx = context_of(tc)
     with ctx.lock:                                      # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
-        return _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask)
+        return _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask, grid)
 
 
-def _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask=None):
+def _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask=None, grid=None):
     from ._frames import FrameKey, cache_of, settle_frames
     ctx.sync_select_mask(mask)                        # tc.selectionMask: sent when its bytes differ from what the context holds
+    ctx.sync_select_grid(grid)                        # tc.selectionGrid: sent when it differs from what the context holds
     if cache_of(tc).handles and not ctx.configured_for(tc):
         cache_of(tc).keep_all_handles()               # new parameters void every pyramid of the context: kept handles fetch theirs first
     ctx.configure(tc)

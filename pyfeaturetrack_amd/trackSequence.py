@@ -143,6 +143,7 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     KLTReplaceLostFeatures).  tc.affineConsistencyCheck >= 0 runs the affine check on every step,
     tc.forwardBackwardCheck the forward-backward check (rejected features are lost ones: the replacement pass fills their slots).
     tc.selectionMask (zero = no feature here) holds for the first selection and every replacement; it is read once, when the call starts.
+    tc.selectionGrid = (cell_width, cell_height, max_per_cell) likewise: no cell holds more than max_per_cell features after any of them.
     tc.motionPrediction = "constant_velocity": from the second step on every feature's search starts at its position plus its last
     displacement (klt_predict_cv_async on the two last rows of the table, then klt_track_guess_async: the previous list and the guesses
     never leave the device); a feature the last step lost or replaced starts at its own position.  Not together with the affine check.
@@ -152,6 +153,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
     from .params import selection_mask_from_tc
     selection_mask_from_tc(tc)           # (TypeError for a tc.selectionMask of an unknown kind, likewise)
+    from .params import select_grid_from_tc
+    grid = select_grid_from_tc(tc)       # (TypeError / ValueError for a tc.selectionGrid that is no (cell_width, cell_height, max_per_cell), likewise)
     from .params import motion_prediction_from_tc
     motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
     from .params import light_params_from_tc
@@ -159,10 +162,10 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
-        return _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch)
+        return _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid)
 
 
-def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch):
+def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid=None):
     frames = iter(frames)
     _fix_window(tc)
     from ._frames import cache_of
@@ -178,6 +181,7 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     from .params import selection_mask_from_tc
     # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
     ctx.sync_select_mask(selection_mask_from_tc(tc, ncols, nrows))
+    ctx.sync_select_grid(grid)          # tc.selectionGrid, read when the call started: the first selection and every replacement
     affine = tc.affineConsistencyCheck >= 0
     from .params import fb_params_from_tc
     fb_check = bool(fb_params_from_tc(tc).enabled) and not affine       # forward-backward check in every tracker step
