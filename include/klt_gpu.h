@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -404,6 +404,35 @@ int klt_set_light_params(klt_ctx *ctx, const klt_light_params *p);          /* a
 /* which kernel the last launch with mode 1 took -- 0: no such launch yet, 1: one feature per wavefront, 2: four 7x7 features per wavefront
  * (7x7 windows, features x pairs >= 2048, KLT_OPT_TRACK_VARIANT != 0).  A diagnostic: both give the same records. */
 int klt_track_light_path(klt_ctx *ctx);
+
+/* ---- per-feature track quality (not in the reference) --------------------------------------------------------- */
+/* One launch that reads two feature lists and level 0 of two slots and writes one 16-byte quality record per feature; it decides
+ * nothing and changes nothing else.  With in / out record i of the two lists, w = window_width, n = w * w, hw = w / 2:
+ *   measured   in.val >= 0 and out.val == KLT_TRACKED (a slot refilled by a replacement pass, val > 0, is not measured), both positions
+ *              0 <= x < ncols and 0 <= y < nrows (NaN and infinities fail; tested before any conversion to int), both windows inside
+ *              the frame by the sampler's own test (ix-hw >= 0, iy-hw >= 0, ix+hw+2 <= ncols, iy+hw+2 <= nrows, ix = (int)x).  Every other
+ *              record is (0, 0, 0, val = 0); a measured one has val = 1.
+ *   samples    T of frame 1's level-0 image at (in.x, in.y); S, Sgx, Sgy of frame 2's image and gradients at (out.x, out.y), the
+ *              tracker's bilinear samples, k row-major over the window.
+ *   residue    SUM |T_k - S_k| (f32 terms, numpy's pairwise f32 sum) / (float)n: the number klt_params.max_residue tests
+ *              (trackFeatures.py:124).
+ *   ncc        the normalised cross-correlation of T and S from FP64 sums of exact products (term k joins partial k mod 64 in
+ *              increasing k, the partials fold by p[l] += p[l + m], l < m, m = 32 .. 1): a = n*SUM TT - (SUM T)^2, b = n*SUM SS - (SUM S)^2,
+ *              c = n*SUM TS - SUM T * SUM S, every operation one FP64 rounding; a > 0 && b > 0: (float)clamp(c / sqrt(a*b), -1, 1), else 0.
+ *              A gain and an offset between the frames leave it alone, where they make the residue meaningless.
+ *   min_eig    the smaller eigenvalue of the window's gradient matrix at the new position, from the same kind of sums gxx, gxy, gyy of
+ *              Sgx, Sgy: d = gxx - gyy, (float)max(((gxx + gyy) - sqrt(d*d + 4*(gxy*gxy))) / 2, 0).
+ * Quality records live in feature buffers (size and alignment of klt_feat): views, downloads, table rows and gathers work unchanged.
+ * Any odd window 3 .. 31.  The launches do not look at the forward-backward, lighting or affine parameters. */
+typedef struct { float residue, ncc, min_eig; int32_t val; } klt_quality;
+/* Both pyramids built (KLT_ERR_STATE) and of equal size (KLT_ERR_ARG), fb_in and fb_out hold n records (KLT_ERR_STATE); fb_quality is
+ * allocated if needed and distinct from fb_in and fb_out, by index and by address (KLT_ERR_ARG).  n == 0: KLT_OK, nothing enqueued. */
+int klt_track_quality_async(klt_ctx *ctx, int slot1, int slot2, int fb_in, int fb_out, int fb_quality, int n);
+/* npairs pairs of equal frame size in one launch; every fb_quality distinct from every pair's fb_in and fb_out, and from each other */
+int klt_track_quality_batch_async(klt_ctx *ctx, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out,
+                                  const int *fb_quality, int npairs, int n);
+/* synchronous, host arrays: q[i] from in[i] and out[i] */
+int klt_track_quality(klt_ctx *ctx, int slot1, int slot2, const klt_feat *in, const klt_feat *out, klt_quality *q, int n);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

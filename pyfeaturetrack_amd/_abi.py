@@ -16,6 +16,10 @@ class KltFeat(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("val", C.c_int32), ("aux", C.c_int32)]
 
 
+class KltQuality(C.Structure):
+    _fields_ = [("residue", C.c_float), ("ncc", C.c_float), ("min_eig", C.c_float), ("val", C.c_int32)]
+
+
 class KltParams(C.Structure):
     _fields_ = [
         ("mindist", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
@@ -138,6 +142,9 @@ SYMBOLS = {
     "klt_predict_cv_async": (_I, [_P, _I, _I, _I, _I]),
     "klt_set_light_params": (_I, [_P, C.POINTER(KltLightParams)]),
     "klt_track_light_path": (_I, [_P]),
+    "klt_track_quality_async": (_I, [_P, _I, _I, _I, _I, _I, _I]),
+    "klt_track_quality_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
+    "klt_track_quality": (_I, [_P, _I, _I, _P, _P, _P, _I]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

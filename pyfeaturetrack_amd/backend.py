@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltTrackStats, load_library)
+                   KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
@@ -20,6 +20,9 @@ assert FEAT_DTYPE.itemsize == C.sizeof(KltFeat)
 AFFINE_DTYPE = np.dtype([("aff_x", np.float32), ("aff_y", np.float32), ("Axx", np.float32), ("Ayx", np.float32),
                          ("Axy", np.float32), ("Ayy", np.float32), ("valid", np.int32), ("pad", np.int32)])
 assert AFFINE_DTYPE.itemsize == C.sizeof(KltAffineRec)
+# a quality record (klt_quality; klt_track_quality*): it lives in a feature buffer, and Python reads that buffer's records through this view
+QUALITY_DTYPE = np.dtype([("residue", np.float32), ("ncc", np.float32), ("min_eig", np.float32), ("val", np.int32)])
+assert QUALITY_DTYPE.itemsize == C.sizeof(KltQuality) == FEAT_DTYPE.itemsize
 
 SELECTING_ALL = 1
 REPLACING_SOME = 2
@@ -31,6 +34,7 @@ MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
 _FB_API_IN, _FB_API_OUT = 65526, 65527
 _FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
 _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
+_FB_API_QUALITY = 59999              # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
 
 
 def _dp(a):
@@ -710,6 +714,30 @@ class Context:
         cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(4)]
         self._check(self._lib.klt_track_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], len(pairs), n))
 
+    # ------------------------------------------------ per-feature track quality (klt_track_quality*)
+    def track_quality(self, slot1, slot2, fl_in, fl_out):
+        """klt_track_quality: a QUALITY_DTYPE array (residue, ncc, min_eig, val), record i measured between fl_in[i] on slot1's level 0 and
+        fl_out[i] on slot2's; val 1 = measured, else the record is all zero."""
+        fl_in = np.ascontiguousarray(fl_in, FEAT_DTYPE)
+        fl_out = np.ascontiguousarray(fl_out, FEAT_DTYPE)
+        if len(fl_in) != len(fl_out):
+            raise ValueError("the two lists have %d and %d records" % (len(fl_in), len(fl_out)))
+        q = np.zeros(len(fl_in), QUALITY_DTYPE)
+        self._check(self._lib.klt_track_quality(self._h, slot1, slot2, fl_in.ctypes.data, fl_out.ctypes.data, q.ctypes.data, len(fl_in)))
+        return q
+
+    def track_quality_async(self, slot1, slot2, fb_in, fb_out, fb_quality, n):
+        self._check(self._lib.klt_track_quality_async(self._h, slot1, slot2, fb_in, fb_out, fb_quality, n))
+
+    def track_quality_batch_async(self, pairs, n):
+        """pairs: [(slot1, slot2, fb_in, fb_out, fb_quality), ...] -- one quality launch for all of them."""
+        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(5)]
+        self._check(self._lib.klt_track_quality_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], cols[4], len(pairs), n))
+
+    def quality_download(self, fb, n):
+        """n quality records of feature buffer `fb` (what a track_quality*_async launch wrote there)"""
+        return self.featbuf_download(fb, n).view(QUALITY_DTYPE)
+
     def track_stats_reset(self):
         self._check(self._lib.klt_track_stats_reset(self._h))
 
@@ -858,5 +886,5 @@ def context_of(tc, device=None):
     return ctx
 
 
-__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
+__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
            "KLT_MAX_LEVELS", "KltParams"]

@@ -425,6 +425,138 @@ int klt_track_fb(klt_ctx *c, int slot1, int slot2, klt_feat *inout, klt_feat *ba
     return KLT_OK;
 }
 
+// ------------------------------------------------------------------------- per-feature track quality
+// what a quality launch asks of one pair's feature buffers before anything is allocated: the quality records in a buffer of their own
+static int check_quality_buffers(klt_ctx *c, int fb_in, int fb_out, int fb_quality)
+{
+    if (fb_quality < 0 || fb_quality > 65535) return fail(c, KLT_ERR_ARG, "fb_quality must be a feature buffer");
+    if (fb_quality == fb_in || fb_quality == fb_out) return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from fb_in and fb_out");
+    return 0;
+}
+
+// level 0 of a pair, its two lists (n records each, KLT_ERR_STATE otherwise) and its quality records (allocated by the caller)
+static int fill_quality_pair(klt_ctx *c, const Slot *s1, const Slot *s2, int fb_in, int fb_out, int fb_quality, int n, QualityPair &p)
+{
+    for (int fb : {fb_in, fb_out})
+        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
+            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    p.i1 = s1->lv[0].img;
+    p.i2 = s2->lv[0].img; p.gx2 = s2->lv[0].gx; p.gy2 = s2->lv[0].gy;
+    p.in = c->fbs[fb_in].d; p.out = c->fbs[fb_out].d;
+    p.q = reinterpret_cast<klt_quality *>(c->fbs[fb_quality].d);
+    return 0;
+}
+
+static int enqueue_quality(klt_ctx *c, const QualityArgs &a, int npairs)
+{
+    const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
+    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 + 48), c->stream);      // booked with the tracker's launches
+    if (launch_track_quality(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
+    return 0;
+}
+
+int klt_track_quality_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int fb_quality, int n)
+{
+    if (int rc = check_ready(c)) return rc;
+    if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
+    if (int rc = check_quality_buffers(c, fb_in, fb_out, fb_quality)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    Slot *s1, *s2;
+    if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
+    if (n == 0) return KLT_OK;
+    for (int fb : {fb_in, fb_out})                           // (before the quality buffer is made: a refused call allocates nothing)
+        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
+            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    if ((size_t)fb_quality < c->fbs.size() && c->fbs[fb_quality].d &&
+        (c->fbs[fb_quality].d == c->fbs[fb_in].d || c->fbs[fb_quality].d == c->fbs[fb_out].d))      // a view can be a second name of the same records
+        return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from fb_in and fb_out");
+    FeatBuf *bq;                                             // (may grow c->fbs: before any pointer into it is taken)
+    if (int rc = get_fb(c, fb_quality, n, &bq)) return rc;
+    QualityArgs a;
+    std::memset(&a, 0, sizeof(a));
+    if (int rc = fill_quality_pair(c, s1, s2, fb_in, fb_out, fb_quality, n, a.one)) return rc;
+    a.n = n; a.window = c->p.window_width; a.ncols = s1->nc; a.nrows = s1->nr;
+    if (int rc = enqueue_quality(c, a, 1)) return rc;
+    {
+        Slot *both[2] = {s1, s2};
+        if (int rc = mark_read(c, both, 2)) return rc;
+    }
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
+int klt_track_quality_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_quality,
+                                  int npairs, int n)
+{
+    if (int rc = check_ready(c)) return rc;
+    if (!slot1 || !slot2 || !fb_in || !fb_out || !fb_quality || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
+    // (quality records that another pair of the launch reads as a list, or writes too: distinct from every pair's buffers)
+    for (int i = 0; i < npairs; i++)
+        for (int j = 0; j < npairs; j++) {
+            if (int rc = check_quality_buffers(c, fb_in[j], fb_out[j], fb_quality[i])) return rc;
+            if (i != j && fb_quality[i] == fb_quality[j]) return fail(c, KLT_ERR_ARG, "two pairs of the batch share fb_quality");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<Slot *> used;
+    Slot *first = nullptr;
+    for (int i = 0; i < npairs; i++) {
+        Slot *s1, *s2;
+        if (int rc = check_pair(c, slot1[i], slot2[i], &s1, &s2)) return rc;
+        if (!first) first = s1;
+        used.push_back(s1);
+        used.push_back(s2);
+        if (s1->nc != first->nc || s1->nr != first->nr) return fail(c, KLT_ERR_ARG, "all pairs of a batch must have the same frame size");
+        for (int fb : {fb_in[i], fb_out[i]})
+            if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
+                return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    }
+    if (n == 0) return KLT_OK;
+    // ... and by address: a view can be a second name of the same records (a buffer that does not exist yet is nobody's second name)
+    for (int i = 0; i < npairs; i++) {
+        const klt_feat *q = (size_t)fb_quality[i] < c->fbs.size() ? c->fbs[fb_quality[i]].d : nullptr;
+        for (int j = 0; q && j < npairs; j++)
+            if (q == c->fbs[fb_in[j]].d || q == c->fbs[fb_out[j]].d || (i != j && (size_t)fb_quality[j] < c->fbs.size() && q == c->fbs[fb_quality[j]].d))
+                return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from every pair's fb_in, fb_out and fb_quality");
+    }
+    for (int i = 0; i < npairs; i++) {
+        FeatBuf *bq;                                         // may grow c->fbs: do it before taking pointers into it
+        if (int rc = get_fb(c, fb_quality[i], n, &bq)) return rc;
+    }
+    std::vector<QualityPair> table((size_t)npairs);
+    for (int i = 0; i < npairs; i++) {
+        std::memset(&table[i], 0, sizeof(QualityPair));
+        if (int rc = fill_quality_pair(c, used[2 * i], used[2 * i + 1], fb_in[i], fb_out[i], fb_quality[i], n, table[i])) return rc;
+    }
+    // the table goes up only when it differs from the one the device holds (pageable source: the runtime stages it before returning;
+    // stream order protects the launch that read the replaced table)
+    if (c->quality_host.size() != table.size() || std::memcmp(c->quality_host.data(), table.data(), table.size() * sizeof(QualityPair)) != 0) {
+        c->quality_host.clear();                             // (nothing is known of the device's copy until the new one is enqueued)
+        if (int rc = ensure(c, c->quality_dev, c->quality_cap, (size_t)npairs)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->quality_dev, table.data(), (size_t)npairs * sizeof(QualityPair), hipMemcpyHostToDevice, c->stream));
+        c->quality_host = table;
+    }
+    QualityArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.pairs = c->quality_dev;
+    a.npairs = npairs;
+    a.n = n; a.window = c->p.window_width; a.ncols = first->nc; a.nrows = first->nr;
+    if (int rc = enqueue_quality(c, a, npairs)) return rc;
+    if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
+int klt_track_quality(klt_ctx *c, int slot1, int slot2, const klt_feat *in, const klt_feat *out, klt_quality *q, int n)
+{
+    if (!c || !in || !out || !q) return fail(c, KLT_ERR_ARG, "null argument");
+    const int fi = 65534, fo = 65535, fq = 65530;
+    if (int rc = klt_featbuf_upload_async(c, fi, in, n)) return rc;         // (the download below synchronises: both lists are ours until then)
+    if (int rc = klt_featbuf_upload_async(c, fo, out, n)) return rc;
+    if (int rc = klt_track_quality_async(c, slot1, slot2, fi, fo, fq, n)) return rc;
+    if (n == 0) return klt_sync(c);
+    return klt_featbuf_download(c, fq, reinterpret_cast<klt_feat *>(q), n);
+}
+
 // ------------------------------------------------------------------------- affine consistency check
 int klt_set_affine_params(klt_ctx *c, const klt_affine_params *p)
 {

@@ -256,6 +256,11 @@ struct klt_ctx {
     klt_fb_params fbp{0, 1.0f};                                    // forward-backward check (klt_set_fb_params)
     klt_light_params lightp{0};                                    // gain / bias tracking (klt_set_light_params); 0 = off
     int light_path = 0;                                            // klt_track_light_path: kernel of the last lighting launch (0: none yet)
+    // batched quality launches (klt_track_quality_batch_async): the descriptor table last sent stays on the device and is sent again only
+    // when it differs
+    std::vector<QualityPair> quality_host;
+    QualityPair *quality_dev = nullptr;
+    size_t quality_cap = 0;
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;

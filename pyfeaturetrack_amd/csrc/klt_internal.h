@@ -94,6 +94,24 @@ struct TrackGuessArgs : TrackArgs {
     const klt_feat *guess;       // single-pair launch: one record per feature (x, y = predicted frame-2 position; val < 0: no guess)
 };
 
+// one frame pair of a quality launch (klt_track_quality_async): level 0 of the two frames as the tracker reads it
+// (records, KLT_PIX_STRIDE), the two lists and the quality records.  The table of a batched launch (device memory, indexed by
+// blockIdx.y) holds these: a table of its own, TrackPairDesc stays as it is.
+static_assert(sizeof(klt_quality) == sizeof(klt_feat) && alignof(klt_quality) == alignof(klt_feat), "quality records live in feature buffers");
+struct QualityPair {
+    const float *i1;                    // frame 1: image plane of level 0
+    const float *i2, *gx2, *gy2;        // frame 2: image and gradient planes of level 0
+    const klt_feat *in, *out;
+    klt_quality *q;
+};
+
+struct QualityArgs {
+    QualityPair one;                    // single-pair launch
+    const QualityPair *pairs;           // batched launch: npairs descriptors (`one` unused)
+    int npairs;
+    int n, window, ncols, nrows;
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -345,6 +363,8 @@ int launch_track(hipStream_t s, const TrackArgs &a);
 int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
 // the gain / bias tracker (track_light_kernels.hip; klt_set_light_params mode 1): *path = 1 wave kernel, 2 quad kernel; a.order is not looked at
 int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
+// per-feature track quality (quality_kernels.hip): one klt_quality record per feature; returns -1 for an unsupported window
+int launch_track_quality(hipStream_t s, const QualityArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

@@ -94,6 +94,9 @@ class KLT_TrackingContext:
         # carries as commented text): None, or "gain_bias" -- KLTTrackFeatures then fits a gain and an offset between the two windows in
         # every Newton iteration and in the residue.  (tc.lighting_insensitive, the reference's switch, raises as it does there.)
         self.lightingCompensation = None
+        # per-feature track quality (not in the reference): True -- KLTTrackFeatures leaves tc.quality_last, KLTTrackSequence's table
+        # carries ft.quality: (residue, ncc, min_eig, val) records, val 1 = measured (backend.QUALITY_DTYPE)
+        self.trackQuality = False
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -704,6 +707,7 @@ class KLT_FeatureTable:
     x = property(lambda self: self.rec["x"])
     y = property(lambda self: self.rec["y"])
     val = property(lambda self: self.rec["val"])
+    quality = None            # KLTTrackSequence with tc.trackQuality: [nFrames, nFeatures] records (residue, ncc, min_eig, val)
 
     def feature(self, feat, frame):
         return _feature_of(self.rec[frame, feat])

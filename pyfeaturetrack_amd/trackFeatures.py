@@ -390,7 +390,11 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     there instead of at its frame-1 position (a row with a NaN: no guess for that feature).  Works with tc.forwardBackwardCheck (the way
     back takes no prior) and in sequential mode; with tc.affineConsistencyCheck >= 0 it raises ValueError.
     tc.lightingCompensation = "gain_bias" (not in the reference as code): the gain / bias tracker of DESIGN.md section 9d, in sequential and
-    in ping-pong mode; ValueError together with forwardBackwardCheck, motionPrediction, affineConsistencyCheck >= 0 or `guess`."""
+    in ping-pong mode; ValueError together with forwardBackwardCheck, motionPrediction, affineConsistencyCheck >= 0 or `guess`.
+    tc.trackQuality = True (not in the reference): tc.quality_last is then a backend.QUALITY_DTYPE array of len(featurelist) -- residue,
+    ncc, min_eig and val (1 = measured) of every feature between the position the list held on entry and the one it holds on return,
+    taken after the forward-backward or affine check if one ran: one more launch, one more download of 16 bytes
+    per feature."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -424,6 +428,12 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         # by the feature list object.
         state = _affine_state_of(tc, ctx, featurelist)
     ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check, guess=guess)
+    # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
+    # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
+    quality = bool(getattr(tc, "trackQuality", False))
+    if quality:
+        from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY
+        ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # The device is tracking; now every byte of the frames that were taken as resident is compared with what their slots were
     # filled from.  One that differs (the same array edited in place off the lattice, ...) is sent and built now and the tracker
     # runs again on the same input records: the records that come back are those of the last launch.
@@ -434,6 +444,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
             again = True
     if again:
         ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check, guess=guess)
+        if quality:
+            ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
     # list-independent half of that replacement -- summed-area tables and eigenvalue keys of frame 2's level 0, 50 us at 1080p -- is
     # enqueued now, behind the tracker, and runs while the host moves the columns and finds its way into the replacement call
@@ -448,6 +460,9 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
             except KltBackendError:                         # (an optimisation only: the replacement scores the frame itself then)
                 pass
     fl_out = ctx.track_complete(nfeat, marked=marked)
+    if quality:                                       # one more download of 16 bytes per feature
+        from .backend import QUALITY_DTYPE
+        tc.quality_last = ctx.quality_download(_FB_API_QUALITY, nfeat) if nfeat else np.zeros(0, QUALITY_DTYPE)
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

@@ -17,6 +17,7 @@ from .selectGoodFeatures import _fix_window, _slots_of
 _FB_TABLE = 60000            # feature-buffer ids used by this module: the table, then one view per frame
 _FB_ROW0 = 60001
 _FB_GUESS = 65525            # ... and the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
+_FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality records, laid out like the feature table (below _FB_TABLE)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -147,6 +148,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     tc.motionPrediction = "constant_velocity": from the second step on every feature's search starts at its position plus its last
     displacement (klt_predict_cv_async on the two last rows of the table, then klt_track_guess_async: the previous list and the guesses
     never leave the device); a feature the last step lost or replaced starts at its own position.  Not together with the affine check.
+    tc.trackQuality = True: the table carries `ft.quality`, a [frames][features] array of backend.QUALITY_DTYPE records -- row k measured between
+    rows k - 1 and k as the tracker left them (before the replacement pass: a refilled slot is not measured), row 0 all val = 0.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
@@ -203,6 +206,19 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                 ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
             tables.append(base)
         return tables[ci] + 1 + off
+
+    quality = bool(getattr(tc, "trackQuality", False))   # one quality launch behind every tracker launch, into a table of its own
+    qtables = []
+
+    def qrow_fb(k):
+        ci, off = divmod(k, chunk)
+        if ci == len(qtables):
+            base = _FBQ_TABLE + ci * (chunk + 1)
+            ctx.featbuf_alloc(base, chunk * nFeatures)
+            for j in range(chunk):
+                ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
+            qtables.append(base)
+        return qtables[ci] + 1 + off
 
     workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
     # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
@@ -279,6 +295,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                     ctx.track_fb_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
                 else:
                     ctx.track_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
+                if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
+                    ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
         # The tracker of frame k + 1 only READS the list that frame k's replacement completes, so it is enqueued before the host looks at
         # that replacement's outcome (klt_select_finish): the GPU has it queued while the host turns around.  In the rare case that the
@@ -373,6 +391,15 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
         hi = min(nframes, lo + chunk)
         ctx.featbuf_download_into(base, ft.rec[lo:hi])          # rows lo .. hi-1 are contiguous in the table: no staging copy
     ft.rec["aux"] = 0
+    if quality:
+        from .backend import FEAT_DTYPE, QUALITY_DTYPE
+        rec = np.zeros((nframes, nFeatures), FEAT_DTYPE)
+        for ci, base in enumerate(qtables):
+            lo = ci * chunk
+            hi = min(nframes, lo + chunk)
+            ctx.featbuf_download_into(base, rec[lo:hi])
+        ft.quality = rec.view(QUALITY_DTYPE)
+        ft.quality[0] = 0                                        # nothing was tracked into the first frame
     if tc.sequentialMode:
         # leave the context as the per-frame API would: the last frame's pyramids are "frame 1" of the next call
         from .trackFeatures import _pyramid_handles
