@@ -117,8 +117,10 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
 /* test hook: >= 0: the library's (value + 1)-th device / pinned-host allocation from now is refused as if memory had run out (KLT_ERR_NOMEM; the
  * context stays usable, the call can be repeated); -1 (default): off.  Lets the tests walk every allocation site of a call sequence. */
 #define KLT_OPT_FAIL_ALLOC_AFTER 19
-/* 1 (default): the level-0 kernel with the fused first reduction walks each 64-column strip down in bands and computes every row of every
- * stage once (frames of >= 128 columns); 0: the tiled kernel, which computes each tile's vertical halo again.  Same results bit for bit. */
+/* 1: the level-0 kernel with the fused first reduction walks each 64-column strip down in bands and computes every row of every
+ * stage once (frames of >= 128 columns); 0: the tiled kernel, which computes each tile's vertical halo again; 2 (default): as 1, on 128-column
+ * strips in 16-row bands where the launch has >= 256 columns and fills the chip with them (fewer halo columns smoothed per output column),
+ * else as 1.  Same results bit for bit. */
 #define KLT_OPT_L0_STREAM 21
 int klt_set_option(klt_ctx *ctx, int option, int value);
 
@@ -201,6 +203,8 @@ int klt_build_pyramids(klt_ctx *ctx, int slot);
 #define KLT_L0_RB32_HRED 4          /* 32-row tiles with the first reduction's horizontal pass (KLT_OPT_FUSED_HREDUCE) */
 #define KLT_L0_STREAM 5             /* smooth_grad_stream (KLT_OPT_L0_STREAM), f32 frames */
 #define KLT_L0_STREAM_NO_CENTRE 6   /* smooth_grad_stream with the derivative taps' centre product elided (u8 frames) */
+#define KLT_L0_STREAM_WIDE 7        /* smooth_grad_stream on 128-column strips in 16-row bands (KLT_OPT_L0_STREAM 2), f32 frames */
+#define KLT_L0_STREAM_WIDE_NO_CENTRE 8  /* ... with the centre product elided (u8 frames) */
 int klt_level0_path(klt_ctx *ctx, int *merged_grad);
 /* bit 0: the slot holds a frame; bit 1: its pyramids are built and match the current parameters / taps (what
  * `tc.pyramid_last is not None` means in the reference, trackFeatures.py:152); 0 for a slot never used */

@@ -268,7 +268,7 @@ int klt_create(int device, klt_ctx **out)
     }
     c->work = c->stream;
     if (const char *v = getenv("KLT_FUSED_HREDUCE")) c->fuse_hreduce = atoi(v) != 0;      // experiment hook (initial value of the option)
-    if (const char *v = getenv("KLT_L0_STREAM")) c->l0_stream = atoi(v) != 0;
+    if (const char *v = getenv("KLT_L0_STREAM")) c->l0_stream = atoi(v) == 2 ? 2 : atoi(v) != 0;
     if (const char *v = getenv("KLT_TRACK_XCD_ORDER")) c->track_xcd_order = atoi(v) != 0;
     if (const char *v = getenv("KLT_COPY_STREAMS")) { const int k = atoi(v); c->ncopy = k < 1 ? 1 : (k > klt_ctx::kMaxCopyStreams ? klt_ctx::kMaxCopyStreams : k); }
     *out = c;
@@ -354,7 +354,7 @@ int klt_set_option(klt_ctx *c, int option, int value)
     if (option == KLT_OPT_SAT_VARIANT) { c->sat_variant = value; return KLT_OK; }
     if (option == KLT_OPT_TRACK_VARIANT) { g_track_variant = value; return KLT_OK; }
     if (option == KLT_OPT_FUSED_HREDUCE) { c->fuse_hreduce = value != 0; return KLT_OK; }
-    if (option == KLT_OPT_L0_STREAM) { c->l0_stream = value != 0; return KLT_OK; }
+    if (option == KLT_OPT_L0_STREAM) { c->l0_stream = value == 2 ? 2 : value != 0; return KLT_OK; }
     if (option == KLT_OPT_TRACK_XCD_ORDER) { c->track_xcd_order = value != 0; return KLT_OK; }
     if (option == KLT_OPT_BUILD_STREAM) {
         if (!value && c->bstream) HIPCHK(c, hipStreamSynchronize(c->bstream));      // pending builds finish; their events stay valid

@@ -162,7 +162,7 @@ struct klt_ctx {
     float *cimg = nullptr;                    // compact image planes of a pyramid build's levels (what the reductions read and write)
     size_t cimg_cap = 0;
     bool fuse_hreduce = true;                 // KLT_OPT_FUSED_HREDUCE
-    bool l0_stream = true;                    // KLT_OPT_L0_STREAM
+    int l0_stream = 2;                        // KLT_OPT_L0_STREAM: 0 tiled, 1 streaming, 2 (default) streaming with wide strips where they apply
     int l0_path = -1;                         // klt_level0_path: KLT_L0_* of the last geometry group of the last build (-1: no build yet)
     bool l0_merged_grad = false;              // ... and whether that group's gradients of levels >= 1 went out as one launch
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER

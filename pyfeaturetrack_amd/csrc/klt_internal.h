@@ -245,9 +245,9 @@ extern int g_track_variant;         // tracker kernels: 4 (default) quad-load ke
 size_t smooth_grad_lds_bytes(int smooth_radius /* -1: no smoothing stage */, int R);
 size_t pyr_reduce_lds_bytes(int ss, int ntaps);
 // kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image gradients only, 3 = u8 image gradients only
-// stream: the streaming level-0 kernel where it applies (KLT_OPT_L0_STREAM)
+// stream: the streaming level-0 kernel where it applies (KLT_OPT_L0_STREAM: 1 = 64-column strips, 2 = 128-column strips where they apply)
 // *path (optional): which kernel went out, a KLT_L0_* code of include/klt_gpu.h
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, bool stream = false, int *path = nullptr);
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, int stream = 0, int *path = nullptr);
 bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss);
 int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch);
 int launch_pyr_reduce(hipStream_t s, const PyrReduceArgs &a, int batch);

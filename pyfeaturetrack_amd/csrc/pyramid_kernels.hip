@@ -680,7 +680,7 @@ __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradA
 
 // ------------------------------------------------------------------------------------------------------
 // Streaming level-0 kernel: the stages of smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>, but a workgroup walks a segment of
-// `seg_h` rows of a 64-column strip in bands of SB output rows and computes every row of every stage once.  The tiled kernel computes
+// `seg_h` rows of a TW-column strip in bands of SB output rows and computes every row of every stage once.  The tiled kernel computes
 // its vertical halo again in every tile (42 / 38 / 38 rows of stages 1 / 2 / 3 for 32 output rows); here the last NS - 1 horizontally
 // smoothed rows and the last 6 rows of the two gradient intermediates are carried to the next band, and the halo is paid once per
 // segment.  Same expressions and operation order as the tiled kernel (both call the stage primitives above), same virtual coordinates
@@ -691,16 +691,19 @@ __global__ __launch_bounds__(NTHR, KLT_L0_WAVES) void smooth_grad_rb(SmoothGradA
 //   B  H-smoothed               B row j  = frame row cbase - rs + j        SB + 2 rs rows    rows [0, 2 rs) carried (Bc)
 //   C  smoothed image           C row i  = frame row cbase + i             SB rows x BW      (region 1, over A)
 //   DE gradient intermediates   DE row k = frame row cbase - 6 + k         SB + 6 rows       rows [0, 6) carried
-// A DE row holds the D row (derivative taps along x) in floats [0, 64) and the E row (Gaussian taps) in [64, 128).  B lives in the DE
+// A DE row holds the D row (derivative taps along x) in floats [0, TW) and the E row (Gaussian taps) in [TW, 2 TW).  B lives in the DE
 // rows past the carried six (dead once stage 2 has run; its last 2 rs rows are saved to Bc first).  The prologue band of a segment
 // (PRO) fills the carries: C rows [SB - 6, SB) = frame rows [s0 - 3, s0 + 3), no gradient output.
 // The H1 plane is stored from the C rows of [s0, s0 + seg_h); the pixel records of [y, y + SB) from each steady band's stage 4, the image
 // taken from C -- its first three rows from Cc, the interior columns of the last three C rows of the band before (two slots, by band
 // parity: a band reads one and fills the other).
-constexpr int SB = 32;
-
-template <int NS>
+// Two geometries are built: TW x SB = 64 x 32 (KLT_OPT_L0_STREAM 1) and 128 x 16 (value 2).  Stages 0-2 run on the strip plus HB = 12 halo
+// columns a side, (TW + 24) / TW of the output: 1.375 for 64 columns, 1.19 for 128.  A band is 2048 output pixels either way, and
+// every carry scales with the strip width only; the wide strip's band is half as high so that the LDS still allows four workgroups per CU.
+// (In the streaming templates TW is the template parameter; it hides the tiled kernels' file-level TW = 64.)
+template <int NS, int TW, int SB>
 struct StreamLds {
+    static_assert(TW % 8 == 0 && SB % 4 == 0 && SB >= 6 + 2 * (NS / 2), "quads, 2 x 4 work items, prologue rows inside one band");
     static constexpr int HB = 12, rs = NS / 2;
     static constexpr int AW = TW + 2 * HB + 8, BW = TW + 2 * HB, DEW = 2 * TW;
     static constexpr int R1 = SB * AW;                           // A, then C
@@ -725,15 +728,20 @@ __device__ __forceinline__ void load_taps_here(TapRegs<NT> &r, const size_t arg_
 }
 
 // u8 frames: the raw rows of a steady band (A rows [0, SB), 4 bytes per quad) are requested one band ahead and stay in flight in three
-// registers (`pre`) while the band before runs its stages 1-4.  Edge bands read element by element through the reflect map (and wait for it).
-template <typename TIn, int NS, bool ZC, bool EDGE, bool PRO>
+// registers (`pre`; 64 x 32: 768 quads, three per thread) while the band before runs its stages 1-4.  Edge bands read element by element through the reflect map (and wait for it).
+// (128 x 16: 640 quads for 256 threads: the third register holds a quad of its own in half of the threads; the others repeat the last quad
+// and do not store it.)
+template <int TW, int SB>
+constexpr int l0_stream_pre_regs() { return (SB * (TW + 32) / 4 + 255) / 256; }
+
+template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE, bool PRO>
 __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
-                                               const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[SB * (TW + 32) / 4 / 256])
+                                               const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[l0_stream_pre_regs<TW, SB>()])
 {
     constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead
     STREAM_CLK_START;
     constexpr int NTHR = 256, NG = 7, ND = 7;
-    using L = StreamLds<NS>;
+    using L = StreamLds<NS, TW, SB>;
     constexpr int HB = L::HB, rs = L::rs, AW = L::AW, BW = L::BW, DEW = L::DEW, DW = TW;
     constexpr int AQ = AW / 4, BQ = BW / 4, DQ = DW / 4;
     constexpr int CLO = PRO ? SB - 6 : 0;                        // C / DE rows made by this band: C [CLO, SB), DE [CLO + 6, SB + 6)
@@ -753,7 +761,8 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     constexpr int X0 = -(HB + 4);                                // frame column of A column 0, relative to the strip
 
     // ---- stage 0: raw rows -> registers; (after the previous band's stage 4) -> A, carried rows into place
-    // (the host takes this kernel for frames of >= 2 strips and >= 64 rows: one reflection brings every index inside)
+    // (the host takes this kernel for frames of >= 2 strips and >= 64 rows: one reflection brings every index inside -- columns reach
+    // TW + 15 past the last strip's first, rows SB + 1 + rs past the frame's last)
     {
         constexpr int NA = SB - ALO, N0 = NA * AQ, U0 = (N0 + NTHR - 1) / NTHR;
         typename RawQuad<TIn>::reg w[U0];
@@ -782,7 +791,6 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     __syncthreads();
     STREAM_MARK(0);
     if constexpr (PF) {
-        static_assert((SB * AQ) % NTHR == 0, "a steady band's quads are whole rounds of the workgroup");
         if (PRO || cbase - 3 + SB < ylim)                        // the A rows of the next steady band
             load_raw_block<uint8_t, SB, AQ, NTHR>(raw, nc, nr, (PRO ? s0 + 3 : cbase + SB) + rs, tx0 + X0, threadIdx.x, pre);
     }
@@ -856,7 +864,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     if (PRO) return;
     __syncthreads();
     STREAM_MARK(3);
-    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase + 29); the pixel records (image from C / Cc, gradx, grady) of two
+    // ---- stage 4: vertical pass, output rows [cbase - 3, cbase - 3 + SB); the pixel records (image from C / Cc, gradx, grady) of two
     // adjacent pixels go out together: 24 contiguous bytes
     TapRegs<NG> kg;
     TapRegs<ND> kd;
@@ -885,21 +893,21 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     STREAM_MARK(4);
 }
 
-template <typename TIn, int NS, bool ZC, bool EDGE>
+template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE>
 __device__ __forceinline__ void l0_stream_segment(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
                                                   const int s0, const int ylim)
 {
-    uint32_t pre[SB * (TW + 32) / 4 / 256];
-    l0_stream_band<TIn, NS, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, 1, pre);          // (fills Cc slot 0)
-    for (int y = s0, par = 0; y < ylim; y += SB, par ^= 1) l0_stream_band<TIn, NS, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, par, pre);
+    uint32_t pre[l0_stream_pre_regs<TW, SB>()];
+    l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, 1, pre);          // (fills Cc slot 0)
+    for (int y = s0, par = 0; y < ylim; y += SB, par ^= 1) l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, par, pre);
 }
 
-// grid = (ceil(ncols / 64), ceil(nrows / seg_h), batch); seg_h a multiple of SB.
+// grid = (ceil(ncols / TW), ceil(nrows / seg_h), batch); seg_h a multiple of SB.
 // `a` must stay the FIRST parameter: load_taps_here reads the taps at kernarg offset offsetof(SmoothGradArgs, ...).
-template <typename TIn, int NS, bool ZC>
+template <typename TIn, int NS, bool ZC, int TW = 64, int SB = 32>
 __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGradArgs a, int seg_h)
 {
-    __shared__ __attribute__((aligned(16))) float lds[StreamLds<NS>::total];
+    __shared__ __attribute__((aligned(16))) float lds[StreamLds<NS, TW, SB>::total];
     const int b = blockIdx.z;
     const int tx0 = blockIdx.x * TW, s0 = blockIdx.y * seg_h;
     const int nc = a.dim_c[b] ? a.dim_c[b] : a.ncols, nr = a.dim_r[b] ? a.dim_r[b] : a.nrows;
@@ -907,8 +915,8 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
     const int ylim = min(s0 + seg_h, nr);
     const bool inside = tx0 + TW <= nc && tx0 / 4 + TW / 4 <= a.h1_nc;
     STAGE_MARK(0);
-    if (inside) l0_stream_segment<TIn, NS, ZC, false>(a, lds, nc, nr, tx0, s0, ylim);
-    else l0_stream_segment<TIn, NS, ZC, true>(a, lds, nc, nr, tx0, s0, ylim);
+    if (inside) l0_stream_segment<TIn, NS, TW, SB, ZC, false>(a, lds, nc, nr, tx0, s0, ylim);
+    else l0_stream_segment<TIn, NS, TW, SB, ZC, true>(a, lds, nc, nr, tx0, s0, ylim);
     STAGE_MARK(5);
 }
 
@@ -1169,12 +1177,25 @@ int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch)
     return 0;
 }
 
-// Segment height of the streaming level-0 kernel: 160 rows, the fastest of the cfg-2 sweep (profiles/README.md).  KLT_L0_SEG (a multiple of 32)
-// overrides it: experiment hook.
-static int l0_stream_seg()
+// Geometries of the streaming level-0 kernel: 64-column strips in 32-row bands (KLT_OPT_L0_STREAM 1), 128-column strips in 16-row bands (2)
+constexpr int L0S_TW = 64, L0S_SB = 32, L0W_TW = 128, L0W_SB = 16;
+// ... and the workgroups a launch needs to take them: two rounds of the 1024 resident slots (256 CUs x 4) for the narrow strips; the wide
+// strips' grid of sixteen 1080p frames is 15 x 9 x 16 = 2160 at their segment height, so the same bound holds for them
+constexpr long long L0S_MIN_WGS = 2048, L0W_MIN_WGS = 2048;
+
+// KLT_L0_WIDE_WGS overrides the wide strips' bound: experiment hook (segment heights whose grid is below it)
+static long long l0_wide_min_wgs()
+{
+    static const long long force = getenv("KLT_L0_WIDE_WGS") ? atoll(getenv("KLT_L0_WIDE_WGS")) : 0;
+    return force > 0 ? force : L0W_MIN_WGS;
+}
+
+// Segment height of the streaming level-0 kernel, per geometry (`wide`: 128 x 16): the fastest of each one's cfg-2 sweep (profiles/README.md).
+// KLT_L0_SEG overrides it for the geometries whose band height divides it (32 narrow, 16 wide): experiment hook.
+static int l0_stream_seg(bool wide)
 {
     static const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0;
-    return force > 0 && force % SB == 0 ? force : 160;
+    return force > 0 && force % (wide ? L0W_SB : L0S_SB) == 0 ? force : wide ? 128 : 160;
 }
 
 // The derivative taps' centre is +0.0 and every sample the two derivative passes see is >= +0 (a u8 frame, smoothing and Gaussian
@@ -1194,7 +1215,7 @@ static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
 // The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
 // *path: the KLT_L0_* code of the kernel launched (klt_level0_path)
 template <typename TIn, bool SMOOTH, int NS>
-static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream, int *path)
+static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path)
 {
     const dim3 blk(256);
     const bool tall = rb_tall_tiles(a, batch);
@@ -1208,9 +1229,23 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
         // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
         // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
         // frame, 1080p batches below 10) keep the tiled kernel, whose 32-row tiles fill the chip
-        const int sh = l0_stream_seg();
-        const dim3 gs((a.ncols + TW - 1) / TW, (a.nrows + sh - 1) / sh, batch);
-        if (stream && a.ncols >= 2 * TW && (long long)gs.x * gs.y * gs.z >= 2048) {
+        // wide strips (KLT_OPT_L0_STREAM 2): frames of two wide strips or more and a grid of the same two rounds at their own segment
+        // height; launches that miss either fall through to the narrow strips' rule, and from there to the tile
+        const int shw = l0_stream_seg(true);
+        const dim3 gw((a.ncols + L0W_TW - 1) / L0W_TW, (a.nrows + shw - 1) / shw, batch);
+        if (stream == 2 && a.ncols >= 2 * L0W_TW && (long long)gw.x * gw.y * gw.z >= l0_wide_min_wgs()) {
+            if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
+                klt_launch((smooth_grad_stream<TIn, NS, true, L0W_TW, L0W_SB>), gw, blk, 0, s, a, shw);
+                *path = KLT_L0_STREAM_WIDE_NO_CENTRE;
+                return 0;
+            }
+            klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB>), gw, blk, 0, s, a, shw);
+            *path = KLT_L0_STREAM_WIDE;
+            return 0;
+        }
+        const int sh = l0_stream_seg(false);
+        const dim3 gs((a.ncols + L0S_TW - 1) / L0S_TW, (a.nrows + sh - 1) / sh, batch);
+        if (stream && a.ncols >= 2 * L0S_TW && (long long)gs.x * gs.y * gs.z >= L0S_MIN_WGS) {
             // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
             if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
                 klt_launch((smooth_grad_stream<TIn, NS, true>), gs, blk, 0, s, a, sh);
@@ -1231,7 +1266,7 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
     return 0;
 }
 
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, bool stream, int *path)
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path)
 {
     int path_unused;
     if (!path) path = &path_unused;

@@ -1,6 +1,6 @@
 // Stage timing of the level-0 kernel: includes the product source with KLT_STAGE_CLOCKS and prints, for 64 workgroups of one
 // tile row, the wall-clock ticks (100 MHz) spent between the stage marks.  `T`: the tiled kernel with the fused reduction, `s`: the
-// streaming kernel (per-stage ticks summed over the bands of one segment), both on 16 1080p u8 frames into planes of pixel records
+// streaming kernel, `w`: the streaming kernel on 128-column strips (per-stage ticks summed over the bands of one segment), all on 16 1080p u8 frames into planes of pixel records
 // as at cfg-2 (`p`, the tiled kernel without the fused reduction, also writes the compact image copy the build then asks for).  Build (from the repo root):
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DKLT_STAGE_CLOCKS -Iinclude -Ipyfeaturetrack_amd/csrc tools/mb/l0_stages.hip -o tools/mb/l0_stages
 #include "../../pyfeaturetrack_amd/csrc/pyramid_kernels.hip"
@@ -31,7 +31,8 @@ int main(int argc, char **argv)
     a.ncols = nc; a.nrows = nr; a.R = 3;
     std::vector<uint8_t> h((size_t)nc * nr);
     for (size_t i = 0; i < h.size(); i++) h[i] = (uint8_t)((i * 2654435761u) >> 24);
-    const bool tiled16 = argc > 1 && argv[1][0] == 'T', stream = argc > 1 && argv[1][0] == 's';
+    const bool wide = argc > 1 && argv[1][0] == 'w';
+    const bool tiled16 = argc > 1 && argv[1][0] == 'T', stream = wide || (argc > 1 && argv[1][0] == 's');
     const int B = tiled16 || stream ? 16 : 2;
     const bool plain = argc > 1 && argv[1][0] == 'p';      // the kernel without the fused horizontal reduction
     float *cimg[KLT_MAX_BATCH], *dst[KLT_MAX_BATCH];
@@ -48,7 +49,7 @@ int main(int argc, char **argv)
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     a.reduce = pr.taps; a.h1_nc = nc / 4;
     for (int b = 0; b < B; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
-    auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, B, 0, !plain, stream); };
+    auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, B, 0, !plain, wide ? 2 : stream); };
     for (int rep = 0; rep < 3; rep++) go();
     hipDeviceSynchronize();
     hipEventRecord(e0);
@@ -58,18 +59,22 @@ int main(int argc, char **argv)
     printf("kernel: %.2f us per launch\n", ms * 1000 / 20);
     long long clk[64 * 8];
     if (stream) {
-        // g_stream_clk accumulated over every launch of this run (3 + 20): per launch, per band of 32 rows (4 bands + the prologue)
+        // g_stream_clk accumulated over every launch of this run (3 + 20): per launch, per band of 2048 output pixels (32 rows of a 64-column
+        // strip, 16 of a 128-column one; the segment height is the kernel's own, or KLT_L0_SEG as the library reads it)
         hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_stream_clk), sizeof(clk));
-        printf("ticks of 10 ns per 32-row band (segment 1 of frame 0, prologue share included)\nblock | load  hsm  vsm  hgrad vgrad | total\n");
+        const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0, sb = wide ? 16 : 32;
+        const int seg = force > 0 && force % sb == 0 ? force : wide ? 128 : 160, nb = wide ? 15 : 30;
+        const double per = 23.0 * (seg / sb);
+        printf("ticks of 10 ns per band of 2048 output pixels (segment 1 of frame 0, %d rows, prologue share included)\nblock | load  hsm  vsm  hgrad vgrad | total\n", seg);
         double sum[5] = {};
-        for (int b = 0; b < 30; b++) {
+        for (int b = 0; b < nb; b++) {
             const long long *c = clk + b * 8;
             double t = 0;
-            for (int k = 0; k < 5; k++) { sum[k] += c[k] / 23.0 / 4; t += c[k] / 23.0 / 4; }
-            printf("%4d | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", b, c[0] / 92.0, c[1] / 92.0, c[2] / 92.0, c[3] / 92.0, c[4] / 92.0, t);
+            for (int k = 0; k < 5; k++) { sum[k] += c[k] / per; t += c[k] / per; }
+            printf("%4d | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", b, c[0] / per, c[1] / per, c[2] / per, c[3] / per, c[4] / per, t);
         }
-        printf("mean | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", sum[0] / 30, sum[1] / 30, sum[2] / 30, sum[3] / 30, sum[4] / 30,
-               (sum[0] + sum[1] + sum[2] + sum[3] + sum[4]) / 30);
+        printf("mean | %5.0f %5.0f %5.0f %5.0f %5.0f | %6.0f\n", sum[0] / nb, sum[1] / nb, sum[2] / nb, sum[3] / nb, sum[4] / nb,
+               (sum[0] + sum[1] + sum[2] + sum[3] + sum[4]) / nb);
         return 0;
     }
     hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_stage_clk), sizeof(clk));
