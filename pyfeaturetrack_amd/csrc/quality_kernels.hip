@@ -28,87 +28,16 @@
 // bits as s / (float)n (rounding a 53-bit quotient of two f32 once more to 24 bits cannot change it, 53 >= 2 * 24 + 2) without an f32
 // division expansion; residue_mean keeps the compiler from narrowing it back.
 //
-// This file shares no code with track_kernels.hip or track_light_kernels.hip (their instantiations are register-tuned, and moving their
-// helpers into a header means editing them): Bilinear, make_bilinear, sample, pairwise_block and pairwise_sum are carried here as
-// copies, operation for operation, as section 9d did.
+// Bilinear, make_bilinear, sample, pairwise_block and pairwise_sum are the tracker's, from track_primitives.h: the single copy, moved
+// there verbatim with the device assembly of this file compared before and after.
 #include <cstdlib>
 
 #include "klt_internal.h"
+#include "track_primitives.h"
 
 #pragma clang fp contract(off)
 
 namespace quality_kernels {
-
-struct Bilinear {
-    double w00, w01, w10;
-    float w11;
-    int ix, iy;
-};
-
-// trackFeaturesUtils.pyx:23-31, :44-47
-__device__ __forceinline__ Bilinear make_bilinear(float x, float y)
-{
-    Bilinear b;
-    b.ix = (int)x;
-    b.iy = (int)y;
-    const float ax = (float)((double)x - (double)b.ix);
-    const float ay = (float)((double)y - (double)b.iy);
-    b.w00 = (1. - (double)ax) * (1. - (double)ay);
-    b.w01 = (double)ax * (1. - (double)ay);
-    b.w10 = (1. - (double)ax) * (double)ay;
-    b.w11 = ax * ay;
-    return b;
-}
-
-// one plane of a level's pixel records (element stride KLT_PIX_STRIDE)
-__device__ __forceinline__ float sample(const float *__restrict__ qg, int nc, const Bilinear &b)
-{
-    constexpr int ST = KLT_PIX_STRIDE;
-    const __attribute__((address_space(1))) float *q = (const __attribute__((address_space(1))) float *)qg;
-    const float t4 = b.w11 * q[ST * (nc + 1)];
-    double v = b.w00 * (double)q[0];
-    v = v + b.w01 * (double)q[ST];
-    v = v + b.w10 * (double)q[ST * nc];
-    v = v + (double)t4;
-    return (float)v;
-}
-
-__host__ __device__ constexpr int quality_npad(int n) { return (n + 3) & ~3; }
-
-// numpy's pairwise summation of n floats in LDS (trackFeatures.py:124) by the wavefront, valid in lane 0
-__device__ __forceinline__ float pairwise_block(const float *a, int n, int s)
-{
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; i++) res = res + a[i];
-        return res;
-    }
-    const int nn = n - (n % 8);
-    float r = 0.f;
-    if (s < 8) {
-        r = a[s];
-        for (int i = 8; i < nn; i += 8) r = r + a[i + s];
-    }
-    r = r + __shfl_down(r, 1);
-    r = r + __shfl_down(r, 2);
-    float res = r + __shfl_down(r, 4);
-    for (int i = nn; i < n; i++) res = res + a[i];
-    return res;
-}
-
-template <int DEPTH>
-__device__ __forceinline__ float pairwise_sum(const float *a, int n, int s)
-{
-    if (n <= 128) return pairwise_block(a, n, s);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return pairwise_sum<DEPTH - 1>(a, n2, s) + pairwise_sum<DEPTH - 1>(a + n2, n - n2, s);
-}
-template <>
-__device__ __forceinline__ float pairwise_sum<0>(const float *a, int n, int s)
-{
-    return pairwise_block(a, n < 128 ? n : 128, s);
-}
 
 // s / (float)n as an IEEE f32 quotient, through FP64 (see the head of the file).  The empty asm makes the quotient's operand opaque: the
 // compiler would otherwise narrow fptrunc(fdiv(fpext s, fpext n)) back to the f32 division and its f32 FMA expansion.
@@ -134,8 +63,6 @@ __device__ __forceinline__ bool window_fits(const Bilinear &b, int hw, int nc, i
 {
     return b.ix - hw >= 0 && b.iy - hw >= 0 && b.ix + hw + 2 <= nc && b.iy + hw + 2 <= nr;
 }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One feature per wavefront.  MAXK: window samples per lane; WCT > 0: window size known at compile time, WCT == 0: any odd window up to 31
 template <int MAXK, int WCT, bool BATCH>
@@ -182,10 +109,10 @@ __global__ __launch_bounds__(64) void quality_eigen_kernel(QualityArgs a)
         const int k = lane + 64 * kk;
         if (k < n) {
             const int off = (k / w) * nc + (k % w);
-            const float t = sample(pr.i1 + KLT_PIX_STRIDE * (base1 + off), nc, b1);
-            const float s = sample(pr.i2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
-            const float sx = sample(pr.gx2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
-            const float sy = sample(pr.gy2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
+            const float t = sample<KLT_PIX_STRIDE>(pr.i1 + KLT_PIX_STRIDE * (base1 + off), nc, b1);
+            const float s = sample<KLT_PIX_STRIDE>(pr.i2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
+            const float sx = sample<KLT_PIX_STRIDE>(pr.gx2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
+            const float sy = sample<KLT_PIX_STRIDE>(pr.gy2 + KLT_PIX_STRIDE * (base2 + off), nc, b2);
             lds[k] = fabsf(t - s);
             const double td = (double)t, sd = (double)s, sxd = (double)sx, syd = (double)sy;
             st = st + td;
@@ -233,16 +160,11 @@ static int launch_quality_t(hipStream_t s, const QualityArgs &a)
 {
     const int n = a.window * a.window;
     if (a.window < 3 || !(a.window & 1) || n > 1024) return -1;
-    const unsigned lds = (unsigned)(quality_npad(n) * sizeof(float));
+    const unsigned lds = (unsigned)(track_npad(n) * sizeof(float));
     const dim3 grid(a.n, BATCH ? a.npairs : 1), block(64);
-    // the tracker's MAXK classes (launch_track_light_t)
-    if (a.window == 7) klt_launch((quality_eigen_kernel<1, 7, BATCH>), grid, block, lds, s, a);
-    else if (a.window == 15) klt_launch((quality_eigen_kernel<4, 15, BATCH>), grid, block, lds, s, a);
-    else if (n <= 64) klt_launch((quality_eigen_kernel<1, 0, BATCH>), grid, block, lds, s, a);
-    else if (n <= 128) klt_launch((quality_eigen_kernel<2, 0, BATCH>), grid, block, lds, s, a);
-    else if (n <= 256) klt_launch((quality_eigen_kernel<4, 0, BATCH>), grid, block, lds, s, a);
-    else if (n <= 512) klt_launch((quality_eigen_kernel<8, 0, BATCH>), grid, block, lds, s, a);
-    else klt_launch((quality_eigen_kernel<16, 0, BATCH>), grid, block, lds, s, a);
+    for_window_class(a.window, [&](auto maxk, auto wct) {
+        klt_launch((quality_eigen_kernel<maxk.value, wct.value, BATCH>), grid, block, lds, s, a);
+    });
     return 0;
 }
 

@@ -12,7 +12,7 @@
 //   gradients  alpha_g = (float)sqrt((double)((sum1/nf) / (sum2/nf))) -- the ratio of the MEANS, which is what KLT 1.3.4 computes under the
 //              names sum1_squared / sum2_squared (:223-227);  sx_k = Tgx_k + Sgx_k*alpha_g, sy_k likewise
 //   step       the five product sums, _solveEquation, the step factor, both bounds tests, the iteration cap, the status priority,
-//              retainTrackers and the record's border rule: the plain tracker's (track_level / track_record of track_kernels.hip)
+//              retainTrackers and the record's border rule: the plain tracker's (track_level of track_kernels.hip, track_record)
 //   residue    at the final position from |diff_k| with alpha and beta recomputed there, added with numpy's pairwise sum
 //   degenerate sum1, sq1, sum2, sq2 are tested on their bits to be positive and finite (0 < bits <= 0x7f7fffff) before anything is computed
 //              from them, then alpha and alpha_g to be finite; if not, the level ends with KLT_SMALL_DET and the position stays where it is
@@ -25,130 +25,17 @@
 // built from fused multiply-adds: tests/test_host_and_abi.py allows the tracker's code objects the FMAs of IEEE f32 divisions and no
 // others.  light_sqrt takes the hardware's approximate root and settles the last bits by exact FP64 comparisons.
 //
-// This file shares no code with track_kernels.hip: that file's instantiations are register-tuned (tools/kernel_regs.py), and moving its
-// helpers into a header means editing it -- every such move tried before changed register figures (see the note there).  So Bilinear,
-// sample, chain_sum, pairwise_sum, solve_step, load_records and sample_quad are carried here as copies, operation for operation.
+// Bilinear, sample, chain_sum, pairwise_sum, solve_step, load_level, track_record, load_records and sample_quad are the plain tracker's,
+// from track_primitives.h: the single copy, moved there verbatim with the device assembly of this file compared before and after.
 // The namespace's name keeps "track_kernel" in the kernels' symbols, which is how the FMA test tells tracker code objects from others.
 #include <cstdlib>
 
 #include "klt_internal.h"
+#include "track_primitives.h"
 
 #pragma clang fp contract(off)
 
 namespace track_kernel_light {
-
-struct Bilinear {
-    double w00, w01, w10;
-    float w11;
-    int ix, iy;
-};
-
-// trackFeaturesUtils.pyx:23-31, :44-47
-__device__ __forceinline__ Bilinear make_bilinear(float x, float y)
-{
-    Bilinear b;
-    b.ix = (int)x;
-    b.iy = (int)y;
-    const float ax = (float)((double)x - (double)b.ix);
-    const float ay = (float)((double)y - (double)b.iy);
-    b.w00 = (1. - (double)ax) * (1. - (double)ay);
-    b.w01 = (double)ax * (1. - (double)ay);
-    b.w10 = (1. - (double)ax) * (double)ay;
-    b.w11 = ax * ay;
-    return b;
-}
-
-// one plane of a level's pixel records (element stride KLT_PIX_STRIDE)
-__device__ __forceinline__ float sample(const float *__restrict__ qg, int nc, const Bilinear &b)
-{
-    constexpr int ST = KLT_PIX_STRIDE;
-    const __attribute__((address_space(1))) float *q = (const __attribute__((address_space(1))) float *)qg;
-    const float t4 = b.w11 * q[ST * (nc + 1)];
-    double v = b.w00 * (double)q[0];
-    v = v + b.w01 * (double)q[ST];
-    v = v + b.w10 * (double)q[ST * nc];
-    v = v + (double)t4;
-    return (float)v;
-}
-
-// _solveEquation, trackFeaturesUtils.pyx:318-340
-__device__ __forceinline__ bool solve_step(float gxx, float gxy, float gyy, float ex, float ey, float small, float &dx, float &dy)
-{
-    const float p1 = gxx * gyy, p2 = gxy * gxy;
-    const float det = p1 - p2;
-    const float n1 = gyy * ex, n2 = gxy * ey, n3 = gxx * ey, n4 = gxy * ex;
-    dx = (n1 - n2) / det;
-    dy = (n3 - n4) / det;
-    return det < small;
-}
-
-__host__ __device__ constexpr int track_npad(int n) { return (n + 3) & ~3; }
-__host__ __device__ constexpr size_t track_lds_bytes(int n) { return 5 * (size_t)track_npad(n) * sizeof(float); }
-
-// N terms (N known at compile time) added in row-major order, sequential f32 adds, read from LDS 16 bytes at a time
-template <int N, int UNROLL>
-__device__ __forceinline__ float chain_sum(const float4 *T4)
-{
-    float acc = 0.f;
-#pragma unroll UNROLL
-    for (int q = 0; q < (N + 3) / 4; q++) {
-        const float4 v = T4[q];
-        acc = acc + v.x;
-        if (4 * q + 1 < N) acc = acc + v.y;
-        if (4 * q + 2 < N) acc = acc + v.z;
-        if (4 * q + 3 < N) acc = acc + v.w;
-    }
-    return acc;
-}
-
-// numpy's pairwise summation of n floats in LDS (trackFeatures.py:124) by a group of lanes, valid in the group's lane s == 0
-__device__ __forceinline__ float pairwise_block(const float *a, int n, int s)
-{
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; i++) res = res + a[i];
-        return res;
-    }
-    const int nn = n - (n % 8);
-    float r = 0.f;
-    if (s < 8) {
-        r = a[s];
-        for (int i = 8; i < nn; i += 8) r = r + a[i + s];
-    }
-    r = r + __shfl_down(r, 1);
-    r = r + __shfl_down(r, 2);
-    float res = r + __shfl_down(r, 4);
-    for (int i = nn; i < n; i++) res = res + a[i];
-    return res;
-}
-
-template <int DEPTH>
-__device__ __forceinline__ float pairwise_sum(const float *a, int n, int s)
-{
-    if (n <= 128) return pairwise_block(a, n, s);
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return pairwise_sum<DEPTH - 1>(a, n2, s) + pairwise_sum<DEPTH - 1>(a + n2, n - n2, s);
-}
-template <>
-__device__ __forceinline__ float pairwise_sum<0>(const float *a, int n, int s)
-{
-    return pairwise_block(a, n < 128 ? n : 128, s);
-}
-__device__ float pairwise_sum_wave(const float *a, int n, int lane) { return pairwise_sum<3>(a, n, lane); }
-
-__device__ __forceinline__ TrackLevel load_level(const TrackLevel *p)
-{
-    typedef const __attribute__((address_space(4))) TrackLevel *cptr;
-    const cptr c = (cptr)p;
-    TrackLevel lv;
-    lv.i1 = c->i1; lv.gx1 = c->gx1; lv.gy1 = c->gy1;
-    lv.i2 = c->i2; lv.gx2 = c->gx2; lv.gy2 = c->gy2;
-    lv.nc = c->nc; lv.nr = c->nr;
-    return lv;
-}
-
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------------------ the gain / bias rule
 // (float)sqrt((double)q) for an f32 q >= 0 (see the head of the file).  The hardware's FP64 root is good to about 24 bits: rounded to f32
@@ -219,7 +106,7 @@ __device__ __forceinline__ float chain_arrays(const float *lds, int npad, int n,
     float acc = 0.f;
     if (lane < narr) {
         const float *T = lds + lane * npad;
-        if constexpr (WCT > 0) acc = chain_sum<WCT * WCT, (WCT <= 8 ? 16 : 4)>(reinterpret_cast<const float4 *>(T));
+        if constexpr (WCT > 0) acc = chain_sum<WCT * WCT, false, (WCT <= 8 ? 16 : 4)>(reinterpret_cast<const float4 *>(T));
         else
             for (int k = 0; k < n; k++) acc = acc + T[k];
     }
@@ -253,9 +140,9 @@ __device__ int track_light_level(const TrackArgsBase &a, const TrackLevel &lv, f
         if (k < n) {
             off[kk] = (k / w) * nc + (k % w);
             const size_t q = (size_t)(b1.iy - hw) * nc + (b1.ix - hw) + off[kk];
-            t_i[kk] = sample(lv.i1 + KLT_PIX_STRIDE * q, nc, b1);
-            t_gx[kk] = sample(lv.gx1 + KLT_PIX_STRIDE * q, nc, b1);
-            t_gy[kk] = sample(lv.gy1 + KLT_PIX_STRIDE * q, nc, b1);
+            t_i[kk] = sample<KLT_PIX_STRIDE>(lv.i1 + KLT_PIX_STRIDE * q, nc, b1);
+            t_gx[kk] = sample<KLT_PIX_STRIDE>(lv.gx1 + KLT_PIX_STRIDE * q, nc, b1);
+            t_gy[kk] = sample<KLT_PIX_STRIDE>(lv.gy1 + KLT_PIX_STRIDE * q, nc, b1);
             lds[k] = t_i[kk];
             lds[npad + k] = t_i[kk] * t_i[kk];
         }
@@ -287,9 +174,9 @@ __device__ int track_light_level(const TrackArgsBase &a, const TrackLevel &lv, f
             s_i[kk] = s_gx[kk] = s_gy[kk] = 0.f;
             if (k < n) {
                 const size_t q = base + off[kk];
-                s_i[kk] = sample(lv.i2 + KLT_PIX_STRIDE * q, nc, b2);
-                s_gx[kk] = sample(lv.gx2 + KLT_PIX_STRIDE * q, nc, b2);
-                s_gy[kk] = sample(lv.gy2 + KLT_PIX_STRIDE * q, nc, b2);
+                s_i[kk] = sample<KLT_PIX_STRIDE>(lv.i2 + KLT_PIX_STRIDE * q, nc, b2);
+                s_gx[kk] = sample<KLT_PIX_STRIDE>(lv.gx2 + KLT_PIX_STRIDE * q, nc, b2);
+                s_gy[kk] = sample<KLT_PIX_STRIDE>(lv.gy2 + KLT_PIX_STRIDE * q, nc, b2);
                 lds[k] = s_i[kk];
                 lds[npad + k] = s_i[kk] * s_i[kk];
             }
@@ -346,7 +233,7 @@ __device__ int track_light_level(const TrackArgsBase &a, const TrackLevel &lv, f
             const int k = lane + 64 * kk;
             s_i[kk] = 0.f;
             if (k < n) {
-                s_i[kk] = sample(lv.i2 + KLT_PIX_STRIDE * (base + off[kk]), nc, b2);
+                s_i[kk] = sample<KLT_PIX_STRIDE>(lv.i2 + KLT_PIX_STRIDE * (base + off[kk]), nc, b2);
                 lds[k] = s_i[kk];
                 lds[npad + k] = s_i[kk] * s_i[kk];
             }
@@ -374,22 +261,6 @@ __device__ int track_light_level(const TrackArgsBase &a, const TrackLevel &lv, f
     if (status == KLT_SMALL_DET || status == KLT_OOB || status == KLT_LARGE_RESIDUE) return status;
     if (iters >= a.max_iterations) return KLT_MAX_ITERATIONS;
     return KLT_TRACKED;
-}
-
-// The record a feature ends with (trackFeatures.py:288-308)
-__device__ __forceinline__ klt_feat track_record(const TrackArgsBase &a, int val, float xout, float yout, uint32_t aux)
-{
-    klt_feat o;
-    o.aux = (int32_t)aux;
-    const double xd = (double)xout, yd = (double)yout;
-    const bool oob = val == KLT_OOB ||
-                     xd < a.borderx || xd > (double)(a.ncols - 1) - a.borderx ||
-                     yd < a.bordery || yd > (double)(a.nrows - 1) - a.bordery;
-    if (oob) { o.x = -1.f; o.y = -1.f; o.val = KLT_OOB; }
-    else if (val == KLT_SMALL_DET || val == KLT_LARGE_RESIDUE || val == KLT_MAX_ITERATIONS) {
-        o.x = -1.f; o.y = -1.f; o.val = val;
-    } else { o.x = xout; o.y = yout; o.val = KLT_TRACKED; }
-    return o;
 }
 
 // One feature per wavefront, every pyramid level inside the launch; features in list order (no XCD-aware order: a.order is not looked at)
@@ -431,54 +302,6 @@ __global__ __launch_bounds__(64) void track_light_kernel(TrackArgsBase a)
 // as 16 quads of four pixels, one 16-byte load per lane and image, per-feature predicates, a footprint whose integer corner has not moved
 // is kept.  Every feature's arithmetic is track_light_level's, operation for operation.
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// the records of pixels q .. q + 3 of a level: 48 contiguous bytes at byte offset 12 q as three raw 16-byte buffer loads
-__device__ __forceinline__ void load_records(const float *rec, unsigned q, f32x4 &im, f32x4 &gx, f32x4 &gy)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)rec, 0, 0x7fffffff, 0x00020000);
-    const unsigned o = 12u * q;
-    const f32x4 a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));          // i0 x0 y0 i1
-    const f32x4 b = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 16u, 0, 0));    // x1 y1 i2 x2
-    const f32x4 c = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o + 32u, 0, 0));    // y2 i3 x3 y3
-    im.x = a.x; im.y = a.w; im.z = b.z; im.w = c.y;
-    gx.x = a.y; gx.y = b.x; gx.z = b.w; gx.w = c.z;
-    gy.x = a.z; gy.y = b.y; gy.z = c.x; gy.w = c.w;
-}
-
-// the image values alone of pixels q .. q + 3 (the residue)
-__device__ __forceinline__ f32x4 load_record_images(const float *rec, unsigned q)
-{
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)rec, 0, 0x7fffffff, 0x00020000);
-    const unsigned o = 12u * q;
-    f32x4 im;
-    im.x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0));
-    im.y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 12u, 0, 0));
-    im.z = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 24u, 0, 0));
-    im.w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, o + 36u, 0, 0));
-    return im;
-}
-
-// the four window samples of a lane from its quad, the quad below (QPR lanes up) and the first pixels of the quads to the right
-template <int QPR>
-__device__ __forceinline__ void sample_quad(const f32x4 a, const Bilinear &b, float out[4])
-{
-    f32x4 lo;
-    lo.x = __shfl_down(a.x, QPR); lo.y = __shfl_down(a.y, QPR); lo.z = __shfl_down(a.z, QPR); lo.w = __shfl_down(a.w, QPR);
-    const float rx = __shfl_down(a.x, 1), dx = __shfl_down(a.x, QPR + 1);
-    const float v00[4] = {a.x, a.y, a.z, a.w}, v01[4] = {a.y, a.z, a.w, rx};
-    const float v10[4] = {lo.x, lo.y, lo.z, lo.w}, v11[4] = {lo.y, lo.z, lo.w, dx};
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const float t4 = b.w11 * v11[m];
-        double d = b.w00 * (double)v00[m];
-        d = d + b.w01 * (double)v01[m];
-        d = d + b.w10 * (double)v10[m];
-        d = d + (double)t4;
-        out[m] = (float)d;
-    }
-}
-
 template <bool BATCH>
 __global__ __launch_bounds__(64) void track_light_quad(TrackArgsBase a)
 {
@@ -510,7 +333,7 @@ __global__ __launch_bounds__(64) void track_light_quad(TrackArgsBase a)
     auto chains = [&](int narr) {
         wave_lds_sync();
         float acc = 0.f;
-        if (s < narr) acc = chain_sum<n, 16>(reinterpret_cast<const float4 *>(gl + s * npad));
+        if (s < narr) acc = chain_sum<n, false, 16>(reinterpret_cast<const float4 *>(gl + s * npad));
         wave_lds_sync();
         return acc;
     };
@@ -690,13 +513,9 @@ static int launch_track_light_t(hipStream_t s, const TrackArgsBase &a, int *path
         return 0;
     }
     const dim3 grid(a.n, ny);
-    if (a.window == 7) klt_launch((track_light_kernel<1, 7, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (a.window == 15) klt_launch((track_light_kernel<4, 15, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 64) klt_launch((track_light_kernel<1, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 128) klt_launch((track_light_kernel<2, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 256) klt_launch((track_light_kernel<4, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else if (n <= 512) klt_launch((track_light_kernel<8, 0, BATCH>), grid, block, (unsigned)lds, s, a);
-    else klt_launch((track_light_kernel<16, 0, BATCH>), grid, block, (unsigned)lds, s, a);
+    for_window_class(a.window, [&](auto maxk, auto wct) {
+        klt_launch((track_light_kernel<maxk.value, wct.value, BATCH>), grid, block, (unsigned)lds, s, a);
+    });
     *path = 1;
     return 0;
 }

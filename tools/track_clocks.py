@@ -3,6 +3,7 @@ KLT_TRACK_CLOCKS (every mark waits for outstanding memory operations first) and 
 Run on the GPU box:  python tools/track_clocks.py"""
 import ctypes as C
 import os
+import re
 import subprocess
 import sys
 
@@ -14,7 +15,9 @@ os.makedirs(os.path.dirname(dbg), exist_ok=True)
 subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
                 "-I" + os.path.join(ROOT, "include"), "-Wno-cuda-compat", "-DKLT_TRACK_CLOCKS", "-c", os.path.join(src, "track_kernels.hip"),
                 "-o", "/tmp/track_clk.o"], check=True)
-objs = [os.path.join(src, f) for f in ("api_context.o", "api_frames.o", "api_featbuf.o", "api_select.o", "api_track.o", "api_comm.o", "api_compat.o", "host_pool.o", "comm.o", "conv_kernels.o", "pyramid_kernels.o", "select_kernels.o", "sat_pipeline.o", "affine_kernels.o")]
+# every other object of the library as the Makefile lists them (built there: `make -C pyfeaturetrack_amd/csrc`)
+srcs = re.search(r"^SRCS\s*:=\s*(.*)$", open(os.path.join(src, "Makefile")).read(), re.M).group(1).split()
+objs = [os.path.join(src, f[:-len(".hip")] + ".o") for f in srcs if f != "track_kernels.hip"]
 subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", "-o", dbg, "/tmp/track_clk.o"] + objs + ["-ldl", "-lpthread"], check=True)
 os.environ["KLT_GPU_LIB"] = dbg
 
