@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -52,7 +52,8 @@ typedef enum {
 /* feature status codes, klt.py:23-29 (kltState) */
 enum { KLT_TRACKED = 0, KLT_NOT_FOUND = -1, KLT_SMALL_DET = -2, KLT_MAX_ITERATIONS = -3,
        KLT_OOB = -4, KLT_LARGE_RESIDUE = -5,
-       KLT_FB_INCONSISTENT = -6 /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */ };
+       KLT_FB_INCONSISTENT = -6, /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */
+       KLT_MODEL_OUTLIER = -7    /* not in the reference: off the frame pair's dominant affine motion (klt_motion_check_async); lost likewise */ };
 
 /* selection modes, selectGoodFeatures.py:11-13 */
 enum { KLT_SELECTING_ALL = 1, KLT_REPLACING_SOME = 2 };
@@ -437,6 +438,74 @@ int klt_track_quality_batch_async(klt_ctx *ctx, const int *slot1, const int *slo
                                   const int *fb_quality, int npairs, int n);
 /* synchronous, host arrays: q[i] from in[i] and out[i] */
 int klt_track_quality(klt_ctx *ctx, int slot1, int slot2, const klt_feat *in, const klt_feat *out, klt_quality *q, int n);
+
+/* ---- motion-model check (not in the reference) ------------------------------------------------------------------ */
+/* Judges every track of a frame pair against the other tracks of that pair: a seeded consensus search for the pair's dominant affine
+ * motion, one least-squares refit, and every tracked feature that does not follow the result becomes (-1, -1, KLT_MODEL_OUTLIER, aux).
+ * It reads two feature lists and nothing else (no frame), and runs stream-ordered behind whatever wrote them.
+ *
+ * THE RULE.  Inputs: lists `in` and `out` of n records (the tracker's input and its result) and klt_model_params.  All arithmetic is
+ * FP64, one rounding per operation, nothing contracted, in exactly the order written here; the device code divides nothing and takes
+ * no square root: a model is kept in homogeneous form, six numerators and one denominator, q = (N / D) (p, 1).
+ * Magnitudes: coordinates are below 2^16 and n below 2^24, so a hypothesis's numbers stay below 2^34, its residuals' squares below
+ * 2^106, the refit's sums below 2^56, its cofactors below 2^114, its numerators and determinant below 2^172 and the squares of the
+ * residuals under it below 2^380 -- nothing comes near 2^1023, nothing overflows.
+ *  1 candidates  record i is a candidate iff in.val >= 0, out.val == KLT_TRACKED and all four coordinates satisfy 0 <= x < ncols,
+ *                0 <= y < nrows as f32 comparisons (NaN and the infinities fail; a slot a replacement pass refilled, val > 0, is not
+ *                one).  Candidates are numbered k = 0 .. m-1 in list order; p_k = ((double)in.x - cx, (double)in.y - cy), q_k likewise
+ *                from out, cx = ncols / 2, cy = nrows / 2 (integer division).  m < min_inliers: no model (valid = 0), out untouched.
+ *  2 samples     hypothesis h = 0 .. hypotheses-1 takes candidates r_j = mulhi32(mix(seed ^ mix(3*h + j)), m), j = 0, 1, 2, in uint32
+ *                arithmetic: mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16;
+ *                mulhi32(u, m) = (uint64)u * m >> 32.  Repeated or collinear picks need no special case: their area is 0.
+ *  3 hypothesis  with p0 = p_r0 ..., u = p1 - p0, v = p2 - p0, a = q1 - q0, b = q2 - q0 (componentwise):
+ *                  D   = u.x*v.y - u.y*v.x
+ *                  Nxx = a.x*v.y - b.x*u.y      Nxy = b.x*u.x - a.x*v.x      Ntx = D*q0.x - (Nxx*p0.x + Nxy*p0.y)
+ *                  Nyx = a.y*v.y - b.y*u.y      Nyy = b.y*u.x - a.y*v.x      Nty = D*q0.y - (Nyx*p0.x + Nyy*p0.y)
+ *                It counts iff fabs(D) >= (double)min_area (NaN fails); otherwise its score is -1.  Candidate k is an inlier of a
+ *                model (N, D) iff rx*rx + ry*ry <= (t*t) * (D*D) with t = (double)max_error,
+ *                  rx = ((Nxx*p.x + Nxy*p.y) + Ntx) - D*q.x        ry = ((Nyx*p.x + Nyy*p.y) + Nty) - D*q.y
+ *                The score is the number of inliers.  The best hypothesis has the largest score, ties go to the smallest h.  Best
+ *                score < min_inliers: valid = 0, out untouched.
+ *  4 refit, once over the inliers of the best hypothesis, twelve sums: S1 = SUM 1.0, Sx = SUM p.x, Sy = SUM p.y, Sxx = SUM p.x*p.x,
+ *                Sxy = SUM p.x*p.y, Syy = SUM p.y*p.y and, for the right-hand sides, X0 = SUM p.x*q.x, X1 = SUM p.y*q.x, X2 = SUM q.x,
+ *                Y0 = SUM p.x*q.y, Y1 = SUM p.y*q.y, Y2 = SUM q.y.  The term of candidate k joins partial k mod 64 in increasing k
+ *                (non-inliers are skipped), the 64 partials fold by p[l] += p[l + w], l < w, w = 32 .. 1.  Cramer's rule on the 3x3
+ *                normal equations, through the cofactors
+ *                  c00 = Syy*S1 - Sy*Sy      c01 = Sx*Sy - Sxy*S1      c02 = Sxy*Sy - Sx*Syy
+ *                  c11 = Sxx*S1 - Sx*Sx      c12 = Sxy*Sx - Sxx*Sy     c22 = Sxx*Syy - Sxy*Sxy
+ *                  D2  = (Sxx*c00 + Sxy*c01) + Sx*c02
+ *                  Nxx = (c00*X0 + c01*X1) + c02*X2    Nxy = (c01*X0 + c11*X1) + c12*X2    Ntx = (c02*X0 + c12*X1) + c22*X2
+ *                  Nyx, Nyy, Nty likewise from Y0, Y1, Y2.
+ *                D2 > 0 (NaN fails): the model is the refit with D = D2, valid = 1.  Otherwise the hypothesis is kept, valid = 2.  The
+ *                inlier test of step 3 is evaluated once more under the final model; there is no iteration.
+ *  5 outputs     every candidate that is not an inlier of the final model becomes (-1, -1, KLT_MODEL_OUTLIER, out.aux) in `out`; every
+ *                other record of `out` keeps its bytes.  One klt_motion_model goes to a feature buffer of five klt_feat records:
+ *                valid = 0: the seven numbers, n_inliers and hypothesis_inliers are 0, hypothesis is -1; otherwise the final model,
+ *                its inlier count, the best hypothesis and its score.  n_candidates = m; pad = ncols | nrows << 16 in every record the
+ *                check writes (what klt_motion_model_affine uncentres with).  The division happens on the host. */
+typedef struct { int32_t mode; int32_t ncols, nrows; int32_t hypotheses; uint32_t seed; int32_t min_inliers; float max_error; float min_area; } klt_model_params;
+typedef struct { double nxx, nxy, ntx, nyx, nyy, nty, d; int32_t valid, n_candidates, n_inliers, hypothesis, hypothesis_inliers, pad; } klt_motion_model;
+/* mode: 0 = off (the default), 1 = affine; anything else is KLT_ERR_ARG, and so are hypotheses outside 1 .. 65536, min_inliers < 3,
+ * max_error or min_area negative or NaN, and (mode 1) ncols / nrows outside 1 .. 65535.  Defaults: 256 hypotheses, seed 0, min_inliers 8,
+ * max_error 1.0 px, min_area 1.0 px^2.  Not in the reference; DESIGN.md section 9g. */
+int klt_set_model_params(klt_ctx *ctx, const klt_model_params *p);
+/* The check on two resident lists: fb_out is rewritten in place, fb_model (allocated if needed) takes the klt_motion_model; fb_model
+ * must be distinct from fb_in and fb_out by index and by address, and fb_in from fb_out (KLT_ERR_ARG); lists shorter than n:
+ * KLT_ERR_STATE; mode 0: KLT_ERR_STATE with a klt_last_error text; n == 0: KLT_OK, nothing enqueued.  The candidate and score scratch
+ * belongs to the context (out of memory: KLT_ERR_NOMEM, nothing half-allocated).  Not in the reference; DESIGN.md section 9g. */
+int klt_motion_check_async(klt_ctx *ctx, int fb_in, int fb_out, int fb_model, int n);
+/* npairs pairs in the same launches; every fb_model distinct from every list and from each other, every fb_out from every other list.
+ * Not in the reference; DESIGN.md section 9g. */
+int klt_motion_check_batch_async(klt_ctx *ctx, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n);
+/* synchronous, host arrays: out is rewritten, *model filled, *n_outliers (may be NULL) = the records that became KLT_MODEL_OUTLIER.
+ * Not in the reference; DESIGN.md section 9g. */
+int klt_motion_check(klt_ctx *ctx, const klt_feat *in, klt_feat *out, klt_motion_model *model, int n, int *n_outliers);
+/* host only: the map q = A p + t (A row-major) in UNCENTRED pixel coordinates from a model record; KLT_ERR_ARG for a null pointer,
+ * KLT_ERR_STATE for a record with valid == 0 or d == 0.  Not in the reference; DESIGN.md section 9g. */
+int klt_motion_model_affine(const klt_motion_model *model, double A[4], double t[2]);
+/* 0: no motion-check launch yet; 1: the last one ran as three launches on one pair, 2: as three launches on a table of pairs.  A
+ * diagnostic, like klt_track_light_path.  Not in the reference; DESIGN.md section 9g. */
+int klt_motion_check_path(klt_ctx *ctx);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

@@ -20,6 +20,17 @@ class KltQuality(C.Structure):
     _fields_ = [("residue", C.c_float), ("ncc", C.c_float), ("min_eig", C.c_float), ("val", C.c_int32)]
 
 
+class KltModelParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ncols", C.c_int32), ("nrows", C.c_int32), ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+                ("min_inliers", C.c_int32), ("max_error", C.c_float), ("min_area", C.c_float)]
+
+
+class KltMotionModel(C.Structure):
+    _fields_ = [("nxx", C.c_double), ("nxy", C.c_double), ("ntx", C.c_double), ("nyx", C.c_double), ("nyy", C.c_double),
+                ("nty", C.c_double), ("d", C.c_double), ("valid", C.c_int32), ("n_candidates", C.c_int32), ("n_inliers", C.c_int32),
+                ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
+
+
 class KltParams(C.Structure):
     _fields_ = [
         ("mindist", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
@@ -145,6 +156,12 @@ SYMBOLS = {
     "klt_track_quality_async": (_I, [_P, _I, _I, _I, _I, _I, _I]),
     "klt_track_quality_batch_async": (_I, [_P, _PI, _PI, _PI, _PI, _PI, _I, _I]),
     "klt_track_quality": (_I, [_P, _I, _I, _P, _P, _P, _I]),
+    "klt_set_model_params": (_I, [_P, C.POINTER(KltModelParams)]),
+    "klt_motion_check_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_motion_check_batch_async": (_I, [_P, _PI, _PI, _PI, _I, _I]),
+    "klt_motion_check": (_I, [_P, _P, _P, C.POINTER(KltMotionModel), _I, _PI]),
+    "klt_motion_model_affine": (_I, [C.POINTER(KltMotionModel), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "klt_motion_check_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltQuality, KltTrackStats, load_library)
+                   KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
@@ -24,6 +24,12 @@ assert AFFINE_DTYPE.itemsize == C.sizeof(KltAffineRec)
 QUALITY_DTYPE = np.dtype([("residue", np.float32), ("ncc", np.float32), ("min_eig", np.float32), ("val", np.int32)])
 assert QUALITY_DTYPE.itemsize == C.sizeof(KltQuality) == FEAT_DTYPE.itemsize
 
+# a motion model (klt_motion_model; klt_motion_check*): one record in a feature buffer of five klt_feat records
+MODEL_DTYPE = np.dtype([("nxx", np.float64), ("nxy", np.float64), ("ntx", np.float64), ("nyx", np.float64), ("nyy", np.float64),
+                        ("nty", np.float64), ("d", np.float64), ("valid", np.int32), ("n_candidates", np.int32), ("n_inliers", np.int32),
+                        ("hypothesis", np.int32), ("hypothesis_inliers", np.int32), ("pad", np.int32)])
+assert MODEL_DTYPE.itemsize == C.sizeof(KltMotionModel) == 5 * FEAT_DTYPE.itemsize
+
 SELECTING_ALL = 1
 REPLACING_SOME = 2
 # the reference-shaped API's tracker reads and writes its pinned record arrays in place (klt_featbuf_map_host); KLT_MAP_RECORDS=0 in
@@ -34,6 +40,7 @@ MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
 _FB_API_IN, _FB_API_OUT = 65526, 65527
 _FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
 _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
+_FB_API_MODEL = 53999                # the model record of a KLTTrackFeatures call with tc.motionModelCheck (48000 .. 53998: KLTTrackSequence's model rows)
 _FB_API_QUALITY = 59999              # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
 
 
@@ -738,6 +745,49 @@ class Context:
         """n quality records of feature buffer `fb` (what a track_quality*_async launch wrote there)"""
         return self.featbuf_download(fb, n).view(QUALITY_DTYPE)
 
+    # ------------------------------------------------ motion-model check (klt_set_model_params, klt_motion_check*)
+    def set_model_params(self, mp=None, **kw):
+        """klt_set_model_params: `mp` a KltModelParams, or its fields by name (mode, ncols, nrows, hypotheses, seed, min_inliers,
+        max_error, min_area; defaults 1, -, -, 256, 0, 8, 1.0, 1.0)"""
+        if mp is None:
+            d = dict(mode=1, hypotheses=256, seed=0, min_inliers=8, max_error=1.0, min_area=1.0)
+            d.update(kw)
+            mp = KltModelParams(**d)
+        key = bytes(mp)
+        if key != getattr(self, "_model_key", None):
+            self._model_key = None
+            self._check(self._lib.klt_set_model_params(self._h, C.byref(mp)))
+            self._model_key = key
+
+    def motion_check(self, fl_in, fl_out):
+        """klt_motion_check: (out, model, n_outliers) -- fl_out with every tracked record off the dominant affine motion turned into
+        (-1, -1, KLT_MODEL_OUTLIER, aux), the MODEL_DTYPE record, and how many records that were"""
+        fl_in = np.ascontiguousarray(fl_in, FEAT_DTYPE)
+        out = np.array(fl_out, FEAT_DTYPE, order="C")
+        if len(fl_in) != len(out):
+            raise ValueError("the two lists have %d and %d records" % (len(fl_in), len(out)))
+        model = np.zeros(1, MODEL_DTYPE)
+        cnt = C.c_int(0)
+        self._check(self._lib.klt_motion_check(self._h, fl_in.ctypes.data, out.ctypes.data,
+                                               C.cast(model.ctypes.data, C.POINTER(KltMotionModel)), len(out), C.byref(cnt)))
+        return out, model[0], cnt.value
+
+    def motion_check_async(self, fb_in, fb_out, fb_model, n):
+        self._check(self._lib.klt_motion_check_async(self._h, fb_in, fb_out, fb_model, n))
+
+    def motion_check_batch_async(self, pairs, n):
+        """pairs: [(fb_in, fb_out, fb_model), ...] -- the check's launches once for all of them."""
+        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(3)]
+        self._check(self._lib.klt_motion_check_batch_async(self._h, cols[0], cols[1], cols[2], len(pairs), n))
+
+    def motion_check_path(self):
+        """klt_motion_check_path: 0 no motion-check launch yet, 1 the last one ran on one pair, 2 on a table of pairs (a diagnostic)"""
+        return self._check(self._lib.klt_motion_check_path(self._h))
+
+    def model_download(self, fb):
+        """the MODEL_DTYPE record of feature buffer `fb` (what a motion_check*_async launch wrote there)"""
+        return self.featbuf_download(fb, 5).view(MODEL_DTYPE)[0]
+
     def track_stats_reset(self):
         self._check(self._lib.klt_track_stats_reset(self._h))
 
@@ -886,5 +936,25 @@ def context_of(tc, device=None):
     return ctx
 
 
-__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
+def model_affine(model):
+    """klt_motion_model_affine: (A, t) of the map q = A p + t in uncentred pixel coordinates -- A a 2x2 float64 array, t of length 2 --
+    from a MODEL_DTYPE record; (None, None) for one without a model (valid == 0)"""
+    rec = np.zeros(1, MODEL_DTYPE)
+    rec[0] = model
+    A, t = np.zeros(4, np.float64), np.zeros(2, np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = load_library().klt_motion_model_affine(C.cast(rec.ctypes.data, C.POINTER(KltMotionModel)), A.ctypes.data_as(dp), t.ctypes.data_as(dp))
+    if rc != 0:
+        return None, None
+    return A.reshape(2, 2), t
+
+
+def model_summary(model):
+    """what KLTTrackFeatures leaves in tc.model_last: a dict with A (2x2), t, valid, candidates, inliers, hypothesis"""
+    A, t = model_affine(model)
+    return {"A": A, "t": t, "valid": int(model["valid"]), "candidates": int(model["n_candidates"]), "inliers": int(model["n_inliers"]),
+            "hypothesis": int(model["hypothesis"])}
+
+
+__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "MODEL_DTYPE", "model_affine", "model_summary", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
            "KLT_MAX_LEVELS", "KltParams"]

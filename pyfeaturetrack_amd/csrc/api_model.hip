@@ -1,0 +1,204 @@
+// api_model.hip -- the motion-model check (not in the reference): parameters, the single-pair, batched and
+// synchronous entry points, and the host-side division that turns a model record into an affine map.  The rule stands in
+// include/klt_gpu.h, the kernels in model_kernels.hip.
+#include <cmath>
+
+#include "klt_context.h"
+
+using namespace kltapi;
+
+// a pair's slice of the context's scratch: candidates (32 bytes each), their record numbers and aux (8 bytes each), one score per
+// hypothesis, the candidate count; a multiple of 256 bytes
+static size_t model_slice_bytes(int n, int hypotheses)
+{
+    const size_t b = (size_t)n * 32 + (size_t)n * 8 + (size_t)hypotheses * 4 + 16;
+    return (b + 255) & ~(size_t)255;
+}
+
+static void fill_model_scratch(klt_ctx *c, int i, int n, ModelPair &p)
+{
+    unsigned char *base = c->model_scratch + (size_t)i * model_slice_bytes(n, c->modelp.hypotheses);
+    p.cand = reinterpret_cast<double *>(base);
+    p.idx = reinterpret_cast<int *>(base + (size_t)n * 32);
+    p.scores = reinterpret_cast<int *>(base + (size_t)n * 40);
+    p.count = p.scores + c->modelp.hypotheses;
+}
+
+static void fill_model_args(const klt_ctx *c, int n, ModelArgs &a)
+{
+    const klt_model_params &m = c->modelp;
+    a.n = n; a.ncols = m.ncols; a.nrows = m.nrows; a.hypotheses = m.hypotheses; a.min_inliers = m.min_inliers; a.seed = m.seed;
+    a.cx = (double)(m.ncols / 2); a.cy = (double)(m.nrows / 2);
+    a.t2 = (double)m.max_error * (double)m.max_error;
+    a.min_area = (double)m.min_area;
+}
+
+// the three launches, each timed as a tracker-family launch of its own (klt_timing_enable: their sum is the check's cost)
+static int enqueue_model(klt_ctx *c, const ModelArgs &a, int npairs)
+{
+    const double list = (double)npairs * a.n * 32;
+    { TimerScope t(c, F_TRACK, list + (double)npairs * a.n * 40, c->stream); launch_model_gather(c->stream, a); }
+    { TimerScope t(c, F_TRACK, (double)npairs * a.n * 32 * a.hypotheses, c->stream); launch_model_score(c->stream, a); }
+    { TimerScope t(c, F_TRACK, (double)npairs * a.n * 64, c->stream); launch_model_decide(c->stream, a); }
+    return 0;
+}
+
+static int model_off(klt_ctx *c)
+{
+    return fail(c, KLT_ERR_STATE, "the motion-model check is off (klt_set_model_params mode 0)");
+}
+
+static bool list_ok(const klt_ctx *c, int fb, int n)
+{
+    return fb >= 0 && (size_t)fb < c->fbs.size() && c->fbs[fb].d && c->fbs[fb].cap >= n;
+}
+
+extern "C" {
+
+int klt_set_model_params(klt_ctx *c, const klt_model_params *p)
+{
+    if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
+    if (p->mode != 0 && p->mode != 1) return fail(c, KLT_ERR_ARG, "motion-model mode must be 0 (off) or 1 (affine)");
+    if (p->hypotheses < 1 || p->hypotheses > 65536) return fail(c, KLT_ERR_ARG, "motion model: hypotheses must lie in 1 .. 65536");
+    if (p->min_inliers < 3) return fail(c, KLT_ERR_ARG, "motion model: min_inliers must be at least 3");
+    if (!(p->max_error >= 0.f) || !(p->min_area >= 0.f))                                  // (NaN fails the comparison)
+        return fail(c, KLT_ERR_ARG, "motion model: max_error and min_area must be numbers >= 0");
+    if (p->mode == 1 && (p->ncols < 1 || p->ncols > 65535 || p->nrows < 1 || p->nrows > 65535))
+        return fail(c, KLT_ERR_ARG, "motion model: ncols and nrows must lie in 1 .. 65535");
+    c->modelp = *p;
+    return KLT_OK;
+}
+
+int klt_motion_check_path(klt_ctx *c)
+{
+    if (!c) return KLT_ERR_ARG;
+    return c->model_path;
+}
+
+int klt_motion_check_async(klt_ctx *c, int fb_in, int fb_out, int fb_model, int n)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
+    if (fb_model < 0 || fb_model > 65535) return fail(c, KLT_ERR_ARG, "fb_model must be a feature buffer");
+    if (fb_model == fb_in || fb_model == fb_out || fb_in == fb_out) return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
+    if (c->modelp.mode == 0) return model_off(c);
+    if (n == 0) return KLT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!list_ok(c, fb_in, n) || !list_ok(c, fb_out, n)) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    if (c->fbs[fb_in].d == c->fbs[fb_out].d) return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
+    if ((size_t)fb_model < c->fbs.size() && c->fbs[fb_model].d &&
+        (c->fbs[fb_model].d == c->fbs[fb_in].d || c->fbs[fb_model].d == c->fbs[fb_out].d))          // a view can be a second name of the same records
+        return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
+    if (int rc = ensure(c, c->model_scratch, c->model_scratch_cap, model_slice_bytes(n, c->modelp.hypotheses))) return rc;
+    FeatBuf *bm;                                             // (may grow c->fbs: before any pointer into it is taken)
+    if (int rc = get_fb(c, fb_model, 5, &bm)) return rc;
+    ModelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.one.in = c->fbs[fb_in].d; a.one.out = c->fbs[fb_out].d;
+    a.one.model = reinterpret_cast<klt_motion_model *>(c->fbs[fb_model].d);
+    fill_model_scratch(c, 0, n, a.one);
+    fill_model_args(c, n, a);
+    if (int rc = enqueue_model(c, a, 1)) return rc;
+    c->model_path = 1;
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
+int klt_motion_check_batch_async(klt_ctx *c, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n)
+{
+    if (!c) return KLT_ERR_ARG;
+    if (!fb_in || !fb_out || !fb_model || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
+    // a model record that another pair of the launch reads as a list, a list that another pair rewrites: by index first ...
+    for (int i = 0; i < npairs; i++) {
+        if (fb_model[i] < 0 || fb_model[i] > 65535) return fail(c, KLT_ERR_ARG, "fb_model must be a feature buffer");
+        for (int j = 0; j < npairs; j++) {
+            if (fb_model[i] == fb_in[j] || fb_model[i] == fb_out[j] || (i != j && fb_model[i] == fb_model[j]))
+                return fail(c, KLT_ERR_ARG, "every fb_model must be distinct from every list and from each other");
+            if (fb_out[i] == fb_in[j] || (i != j && fb_out[i] == fb_out[j]))
+                return fail(c, KLT_ERR_ARG, "every fb_out must be distinct from every other list");
+        }
+    }
+    if (c->modelp.mode == 0) return model_off(c);
+    if (n == 0) return KLT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int i = 0; i < npairs; i++)
+        if (!list_ok(c, fb_in[i], n) || !list_ok(c, fb_out[i], n)) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    // ... then by address: a view can be a second name of the same records (a buffer that does not exist yet is nobody's second name)
+    for (int i = 0; i < npairs; i++) {
+        const klt_feat *mi = (size_t)fb_model[i] < c->fbs.size() ? c->fbs[fb_model[i]].d : nullptr;
+        const klt_feat *oi = c->fbs[fb_out[i]].d;
+        for (int j = 0; j < npairs; j++) {
+            const klt_feat *mj = (size_t)fb_model[j] < c->fbs.size() ? c->fbs[fb_model[j]].d : nullptr;
+            if (mi && (mi == c->fbs[fb_in[j]].d || mi == c->fbs[fb_out[j]].d || (i != j && mi == mj)))
+                return fail(c, KLT_ERR_ARG, "every fb_model must be distinct from every list and from each other");
+            if (oi == c->fbs[fb_in[j]].d || (i != j && oi == c->fbs[fb_out[j]].d))
+                return fail(c, KLT_ERR_ARG, "every fb_out must be distinct from every other list");
+        }
+    }
+    if (int rc = ensure(c, c->model_scratch, c->model_scratch_cap, (size_t)npairs * model_slice_bytes(n, c->modelp.hypotheses))) return rc;
+    for (int i = 0; i < npairs; i++) {
+        FeatBuf *bm;                                         // may grow c->fbs: do it before taking pointers into it
+        if (int rc = get_fb(c, fb_model[i], 5, &bm)) return rc;
+    }
+    std::vector<ModelPair> table((size_t)npairs);
+    for (int i = 0; i < npairs; i++) {
+        std::memset(&table[i], 0, sizeof(ModelPair));
+        table[i].in = c->fbs[fb_in[i]].d; table[i].out = c->fbs[fb_out[i]].d;
+        table[i].model = reinterpret_cast<klt_motion_model *>(c->fbs[fb_model[i]].d);
+        fill_model_scratch(c, i, n, table[i]);
+    }
+    // the table goes up only when it differs from the one the device holds (pageable source: the runtime stages it before returning;
+    // stream order protects the launch that read the replaced table)
+    if (c->model_host.size() != table.size() || std::memcmp(c->model_host.data(), table.data(), table.size() * sizeof(ModelPair)) != 0) {
+        c->model_host.clear();                               // (nothing is known of the device's copy until the new one is enqueued)
+        if (int rc = ensure(c, c->model_dev, c->model_cap, (size_t)npairs)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->model_dev, table.data(), (size_t)npairs * sizeof(ModelPair), hipMemcpyHostToDevice, c->stream));
+        c->model_host = table;
+    }
+    ModelArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.pairs = c->model_dev;
+    a.npairs = npairs;
+    fill_model_args(c, n, a);
+    if (int rc = enqueue_model(c, a, npairs)) return rc;
+    c->model_path = 2;
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
+}
+
+int klt_motion_check(klt_ctx *c, const klt_feat *in, klt_feat *out, klt_motion_model *model, int n, int *n_outliers)
+{
+    if (!c || !in || !out || !model) return fail(c, KLT_ERR_ARG, "null argument");
+    if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
+    if (c->modelp.mode == 0) return model_off(c);
+    const int fi = 65534, fo = 65535, fm = 65530;
+    std::memset(model, 0, sizeof(*model));
+    if (n_outliers) *n_outliers = 0;
+    if (n == 0) return KLT_OK;
+    int before = 0;
+    for (int i = 0; i < n; i++) before += out[i].val == KLT_MODEL_OUTLIER;
+    if (int rc = klt_featbuf_upload_async(c, fi, in, n)) return rc;         // (the downloads below synchronise: both lists are ours until then)
+    if (int rc = klt_featbuf_upload_async(c, fo, out, n)) return rc;
+    if (int rc = klt_motion_check_async(c, fi, fo, fm, n)) return rc;
+    if (int rc = klt_featbuf_download(c, fo, out, n)) return rc;
+    if (int rc = klt_featbuf_download(c, fm, reinterpret_cast<klt_feat *>(model), 5)) return rc;
+    if (n_outliers) {
+        int after = 0;
+        for (int i = 0; i < n; i++) after += out[i].val == KLT_MODEL_OUTLIER;
+        *n_outliers = after - before;
+    }
+    return KLT_OK;
+}
+
+int klt_motion_model_affine(const klt_motion_model *m, double A[4], double t[2])
+{
+    if (!m || !A || !t) return KLT_ERR_ARG;
+    if (m->valid == 0 || m->d == 0.0 || std::isnan(m->d)) return KLT_ERR_STATE;
+    const double cx = (double)(((uint32_t)m->pad & 0xffffu) / 2), cy = (double)(((uint32_t)m->pad >> 16) / 2);
+    A[0] = m->nxx / m->d; A[1] = m->nxy / m->d; A[2] = m->nyx / m->d; A[3] = m->nyy / m->d;
+    t[0] = (m->ntx / m->d + cx) - (A[0] * cx + A[1] * cy);
+    t[1] = (m->nty / m->d + cy) - (A[2] * cx + A[3] * cy);
+    return KLT_OK;
+}
+
+}  // extern "C"

@@ -261,6 +261,15 @@ struct klt_ctx {
     std::vector<QualityPair> quality_host;
     QualityPair *quality_dev = nullptr;
     size_t quality_cap = 0;
+    // motion-model check (klt_set_model_params, klt_motion_check*): candidates and scores live in one scratch allocation, a slice per pair;
+    // the descriptor table of a batched launch stays on the device and is sent again only when it differs
+    klt_model_params modelp{0, 0, 0, 256, 0u, 8, 1.0f, 1.0f};
+    int model_path = 0;                                            // klt_motion_check_path
+    unsigned char *model_scratch = nullptr;
+    size_t model_scratch_cap = 0;
+    std::vector<ModelPair> model_host;
+    ModelPair *model_dev = nullptr;
+    size_t model_cap = 0;
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;

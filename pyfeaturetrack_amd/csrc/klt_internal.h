@@ -112,6 +112,31 @@ struct QualityArgs {
     int n, window, ncols, nrows;
 };
 
+// one frame pair of a motion-model check (klt_motion_check_async): the two lists, the model record (in a feature
+// buffer of five records) and the pair's part of the context's scratch.  The table of a batched launch (device memory, indexed by
+// blockIdx.y) holds these.
+static_assert(sizeof(klt_motion_model) == 5 * sizeof(klt_feat), "a model record lives in a feature buffer of five records");
+struct ModelPair {
+    const klt_feat *in;
+    klt_feat *out;
+    klt_motion_model *model;
+    double *cand;                       // [n][4]: (p.x, p.y, q.x, q.y) of candidate k, centred
+    int *idx;                           // [n][2]: candidate k's record number and its out.aux
+    int *scores;                        // [hypotheses]
+    int *count;                         // m, the number of candidates
+};
+
+struct ModelArgs {
+    ModelPair one;                      // single-pair launch
+    const ModelPair *pairs;             // batched launch: npairs descriptors (`one` unused)
+    int npairs;
+    int n, ncols, nrows, hypotheses, min_inliers;
+    uint32_t seed;
+    double cx, cy;                      // (double)(ncols / 2), (double)(nrows / 2)
+    double t2;                          // (double)max_error * (double)max_error
+    double min_area;
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -365,6 +390,10 @@ int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
 int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
 // per-feature track quality (quality_kernels.hip): one klt_quality record per feature; returns -1 for an unsupported window
 int launch_track_quality(hipStream_t s, const QualityArgs &a);
+// the motion-model check (model_kernels.hip), three launches in stream order: candidates, one score per hypothesis, the decision
+void launch_model_gather(hipStream_t s, const ModelArgs &a);
+void launch_model_score(hipStream_t s, const ModelArgs &a);
+void launch_model_decide(hipStream_t s, const ModelArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

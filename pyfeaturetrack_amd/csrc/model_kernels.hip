@@ -1,0 +1,380 @@
+// Motion-model check (gfx950, wave64): klt_motion_check_async.  Three launches in stream order read two feature lists, find the frame
+// pair's dominant affine motion by a seeded consensus search with one least-squares refit, and turn every tracked feature that does not
+// follow it into (-1, -1, KLT_MODEL_OUTLIER, aux).  Nothing here reads a frame.  THE RULE stands in include/klt_gpu.h ("motion-model
+// check"), word for word what this file computes; DESIGN.md section 9g has it once more with its reasons, tests/model_expected.py is
+// its numpy restatement and the device equals that bit for bit.
+//
+// Everything is FP64 with one rounding per operation in the header's order, `+`, `-` and `*` only: no division, no square root (a model
+// is six numerators and a denominator), and no `/` or `%` by a run-time integer either -- tests/test_host_and_abi.py forbids the FMAs
+// that those expand into.  Every product and sum below is its own statement or parenthesis, and contraction is off.
+//
+//   model_gather_kernel   one workgroup of 16 wavefronts per pair.  A tile of 8192 records is loaded at once (8 rounds of 1024, every load
+//                         in flight together), each wavefront counts its 64 records' candidates by ballot, a two-wavefront scan of the 128 counts
+//                         gives every (round, wavefront) its base, and a candidate's number is base + mbcnt: list order, as the rule asks.
+//                         Writes the centred (p, q) as 32-byte records, (record number, out.aux) beside them, and m.
+//   model_score_kernel    one wavefront per hypothesis, four per workgroup.  The picks and the seven numbers are wave-uniform; lanes stride
+//                         over the candidates (two 16-byte loads each); the count is a ballot's popcount; one int32 score per hypothesis.
+//   model_decide_kernel   one workgroup per pair.  Argmax of a key (score + 1) << 32 | ~h: the largest score, then the smallest h, whatever
+//                         the reduction's order.  Wavefront 0 redoes the best hypothesis and adds the twelve sums -- lane l IS partial l
+//                         of the rule, folded by __shfl_down --, solves by Cramer's rule; then all eight wavefronts test every candidate
+//                         under the final model, scatter the outlier records through the candidate-to-record index (one 16-byte store
+//                         each) and count; thread 0 writes the 80-byte model record.
+// Batched form: blockIdx.y selects the pair from a table in device memory (ModelPair), the mechanism of QualityPair.
+#include "klt_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace model_kernels {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int GATHER_WAVES = 16, GATHER_ROUNDS = 8, GATHER_THREADS = 64 * GATHER_WAVES;
+constexpr int SCORE_WAVES = 4;
+constexpr int DECIDE_THREADS = 512;
+constexpr int SCORE_AHEAD = 4, SUM_AHEAD = 8, FINAL_AHEAD = 4;      // candidates a lane loads before it uses the first: the loops wait for L2, not for arithmetic
+
+template <bool BATCH>
+__device__ __forceinline__ ModelPair pair_of(const ModelArgs &a)
+{
+    if (!BATCH) return a.one;
+    typedef const __attribute__((address_space(4))) ModelPair *cptr;
+    const cptr c = (cptr)(a.pairs + blockIdx.y);
+    ModelPair pr;
+    pr.in = c->in; pr.out = c->out; pr.model = c->model; pr.cand = c->cand; pr.idx = c->idx; pr.scores = c->scores; pr.count = c->count;
+    return pr;
+}
+
+// 0 <= v < limit as f32 comparisons, false for NaN and the infinities
+__device__ __forceinline__ bool inside(float v, int limit) { return v >= 0.f && v < (float)limit; }
+
+__device__ __forceinline__ uint32_t mix(uint32_t x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+// candidate number r_j of hypothesis h among m candidates
+__device__ __forceinline__ int pick(uint32_t seed, uint32_t h, uint32_t j, int m)
+{
+    return (int)__umulhi(mix(seed ^ mix(3u * h + j)), (uint32_t)m);
+}
+
+struct Cand { double px, py, qx, qy; };
+
+__device__ __forceinline__ Cand load_cand(const double *cand, int k)
+{
+    const f64x2 *c = reinterpret_cast<const f64x2 *>(cand) + 2 * (size_t)k;
+    const f64x2 p = c[0], q = c[1];
+    return Cand{p.x, p.y, q.x, q.y};
+}
+
+// U candidates k0 + stride * j + lane_or_thread, j = 0 .. U-1, all loads issued before the first is used; one beyond m is (0, 0, 0, 0), ok[j] false
+template <int U>
+__device__ __forceinline__ void load_ahead(const double *cand, int k0, int stride, int m, Cand (&c)[U], bool (&ok)[U])
+{
+#pragma unroll
+    for (int j = 0; j < U; j++) {
+        const int k = k0 + stride * j;
+        ok[j] = k < m;
+        c[j] = Cand{0., 0., 0., 0.};
+        if (ok[j]) c[j] = load_cand(cand, k);
+    }
+}
+
+struct Model { double nxx, nxy, ntx, nyx, nyy, nty, d; };
+
+// step 3 of the rule: the seven numbers of hypothesis h
+__device__ __forceinline__ Model hypothesis(const ModelPair &pr, uint32_t seed, int h, int m)
+{
+    const Cand c0 = load_cand(pr.cand, pick(seed, (uint32_t)h, 0u, m));
+    const Cand c1 = load_cand(pr.cand, pick(seed, (uint32_t)h, 1u, m));
+    const Cand c2 = load_cand(pr.cand, pick(seed, (uint32_t)h, 2u, m));
+    const double ux = c1.px - c0.px, uy = c1.py - c0.py, vx = c2.px - c0.px, vy = c2.py - c0.py;
+    const double ax = c1.qx - c0.qx, ay = c1.qy - c0.qy, bx = c2.qx - c0.qx, by = c2.qy - c0.qy;
+    Model M;
+    const double d1 = ux * vy, d2 = uy * vx;
+    M.d = d1 - d2;
+    const double xx1 = ax * vy, xx2 = bx * uy, xy1 = bx * ux, xy2 = ax * vx;
+    M.nxx = xx1 - xx2;
+    M.nxy = xy1 - xy2;
+    const double yx1 = ay * vy, yx2 = by * uy, yy1 = by * ux, yy2 = ay * vx;
+    M.nyx = yx1 - yx2;
+    M.nyy = yy1 - yy2;
+    const double tx1 = M.d * c0.qx, tx2 = M.nxx * c0.px, tx3 = M.nxy * c0.py;
+    M.ntx = tx1 - (tx2 + tx3);
+    const double ty1 = M.d * c0.qy, ty2 = M.nyx * c0.px, ty3 = M.nyy * c0.py;
+    M.nty = ty1 - (ty2 + ty3);
+    return M;
+}
+
+// the inlier test of step 3 under a model; thr = (t*t) * (D*D)
+__device__ __forceinline__ bool is_inlier(const Model &M, double thr, const Cand &c)
+{
+    const double x1 = M.nxx * c.px, x2 = M.nxy * c.py, x3 = M.d * c.qx;
+    const double rx = ((x1 + x2) + M.ntx) - x3;
+    const double y1 = M.nyx * c.px, y2 = M.nyy * c.py, y3 = M.d * c.qy;
+    const double ry = ((y1 + y2) + M.nty) - y3;
+    const double ex = rx * rx, ey = ry * ry;
+    return ex + ey <= thr;
+}
+
+__device__ __forceinline__ double threshold(const Model &M, double t2)
+{
+    const double dd = M.d * M.d;
+    return t2 * dd;
+}
+
+// the 64 partials of the rule, one per lane, folded into lane 0 (p[l] += p[l + w], l < w, w = 32 .. 1) and handed to every lane
+__device__ __forceinline__ double fold64(double p)
+{
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) p = p + __shfl_down(p, w);
+    return __shfl(p, 0);
+}
+
+__device__ __forceinline__ int lane_rank(unsigned long long ballot)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
+}
+
+template <bool BATCH>
+__global__ __launch_bounds__(GATHER_THREADS) void model_gather_kernel(ModelArgs a)
+{
+    __shared__ int cnt[GATHER_ROUNDS * GATHER_WAVES], pre[GATHER_ROUNDS * GATHER_WAVES];
+    __shared__ int half_total[2];
+    static_assert(GATHER_ROUNDS * GATHER_WAVES == 128, "the prefix below is two wavefronts wide");
+    const ModelPair pr = pair_of<BATCH>(a);
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int n = a.n, nc = a.ncols, nr = a.nrows;
+    int base = 0;
+    for (int tile = 0; tile < n; tile += GATHER_ROUNDS * GATHER_THREADS) {
+        f32x4 fi[GATHER_ROUNDS], fo[GATHER_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < GATHER_ROUNDS; r++) {
+            const int i = tile + r * GATHER_THREADS + t;
+            const f32x4 lost = {-1.f, -1.f, __int_as_float(-1), 0.f};
+            fi[r] = lost; fo[r] = lost;
+            if (i < n) {
+                fi[r] = *reinterpret_cast<const f32x4 *>(pr.in + i);
+                fo[r] = *reinterpret_cast<const f32x4 *>(pr.out + i);
+            }
+        }
+        int rank[GATHER_ROUNDS];
+        bool ok[GATHER_ROUNDS];
+#pragma unroll
+        for (int r = 0; r < GATHER_ROUNDS; r++) {
+            ok[r] = __float_as_int(fi[r].z) >= 0 && __float_as_int(fo[r].z) == KLT_TRACKED &&
+                    inside(fi[r].x, nc) && inside(fi[r].y, nr) && inside(fo[r].x, nc) && inside(fo[r].y, nr);
+            const unsigned long long b = __ballot(ok[r]);
+            rank[r] = lane_rank(b);
+            if (lane == 0) cnt[r * GATHER_WAVES + w] = __popcll(b);
+        }
+        __syncthreads();
+        if (t < GATHER_ROUNDS * GATHER_WAVES) {              // records of (round, wavefront) e come before those of e + 1: an exclusive prefix,
+            const int v = cnt[t];                            // scanned inside each of the first two wavefronts (whole ones: no divergence)
+            int incl = v;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int u = __shfl_up(incl, o);
+                if (lane >= o) incl += u;
+            }
+            pre[t] = incl - v;
+            if (lane == 63) half_total[w] = incl;
+        }
+        __syncthreads();
+        const int tile_total = half_total[0] + half_total[1];
+#pragma unroll
+        for (int r = 0; r < GATHER_ROUNDS; r++) {
+            if (ok[r]) {
+                const int e = r * GATHER_WAVES + w;
+                const int k = base + pre[e] + (e >= 64 ? half_total[0] : 0) + rank[r];         // k < m <= n
+                const f64x2 p = {(double)fi[r].x - a.cx, (double)fi[r].y - a.cy};
+                const f64x2 q = {(double)fo[r].x - a.cx, (double)fo[r].y - a.cy};
+                f64x2 *c = reinterpret_cast<f64x2 *>(pr.cand) + 2 * (size_t)k;
+                c[0] = p;
+                c[1] = q;
+                const i32x2 id = {tile + r * GATHER_THREADS + t, __float_as_int(fo[r].w)};
+                *(reinterpret_cast<i32x2 *>(pr.idx) + k) = id;
+            }
+        }
+        base += tile_total;
+        __syncthreads();                                     // (cnt, pre and tile_total are rewritten by the next tile)
+    }
+    if (t == 0) *pr.count = base;
+}
+
+template <bool BATCH>
+__global__ __launch_bounds__(64 * SCORE_WAVES) void model_score_kernel(ModelArgs a)
+{
+    const ModelPair pr = pair_of<BATCH>(a);
+    const int lane = threadIdx.x & 63;
+    const int h = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * SCORE_WAVES + (threadIdx.x >> 6)));
+    if (h >= a.hypotheses) return;
+    const int m = *pr.count;
+    if (m < a.min_inliers) return;                           // no model: the decision does not look at the scores
+    const Model M = hypothesis(pr, a.seed, h, m);
+    int score = -1;
+    if (fabs(M.d) >= a.min_area) {                           // (NaN fails)
+        const double thr = threshold(M, a.t2);
+        score = 0;
+        for (int k0 = 0; k0 < m; k0 += 64 * SCORE_AHEAD) {  // (a count: the order of the candidates does not matter)
+            Cand c[SCORE_AHEAD];
+            bool ok[SCORE_AHEAD];
+            load_ahead<SCORE_AHEAD>(pr.cand, k0 + lane, 64, m, c, ok);
+#pragma unroll
+            for (int j = 0; j < SCORE_AHEAD; j++) score += __popcll(__ballot(ok[j] && is_inlier(M, thr, c[j])));
+        }
+    }
+    if (lane == 0) pr.scores[h] = score;
+}
+
+__device__ __forceinline__ void write_model(klt_motion_model *dst, const Model &M, int valid, int m, int n_inliers, int hyp, int hyp_inliers,
+                                            int size)
+{
+    klt_motion_model r;
+    r.nxx = M.nxx; r.nxy = M.nxy; r.ntx = M.ntx; r.nyx = M.nyx; r.nyy = M.nyy; r.nty = M.nty; r.d = M.d;
+    r.valid = valid; r.n_candidates = m; r.n_inliers = n_inliers; r.hypothesis = hyp; r.hypothesis_inliers = hyp_inliers; r.pad = size;
+    *dst = r;
+}
+
+template <bool BATCH>
+__global__ __launch_bounds__(DECIDE_THREADS) void model_decide_kernel(ModelArgs a)
+{
+    __shared__ unsigned long long wave_key[DECIDE_THREADS / 64];
+    __shared__ double final_model[7];
+    __shared__ int final_valid, inlier_count;
+    const ModelPair pr = pair_of<BATCH>(a);
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int m = *pr.count;
+    const int size = (int)((unsigned)a.ncols | (unsigned)a.nrows << 16);
+    const Model none = {0., 0., 0., 0., 0., 0., 0.};
+    if (m < a.min_inliers) {                                 // (uniform over the workgroup, like every return below)
+        if (t == 0) write_model(pr.model, none, 0, m, 0, -1, 0, size);
+        return;
+    }
+    // the best hypothesis: the largest score, ties to the smallest h
+    unsigned long long key = 0;
+    for (int h = t; h < a.hypotheses; h += DECIDE_THREADS) {
+        const unsigned long long k = (unsigned long long)(unsigned)(pr.scores[h] + 1) << 32 | (0xffffffffu - (unsigned)h);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned lo = __shfl_down((unsigned)key, o), hi = __shfl_down((unsigned)(key >> 32), o);
+        const unsigned long long k = (unsigned long long)hi << 32 | lo;
+        key = k > key ? k : key;
+    }
+    if (lane == 0) wave_key[w] = key;
+    if (t == 0) inlier_count = 0;
+    __syncthreads();
+    key = wave_key[0];
+#pragma unroll
+    for (int i = 1; i < DECIDE_THREADS / 64; i++) key = wave_key[i] > key ? wave_key[i] : key;
+    const int best_score = (int)(unsigned)(key >> 32) - 1;
+    const int best = (int)(0xffffffffu - (unsigned)key);
+    if (best_score < a.min_inliers) {
+        if (t == 0) write_model(pr.model, none, 0, m, 0, -1, 0, size);
+        return;
+    }
+    if (w == 0) {
+        const Model H = hypothesis(pr, a.seed, best, m);
+        const double thr = threshold(H, a.t2);
+        double s1 = 0., sx = 0., sy = 0., sxx = 0., sxy = 0., syy = 0., x0 = 0., x1 = 0., x2 = 0., y0 = 0., y1 = 0., y2 = 0.;
+        for (int k0 = 0; k0 < m; k0 += 64 * SUM_AHEAD) {     // lane l: candidates l, l + 64, ... in increasing k
+            Cand cs[SUM_AHEAD];
+            bool ok[SUM_AHEAD];
+            load_ahead<SUM_AHEAD>(pr.cand, k0 + lane, 64, m, cs, ok);
+#pragma unroll
+            for (int j = 0; j < SUM_AHEAD; j++) {
+                const Cand c = cs[j];
+                if (ok[j] && is_inlier(H, thr, c)) {
+                    s1 = s1 + 1.0;
+                    sx = sx + c.px;
+                    sy = sy + c.py;
+                    sxx = sxx + c.px * c.px;
+                    sxy = sxy + c.px * c.py;
+                    syy = syy + c.py * c.py;
+                    x0 = x0 + c.px * c.qx;
+                    x1 = x1 + c.py * c.qx;
+                    x2 = x2 + c.qx;
+                    y0 = y0 + c.px * c.qy;
+                    y1 = y1 + c.py * c.qy;
+                    y2 = y2 + c.qy;
+                }
+            }
+        }
+        s1 = fold64(s1); sx = fold64(sx); sy = fold64(sy); sxx = fold64(sxx); sxy = fold64(sxy); syy = fold64(syy);
+        x0 = fold64(x0); x1 = fold64(x1); x2 = fold64(x2); y0 = fold64(y0); y1 = fold64(y1); y2 = fold64(y2);
+        const double a1 = syy * s1, a2 = sy * sy, b1 = sx * sy, b2 = sxy * s1, e1 = sxy * sy, e2 = sx * syy;
+        const double c00 = a1 - a2, c01 = b1 - b2, c02 = e1 - e2;
+        const double f1 = sxx * s1, f2 = sx * sx, g1 = sxy * sx, g2 = sxx * sy, h1 = sxx * syy, h2 = sxy * sxy;
+        const double c11 = f1 - f2, c12 = g1 - g2, c22 = h1 - h2;
+        const double q1 = sxx * c00, q2 = sxy * c01, q3 = sx * c02;
+        Model R;
+        R.d = (q1 + q2) + q3;
+        { const double u1 = c00 * x0, u2 = c01 * x1, u3 = c02 * x2; R.nxx = (u1 + u2) + u3; }
+        { const double u1 = c01 * x0, u2 = c11 * x1, u3 = c12 * x2; R.nxy = (u1 + u2) + u3; }
+        { const double u1 = c02 * x0, u2 = c12 * x1, u3 = c22 * x2; R.ntx = (u1 + u2) + u3; }
+        { const double u1 = c00 * y0, u2 = c01 * y1, u3 = c02 * y2; R.nyx = (u1 + u2) + u3; }
+        { const double u1 = c01 * y0, u2 = c11 * y1, u3 = c12 * y2; R.nyy = (u1 + u2) + u3; }
+        { const double u1 = c02 * y0, u2 = c12 * y1, u3 = c22 * y2; R.nty = (u1 + u2) + u3; }
+        const bool refit = R.d > 0.;                         // (NaN fails)
+        const Model F = refit ? R : H;
+        if (lane == 0) {
+            final_model[0] = F.nxx; final_model[1] = F.nxy; final_model[2] = F.ntx; final_model[3] = F.nyx; final_model[4] = F.nyy;
+            final_model[5] = F.nty; final_model[6] = F.d;
+            final_valid = refit ? 1 : 2;
+        }
+    }
+    __syncthreads();
+    const Model F = {final_model[0], final_model[1], final_model[2], final_model[3], final_model[4], final_model[5], final_model[6]};
+    const double thr = threshold(F, a.t2);
+    int inliers = 0;
+    for (int k0 = 0; k0 < m; k0 += DECIDE_THREADS * FINAL_AHEAD) {
+        Cand cs[FINAL_AHEAD];
+        bool ok[FINAL_AHEAD];
+        load_ahead<FINAL_AHEAD>(pr.cand, k0 + t, DECIDE_THREADS, m, cs, ok);
+#pragma unroll
+        for (int j = 0; j < FINAL_AHEAD; j++) {
+            const bool inl = ok[j] && is_inlier(F, thr, cs[j]);
+            if (ok[j] && !inl) {
+                const i32x2 id = *(reinterpret_cast<const i32x2 *>(pr.idx) + (k0 + t + DECIDE_THREADS * j));   // id.x < n: written by the gather
+                const f32x4 rec = {-1.f, -1.f, __int_as_float(KLT_MODEL_OUTLIER), __int_as_float(id.y)};
+                *reinterpret_cast<f32x4 *>(pr.out + id.x) = rec;
+            }
+            inliers += __popcll(__ballot(inl));
+        }
+    }
+    if (lane == 0 && inliers) atomicAdd(&inlier_count, inliers);
+    __syncthreads();
+    if (t == 0) write_model(pr.model, F, final_valid, m, inlier_count, best, best_score, size);
+}
+
+template <bool BATCH>
+static void launch_all(hipStream_t s, const ModelArgs &a, int which)
+{
+    const unsigned pairs = BATCH ? (unsigned)a.npairs : 1u;
+    if (which == 0) klt_launch((model_gather_kernel<BATCH>), dim3(1, pairs), dim3(GATHER_THREADS), 0, s, a);
+    if (which == 1)
+        klt_launch((model_score_kernel<BATCH>), dim3((a.hypotheses + SCORE_WAVES - 1) / SCORE_WAVES, pairs), dim3(64 * SCORE_WAVES), 0, s, a);
+    if (which == 2) klt_launch((model_decide_kernel<BATCH>), dim3(1, pairs), dim3(DECIDE_THREADS), 0, s, a);
+}
+
+}  // namespace model_kernels
+
+void launch_model_gather(hipStream_t s, const ModelArgs &a)
+{
+    if (a.pairs) model_kernels::launch_all<true>(s, a, 0); else model_kernels::launch_all<false>(s, a, 0);
+}
+
+void launch_model_score(hipStream_t s, const ModelArgs &a)
+{
+    if (a.pairs) model_kernels::launch_all<true>(s, a, 1); else model_kernels::launch_all<false>(s, a, 1);
+}
+
+void launch_model_decide(hipStream_t s, const ModelArgs &a)
+{
+    if (a.pairs) model_kernels::launch_all<true>(s, a, 2); else model_kernels::launch_all<false>(s, a, 2);
+}

@@ -37,6 +37,7 @@ class kltState:
     KLT_OOB = -4
     KLT_LARGE_RESIDUE = -5
     KLT_FB_INCONSISTENT = -6          # not in the reference: rejected by the forward-backward check (tc.forwardBackwardCheck)
+    KLT_MODEL_OUTLIER = -7            # not in the reference: off the frame pair's dominant affine motion (tc.motionModelCheck)
 
 
 def _pyramidSigma(tc):
@@ -97,6 +98,14 @@ class KLT_TrackingContext:
         # per-feature track quality (not in the reference): True -- KLTTrackFeatures leaves tc.quality_last, KLTTrackSequence's table
         # carries ft.quality: (residue, ncc, min_eig, val) records, val 1 = measured (backend.QUALITY_DTYPE)
         self.trackQuality = False
+        # motion-model check (not in the reference): None, or "affine" -- behind the tracker, a seeded consensus search finds the frame
+        # pair's dominant affine motion among the tracks and every tracked feature that does not follow it within model_max_error px is
+        # lost (KLT_MODEL_OUTLIER); KLTTrackFeatures leaves tc.model_last, KLTTrackSequence's table carries ft.models
+        self.motionModelCheck = None
+        self.model_max_error = 1.0
+        self.model_hypotheses = 256
+        self.model_seed = 0
+        self.model_min_inliers = 8
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -708,6 +717,7 @@ class KLT_FeatureTable:
     y = property(lambda self: self.rec["y"])
     val = property(lambda self: self.rec["val"])
     quality = None            # KLTTrackSequence with tc.trackQuality: [nFrames, nFeatures] records (residue, ncc, min_eig, val)
+    models = None             # KLTTrackSequence with tc.motionModelCheck: [nFrames] backend.MODEL_DTYPE records, row 0 all zero
 
     def feature(self, feat, frame):
         return _feature_of(self.rec[frame, feat])

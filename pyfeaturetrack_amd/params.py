@@ -1,7 +1,7 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import numpy as np
 
-from ._abi import KltAffineParams, KltFbParams, KltLightParams, KltParams
+from ._abi import KltAffineParams, KltFbParams, KltLightParams, KltModelParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -98,6 +98,43 @@ def light_params_from_tc(tc, guess=False, sequence=False):
             if on:
                 raise ValueError("lightingCompensation and {0} cannot be used together".format(what))
     return lp
+
+
+MOTION_MODEL_CHECKS = (None, "affine")
+
+
+def model_params_from_tc(tc, ncols=None, nrows=None):
+    """tc.motionModelCheck / tc.model_max_error / tc.model_hypotheses / tc.model_seed / tc.model_min_inliers (and tc.model_min_area, 1.0
+    px^2 unless set) -> klt_model_params for a frame of ncols x nrows: None (the default) packs mode 0, "affine" mode 1.  All are read
+    with defaults: a tracking context made elsewhere has none of them.  ValueError -- before any device work -- for another value, for the
+    check together with tc.affineConsistencyCheck >= 0 (that check keeps per-feature state keyed on loss), and for parameters
+    klt_set_model_params would refuse."""
+    mode = getattr(tc, "motionModelCheck", None)
+    if not isinstance(mode, (str, type(None))) or mode not in MOTION_MODEL_CHECKS:
+        raise ValueError("tc.motionModelCheck must be None or 'affine' (got {0!r})".format(mode))
+    mp = KltModelParams()
+    mp.mode = 0 if mode is None else 1
+    mp.ncols, mp.nrows = int(ncols or 0), int(nrows or 0)
+    if not mp.mode:
+        mp.hypotheses, mp.seed, mp.min_inliers, mp.max_error, mp.min_area = 256, 0, 8, 1.0, 1.0
+        return mp
+    if getattr(tc, "affineConsistencyCheck", -1) >= 0:
+        raise ValueError("motionModelCheck and affineConsistencyCheck cannot both be switched on")
+    hyp, seed = int(getattr(tc, "model_hypotheses", 256)), int(getattr(tc, "model_seed", 0))
+    inl = int(getattr(tc, "model_min_inliers", 8))
+    err, area = float(getattr(tc, "model_max_error", 1.0)), float(getattr(tc, "model_min_area", 1.0))
+    if not 1 <= hyp <= 65536:
+        raise ValueError("tc.model_hypotheses must lie in 1 .. 65536 (got {0})".format(hyp))
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError("tc.model_seed must lie in 0 .. 2**32 - 1 (got {0})".format(seed))
+    if inl < 3:
+        raise ValueError("tc.model_min_inliers must be at least 3 (got {0})".format(inl))
+    if not err >= 0.0 or not area >= 0.0:
+        raise ValueError("tc.model_max_error and tc.model_min_area must be numbers >= 0")
+    if ncols is not None and not (1 <= mp.ncols <= 65535 and 1 <= mp.nrows <= 65535):
+        raise ValueError("the motion-model check takes frames of 1 .. 65535 columns and rows")
+    mp.hypotheses, mp.seed, mp.min_inliers, mp.max_error, mp.min_area = hyp, seed, inl, err, area
+    return mp
 
 
 def guess_records(guess, n, affine=False):

@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import fb_params_from_tc, guess_records, light_params_from_tc
+from .params import fb_params_from_tc, guess_records, light_params_from_tc, model_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -394,7 +394,12 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     tc.trackQuality = True (not in the reference): tc.quality_last is then a backend.QUALITY_DTYPE array of len(featurelist) -- residue,
     ncc, min_eig and val (1 = measured) of every feature between the position the list held on entry and the one it holds on return,
     taken after the forward-backward or affine check if one ran: one more launch, one more download of 16 bytes
-    per feature."""
+    per feature.
+    tc.motionModelCheck = "affine" (not in the reference): behind the tracker (and its forward-backward check) the frame pair's dominant
+    affine motion is found among the tracks and every tracked feature further than tc.model_max_error px from it comes back lost, as
+    (-1, -1, KLT_MODEL_OUTLIER); tc.model_last is then a dict A (2x2), t, valid, candidates, inliers, hypothesis.
+    Works with `guess=`, tc.forwardBackwardCheck, tc.lightingCompensation and tc.trackQuality (a flagged record is not measured);
+    ValueError together with tc.affineConsistencyCheck >= 0, for another value and for parameters out of range."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -402,6 +407,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     fb_params_from_tc(tc)                             # (ValueError for the forward-backward and the affine check together, before any device work)
     light_params_from_tc(tc, guess=guess is not None)      # (ValueError for lightingCompensation with a check, a prior or a guess, likewise)
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
+    model_params_from_tc(tc)                          # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -428,6 +434,13 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         # by the feature list object.
         state = _affine_state_of(tc, ctx, featurelist)
     ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check, guess=guess)
+    # tc.motionModelCheck: three more launches behind the tracker (and its forward-backward check), on the tracker's own two feature
+    # buffers -- the output list is rewritten in place -- and in front of the quality launch: a flagged record is then simply unmeasured
+    model = model_params_from_tc(tc, ncols, nrows)
+    if model.mode:
+        from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_MODEL
+        ctx.set_model_params(model)
+        ctx.motion_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_MODEL, nfeat)
     # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
     # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
     quality = bool(getattr(tc, "trackQuality", False))
@@ -444,6 +457,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
             again = True
     if again:
         ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check, guess=guess)
+        if model.mode:
+            ctx.motion_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_MODEL, nfeat)
         if quality:
             ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
@@ -463,6 +478,9 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
     if quality:                                       # one more download of 16 bytes per feature
         from .backend import QUALITY_DTYPE
         tc.quality_last = ctx.quality_download(_FB_API_QUALITY, nfeat) if nfeat else np.zeros(0, QUALITY_DTYPE)
+    if model.mode:                                    # one more download of 80 bytes
+        from .backend import MODEL_DTYPE, model_summary
+        tc.model_last = model_summary(ctx.model_download(_FB_API_MODEL) if nfeat else np.zeros(1, MODEL_DTYPE)[0])
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

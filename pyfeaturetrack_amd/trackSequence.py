@@ -18,6 +18,7 @@ _FB_TABLE = 60000            # feature-buffer ids used by this module: the table
 _FB_ROW0 = 60001
 _FB_GUESS = 65525            # ... and the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
 _FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality records, laid out like the feature table (below _FB_TABLE)
+_FBM_TABLE = 48000           # tc.motionModelCheck: a parallel table of model records, five feature records per frame (below _FBQ_TABLE)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -150,6 +151,9 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     never leave the device); a feature the last step lost or replaced starts at its own position.  Not together with the affine check.
     tc.trackQuality = True: the table carries `ft.quality`, a [frames][features] array of backend.QUALITY_DTYPE records -- row k measured between
     rows k - 1 and k as the tracker left them (before the replacement pass: a refilled slot is not measured), row 0 all val = 0.
+    tc.motionModelCheck = "affine": one motion-model check per frame behind the tracker and in front of that frame's replacement pass, which
+    refills the slots it flagged (KLT_MODEL_OUTLIER); `ft.models` holds one backend.MODEL_DTYPE record per frame, row 0 all zero.  Not
+    together with the affine consistency check.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
@@ -162,6 +166,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
     from .params import light_params_from_tc
     light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
+    from .params import model_params_from_tc
+    model_params_from_tc(tc)             # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -219,6 +225,22 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                 ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
             qtables.append(base)
         return qtables[ci] + 1 + off
+
+    from .params import model_params_from_tc
+    model = model_params_from_tc(tc, ncols, nrows)       # the same check behind every tracker launch, its record into a table of its own
+    if model.mode:
+        ctx.set_model_params(model)
+    mtables = []
+
+    def mrow_fb(k):
+        ci, off = divmod(k, chunk)
+        if ci == len(mtables):
+            base = _FBM_TABLE + ci * (chunk + 1)
+            ctx.featbuf_alloc(base, chunk * 5)
+            for j in range(chunk):
+                ctx.featbuf_view(base + 1 + j, base, j * 5, 5)
+            mtables.append(base)
+        return mtables[ci] + 1 + off
 
     workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
     # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
@@ -295,6 +317,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                     ctx.track_fb_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
                 else:
                     ctx.track_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
+                if model.mode:                       # wherever the tracker goes, in front of the quality launch and of frame j's select_begin
+                    ctx.motion_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
                 if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
                     ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
@@ -400,6 +424,18 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
             ctx.featbuf_download_into(base, rec[lo:hi])
         ft.quality = rec.view(QUALITY_DTYPE)
         ft.quality[0] = 0                                        # nothing was tracked into the first frame
+    if model.mode:
+        from .backend import FEAT_DTYPE, MODEL_DTYPE
+        rec = np.zeros((nframes, 5), FEAT_DTYPE)
+        for ci, base in enumerate(mtables):
+            lo = ci * chunk
+            hi = min(nframes, lo + chunk)
+            if hi > lo:
+                ctx.featbuf_download_into(base, rec[lo:hi])
+        ft.models = rec.view(MODEL_DTYPE).reshape(nframes)
+        if nFeatures == 0:
+            ft.models[:] = np.zeros(1, MODEL_DTYPE)[0]           # (no list, no launch: nothing was written)
+        ft.models[0] = np.zeros(1, MODEL_DTYPE)[0]               # nothing was tracked into the first frame
     if tc.sequentialMode:
         # leave the context as the per-frame API would: the last frame's pyramids are "frame 1" of the next call
         from .trackFeatures import _pyramid_handles
