@@ -35,8 +35,9 @@ REPLACING_SOME = 2
 # the reference-shaped API's tracker reads and writes its pinned record arrays in place (klt_featbuf_map_host); KLT_MAP_RECORDS=0 in
 # the environment goes back to one copy command each way
 MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
-# feature buffers of the reference-shaped API (65534 / 65535 are the staging buffers of the synchronous klt_track / klt_select entry
-# points, 65533 the API's selection list, 60000 .. 65524 KLTTrackSequence's table rows)
+# feature buffers of the reference-shaped API (the library keeps 65530 .. 65532, 65534 and 65535 for itself: the staging buffers of its
+# synchronous entry points -- klt_track*, klt_select, klt_track_quality, klt_motion_check; 65533 is the API's selection list,
+# 60000 .. 65524 KLTTrackSequence's table rows)
 _FB_API_IN, _FB_API_OUT = 65526, 65527
 _FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
 _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
@@ -46,6 +47,11 @@ _FB_API_QUALITY = 59999              # quality records of a KLTTrackFeatures cal
 
 def _dp(a):
     return (C.c_double * len(a))(*a)
+
+
+def _columns(pairs, count):
+    """the first `count` columns of a `pairs` list as c_int arrays: what a batched entry point takes"""
+    return [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(count)]
 
 
 class Context:
@@ -160,7 +166,7 @@ class Context:
     def track_fb_batch_async(self, pairs, n):
         """pairs: [(slot1, slot2, fb_in, fb_out[, fb_back]), ...] -- one forward-backward launch for all of them; without any fb_back
         no backward records are kept."""
-        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(4)]
+        cols = _columns(pairs, 4)
         back = None
         if any(len(p) > 4 for p in pairs):
             back = (C.c_int * len(pairs))(*[p[4] if len(p) > 4 else -1 for p in pairs])
@@ -185,7 +191,7 @@ class Context:
 
     def track_guess_batch_async(self, pairs, n):
         """pairs: [(slot1, slot2, fb_in, fb_guess, fb_out), ...] -- one launch for all of them; fb_guess -1: that pair has no guess."""
-        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(5)]
+        cols = _columns(pairs, 5)
         self._check(self._lib.klt_track_guess_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], cols[4], len(pairs), n))
 
     def predict_cv_async(self, fb_prev, fb_cur, fb_guess, n):
@@ -718,7 +724,7 @@ class Context:
 
     def track_batch_async(self, pairs, n):
         """pairs: [(slot1, slot2, fb_in, fb_out), ...] -- one tracker launch for all of them."""
-        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(4)]
+        cols = _columns(pairs, 4)
         self._check(self._lib.klt_track_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], len(pairs), n))
 
     # ------------------------------------------------ per-feature track quality (klt_track_quality*)
@@ -738,7 +744,7 @@ class Context:
 
     def track_quality_batch_async(self, pairs, n):
         """pairs: [(slot1, slot2, fb_in, fb_out, fb_quality), ...] -- one quality launch for all of them."""
-        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(5)]
+        cols = _columns(pairs, 5)
         self._check(self._lib.klt_track_quality_batch_async(self._h, cols[0], cols[1], cols[2], cols[3], cols[4], len(pairs), n))
 
     def quality_download(self, fb, n):
@@ -777,7 +783,7 @@ class Context:
 
     def motion_check_batch_async(self, pairs, n):
         """pairs: [(fb_in, fb_out, fb_model), ...] -- the check's launches once for all of them."""
-        cols = [(C.c_int * len(pairs))(*[p[k] for p in pairs]) for k in range(3)]
+        cols = _columns(pairs, 3)
         self._check(self._lib.klt_motion_check_batch_async(self._h, cols[0], cols[1], cols[2], len(pairs), n))
 
     def motion_check_path(self):

@@ -46,7 +46,7 @@ static int gather_common(klt_ctx *c, int fb_src, int fb_dst, int n, int root /* 
     if (!c) return KLT_ERR_ARG;
     if (!c->comm) return fail(c, KLT_ERR_STATE, "klt_comm_init_rank has not been called");
     if (n <= 0 || fb_src == fb_dst) return fail(c, KLT_ERR_ARG, "bad gather arguments");
-    if (fb_src < 0 || (size_t)fb_src >= c->fbs.size() || c->fbs[fb_src].cap < n) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
+    if (!fb_holds(c, fb_src, n)) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
     HIPCHK(c, hipSetDevice(c->device));
     const int nranks = comm_nranks(c->comm), rank = comm_rank(c->comm);
     const bool need_dst = root < 0 || rank == root;
@@ -85,7 +85,7 @@ int klt_gatherv_featbuf_async(klt_ctx *c, int fb_src, int fb_dst, const int *cou
     }
     if (total <= 0 || total > 0x7fffffffLL) return fail(c, KLT_ERR_ARG, "gathered table empty or too large");
     const int n = counts[rank];
-    if (n > 0 && (fb_src < 0 || (size_t)fb_src >= c->fbs.size() || c->fbs[fb_src].cap < n)) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
+    if (n > 0 && !fb_holds(c, fb_src, n)) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
     HIPCHK(c, hipSetDevice(c->device));
     klt_feat *dst = nullptr;
     if (rank == root) {
@@ -112,7 +112,7 @@ int klt_comm_set_timeout(klt_ctx *c, double ms)
 int klt_comm_fence_featbuf_async(klt_ctx *c, int fb)
 {
     if (!c) return KLT_ERR_ARG;
-    if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].comm_done) return KLT_OK;
+    if (!fb_holds(c, fb, 0) || !c->fbs[fb].comm_done) return KLT_OK;
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->fbs[fb].comm_done, 0));
     return KLT_OK;
 }
@@ -143,7 +143,7 @@ int klt_sendrecv_featbuf_async(klt_ctx *c, int fb_send, int to, int fb_recv, int
     }
     const klt_feat *src = nullptr;
     if (to >= 0) {
-        if (fb_send < 0 || (size_t)fb_send >= c->fbs.size() || c->fbs[fb_send].cap < n) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
+        if (!fb_holds(c, fb_send, n)) return fail(c, KLT_ERR_STATE, "source feature buffer not that large");
         src = c->fbs[fb_send].d;
     }
     std::string err;

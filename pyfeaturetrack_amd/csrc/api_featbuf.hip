@@ -36,7 +36,7 @@ int klt_featbuf_upload_async(klt_ctx *c, int fb, const klt_feat *src, int n)
 int klt_featbuf_download(klt_ctx *c, int fb, klt_feat *dst, int n)
 {
     if (!c || !dst || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
-    if (fb < 0 || (size_t)fb >= c->fbs.size() || c->fbs[fb].cap < n) return fail(c, KLT_ERR_STATE, "feature buffer not that large");
+    if (!fb_holds(c, fb, n)) return fail(c, KLT_ERR_STATE, "feature buffer not that large");
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = klt_comm_fence_async(c)) return rc;        // a gathered table is complete before it is read back
     HIPCHK(c, hipMemcpyAsync(dst, c->fbs[fb].d, (size_t)n * sizeof(klt_feat), down(c->fbs[fb]), c->stream));
@@ -52,7 +52,7 @@ int klt_featbuf_download(klt_ctx *c, int fb, klt_feat *dst, int n)
 int klt_featbuf_download_async(klt_ctx *c, int fb, klt_feat *dst, int n)
 {
     if (!c || !dst || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
-    if (fb < 0 || (size_t)fb >= c->fbs.size() || c->fbs[fb].cap < n) return fail(c, KLT_ERR_STATE, "feature buffer not that large");
+    if (!fb_holds(c, fb, n)) return fail(c, KLT_ERR_STATE, "feature buffer not that large");
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t attr;                           // a pageable destination would be staged synchronously
     if (hipPointerGetAttributes(&attr, dst) != hipSuccess || attr.type != hipMemoryTypeHost) {
@@ -112,7 +112,7 @@ int klt_featbuf_alloc(klt_ctx *c, int fb, int n)
 int klt_featbuf_view(klt_ctx *c, int fb_view, int fb_parent, int offset, int n)
 {
     if (!c || offset < 0 || n <= 0 || fb_view == fb_parent) return fail(c, KLT_ERR_ARG, "bad argument");
-    if (fb_parent < 0 || (size_t)fb_parent >= c->fbs.size() || c->fbs[fb_parent].cap < offset + n || c->fbs[fb_parent].view)
+    if (!fb_holds(c, fb_parent, offset + n) || c->fbs[fb_parent].view)
         return fail(c, KLT_ERR_STATE, "parent feature buffer too small (or itself a view)");
     if (fb_view < 0 || fb_view > 65535) return fail(c, KLT_ERR_ARG, "feature buffer index out of range");
     if ((size_t)fb_view >= c->fbs.size()) c->fbs.resize(fb_view + 1);
@@ -155,7 +155,7 @@ int klt_featbuf_map_host(klt_ctx *c, int fb, klt_feat *host, int n)
 
 void *klt_featbuf_devptr(klt_ctx *c, int fb)
 {
-    if (!c || fb < 0 || (size_t)fb >= c->fbs.size()) return nullptr;
+    if (!c || !fb_holds(c, fb, 0)) return nullptr;
     return c->fbs[fb].d;
 }
 

@@ -1,11 +1,7 @@
 // api_model.hip -- the motion-model check (not in the reference): parameters, the single-pair, batched and
 // synchronous entry points, and the host-side division that turns a model record into an affine map.  The rule stands in
 // include/klt_gpu.h, the kernels in model_kernels.hip.
-#include <cmath>
-
 #include "klt_context.h"
-
-using namespace kltapi;
 
 // a pair's slice of the context's scratch: candidates (32 bytes each), their record numbers and aux (8 bytes each), one score per
 // hypothesis, the candidate count; a multiple of 256 bytes
@@ -48,10 +44,10 @@ static int model_off(klt_ctx *c)
     return fail(c, KLT_ERR_STATE, "the motion-model check is off (klt_set_model_params mode 0)");
 }
 
-static bool list_ok(const klt_ctx *c, int fb, int n)
-{
-    return fb >= 0 && (size_t)fb < c->fbs.size() && c->fbs[fb].d && c->fbs[fb].cap >= n;
-}
+static const char *const kModelNoBuffer = "fb_model must be a feature buffer";
+static const char *const kPairwiseDistinct = "fb_in, fb_out and fb_model must be pairwise distinct";
+static const char *const kModelNotDistinct = "every fb_model must be distinct from every list and from each other";
+static const char *const kOutNotDistinct = "every fb_out must be distinct from every other list";
 
 extern "C" {
 
@@ -79,16 +75,14 @@ int klt_motion_check_async(klt_ctx *c, int fb_in, int fb_out, int fb_model, int 
 {
     if (!c) return KLT_ERR_ARG;
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
-    if (fb_model < 0 || fb_model > 65535) return fail(c, KLT_ERR_ARG, "fb_model must be a feature buffer");
-    if (fb_model == fb_in || fb_model == fb_out || fb_in == fb_out) return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
+    if (int rc = own_index(c, fb_model, {fb_in, fb_out}, kModelNoBuffer, kPairwiseDistinct)) return rc;
+    if (fb_in == fb_out) return fail(c, KLT_ERR_ARG, kPairwiseDistinct);
     if (c->modelp.mode == 0) return model_off(c);
     if (n == 0) return KLT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!list_ok(c, fb_in, n) || !list_ok(c, fb_out, n)) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
-    if (c->fbs[fb_in].d == c->fbs[fb_out].d) return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
-    if ((size_t)fb_model < c->fbs.size() && c->fbs[fb_model].d &&
-        (c->fbs[fb_model].d == c->fbs[fb_in].d || c->fbs[fb_model].d == c->fbs[fb_out].d))          // a view can be a second name of the same records
-        return fail(c, KLT_ERR_ARG, "fb_in, fb_out and fb_model must be pairwise distinct");
+    if (int rc = lists_set(c, {fb_in, fb_out}, n)) return rc;
+    if (c->fbs[fb_in].d == c->fbs[fb_out].d) return fail(c, KLT_ERR_ARG, kPairwiseDistinct);
+    if (int rc = own_records(c, fb_model, {fb_in, fb_out}, kPairwiseDistinct)) return rc;
     if (int rc = ensure(c, c->model_scratch, c->model_scratch_cap, model_slice_bytes(n, c->modelp.hypotheses))) return rc;
     FeatBuf *bm;                                             // (may grow c->fbs: before any pointer into it is taken)
     if (int rc = get_fb(c, fb_model, 5, &bm)) return rc;
@@ -109,30 +103,22 @@ int klt_motion_check_batch_async(klt_ctx *c, const int *fb_in, const int *fb_out
     if (!c) return KLT_ERR_ARG;
     if (!fb_in || !fb_out || !fb_model || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
     // a model record that another pair of the launch reads as a list, a list that another pair rewrites: by index first ...
-    for (int i = 0; i < npairs; i++) {
-        if (fb_model[i] < 0 || fb_model[i] > 65535) return fail(c, KLT_ERR_ARG, "fb_model must be a feature buffer");
+    for (int i = 0; i < npairs; i++)
         for (int j = 0; j < npairs; j++) {
-            if (fb_model[i] == fb_in[j] || fb_model[i] == fb_out[j] || (i != j && fb_model[i] == fb_model[j]))
-                return fail(c, KLT_ERR_ARG, "every fb_model must be distinct from every list and from each other");
-            if (fb_out[i] == fb_in[j] || (i != j && fb_out[i] == fb_out[j]))
-                return fail(c, KLT_ERR_ARG, "every fb_out must be distinct from every other list");
+            if (int rc = own_index(c, fb_model[i], {fb_in[j], fb_out[j], i != j ? fb_model[j] : -1}, kModelNoBuffer, kModelNotDistinct)) return rc;
+            if (fb_out[i] == fb_in[j] || (i != j && fb_out[i] == fb_out[j])) return fail(c, KLT_ERR_ARG, kOutNotDistinct);
         }
-    }
     if (c->modelp.mode == 0) return model_off(c);
     if (n == 0) return KLT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < npairs; i++)
-        if (!list_ok(c, fb_in[i], n) || !list_ok(c, fb_out[i], n)) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
-    // ... then by address: a view can be a second name of the same records (a buffer that does not exist yet is nobody's second name)
+        if (int rc = lists_set(c, {fb_in[i], fb_out[i]}, n)) return rc;
+    // ... then by address
     for (int i = 0; i < npairs; i++) {
-        const klt_feat *mi = (size_t)fb_model[i] < c->fbs.size() ? c->fbs[fb_model[i]].d : nullptr;
         const klt_feat *oi = c->fbs[fb_out[i]].d;
         for (int j = 0; j < npairs; j++) {
-            const klt_feat *mj = (size_t)fb_model[j] < c->fbs.size() ? c->fbs[fb_model[j]].d : nullptr;
-            if (mi && (mi == c->fbs[fb_in[j]].d || mi == c->fbs[fb_out[j]].d || (i != j && mi == mj)))
-                return fail(c, KLT_ERR_ARG, "every fb_model must be distinct from every list and from each other");
-            if (oi == c->fbs[fb_in[j]].d || (i != j && oi == c->fbs[fb_out[j]].d))
-                return fail(c, KLT_ERR_ARG, "every fb_out must be distinct from every other list");
+            if (int rc = own_records(c, fb_model[i], {fb_in[j], fb_out[j], i != j ? fb_model[j] : -1}, kModelNotDistinct)) return rc;
+            if (oi == c->fbs[fb_in[j]].d || (i != j && oi == c->fbs[fb_out[j]].d)) return fail(c, KLT_ERR_ARG, kOutNotDistinct);
         }
     }
     if (int rc = ensure(c, c->model_scratch, c->model_scratch_cap, (size_t)npairs * model_slice_bytes(n, c->modelp.hypotheses))) return rc;
@@ -147,17 +133,9 @@ int klt_motion_check_batch_async(klt_ctx *c, const int *fb_in, const int *fb_out
         table[i].model = reinterpret_cast<klt_motion_model *>(c->fbs[fb_model[i]].d);
         fill_model_scratch(c, i, n, table[i]);
     }
-    // the table goes up only when it differs from the one the device holds (pageable source: the runtime stages it before returning;
-    // stream order protects the launch that read the replaced table)
-    if (c->model_host.size() != table.size() || std::memcmp(c->model_host.data(), table.data(), table.size() * sizeof(ModelPair)) != 0) {
-        c->model_host.clear();                               // (nothing is known of the device's copy until the new one is enqueued)
-        if (int rc = ensure(c, c->model_dev, c->model_cap, (size_t)npairs)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->model_dev, table.data(), (size_t)npairs * sizeof(ModelPair), hipMemcpyHostToDevice, c->stream));
-        c->model_host = table;
-    }
     ModelArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.pairs = c->model_dev;
+    if (int rc = send_if_changed(c, c->model_table, table, &a.pairs)) return rc;
     a.npairs = npairs;
     fill_model_args(c, n, a);
     if (int rc = enqueue_model(c, a, npairs)) return rc;
@@ -171,17 +149,16 @@ int klt_motion_check(klt_ctx *c, const klt_feat *in, klt_feat *out, klt_motion_m
     if (!c || !in || !out || !model) return fail(c, KLT_ERR_ARG, "null argument");
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
     if (c->modelp.mode == 0) return model_off(c);
-    const int fi = 65534, fo = 65535, fm = 65530;
     std::memset(model, 0, sizeof(*model));
     if (n_outliers) *n_outliers = 0;
     if (n == 0) return KLT_OK;
     int before = 0;
     for (int i = 0; i < n; i++) before += out[i].val == KLT_MODEL_OUTLIER;
-    if (int rc = klt_featbuf_upload_async(c, fi, in, n)) return rc;         // (the downloads below synchronise: both lists are ours until then)
-    if (int rc = klt_featbuf_upload_async(c, fo, out, n)) return rc;
-    if (int rc = klt_motion_check_async(c, fi, fo, fm, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fo, out, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fm, reinterpret_cast<klt_feat *>(model), 5)) return rc;
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncIn, in, n)) return rc;      // (the downloads below synchronise: both lists are ours until then)
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncOut, out, n)) return rc;
+    if (int rc = klt_motion_check_async(c, kFbSyncIn, kFbSyncOut, kFbSyncOwn, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOut, out, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOwn, reinterpret_cast<klt_feat *>(model), 5)) return rc;
     if (n_outliers) {
         int after = 0;
         for (int i = 0; i < n; i++) after += out[i].val == KLT_MODEL_OUTLIER;

@@ -691,10 +691,9 @@ int klt_select_async(klt_ctx *c, int slot, int mode, int use_pyramid, int fb, in
 int klt_select(klt_ctx *c, int slot, int mode, int use_pyramid, klt_feat *inout, int n, int *n_placed)
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
-    const int fb = 65535;       // private staging buffer
-    if (int rc = klt_featbuf_upload(c, fb, inout, n)) return rc;
-    if (int rc = klt_select_async(c, slot, mode, use_pyramid, fb, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fb, inout, n)) return rc;
+    if (int rc = klt_featbuf_upload(c, kFbSyncOut, inout, n)) return rc;
+    if (int rc = klt_select_async(c, slot, mode, use_pyramid, kFbSyncOut, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOut, inout, n)) return rc;
     if (n_placed) {
         HIPCHK(c, hipMemcpy(n_placed, c->placed_d, sizeof(int), hipMemcpyDeviceToHost));
     }
@@ -723,7 +722,7 @@ int klt_min_distance_walk(klt_ctx *c, const uint64_t *keys, int nkeys, int ncols
         }
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const int fb = 65535;                                  // the synchronous entry points' staging buffer
+    const int fb = kFbSyncOut;
     if (int rc = klt_featbuf_upload(c, fb, inout, n)) return rc;
     if (int rc = ensure(c, c->keys2, c->keys2_cap, (size_t)nkeys + 1)) return rc;
     if (nkeys) HIPCHK(c, hipMemcpyAsync(c->keys2, keys, (size_t)nkeys * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));

@@ -1,5 +1,6 @@
 // api_track.hip -- the tracker (trackFeatures.py:205-409): single-pair and batched launches with their XCD-aware feature orders, the
-// affine consistency check and its per-feature state, the iteration counters behind the roofline figures.
+// constant-velocity prediction, the iteration counters behind the roofline figures; and what every launch on a frame pair shares
+// (klt_context.h lists it).  The kernels: track_kernels.hip, track_light_kernels.hip.
 #include "klt_context.h"
 
 // The caches of feature orders and descriptor tables: the entry that `match` accepts, or null ...
@@ -25,6 +26,63 @@ static Entry *cache_place(std::vector<Entry> &v, size_t capacity)
         if (e.used < lru->used) lru = &e;
     return lru;
 }
+
+namespace kltapi {
+
+int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2)
+{
+    if (int rc = get_slot(c, slot1, p1, false)) return rc;
+    if (int rc = get_slot(c, slot2, p2, false)) return rc;
+    Slot *s1 = *p1, *s2 = *p2;
+    if (!s1->pyr_valid || !s2->pyr_valid) return fail(c, KLT_ERR_STATE, "pyramids of both slots must be built before tracking");
+    if (int rc = wait_built(c, s1)) return rc;
+    if (int rc = wait_built(c, s2)) return rc;
+    if (s1->nc != s2->nc || s1->nr != s2->nr || s1->nlev != s2->nlev || s1->ss != s2->ss)
+        return fail(c, KLT_ERR_ARG, "the two frames differ in size");            // trackFeatures.py:156-159, :217
+    return 0;
+}
+
+void level_planes(const Slot *s1, const Slot *s2, int l, const float *&i1, const float *&gx1, const float *&gy1, const float *&i2,
+                  const float *&gx2, const float *&gy2)
+{
+    i1 = s1->lv[l].img; gx1 = s1->lv[l].gx; gy1 = s1->lv[l].gy;
+    i2 = s2->lv[l].img; gx2 = s2->lv[l].gx; gy2 = s2->lv[l].gy;
+}
+
+// gain / bias tracking is offered by klt_track, klt_track_async and klt_track_batch_async alone: every other tracker entry point is refused
+// while it is switched on, before anything is enqueued
+int refuse_with_light(klt_ctx *c, const char *what)
+{
+    if (!c || !c->lightp.mode) return 0;
+    return fail(c, KLT_ERR_STATE, std::string(what) + " is not offered together with lighting compensation (klt_set_light_params mode 1)");
+}
+
+int count_live(const klt_feat *f, int n)
+{
+    int k = 0;
+    for (int i = 0; i < n; i++) k += f[i].val >= 0;
+    return k;
+}
+
+int batch_arguments(klt_ctx *c, std::initializer_list<const int *> columns, int npairs, int n)
+{
+    const bool null_column = std::count(columns.begin(), columns.end(), nullptr) > 0;
+    return null_column || npairs <= 0 || npairs > 65535 || n < 0 ? fail(c, KLT_ERR_ARG, "bad argument") : 0;
+}
+
+int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used)
+{
+    Slot *s1, *s2;
+    if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
+    used.push_back(s1);
+    used.push_back(s2);
+    const Slot *first = used[0];
+    if (s1->nc != first->nc || s1->nr != first->nr || (same_levels && s1->nlev != first->nlev))
+        return fail(c, KLT_ERR_ARG, "all pairs of a batch must have the same frame size");
+    return 0;
+}
+
+}  // namespace kltapi
 
 extern "C" {
 
@@ -87,27 +145,6 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
     return 0;
 }
 
-static int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2)
-{
-    if (int rc = get_slot(c, slot1, p1, false)) return rc;
-    if (int rc = get_slot(c, slot2, p2, false)) return rc;
-    Slot *s1 = *p1, *s2 = *p2;
-    if (!s1->pyr_valid || !s2->pyr_valid) return fail(c, KLT_ERR_STATE, "pyramids of both slots must be built before tracking");
-    if (int rc = wait_built(c, s1)) return rc;
-    if (int rc = wait_built(c, s2)) return rc;
-    if (s1->nc != s2->nc || s1->nr != s2->nr || s1->nlev != s2->nlev || s1->ss != s2->ss)
-        return fail(c, KLT_ERR_ARG, "the two frames differ in size");            // trackFeatures.py:156-159, :217
-    return 0;
-}
-
-// the six planes of level l of a frame pair
-static void level_planes(const Slot *s1, const Slot *s2, int l, const float *&i1, const float *&gx1, const float *&gy1, const float *&i2,
-                         const float *&gx2, const float *&gy2)
-{
-    i1 = s1->lv[l].img; gx1 = s1->lv[l].gx; gy1 = s1->lv[l].gy;
-    i2 = s2->lv[l].img; gx2 = s2->lv[l].gx; gy2 = s2->lv[l].gy;
-}
-
 static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv)
 {
     for (int l = 0; l < s1->nlev; l++) {
@@ -126,25 +163,19 @@ static int check_fb_buffers(klt_ctx *c, int fb_in, int fb_out, int fb_back)
 }
 
 // what a launch with a motion prior asks of a pair's guess list (klt_track_guess*): a feature buffer of its own next to the ones the
-// launch writes -- by index and by address, a view can be a second name of the same records.  (It may be fb_in: every feature's guess
-// is then its own position.)
+// launch writes (own_index; fb_back: a buffer or -1).  (It may be fb_in: every feature's guess is then its own position.)
+static const char *const kGuessNotDistinct = "fb_guess must be distinct from fb_out and fb_back";
 static int check_guess_buffer(klt_ctx *c, int fb_guess, int fb_out, int fb_back)
 {
-    if (fb_guess < 0 || fb_guess > 65535) return fail(c, KLT_ERR_ARG, "fb_guess must be a feature buffer");
-    if (fb_guess == fb_out || fb_guess == fb_back) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
-    return 0;
+    return own_index(c, fb_guess, {fb_out, fb_back}, "fb_guess must be a feature buffer", kGuessNotDistinct);
 }
 
-// ... once the launch's own buffers exist: the guess list holds n records and shares no memory with them
+// ... once the launch's own buffers exist: the guess list holds n records and shares no memory with them (own_records)
 static int guess_records(klt_ctx *c, int fb_guess, int fb_out, int fb_back, int n, const klt_feat **guess)
 {
-    if ((size_t)fb_guess >= c->fbs.size() || !c->fbs[fb_guess].d || c->fbs[fb_guess].cap < n)
-        return fail(c, KLT_ERR_ARG, "the guess feature buffer holds fewer records than the feature list");
-    const klt_feat *g = c->fbs[fb_guess].d;
-    if (g == c->fbs[fb_out].d || (fb_back >= 0 && g == c->fbs[fb_back].d))
-        return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
-    *guess = g;
-    return 0;
+    if (!fb_holds_records(c, fb_guess, n)) return fail(c, KLT_ERR_ARG, "the guess feature buffer holds fewer records than the feature list");
+    *guess = c->fbs[fb_guess].d;
+    return own_records(c, fb_guess, {fb_out, fb_back}, kGuessNotDistinct);
 }
 
 // the tracker launch of `npairs` pairs of `nlev` levels under its timer (guess: the kernels that start from a predicted position)
@@ -158,21 +189,6 @@ static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nl
     }
     if (guess ? launch_track_guess(c->stream, a) : launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
     return 0;
-}
-
-// gain / bias tracking is offered by klt_track, klt_track_async and klt_track_batch_async alone: every other tracker entry point is refused
-// while it is switched on, before anything is enqueued
-static int refuse_with_light(klt_ctx *c, const char *what)
-{
-    if (!c || !c->lightp.mode) return 0;
-    return fail(c, KLT_ERR_STATE, std::string(what) + " is not offered together with lighting compensation (klt_set_light_params mode 1)");
-}
-
-static int count_live(const klt_feat *f, int n)
-{
-    int k = 0;
-    for (int i = 0; i < n; i++) k += f[i].val >= 0;
-    return k;
 }
 
 // klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1); guess == true:
@@ -191,7 +207,7 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s1, *s2;
     if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
-    if (fb_in < 0 || (size_t)fb_in >= c->fbs.size() || c->fbs[fb_in].cap < n) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    if (int rc = lists_set(c, {fb_in}, n, false)) return rc;
     FeatBuf *bo;
     if (fb && fb_back >= 0)                                  // (may grow c->fbs: before any pointer into it is taken)
         if (int rc = get_fb(c, fb_back, n > 0 ? n : 1, &bo)) return rc;
@@ -211,10 +227,7 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
         if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
     if (int rc = enqueue_track(c, a, 1, s1->nlev, guess)) return rc;
     if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
-    {
-        Slot *both[2] = {s1, s2};
-        if (int rc = mark_read(c, both, 2)) return rc;
-    }
+    if (int rc = mark_read_pair(c, s1, s2)) return rc;
     HIPCHK(c, hipGetLastError());
     return KLT_OK;
 }
@@ -246,9 +259,7 @@ int klt_predict_cv_async(klt_ctx *c, int fb_prev, int fb_cur, int fb_guess, int 
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
     if (fb_guess == fb_prev || fb_guess == fb_cur) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_prev and fb_cur");
     HIPCHK(c, hipSetDevice(c->device));
-    for (int fb : {fb_prev, fb_cur})
-        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
-            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    if (int rc = lists_set(c, {fb_prev, fb_cur}, n)) return rc;
     FeatBuf *bg;                                             // (may grow c->fbs: before any pointer into it is taken)
     if (int rc = get_fb(c, fb_guess, n > 0 ? n : 1, &bg)) return rc;
     if (bg->d == c->fbs[fb_prev].d || bg->d == c->fbs[fb_cur].d)
@@ -288,7 +299,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     if (int rc = check_ready(c)) return rc;
     if (fb || fb_guess)
         if (int rc = refuse_with_light(c, fb ? "the forward-backward check" : "a motion prior")) return rc;
-    if (!slot1 || !slot2 || !fb_in || !fb_out || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
+    if (int rc = batch_arguments(c, {slot1, slot2, fb_in, fb_out}, npairs, n)) return rc;
     if (fb_guess)
         for (int i = 0; i < npairs; i++) {
             if (fb_guess[i] == -1) continue;
@@ -302,7 +313,6 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<TrackPairDesc> table((size_t)npairs);
     std::vector<Slot *> used;
-    Slot *first = nullptr;
     for (int i = 0; i < npairs; i++) {
         FeatBuf *bo;                      // may grow c->fbs: do it before taking pointers into it
         if (int rc = get_fb(c, fb_out[i], n > 0 ? n : 1, &bo)) return rc;
@@ -310,25 +320,16 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
             if (int rc = get_fb(c, fb_back[i], n > 0 ? n : 1, &bo)) return rc;
     }
     for (int i = 0; i < npairs; i++) {
-        Slot *s1, *s2;
-        if (int rc = check_pair(c, slot1[i], slot2[i], &s1, &s2)) return rc;
-        if (!first) first = s1;
-        used.push_back(s1);
-        used.push_back(s2);
-        if (s1->nc != first->nc || s1->nr != first->nr || s1->nlev != first->nlev)
-            return fail(c, KLT_ERR_ARG, "all pairs of a batch must have the same frame size");
-        if (fb_in[i] < 0 || (size_t)fb_in[i] >= c->fbs.size() || c->fbs[fb_in[i]].cap < n)
-            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+        if (int rc = batch_pair(c, slot1[i], slot2[i], true, used)) return rc;
+        if (int rc = lists_set(c, {fb_in[i]}, n, false)) return rc;
         std::memset(&table[i], 0, sizeof(TrackPairDesc));
-        fill_levels(s1, s2, table[i].lv);
+        fill_levels(used[2 * i], used[2 * i + 1], table[i].lv);
         table[i].in = c->fbs[fb_in[i]].d;
         table[i].out = c->fbs[fb_out[i]].d;
         if (fb && fb_back && fb_back[i] >= 0) table[i].back = c->fbs[fb_back[i]].d;
-        if (fb_guess && fb_guess[i] >= 0) {
-            if (int rc = guess_records(c, fb_guess[i], fb_out[i], -1, n, &table[i].guess)) return rc;
-            for (int j = 0; j < npairs; j++)
-                if (table[i].guess == c->fbs[fb_out[j]].d) return fail(c, KLT_ERR_ARG, "fb_guess must be distinct from fb_out and fb_back");
-        }
+        if (fb_guess && fb_guess[i] >= 0)
+            for (int j = 0; j < npairs; j++)                 // (next to this pair's output and every other pair's)
+                if (int rc = guess_records(c, fb_guess[i], fb_out[i], fb_out[j], n, &table[i].guess)) return rc;
     }
     // the descriptor table is uploaded only when none of the tables kept on the device holds it (found by hash; at most 256 tables,
     // the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order protects the
@@ -353,7 +354,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     std::memset(&a, 0, sizeof(a));
     a.pairs = bt->dev;
     a.npairs = npairs;
-    fill_track_params(c, first, a, n);
+    fill_track_params(c, used[0], a, n);
     if (fb) fill_fb_params(c, a);
     if (!c->lightp.mode) {
         // one permutation per pair, kept with the set of input lists (see set_track_order)
@@ -361,9 +362,9 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
         if (int rc = set_track_order(c, a, n, ins)) return rc;
     }
-    if (int rc = enqueue_track(c, a, npairs, first->nlev, fb_guess != nullptr)) return rc;
+    if (int rc = enqueue_track(c, a, npairs, used[0]->nlev, fb_guess != nullptr)) return rc;
     if (c->collect_stats)
-        for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, first->nlev, c->stats_d);
+        for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, used[0]->nlev, c->stats_d);
     if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
     HIPCHK(c, hipGetLastError());
     return KLT_OK;
@@ -391,11 +392,10 @@ int klt_track_guess(klt_ctx *c, int slot1, int slot2, klt_feat *inout, const klt
 {
     if (!c || !inout || !guess) return fail(c, KLT_ERR_ARG, "null argument");
     if (int rc = refuse_with_light(c, "a motion prior")) return rc;
-    const int fi = 65534, fo = 65535, fg = 65531;
-    if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: both lists are ours until then)
-    if (int rc = klt_featbuf_upload_async(c, fg, guess, n)) return rc;
-    if (int rc = klt_track_guess_async(c, slot1, slot2, fi, fg, fo, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncIn, inout, n)) return rc;      // (the download below synchronises: both lists are ours until then)
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncGuess, guess, n)) return rc;
+    if (int rc = klt_track_guess_async(c, slot1, slot2, kFbSyncIn, kFbSyncGuess, kFbSyncOut, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOut, inout, n)) return rc;
     if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }
@@ -403,10 +403,9 @@ int klt_track_guess(klt_ctx *c, int slot1, int slot2, klt_feat *inout, const klt
 int klt_track(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int *n_tracked)
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
-    const int fi = 65534, fo = 65535;
-    if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;      // (the download below synchronises: `inout` is ours until then)
-    if (int rc = klt_track_async(c, slot1, slot2, fi, fo, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncIn, inout, n)) return rc;      // (the download below synchronises: `inout` is ours until then)
+    if (int rc = klt_track_async(c, slot1, slot2, kFbSyncIn, kFbSyncOut, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOut, inout, n)) return rc;
     if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }
@@ -415,268 +414,11 @@ int klt_track_fb(klt_ctx *c, int slot1, int slot2, klt_feat *inout, klt_feat *ba
 {
     if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
     if (int rc = refuse_with_light(c, "the forward-backward check")) return rc;
-    const int fi = 65534, fo = 65535, fbk = 65532;
-    if (int rc = klt_featbuf_upload_async(c, fi, inout, n)) return rc;
-    if (int rc = klt_track_fb_async(c, slot1, slot2, fi, fo, n, back ? fbk : -1)) return rc;
+    if (int rc = klt_featbuf_upload_async(c, kFbSyncIn, inout, n)) return rc;
+    if (int rc = klt_track_fb_async(c, slot1, slot2, kFbSyncIn, kFbSyncOut, n, back ? kFbSyncBack : -1)) return rc;
     if (back)
-        if (int rc = klt_featbuf_download(c, fbk, back, n)) return rc;
-    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
-    if (n_tracked) *n_tracked = count_live(inout, n);
-    return KLT_OK;
-}
-
-// ------------------------------------------------------------------------- per-feature track quality
-// what a quality launch asks of one pair's feature buffers before anything is allocated: the quality records in a buffer of their own
-static int check_quality_buffers(klt_ctx *c, int fb_in, int fb_out, int fb_quality)
-{
-    if (fb_quality < 0 || fb_quality > 65535) return fail(c, KLT_ERR_ARG, "fb_quality must be a feature buffer");
-    if (fb_quality == fb_in || fb_quality == fb_out) return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from fb_in and fb_out");
-    return 0;
-}
-
-// level 0 of a pair, its two lists (n records each, KLT_ERR_STATE otherwise) and its quality records (allocated by the caller)
-static int fill_quality_pair(klt_ctx *c, const Slot *s1, const Slot *s2, int fb_in, int fb_out, int fb_quality, int n, QualityPair &p)
-{
-    for (int fb : {fb_in, fb_out})
-        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
-            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
-    p.i1 = s1->lv[0].img;
-    p.i2 = s2->lv[0].img; p.gx2 = s2->lv[0].gx; p.gy2 = s2->lv[0].gy;
-    p.in = c->fbs[fb_in].d; p.out = c->fbs[fb_out].d;
-    p.q = reinterpret_cast<klt_quality *>(c->fbs[fb_quality].d);
-    return 0;
-}
-
-static int enqueue_quality(klt_ctx *c, const QualityArgs &a, int npairs)
-{
-    const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
-    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 + 48), c->stream);      // booked with the tracker's launches
-    if (launch_track_quality(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
-    return 0;
-}
-
-int klt_track_quality_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int fb_quality, int n)
-{
-    if (int rc = check_ready(c)) return rc;
-    if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
-    if (int rc = check_quality_buffers(c, fb_in, fb_out, fb_quality)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    Slot *s1, *s2;
-    if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
-    if (n == 0) return KLT_OK;
-    for (int fb : {fb_in, fb_out})                           // (before the quality buffer is made: a refused call allocates nothing)
-        if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
-            return fail(c, KLT_ERR_STATE, "input feature buffer not set");
-    if ((size_t)fb_quality < c->fbs.size() && c->fbs[fb_quality].d &&
-        (c->fbs[fb_quality].d == c->fbs[fb_in].d || c->fbs[fb_quality].d == c->fbs[fb_out].d))      // a view can be a second name of the same records
-        return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from fb_in and fb_out");
-    FeatBuf *bq;                                             // (may grow c->fbs: before any pointer into it is taken)
-    if (int rc = get_fb(c, fb_quality, n, &bq)) return rc;
-    QualityArgs a;
-    std::memset(&a, 0, sizeof(a));
-    if (int rc = fill_quality_pair(c, s1, s2, fb_in, fb_out, fb_quality, n, a.one)) return rc;
-    a.n = n; a.window = c->p.window_width; a.ncols = s1->nc; a.nrows = s1->nr;
-    if (int rc = enqueue_quality(c, a, 1)) return rc;
-    {
-        Slot *both[2] = {s1, s2};
-        if (int rc = mark_read(c, both, 2)) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
-}
-
-int klt_track_quality_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, const int *fb_quality,
-                                  int npairs, int n)
-{
-    if (int rc = check_ready(c)) return rc;
-    if (!slot1 || !slot2 || !fb_in || !fb_out || !fb_quality || npairs <= 0 || npairs > 65535 || n < 0) return fail(c, KLT_ERR_ARG, "bad argument");
-    // (quality records that another pair of the launch reads as a list, or writes too: distinct from every pair's buffers)
-    for (int i = 0; i < npairs; i++)
-        for (int j = 0; j < npairs; j++) {
-            if (int rc = check_quality_buffers(c, fb_in[j], fb_out[j], fb_quality[i])) return rc;
-            if (i != j && fb_quality[i] == fb_quality[j]) return fail(c, KLT_ERR_ARG, "two pairs of the batch share fb_quality");
-        }
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<Slot *> used;
-    Slot *first = nullptr;
-    for (int i = 0; i < npairs; i++) {
-        Slot *s1, *s2;
-        if (int rc = check_pair(c, slot1[i], slot2[i], &s1, &s2)) return rc;
-        if (!first) first = s1;
-        used.push_back(s1);
-        used.push_back(s2);
-        if (s1->nc != first->nc || s1->nr != first->nr) return fail(c, KLT_ERR_ARG, "all pairs of a batch must have the same frame size");
-        for (int fb : {fb_in[i], fb_out[i]})
-            if (fb < 0 || (size_t)fb >= c->fbs.size() || !c->fbs[fb].d || c->fbs[fb].cap < n)
-                return fail(c, KLT_ERR_STATE, "input feature buffer not set");
-    }
-    if (n == 0) return KLT_OK;
-    // ... and by address: a view can be a second name of the same records (a buffer that does not exist yet is nobody's second name)
-    for (int i = 0; i < npairs; i++) {
-        const klt_feat *q = (size_t)fb_quality[i] < c->fbs.size() ? c->fbs[fb_quality[i]].d : nullptr;
-        for (int j = 0; q && j < npairs; j++)
-            if (q == c->fbs[fb_in[j]].d || q == c->fbs[fb_out[j]].d || (i != j && (size_t)fb_quality[j] < c->fbs.size() && q == c->fbs[fb_quality[j]].d))
-                return fail(c, KLT_ERR_ARG, "fb_quality must be distinct from every pair's fb_in, fb_out and fb_quality");
-    }
-    for (int i = 0; i < npairs; i++) {
-        FeatBuf *bq;                                         // may grow c->fbs: do it before taking pointers into it
-        if (int rc = get_fb(c, fb_quality[i], n, &bq)) return rc;
-    }
-    std::vector<QualityPair> table((size_t)npairs);
-    for (int i = 0; i < npairs; i++) {
-        std::memset(&table[i], 0, sizeof(QualityPair));
-        if (int rc = fill_quality_pair(c, used[2 * i], used[2 * i + 1], fb_in[i], fb_out[i], fb_quality[i], n, table[i])) return rc;
-    }
-    // the table goes up only when it differs from the one the device holds (pageable source: the runtime stages it before returning;
-    // stream order protects the launch that read the replaced table)
-    if (c->quality_host.size() != table.size() || std::memcmp(c->quality_host.data(), table.data(), table.size() * sizeof(QualityPair)) != 0) {
-        c->quality_host.clear();                             // (nothing is known of the device's copy until the new one is enqueued)
-        if (int rc = ensure(c, c->quality_dev, c->quality_cap, (size_t)npairs)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->quality_dev, table.data(), (size_t)npairs * sizeof(QualityPair), hipMemcpyHostToDevice, c->stream));
-        c->quality_host = table;
-    }
-    QualityArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.pairs = c->quality_dev;
-    a.npairs = npairs;
-    a.n = n; a.window = c->p.window_width; a.ncols = first->nc; a.nrows = first->nr;
-    if (int rc = enqueue_quality(c, a, npairs)) return rc;
-    if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
-}
-
-int klt_track_quality(klt_ctx *c, int slot1, int slot2, const klt_feat *in, const klt_feat *out, klt_quality *q, int n)
-{
-    if (!c || !in || !out || !q) return fail(c, KLT_ERR_ARG, "null argument");
-    const int fi = 65534, fo = 65535, fq = 65530;
-    if (int rc = klt_featbuf_upload_async(c, fi, in, n)) return rc;         // (the download below synchronises: both lists are ours until then)
-    if (int rc = klt_featbuf_upload_async(c, fo, out, n)) return rc;
-    if (int rc = klt_track_quality_async(c, slot1, slot2, fi, fo, fq, n)) return rc;
-    if (n == 0) return klt_sync(c);
-    return klt_featbuf_download(c, fq, reinterpret_cast<klt_feat *>(q), n);
-}
-
-// ------------------------------------------------------------------------- affine consistency check
-int klt_set_affine_params(klt_ctx *c, const klt_affine_params *p)
-{
-    if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
-    if (p->mode < -1 || p->mode > 2) return fail(c, KLT_ERR_ARG, "affineConsistencyCheck must be -1, 0, 1 or 2");
-    if (p->mode >= 0 && (p->window_width < 3 || p->window_height < 3 || !(p->window_width & 1) || !(p->window_height & 1) ||
-                         p->window_width > 63 || p->window_height > 63 || p->max_iterations < 1))
-        return fail(c, KLT_ERR_ARG, "affine window must be odd, 3..63; max_iterations >= 1");
-    if (c->ap.window_width != p->window_width || c->ap.window_height != p->window_height)
-        for (AffState &a : c->aff)
-            if (a.rec) return fail(c, KLT_ERR_STATE, "affine window cannot change while affine states exist");
-    c->ap = *p;
-    return KLT_OK;
-}
-
-int klt_affine_alloc(klt_ctx *c, int state, int n)
-{
-    if (!c || state < 0 || state > 4095 || n <= 0) return fail(c, KLT_ERR_ARG, "bad argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((size_t)state >= c->aff.size()) c->aff.resize(state + 1);
-    AffState &a = c->aff[state];
-    const int tn = (c->ap.window_width + 2) * (c->ap.window_height + 2);
-    if (a.n < n || a.tn != tn) {
-        if (a.rec) { if (int rc = sync_all(c)) return rc; hipFree(a.rec); hipFree(a.tpl); a.rec = nullptr; a.tpl = nullptr; a.n = 0; }
-        DEVALLOC(c, a.rec, (size_t)n * sizeof(klt_affine_rec));
-        if (int rc = dev_alloc(c, (void **)&a.tpl, (size_t)n * 3 * tn * sizeof(float), "affine templates")) {
-            hipFree(a.rec);                                   // a state is its records AND its templates, or nothing
-            a.rec = nullptr;
-            return rc;
-        }
-        a.n = n;
-        a.tn = tn;
-    }
-    launch_affine_reset(c->stream, a.rec, a.n);
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
-}
-
-int klt_affine_free(klt_ctx *c, int state)
-{
-    if (!c) return KLT_ERR_ARG;
-    if (state < 0 || (size_t)state >= c->aff.size() || !c->aff[state].rec) return KLT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = sync_all(c)) return rc;
-    AffState &a = c->aff[state];
-    hipFree(a.rec); hipFree(a.tpl);
-    a = AffState();
-    if (c->select_aff_state == state) c->select_aff_state = -1;
-    return KLT_OK;
-}
-
-// records (and, if asked, templates) of the first n features of `src` into `dst` (allocated here if needed), on the context's stream:
-// a snapshot of the per-feature state, e.g. to replay a step of a sequence from the same state
-int klt_affine_copy_async(klt_ctx *c, int dst, int src, int n, int with_templates)
-{
-    if (!c || dst == src || n <= 0) return fail(c, KLT_ERR_ARG, "bad argument");
-    if (src < 0 || (size_t)src >= c->aff.size() || !c->aff[src].rec || c->aff[src].n < n)
-        return fail(c, KLT_ERR_STATE, "source affine state not allocated (or smaller than requested)");
-    if (dst < 0 || (size_t)dst >= c->aff.size() || !c->aff[dst].rec || c->aff[dst].n < n) {
-        if (int rc = klt_affine_alloc(c, dst, c->aff[src].n)) return rc;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const AffState &s = c->aff[src];
-    AffState &d = c->aff[dst];
-    if (d.tn != s.tn) return fail(c, KLT_ERR_STATE, "affine states of different window sizes");
-    HIPCHK(c, hipMemcpyAsync(d.rec, s.rec, (size_t)n * sizeof(klt_affine_rec), hipMemcpyDeviceToDevice, c->stream));
-    if (with_templates)
-        HIPCHK(c, hipMemcpyAsync(d.tpl, s.tpl, (size_t)n * 3 * s.tn * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    return KLT_OK;
-}
-
-int klt_affine_download(klt_ctx *c, int state, klt_affine_rec *dst, int n)
-{
-    if (!c || !dst || state < 0 || (size_t)state >= c->aff.size() || !c->aff[state].rec || c->aff[state].n < n)
-        return fail(c, KLT_ERR_STATE, "affine state not allocated (or smaller than requested)");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(dst, c->aff[state].rec, (size_t)n * sizeof(klt_affine_rec), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KLT_OK;
-}
-
-int klt_track_affine_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n, int state)
-{
-    if (!c) return KLT_ERR_ARG;
-    if (int rc = refuse_with_light(c, "the affine consistency check")) return rc;
-    if (fb_in == fb_out) return fail(c, KLT_ERR_ARG, "the consistency check needs the records before and after: fb_in != fb_out");
-    if (c->ap.mode >= 0 && (state < 0 || (size_t)state >= c->aff.size() || !c->aff[state].rec || c->aff[state].n < n))
-        return fail(c, KLT_ERR_STATE, "affine state not allocated (klt_affine_alloc) or smaller than the feature list");
-    if (int rc = klt_track_async(c, slot1, slot2, fb_in, fb_out, n)) return rc;
-    if (c->ap.mode < 0 || n == 0) return KLT_OK;
-    Slot *s1 = &c->slots[slot1], *s2 = &c->slots[slot2];
-    AffState &as = c->aff[state];
-    AffineArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.in = c->fbs[fb_in].d; a.out = c->fbs[fb_out].d; a.rec = as.rec; a.tpl = as.tpl;
-    level_planes(s1, s2, 0, a.i1, a.gx1, a.gy1, a.i2, a.gx2, a.gy2);
-    a.n = n; a.ncols = s1->nc; a.nrows = s1->nr; a.mode = c->ap.mode;
-    a.width = c->ap.window_width; a.height = c->ap.window_height; a.max_iterations = c->ap.max_iterations;
-    a.step = c->p.step_factor; a.small = c->p.min_determinant; a.th = c->p.min_displacement;
-    a.th_aff = c->ap.min_displacement; a.max_residue = c->ap.max_residue; a.max_differ = c->ap.max_displacement_differ;
-    {
-        TimerScope t(c, F_AFFINE, (double)n * 12.0 * (a.width + 1) * (a.height + 1) * 3, c->stream);
-        launch_affine(c->stream, a);
-    }
-    {
-        Slot *both[2] = {s1, s2};
-        if (int rc = mark_read(c, both, 2)) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
-}
-
-int klt_track_affine(klt_ctx *c, int slot1, int slot2, klt_feat *inout, int n, int state, int *n_tracked)
-{
-    if (!c || !inout) return fail(c, KLT_ERR_ARG, "null argument");
-    if (int rc = refuse_with_light(c, "the affine consistency check")) return rc;
-    const int fi = 65534, fo = 65535;
-    if (int rc = klt_featbuf_upload(c, fi, inout, n)) return rc;
-    if (int rc = klt_track_affine_async(c, slot1, slot2, fi, fo, n, state)) return rc;
-    if (int rc = klt_featbuf_download(c, fo, inout, n)) return rc;
+        if (int rc = klt_featbuf_download(c, kFbSyncBack, back, n)) return rc;
+    if (int rc = klt_featbuf_download(c, kFbSyncOut, inout, n)) return rc;
     if (n_tracked) *n_tracked = count_live(inout, n);
     return KLT_OK;
 }

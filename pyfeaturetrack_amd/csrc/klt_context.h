@@ -7,7 +7,10 @@
 //   api_frames.hip    frames in (uploads, pinned / device memory, adoption), pyramid build, stand-alone convolutions, plane read-back
 //   api_featbuf.hip   feature buffers: copies either way, views, host-mapped buffers
 //   api_select.hip    selection: score preparation, the begin / finish protocol, the given-list walk, its inspection hooks
-//   api_track.hip     tracker launches (single pair, batched), affine consistency check, iteration counters
+//   api_track.hip     tracker launches (single pair, batched), constant-velocity prediction, iteration counters
+//   api_quality.hip   per-feature track quality (single pair, batched)
+//   api_model.hip     motion-model check (single pair, batched), the model record as an affine map
+//   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
 #pragma once
@@ -16,6 +19,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <utility>
@@ -81,6 +85,20 @@ inline const float *rawf(const Slot *s) { return s->f32_in_raw ? reinterpret_cas
 struct FeatBuf { klt_feat *d = nullptr; int cap = 0; bool view = false; hipEvent_t comm_done = nullptr; /* last collective that touched it */ };
 
 struct AffState { klt_affine_rec *rec = nullptr; float *tpl = nullptr; int n = 0, tn = 0; };
+
+// The feature buffers behind the synchronous entry points (klt_track, klt_select, klt_track_quality, ...): staging for the caller's
+// arrays -- the list in, the list out, the backward records, the guesses, and the private record buffer of klt_track_quality (quality
+// records) and klt_motion_check (the model record).  One set serves them all, the last one two of them: every synchronous entry point
+// has downloaded what it wants before it returns, so no two of them are ever in flight on these buffers.
+constexpr int kFbSyncIn = 65534, kFbSyncOut = 65535, kFbSyncBack = 65532, kFbSyncGuess = 65531, kFbSyncOwn = 65530;
+
+// The descriptor table of a batched launch that stays on the device and is sent again only when it differs (send_if_changed)
+template <class Desc>
+struct SentTable {
+    std::vector<Desc> host;           // what `dev` holds
+    Desc *dev = nullptr;
+    size_t cap = 0;
+};
 
 struct Timed { int fam; hipEvent_t a, b; double bytes; };
 
@@ -256,20 +274,13 @@ struct klt_ctx {
     klt_fb_params fbp{0, 1.0f};                                    // forward-backward check (klt_set_fb_params)
     klt_light_params lightp{0};                                    // gain / bias tracking (klt_set_light_params); 0 = off
     int light_path = 0;                                            // klt_track_light_path: kernel of the last lighting launch (0: none yet)
-    // batched quality launches (klt_track_quality_batch_async): the descriptor table last sent stays on the device and is sent again only
-    // when it differs
-    std::vector<QualityPair> quality_host;
-    QualityPair *quality_dev = nullptr;
-    size_t quality_cap = 0;
-    // motion-model check (klt_set_model_params, klt_motion_check*): candidates and scores live in one scratch allocation, a slice per pair;
-    // the descriptor table of a batched launch stays on the device and is sent again only when it differs
+    SentTable<QualityPair> quality_table;                          // batched quality launches (klt_track_quality_batch_async)
+    // motion-model check (klt_set_model_params, klt_motion_check*): candidates and scores live in one scratch allocation, a slice per pair
     klt_model_params modelp{0, 0, 0, 256, 0u, 8, 1.0f, 1.0f};
     int model_path = 0;                                            // klt_motion_check_path
     unsigned char *model_scratch = nullptr;
     size_t model_scratch_cap = 0;
-    std::vector<ModelPair> model_host;
-    ModelPair *model_dev = nullptr;
-    size_t model_cap = 0;
+    SentTable<ModelPair> model_table;                              // klt_motion_check_batch_async
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -386,6 +397,61 @@ int ensure(klt_ctx *c, T *&ptr, size_t &cap, size_t want)
     return 0;
 }
 
+// The table goes up only when it differs from the one the device holds (pageable source: the runtime stages it before returning; stream
+// order protects the launch that read the replaced table); *dev = where the launch finds it
+template <class Desc>
+int send_if_changed(klt_ctx *c, SentTable<Desc> &t, const std::vector<Desc> &table, const Desc **dev)
+{
+    if (t.host.size() != table.size() || std::memcmp(t.host.data(), table.data(), table.size() * sizeof(Desc)) != 0) {
+        t.host.clear();                                      // (nothing is known of the device's copy until the new one is enqueued)
+        if (int rc = ensure(c, t.dev, t.cap, table.size())) return rc;
+        HIPCHK(c, hipMemcpyAsync(t.dev, table.data(), table.size() * sizeof(Desc), hipMemcpyHostToDevice, c->stream));
+        t.host = table;
+    }
+    *dev = t.dev;
+    return 0;
+}
+
+inline int mark_read_pair(klt_ctx *c, Slot *s1, Slot *s2)
+{
+    Slot *both[2] = {s1, s2};
+    return mark_read(c, both, 2);
+}
+
+// ---- feature buffers as the launches look at them
+// "buffer fb holds n records": an index of the context's table whose entry reaches n records ...
+inline bool fb_holds(const klt_ctx *c, int fb, int n) { return fb >= 0 && (size_t)fb < c->fbs.size() && c->fbs[fb].cap >= n; }
+// ... and has memory.  The two differ for n == 0 alone (an index below a used one that never got memory: no records, and none missing):
+// the tracker's input lists, downloads and collectives ask the first, every other launch that reads a list the second
+inline bool fb_holds_records(const klt_ctx *c, int fb, int n) { return fb_holds(c, fb, n) && c->fbs[fb].d; }
+
+// KLT_ERR_STATE unless each of the launch's lists holds n records (in memory, unless the caller is the tracker)
+inline int lists_set(klt_ctx *c, std::initializer_list<int> lists, int n, bool in_memory = true)
+{
+    for (int fb : lists)
+        if (!(in_memory ? fb_holds_records(c, fb, n) : fb_holds(c, fb, n))) return fail(c, KLT_ERR_STATE, "input feature buffer not set");
+    return 0;
+}
+
+// A launch's private record buffer (fb_guess, fb_quality, fb_model) holds records of its own.  By index, before the device or a slot is
+// touched: a feature-buffer index that is none of `others` (an entry of -1 stands for no buffer) ...
+inline int own_index(klt_ctx *c, int fb, std::initializer_list<int> others, const char *not_a_buffer, const char *not_distinct)
+{
+    if (fb < 0 || fb > 65535) return fail(c, KLT_ERR_ARG, not_a_buffer);
+    for (int other : others)
+        if (fb == other) return fail(c, KLT_ERR_ARG, not_distinct);
+    return 0;
+}
+// ... and by address, once the launch's lists are known to exist: a view can be a second name of the same records (a buffer that does
+// not exist yet is nobody's second name).  get_fb of the private buffer comes after both: a refused call allocates nothing
+inline int own_records(klt_ctx *c, int fb, std::initializer_list<int> others, const char *not_distinct)
+{
+    if (!fb_holds_records(c, fb, 0)) return 0;
+    for (int other : others)
+        if (fb_holds_records(c, other, 0) && c->fbs[fb].d == c->fbs[other].d) return fail(c, KLT_ERR_ARG, not_distinct);
+    return 0;
+}
+
 // ---- api_frames.hip
 // The kernels address a plane with 32-bit BYTE offsets into a buffer descriptor of 2 GB (raw buffer operations, klt_internal.h), and the
 // largest plane is the record plane of level 0 with 12 bytes per pixel: a frame must stay below 2^27 pixels (1.5 GB of records).
@@ -403,6 +469,18 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
 int download_plane(klt_ctx *c, const float *src, int stride, size_t cnt, float *dst);      // every stride-th float of a device plane to the host
+
+// ---- api_track.hip
+int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2);      // both slots hold built pyramids of one geometry (and the main stream waits for their builds)
+void level_planes(const Slot *s1, const Slot *s2, int l, const float *&i1, const float *&gx1, const float *&gy1, const float *&i2,
+                  const float *&gx2, const float *&gy2);                     // the six planes of level l of a frame pair
+int refuse_with_light(klt_ctx *c, const char *what);                         // KLT_ERR_STATE while gain / bias tracking is switched on
+int count_live(const klt_feat *f, int n);
+// a batched launch on frame pairs: its argument test (`columns`: the arrays of the call, none may be null), and pair by pair -- so that
+// the order of refusals stays pair 0's slots, pair 0's lists, pair 1's slots, ... -- the pair's slots (check_pair) appended to `used`
+// and held against the first pair's frame size (and level count, if `same_levels`)
+int batch_arguments(klt_ctx *c, std::initializer_list<const int *> columns, int npairs, int n);
+int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used);
 
 // ---- api_select.hip
 // the three summed-area tables of a gradient pair (goodFeaturesUtils.pyx:49-51); rows_only: the column pass is left to the caller
