@@ -195,6 +195,9 @@ def run_cfg2(args, json_fd):
         kt = kernel_table(stamped, paired, npairs_roof, {"track": track_bytes(p, st, npairs_roof * NFEAT)})
         st_pair = {k: ([x / npairs_roof for x in v] if isinstance(v, list) else v / npairs_roof) for k, v in st.items()}
         pyr_b, trk_b = algorithmic_bytes(p, WIDTH, HEIGHT, st_pair, NFEAT)
+        lean0 = ctx.level0_lean()                      # KLT_OPT_L0_LAZY_GRAD: the timed builds left the level-0 gradients (12 B per pixel
+        if lean0:                                      # of SURVEY 8(d)'s pyramid bytes) to the tracker's footprints: not booked by any launch
+            pyr_b -= 12 * WIDTH * HEIGHT
         dom = "smooth_grad_l0"
         # PMC-derived figures are NOT measured by this run: committed results of the builder's rocprofv3 --pmc passes, with their
         # provenance, dropped when the kernel source changed since (committed_counters)
@@ -216,12 +219,17 @@ def run_cfg2(args, json_fd):
         elif sq_source:
             issue = {"source": sq_source}
         npx = WIDTH * HEIGHT * 2 * B
-        moved = npx * (1 + 4 + 12) + npx // p.subsampling * 4      # what crosses L2: u8 in, image + two gradients + the H1 plane out
+        # what crosses L2: u8 in, image + two gradients + the H1 plane out; a lean launch (KLT_OPT_L0_LAZY_GRAD) writes no gradients
+        moved = npx * ((1 + 4) if lean0 else (1 + 4 + 12)) + npx // p.subsampling * 4
         roofline = roofline_of(kt, npairs_roof, ms_per_pair, dominant=dom, extra={
             "traffic": traffic, "traffic_source": traffic_source, "issue_bound": issue, "pairs_per_launch": B,
-            "frac_note": "frac books SURVEY 8(d)'s 21 B per pixel (17 for smoothing + gradients, 4 for the first reduction's input, which this "
-                         "kernel consumes from LDS); frac_moved books the 18 B per pixel that actually cross the L2 (4 of the 21 never leave LDS, "
-                         "the H1 plane adds 1)",
+            "frac_note": ("frac books 9 B per pixel (SURVEY 8(d)'s 5 for smoothing, 4 for the first reduction's input, which this kernel consumes "
+                          "from LDS; the launch is lean -- KLT_OPT_L0_LAZY_GRAD -- and makes no gradients, whose 12 B per pixel are left out of the "
+                          "step's formula as well); frac_moved books the 6 B per pixel that actually cross the L2 (u8 in, image and H1 plane out)"
+                          if lean0 else
+                          "frac books SURVEY 8(d)'s 21 B per pixel (17 for smoothing + gradients, 4 for the first reduction's input, which this "
+                          "kernel consumes from LDS); frac_moved books the 18 B per pixel that actually cross the L2 (4 of the 21 never leave LDS, "
+                          "the H1 plane adds 1)"),
             "moved_bytes_per_launch": moved, "achieved_moved": moved / (kt[dom]["us_per_launch"] * 1e-6) / 1e9,
             "frac_moved": moved / (kt[dom]["us_per_launch"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
             "step_unit": "one frame pair", "step_algorithmic_bytes_formula": 2 * pyr_b + trk_b,

@@ -123,6 +123,20 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
  * strips in 16-row bands where the launch has >= 256 columns and fills the chip with them (fewer halo columns smoothed per output column),
  * else as 1.  Same results bit for bit. */
 #define KLT_OPT_L0_STREAM 21
+/* Level-0 gradients on demand.  A LEAN build of a slot launches the streaming level-0 kernel without its gradient passes: it writes the
+ * smoothed image to a compact f32 plane of the slot (4 bytes per pixel, allocated on the slot's first lean build and freed with the slot,
+ * on top of the 12 bytes per pixel of the level's records) and leaves the level-0 records unwritten; levels >= 1 are built as ever.  The
+ * plain 7x7 quad tracker (klt_track_async, klt_track_batch_async; lists of features x pairs >= 2048, default KLT_OPT_TRACK_VARIANT, sums in
+ * the reference's order, no lighting compensation) then makes the gradients of the footprints it visits itself, from that plane.  Whatever
+ * else reads level 0 of a lean slot -- every other tracker, a launch that mixes slots with and without a compact plane, selection, score
+ * preparation, quality, the affine check, klt_download_f32 -- first gets the records made from the compact plane by the gradient launch of
+ * the levels >= 1.  Records, planes and every result are the same bit for bit either way.
+ *   0: never lean.
+ *   1 (default): a slot is built lean when, since its previous build, such a tracker launch read it and nothing asked for its level-0
+ *      records -- so a slot's first build is full, a flow that selects or checks on every frame stays full, and a flow that only tracks
+ *      resident or streamed frames goes lean from its second build on.
+ *   2: always lean where a streaming kernel is launched (for tests). */
+#define KLT_OPT_L0_LAZY_GRAD 22
 int klt_set_option(klt_ctx *ctx, int option, int value);
 
 /* ---- parameters and taps ------------------------------------------------------------------- */
@@ -207,6 +221,9 @@ int klt_build_pyramids(klt_ctx *ctx, int slot);
 #define KLT_L0_STREAM_WIDE 7        /* smooth_grad_stream on 128-column strips in 16-row bands (KLT_OPT_L0_STREAM 2), f32 frames */
 #define KLT_L0_STREAM_WIDE_NO_CENTRE 8  /* ... with the centre product elided (u8 frames) */
 int klt_level0_path(klt_ctx *ctx, int *merged_grad);
+/* *lean = 1 if the last geometry group of the last build went out lean (KLT_OPT_L0_LAZY_GRAD; klt_level0_path reports the code of the
+ * streaming geometry as for a full launch), else 0.  KLT_ERR_STATE before the first build. */
+int klt_level0_lean(klt_ctx *ctx, int *lean);
 /* bit 0: the slot holds a frame; bit 1: its pyramids are built and match the current parameters / taps (what
  * `tc.pyramid_last is not None` means in the reference, trackFeatures.py:152); 0 for a slot never used */
 int klt_slot_state(klt_ctx *ctx, int slot);

@@ -114,6 +114,7 @@ SYMBOLS = {
     "klt_set_option": (_I, [_P, _I, _I]),
     "klt_build_pyramids": (_I, [_P, _I]),
     "klt_level0_path": (_I, [_P, _PI]),
+    "klt_level0_lean": (_I, [_P, _PI]),
     "klt_slot_state": (_I, [_P, _I]),
     "klt_device_memory": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "klt_slot_generation": (_I, [_P, _I, C.POINTER(C.c_uint64)]),

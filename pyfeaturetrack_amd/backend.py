@@ -376,6 +376,13 @@ class Context:
         code = self._check(self._lib.klt_level0_path(self._h, C.byref(merged)))
         return code, bool(merged.value)
 
+    def level0_lean(self):
+        """True if the last build's last group of frames went out lean: level 0 as the compact smoothed image alone, its gradients left
+        to the tracker (klt_level0_lean, KLT_OPT_L0_LAZY_GRAD; a diagnostic -- lean and full builds give the same results)"""
+        lean = C.c_int()
+        self._check(self._lib.klt_level0_lean(self._h, C.byref(lean)))
+        return bool(lean.value)
+
     def set_option(self, option, value):
         self._check(self._lib.klt_set_option(self._h, option, int(value)))
 

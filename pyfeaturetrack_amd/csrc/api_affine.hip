@@ -94,6 +94,8 @@ int klt_track_affine_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_o
     if (int rc = klt_track_async(c, slot1, slot2, fb_in, fb_out, n)) return rc;
     if (c->ap.mode < 0 || n == 0) return KLT_OK;
     Slot *s1 = &c->slots[slot1], *s2 = &c->slots[slot2];
+    if (int rc = ensure_level0_records(c, s1)) return rc;     // (the tracker launch above may have read compact level-0 images)
+    if (int rc = ensure_level0_records(c, s2)) return rc;
     AffState &as = c->aff[state];
     AffineArgs a;
     std::memset(&a, 0, sizeof(a));

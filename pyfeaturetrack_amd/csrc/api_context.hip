@@ -297,7 +297,7 @@ void klt_destroy(klt_ctx *c)
     for (void *p : c->dev_allocs) hipFree(p);
     for (hipEvent_t e : c->ring) hipEventDestroy(e);
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
-    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); }
+    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); }
     for (FeatBuf &b : c->fbs)
         if (!b.view) hipFree(b.d);
     hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg);
@@ -341,8 +341,10 @@ int klt_set_params(klt_ctx *c, const klt_params *p)
     c->p = *p;
     if (c->p.nPyramidLevels == 1 && (ss < 2)) c->p.subsampling = 2;
     c->have_params = true;
-    if (relayout)
+    if (relayout) {
         for (Slot &s : c->slots) s.pyr_valid = false;
+        c->cfg_gen++;
+    }
     return KLT_OK;
 }
 
@@ -355,6 +357,11 @@ int klt_set_option(klt_ctx *c, int option, int value)
     if (option == KLT_OPT_TRACK_VARIANT) { g_track_variant = value; return KLT_OK; }
     if (option == KLT_OPT_FUSED_HREDUCE) { c->fuse_hreduce = value != 0; return KLT_OK; }
     if (option == KLT_OPT_L0_STREAM) { c->l0_stream = value == 2 ? 2 : value != 0; return KLT_OK; }
+    if (option == KLT_OPT_L0_LAZY_GRAD) {
+        if (value < 0 || value > 2) return fail(c, KLT_ERR_ARG, "KLT_OPT_L0_LAZY_GRAD takes 0, 1 or 2");
+        c->l0_lazy_grad = value;
+        return KLT_OK;
+    }
     if (option == KLT_OPT_TRACK_XCD_ORDER) { c->track_xcd_order = value != 0; return KLT_OK; }
     if (option == KLT_OPT_BUILD_STREAM) {
         if (!value && c->bstream) HIPCHK(c, hipStreamSynchronize(c->bstream));      // pending builds finish; their events stay valid
@@ -423,7 +430,7 @@ int klt_slot_free(klt_ctx *c, int slot)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     Slot &s = c->slots[slot];
-    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes);
+    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img);
     s = Slot();
     return KLT_OK;
 }

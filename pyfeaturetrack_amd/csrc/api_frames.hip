@@ -157,13 +157,26 @@ static bool l0_hred(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
     return c->fuse_hreduce && smooth_grad_hred_ok(a, batch, raw_kind == 1 ? 0 : 1, c->gauss[1], c->p.subsampling);
 }
 
+// Would a level-0 launch of `batch` frames with the fused reduction go out lean if asked to (a streaming kernel: launch_smooth_grad's rule)?
+static bool l0_lean_ok(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
+{
+    SmoothGradArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
+    a.ncols = nc; a.nrows = nr;
+    return l0_hred(c, batch, raw_kind, nc, nr) && smooth_grad_lean_ok(a, batch, raw_kind == 1 ? 0 : 1, true, c->l0_stream);
+}
+
 // smooth(raw frame) + gradients for up to KLT_MAX_BATCH same-sized frames in one launch: pixel records `rec`, and (cimg, optional,
 // not with the fused reduction) the smoothed image as compact planes as well
 // *fused_h1 (optional, in/out): in = the caller wants the horizontal pass of the first reduction fused into this launch; out =
 // whether it was (then c->h1 holds one H1 plane of nr x (nc / ss) floats per frame)
 // *path (optional, out): the KLT_L0_* code of the kernel launched
+// lean: a lean launch (KLT_OPT_L0_LAZY_GRAD): the smoothed image to `cimg` and nothing to `rec`.  Only a streaming kernel has the form:
+// the caller asks for it where l0_lean_ok says the launch is one, and a launch that cannot be lean is refused, not sent out full.
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */, int *path /* = nullptr */)
+                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */, int *path /* = nullptr */,
+                              bool lean /* = false */)
 {
     SmoothGradArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -172,7 +185,10 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     a.ncols = nc; a.nrows = nr; a.R = grad_radius(c);
     const int kind = raw_kind == 1 ? 0 : 1;
     bool hred = fused_h1 && *fused_h1 && l0_hred(c, batch, raw_kind, nc, nr);
-    if (hred && cimg) return fail(c, KLT_ERR_STATE, "level-0 launch: a compact image copy with the fused reduction");
+    // (a lean launch -- only ever a streaming kernel, i.e. one with the fused reduction -- writes the compact planes INSTEAD of the records)
+    if (lean && !(hred && cimg && smooth_grad_lean_ok(a, batch, kind, hred, c->l0_stream)))
+        return fail(c, KLT_ERR_STATE, "level-0 launch: no lean form for this launch");
+    if (hred && cimg && !lean) return fail(c, KLT_ERR_STATE, "level-0 launch: a compact image copy with the fused reduction");
     if (hred) {
         const size_t plane = (size_t)nr * (nc / c->p.subsampling);
         if (int rc = ensure_h1(c, plane * batch)) return rc;
@@ -185,9 +201,12 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     // algorithmic bytes: smoothing b_in + 4, gradients 12 per pixel; with the fused horizontal reduction this
     // launch also consumes the reduction stage's input (4 per pixel of level 0 -- the part of 4 (N0 + N1) that no longer
     // touches HBM); pyr_vreduce is charged the stage's output, so the step total is unchanged
-    TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + N * 12 + (hred ? 4.0 * N : 0.0));
-    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path))
+    // (a lean launch writes the image alone, no gradients)
+    TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + (lean ? 0.0 : N * 12) + (hred ? 4.0 * N : 0.0));
+    bool went_lean = lean;
+    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path, &went_lean))
         return fail(c, KLT_ERR_DEVICE, std::string("smooth_grad launch: ") + hipGetErrorString((hipError_t)e));
+    if (went_lean != lean) return fail(c, KLT_ERR_STATE, "level-0 launch: lean form not as planned");
     return 0;
 }
 
@@ -204,6 +223,60 @@ int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *co
         return fail(c, KLT_ERR_DEVICE, std::string("gradient launch: ") + hipGetErrorString((hipError_t)e));
     return 0;
 }
+
+// KLT_OPT_L0_LAZY_GRAD: would this slot's build be lean if its launch has the form?  1 (adaptive): since its previous build -- of the
+// same frame size, under the same taps and pyramid shape -- a tracker launch with a lazy form read it and nothing asked for its level-0
+// records.  (A slot's first build is full.)
+static bool wants_lean(const klt_ctx *c, const Slot *s)
+{
+    if (c->l0_lazy_grad == 2) return true;
+    return c->l0_lazy_grad == 1 && s->lazy_read && !s->rec0_asked && s->built_nc == s->nc && s->built_nr == s->nr && s->built_cfg == c->cfg_gen;
+}
+
+// (declared in klt_context.h)
+int ensure_level0_records(klt_ctx *c, Slot *const *slots, int n, bool asked /* = true */)
+{
+    std::vector<Slot *> todo;
+    for (int i = 0; i < n; i++) {
+        Slot *s = slots[i];
+        if (asked) s->rec0_asked = true;
+        if (!s->pyr_valid || s->rec0_valid || std::find(todo.begin(), todo.end(), s) != todo.end()) continue;
+        if (!s->l0img_valid) return fail(c, KLT_ERR_STATE, "a built slot holds neither level-0 records nor a compact level-0 image");
+        if (c->capturing) return fail(c, KLT_ERR_STATE, "level-0 records would have to be made during a stream capture");
+        if (int rc = wait_built(c, s)) return rc;            // the main stream is behind the slot's build
+        todo.push_back(s);
+    }
+    if (todo.empty()) return 0;
+    hipStream_t const caller = c->work;
+    // slots of one frame size share a launch, KLT_MAX_BATCH at a time
+    std::vector<bool> done(todo.size(), false);
+    for (size_t i0 = 0; i0 < todo.size(); i0++) {
+        if (done[i0]) continue;
+        const float *img[KLT_MAX_BATCH];
+        float *rec[KLT_MAX_BATCH];
+        std::vector<Slot *> g;
+        for (size_t i = i0; i < todo.size() && g.size() < (size_t)KLT_MAX_BATCH; i++)
+            if (!done[i] && todo[i]->nc == todo[i0]->nc && todo[i]->nr == todo[i0]->nr) {
+                img[g.size()] = todo[i]->l0img; rec[g.size()] = todo[i]->lv[0].img;
+                g.push_back(todo[i]);
+                done[i] = true;
+            }
+        c->work = c->stream;
+        const int rc = enqueue_fused_grad(c, (int)g.size(), img, rec, todo[i0]->nc, todo[i0]->nr);
+        c->work = caller;
+        if (rc) return rc;
+        for (Slot *s : g) s->rec0_valid = true;
+    }
+    if (caller != c->stream) {                               // a reader on the build stream: behind the launch just enqueued
+        hipEvent_t e;
+        if (int rc2 = fresh_event(c, &e)) return rc2;
+        HIPCHK(c, hipEventRecord(e, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(caller, e, 0));
+    }
+    return 0;
+}
+
+int ensure_level0_records(klt_ctx *c, Slot *s, bool asked /* = true */) { return ensure_level0_records(c, &s, 1, asked); }
 
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
 {
@@ -263,7 +336,8 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         if (done[i0]) continue;
         std::vector<Slot *> g;
         for (int i = i0; i < n && (int)g.size() < KLT_MAX_BATCH; i++)
-            if (!done[i] && sl[i]->nc == sl[i0]->nc && sl[i]->nr == sl[i0]->nr && sl[i]->raw_kind == sl[i0]->raw_kind) {
+            if (!done[i] && sl[i]->nc == sl[i0]->nc && sl[i]->nr == sl[i0]->nr && sl[i]->raw_kind == sl[i0]->raw_kind &&
+                wants_lean(c, sl[i]) == wants_lean(c, sl[i0])) {
                 g.push_back(sl[i]);
                 done[i] = true;
             }
@@ -288,17 +362,22 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         auto cimg_of = [&](int l, int b) { return c->cimg + cper * b + coff[l]; };
 
         // level 0: smoothed frame (trackFeatures.py:165-166) and its gradients (:171-172)
-        bool h1_fused = false;
+        bool h1_fused = false, lean = false;
         int l0_path = KLT_L0_TWO_PASS;
         if (fused0) {
+            // KLT_OPT_L0_LAZY_GRAD: a group of slots that want it goes out lean where the launch is a streaming kernel's (which implies the
+            // fused reduction) -- the smoothed image to the slots' compact planes, no level-0 records
+            lean = h1_want && wants_lean(c, s0) && l0_lean_ok(c, B, s0->raw_kind, s0->nc, s0->nr);
+            for (int b = 0; b < B && lean; b++)
+                if (int rc = ensure(c, g[b]->l0img, g[b]->l0img_cap, (size_t)s0->nc * s0->nr)) return rc;
             for (int b = 0; b < B; b++) {
                 raw[b] = g[b]->raw_kind == 1 ? (const void *)raw8(g[b]) : (const void *)rawf(g[b]);
                 rec[b] = g[b]->lv[0].img;
-                cim[b] = cimg_of(0, b);
+                cim[b] = lean ? g[b]->l0img : cimg_of(0, b);
             }
             h1_fused = h1_want;
             const bool copy0 = !h1_want && s0->nlev > 1;
-            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 ? cim : nullptr, s0->nc, s0->nr, &h1_fused, &l0_path)) return rc;
+            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 || lean ? cim : nullptr, s0->nc, s0->nr, &h1_fused, &l0_path, lean)) return rc;
             if (h1_fused != h1_want) return fail(c, KLT_ERR_STATE, "level-0 launch: fused reduction not as planned");
         } else {
             for (int b = 0; b < B; b++) {
@@ -310,6 +389,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         const bool merged_grad = s0->nlev > 1 && fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767;
         c->l0_path = l0_path;
         c->l0_merged_grad = merged_grad;
+        c->l0_lean = lean;
         // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
         // then the gradients of the new level.  Only surviving columns / rows are evaluated.
         for (int l = 1; l < s0->nlev; l++) {
@@ -374,7 +454,12 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
             if (int er = launch_smooth_grad(c->work, a, e, 2))
                 return fail(c, KLT_ERR_DEVICE, std::string("gradient launch: ") + hipGetErrorString((hipError_t)er));
         }
-        for (Slot *s : g) { s->pyr_valid = true; s->gen = ++c->gen_counter; }
+        for (Slot *s : g) {
+            s->pyr_valid = true; s->gen = ++c->gen_counter;
+            s->rec0_valid = !lean; s->l0img_valid = lean;
+            s->lazy_read = s->rec0_asked = false;
+            s->built_nc = s->nc; s->built_nr = s->nr; s->built_cfg = c->cfg_gen;
+        }
     }
     // the next asynchronous copy into these slots waits for this build
     if (int rc = mark_consumed(c, sl.data(), n, c->work)) return rc;
@@ -429,6 +514,7 @@ int klt_set_kernels(klt_ctx *c, int which, const double *gauss, int ng, const do
     c->deriv[which] = d;
     c->have_taps[which] = true;
     for (Slot &s : c->slots) s.pyr_valid = false;
+    c->cfg_gen++;
     return KLT_OK;
 }
 
@@ -647,6 +733,14 @@ int klt_level0_path(klt_ctx *c, int *merged_grad)
     return c->l0_path;
 }
 
+int klt_level0_lean(klt_ctx *c, int *lean)
+{
+    if (!c || !lean) return fail(c, KLT_ERR_ARG, "null argument");
+    if (c->l0_path < 0) return fail(c, KLT_ERR_STATE, "no pyramid build yet");
+    *lean = c->l0_lean ? 1 : 0;
+    return KLT_OK;
+}
+
 int klt_level_dims(klt_ctx *c, int slot, int level, int *ncols, int *nrows)
 {
     if (!c) return KLT_ERR_ARG;
@@ -670,6 +764,8 @@ int klt_download_f32(klt_ctx *c, int slot, int pyramid, int level, float *dst)
     const float *src = pyramid == 0 ? l.img : (pyramid == 1 ? l.gx : l.gy);
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = wait_built(c, s)) return rc;
+    if (level == 0)
+        if (int rc = ensure_level0_records(c, s)) return rc;
     return download_plane(c, src, KLT_PIX_STRIDE, (size_t)l.nc * l.nr, dst);
 }
 

@@ -64,9 +64,10 @@ int klt_track_quality_batch_async(klt_ctx *c, const int *slot1, const int *slot2
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<Slot *> used;
     for (int i = 0; i < npairs; i++) {
-        if (int rc = batch_pair(c, slot1[i], slot2[i], false, used)) return rc;
+        if (int rc = batch_pair(c, slot1[i], slot2[i], false, used, true)) return rc;
         if (int rc = lists_set(c, {fb_in[i], fb_out[i]}, n)) return rc;
     }
+    if (int rc = ensure_level0_records(c, used.data(), (int)used.size())) return rc;      // (lean slots: their records, one launch for all)
     if (n == 0) return KLT_OK;
     // ... and by address
     for (int i = 0; i < npairs; i++)

@@ -286,6 +286,7 @@ int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, c
     if (use_pyramid) {
         if (!s->pyr_valid) return fail(c, KLT_ERR_STATE, "use_pyramid requested but the slot's pyramids are not built");
         if (int rc = wait_built(c, s)) return rc;
+        if (int rc = ensure_level0_records(c, s)) return rc;
         *img_out = s->lv[0].img; *gx = s->lv[0].gx; *gy = s->lv[0].gy;
         return 0;
     }
@@ -559,6 +560,7 @@ int klt_select_prepare_async(klt_ctx *c, int slot)
         for (auto &e : c->pre)                  // an earlier preparation on the build stream shares the table scratch
             if (e.ev && event_live(c, e.ev_serial)) HIPCHK(c, hipStreamWaitEvent(c->stream, e.ev, 0));
     }
+    if (int rc = ensure_level0_records(c, s)) return rc;      // (a lean slot: made on the main stream, this one ordered behind it)
     // the set that already belongs to these contents, else a free one, else the oldest
     ScoreCache *e = nullptr;
     for (auto &x : c->pre) if (x.gen == s->gen) { e = &x; break; }

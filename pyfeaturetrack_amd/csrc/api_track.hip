@@ -29,7 +29,7 @@ static Entry *cache_place(std::vector<Entry> &v, size_t capacity)
 
 namespace kltapi {
 
-int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2)
+int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2, bool lazy_ok /* = false */)
 {
     if (int rc = get_slot(c, slot1, p1, false)) return rc;
     if (int rc = get_slot(c, slot2, p2, false)) return rc;
@@ -39,6 +39,10 @@ int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2)
     if (int rc = wait_built(c, s2)) return rc;
     if (s1->nc != s2->nc || s1->nr != s2->nr || s1->nlev != s2->nlev || s1->ss != s2->ss)
         return fail(c, KLT_ERR_ARG, "the two frames differ in size");            // trackFeatures.py:156-159, :217
+    if (!lazy_ok) {
+        if (int rc = ensure_level0_records(c, s1)) return rc;
+        if (int rc = ensure_level0_records(c, s2)) return rc;
+    }
     return 0;
 }
 
@@ -70,10 +74,10 @@ int batch_arguments(klt_ctx *c, std::initializer_list<const int *> columns, int 
     return null_column || npairs <= 0 || npairs > 65535 || n < 0 ? fail(c, KLT_ERR_ARG, "bad argument") : 0;
 }
 
-int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used)
+int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used, bool lazy_ok /* = false */)
 {
     Slot *s1, *s2;
-    if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
+    if (int rc = check_pair(c, slot1, slot2, &s1, &s2, lazy_ok)) return rc;
     used.push_back(s1);
     used.push_back(s2);
     const Slot *first = used[0];
@@ -145,12 +149,35 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
     return 0;
 }
 
-static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv)
+// lazy: level 0 is the two slots' compact images (TrackLazyArgs; the kernels do not look at that level's gradient pointers)
+static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv, bool lazy = false)
 {
     for (int l = 0; l < s1->nlev; l++) {
         level_planes(s1, s2, l, lv[l].i1, lv[l].gx1, lv[l].gy1, lv[l].i2, lv[l].gx2, lv[l].gy2);
         lv[l].nc = s1->lv[l].nc; lv[l].nr = s1->lv[l].nr;
     }
+    if (lazy) {
+        lv[0].i1 = s1->l0img; lv[0].i2 = s2->l0img;
+        lv[0].gx1 = lv[0].gy1 = lv[0].gx2 = lv[0].gy2 = nullptr;
+    }
+}
+
+// KLT_OPT_L0_LAZY_GRAD, a plain tracker launch of `npairs` pairs on `slots`: *capable = the launch has a lazy form (track_lazy_capable, 7-tap
+// gradient filters), *lazy = it has and every slot holds a compact level-0 image.  Otherwise the slots without level-0 records get them
+// here (one launch per KLT_MAX_BATCH slots); the fallback of a launch that has a lazy form is not held against the slots.
+static int settle_level0(klt_ctx *c, const TrackArgsBase &a, int npairs, Slot *const *slots, int nslots, bool *capable, bool *lazy)
+{
+    *capable = track_lazy_capable(a.window, a.tree_sums, a.n, npairs) && merged_grad_ok(c);
+    bool all = *capable;
+    for (int i = 0; i < nslots; i++) all = all && slots[i]->l0img_valid;
+    *lazy = all;
+    return all ? 0 : ensure_level0_records(c, slots, nslots, !*capable);
+}
+
+// ... and once the launch is out: a launch that has a lazy form leaves its mark on the slots it read (their next build may be lean)
+static void mark_lazy_read(Slot *const *slots, int nslots, bool capable)
+{
+    for (int i = 0; i < nslots && capable; i++) slots[i]->lazy_read = true;
 }
 
 // what a forward-backward launch asks of a pair's three feature buffers (fb_back: a buffer or -1)
@@ -179,10 +206,20 @@ static int guess_records(klt_ctx *c, int fb_guess, int fb_out, int fb_back, int 
 }
 
 // the tracker launch of `npairs` pairs of `nlev` levels under its timer (guess: the kernels that start from a predicted position)
-static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nlev, bool guess = false)
+// lazy: the plain 7x7 quad kernels that read level 0 as compact images (settle_level0)
+static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nlev, bool guess = false, bool lazy = false)
 {
     const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
-    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * nlev + 32), c->stream);   // refined by the caller from klt_track_stats
+    // (a lazy level 0 reads the 14 x 14 image patch around a footprint, 4 bytes per pixel, instead of the footprint's records)
+    const double foot0 = lazy ? 4.0 * 14 * 14 : foot;
+    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * (nlev - 1) + foot0 * 2 + 32), c->stream);   // refined by the caller from klt_track_stats
+    if (lazy) {
+        TrackLazyArgs la;
+        static_cast<TrackArgsBase &>(la) = a;
+        for (int i = 0; i < 4; i++) { la.kg[i] = c->gauss[2].k[i]; la.kd[i] = c->deriv[2].k[i]; }
+        if (launch_track_lazy(c->stream, la)) return fail(c, KLT_ERR_STATE, "tracker launch: no lazy form for this launch");
+        return 0;
+    }
     if (c->lightp.mode) {                                   // gain / bias tracking (klt_set_light_params): kernels of their own, features in list order
         if (launch_track_light(c->stream, a, &c->light_path)) return fail(c, KLT_ERR_ARG, "unsupported window size");
         return 0;
@@ -206,7 +243,8 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
         if (int rc = check_guess_buffer(c, fb_guess, fb_out, fb ? fb_back : -1)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s1, *s2;
-    if (int rc = check_pair(c, slot1, slot2, &s1, &s2)) return rc;
+    const bool plain = !fb && !guess && !c->lightp.mode;     // the launches with a lazy form look after level 0 themselves (settle_level0)
+    if (int rc = check_pair(c, slot1, slot2, &s1, &s2, plain)) return rc;
     if (int rc = lists_set(c, {fb_in}, n, false)) return rc;
     FeatBuf *bo;
     if (fb && fb_back >= 0)                                  // (may grow c->fbs: before any pointer into it is taken)
@@ -216,16 +254,21 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
     std::memset(&a, 0, sizeof(a));
     if (guess)
         if (int rc = guess_records(c, fb_guess, fb_out, fb ? fb_back : -1, n, &a.guess)) return rc;
-    fill_levels(s1, s2, a.lv);
     a.in = c->fbs[fb_in].d; a.out = bo->d;
     fill_track_params(c, s1, a, n);
+    bool lazy = false, capable = false;
+    Slot *const both[2] = {s1, s2};
+    if (plain)
+        if (int rc = settle_level0(c, a, 1, both, 2, &capable, &lazy)) return rc;
+    fill_levels(s1, s2, a.lv, lazy);
     if (fb) {
         fill_fb_params(c, a);
         a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
     }
     if (!c->lightp.mode)
         if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
-    if (int rc = enqueue_track(c, a, 1, s1->nlev, guess)) return rc;
+    if (int rc = enqueue_track(c, a, 1, s1->nlev, guess, lazy)) return rc;
+    mark_lazy_read(both, 2, capable);
     if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
     if (int rc = mark_read_pair(c, s1, s2)) return rc;
     HIPCHK(c, hipGetLastError());
@@ -319,11 +362,11 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         if (fb && fb_back && fb_back[i] >= 0)
             if (int rc = get_fb(c, fb_back[i], n > 0 ? n : 1, &bo)) return rc;
     }
+    const bool plain = !fb && !fb_guess && !c->lightp.mode;  // the launches with a lazy form look after level 0 themselves (settle_level0)
     for (int i = 0; i < npairs; i++) {
-        if (int rc = batch_pair(c, slot1[i], slot2[i], true, used)) return rc;
+        if (int rc = batch_pair(c, slot1[i], slot2[i], true, used, true)) return rc;
         if (int rc = lists_set(c, {fb_in[i]}, n, false)) return rc;
         std::memset(&table[i], 0, sizeof(TrackPairDesc));
-        fill_levels(used[2 * i], used[2 * i + 1], table[i].lv);
         table[i].in = c->fbs[fb_in[i]].d;
         table[i].out = c->fbs[fb_out[i]].d;
         if (fb && fb_back && fb_back[i] >= 0) table[i].back = c->fbs[fb_back[i]].d;
@@ -331,6 +374,13 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
             for (int j = 0; j < npairs; j++)                 // (next to this pair's output and every other pair's)
                 if (int rc = guess_records(c, fb_guess[i], fb_out[i], fb_out[j], n, &table[i].guess)) return rc;
     }
+    TrackGuessArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_track_params(c, used[0], a, n);
+    bool lazy = false, capable = false;
+    if (plain) { if (int rc = settle_level0(c, a, npairs, used.data(), (int)used.size(), &capable, &lazy)) return rc; }
+    else if (int rc = ensure_level0_records(c, used.data(), (int)used.size())) return rc;      // (no lazy form: the records, one launch for all)
+    for (int i = 0; i < npairs; i++) fill_levels(used[2 * i], used[2 * i + 1], table[i].lv, lazy);
     // the descriptor table is uploaded only when none of the tables kept on the device holds it (found by hash; at most 256 tables,
     // the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order protects the
     // launch that read the replaced table
@@ -350,11 +400,8 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         bt->hash = hash;
     }
     bt->used = ++c->batch_clock;
-    TrackGuessArgs a;
-    std::memset(&a, 0, sizeof(a));
     a.pairs = bt->dev;
     a.npairs = npairs;
-    fill_track_params(c, used[0], a, n);
     if (fb) fill_fb_params(c, a);
     if (!c->lightp.mode) {
         // one permutation per pair, kept with the set of input lists (see set_track_order)
@@ -362,7 +409,8 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
         if (int rc = set_track_order(c, a, n, ins)) return rc;
     }
-    if (int rc = enqueue_track(c, a, npairs, used[0]->nlev, fb_guess != nullptr)) return rc;
+    if (int rc = enqueue_track(c, a, npairs, used[0]->nlev, fb_guess != nullptr, lazy)) return rc;
+    mark_lazy_read(used.data(), (int)used.size(), capable);
     if (c->collect_stats)
         for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, used[0]->nlev, c->stats_d);
     if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;

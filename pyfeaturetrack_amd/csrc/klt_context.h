@@ -51,7 +51,17 @@ struct Slot {
     Level lv[KLT_MAX_LEVELS];
     int nlev = 0, ss = 0;
     bool pyr_valid = false;
-    uint64_t gen = 0;                 // which build filled the pyramids (unique per build; travels with klt_swap_slots)
+    // KLT_OPT_L0_LAZY_GRAD: the compact level-0 image a lean build writes instead of the level-0 records (nc x nr floats, allocated on
+    // the slot's first lean build).  A built slot has valid level-0 records (rec0_valid), a valid compact image (l0img_valid), or --
+    // once ensure_level0_records has made the records of a lean build -- both.
+    float *l0img = nullptr;
+    size_t l0img_cap = 0;             // floats
+    bool rec0_valid = false, l0img_valid = false;
+    // since the slot's last build: a tracker launch that has a lazy form read it / something asked for its level-0 records
+    bool lazy_read = false, rec0_asked = false;
+    int built_nc = 0, built_nr = 0;   // frame size and taps / pyramid shape (klt_ctx::cfg_gen) of that build: a change of either resets
+    uint64_t built_cfg = 0;           // the slot to a full build
+    uint64_t gen = 0;                // which build filled the pyramids (unique per build; travels with klt_swap_slots)
     hipEvent_t ev_upload = nullptr;   // asynchronous ingest: frame copy finished (the build waits for it)
     hipEvent_t ev_consumed = nullptr; // last kernel on `stream` that read the raw frame u8
     uint64_t upload_serial = 0, consumed_serial = 0, consumed_alt_serial = 0;   // when the ring handed those events out (event_live)
@@ -183,6 +193,9 @@ struct klt_ctx {
     int l0_stream = 2;                        // KLT_OPT_L0_STREAM: 0 tiled, 1 streaming, 2 (default) streaming with wide strips where they apply
     int l0_path = -1;                         // klt_level0_path: KLT_L0_* of the last geometry group of the last build (-1: no build yet)
     bool l0_merged_grad = false;              // ... and whether that group's gradients of levels >= 1 went out as one launch
+    int l0_lazy_grad = 1;                     // KLT_OPT_L0_LAZY_GRAD: 0 never lean, 1 adaptive, 2 lean wherever a streaming kernel is launched
+    bool l0_lean = false;                     // klt_level0_lean: that group went out lean
+    uint64_t cfg_gen = 1;                     // counts the changes of the taps and of the pyramid's shape (Slot::built_cfg)
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
     // selection scratch
@@ -465,13 +478,21 @@ int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *rec);
 bool fused_smooth_ok(const klt_ctx *c);
 bool fused_grad_ok(const klt_ctx *c);
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr, int *path = nullptr);
+                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr, int *path = nullptr, bool lean = false);
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
+// KLT_OPT_L0_LAZY_GRAD: whoever reads lv[0].img / .gx / .gy of a built slot calls this first.  The records of a lean slot are made from its
+// compact image by the gradient launch of the levels >= 1, on the main stream behind the slot's build (wait_built); a caller that
+// enqueues on the build stream is ordered behind it.  `asked` (every reader but the tracker's own fallback): the slot's next build is full.
+int ensure_level0_records(klt_ctx *c, Slot *s, bool asked = true);
+int ensure_level0_records(klt_ctx *c, Slot *const *slots, int n, bool asked = true);      // ... of several slots: one launch per KLT_MAX_BATCH slots of a size
+bool merged_grad_ok(const klt_ctx *c);                       // 7-tap Gaussian / derivative gradient filters (what the specialised kernels take)
 int download_plane(klt_ctx *c, const float *src, int stride, size_t cnt, float *dst);      // every stride-th float of a device plane to the host
 
 // ---- api_track.hip
-int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2);      // both slots hold built pyramids of one geometry (and the main stream waits for their builds)
+// both slots hold built pyramids of one geometry (and the main stream waits for their builds); their level-0 records are there
+// (ensure_level0_records) unless the caller has a lazy form and looks after that itself (lazy_ok)
+int check_pair(klt_ctx *c, int slot1, int slot2, Slot **p1, Slot **p2, bool lazy_ok = false);
 void level_planes(const Slot *s1, const Slot *s2, int l, const float *&i1, const float *&gx1, const float *&gy1, const float *&i2,
                   const float *&gx2, const float *&gy2);                     // the six planes of level l of a frame pair
 int refuse_with_light(klt_ctx *c, const char *what);                         // KLT_ERR_STATE while gain / bias tracking is switched on
@@ -480,7 +501,7 @@ int count_live(const klt_feat *f, int n);
 // the order of refusals stays pair 0's slots, pair 0's lists, pair 1's slots, ... -- the pair's slots (check_pair) appended to `used`
 // and held against the first pair's frame size (and level count, if `same_levels`)
 int batch_arguments(klt_ctx *c, std::initializer_list<const int *> columns, int npairs, int n);
-int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used);
+int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used, bool lazy_ok = false);
 
 // ---- api_select.hip
 // the three summed-area tables of a gradient pair (goodFeaturesUtils.pyx:49-51); rows_only: the column pass is left to the caller

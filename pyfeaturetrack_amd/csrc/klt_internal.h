@@ -94,6 +94,14 @@ struct TrackGuessArgs : TrackArgs {
     const klt_feat *guess;       // single-pair launch: one record per feature (x, y = predicted frame-2 position; val < 0: no guess)
 };
 
+// ... and the kernel argument of the plain 7x7 quad kernels that make their level-0 gradients themselves (KLT_OPT_L0_LAZY_GRAD; DESIGN.md
+// section 5): level 0 of both frames is the slot's compact image plane (lv[0].i1 / .i2, element stride 1; the four gradient pointers of
+// that level are not looked at), and the kernels carry the taps of the two gradient filters -- 7 taps each, the four left of and at the
+// centre as corr_regs (below) reads them.  A struct of its own: TrackArgsBase and the kernels that take it stay as they are.
+struct TrackLazyArgs : TrackArgsBase {
+    double kg[4], kd[4];         // Gaussian (symmetric) and derivative (antisymmetric) taps
+};
+
 // one frame pair of a quality launch (klt_track_quality_async): level 0 of the two frames as the tracker reads it
 // (records, KLT_PIX_STRIDE), the two lists and the quality records.  The table of a batched launch (device memory, indexed by
 // blockIdx.y) holds these: a table of its own, TrackPairDesc stays as it is.
@@ -266,14 +274,51 @@ __device__ __forceinline__ float plane_load(plane_rsrc r, unsigned byte_off)
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
 }
 
+// ---- shared by the level-0 kernels (pyramid_kernels.hip) and the tracker's level-0 gradients on demand (track_kernels.hip): one text, so
+// that the two cannot drift apart.  (Both files switch contraction off for the whole translation unit, as the build's flags do.)
+// The reflect map for indices at most n beyond either end (frames at least as large as the halo): branch-free
+__device__ __forceinline__ int reflect_once(int i, int n)
+{
+    return i < 0 ? -1 - i : i >= n ? 2 * n - 1 - i : i;
+}
+
+template <int NT>
+struct TapRegs { double k[NT]; };
+
+// Register-blocked variant (the one dispatched for the default sigmas).  Every thread produces 4 horizontally
+// adjacent samples per step: LDS is read 16 bytes at a time (ds_read_b128, one aligned quad per lane), each
+// sample is widened to f64 once per quad instead of once per tap, and the integer index math is amortised over
+// four outputs.  The per-output FP64 expression and its operation order are unchanged.
+// Column frames (relative to the tile's first output column): A (raw) starts at -8, B / C at -4, D / E at 0,
+// all row strides are multiples of 4 floats.  Needs tap radii <= 4.
+// ZC (antisymmetric taps only): the centre tap is +0.0 and the centre sample is >= +0 and finite, so the first product c[0] * k[H]
+// is +0 and the first addition +0 + p equals p + 0.0 bit for bit (-0 included): the multiply is dropped, the addition kept.
+template <int NT, int SYM, bool ZC = false>
+__device__ __forceinline__ float corr_regs(const double *c /* centre */, const TapRegs<NT> &t)
+{
+    constexpr int H = NT / 2;
+    static_assert(!ZC || SYM < 0, "centre-tap elision is for the derivative taps");
+    double acc = ZC ? (c[-H] - c[H]) * t.k[0] + 0.0 : c[0] * t.k[H];
+#pragma unroll
+    for (int jj = ZC ? -H + 1 : -H; jj < 0; jj++) {
+        const double pr = SYM > 0 ? c[jj] + c[-jj] : c[jj] - c[-jj];
+        acc = acc + pr * t.k[H + jj];
+    }
+    return (float)acc;
+}
+
 extern int g_track_variant;         // tracker kernels: 4 (default) quad-load kernels where they apply, 0 always track_kernel
 size_t smooth_grad_lds_bytes(int smooth_radius /* -1: no smoothing stage */, int R);
 size_t pyr_reduce_lds_bytes(int ss, int ntaps);
 // kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image gradients only, 3 = u8 image gradients only
 // stream: the streaming level-0 kernel where it applies (KLT_OPT_L0_STREAM: 1 = 64-column strips, 2 = 128-column strips where they apply)
 // *path (optional): which kernel went out, a KLT_L0_* code of include/klt_gpu.h
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, int stream = 0, int *path = nullptr);
+// *lean (optional, in/out): in = the caller would take the lean form of a streaming kernel (no gradients, no records: the smoothed image
+// goes to the compact planes a.cimg instead); out = whether that is what went out (the tiled kernels have no lean form)
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, int stream = 0, int *path = nullptr,
+                       bool *lean = nullptr);
 bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss);
+bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream);      // a launch asked to be lean would be
 int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch);
 int launch_pyr_reduce(hipStream_t s, const PyrReduceArgs &a, int batch);
 
@@ -386,6 +431,10 @@ int  launch_nms_quota(hipStream_t s, const NmsArgs &a, const QuotaArgs &g);   //
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
 int launch_track(hipStream_t s, const TrackArgs &a);
 int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
+// Would launch_track take the plain 7x7 quad kernel for this launch (the one kernel with a lazy form)? ...
+bool track_lazy_capable(int window, int tree_sums, int n, int npairs);
+// ... and that form: level 0 of every pair is a compact image plane (TrackLazyArgs)
+int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a);
 // the gain / bias tracker (track_light_kernels.hip; klt_set_light_params mode 1): *path = 1 wave kernel, 2 quad kernel; a.order is not looked at
 int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
 // per-feature track quality (quality_kernels.hip): one klt_quality record per feature; returns -1 for an unsupported window

@@ -227,11 +227,6 @@ __global__ __launch_bounds__(256) void pyr_reduce_kernel(PyrReduceArgs a)
 // in scalar registers for the whole kernel and the correlate loops are fully unrolled (same operation order).
 // The runtime-sized kernels above remain the fallback for unusual sigmas.
 
-// The reflect map for indices at most n beyond either end (frames at least as large as the halo): branch-free
-__device__ __forceinline__ int reflect_once(int i, int n)
-{
-    return i < 0 ? -1 - i : i >= n ? 2 * n - 1 - i : i;
-}
 
 __device__ __forceinline__ int reflect_fast(int i, int n)
 {
@@ -240,8 +235,6 @@ __device__ __forceinline__ int reflect_fast(int i, int n)
     return i;
 }
 
-template <int NT>
-struct TapRegs { double k[NT]; };
 
 template <int NT>
 __device__ __forceinline__ void load_taps(TapRegs<NT> &r, const Taps &t)
@@ -250,27 +243,8 @@ __device__ __forceinline__ void load_taps(TapRegs<NT> &r, const Taps &t)
     for (int i = 0; i < NT; i++) r.k[i] = t.k[i];
 }
 
-// Register-blocked variant (the one dispatched for the default sigmas).  Every thread produces 4 horizontally
-// adjacent samples per step: LDS is read 16 bytes at a time (ds_read_b128, one aligned quad per lane), each
-// sample is widened to f64 once per quad instead of once per tap, and the integer index math is amortised over
-// four outputs.  The per-output FP64 expression and its operation order are unchanged.
-// Column frames (relative to the tile's first output column): A (raw) starts at -8, B / C at -4, D / E at 0,
-// all row strides are multiples of 4 floats.  Needs tap radii <= 4.
-// ZC (antisymmetric taps only): the centre tap is +0.0 and the centre sample is >= +0 and finite, so the first product c[0] * k[H]
-// is +0 and the first addition +0 + p equals p + 0.0 bit for bit (-0 included): the multiply is dropped, the addition kept.
-template <int NT, int SYM, bool ZC = false>
-__device__ __forceinline__ float corr_regs(const double *c /* centre */, const TapRegs<NT> &t)
-{
-    constexpr int H = NT / 2;
-    static_assert(!ZC || SYM < 0, "centre-tap elision is for the derivative taps");
-    double acc = ZC ? (c[-H] - c[H]) * t.k[0] + 0.0 : c[0] * t.k[H];
-#pragma unroll
-    for (int jj = ZC ? -H + 1 : -H; jj < 0; jj++) {
-        const double pr = SYM > 0 ? c[jj] + c[-jj] : c[jj] - c[-jj];
-        acc = acc + pr * t.k[H + jj];
-    }
-    return (float)acc;
-}
+// (corr_regs, the per-output expression of the register-blocked kernels, and reflect_once live in klt_internal.h: the tracker's level-0
+// gradients on demand use the same text)
 
 // Three aligned quads of an LDS row, widened.  The loads are volatile so that they stay three ds_read_b128: when only 8 or
 // 10 of the 12 samples are used the compiler otherwise narrows them to ds_read2_b32 pairs, and dword reads at a lane stride
@@ -734,7 +708,11 @@ __device__ __forceinline__ void load_taps_here(TapRegs<NT> &r, const size_t arg_
 template <int TW, int SB>
 constexpr int l0_stream_pre_regs() { return (SB * (TW + 32) / 4 + 255) / 256; }
 
-template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE, bool PRO>
+// LEAN (KLT_OPT_L0_LAZY_GRAD): no gradients and no pixel records -- the gradient half of stage 3, stage 4, the DE rows, the Cc carry and
+// their copies are left out, and the interior columns of the band's C rows go to the frame's compact image plane (a.cimg) instead, 16
+// bytes per lane in coalesced rows.  Stages 0-2 and 3b, the halo, the prologue, the reflect map and the prefetch are the full kernel's;
+// the LDS layout too (the DE rows past the carried six still hold B; the rest of that region and Cc lie unused).
+template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE, bool PRO, bool LEAN = false>
 __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
                                                const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[l0_stream_pre_regs<TW, SB>()])
 {
@@ -781,7 +759,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
         }
         if (!PRO) {
             // B rows [0, 2 rs) from Bc; DE rows [SB, SB + 6) -> [0, 6)
-            constexpr int NB = 2 * rs * BQ, NDQ = 6 * (DEW / 4);
+            constexpr int NB = 2 * rs * BQ, NDQ = LEAN ? 0 : 6 * (DEW / 4);
             for (int i = NTHR - 1 - tid; i < NB + NDQ; i += NTHR) {
                 if (i < NB) *reinterpret_cast<float4 *>(B + 4 * i) = *reinterpret_cast<const float4 *>(Bc + 4 * i);
                 else *reinterpret_cast<float4 *>(DE + 4 * (i - NB)) = *reinterpret_cast<const float4 *>(DE + SB * DEW + 4 * (i - NB));
@@ -823,8 +801,25 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     }
     __syncthreads();
     STREAM_MARK(2);
-    // ---- stage 3: horizontal pass of both gradients, C rows [CLO, SB) -> DE rows [CLO + 6, SB + 6)
-    {
+    if constexpr (LEAN) {
+        // ---- stage 3 (lean): the interior columns of C rows [CLO, SB) that belong to the segment -> the compact image plane
+        const plane_rsrc img = plane_of(a.cimg[b]);
+        for (int i = (tid + NTHR / 2) & (NTHR - 1); i < (SB - CLO) * DQ; i += NTHR) {
+            const int r = CLO + i / DQ, q = i % DQ;
+            const int y = cbase + r, x = tx0 + 4 * q;
+            if ((PRO && y < s0) || y >= ylim || (EDGE && x >= nc)) continue;
+            const float4 v = *reinterpret_cast<const float4 *>(C + r * BW + HB + 4 * q);
+            const unsigned ob = band_b0 + __umul24((unsigned)r, row_bytes) + 16u * (unsigned)q;      // byte offset of (y, x)
+            if (!EDGE || x + 3 < nc) {
+                plane_store4(img, ob, make_float2(v.x, v.y), make_float2(v.z, v.w));
+            } else {
+                plane_store(img, ob, v.x);
+                if (x + 1 < nc) plane_store(img, ob + 4, v.y);
+                if (x + 2 < nc) plane_store(img, ob + 8, v.z);
+            }
+        }
+    } else {
+        // ---- stage 3: horizontal pass of both gradients, C rows [CLO, SB) -> DE rows [CLO + 6, SB + 6)
         TapRegs<NG> kg;
         TapRegs<ND> kd;
         load_taps_here(kg, offsetof(SmoothGradArgs, ggauss.k));
@@ -861,7 +856,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
             }
         }
     }
-    if (PRO) return;
+    if (PRO || LEAN) return;
     __syncthreads();
     STREAM_MARK(3);
     // ---- stage 4: vertical pass, output rows [cbase - 3, cbase - 3 + SB); the pixel records (image from C / Cc, gradx, grady) of two
@@ -893,18 +888,18 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     STREAM_MARK(4);
 }
 
-template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE>
+template <typename TIn, int NS, int TW, int SB, bool ZC, bool EDGE, bool LEAN>
 __device__ __forceinline__ void l0_stream_segment(const SmoothGradArgs &a, float *const lds, const int nc, const int nr, const int tx0,
                                                   const int s0, const int ylim)
 {
     uint32_t pre[l0_stream_pre_regs<TW, SB>()];
-    l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, true>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, 1, pre);          // (fills Cc slot 0)
-    for (int y = s0, par = 0; y < ylim; y += SB, par ^= 1) l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, false>(a, lds, nc, nr, tx0, y + 3, s0, ylim, par, pre);
+    l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, true, LEAN>(a, lds, nc, nr, tx0, s0 + 3 - SB, s0, ylim, 1, pre);          // (fills Cc slot 0)
+    for (int y = s0, par = 0; y < ylim; y += SB, par ^= 1) l0_stream_band<TIn, NS, TW, SB, ZC, EDGE, false, LEAN>(a, lds, nc, nr, tx0, y + 3, s0, ylim, par, pre);
 }
 
 // grid = (ceil(ncols / TW), ceil(nrows / seg_h), batch); seg_h a multiple of SB.
 // `a` must stay the FIRST parameter: load_taps_here reads the taps at kernarg offset offsetof(SmoothGradArgs, ...).
-template <typename TIn, int NS, bool ZC, int TW = 64, int SB = 32>
+template <typename TIn, int NS, bool ZC, int TW = 64, int SB = 32, bool LEAN = false>
 __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGradArgs a, int seg_h)
 {
     __shared__ __attribute__((aligned(16))) float lds[StreamLds<NS, TW, SB>::total];
@@ -915,8 +910,8 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
     const int ylim = min(s0 + seg_h, nr);
     const bool inside = tx0 + TW <= nc && tx0 / 4 + TW / 4 <= a.h1_nc;
     STAGE_MARK(0);
-    if (inside) l0_stream_segment<TIn, NS, TW, SB, ZC, false>(a, lds, nc, nr, tx0, s0, ylim);
-    else l0_stream_segment<TIn, NS, TW, SB, ZC, true>(a, lds, nc, nr, tx0, s0, ylim);
+    if (inside) l0_stream_segment<TIn, NS, TW, SB, ZC, false, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
+    else l0_stream_segment<TIn, NS, TW, SB, ZC, true, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
     STAGE_MARK(5);
 }
 
@@ -1198,6 +1193,26 @@ static int l0_stream_seg(bool wide)
     return force > 0 && force % (wide ? L0W_SB : L0S_SB) == 0 ? force : wide ? 128 : 160;
 }
 
+// Which streaming geometry a level-0 launch with the fused reduction takes: 2 = wide strips, 1 = narrow strips, 0 = none (the tile).
+// Wide strips (KLT_OPT_L0_STREAM 2): frames of two wide strips or more and a grid of two rounds of the resident slots at their own
+// segment height; launches that miss either fall through to the narrow strips' rule, and from there to the tile.
+static int l0_stream_geometry(const SmoothGradArgs &a, int batch, int stream)
+{
+    const int shw = l0_stream_seg(true), sh = l0_stream_seg(false);
+    const long long gw = (long long)((a.ncols + L0W_TW - 1) / L0W_TW) * ((a.nrows + shw - 1) / shw) * batch;
+    const long long gs = (long long)((a.ncols + L0S_TW - 1) / L0S_TW) * ((a.nrows + sh - 1) / sh) * batch;
+    if (stream == 2 && a.ncols >= 2 * L0W_TW && gw >= l0_wide_min_wgs()) return 2;
+    if (stream && a.ncols >= 2 * L0S_TW && gs >= L0S_MIN_WGS) return 1;
+    return 0;
+}
+
+// Would launch_smooth_grad send this launch out lean if asked to (a streaming kernel: the fused reduction, specialised taps)?
+bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream)
+{
+    return hred && kind < 2 && a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && a.smooth.sym == 1 &&
+           (a.smooth.n == 5 || a.smooth.n == 9) && l0_stream_geometry(a, batch, stream) != 0;
+}
+
 // The derivative taps' centre is +0.0 and every sample the two derivative passes see is >= +0 (a u8 frame, smoothing and Gaussian
 // taps without sign bits): corr_regs<..., ZC> may drop the centre product
 static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
@@ -1215,8 +1230,10 @@ static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
 // The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
 // *path: the KLT_L0_* code of the kernel launched (klt_level0_path)
 template <typename TIn, bool SMOOTH, int NS>
-static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path)
+static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean)
 {
+    const bool want_lean = *lean;
+    *lean = false;                                           // (set where a lean kernel goes out)
     const dim3 blk(256);
     const bool tall = rb_tall_tiles(a, batch);
     const int th = tall ? 32 : 16;
@@ -1233,7 +1250,16 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
         // height; launches that miss either fall through to the narrow strips' rule, and from there to the tile
         const int shw = l0_stream_seg(true);
         const dim3 gw((a.ncols + L0W_TW - 1) / L0W_TW, (a.nrows + shw - 1) / shw, batch);
-        if (stream == 2 && a.ncols >= 2 * L0W_TW && (long long)gw.x * gw.y * gw.z >= l0_wide_min_wgs()) {
+        const int geom = l0_stream_geometry(a, batch, stream);
+        if (geom == 2) {
+            if (want_lean) {
+                // (the lean form has no derivative pass: one instantiation per input type and tap count, reported under the code the
+                // full launch would get)
+                klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB, true>), gw, blk, 0, s, a, shw);
+                *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_WIDE_NO_CENTRE : KLT_L0_STREAM_WIDE;
+                *lean = true;
+                return 0;
+            }
             if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
                 klt_launch((smooth_grad_stream<TIn, NS, true, L0W_TW, L0W_SB>), gw, blk, 0, s, a, shw);
                 *path = KLT_L0_STREAM_WIDE_NO_CENTRE;
@@ -1245,7 +1271,13 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
         }
         const int sh = l0_stream_seg(false);
         const dim3 gs((a.ncols + L0S_TW - 1) / L0S_TW, (a.nrows + sh - 1) / sh, batch);
-        if (stream && a.ncols >= 2 * L0S_TW && (long long)gs.x * gs.y * gs.z >= L0S_MIN_WGS) {
+        if (geom == 1) {
+            if (want_lean) {
+                klt_launch((smooth_grad_stream<TIn, NS, false, L0S_TW, L0S_SB, true>), gs, blk, 0, s, a, sh);
+                *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_NO_CENTRE : KLT_L0_STREAM;
+                *lean = true;
+                return 0;
+            }
             // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
             if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
                 klt_launch((smooth_grad_stream<TIn, NS, true>), gs, blk, 0, s, a, sh);
@@ -1266,22 +1298,25 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
     return 0;
 }
 
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path)
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean)
 {
     int path_unused;
     if (!path) path = &path_unused;
+    bool lean_unused = false;
+    if (!lean) lean = &lean_unused;
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
     if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
         const int ns = smooth ? a.smooth.n : 1;
-        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path);
-        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path);
-        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path);
-        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path);
-        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path);
-        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path);
+        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path, lean);
         if (hred) return -1;                                     // (smooth_grad_hred_ok admits 5 and 9 smoothing taps only)
     }
+    *lean = false;
     const size_t lds = smooth_grad_lds_bytes(smooth ? a.smooth.n / 2 : -1, a.R);
     const dim3 grid((a.ncols + TW - 1) / TW, (a.nrows + TH - 1) / TH, batch), block(256);
     int e = 0;

@@ -329,17 +329,129 @@ __device__ __forceinline__ float group_tree_sum(float v)
     return v;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// LAZY (7x7, plain kernels): level 0 of a frame is its compact smoothed image alone (a lean level-0 build, pyramid_kernels.hip), and the
+// 16 lanes of a feature make the three record quads of a footprint themselves.  The gradients of an 8 x 8 footprint with corner (cx, cy)
+// need the 14 x 14 image patch around it, rows and columns through the reflect map (scipy reflects the smoothed image when it
+// differentiates it): horizontal pass of both filters at 14 rows x 8 columns (derivative taps -> D, Gaussian taps -> E), f32 rounding,
+// vertical pass at the 8 x 8 footprint (Gaussian taps down D = gradx, derivative taps down E = grady) -- the FP64 expression and the
+// operation order of the level-0 kernels (corr_regs itself, klt_internal.h) without the centre-tap elision, so the values are the
+// records' bit for bit.  The rows and columns of the patch go through reflect_once.  With two or more levels a feature whose patch would
+// leave the frame has left the image at a coarser level before (at subsampling 4 a level-1 window needs 12 pixels of level 0 to the
+// edge, the patch 6), and the features of a wavefront that need nothing are placed at the frame's corner, so in the launches that exist
+// today the map is a safety clamp that keeps every lane's addresses inside the plane, not a path a result depends on.
+// LDS of a feature during the phase: the patch P (14 rows of 16 floats), then D and E (14 rows of 8); it takes the place of the five
+// product arrays, which are dead while it runs.  A feature's region is padded so that two features' lanes fall on different banks.
+constexpr int LZ_PW = 16, LZ_ROWS = 14, LZ_P = LZ_ROWS * LZ_PW, LZ_DE = LZ_ROWS * 8, LZ_FLOATS = LZ_P + 2 * LZ_DE + 16;
+
+// The taps of one gradient filter, read from the kernel argument (the TrackLazyArgs at offset 0 of the kernarg segment) where they are
+// used: the address goes through an empty asm statement so that the scalar loads are not hoisted and held across the Newton loop
+static_assert(sizeof(TrackLazyArgs) == sizeof(TrackArgsBase) + 8 * sizeof(double), "the taps lie right behind the plain kernels' argument");
+// (corr_regs reads the taps left of and at the centre, t.k[0 .. 3] of the seven)
+__device__ __forceinline__ void lazy_taps(TapRegs<7> &t, bool deriv)
+{
+    typedef const __attribute__((address_space(4))) char *kptr;
+    kptr p = (kptr)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(TrackArgsBase) + (deriv ? 4 * sizeof(double) : 0);
+    asm volatile("" : "+s"(p));
+#pragma unroll
+    for (int i = 0; i < 7; i++) t.k[i] = i < 4 ? ((const __attribute__((address_space(4))) double *)p)[i] : 0.0;
+}
+
+// The record quads of lane s = 2 qr + qh (footprint row qr, columns 4 qh .. 4 qh + 3) of the footprint at corner (cx, cy) of `plane`
+// (nc x nr, at least 14 x 14), for the features that `need` them; the other features of the wavefront go through the same steps on the
+// patch at the frame's corner and keep what they hold.  fl: the feature's LDS region.  Every step keeps few values in registers (the
+// kernel around it is close to its register budget): the patch comes in two halves, the vertical pass makes one plane's pixel pair at a time.
+__device__ __forceinline__ void lazy_records(const float *plane, int nc, int nr, int cx, int cy, bool need, float *fl, int s,
+                                             f32x4 &im, f32x4 &gx, f32x4 &gy)
+{
+    {
+        // the patch: lane s takes column cx - 3 + s of the 14 rows (lanes 14 and 15 repeat column 13)
+        const plane_rsrc pl = plane_of(plane);
+        const int x0 = need ? cx - 3 : 0, y0 = need ? cy - 3 : 0;
+        const unsigned col = (unsigned)reflect_once(x0 + (s < 13 ? s : 13), nc);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            float v[LZ_ROWS / 2];
+#pragma unroll
+            for (int r = 0; r < LZ_ROWS / 2; r++)
+                v[r] = plane_load(pl, 4u * (__umul24((unsigned)reflect_once(y0 + 7 * h + r, nr), (unsigned)nc) + col));
+#pragma unroll
+            for (int r = 0; r < LZ_ROWS / 2; r++) fl[(7 * h + r) * LZ_PW + s] = v[r];
+            wave_lds_sync();
+        }
+    }
+    {
+        // horizontal pass: lane s takes footprint column s % 8 of the rows s / 8, s / 8 + 2, ...
+        TapRegs<7> kg, kd;
+        lazy_taps(kg, false);
+        lazy_taps(kd, true);
+        const float *p = fl + (s >> 3) * LZ_PW + (s & 7);
+        float *d = fl + LZ_P + s;
+#pragma unroll 1
+        for (int j = 0; j < LZ_ROWS / 2; j++, p += 2 * LZ_PW, d += 16) {
+            double w[7];
+#pragma unroll
+            for (int i = 0; i < 7; i++) w[i] = (double)p[i];
+            d[0] = corr_regs<7, -1>(w + 3, kd);
+            d[LZ_DE] = corr_regs<7, 1>(w + 3, kg);
+        }
+    }
+    wave_lds_sync();
+    f32x4 oi, ox, oy;
+    {
+        // vertical pass: the lane's own quad -- Gaussian taps down D (gradx), derivative taps down E (grady)
+        const int qr = s >> 1, qh = s & 1;
+        const float *d = fl + LZ_P + qr * 8 + 4 * qh;
+        float o[8];
+#pragma unroll 1
+        for (int u = 0; u < 4; u++) {                        // u = 2 plane + half
+            TapRegs<7> k;
+            lazy_taps(k, u >= 2);
+            const float *c = d + (u >> 1) * LZ_DE + 2 * (u & 1);
+            double w0[7], w1[7];
+#pragma unroll
+            for (int j = 0; j < 7; j++) {
+                const float2 t = *reinterpret_cast<const float2 *>(c + 8 * j);
+                w0[j] = (double)t.x; w1[j] = (double)t.y;
+            }
+            float a0, a1;
+            if (u < 2) { a0 = corr_regs<7, 1>(w0 + 3, k); a1 = corr_regs<7, 1>(w1 + 3, k); }
+            else { a0 = corr_regs<7, -1>(w0 + 3, k); a1 = corr_regs<7, -1>(w1 + 3, k); }
+            // (o[] by a constant index: the loop is not unrolled, so each slot is set under its own test)
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (u == e) { o[2 * e] = a0; o[2 * e + 1] = a1; }
+        }
+        ox.x = o[0]; ox.y = o[1]; ox.z = o[2]; ox.w = o[3];
+        oy.x = o[4]; oy.y = o[5]; oy.z = o[6]; oy.w = o[7];
+        const float *c = fl + (qr + 3) * LZ_PW + 3 + 4 * qh;
+        oi.x = c[0]; oi.y = c[1]; oi.z = c[2]; oi.w = c[3];
+    }
+    wave_lds_sync();
+    if (need) { im = oi; gx = ox; gy = oy; }
+}
+
+// the image values of pixels q .. q + 3 of a compact plane (the residue at a lazy level 0)
+__device__ __forceinline__ f32x4 load_plane_images(const float *plane, unsigned q)
+{
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(plane_of(plane), 4u * q, 0, 0));
+}
+
 // FB: the forward-backward check in the same launch (see track_kernel).  A lane group whose feature is not tracked back -- not live, or
 // lost on the way forward -- idles through the second pass under the predicate that masks a finished feature in the first.
 // (WAVES = occupancy target + GUESS_WAVES for the instantiations with a prior: the plain ones are looked up by the head of their names --
 // batch flag, window, target, sum form -- which has to stay theirs alone; as a shared body under two kernel names the 15x15 kernel took
 // 48 instead of 40 bytes of scratch and four plain instantiations two more SGPRs)
-constexpr int GUESS_WAVES = 8;
+// (LAZY, the instantiations that make their level-0 gradients themselves, carry a mark of their own there for the same reason: WAVES =
+// occupancy target + LAZY_WAVES)
+constexpr int GUESS_WAVES = 8, LAZY_WAVES = 16;
 
 template <bool BATCH, int W, int WAVES = 1, bool TREE = false, bool FB = false, bool GUESS = false>
-__global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(TrackKernArgs<FB, GUESS> a)
+__global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std::conditional_t<(WAVES >= LAZY_WAVES), TrackLazyArgs, TrackKernArgs<FB, GUESS>> a)
 {
-    static_assert(GUESS == (WAVES >= GUESS_WAVES), "instantiations with a prior carry the mark in their occupancy target");
+    constexpr bool LAZY = WAVES >= LAZY_WAVES;
+    static_assert(GUESS == (WAVES >= GUESS_WAVES && !LAZY), "instantiations with a prior carry the mark in their occupancy target");
+    static_assert(!LAZY || (W == 7 && !TREE && !FB && !GUESS), "level-0 gradients on demand: the plain 7x7 kernels only");
     static_assert(W == 7 || W == 15, "quad kernels exist for 7x7 and 15x15 windows");
     static_assert(!(FB && TREE), "the forward-backward check uses the reference-order sums");
     constexpr int FPW = W == 7 ? 4 : 1;                      // features per wavefront
@@ -421,7 +533,17 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(Tra
             // (row * nc as a 24-bit multiply: both are far below 2^24, and the 32-bit integer multiply is a quarter-rate instruction)
             const unsigned q1 = run ? __umul24((unsigned)(b1.iy - hw + qr), (unsigned)nc) + (unsigned)(b1.ix - hw + 4 * qh) : 0u;   // 32-bit element offsets: scalar base + vector offset loads
             f32x4 t_qi, t_qgx, t_qgy;
-            load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
+            float *const fl = lds + g * LZ_FLOATS;               // LAZY: this feature's patch and gradient intermediates
+            if constexpr (LAZY) {
+                if (r == 0) {
+                    t_qi = f32x4{0.f, 0.f, 0.f, 0.f}; t_qgx = t_qi; t_qgy = t_qi;
+                    lazy_records(lv.i1, nc, nr, b1.ix - hw, b1.iy - hw, run, fl, s, t_qi, t_qgx, t_qgy);
+                } else {
+                    load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
+                }
+            } else {
+                load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
+            }
 
             // the first Newton iteration starts from a position that is already known: its bounds test (trackFeaturesUtils.pyx:428-431)
             // and its footprint loads go out now, behind the template's
@@ -444,6 +566,16 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(Tra
                 b2 = make_bilinear(x2, y2);
                 if (REUSE) {
                     const unsigned q = __umul24((unsigned)(b2.iy - hw + qr), (unsigned)nc) + (unsigned)(b2.ix - hw + 4 * qh);
+                    if constexpr (LAZY) {
+                        if (r == 0) {
+                            const bool need = iterating && q != q_held;
+                            if (__any(need)) lazy_records(lv.i2, nc, nr, b2.ix - hw, b2.iy - hw, need, fl, s, s_qi, s_qgx, s_qgy);
+                            if (need) q_held = q;
+                        } else if (iterating && q != q_held) {
+                            load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
+                            q_held = q;
+                        }
+                    } else
                     if (iterating && q != q_held) {
                         load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
                         q_held = q;
@@ -528,6 +660,9 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(Tra
                 if (REUSE) {
                     const unsigned q = __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh);
                     r_qi = s_qi;                                 // the last footprint, if the final position has the same integer corner
+                    if constexpr (LAZY) {
+                        if (need_res && q != q_held) r_qi = r == 0 ? load_plane_images(lv.i2, q) : load_record_images(lv.i2, q);
+                    } else
                     if (need_res && q != q_held) r_qi = load_record_images(lv.i2, q);
                 } else {
                     const unsigned q = need_res ? __umul24((unsigned)(br.iy - hw + qr), (unsigned)nc) + (unsigned)(br.ix - hw + 4 * qh) : 0u;
@@ -717,6 +852,13 @@ int g_track_variant = getenv("KLT_TRACK_VARIANT") ? atoi(getenv("KLT_TRACK_VARIA
 
 // FB: the forward-backward kernels (klt_track_fb_async), chosen by the same rules; they have no tree-sum form
 // GUESS: the kernels with a motion prior (klt_track_guess*), chosen by the same rules again
+// Does a launch take the 7x7 quad kernel?  (short 7x7 lists keep one feature per wavefront: with a few hundred features the launch is pure
+// latency, which four features in lock step lengthen)
+static bool track_quad7_rule(int window, int n, int npairs)
+{
+    return g_track_variant != 0 && window == 7 && (long long)n * npairs >= 2048;
+}
+
 template <bool BATCH, bool FB, bool GUESS, class Args>
 static int launch_track_t(hipStream_t s, const Args &a)
 {
@@ -731,7 +873,7 @@ static int launch_track_t(hipStream_t s, const Args &a)
         hipLaunchKernelGGL(track_order_kernel, dim3(ny), dim3(ORDER_T), 0, s, a.in, BATCH ? a.pairs : nullptr, a.n, a.order);
     // (short 7x7 lists keep one feature per wavefront: with a few hundred features the launch is pure latency, which four
     // features in lock step lengthen)
-    if (g_track_variant != 0 && a.window == 7 && (long long)a.n * ny >= 2048) {
+    if (track_quad7_rule(a.window, a.n, (int)ny)) {
         const dim3 gq(a.order ? 8 * ((a.order_chunk + 3) / 4) : (a.n + 3) / 4, ny);
         // (occupancy targets 5 / 6 for this kernel -- 96 / 80 VGPRs with 84 / 172 bytes of scratch per lane instead of 122 VGPRs -- were
         // measured again in round 3 on eight-pair launches, 10 000 wavefronts, where a fifth resident wavefront per SIMD could hide
@@ -863,6 +1005,26 @@ int launch_track(hipStream_t s, const TrackArgs &a)
     }
     if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false, false>(s, a) : 0;
     return launch_track_t<false, false, false>(s, a);
+}
+
+// (the rule of launch_track_t for the plain 7x7 quad kernel with the reference-order sums)
+bool track_lazy_capable(int window, int tree_sums, int n, int npairs)
+{
+    return track_quad7_rule(window, n, npairs) && !tree_sums && n > 0 && npairs > 0;
+}
+
+int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a)
+{
+    const unsigned ny = a.pairs ? a.npairs : 1;
+    if (!track_lazy_capable(a.window, a.tree_sums, a.n, (int)ny)) return -1;
+    if (a.order && a.order_refresh)
+        hipLaunchKernelGGL(track_order_kernel, dim3(ny), dim3(ORDER_T), 0, s, a.in, a.pairs ? a.pairs : nullptr, a.n, a.order);
+    const dim3 gq(a.order ? 8 * ((a.order_chunk + 3) / 4) : (a.n + 3) / 4, ny), block(64);
+    // LDS: the four features' product arrays or, at level 0, their patches (the larger of the two)
+    constexpr unsigned lds = (unsigned)(4 * sizeof(float) * (LZ_FLOATS > 5 * track_npad(49) ? LZ_FLOATS : 5 * track_npad(49)));
+    if (a.pairs) klt_launch((track_kernel_quad<true, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
+    else klt_launch((track_kernel_quad<false, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
+    return 0;
 }
 
 int launch_track_guess(hipStream_t s, const TrackGuessArgs &a)
