@@ -137,6 +137,13 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
  *      resident or streamed frames goes lean from its second build on.
  *   2: always lean where a streaming kernel is launched (for tests). */
 #define KLT_OPT_L0_LAZY_GRAD 22
+/* Which kernel a lean launch takes.  1: the wave form (smooth_grad_lean_wave: a wavefront owns a 232-column strip and walks it down a
+ * segment of KLT_L0_LEAN_WAVE_SEG rows on its own, no workgroup barrier) where the frames have >= 256 columns and at least as many rows
+ * as smoothing taps, the banded form elsewhere; 0: always the banded form (the streaming kernel without its gradient passes).  Which
+ * builds go lean does not depend on it, and the planes are the same bit for bit. */
+#define KLT_OPT_L0_LEAN_FORM 23
+#define KLT_L0_LEAN_FORM_DEFAULT 1
+#define KLT_L0_LEAN_WAVE_SEG 32     /* segment height of the wave form, rows (pyfeaturetrack_amd/_abi.py carries the same figure) */
 int klt_set_option(klt_ctx *ctx, int option, int value);
 
 /* ---- parameters and taps ------------------------------------------------------------------- */
@@ -224,6 +231,9 @@ int klt_level0_path(klt_ctx *ctx, int *merged_grad);
 /* *lean = 1 if the last geometry group of the last build went out lean (KLT_OPT_L0_LAZY_GRAD; klt_level0_path reports the code of the
  * streaming geometry as for a full launch), else 0.  KLT_ERR_STATE before the first build. */
 int klt_level0_lean(klt_ctx *ctx, int *lean);
+/* *form = which kernel that group's level-0 launch was: 0 not lean, 1 the banded lean form, 2 the wave form (KLT_OPT_L0_LEAN_FORM).
+ * KLT_ERR_STATE before the first build. */
+int klt_level0_lean_form(klt_ctx *ctx, int *form);
 /* bit 0: the slot holds a frame; bit 1: its pyramids are built and match the current parameters / taps (what
  * `tc.pyramid_last is not None` means in the reference, trackFeatures.py:152); 0 for a slot never used */
 int klt_slot_state(klt_ctx *ctx, int slot);

@@ -8,6 +8,10 @@ import ctypes as C
 import os
 
 KLT_MAX_LEVELS = 8
+# the lean level-0 kernel's wave form (include/klt_gpu.h): option code, output columns of a wavefront's strip, rows of a segment
+KLT_OPT_L0_LEAN_FORM = 23
+L0_LEAN_WAVE_COLS = 232
+L0_LEAN_WAVE_SEG = 32              # KLT_L0_LEAN_WAVE_SEG
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkltgpu.so")
 
@@ -115,6 +119,7 @@ SYMBOLS = {
     "klt_build_pyramids": (_I, [_P, _I]),
     "klt_level0_path": (_I, [_P, _PI]),
     "klt_level0_lean": (_I, [_P, _PI]),
+    "klt_level0_lean_form": (_I, [_P, _PI]),
     "klt_slot_state": (_I, [_P, _I]),
     "klt_device_memory": (_I, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "klt_slot_generation": (_I, [_P, _I, C.POINTER(C.c_uint64)]),

@@ -383,6 +383,13 @@ class Context:
         self._check(self._lib.klt_level0_lean(self._h, C.byref(lean)))
         return bool(lean.value)
 
+    def level0_lean_form(self):
+        """Which kernel that group's level-0 launch was: 0 not lean, 1 the banded lean form, 2 the wave form (klt_level0_lean_form,
+        KLT_OPT_L0_LEAN_FORM; a diagnostic -- every form gives the same planes)"""
+        form = C.c_int()
+        self._check(self._lib.klt_level0_lean_form(self._h, C.byref(form)))
+        return form.value
+
     def set_option(self, option, value):
         self._check(self._lib.klt_set_option(self._h, option, int(value)))
 

@@ -269,6 +269,7 @@ int klt_create(int device, klt_ctx **out)
     c->work = c->stream;
     if (const char *v = getenv("KLT_FUSED_HREDUCE")) c->fuse_hreduce = atoi(v) != 0;      // experiment hook (initial value of the option)
     if (const char *v = getenv("KLT_L0_STREAM")) c->l0_stream = atoi(v) == 2 ? 2 : atoi(v) != 0;
+    if (const char *v = getenv("KLT_L0_LEAN_FORM")) c->l0_lean_form_opt = atoi(v) != 0;
     if (const char *v = getenv("KLT_TRACK_XCD_ORDER")) c->track_xcd_order = atoi(v) != 0;
     if (const char *v = getenv("KLT_COPY_STREAMS")) { const int k = atoi(v); c->ncopy = k < 1 ? 1 : (k > klt_ctx::kMaxCopyStreams ? klt_ctx::kMaxCopyStreams : k); }
     *out = c;
@@ -360,6 +361,11 @@ int klt_set_option(klt_ctx *c, int option, int value)
     if (option == KLT_OPT_L0_LAZY_GRAD) {
         if (value < 0 || value > 2) return fail(c, KLT_ERR_ARG, "KLT_OPT_L0_LAZY_GRAD takes 0, 1 or 2");
         c->l0_lazy_grad = value;
+        return KLT_OK;
+    }
+    if (option == KLT_OPT_L0_LEAN_FORM) {
+        if (value < 0 || value > 1) return fail(c, KLT_ERR_ARG, "KLT_OPT_L0_LEAN_FORM takes 0 or 1");
+        c->l0_lean_form_opt = value;
         return KLT_OK;
     }
     if (option == KLT_OPT_TRACK_XCD_ORDER) { c->track_xcd_order = value != 0; return KLT_OK; }

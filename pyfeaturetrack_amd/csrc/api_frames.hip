@@ -204,7 +204,8 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
     // (a lean launch writes the image alone, no gradients)
     TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + (lean ? 0.0 : N * 12) + (hred ? 4.0 * N : 0.0));
     bool went_lean = lean;
-    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path, &went_lean))
+    c->l0_launch_form = c->l0_lean_form_opt;
+    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path, &went_lean, &c->l0_launch_form))
         return fail(c, KLT_ERR_DEVICE, std::string("smooth_grad launch: ") + hipGetErrorString((hipError_t)e));
     if (went_lean != lean) return fail(c, KLT_ERR_STATE, "level-0 launch: lean form not as planned");
     return 0;
@@ -390,6 +391,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         c->l0_path = l0_path;
         c->l0_merged_grad = merged_grad;
         c->l0_lean = lean;
+        c->l0_lean_form = lean ? c->l0_launch_form : 0;
         // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
         // then the gradients of the new level.  Only surviving columns / rows are evaluated.
         for (int l = 1; l < s0->nlev; l++) {
@@ -731,6 +733,14 @@ int klt_level0_path(klt_ctx *c, int *merged_grad)
     if (c->l0_path < 0) return fail(c, KLT_ERR_STATE, "no pyramid build yet");
     if (merged_grad) *merged_grad = c->l0_merged_grad ? 1 : 0;
     return c->l0_path;
+}
+
+int klt_level0_lean_form(klt_ctx *c, int *form)
+{
+    if (!c || !form) return fail(c, KLT_ERR_ARG, "null argument");
+    if (c->l0_path < 0) return fail(c, KLT_ERR_STATE, "no pyramid build yet");
+    *form = c->l0_lean_form;
+    return KLT_OK;
 }
 
 int klt_level0_lean(klt_ctx *c, int *lean)

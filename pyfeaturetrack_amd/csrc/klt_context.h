@@ -195,6 +195,9 @@ struct klt_ctx {
     bool l0_merged_grad = false;              // ... and whether that group's gradients of levels >= 1 went out as one launch
     int l0_lazy_grad = 1;                     // KLT_OPT_L0_LAZY_GRAD: 0 never lean, 1 adaptive, 2 lean wherever a streaming kernel is launched
     bool l0_lean = false;                     // klt_level0_lean: that group went out lean
+    int l0_lean_form_opt = KLT_L0_LEAN_FORM_DEFAULT;   // KLT_OPT_L0_LEAN_FORM: 1 the wave form where it applies, 0 the banded form
+    int l0_lean_form = 0;                     // klt_level0_lean_form: 0 not lean, 1 banded, 2 wave (that group's launch)
+    int l0_launch_form = 0;                   // ... of the last level-0 launch (enqueue_fused_smooth_grad)
     uint64_t cfg_gen = 1;                     // counts the changes of the taps and of the pyramid's shape (Slot::built_cfg)
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)

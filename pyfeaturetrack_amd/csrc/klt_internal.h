@@ -313,10 +313,12 @@ size_t pyr_reduce_lds_bytes(int ss, int ntaps);
 // kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image gradients only, 3 = u8 image gradients only
 // stream: the streaming level-0 kernel where it applies (KLT_OPT_L0_STREAM: 1 = 64-column strips, 2 = 128-column strips where they apply)
 // *path (optional): which kernel went out, a KLT_L0_* code of include/klt_gpu.h
+// *lean_form (optional, in/out): in = 1: a lean launch takes the wave form where it applies (KLT_OPT_L0_LEAN_FORM); out = 0 not lean, 1 the
+// banded lean form, 2 the wave form
 // *lean (optional, in/out): in = the caller would take the lean form of a streaming kernel (no gradients, no records: the smoothed image
 // goes to the compact planes a.cimg instead); out = whether that is what went out (the tiled kernels have no lean form)
 int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, int stream = 0, int *path = nullptr,
-                       bool *lean = nullptr);
+                       bool *lean = nullptr, int *lean_form = nullptr);
 bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss);
 bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream);      // a launch asked to be lean would be
 int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch);

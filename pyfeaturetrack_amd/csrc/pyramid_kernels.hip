@@ -22,6 +22,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "klt_internal.h"
 
@@ -856,7 +857,10 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
             }
         }
     }
-    if (PRO || LEAN) return;
+    if (PRO || LEAN) {
+        STREAM_MARK(3);                                          // (lean: the plane stores and stage 3b)
+        return;
+    }
     __syncthreads();
     STREAM_MARK(3);
     // ---- stage 4: vertical pass, output rows [cbase - 3, cbase - 3 + SB); the pixel records (image from C / Cc, gradx, grady) of two
@@ -913,6 +917,198 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
     if (inside) l0_stream_segment<TIn, NS, TW, SB, ZC, false, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
     else l0_stream_segment<TIn, NS, TW, SB, ZC, true, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
     STAGE_MARK(5);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Lean level-0 kernel, wave form (KLT_OPT_L0_LEAN_FORM): what smooth_grad_stream<..., LEAN> computes -- the smoothed image to the compact
+// plane a.cimg and the horizontal pass of the first pyramid reduction to a.h1 -- with no workgroup barrier and no plane staged through
+// LDS.  The lean banded kernel encloses 40 % of the full kernel's work in the full kernel's four barriers per band and runs at 0.64 of
+// its VALU issue time (profiles/README.md); here a WAVEFRONT owns a strip and walks it down a segment of rows on its own.
+//   Lane l owns the four columns x0 - 12 + 4 l ... + 3 of the strip at x0 = 232 * strip: lanes 3..60 are the strip's 232 output
+//   columns, lanes 0-2 and 61-63 the 12-column halo of the 21-tap reduction.  Per row: the lane's raw quad (requested PD rows ahead,
+//   held in registers), the samples left and right of it from the neighbouring lanes (ds_bpermute), the horizontal smoothing of the four
+//   columns into a rotating window of the last NS H-smoothed rows in registers (the row loop is unrolled NS times, so the window's
+//   indices are compile-time; kept widened for 5 taps, f32 and widened at use for 9), the vertical smoothing from the window, one
+//   16-byte store to the compact plane, and the same quad into a 1 KB row of LDS that only this wavefront touches, from which the lane
+//   reads the rest of its 21-sample window (quads l - 2 .. l + 2 and the first sample of l + 3) for the H1 sample at column 4 l + 2 of
+//   its quad.  One wavefront's LDS operations complete in order: s_waitcnt is all that orders the row's store and its loads.
+// The NS - 1 rows above a segment are H-smoothed again (stage 1 only).  Rows go through the reflect map on the row index.  The first and
+// the last strip of a frame, and frames whose width is no multiple of 4, read element by element through reflect_once and predicate
+// their stores (EDGE).  Same virtual coordinates, expressions and operation order as the banded kernel (corr_quad, corr_regs and
+// hreduce_pair's sum), so the same values (header of this file).  The host takes it for frames of >= 256 columns and >= NS rows: one
+// reflection brings every index inside (columns reach 245 past the last strip's first, rows NS / 2 past either end).
+constexpr int LW_COLS = 232, LW_HALO = 12, LW_WAVES = 4;         // output columns of a strip, halo columns a side, wavefronts per workgroup
+
+// The raw samples of one row and lane in flight: the RawQuad register of the aligned path, four zero-extended bytes of a u8 edge strip
+template <typename TIn, bool EDGE> struct WaveRaw { typedef typename RawQuad<TIn>::reg reg; };
+template <> struct WaveRaw<uint8_t, true> { typedef uint4 reg; };
+__device__ __forceinline__ uint32_t wave_quad(uint4 e) { return e.x | e.y << 8 | e.z << 16 | e.w << 24; }
+__device__ __forceinline__ uint32_t wave_quad(uint32_t w) { return w; }
+__device__ __forceinline__ float4 wave_quad(float4 v) { return v; }
+
+__device__ __forceinline__ float lane_read(int lane_b /* 4 x source lane */, float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(lane_b, __builtin_bit_cast(int, v)));
+}
+
+template <typename TIn, int NS, bool EDGE>
+__device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float *const wrow /* 2 x 256 floats of this wavefront */, const int b,
+                                                  const int nc, const int nr, const int x0, const int s0, const int ylim)
+{
+    constexpr int rs = NS / 2, PD = NS % 3 == 0 ? 3 : NS;        // rows in flight: a divisor of the unroll count
+    constexpr int NR = 21, HR = NR / 2;
+    constexpr bool U8 = sizeof(TIn) == 1, NXT = rs > 3;          // (NXT: lane 63's first output reads one sample past its quad)
+    typedef typename WaveRaw<TIn, EDGE>::reg raw_t;
+    typedef typename std::conditional<(NS <= 5), double, float>::type win_t;
+    typedef volatile __attribute__((address_space(3))) f32x4 *lds_quad_ptr;
+    typedef const volatile __attribute__((address_space(3))) float *lds_f32_ptr;
+    const int lane = threadIdx.x & 63;
+    const int cx = x0 - LW_HALO + 4 * lane;                      // the lane's first column (virtual)
+    const bool out_lane = lane >= LW_HALO / 4 && lane < 64 - LW_HALO / 4;
+    const plane_rsrc rawp = plane_of(a.raw[b]), img = plane_of(a.cimg[b]), h1 = plane_of(a.h1[b]);
+    const int h1_nc = a.h1_nc;
+    const unsigned raw_row_b = (unsigned)nc * (unsigned)sizeof(TIn);
+    // byte offsets of the lane's columns in a raw row: the quad's (aligned path) or each element's through the reflect map; `xn`: the
+    // sample right of lane 63's quad
+    unsigned xo[EDGE ? 4 : 1];
+    if constexpr (EDGE) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) xo[k] = (unsigned)reflect_once(cx + k, nc) * (unsigned)sizeof(TIn);
+    } else {
+        xo[0] = (unsigned)cx * (unsigned)sizeof(TIn);
+    }
+    const unsigned xn = (unsigned)(EDGE ? reflect_once(cx + 4, nc) : cx + 4) * (unsigned)sizeof(TIn);
+    const int prev_b = 4 * max(lane - 1, 0), next_b = 4 * min(lane + 1, 63);
+    // LDS: quads l - 2, l - 1, l + 1, l + 2 and the first float of l + 3 (clamped: the halo lanes' H1 samples are not stored)
+    const int q_m2 = 4 * max(lane - 2, 0), q_m1 = 4 * max(lane - 1, 0), q_p1 = 4 * min(lane + 1, 63), q_p2 = 4 * min(lane + 2, 63),
+              q_p3 = 4 * min(lane + 3, 63);
+    const int T = ylim - s0 + 2 * rs;                            // H-smoothed rows of the segment: step t makes frame row s0 - rs + t
+
+    auto request = [&](int t, raw_t &q, float &nx) {
+        const unsigned row_b = (unsigned)reflect_once(s0 - rs + t, nr) * raw_row_b;
+        if constexpr (!EDGE) {
+            if constexpr (U8) q = __builtin_amdgcn_raw_buffer_load_b32(rawp, row_b + xo[0], 0, 0);
+            else q = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rawp, row_b + xo[0], 0, 0));
+        } else if constexpr (U8) {
+            q.x = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rawp, row_b + xo[0], 0, 0); q.y = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rawp, row_b + xo[1], 0, 0);
+            q.z = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rawp, row_b + xo[2], 0, 0); q.w = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rawp, row_b + xo[3], 0, 0);
+        } else {
+            q.x = plane_load(rawp, row_b + xo[0]); q.y = plane_load(rawp, row_b + xo[1]);
+            q.z = plane_load(rawp, row_b + xo[2]); q.w = plane_load(rawp, row_b + xo[3]);
+        }
+        if constexpr (NXT) {
+            if (lane == 63) {
+                if constexpr (U8) nx = (float)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rawp, row_b + xn, 0, 0);
+                else nx = plane_load(rawp, row_b + xn);
+            }
+        }
+    };
+
+    TapRegs<NS> ks;
+    TapRegs<HR + 1> kr;
+    load_taps(ks, a.smooth);
+    load_taps(kr, a.reduce);
+    raw_t pre[PD];
+    float nxt[PD] = {};
+#pragma unroll
+    for (int u = 0; u < PD; u++)
+        if (u < T) request(u, pre[u], nxt[u]);
+    win_t win[NS][4];
+    for (int t0 = 0; t0 < T; t0 += NS) {
+#pragma unroll
+        for (int u = 0; u < NS; u++) {
+            const int t = t0 + u;
+            if (t >= T) break;
+            // ---- the row's raw samples: the lane's quad, and the quads of its neighbours
+            const typename RawQuad<TIn>::reg w = wave_quad(pre[u % PD]);
+            const float nx = nxt[u % PD];
+            if (t + PD < T) request(t + PD, pre[u % PD], nxt[u % PD]);
+            float4 mid = quad_f32(w), lo, hi;
+            if constexpr (U8) {
+                lo = unpack_u8x4((uint32_t)__builtin_amdgcn_ds_bpermute(prev_b, (int)w));
+                hi = unpack_u8x4((uint32_t)__builtin_amdgcn_ds_bpermute(next_b, (int)w));
+            } else {
+                lo.x = rs > 3 ? lane_read(prev_b, mid.x) : 0.f; lo.y = rs > 2 ? lane_read(prev_b, mid.y) : 0.f;
+                lo.z = rs > 1 ? lane_read(prev_b, mid.z) : 0.f; lo.w = lane_read(prev_b, mid.w);
+                hi.x = lane_read(next_b, mid.x); hi.y = rs > 1 ? lane_read(next_b, mid.y) : 0.f;
+                hi.z = rs > 2 ? lane_read(next_b, mid.z) : 0.f; hi.w = rs > 3 ? lane_read(next_b, mid.w) : 0.f;
+            }
+            if constexpr (NXT) if (lane == 63) hi.x = nx;
+            // ---- horizontal smoothing of the four columns -> the window's slot u
+            {
+                double v[12];
+                v[0] = (double)lo.x; v[1] = (double)lo.y; v[2] = (double)lo.z; v[3] = (double)lo.w;
+                v[4] = (double)mid.x; v[5] = (double)mid.y; v[6] = (double)mid.z; v[7] = (double)mid.w;
+                v[8] = (double)hi.x; v[9] = (double)hi.y; v[10] = (double)hi.z; v[11] = (double)hi.w;
+                const float4 hq = corr_quad<NS, 1>(v, ks);
+                win[u][0] = (win_t)hq.x; win[u][1] = (win_t)hq.y; win[u][2] = (win_t)hq.z; win[u][3] = (win_t)hq.w;
+            }
+            if (t < 2 * rs) continue;
+            // ---- vertical smoothing: frame row y from the window (the row rs + j below y's first sits in slot (u + 1 + j) mod NS)
+            const int y = s0 + t - 2 * rs;
+            float c[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                double v[NS];
+#pragma unroll
+                for (int j = 0; j < NS; j++) v[j] = (double)win[(u + 1 + j) % NS][k];
+                c[k] = corr_regs<NS, 1>(v + rs, ks);
+            }
+            if (out_lane) {
+                const unsigned ob = 4u * ((unsigned)y * (unsigned)nc + (unsigned)cx);
+                if (!EDGE || cx + 3 < nc) {
+                    plane_store4(img, ob, make_float2(c[0], c[1]), make_float2(c[2], c[3]));
+                } else {
+                    if (cx < nc) plane_store(img, ob, c[0]);
+                    if (cx + 1 < nc) plane_store(img, ob + 4, c[1]);
+                    if (cx + 2 < nc) plane_store(img, ob + 8, c[2]);
+                }
+            }
+            // ---- the H1 sample at column cx + 2: the row through this wavefront's LDS slot (by row parity), then the 21-tap sum
+            float *const slot = wrow + (t & 1) * 256;
+            f32x4 cq;
+            cq.x = c[0]; cq.y = c[1]; cq.z = c[2]; cq.w = c[3];
+            *(lds_quad_ptr)(slot + 4 * lane) = cq;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const f32x4 qa = *(lds_quad_ptr)(slot + q_m2), qb = *(lds_quad_ptr)(slot + q_m1), qd = *(lds_quad_ptr)(slot + q_p1),
+                        qe = *(lds_quad_ptr)(slot + q_p2);
+            const float qf = *(lds_f32_ptr)(slot + q_p3);
+            double m[NR];
+            m[0] = (double)qa.x; m[1] = (double)qa.y; m[2] = (double)qa.z; m[3] = (double)qa.w;
+            m[4] = (double)qb.x; m[5] = (double)qb.y; m[6] = (double)qb.z; m[7] = (double)qb.w;
+            m[8] = (double)c[0]; m[9] = (double)c[1]; m[10] = (double)c[2]; m[11] = (double)c[3];
+            m[12] = (double)qd.x; m[13] = (double)qd.y; m[14] = (double)qd.z; m[15] = (double)qd.w;
+            m[16] = (double)qe.x; m[17] = (double)qe.y; m[18] = (double)qe.z; m[19] = (double)qe.w;
+            m[20] = (double)qf;
+            double acc = m[HR] * kr.k[HR];                       // (hreduce_pair's sum at the centre m[HR])
+#pragma unroll
+            for (int jj = -HR; jj < 0; jj++) acc = acc + (m[HR + jj] + m[HR - jj]) * kr.k[HR + jj];
+            const int xg = cx / 4;
+            if (out_lane && (!EDGE || xg < h1_nc)) plane_store(h1, 4u * ((unsigned)y * (unsigned)h1_nc + (unsigned)xg), (float)acc);
+        }
+    }
+}
+
+// grid = ceil(units / 4) workgroups of four wavefronts; unit = (frame * nsegs + segment) * nstrips + strip, any four units to a workgroup
+// (a wavefront per SIMD).  `a` stays the first parameter, as for smooth_grad_stream.
+template <typename TIn, int NS>
+__global__ __launch_bounds__(64 * LW_WAVES, KLT_L0_WAVES) void smooth_grad_lean_wave(SmoothGradArgs a, int seg_h, int nstrips, int nsegs, int nunits)
+{
+    __shared__ __attribute__((aligned(16))) float lds[LW_WAVES * 2 * 256];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int unit = blockIdx.x * LW_WAVES + wave;
+    if (unit >= nunits) return;
+    const int strip = unit % nstrips, rest = unit / nstrips, seg = rest % nsegs, b = rest / nsegs;
+    const int nc = a.dim_c[b] ? a.dim_c[b] : a.ncols, nr = a.dim_r[b] ? a.dim_r[b] : a.nrows;
+    const int x0 = strip * LW_COLS, s0 = seg * seg_h;
+    if (x0 >= nc || s0 >= nr) return;
+    const int ylim = min(s0 + seg_h, nr);
+    // every column the strip reads inside the frame, its quads aligned
+    const bool inside = (nc & 3) == 0 && x0 >= LW_HALO && x0 + LW_COLS + LW_HALO + (NS / 2 > 3 ? 4 : 0) <= nc && x0 / 4 + LW_COLS / 4 <= a.h1_nc;
+    if (inside) lean_wave_segment<TIn, NS, false>(a, lds + wave * 512, b, nc, nr, x0, s0, ylim);
+    else lean_wave_segment<TIn, NS, true>(a, lds + wave * 512, b, nc, nr, x0, s0, ylim);
 }
 
 // The f32-rounded horizontal result is kept in LDS as the double it widens to (one widening per sample instead of one
@@ -1206,6 +1402,31 @@ static int l0_stream_geometry(const SmoothGradArgs &a, int batch, int stream)
     return 0;
 }
 
+// The wave form of a lean launch (smooth_grad_lean_wave): segment height in rows, the fastest of its sweep (profiles/README.md; the constant is
+// KLT_L0_LEAN_WAVE_SEG of include/klt_gpu.h).  KLT_L0_SEG overrides it: experiment hook.
+static int l0_wave_seg()
+{
+    static const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0;
+    return force > 0 ? force : KLT_L0_LEAN_WAVE_SEG;
+}
+
+// Does a lean launch that asks for the wave form get it?  Frames of >= 256 columns and at least one vertical window high (one reflection
+// brings every index of a strip inside), all of one size.
+bool smooth_grad_lean_wave_ok(const SmoothGradArgs &a, int batch)
+{
+    for (int b = 0; b < batch; b++)
+        if (a.dim_c[b] || a.dim_r[b]) return false;
+    return a.ncols >= 256 && a.nrows >= a.smooth.n;
+}
+
+template <typename TIn, int NS>
+static void launch_lean_wave(hipStream_t s, const SmoothGradArgs &a, int batch)
+{
+    const int seg = l0_wave_seg();
+    const int nstrips = (a.ncols + LW_COLS - 1) / LW_COLS, nsegs = (a.nrows + seg - 1) / seg, nunits = nstrips * nsegs * batch;
+    klt_launch((smooth_grad_lean_wave<TIn, NS>), dim3((nunits + LW_WAVES - 1) / LW_WAVES), dim3(64 * LW_WAVES), 0, s, a, seg, nstrips, nsegs, nunits);
+}
+
 // Would launch_smooth_grad send this launch out lean if asked to (a streaming kernel: the fused reduction, specialised taps)?
 bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream)
 {
@@ -1230,10 +1451,14 @@ static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
 // The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
 // *path: the KLT_L0_* code of the kernel launched (klt_level0_path)
 template <typename TIn, bool SMOOTH, int NS>
-static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean)
+static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean,
+                                 int *lean_form)
 {
     const bool want_lean = *lean;
     *lean = false;                                           // (set where a lean kernel goes out)
+    // a lean launch takes the wave form where it is asked for and applies, else the banded form of the geometry's kernel
+    const bool wave = *lean_form == 1 && smooth_grad_lean_wave_ok(a, batch);
+    *lean_form = 0;
     const dim3 blk(256);
     const bool tall = rb_tall_tiles(a, batch);
     const int th = tall ? 32 : 16;
@@ -1255,7 +1480,9 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
             if (want_lean) {
                 // (the lean form has no derivative pass: one instantiation per input type and tap count, reported under the code the
                 // full launch would get)
-                klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB, true>), gw, blk, 0, s, a, shw);
+                if (wave) launch_lean_wave<TIn, NS>(s, a, batch);
+                else klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB, true>), gw, blk, 0, s, a, shw);
+                *lean_form = wave ? 2 : 1;
                 *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_WIDE_NO_CENTRE : KLT_L0_STREAM_WIDE;
                 *lean = true;
                 return 0;
@@ -1273,7 +1500,9 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
         const dim3 gs((a.ncols + L0S_TW - 1) / L0S_TW, (a.nrows + sh - 1) / sh, batch);
         if (geom == 1) {
             if (want_lean) {
-                klt_launch((smooth_grad_stream<TIn, NS, false, L0S_TW, L0S_SB, true>), gs, blk, 0, s, a, sh);
+                if (wave) launch_lean_wave<TIn, NS>(s, a, batch);
+                else klt_launch((smooth_grad_stream<TIn, NS, false, L0S_TW, L0S_SB, true>), gs, blk, 0, s, a, sh);
+                *lean_form = wave ? 2 : 1;
                 *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_NO_CENTRE : KLT_L0_STREAM;
                 *lean = true;
                 return 0;
@@ -1298,25 +1527,28 @@ static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int bat
     return 0;
 }
 
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean)
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean, int *lean_form)
 {
     int path_unused;
     if (!path) path = &path_unused;
     bool lean_unused = false;
     if (!lean) lean = &lean_unused;
+    int form_unused = 0;
+    if (!lean_form) lean_form = &form_unused;
     const bool smooth = kind < 2;
     // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
     if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
         const int ns = smooth ? a.smooth.n : 1;
-        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path, lean);
-        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path, lean);
-        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path, lean);
-        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path, lean);
-        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path, lean);
-        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path, lean);
+        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path, lean, lean_form);
+        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path, lean, lean_form);
+        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path, lean, lean_form);
+        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path, lean, lean_form);
+        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path, lean, lean_form);
+        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path, lean, lean_form);
         if (hred) return -1;                                     // (smooth_grad_hred_ok admits 5 and 9 smoothing taps only)
     }
     *lean = false;
+    *lean_form = 0;
     const size_t lds = smooth_grad_lds_bytes(smooth ? a.smooth.n / 2 : -1, a.R);
     const dim3 grid((a.ncols + TW - 1) / TW, (a.nrows + TH - 1) / TH, batch), block(256);
     int e = 0;

@@ -3,6 +3,9 @@
 // streaming kernel, `w`: the streaming kernel on 128-column strips (per-stage ticks summed over the bands of one segment), all on 16 1080p u8 frames into planes of pixel records
 // as at cfg-2 (`p`, the tiled kernel without the fused reduction, also writes the compact image copy the build then asks for).  Build (from the repo root):
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DKLT_STAGE_CLOCKS -Iinclude -Ipyfeaturetrack_amd/csrc tools/mb/l0_stages.hip -o tools/mb/l0_stages
+// `l` / `n`: the lean banded kernel on wide / narrow strips (into compact planes), `v`: the lean wave form (time per launch only).
+// Without -DKLT_STAGE_CLOCKS it launches the product kernels unmarked and prints the time per launch only (the program a counter pass
+// runs; built as tools/mb/l0_plain).
 #include "../../pyfeaturetrack_amd/csrc/pyramid_kernels.hip"
 #include <cstdio>
 #include <cmath>
@@ -31,8 +34,13 @@ int main(int argc, char **argv)
     a.ncols = nc; a.nrows = nr; a.R = 3;
     std::vector<uint8_t> h((size_t)nc * nr);
     for (size_t i = 0; i < h.size(); i++) h[i] = (uint8_t)((i * 2654435761u) >> 24);
-    const bool wide = argc > 1 && argv[1][0] == 'w';
-    const bool tiled16 = argc > 1 && argv[1][0] == 'T', stream = wide || (argc > 1 && argv[1][0] == 's');
+    // `l` / `n`: the lean form (KLT_OPT_L0_LAZY_GRAD) of the wide / narrow streaming kernel: stages load, hsm, vsm and (as "hgrad") the
+    // plane stores with the horizontal reduction; `v`: the lean wave form (no stage marks: time per launch only)
+    const char mode = argc > 1 ? argv[1][0] : ' ';
+    const bool wave = mode == 'v';
+    const bool lean_mode = mode == 'l' || mode == 'n' || wave;
+    const bool wide = mode == 'w' || mode == 'l' || wave;
+    const bool tiled16 = mode == 'T', stream = wide || mode == 's' || mode == 'n';
     const int B = tiled16 || stream ? 16 : 2;
     const bool plain = argc > 1 && argv[1][0] == 'p';      // the kernel without the fused horizontal reduction
     float *cimg[KLT_MAX_BATCH], *dst[KLT_MAX_BATCH];
@@ -40,7 +48,7 @@ int main(int argc, char **argv)
         uint8_t *raw; float *rec;
         hipMalloc(&raw, h.size()); hipMalloc(&rec, 4 * KLT_PIX_STRIDE * h.size()); hipMalloc(&cimg[b], 4 * h.size()); hipMalloc(&dst[b], 4 * h.size());
         hipMemcpy(raw, h.data(), h.size(), hipMemcpyHostToDevice);
-        a.raw[b] = raw; a.rec[b] = rec; a.cimg[b] = plain ? cimg[b] : nullptr;
+        a.raw[b] = raw; a.rec[b] = rec; a.cimg[b] = plain || lean_mode ? cimg[b] : nullptr;
     }
     PyrReduceArgs pr = {};
     gauss_taps(pr.taps, dummy, 3.6, 21);
@@ -49,7 +57,13 @@ int main(int argc, char **argv)
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     a.reduce = pr.taps; a.h1_nc = nc / 4;
     for (int b = 0; b < B; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
-    auto go = [&]() { if (reduce) launch_pyr_reduce(0, pr, 2); else launch_smooth_grad(0, a, B, 0, !plain, wide ? 2 : stream); };
+    auto go = [&]() {
+        bool lean = lean_mode;
+        if (reduce) launch_pyr_reduce(0, pr, 2);
+        int form = wave ? 1 : 0;
+        if (!reduce) launch_smooth_grad(0, a, B, 0, !plain, wide ? 2 : stream, nullptr, &lean, &form);
+        if (lean != lean_mode || form != (wave ? 2 : lean_mode ? 1 : 0)) { printf("the launch did not go out in the form asked for\n"); exit(1); }
+    };
     for (int rep = 0; rep < 3; rep++) go();
     hipDeviceSynchronize();
     hipEventRecord(e0);
@@ -57,6 +71,10 @@ int main(int argc, char **argv)
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("kernel: %.2f us per launch\n", ms * 1000 / 20);
+#ifndef KLT_STAGE_CLOCKS
+    return 0;                                   // (built without the stage marks: the product kernels, for counter passes)
+#else
+    if (wave) return 0;
     long long clk[64 * 8];
     if (stream) {
         // g_stream_clk accumulated over every launch of this run (3 + 20): per launch, per band of 2048 output pixels (32 rows of a 64-column
@@ -131,4 +149,5 @@ int main(int argc, char **argv)
     for (int i = 0; i < 256; i++) if (cnt[i]) printf("   %02x %2d %5lld %5lld\n", i, cnt[i], firstend[i], lastend[i]);
     // peak concurrency per CU: events
     return 0;
+#endif
 }
