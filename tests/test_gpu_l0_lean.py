@@ -2,7 +2,8 @@
 the smoothed image to the slot's compact plane) and the records made from that plane on demand (ensure_level0_records).
 
 Every plane case builds one batch of 32 DISTINCT frames twice -- option 0 (full) and option 2 (lean wherever a streaming kernel is
-launched) -- asserts through klt_level0_path that both builds launched the streaming geometry the case was written for and through
+launched), with a full build of the same frames in reversed slot order in between, so that the record buffers hold other pixels when the
+lean build starts and records that nothing made on demand cannot pass for the right ones -- asserts through klt_level0_path that both builds launched the streaming geometry the case was written for and through
 klt_level0_lean that the second one was lean, and compares, bit for bit and without tolerances:
   * the image plane of level 0 and all three planes of level 1 of EVERY frame of the lean build with the full build's, and those of
     frames 0, 1, 15 and 31 with the CPU oracle's;
@@ -141,6 +142,7 @@ def test_lean_build_planes(ctx, case, f32):
                 for p in range(3):
                     bad = first_difference(full[k][l][p], want[k][l][p])
                     assert not bad, "full build: frame %d, plane %d of level %d against the oracle: %s" % (k, p, l, bad)
+        _build(ctx, fr[::-1], 0, geom, f32, False)       # slot k holds frame 31 - k: the record buffers hold other pixels when the lean build starts
         _build(ctx, fr, 2, geom, f32, True)
         for k in range(batch):
             _compare("lean build", ctx.download_level(k, 0, 0), full, want, k, 0, 0)

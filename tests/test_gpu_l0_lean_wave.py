@@ -2,7 +2,8 @@
 down a segment of rows on its own) against the banded lean form, the full build and the CPU oracle.
 
 Every plane case builds one batch of 32 DISTINCT frames three times -- full (KLT_OPT_L0_LAZY_GRAD 0), lean with form 0 (banded) and lean
-with form 1 (wave) -- asserts klt_level0_lean_form = 0, 1 and 2 for the three, and compares, bit for bit and without tolerances, for both
+with form 1 (wave), each lean build after a full build of the same frames in reversed slot order (the record buffers then hold other
+pixels than the ones to be made on demand) -- asserts klt_level0_lean_form = 0, 1 and 2 for the three, and compares, bit for bit and without tolerances, for both
 lean builds:
   * the image plane of level 0 and all three planes of level 1 of EVERY frame with the full build's, and those of frames 0, 1, 15 and 31
     with the CPU oracle's;
@@ -165,6 +166,7 @@ def test_wave_build_planes(ctx, case, f32):
                     bad = first_difference(full[k][l][p], want[k][l][p])
                     assert not bad, "full build: frame %d, plane %d of level %d against the oracle: %s" % (k, p, l, bad)
         for form, want_form, name in ((0, 1, "banded lean build"), (1, 2, "wave lean build")):
+            _build(ctx, fr[::-1], 0, 1, 0)                   # slot k holds frame 31 - k: the record buffers hold other pixels when the lean build starts
             _build(ctx, fr, 2, form, want_form)
             for k in range(batch):
                 _compare(name, ctx.download_level(k, 0, 0), full, want, k, 0, 0)
