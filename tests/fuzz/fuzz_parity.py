@@ -5,6 +5,8 @@ per trial: pyramids of two frames, selection, tracking, replacement of the lost 
 bit for bit.
 
     python3 tests/fuzz/fuzz_parity.py [--trials 40] [--seed 1] [--max-pixels 400000] [--max-n 700] [--max-side 900]
+--light / --quality / --model: gain / bias tracking, track quality and the motion-model check on the draws of
+tests/feature_draws_expected.py, against the numpy restatements of their rules.
 --fb / --guess / --mask: the forward-backward check, the motion prior and the selection mask on the draws of tests/draws_expected.py (the
 trial functions tests/test_gpu_draws.py runs on its fixed seed table), trial k on draw seed * 100000 + k.
 --pyramid: the level-0 pyramid kernels on the draws of tests/pyramid_expected.py (the kernel first, then a batch of frames that reaches it;
@@ -389,6 +391,39 @@ def run_draws_trials(a):
     ctx.close()
 
 
+def run_feature_draws_trials(a):
+    """--light / --quality / --model: the trial functions of tests/feature_draws_expected.py on fresh draws"""
+    import feature_draws_expected as fe
+    ctx = Context(0)
+    t0 = time.time()
+    for k in range(a.trials):
+        seed = a.seed * 100000 + k
+        if a.light:
+            c = fe.light_case(seed)
+            bad = fe.run_light_trial(ctx, c)
+            f = fe.light_facts(c)
+            stat = "live %d, tracked %d, statuses %s, degenerate by sign %d / by overflow %d, steps not finite %d" % (
+                f["live"], f["tracked"], sorted(f["statuses"]), f.get("not_positive", 0), f.get("overflowed", 0), f.get("step_not_finite", 0))
+            fe.light_case.cache_clear()
+        elif a.quality:
+            c = fe.quality_case(seed)
+            bad = fe.run_quality_trial(ctx, c)
+            f = fe.quality_facts(c)
+            stat = "measured %d, unmeasured %d, ncc = 0 %d / %d, min_eig = 0 %d, clamps %d / %d" % (
+                f["measured"], f["unmeasured"], f.get("a_le_0", 0), f.get("b_le_0", 0), f.get("e_le_0", 0), f.get("clamp_high", 0), f.get("clamp_low", 0))
+            fe.quality_case.cache_clear()
+        else:
+            c = fe.model_case(seed)
+            bad = fe.run_model_trial(ctx, c)
+            stat = "; ".join("valid %d, m %d, flagged %d" % (f["valid"], f["m"], f["flagged"]) for f in fe.model_facts(c))
+            fe.model_case.cache_clear()
+        print("trial %3d %s  %s  %s" % (k, "ok  " if not bad else "FAIL (%s)" % bad, c["t"], stat), flush=True)
+        if bad:
+            sys.exit(1)
+    print("%d trials identical in %.0f s" % (a.trials, time.time() - t0))
+    ctx.close()
+
+
 def run_pyramid_trials(a):
     """--pyramid: run_pyramid_trial of tests/pyramid_expected.py on fresh draws"""
     import pyramid_expected as pe
@@ -445,7 +480,12 @@ def main():
     ap.add_argument("--mask", action="store_true", help="klt_set_select_mask* on the mask draws of tests/draws_expected.py")
     ap.add_argument("--pyramid", action="store_true", help="the level-0 pyramid kernels on the draws of tests/pyramid_expected.py, against the oracle")
     ap.add_argument("--scores", action="store_true", help="the selection score kernels on the draws of tests/select_scores_expected.py, against the oracle")
+    ap.add_argument("--light", action="store_true", help="gain / bias tracking on the draws of tests/feature_draws_expected.py, against the rule's restatement")
+    ap.add_argument("--quality", action="store_true", help="klt_track_quality* on the quality draws of tests/feature_draws_expected.py")
+    ap.add_argument("--model", action="store_true", help="klt_motion_check* on the model draws of tests/feature_draws_expected.py")
     a = ap.parse_args()
+    if a.light or a.quality or a.model:
+        return run_feature_draws_trials(a)
     if a.scores:
         return run_scores_trials(a)
     if a.pyramid:

@@ -134,11 +134,12 @@ def unmeasured_kinds(fin, fout, w, ncols, nrows, start=0):
         put(ok_in, (cx, cy, code, 0), False)
     put(ok_in, (cx, cy, 1, 0), False)                                         # out.val > 0: refilled by a replacement pass
     put(ok_in, (cx, cy, 4711, 0), False)
-    for bad in (np.nan, np.inf, -np.inf, 1e30, -1e30, -0.5, float(ncols), float(max(ncols, nrows))):
-        put((bad, cy, 1, 0), ok_out, False)
-        put((cx, bad, 1, 0), ok_out, False)
-        put(ok_in, (bad, cy, KLT_TRACKED, 0), False)
-        put(ok_in, (cx, bad, KLT_TRACKED, 0), False)
+    for bad in (np.nan, np.inf, -np.inf, 1e30, -1e30, -0.5, None, float(max(ncols, nrows))):
+        bad_x, bad_y = (float(ncols), float(nrows)) if bad is None else (bad, bad)       # None: the first coordinate off the frame, per axis
+        put((bad_x, cy, 1, 0), ok_out, False)
+        put((cx, bad_y, 1, 0), ok_out, False)
+        put(ok_in, (bad_x, cy, KLT_TRACKED, 0), False)
+        put(ok_in, (cx, bad_y, KLT_TRACKED, 0), False)
     put(ok_in, ok_out, True)
     put((cx, cy, 0, 0), (F32(ncols // 2), F32(nrows // 2), KLT_TRACKED, 0), True)     # integer coordinates
     for x, y, fits in edge_positions(w, ncols, nrows):                        # windows that touch each edge, on either side
