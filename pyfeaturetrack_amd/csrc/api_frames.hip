@@ -140,74 +140,47 @@ bool fused_smooth_ok(const klt_ctx *c)
     return c->use_fused && c->gauss[0].sym == 1 && smooth_grad_lds_bytes(c->gauss[0].n / 2, grad_radius(c)) <= kMaxLds;
 }
 // the register-blocked kernels take per-entry geometry (levels of different size in one launch); dims must fit a short
-bool merged_grad_ok(const klt_ctx *c)
-{
-    return c->gauss[2].sym == 1 && c->deriv[2].sym == -1 && c->gauss[2].n == 7 && c->deriv[2].n == 7;
-}
+bool merged_grad_ok(const klt_ctx *c) { return l0_taps_specialised(nullptr, c->gauss[2], c->deriv[2]); }
 bool fused_grad_ok(const klt_ctx *c) { return c->use_fused && smooth_grad_lds_bytes(-1, grad_radius(c)) <= kMaxLds; }
 bool fused_reduce_ok(const klt_ctx *c) { return c->use_fused && pyr_reduce_lds_bytes(c->p.subsampling, c->gauss[1].n) <= kMaxLds; }
 
-// Would a level-0 launch of `batch` frames that wants the first reduction's horizontal pass get it (enqueue_fused_smooth_grad)?
-static bool l0_hred(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
+// The plan of a level-0 or gradient launch under this context's taps and options: which kernel, which form, which grid (plan_level0)
+L0Plan plan_l0(const klt_ctx *c, int batch, int kind, int nc, int nr, bool uniform /* = true */, bool want_hred /* = false */, bool want_lean /* = false */)
 {
-    SmoothGradArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
-    a.ncols = nc; a.nrows = nr;
-    return c->fuse_hreduce && smooth_grad_hred_ok(a, batch, raw_kind == 1 ? 0 : 1, c->gauss[1], c->p.subsampling);
+    const L0Request q = {nc, nr, batch, kind, uniform, &c->gauss[0], &c->gauss[2], &c->deriv[2], &c->gauss[1], c->p.subsampling,
+                         c->fuse_hreduce, c->l0_stream, c->l0_lean_form_opt, want_hred, want_lean};
+    return plan_level0(q, l0_tuning_from_env());
 }
 
-// Would a level-0 launch of `batch` frames with the fused reduction go out lean if asked to (a streaming kernel: launch_smooth_grad's rule)?
-static bool l0_lean_ok(const klt_ctx *c, int batch, int raw_kind, int nc, int nr)
-{
-    SmoothGradArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
-    a.ncols = nc; a.nrows = nr;
-    return l0_hred(c, batch, raw_kind, nc, nr) && smooth_grad_lean_ok(a, batch, raw_kind == 1 ? 0 : 1, true, c->l0_stream);
-}
-
-// smooth(raw frame) + gradients for up to KLT_MAX_BATCH same-sized frames in one launch: pixel records `rec`, and (cimg, optional,
-// not with the fused reduction) the smoothed image as compact planes as well
-// *fused_h1 (optional, in/out): in = the caller wants the horizontal pass of the first reduction fused into this launch; out =
-// whether it was (then c->h1 holds one H1 plane of nr x (nc / ss) floats per frame)
-// *path (optional, out): the KLT_L0_* code of the kernel launched
-// lean: a lean launch (KLT_OPT_L0_LAZY_GRAD): the smoothed image to `cimg` and nothing to `rec`.  Only a streaming kernel has the form:
-// the caller asks for it where l0_lean_ok says the launch is one, and a launch that cannot be lean is refused, not sent out full.
+// smooth(raw frame) + gradients for up to KLT_MAX_BATCH same-sized frames in one launch, as `plan` (of plan_l0 for this batch and size) has
+// it: pixel records `rec`, and (cimg, optional, not with the fused reduction) the smoothed image as compact planes as well
+// plan.hred: the horizontal pass of the first reduction goes out with this launch (then c->h1 holds one H1 plane of nr x (nc / ss) floats
+// per frame)
+// plan.lean: a lean launch (KLT_OPT_L0_LAZY_GRAD) -- only ever a streaming kernel, i.e. one with the fused reduction: the smoothed image to
+// `cimg` INSTEAD of the records
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 /* = nullptr */, int *path /* = nullptr */,
-                              bool lean /* = false */)
+                              float *const *cimg, int nc, int nr, const L0Plan &plan)
 {
     SmoothGradArgs a;
     std::memset(&a, 0, sizeof(a));
     for (int b = 0; b < batch; b++) { a.raw[b] = raw[b]; a.rec[b] = rec[b]; a.cimg[b] = cimg ? cimg[b] : nullptr; }
     a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
     a.ncols = nc; a.nrows = nr; a.R = grad_radius(c);
-    const int kind = raw_kind == 1 ? 0 : 1;
-    bool hred = fused_h1 && *fused_h1 && l0_hred(c, batch, raw_kind, nc, nr);
-    // (a lean launch -- only ever a streaming kernel, i.e. one with the fused reduction -- writes the compact planes INSTEAD of the records)
-    if (lean && !(hred && cimg && smooth_grad_lean_ok(a, batch, kind, hred, c->l0_stream)))
-        return fail(c, KLT_ERR_STATE, "level-0 launch: no lean form for this launch");
-    if (hred && cimg && !lean) return fail(c, KLT_ERR_STATE, "level-0 launch: a compact image copy with the fused reduction");
-    if (hred) {
+    if (plan.hred) {
         const size_t plane = (size_t)nr * (nc / c->p.subsampling);
         if (int rc = ensure_h1(c, plane * batch)) return rc;
         a.reduce = c->gauss[1];
         a.h1_nc = nc / c->p.subsampling;
         for (int b = 0; b < batch; b++) a.h1[b] = c->h1 + plane * b;
     }
-    if (fused_h1) *fused_h1 = hred;
     const double N = (double)nc * nr * batch;
     // algorithmic bytes: smoothing b_in + 4, gradients 12 per pixel; with the fused horizontal reduction this
     // launch also consumes the reduction stage's input (4 per pixel of level 0 -- the part of 4 (N0 + N1) that no longer
     // touches HBM); pyr_vreduce is charged the stage's output, so the step total is unchanged
     // (a lean launch writes the image alone, no gradients)
-    TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + (lean ? 0.0 : N * 12) + (hred ? 4.0 * N : 0.0));
-    bool went_lean = lean;
-    c->l0_launch_form = c->l0_lean_form_opt;
-    if (int e = launch_smooth_grad(c->work, a, batch, kind, hred, c->l0_stream, path, &went_lean, &c->l0_launch_form))
+    TimerScope t(c, F_SMOOTH_GRAD, N * ((raw_kind == 1 ? 1 : 4) + 4) + (plan.lean ? 0.0 : N * 12) + (plan.hred ? 4.0 * N : 0.0));
+    if (int e = launch_smooth_grad(c->work, a, plan))
         return fail(c, KLT_ERR_DEVICE, std::string("smooth_grad launch: ") + hipGetErrorString((hipError_t)e));
-    if (went_lean != lean) return fail(c, KLT_ERR_STATE, "level-0 launch: lean form not as planned");
     return 0;
 }
 
@@ -220,7 +193,7 @@ int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *co
     a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
     a.ncols = nc; a.nrows = nr; a.R = grad_radius(c);
     TimerScope t(c, F_GRAD, (double)nc * nr * batch * 12);
-    if (int e = launch_smooth_grad(c->work, a, batch, u8_input ? 3 : 2))
+    if (int e = launch_smooth_grad(c->work, a, plan_l0(c, batch, u8_input ? 3 : 2, nc, nr)))
         return fail(c, KLT_ERR_DEVICE, std::string("gradient launch: ") + hipGetErrorString((hipError_t)e));
     return 0;
 }
@@ -279,20 +252,10 @@ int ensure_level0_records(klt_ctx *c, Slot *const *slots, int n, bool asked /* =
 
 int ensure_level0_records(klt_ctx *c, Slot *s, bool asked /* = true */) { return ensure_level0_records(c, &s, 1, asked); }
 
-int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
+// KLT_OPT_BUILD_STREAM, entry: a build on the build stream goes behind the main stream once, a build on the main stream behind the last
+// build over there
+static int enter_build_stream(klt_ctx *c, bool on_bstream)
 {
-    if (int rc = check_ready(c)) return rc;
-    if (!slot_ids || n <= 0) return fail(c, KLT_ERR_ARG, "empty slot list");
-    HIPCHK(c, hipSetDevice(c->device));
-    // KLT_OPT_BUILD_STREAM: the whole build goes to the build stream, behind everything enqueued on the main stream so far (the
-    // earlier readers of these slots, synchronous uploads) -- one event each way per build.  The generic two-pass kernels share
-    // scratch with the selection, so they stay on the main stream.
-    WorkScope work_scope{c};
-    // (Round 3 measured the level-0 kernel alone on the build stream, levels >= 1 and the tracker on the main stream -- "KLT_OPT_L0_STREAM",
-    // commit 72f1f4e: bit-identical, and no faster: one context 0.0452 ms per pair against 0.0462 on one stream with two pairs per launch.
-    // The level-0 kernel and the tracker are both bound by VALU issue: running side by side they take 70 us where they take 48 + 26 one
-    // after the other, profiles/README.md.)
-    const bool on_bstream = c->build_stream_on && c->use_fused && fused_smooth_ok(c) && fused_grad_ok(c) && fused_reduce_ok(c);
     if (on_bstream) {
         if (!c->bstream) HIPCHK(c, hipStreamCreateWithFlags(&c->bstream, hipStreamNonBlocking));
         if (c->last_build_on_bstream != 1) {
@@ -307,6 +270,112 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         if (event_live(c, c->bbuild_serial)) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_bbuild, 0));
         else HIPCHK(c, hipStreamSynchronize(c->bstream));
     }
+    return 0;
+}
+
+// ... and exit: the event that readers of these slots (and the next build on the main stream) wait for
+static int leave_build_stream(klt_ctx *c, const std::vector<Slot *> &sl)
+{
+    hipEvent_t e;
+    uint64_t serial;
+    if (int rc = fresh_event(c, &e, &serial)) return rc;
+    HIPCHK(c, hipEventRecord(e, c->bstream));
+    for (Slot *s : sl) { s->ev_built = e; s->built_serial = serial; s->built_pending = true; }
+    c->ev_bbuild = e; c->bbuild_serial = serial;
+    return 0;
+}
+
+// Levels 1..L-1 of one group `g` of equal frames, from the compact planes of the scratch laid out by coff / cper (level 1 from the H1 planes
+// where the level-0 launch made them: h1_fused)
+static int build_upper_levels(klt_ctx *c, const std::vector<Slot *> &g, bool h1_fused, bool merged_grad, const size_t *coff, size_t cper)
+{
+    const int B = (int)g.size(), ss = c->p.subsampling;
+    Slot *s0 = g[0];
+    const float *src[KLT_MAX_BATCH];
+    float *rec[KLT_MAX_BATCH];
+    auto cimg_of = [&](int l, int b) { return c->cimg + cper * b + coff[l]; };
+    // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
+    // then the gradients of the new level.  Only surviving columns / rows are evaluated.
+    for (int l = 1; l < s0->nlev; l++) {
+        const Level &ls = s0->lv[l - 1];
+        const Level &ld = s0->lv[l];
+        if (fused_reduce_ok(c)) {
+            PyrReduceArgs a;
+            std::memset(&a, 0, sizeof(a));
+            for (int b = 0; b < B; b++) { a.src[b] = cimg_of(l - 1, b); a.dst[b] = cimg_of(l, b); }
+            a.taps = c->gauss[1];
+            a.src_nc = ls.nc; a.src_nr = ls.nr; a.dst_nc = ld.nc; a.dst_nr = ld.nr; a.ss = ss;
+            a.log2ss = 0;
+            while ((1 << a.log2ss) < ss) a.log2ss++;
+            if (l == 1 && h1_fused) {
+                // vertical pass only: H1 (level-0 rows x level-1 columns) -> level 1
+                const size_t plane = (size_t)ls.nr * ld.nc;
+                for (int b = 0; b < B; b++) a.src[b] = c->h1 + plane * b;
+                TimerScope t(c, F_PYR_REDUCE, 4.0 * B * ((double)ld.nc * ld.nr));
+                if (int e = launch_pyr_vreduce(c->work, a, B))
+                    return fail(c, KLT_ERR_DEVICE, std::string("pyr_vreduce launch: ") + hipGetErrorString((hipError_t)e));
+            } else {
+                TimerScope t(c, F_PYR_REDUCE, 4.0 * B * ((double)ls.nc * ls.nr + (double)ld.nc * ld.nr));
+                if (int e = launch_pyr_reduce(c->work, a, B))
+                    return fail(c, KLT_ERR_DEVICE, std::string("pyr_reduce launch: ") + hipGetErrorString((hipError_t)e));
+            }
+        } else {
+            for (int b = 0; b < B; b++) {
+                {
+                    TimerScope t(c, F_PYR_H, 4.0 * ((double)ls.nc * ls.nr + (double)ld.nc * ls.nr));
+                    launch_hconv_f32(c->work, cimg_of(l - 1, b), ls.nc, ls.nr, c->tmpA, nullptr, ld.nc, ss, ss / 2, c->gauss[1], nullptr);
+                }
+                {
+                    TimerScope t(c, F_PYR_V, 4.0 * ((double)ld.nc * ls.nr + (double)ld.nc * ld.nr));
+                    launch_vconv(c->work, c->tmpA, nullptr, ld.nc, ls.nr, cimg_of(l, b), nullptr, ld.nr, ss, ss / 2, c->gauss[1], nullptr);
+                }
+            }
+        }
+        if (merged_grad) continue;          // gradients of all levels >= 1 go out in one launch below
+        if (fused_grad_ok(c)) {
+            for (int b = 0; b < B; b++) { src[b] = cimg_of(l, b); rec[b] = g[b]->lv[l].img; }
+            if (int rc = enqueue_fused_grad(c, B, src, rec, ld.nc, ld.nr)) return rc;
+        } else {
+            for (int b = 0; b < B; b++) enqueue_gradients(c, cimg_of(l, b), ld.nc, ld.nr, g[b]->lv[l].img);
+        }
+    }
+    if (merged_grad) {
+        // one launch for the gradients of every level >= 1 of every frame: entry = (frame, level), per-entry geometry; each reads its
+        // compact level image and writes the level's records
+        SmoothGradArgs a;
+        std::memset(&a, 0, sizeof(a));
+        int e = 0;
+        double bytes = 0;
+        for (int l = 1; l < s0->nlev; l++)
+            for (int b = 0; b < B; b++, e++) {
+                a.raw[e] = cimg_of(l, b); a.rec[e] = g[b]->lv[l].img;
+                a.dim_c[e] = (short)g[b]->lv[l].nc; a.dim_r[e] = (short)g[b]->lv[l].nr;
+                bytes += 12.0 * g[b]->lv[l].nc * g[b]->lv[l].nr;
+            }
+        a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
+        a.ncols = s0->lv[1].nc; a.nrows = s0->lv[1].nr; a.R = grad_radius(c);
+        TimerScope t(c, F_GRAD, bytes);
+        if (int er = launch_smooth_grad(c->work, a, plan_l0(c, e, 2, a.ncols, a.nrows, false)))
+            return fail(c, KLT_ERR_DEVICE, std::string("gradient launch: ") + hipGetErrorString((hipError_t)er));
+    }
+    return 0;
+}
+
+int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
+{
+    if (int rc = check_ready(c)) return rc;
+    if (!slot_ids || n <= 0) return fail(c, KLT_ERR_ARG, "empty slot list");
+    HIPCHK(c, hipSetDevice(c->device));
+    // KLT_OPT_BUILD_STREAM: the whole build goes to the build stream, behind everything enqueued on the main stream so far (the
+    // earlier readers of these slots, synchronous uploads) -- one event each way per build.  The generic two-pass kernels share
+    // scratch with the selection, so they stay on the main stream.
+    WorkScope work_scope{c};
+    // (Round 3 measured the level-0 kernel alone on the build stream, levels >= 1 and the tracker on the main stream -- "KLT_OPT_L0_STREAM",
+    // commit 72f1f4e: bit-identical, and no faster: one context 0.0452 ms per pair against 0.0462 on one stream with two pairs per launch.
+    // The level-0 kernel and the tracker are both bound by VALU issue: running side by side they take 70 us where they take 48 + 26 one
+    // after the other, profiles/README.md.)
+    const bool on_bstream = c->build_stream_on && c->use_fused && fused_smooth_ok(c) && fused_grad_ok(c) && fused_reduce_ok(c);
+    if (int rc = enter_build_stream(c, on_bstream)) return rc;
     std::vector<Slot *> sl((size_t)n);
     std::vector<uint64_t> read_waited;
     for (int i = 0; i < n; i++) {
@@ -330,7 +399,6 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         sl[i]->read_valid = false;
     }
     c->last_build_on_bstream = on_bstream ? 1 : 0;
-    const int ss = c->p.subsampling;
     // groups of frames with the same geometry and input type share launches
     std::vector<bool> done((size_t)n, false);
     for (int i0 = 0; i0 < n; i0++) {
@@ -345,30 +413,27 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         const int B = (int)g.size();
         Slot *s0 = g[0];
         const void *raw[KLT_MAX_BATCH];
-        const float *src[KLT_MAX_BATCH];
         float *rec[KLT_MAX_BATCH], *cim[KLT_MAX_BATCH];
         if (int rc = ensure_tmp(c, (size_t)s0->nc * s0->nr)) return rc;
 
         // level 1 comes from the H1 planes written by the level-0 kernel, or from a compact copy of level 0
+        // KLT_OPT_L0_LAZY_GRAD: a group of slots that want it goes out lean where the launch is a streaming kernel's (which implies the
+        // fused reduction) -- the smoothed image to the slots' compact planes, no level-0 records
         const bool fused0 = fused_smooth_ok(c);
-        const bool h1_want = fused0 && s0->nlev > 1 && fused_reduce_ok(c) && l0_hred(c, B, s0->raw_kind, s0->nc, s0->nr);
+        const L0Plan plan = plan_l0(c, B, s0->raw_kind == 1 ? 0 : 1, s0->nc, s0->nr, true, fused0 && s0->nlev > 1 && fused_reduce_ok(c), wants_lean(c, s0));
+        const bool lean = plan.lean;
         // The reductions read and write compact image planes, and the gradient launches of levels >= 1 read them: scratch for the levels
         // of every frame of the group (level 0 only where something reads it), 16-byte aligned
         size_t coff[KLT_MAX_LEVELS], cper = 0;
         for (int l = 0; l < s0->nlev; l++) {
             coff[l] = cper;
-            if (l > 0 || (!h1_want && (!fused0 || s0->nlev > 1))) cper += ((size_t)s0->lv[l].nc * s0->lv[l].nr + 3) & ~(size_t)3;
+            if (l > 0 || (!plan.hred && (!fused0 || s0->nlev > 1))) cper += ((size_t)s0->lv[l].nc * s0->lv[l].nr + 3) & ~(size_t)3;
         }
         if (cper) { if (int rc = ensure_cimg(c, cper * B)) return rc; }
         auto cimg_of = [&](int l, int b) { return c->cimg + cper * b + coff[l]; };
 
         // level 0: smoothed frame (trackFeatures.py:165-166) and its gradients (:171-172)
-        bool h1_fused = false, lean = false;
-        int l0_path = KLT_L0_TWO_PASS;
         if (fused0) {
-            // KLT_OPT_L0_LAZY_GRAD: a group of slots that want it goes out lean where the launch is a streaming kernel's (which implies the
-            // fused reduction) -- the smoothed image to the slots' compact planes, no level-0 records
-            lean = h1_want && wants_lean(c, s0) && l0_lean_ok(c, B, s0->raw_kind, s0->nc, s0->nr);
             for (int b = 0; b < B && lean; b++)
                 if (int rc = ensure(c, g[b]->l0img, g[b]->l0img_cap, (size_t)s0->nc * s0->nr)) return rc;
             for (int b = 0; b < B; b++) {
@@ -376,10 +441,8 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
                 rec[b] = g[b]->lv[0].img;
                 cim[b] = lean ? g[b]->l0img : cimg_of(0, b);
             }
-            h1_fused = h1_want;
-            const bool copy0 = !h1_want && s0->nlev > 1;
-            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 || lean ? cim : nullptr, s0->nc, s0->nr, &h1_fused, &l0_path, lean)) return rc;
-            if (h1_fused != h1_want) return fail(c, KLT_ERR_STATE, "level-0 launch: fused reduction not as planned");
+            const bool copy0 = !plan.hred && s0->nlev > 1;
+            if (int rc = enqueue_fused_smooth_grad(c, B, raw, s0->raw_kind, rec, copy0 || lean ? cim : nullptr, s0->nc, s0->nr, plan)) return rc;
         } else {
             for (int b = 0; b < B; b++) {
                 enqueue_smooth_raw(c, g[b], cimg_of(0, b));
@@ -388,74 +451,11 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         }
         // what klt_level0_path reports: the last group's level-0 kernel, and whether its gradients of levels >= 1 are one launch
         const bool merged_grad = s0->nlev > 1 && fused_grad_ok(c) && merged_grad_ok(c) && B * (s0->nlev - 1) <= KLT_MAX_BATCH && s0->nc / s0->ss <= 32767 && s0->nr / s0->ss <= 32767;
-        c->l0_path = l0_path;
+        c->l0_path = fused0 ? plan.path : KLT_L0_TWO_PASS;
         c->l0_merged_grad = merged_grad;
         c->l0_lean = lean;
-        c->l0_lean_form = lean ? c->l0_launch_form : 0;
-        // levels 1..L-1: smooth with the pyramid sigma, keep pixel (ss*y + ss/2, ss*x + ss/2) (pyramid.py:59-72),
-        // then the gradients of the new level.  Only surviving columns / rows are evaluated.
-        for (int l = 1; l < s0->nlev; l++) {
-            const Level &ls = s0->lv[l - 1];
-            const Level &ld = s0->lv[l];
-            if (fused_reduce_ok(c)) {
-                PyrReduceArgs a;
-                std::memset(&a, 0, sizeof(a));
-                for (int b = 0; b < B; b++) { a.src[b] = cimg_of(l - 1, b); a.dst[b] = cimg_of(l, b); }
-                a.taps = c->gauss[1];
-                a.src_nc = ls.nc; a.src_nr = ls.nr; a.dst_nc = ld.nc; a.dst_nr = ld.nr; a.ss = ss;
-                a.log2ss = 0;
-                while ((1 << a.log2ss) < ss) a.log2ss++;
-                if (l == 1 && h1_fused) {
-                    // vertical pass only: H1 (level-0 rows x level-1 columns) -> level 1
-                    const size_t plane = (size_t)ls.nr * ld.nc;
-                    for (int b = 0; b < B; b++) a.src[b] = c->h1 + plane * b;
-                    TimerScope t(c, F_PYR_REDUCE, 4.0 * B * ((double)ld.nc * ld.nr));
-                    if (int e = launch_pyr_vreduce(c->work, a, B))
-                        return fail(c, KLT_ERR_DEVICE, std::string("pyr_vreduce launch: ") + hipGetErrorString((hipError_t)e));
-                } else {
-                    TimerScope t(c, F_PYR_REDUCE, 4.0 * B * ((double)ls.nc * ls.nr + (double)ld.nc * ld.nr));
-                    if (int e = launch_pyr_reduce(c->work, a, B))
-                        return fail(c, KLT_ERR_DEVICE, std::string("pyr_reduce launch: ") + hipGetErrorString((hipError_t)e));
-                }
-            } else {
-                for (int b = 0; b < B; b++) {
-                    {
-                        TimerScope t(c, F_PYR_H, 4.0 * ((double)ls.nc * ls.nr + (double)ld.nc * ls.nr));
-                        launch_hconv_f32(c->work, cimg_of(l - 1, b), ls.nc, ls.nr, c->tmpA, nullptr, ld.nc, ss, ss / 2, c->gauss[1], nullptr);
-                    }
-                    {
-                        TimerScope t(c, F_PYR_V, 4.0 * ((double)ld.nc * ls.nr + (double)ld.nc * ld.nr));
-                        launch_vconv(c->work, c->tmpA, nullptr, ld.nc, ls.nr, cimg_of(l, b), nullptr, ld.nr, ss, ss / 2, c->gauss[1], nullptr);
-                    }
-                }
-            }
-            if (merged_grad) continue;          // gradients of all levels >= 1 go out in one launch below
-            if (fused_grad_ok(c)) {
-                for (int b = 0; b < B; b++) { src[b] = cimg_of(l, b); rec[b] = g[b]->lv[l].img; }
-                if (int rc = enqueue_fused_grad(c, B, src, rec, ld.nc, ld.nr)) return rc;
-            } else {
-                for (int b = 0; b < B; b++) enqueue_gradients(c, cimg_of(l, b), ld.nc, ld.nr, g[b]->lv[l].img);
-            }
-        }
-        if (merged_grad) {
-            // one launch for the gradients of every level >= 1 of every frame: entry = (frame, level), per-entry geometry; each reads its
-            // compact level image and writes the level's records
-            SmoothGradArgs a;
-            std::memset(&a, 0, sizeof(a));
-            int e = 0;
-            double bytes = 0;
-            for (int l = 1; l < s0->nlev; l++)
-                for (int b = 0; b < B; b++, e++) {
-                    a.raw[e] = cimg_of(l, b); a.rec[e] = g[b]->lv[l].img;
-                    a.dim_c[e] = (short)g[b]->lv[l].nc; a.dim_r[e] = (short)g[b]->lv[l].nr;
-                    bytes += 12.0 * g[b]->lv[l].nc * g[b]->lv[l].nr;
-                }
-            a.smooth = c->gauss[0]; a.ggauss = c->gauss[2]; a.gderiv = c->deriv[2];
-            a.ncols = s0->lv[1].nc; a.nrows = s0->lv[1].nr; a.R = grad_radius(c);
-            TimerScope t(c, F_GRAD, bytes);
-            if (int er = launch_smooth_grad(c->work, a, e, 2))
-                return fail(c, KLT_ERR_DEVICE, std::string("gradient launch: ") + hipGetErrorString((hipError_t)er));
-        }
+        c->l0_lean_form = plan.lean_form;
+        if (int rc = build_upper_levels(c, g, plan.hred, merged_grad, coff, cper)) return rc;
         for (Slot *s : g) {
             s->pyr_valid = true; s->gen = ++c->gen_counter;
             s->rec0_valid = !lean; s->l0img_valid = lean;
@@ -465,14 +465,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     }
     // the next asynchronous copy into these slots waits for this build
     if (int rc = mark_consumed(c, sl.data(), n, c->work)) return rc;
-    if (on_bstream) {
-        hipEvent_t e;
-        uint64_t serial;
-        if (int rc = fresh_event(c, &e, &serial)) return rc;
-        HIPCHK(c, hipEventRecord(e, c->bstream));
-        for (Slot *s : sl) { s->ev_built = e; s->built_serial = serial; s->built_pending = true; }
-        c->ev_bbuild = e; c->bbuild_serial = serial;
-    }
+    if (on_bstream) { if (int rc = leave_build_stream(c, sl)) return rc; }
     for (Slot *s : sl) s->built_on_bstream = on_bstream;
     HIPCHK(c, hipGetLastError());
     return KLT_OK;

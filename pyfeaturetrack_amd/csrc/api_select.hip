@@ -296,7 +296,8 @@ int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, c
     bool grads_done = false;
     if (c->p.smoothBeforeSelecting && fused_smooth_ok(c)) {
         const void *raw = s->raw_kind == 1 ? (const void *)raw8(s) : (const void *)rawf(s);
-        if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr)) return rc;
+        if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr, plan_l0(c, 1, s->raw_kind == 1 ? 0 : 1, nc, nr)))
+            return rc;
         grads_done = true;
     } else if (c->p.smoothBeforeSelecting) {
         enqueue_smooth_raw(c, s, c->sel_img);

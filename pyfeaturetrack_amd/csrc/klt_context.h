@@ -197,7 +197,6 @@ struct klt_ctx {
     bool l0_lean = false;                     // klt_level0_lean: that group went out lean
     int l0_lean_form_opt = KLT_L0_LEAN_FORM_DEFAULT;   // KLT_OPT_L0_LEAN_FORM: 1 the wave form where it applies, 0 the banded form
     int l0_lean_form = 0;                     // klt_level0_lean_form: 0 not lean, 1 banded, 2 wave (that group's launch)
-    int l0_launch_form = 0;                   // ... of the last level-0 launch (enqueue_fused_smooth_grad)
     uint64_t cfg_gen = 1;                     // counts the changes of the taps and of the pyramid's shape (Slot::built_cfg)
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
@@ -481,7 +480,8 @@ int enqueue_gradients(klt_ctx *c, const float *img, int nc, int nr, float *rec);
 bool fused_smooth_ok(const klt_ctx *c);
 bool fused_grad_ok(const klt_ctx *c);
 int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int raw_kind, float *const *rec,
-                              float *const *cimg, int nc, int nr, bool *fused_h1 = nullptr, int *path = nullptr, bool lean = false);
+                              float *const *cimg, int nc, int nr, const L0Plan &plan);
+L0Plan plan_l0(const klt_ctx *c, int batch, int kind, int nc, int nr, bool uniform = true, bool want_hred = false, bool want_lean = false);
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
 // KLT_OPT_L0_LAZY_GRAD: whoever reads lv[0].img / .gx / .gy of a built slot calls this first.  The records of a lean slot are made from its

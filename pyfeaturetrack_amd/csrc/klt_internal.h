@@ -6,16 +6,7 @@
 #include <string>
 
 #include "klt_gpu.h"
-
-// FP64 taps in the order scipy.ndimage.correlate1d consumes them (i.e. the convolve.py taps reversed,
-// convolve1d does `weights[::-1]`), plus the symmetry class its inner loop switches on.
-struct Taps {
-    double k[KLT_MAX_KERNEL_WIDTH];
-    int n;
-    int sym;   // +1 symmetric, -1 antisymmetric, 0 neither
-};
-
-constexpr int KLT_MAX_BATCH = 32;   // frames per fused pyramid launch (pointer tables travel in the kernarg segment)
+#include "l0_plan.h"                  // Taps, KLT_MAX_BATCH, the level-0 launch plan
 
 struct SmoothGradArgs {
     const void *raw[KLT_MAX_BATCH];   // u8 or f32 frame (or, for gradients only, the compact level image)
@@ -308,19 +299,10 @@ __device__ __forceinline__ float corr_regs(const double *c /* centre */, const T
 }
 
 extern int g_track_variant;         // tracker kernels: 4 (default) quad-load kernels where they apply, 0 always track_kernel
-size_t smooth_grad_lds_bytes(int smooth_radius /* -1: no smoothing stage */, int R);
 size_t pyr_reduce_lds_bytes(int ss, int ntaps);
-// kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image gradients only, 3 = u8 image gradients only
-// stream: the streaming level-0 kernel where it applies (KLT_OPT_L0_STREAM: 1 = 64-column strips, 2 = 128-column strips where they apply)
-// *path (optional): which kernel went out, a KLT_L0_* code of include/klt_gpu.h
-// *lean_form (optional, in/out): in = 1: a lean launch takes the wave form where it applies (KLT_OPT_L0_LEAN_FORM); out = 0 not lean, 1 the
-// banded lean form, 2 the wave form
-// *lean (optional, in/out): in = the caller would take the lean form of a streaming kernel (no gradients, no records: the smoothed image
-// goes to the compact planes a.cimg instead); out = whether that is what went out (the tiled kernels have no lean form)
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred = false, int stream = 0, int *path = nullptr,
-                       bool *lean = nullptr, int *lean_form = nullptr);
-bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss);
-bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream);      // a launch asked to be lean would be
+// the kernel, form and grid that plan_level0 (l0_plan.h) chose for these arguments: a lean plan writes the smoothed image to the compact
+// planes a.cimg and nothing to a.rec, a plan with hred writes the H1 planes a.h1 as well
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, const L0Plan &plan);
 int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch);
 int launch_pyr_reduce(hipStream_t s, const PyrReduceArgs &a, int batch);
 

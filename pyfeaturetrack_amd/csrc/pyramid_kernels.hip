@@ -1318,12 +1318,7 @@ __global__ __launch_bounds__(256) void pyr_vreduce_kernel(PyrReduceArgs a)
 
 }  // namespace
 
-size_t smooth_grad_lds_bytes(int rs, int R)
-{
-    const int IW = TW + 2 * R, IH = TH + 2 * R, RW = IW + 2 * rs, RH = IH + 2 * rs;
-    const int ab = rs >= 0 ? RH * RW + RH * IW : 0, de = 2 * IH * TW;
-    return sizeof(float) * (size_t)((ab > de ? ab : de) + IH * IW);
-}
+static_assert(TW == L0_TILE_W && TH == L0_TILE_H && LW_COLS == L0_WAVE_COLS && LW_WAVES == L0_WAVE_WAVES, "l0_plan.h plans grids for these tiles");
 
 size_t pyr_reduce_lds_bytes(int ss, int ntaps)
 {
@@ -1343,24 +1338,6 @@ static int set_lds(K kernel, size_t lds)
     return 0;
 }
 
-// Do the register-blocked kernels take the 32-row tile for this launch?  Small launches take the 16-row tile so that the grid still covers
-// the chip.  KLT_RB_TH (16 or 32) overrides the choice: experiment hook.
-static bool rb_tall_tiles(const SmoothGradArgs &a, int batch)
-{
-    static const int force_th = getenv("KLT_RB_TH") ? atoi(getenv("KLT_RB_TH")) : 0;
-    return force_th ? force_th == 32 : (long long)a.ncols * a.nrows * batch >= 1000000;
-}
-
-// kind: 0 = u8 frame + smoothing, 1 = f32 frame + smoothing, 2 = f32 image, gradients only, 3 = u8 image, gradients only
-// Is the fused horizontal reduction available for this launch?  (specialised taps, tall tiles, subsampling 4 with 21 taps,
-// frames tall enough that the vertical pass needs a single reflection)
-bool smooth_grad_hred_ok(const SmoothGradArgs &a, int batch, int kind, const Taps &reduce, int ss)
-{
-    return rb_tall_tiles(a, batch) && kind < 2 && a.smooth.sym == 1 && (a.smooth.n == 5 || a.smooth.n == 9) &&
-           a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && ss == 4 && reduce.sym == 1 && reduce.n == 21 &&
-           a.nrows >= 64 && a.ncols >= 64;
-}
-
 int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch)
 {
     const dim3 grid((a.dst_nc + 63) / 64, (a.dst_nr + 15) / 16, batch);
@@ -1368,200 +1345,60 @@ int launch_pyr_vreduce(hipStream_t s, const PyrReduceArgs &a, int batch)
     return 0;
 }
 
-// Geometries of the streaming level-0 kernel: 64-column strips in 32-row bands (KLT_OPT_L0_STREAM 1), 128-column strips in 16-row bands (2)
-constexpr int L0S_TW = 64, L0S_SB = 32, L0W_TW = 128, L0W_SB = 16;
-// ... and the workgroups a launch needs to take them: two rounds of the 1024 resident slots (256 CUs x 4) for the narrow strips; the wide
-// strips' grid of sixteen 1080p frames is 15 x 9 x 16 = 2160 at their segment height, so the same bound holds for them
-constexpr long long L0S_MIN_WGS = 2048, L0W_MIN_WGS = 2048;
-
-// KLT_L0_WIDE_WGS overrides the wide strips' bound: experiment hook (segment heights whose grid is below it)
-static long long l0_wide_min_wgs()
+// The banded streaming kernels of one input type, smoothing tap count and geometry
+template <typename TIn, int NS, int STRIP, int BAND>
+static void launch_smooth_grad_banded(hipStream_t s, const SmoothGradArgs &a, const L0Plan &p, const dim3 &g, const dim3 &blk)
 {
-    static const long long force = getenv("KLT_L0_WIDE_WGS") ? atoll(getenv("KLT_L0_WIDE_WGS")) : 0;
-    return force > 0 ? force : L0W_MIN_WGS;
+    if (p.lean) { klt_launch((smooth_grad_stream<TIn, NS, false, STRIP, BAND, true>), g, blk, 0, s, a, p.seg); return; }
+    if constexpr (sizeof(TIn) == 1) if (p.zc) { klt_launch((smooth_grad_stream<TIn, NS, true, STRIP, BAND>), g, blk, 0, s, a, p.seg); return; }
+    klt_launch((smooth_grad_stream<TIn, NS, false, STRIP, BAND>), g, blk, 0, s, a, p.seg);
 }
 
-// Segment height of the streaming level-0 kernel, per geometry (`wide`: 128 x 16): the fastest of each one's cfg-2 sweep (profiles/README.md).
-// KLT_L0_SEG overrides it for the geometries whose band height divides it (32 narrow, 16 wide): experiment hook.
-static int l0_stream_seg(bool wide)
-{
-    static const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0;
-    return force > 0 && force % (wide ? L0W_SB : L0S_SB) == 0 ? force : wide ? 128 : 160;
-}
-
-// Which streaming geometry a level-0 launch with the fused reduction takes: 2 = wide strips, 1 = narrow strips, 0 = none (the tile).
-// Wide strips (KLT_OPT_L0_STREAM 2): frames of two wide strips or more and a grid of two rounds of the resident slots at their own
-// segment height; launches that miss either fall through to the narrow strips' rule, and from there to the tile.
-static int l0_stream_geometry(const SmoothGradArgs &a, int batch, int stream)
-{
-    const int shw = l0_stream_seg(true), sh = l0_stream_seg(false);
-    const long long gw = (long long)((a.ncols + L0W_TW - 1) / L0W_TW) * ((a.nrows + shw - 1) / shw) * batch;
-    const long long gs = (long long)((a.ncols + L0S_TW - 1) / L0S_TW) * ((a.nrows + sh - 1) / sh) * batch;
-    if (stream == 2 && a.ncols >= 2 * L0W_TW && gw >= l0_wide_min_wgs()) return 2;
-    if (stream && a.ncols >= 2 * L0S_TW && gs >= L0S_MIN_WGS) return 1;
-    return 0;
-}
-
-// The wave form of a lean launch (smooth_grad_lean_wave): segment height in rows, the fastest of its sweep (profiles/README.md; the constant is
-// KLT_L0_LEAN_WAVE_SEG of include/klt_gpu.h).  KLT_L0_SEG overrides it: experiment hook.
-static int l0_wave_seg()
-{
-    static const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0;
-    return force > 0 ? force : KLT_L0_LEAN_WAVE_SEG;
-}
-
-// Does a lean launch that asks for the wave form get it?  Frames of >= 256 columns and at least one vertical window high (one reflection
-// brings every index of a strip inside), all of one size.
-bool smooth_grad_lean_wave_ok(const SmoothGradArgs &a, int batch)
-{
-    for (int b = 0; b < batch; b++)
-        if (a.dim_c[b] || a.dim_r[b]) return false;
-    return a.ncols >= 256 && a.nrows >= a.smooth.n;
-}
-
-template <typename TIn, int NS>
-static void launch_lean_wave(hipStream_t s, const SmoothGradArgs &a, int batch)
-{
-    const int seg = l0_wave_seg();
-    const int nstrips = (a.ncols + LW_COLS - 1) / LW_COLS, nsegs = (a.nrows + seg - 1) / seg, nunits = nstrips * nsegs * batch;
-    klt_launch((smooth_grad_lean_wave<TIn, NS>), dim3((nunits + LW_WAVES - 1) / LW_WAVES), dim3(64 * LW_WAVES), 0, s, a, seg, nstrips, nsegs, nunits);
-}
-
-// Would launch_smooth_grad send this launch out lean if asked to (a streaming kernel: the fused reduction, specialised taps)?
-bool smooth_grad_lean_ok(const SmoothGradArgs &a, int batch, int kind, bool hred, int stream)
-{
-    return hred && kind < 2 && a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && a.smooth.sym == 1 &&
-           (a.smooth.n == 5 || a.smooth.n == 9) && l0_stream_geometry(a, batch, stream) != 0;
-}
-
-// The derivative taps' centre is +0.0 and every sample the two derivative passes see is >= +0 (a u8 frame, smoothing and Gaussian
-// taps without sign bits): corr_regs<..., ZC> may drop the centre product
-static bool deriv_centre_elidable(const SmoothGradArgs &a, int kind)
-{
-    auto sign_free = [](const Taps &t) {
-        for (int i = 0; i < t.n; i++)
-            if (std::signbit(t.k[i]) || !std::isfinite(t.k[i])) return false;
-        return true;
-    };
-    uint64_t centre;
-    std::memcpy(&centre, &a.gderiv.k[a.gderiv.n / 2], sizeof(centre));
-    return kind == 0 && centre == 0 && sign_free(a.smooth) && sign_free(a.ggauss);
-}
-
-// The register-blocked kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
-// *path: the KLT_L0_* code of the kernel launched (klt_level0_path)
+// The register-blocked and streaming kernels of one input type and smoothing tap count (SMOOTH = false: gradients only, NS = 1)
+// (28- / 24- / 20-row tiles -- 32.0 / 28.4 / 24.8 KB of LDS, five / five / six workgroups per CU -- were measured in
+// round 2: 29.9 / 29.9 / 30.4 us event-timed against 28.1 for the 32-row tile: the extra halo work outweighs the occupancy)
+// (three / two workgroups per CU instead of four -- dynamic LDS padding, same kernel -- read 0.0379 / 0.0382 ms per pair with
+// three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
 template <typename TIn, bool SMOOTH, int NS>
-static int launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean,
-                                 int *lean_form)
+static void launch_smooth_grad_rb(hipStream_t s, const SmoothGradArgs &a, const L0Plan &p)
 {
-    const bool want_lean = *lean;
-    *lean = false;                                           // (set where a lean kernel goes out)
-    // a lean launch takes the wave form where it is asked for and applies, else the banded form of the geometry's kernel
-    const bool wave = *lean_form == 1 && smooth_grad_lean_wave_ok(a, batch);
-    *lean_form = 0;
-    const dim3 blk(256);
-    const bool tall = rb_tall_tiles(a, batch);
-    const int th = tall ? 32 : 16;
-    const dim3 g((a.ncols + TW - 1) / TW, (a.nrows + th - 1) / th, batch);
-    if constexpr (SMOOTH) if (hred) {
-        // (28- / 24- / 20-row tiles -- 32.0 / 28.4 / 24.8 KB of LDS, five / five / six workgroups per CU -- were measured in
-        // round 2: 29.9 / 29.9 / 30.4 us event-timed against 28.1 for the 32-row tile: the extra halo work outweighs the occupancy)
-        // (three / two workgroups per CU instead of four -- dynamic LDS padding, same kernel -- read 0.0379 / 0.0382 ms per pair with
-        // three pairs in flight against 0.0365, and 0.0576 against 0.0556 on one stream: round 2)
-        // streaming kernel (KLT_OPT_L0_STREAM): frames of two strips or more (hred implies >= 64 rows)
-        // ... where its grid covers the 1024 resident workgroup slots (256 CUs x 4) at least twice; smaller launches (one 4K
-        // frame, 1080p batches below 10) keep the tiled kernel, whose 32-row tiles fill the chip
-        // wide strips (KLT_OPT_L0_STREAM 2): frames of two wide strips or more and a grid of the same two rounds at their own segment
-        // height; launches that miss either fall through to the narrow strips' rule, and from there to the tile
-        const int shw = l0_stream_seg(true);
-        const dim3 gw((a.ncols + L0W_TW - 1) / L0W_TW, (a.nrows + shw - 1) / shw, batch);
-        const int geom = l0_stream_geometry(a, batch, stream);
-        if (geom == 2) {
-            if (want_lean) {
-                // (the lean form has no derivative pass: one instantiation per input type and tap count, reported under the code the
-                // full launch would get)
-                if (wave) launch_lean_wave<TIn, NS>(s, a, batch);
-                else klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB, true>), gw, blk, 0, s, a, shw);
-                *lean_form = wave ? 2 : 1;
-                *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_WIDE_NO_CENTRE : KLT_L0_STREAM_WIDE;
-                *lean = true;
-                return 0;
-            }
-            if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
-                klt_launch((smooth_grad_stream<TIn, NS, true, L0W_TW, L0W_SB>), gw, blk, 0, s, a, shw);
-                *path = KLT_L0_STREAM_WIDE_NO_CENTRE;
-                return 0;
-            }
-            klt_launch((smooth_grad_stream<TIn, NS, false, L0W_TW, L0W_SB>), gw, blk, 0, s, a, shw);
-            *path = KLT_L0_STREAM_WIDE;
-            return 0;
-        }
-        const int sh = l0_stream_seg(false);
-        const dim3 gs((a.ncols + L0S_TW - 1) / L0S_TW, (a.nrows + sh - 1) / sh, batch);
-        if (geom == 1) {
-            if (want_lean) {
-                if (wave) launch_lean_wave<TIn, NS>(s, a, batch);
-                else klt_launch((smooth_grad_stream<TIn, NS, false, L0S_TW, L0S_SB, true>), gs, blk, 0, s, a, sh);
-                *lean_form = wave ? 2 : 1;
-                *path = sizeof(TIn) == 1 && deriv_centre_elidable(a, kind) ? KLT_L0_STREAM_NO_CENTRE : KLT_L0_STREAM;
-                *lean = true;
-                return 0;
-            }
-            // (the centre-tap elision needs a u8 frame: no f32 instantiation of it)
-            if constexpr (sizeof(TIn) == 1) if (deriv_centre_elidable(a, kind)) {
-                klt_launch((smooth_grad_stream<TIn, NS, true>), gs, blk, 0, s, a, sh);
-                *path = KLT_L0_STREAM_NO_CENTRE;
-                return 0;
-            }
-            klt_launch((smooth_grad_stream<TIn, NS, false>), gs, blk, 0, s, a, sh);
-            *path = KLT_L0_STREAM;
-            return 0;
-        }
-        klt_launch((smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>), g, blk, 0, s, a);
-        *path = KLT_L0_RB32_HRED;
+    const dim3 g(p.gx, p.gy, p.gz), blk(p.block);
+    if constexpr (SMOOTH) if (p.hred) {
+        if (p.family == L0_FAMILY_WAVE) klt_launch((smooth_grad_lean_wave<TIn, NS>), g, blk, 0, s, a, p.seg, p.nstrips, p.nsegs, p.units);
+        else if (p.family == L0_FAMILY_BANDED && p.strip == L0W_TW) launch_smooth_grad_banded<TIn, NS, L0W_TW, L0W_SB>(s, a, p, g, blk);
+        else if (p.family == L0_FAMILY_BANDED) launch_smooth_grad_banded<TIn, NS, L0S_TW, L0S_SB>(s, a, p, g, blk);
+        else klt_launch((smooth_grad_rb<TIn, true, NS, 7, 7, 32, 256, true>), g, blk, 0, s, a);
+        return;
+    }
+    if (p.tile_rows == 32) klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 32>), g, blk, 0, s, a);
+    else klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 16>), g, blk, 0, s, a);
+}
+
+// Executes a plan (plan_level0, l0_plan.h): selects the instantiation by input type, smoothing tap count and the plan's form, decides nothing
+int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, const L0Plan &p)
+{
+    const int kind = p.kind;
+    if (p.family != L0_FAMILY_TILED_LDS) {
+        const int ns = kind < 2 ? a.smooth.n : 1;
+        if (kind == 0 && ns == 5) launch_smooth_grad_rb<uint8_t, true, 5>(s, a, p);
+        if (kind == 1 && ns == 5) launch_smooth_grad_rb<float, true, 5>(s, a, p);
+        if (kind == 0 && ns == 9) launch_smooth_grad_rb<uint8_t, true, 9>(s, a, p);
+        if (kind == 1 && ns == 9) launch_smooth_grad_rb<float, true, 9>(s, a, p);
+        if (kind == 2) launch_smooth_grad_rb<float, false, 1>(s, a, p);
+        if (kind == 3) launch_smooth_grad_rb<uint8_t, false, 1>(s, a, p);
         return 0;
     }
-    if (tall) klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 32>), g, blk, 0, s, a);
-    else klt_launch((smooth_grad_rb<TIn, SMOOTH, NS, 7, 7, 16>), g, blk, 0, s, a);
-    *path = tall ? KLT_L0_RB32 : KLT_L0_RB16;
-    return 0;
-}
-
-int launch_smooth_grad(hipStream_t s, const SmoothGradArgs &a, int batch, int kind, bool hred, int stream, int *path, bool *lean, int *lean_form)
-{
-    int path_unused;
-    if (!path) path = &path_unused;
-    bool lean_unused = false;
-    if (!lean) lean = &lean_unused;
-    int form_unused = 0;
-    if (!lean_form) lean_form = &form_unused;
-    const bool smooth = kind < 2;
-    // compile-time specialisations: Gaussian smoothing (symmetric), Gaussian / derivative gradient taps
-    if (a.ggauss.sym == 1 && a.gderiv.sym == -1 && a.ggauss.n == 7 && a.gderiv.n == 7 && (!smooth || a.smooth.sym == 1)) {
-        const int ns = smooth ? a.smooth.n : 1;
-        if (kind == 0 && ns == 5) return launch_smooth_grad_rb<uint8_t, true, 5>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (kind == 1 && ns == 5) return launch_smooth_grad_rb<float, true, 5>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (kind == 0 && ns == 9) return launch_smooth_grad_rb<uint8_t, true, 9>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (kind == 1 && ns == 9) return launch_smooth_grad_rb<float, true, 9>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (kind == 2) return launch_smooth_grad_rb<float, false, 1>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (kind == 3) return launch_smooth_grad_rb<uint8_t, false, 1>(s, a, batch, kind, hred, stream, path, lean, lean_form);
-        if (hred) return -1;                                     // (smooth_grad_hred_ok admits 5 and 9 smoothing taps only)
-    }
-    *lean = false;
-    *lean_form = 0;
-    const size_t lds = smooth_grad_lds_bytes(smooth ? a.smooth.n / 2 : -1, a.R);
-    const dim3 grid((a.ncols + TW - 1) / TW, (a.nrows + TH - 1) / TH, batch), block(256);
+    const dim3 grid(p.gx, p.gy, p.gz), block(p.block);
     int e = 0;
-    *path = KLT_L0_TILED_LDS;
     switch (kind) {
-    case 0: if ((e = set_lds(smooth_grad_kernel<uint8_t, true>, lds))) return e;
-            klt_launch((smooth_grad_kernel<uint8_t, true>), grid, block, lds, s, a); break;
-    case 1: if ((e = set_lds(smooth_grad_kernel<float, true>, lds))) return e;
-            klt_launch((smooth_grad_kernel<float, true>), grid, block, lds, s, a); break;
-    case 2: if ((e = set_lds(smooth_grad_kernel<float, false>, lds))) return e;
-            klt_launch((smooth_grad_kernel<float, false>), grid, block, lds, s, a); break;
-    default: if ((e = set_lds(smooth_grad_kernel<uint8_t, false>, lds))) return e;
-            klt_launch((smooth_grad_kernel<uint8_t, false>), grid, block, lds, s, a); break;
+    case 0: if ((e = set_lds(smooth_grad_kernel<uint8_t, true>, p.lds))) return e;
+            klt_launch((smooth_grad_kernel<uint8_t, true>), grid, block, p.lds, s, a); break;
+    case 1: if ((e = set_lds(smooth_grad_kernel<float, true>, p.lds))) return e;
+            klt_launch((smooth_grad_kernel<float, true>), grid, block, p.lds, s, a); break;
+    case 2: if ((e = set_lds(smooth_grad_kernel<float, false>, p.lds))) return e;
+            klt_launch((smooth_grad_kernel<float, false>), grid, block, p.lds, s, a); break;
+    default: if ((e = set_lds(smooth_grad_kernel<uint8_t, false>, p.lds))) return e;
+            klt_launch((smooth_grad_kernel<uint8_t, false>), grid, block, p.lds, s, a); break;
     }
     return 0;
 }

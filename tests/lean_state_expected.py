@@ -1,5 +1,5 @@
 """KLT_OPT_L0_LAZY_GRAD: the host's rule for a context's pyramid slots restated in plain Python, no GPU -- which builds go out lean
-(wants_lean, the grouping of a batch, l0_lean_ok: api_frames.hip), which tracker launches have a lazy form (track_lazy_capable,
+(wants_lean, the grouping of a batch: api_frames.hip; the plan's `lean`: l0_plan.h), which tracker launches have a lazy form (track_lazy_capable,
 settle_level0, mark_lazy_read: track_kernels.hip, api_track.hip) and who makes level-0 records on demand (ensure_level0_records and its
 ten call sites).  For a sequence of operations the model predicts
   * after every build, what klt_level0_lean and klt_level0_lean_form say (the last group, as the context reports it);
@@ -37,7 +37,7 @@ NCOLS, NROWS = frame_shape()
 
 
 def lean_launch(ncols, nrows, batch, stream):
-    """l0_lean_ok for u8 frames, three levels, subsampling 4, 5 or 9 smoothing taps: the launch of `batch` frames is a streaming kernel's"""
+    """plan_level0's `lean` (asked for) for u8 frames, three levels, subsampling 4, 5 or 9 smoothing taps: the launch of `batch` frames is a streaming kernel's"""
     return goes_lean(ncols, nrows, batch) if stream == 2 else takes_geometry("narrow", ncols, nrows, batch)
 
 

@@ -36,8 +36,8 @@ def _tap_counts(ss, sigma):
 
 def expected_path(ncols, nrows, batch, f32, levels, ss, smooth_sigma_fact, stream_opt=1, hreduce_opt=1, fused_opt=1):
     """(KLT_L0_* code, merged) that klt_level0_path reports after a build of `batch` equal frames: the kernel of level 0 of the LAST group
-    of at most 32 frames, and whether the gradients of that group's levels >= 1 are one launch.  Restates launch_smooth_grad*,
-    smooth_grad_hred_ok, rb_tall_tiles (pyramid_kernels.hip) and build_pyramids_batch (api_frames.hip) at the default window and
+    of at most 32 frames, and whether the gradients of that group's levels >= 1 are one launch.  Restates plan_level0
+    (l0_plan.h; tests/test_l0_plan_rule.py holds the two together) and build_pyramids_batch (api_frames.hip) at the default window and
     gradient sigma."""
     group = (batch - 1) % MAX_BATCH + 1
     ns, nreduce, ngrad = _tap_counts(ss, smooth_sigma_fact)

@@ -66,7 +66,7 @@ def case_id(c):
 
 
 def takes_geometry(geom, ncols, nrows, batch=MAX_BATCH):
-    """the host's rule (l0_stream_geometry, pyramid_kernels.hip) for the geometry's own value of KLT_OPT_L0_STREAM"""
+    """the host's rule (plan_level0, l0_plan.h) for the geometry's own value of KLT_OPT_L0_STREAM"""
     _, strip, seg, _ = GEOMETRIES[geom]
     hred = ncols * nrows * batch >= 1000000 and nrows >= 64 and ncols >= 64
     return hred and ncols >= 2 * strip and -(-ncols // strip) * -(-nrows // seg) * batch >= WORKGROUPS
@@ -240,10 +240,10 @@ def test_compact_plane_allocation_failure(ctx):
 def test_case_list_and_constants():
     """the constants above are the kernels' and the header's; every case takes its geometry under the host's rule at 32 frames and not with
     one frame fewer; widths, heights, both tap counts and both input types are all there for both geometries"""
-    src = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "pyramid_kernels.hip")).read()
+    src = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "l0_plan.h")).read()
     assert re.search(r"L0S_TW = (\d+), L0S_SB = \d+, L0W_TW = (\d+)", src).groups() == ("64", "128")
     assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", src).groups() == (str(WORKGROUPS),) * 2
-    assert re.search(r"force : wide \? (\d+) : (\d+)", src).groups() == ("128", "160")
+    assert re.search(r"shw = seg_of\(L0W_SB, (\d+)\), sh = seg_of\(L0S_SB, (\d+)\)", src).groups() == ("128", "160")
     hdr = open(os.path.join(REPO, "include", "klt_gpu.h")).read()
     assert re.search(r"#define\s+KLT_OPT_L0_LAZY_GRAD\s+(\d+)", hdr).group(1) == str(OPT_L0_LAZY_GRAD)
     assert re.search(r"#define\s+KLT_OPT_FAIL_ALLOC_AFTER\s+(\d+)", hdr).group(1) == str(OPT_FAIL_ALLOC_AFTER)

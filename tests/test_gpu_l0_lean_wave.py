@@ -33,7 +33,7 @@ from pyfeaturetrack_amd._abi import KLT_OPT_L0_LEAN_FORM, L0_LEAN_WAVE_COLS as S
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPT_L0_LAZY_GRAD = 22
 WORKGROUPS = 2048                                # the grid bound of both banded geometries
-BANDED = ((128, 128, 256), (64, 160, 128))       # strip, segment, fewest columns: wide, then narrow (l0_stream_geometry's order)
+BANDED = ((128, 128, 256), (64, 160, 128))       # strip, segment, fewest columns: wide, then narrow (plan_level0's order)
 LEVELS, SS = 2, 4
 ORACLE_FRAMES = (0, 1, 15, 31)
 TAPS = {0.1: 5, 0.2: 9}
@@ -43,13 +43,13 @@ WIDTH_MOD4 = (2 * STRIP + 13, 2 * STRIP + 26)    # ncols % 4 = 1 and 2
 
 
 def goes_lean(ncols, nrows, batch=MAX_BATCH):
-    """the host's rule for a lean launch at the default KLT_OPT_L0_STREAM (smooth_grad_hred_ok, l0_stream_geometry)"""
+    """the host's rule for a lean launch at the default KLT_OPT_L0_STREAM (plan_level0, l0_plan.h: the fused reduction, a streaming geometry)"""
     hred = ncols * nrows * batch >= 1000000 and nrows >= 64 and ncols >= 64
     return hred and any(ncols >= least and -(-ncols // strip) * -(-nrows // seg) * batch >= WORKGROUPS for strip, seg, least in BANDED)
 
 
 def takes_wave(ncols, nrows, ntaps):
-    """... and for the wave form of it (smooth_grad_lean_wave_ok)"""
+    """... and for the wave form of it (plan_level0 again)"""
     return ncols >= 256 and nrows >= ntaps
 
 
@@ -250,13 +250,15 @@ def test_case_list_and_constants():
     kinds, both tap counts and both input types are all there"""
     hdr = open(os.path.join(REPO, "include", "klt_gpu.h")).read()
     src = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "pyramid_kernels.hip")).read()
+    plan = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "l0_plan.h")).read()
     assert int(re.search(r"#define\s+KLT_OPT_L0_LEAN_FORM\s+(\d+)", hdr).group(1)) == KLT_OPT_L0_LEAN_FORM == 23
     assert int(re.search(r"#define\s+KLT_L0_LEAN_WAVE_SEG\s+(\d+)", hdr).group(1)) == SEG
     assert int(re.search(r"LW_COLS = (\d+), LW_HALO = 12", src).group(1)) == STRIP
-    assert re.search(r"return a\.ncols >= 256 && a\.nrows >= a\.smooth\.n;", src)
-    assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", src).groups() == (str(WORKGROUPS),) * 2
-    assert re.search(r"L0S_TW = (\d+), L0S_SB = \d+, L0W_TW = (\d+)", src).groups() == (str(BANDED[1][0]), str(BANDED[0][0]))
-    assert re.search(r"force : wide \? (\d+) : (\d+)", src).groups() == (str(BANDED[0][1]), str(BANDED[1][1]))
+    assert int(re.search(r"L0_WAVE_COLS = (\d+), L0_WAVE_WAVES = 4", plan).group(1)) == STRIP and "LW_COLS == L0_WAVE_COLS" in src
+    assert re.search(r"q\.lean_form_opt == 1 && q\.uniform && q\.ncols >= 256 && q\.nrows >= q\.smooth->n\)", plan)
+    assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", plan).groups() == (str(WORKGROUPS),) * 2
+    assert re.search(r"L0S_TW = (\d+), L0S_SB = \d+, L0W_TW = (\d+)", plan).groups() == (str(BANDED[1][0]), str(BANDED[0][0]))
+    assert re.search(r"shw = seg_of\(L0W_SB, (\d+)\), sh = seg_of\(L0S_SB, (\d+)\)", plan).groups() == (str(BANDED[0][1]), str(BANDED[1][1]))
     widths = [c for c in CASES if c[0] == "w"]
     heights = [c for c in CASES if c[0] != "w"]
     assert [(c[1] % STRIP) for c in widths[:4]] == list(WIDTH_LAST) and [c[1] % 4 for c in widths[4:]] == [1, 2]

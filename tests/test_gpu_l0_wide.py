@@ -22,7 +22,7 @@ from pyramid_expected import MAX_BATCH, OPT_FUSED_HREDUCE, OPT_FUSED_KERNELS, OP
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STREAM_WIDE, STREAM_WIDE_NO_CENTRE = 7, 8       # klt_level0_path: KLT_L0_STREAM_WIDE*
-WIDE_STRIP, WIDE_BAND, SEG_H = 128, 16, 128     # the wide geometry and its segment height (l0_stream_seg in pyramid_kernels.hip)
+WIDE_STRIP, WIDE_BAND, SEG_H = 128, 16, 128     # the wide geometry and its segment height (plan_level0 in l0_plan.h)
 WIDE_WORKGROUPS = 2048                          # its grid bound
 ROW_HALO = 7                                    # rows a segment reads beyond each end with 9 smoothing taps (3 + 4)
 LEVELS, SS = 2, 4
@@ -34,7 +34,7 @@ def wide_grid(ncols, nrows, batch=MAX_BATCH):
 
 
 def takes_wide(ncols, nrows, batch=MAX_BATCH):
-    """the host's rule for value 2 (launch_smooth_grad_rb): the fused reduction's own conditions, two wide strips, the grid bound"""
+    """the host's rule for value 2 (plan_level0, l0_plan.h): the fused reduction's own conditions, two wide strips, the grid bound"""
     hred = ncols * nrows * batch >= TALL_PIXELS and nrows >= 64 and ncols >= 64
     return hred and ncols >= 2 * WIDE_STRIP and wide_grid(ncols, nrows, batch) >= WIDE_WORKGROUPS
 
@@ -103,7 +103,7 @@ def _tc(sigma):
 
 def unelidable_grad_taps(sigma):
     """the gradient taps of the default sigma with the derivative's centre tap -0.0 instead of +0.0: the host then keeps the centre
-    product (deriv_centre_elidable wants the bits of +0.0)"""
+    product (l0_deriv_centre_elidable, l0_plan.h, wants the bits of +0.0)"""
     from pyfeaturetrack_amd.params import taps_from_params
     g, d = taps_from_params(params_from_tc(_tc(sigma)))[2]
     d = list(d)
@@ -206,10 +206,10 @@ def test_shape_list_puts_every_edge_inside_a_frame():
     """the constants above are the kernel's; every shape takes the wide kernel under the host's rule at 32 frames and not one segment or
     strip smaller; the widths and heights are the listed ones; together the shapes have an edge of every kind -- last strip, last band,
     last segment, prologue -- inside a frame, with 5 and with 9 smoothing taps"""
-    src = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "pyramid_kernels.hip")).read()
+    src = open(os.path.join(REPO, "pyfeaturetrack_amd", "csrc", "l0_plan.h")).read()
     assert re.search(r"L0W_TW = (\d+), L0W_SB = (\d+)", src).groups() == (str(WIDE_STRIP), str(WIDE_BAND))
     assert re.search(r"L0W_MIN_WGS = (\d+)", src).group(1) == str(WIDE_WORKGROUPS)
-    assert re.search(r"force : wide \? (\d+) :", src).group(1) == str(SEG_H) and SEG_H % WIDE_BAND == 0
+    assert re.search(r"shw = seg_of\(L0W_SB, (\d+)\)", src).group(1) == str(SEG_H) and SEG_H % WIDE_BAND == 0
     hdr = open(os.path.join(REPO, "include", "klt_gpu.h")).read()
     assert re.search(r"#define\s+KLT_L0_STREAM_WIDE\s+(\d+)", hdr).group(1) == str(STREAM_WIDE)
     assert re.search(r"#define\s+KLT_L0_STREAM_WIDE_NO_CENTRE\s+(\d+)", hdr).group(1) == str(STREAM_WIDE_NO_CENTRE)

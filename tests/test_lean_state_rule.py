@@ -123,9 +123,9 @@ def test_constants_are_the_sources():
                         ("L0_STREAM", L.OPT_L0_STREAM), ("L0_LAZY_GRAD", L.OPT_L0_LAZY_GRAD), ("L0_LEAN_FORM", L.OPT_L0_LEAN_FORM)):
         assert int(re.search(r"#define\s+KLT_OPT_%s\s+(\d+)" % name, hdr).group(1)) == value, name
     assert int(re.search(r"#define\s+KLT_L0_LEAN_FORM_DEFAULT\s+(\d+)", hdr).group(1)) == 1
-    pyr = src("pyfeaturetrack_amd", "csrc", "pyramid_kernels.hip")
-    assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", pyr).groups() == (str(L.WORKGROUPS),) * 2
-    assert int(re.search(r"constexpr int KLT_MAX_BATCH = (\d+);", src("pyfeaturetrack_amd", "csrc", "klt_internal.h")).group(1)) == L.MAX_BATCH
+    plan = src("pyfeaturetrack_amd", "csrc", "l0_plan.h")
+    assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", plan).groups() == (str(L.WORKGROUPS),) * 2
+    assert int(re.search(r"constexpr int KLT_MAX_BATCH = (\d+);", plan).group(1)) == L.MAX_BATCH
     trk = src("pyfeaturetrack_amd", "csrc", "track_kernels.hip")
     assert int(re.search(r"return g_track_variant != 0 && window == 7 && \(long long\)n \* npairs >= (\d+);", trk).group(1)) == L.QUAD_MIN
     assert re.search(r"return track_quad7_rule\(window, n, npairs\) && !tree_sums && n > 0 && npairs > 0;", trk)

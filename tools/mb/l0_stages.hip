@@ -57,12 +57,17 @@ int main(int argc, char **argv)
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     a.reduce = pr.taps; a.h1_nc = nc / 4;
     for (int b = 0; b < B; b++) { float *h1; hipMalloc(&h1, 4 * (size_t)nr * (nc / 4)); a.h1[b] = h1; }
+    // the launch's plan, as the library makes it (the mode sets the options and the wishes; the experiment hooks are the library's)
+    const L0Request q = {nc, nr, B, 0, true, &a.smooth, &a.ggauss, &a.gderiv, &a.reduce, 4, true, wide ? 2 : stream ? 1 : 0, wave ? 1 : 0, !plain, lean_mode};
+    const L0Plan plan = plan_level0(q, l0_tuning_from_env());
+    if (plan.hred == plain || plan.lean != lean_mode || plan.lean_form != (wave ? 2 : lean_mode ? 1 : 0) ||
+        (stream && !wave && (plan.family != L0_FAMILY_BANDED || plan.strip != (wide ? 128 : 64)))) {
+        printf("the plan is not the form asked for\n");
+        return 1;
+    }
     auto go = [&]() {
-        bool lean = lean_mode;
         if (reduce) launch_pyr_reduce(0, pr, 2);
-        int form = wave ? 1 : 0;
-        if (!reduce) launch_smooth_grad(0, a, B, 0, !plain, wide ? 2 : stream, nullptr, &lean, &form);
-        if (lean != lean_mode || form != (wave ? 2 : lean_mode ? 1 : 0)) { printf("the launch did not go out in the form asked for\n"); exit(1); }
+        else launch_smooth_grad(0, a, plan);
     };
     for (int rep = 0; rep < 3; rep++) go();
     hipDeviceSynchronize();
@@ -78,10 +83,9 @@ int main(int argc, char **argv)
     long long clk[64 * 8];
     if (stream) {
         // g_stream_clk accumulated over every launch of this run (3 + 20): per launch, per band of 2048 output pixels (32 rows of a 64-column
-        // strip, 16 of a 128-column one; the segment height is the kernel's own, or KLT_L0_SEG as the library reads it)
+        // strip, 16 of a 128-column one; the segment height is the plan's: the kernel's own, or KLT_L0_SEG as the library reads it)
         hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_stream_clk), sizeof(clk));
-        const int force = getenv("KLT_L0_SEG") ? atoi(getenv("KLT_L0_SEG")) : 0, sb = wide ? 16 : 32;
-        const int seg = force > 0 && force % sb == 0 ? force : wide ? 128 : 160, nb = wide ? 15 : 30;
+        const int sb = plan.band, seg = plan.seg, nb = plan.nstrips;
         const double per = 23.0 * (seg / sb);
         printf("ticks of 10 ns per band of 2048 output pixels (segment 1 of frame 0, %d rows, prologue share included)\nblock | load  hsm  vsm  hgrad vgrad | total\n", seg);
         double sum[5] = {};
