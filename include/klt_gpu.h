@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -53,7 +53,8 @@ typedef enum {
 enum { KLT_TRACKED = 0, KLT_NOT_FOUND = -1, KLT_SMALL_DET = -2, KLT_MAX_ITERATIONS = -3,
        KLT_OOB = -4, KLT_LARGE_RESIDUE = -5,
        KLT_FB_INCONSISTENT = -6, /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */
-       KLT_MODEL_OUTLIER = -7    /* not in the reference: off the frame pair's dominant affine motion (klt_motion_check_async); lost likewise */ };
+       KLT_MODEL_OUTLIER = -7,   /* not in the reference: off the frame pair's dominant affine motion (klt_motion_check_async); lost likewise */
+       KLT_EPIPOLAR_OUTLIER = -8 /* not in the reference: off the frame pair's fundamental matrix (klt_epipolar_check_async); lost likewise */ };
 
 /* selection modes, selectGoodFeatures.py:11-13 */
 enum { KLT_SELECTING_ALL = 1, KLT_REPLACING_SOME = 2 };
@@ -533,6 +534,76 @@ int klt_motion_model_affine(const klt_motion_model *model, double A[4], double t
 /* 0: no motion-check launch yet; 1: the last one ran as three launches on one pair, 2: as three launches on a table of pairs.  A
  * diagnostic, like klt_track_light_path.  Not in the reference; DESIGN.md section 9g. */
 int klt_motion_check_path(klt_ctx *ctx);
+
+/* ---- epipolar check (not in the reference) ---------------------------------------------------------------------- */
+/* The motion-model check's sibling for a camera that translates through a scene with depth, where parallax is no affine motion: a seeded
+ * consensus search for the pair's fundamental matrix F (q^T F p = 0), one least-squares refit, and every tracked feature off the
+ * result becomes (-1, -1, KLT_EPIPOLAR_OUTLIER, aux).  It reads two feature lists and nothing else, and runs stream-ordered behind
+ * whatever wrote them.  Under pure rotation, a planar scene or an exact image translation F is not unique: the check then flags less,
+ * never more, and the motion-model check is the tool.
+ *
+ * THE RULE.  Inputs: lists `in` and `out` of n records and klt_epipolar_params.  All arithmetic is FP64, one rounding per operation,
+ * nothing contracted, in exactly the order written here; only +, -, * and comparisons: no division, no square root.
+ * Magnitudes: working coordinates lie in [-1, 1] (step 1), so every entry of a row is at most 1 and the 45 sums stay below n < 2^24.
+ * In null9 step k first scales the remaining block so that its largest entry, the pivot P, has 0.5 <= |P| < 1; the update
+ * A[i][j]*P - A[k][j]*A[i][k] of entries below 1 then stays below 2, and the next step scales again: nothing grows from step to step.
+ * In the back-substitution every |A[i][j]| <= |A[i][i]| < 1, so after row i the largest |x| is at most 9 times the previous one:
+ * |x| < 9^8 < 2^26, and x[8] is a product of eight pivots, at least 2^-8: f never is all zero.  a and b of the inlier test are then
+ * below 2^28, r*r and den below 2^60.  Nothing comes near 2^1023 or 2^-1022: nothing overflows, nothing that matters underflows.
+ *  1 candidates  exactly step 1 of the motion-model rule (same conditions, list order, cx = ncols / 2, cy = nrows / 2).  With k the
+ *                smallest integer with 2 * (1 << k) >= max(ncols, nrows) and s = 2^-k, the working coordinates are the centred ones
+ *                times s (exact): p = (((double)in.x - cx) * s, ((double)in.y - cy) * s), q likewise from out.  m < min_inliers: no
+ *                model (valid = 0), out untouched.
+ *  2 samples     hypothesis h takes candidates r_j = mulhi32(mix(seed ^ mix(8*h + j)), m), j = 0 .. 7 (mix, mulhi32: the motion-model rule).
+ *  3 row         of a correspondence: (q.x*p.x, q.x*p.y, q.x, q.y*p.x, q.y*p.y, q.y, p.x, p.y, 1.0), the coefficients of q^T F p for F
+ *                row-major as f[0 .. 8].
+ *  4 null9(A)    the null vector of an 8x9 matrix.  For k = 0 .. 7: the pivot is the entry of largest |value| in rows k .. 7, columns
+ *                k .. 8, the bits of |value| compared as integers, ties to the smallest row, then the smallest column.  ef = its biased
+ *                exponent field; ef == 0 or ef == 0x7ff (zero, subnormal, non-finite): null9 fails.  Otherwise rows k and the pivot's,
+ *                then columns k and the pivot's, are swapped (the column permutation is remembered); every entry of rows k .. 7,
+ *                columns k .. 8 is multiplied by the double whose bits are (2045 - ef) << 52, a power of two that leaves the pivot P
+ *                with 0.5 <= |P| < 1; and for rows i > k, columns j > k: A[i][j] = A[i][j]*P - A[k][j]*A[i][k], two products and one
+ *                difference.  Back-substitution: x[8] = 1; for i = 7 .. 0: sum = ((A[i][i+1]*x[i+1] + A[i][i+2]*x[i+2]) + ...) left
+ *                to right, then x[j] = x[j]*A[i][i] for every j > i, then x[i] = -sum.  Last the column permutation is undone.  Two
+ *                equal rows leave an exactly zero row: repeated picks need no special case.
+ *  5 hypothesis  f = null9 of the eight rows of its picks; null9 fails: score -1.  Candidate k is an inlier of f iff r*r <= t2 * den
+ *                (NaN fails), the Sampson distance cross-multiplied, with t2 = ts*ts, ts = (double)max_error * s and
+ *                  a0 = (f0*p.x + f1*p.y) + f2    a1 = (f3*p.x + f4*p.y) + f5    a2 = (f6*p.x + f7*p.y) + f8
+ *                  b0 = (f0*q.x + f3*q.y) + f6    b1 = (f1*q.x + f4*q.y) + f7
+ *                  r  = (a0*q.x + a1*q.y) + a2    den = ((a0*a0 + a1*a1) + b0*b0) + b1*b1
+ *                The score is the number of inliers; the best hypothesis has the largest score, ties go to the smallest h.  Best
+ *                score < min_inliers: valid = 0, out untouched.
+ *  6 refit, once the 45 sums M[i][j] = SUM row[i]*row[j], i <= j, over the inliers of the best hypothesis (M is symmetric): the term of
+ *                candidate k joins partial k mod 64 in increasing k (non-inliers are skipped), the 64 partials fold by
+ *                p[l] += p[l + w], l < w, w = 32 .. 1.  g = the index of the largest |f_i| of the hypothesis, ties to the smallest.
+ *                f' = null9(M without row g): the normal equations of least squares with f_g free.  null9 succeeds: the model is f',
+ *                valid = 1; otherwise the hypothesis is kept, valid = 2.  The inlier test is evaluated once more under the final
+ *                model; there is no iteration.
+ *  7 outputs     every candidate that is not an inlier of the final model becomes (-1, -1, KLT_EPIPOLAR_OUTLIER, out.aux) in `out`;
+ *                every other byte of `out` stays.  One klt_epipolar_model goes to a feature buffer of six klt_feat records: valid = 0:
+ *                f, n_inliers and hypothesis_inliers are 0, hypothesis is -1; otherwise the final model (in working coordinates), its
+ *                inlier count, the best hypothesis and its score.  n_candidates = m; pad = ncols | nrows << 16 in every record. */
+typedef struct { int32_t mode; int32_t ncols, nrows; int32_t hypotheses; uint32_t seed; int32_t min_inliers; float max_error; } klt_epipolar_params;
+typedef struct { double f[9]; int32_t valid, n_candidates, n_inliers, hypothesis, hypothesis_inliers, pad; } klt_epipolar_model;
+/* mode: 0 = off (the default), 1 = on; anything else is KLT_ERR_ARG, and so are hypotheses outside 1 .. 65536, min_inliers < 8,
+ * max_error negative or NaN, and (mode 1) ncols / nrows outside 1 .. 65535.  Defaults: 512 hypotheses, seed 0, min_inliers 16,
+ * max_error 1.0 px.  Not in the reference; DESIGN.md section 9h. */
+int klt_set_epipolar_params(klt_ctx *ctx, const klt_epipolar_params *p);
+/* The check on two resident lists, with the conventions of klt_motion_check_async: fb_out is rewritten in place, fb_model (allocated if
+ * needed, six records) takes the klt_epipolar_model; the three buffers pairwise distinct by index and by address (KLT_ERR_ARG); lists
+ * shorter than n: KLT_ERR_STATE; mode 0: KLT_ERR_STATE with a klt_last_error text; n == 0: KLT_OK, nothing enqueued.  The scratch
+ * belongs to the context and to this check alone (out of memory: KLT_ERR_NOMEM, nothing half-allocated). */
+int klt_epipolar_check_async(klt_ctx *ctx, int fb_in, int fb_out, int fb_model, int n);
+/* npairs pairs in the same launches; every fb_model distinct from every list and from each other, every fb_out from every other list. */
+int klt_epipolar_check_batch_async(klt_ctx *ctx, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n);
+/* synchronous, host arrays: out is rewritten, *model filled, *n_outliers (may be NULL) = the records that became KLT_EPIPOLAR_OUTLIER. */
+int klt_epipolar_check(klt_ctx *ctx, const klt_feat *in, klt_feat *out, klt_epipolar_model *model, int n, int *n_outliers);
+/* host only: F (row-major) in UNCENTRED pixel coordinates, q^T F p = 0 for p in frame 1 and q in frame 2: T^T f T with
+ * T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]], scaled to unit Frobenius norm.  KLT_ERR_ARG for a null pointer, KLT_ERR_STATE for a
+ * record with valid == 0 (or one whose norm is zero or not finite). */
+int klt_epipolar_matrix(const klt_epipolar_model *model, double F[9]);
+/* 0: no epipolar-check launch yet; 1: the last one ran as three launches on one pair, 2: on a table of pairs.  A diagnostic. */
+int klt_epipolar_check_path(klt_ctx *ctx);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

@@ -35,6 +35,16 @@ class KltMotionModel(C.Structure):
                 ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
 
 
+class KltEpipolarParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ncols", C.c_int32), ("nrows", C.c_int32), ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+                ("min_inliers", C.c_int32), ("max_error", C.c_float)]
+
+
+class KltEpipolarModel(C.Structure):
+    _fields_ = [("f", C.c_double * 9), ("valid", C.c_int32), ("n_candidates", C.c_int32), ("n_inliers", C.c_int32),
+                ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
+
+
 class KltParams(C.Structure):
     _fields_ = [
         ("mindist", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
@@ -168,6 +178,12 @@ SYMBOLS = {
     "klt_motion_check": (_I, [_P, _P, _P, C.POINTER(KltMotionModel), _I, _PI]),
     "klt_motion_model_affine": (_I, [C.POINTER(KltMotionModel), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "klt_motion_check_path": (_I, [_P]),
+    "klt_set_epipolar_params": (_I, [_P, C.POINTER(KltEpipolarParams)]),
+    "klt_epipolar_check_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_epipolar_check_batch_async": (_I, [_P, _PI, _PI, _PI, _I, _I]),
+    "klt_epipolar_check": (_I, [_P, _P, _P, C.POINTER(KltEpipolarModel), _I, _PI]),
+    "klt_epipolar_matrix": (_I, [C.POINTER(KltEpipolarModel), C.POINTER(C.c_double)]),
+    "klt_epipolar_check_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

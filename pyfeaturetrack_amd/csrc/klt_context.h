@@ -10,6 +10,7 @@
 //   api_track.hip     tracker launches (single pair, batched), constant-velocity prediction, iteration counters
 //   api_quality.hip   per-feature track quality (single pair, batched)
 //   api_model.hip     motion-model check (single pair, batched), the model record as an affine map
+//   api_epipolar.hip  epipolar check (single pair, batched), the model record as a fundamental matrix in pixels
 //   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
@@ -296,6 +297,12 @@ struct klt_ctx {
     unsigned char *model_scratch = nullptr;
     size_t model_scratch_cap = 0;
     SentTable<ModelPair> model_table;                              // klt_motion_check_batch_async
+    // epipolar check (klt_set_epipolar_params, klt_epipolar_check*): scratch and pair table of its own, laid out like the motion-model check's
+    klt_epipolar_params epip{0, 0, 0, 512, 0u, 16, 1.0f};
+    int epi_path = 0;                                              // klt_epipolar_check_path
+    unsigned char *epi_scratch = nullptr;
+    size_t epi_scratch_cap = 0;
+    SentTable<ModelPair> epi_table;                                // klt_epipolar_check_batch_async
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -466,6 +473,21 @@ inline int own_records(klt_ctx *c, int fb, std::initializer_list<int> others, co
         if (fb_holds_records(c, other, 0) && c->fbs[fb].d == c->fbs[other].d) return fail(c, KLT_ERR_ARG, not_distinct);
     return 0;
 }
+
+// ---- api_model.hip
+// What the two consensus checks over feature lists (motion model: api_model.hip, epipolar: api_epipolar.hip) differ in before their
+// launches: whose scratch, how many hypotheses' scores, how many feature records the model record takes, whether the check is on and
+// what to say when it is not.  consensus_prepare* hold the one copy of the refusals, of the scratch layout and of the pair descriptors.
+struct ConsensusCheck {
+    unsigned char *&scratch;
+    size_t &scratch_cap;
+    int hypotheses, model_records;
+    bool on;
+    const char *off_message;
+};
+int consensus_prepare(klt_ctx *c, ConsensusCheck k, int fb_in, int fb_out, int fb_model, int n, ModelPair *one, int *go);
+int consensus_prepare_batch(klt_ctx *c, ConsensusCheck k, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n,
+                            std::vector<ModelPair> *table, int *go);
 
 // ---- api_frames.hip
 // The kernels address a plane with 32-bit BYTE offsets into a buffer descriptor of 2 GB (raw buffer operations, klt_internal.h), and the

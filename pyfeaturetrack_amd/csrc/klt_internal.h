@@ -136,6 +136,15 @@ struct ModelArgs {
     double min_area;
 };
 
+// the epipolar check (klt_epipolar_check_async) gathers its candidates with the motion-model check's launch and
+// descriptors (ModelPair::model then points at a klt_epipolar_model, in a feature buffer of six records; ModelArgs::min_area is unused,
+// t2 is the squared threshold in working coordinates); its own two kernels also take the working scale
+static_assert(sizeof(klt_epipolar_model) == 6 * sizeof(klt_feat), "an epipolar model record lives in a feature buffer of six records");
+struct EpipolarArgs {
+    ModelArgs m;
+    double s;                           // 2^-k, k the smallest integer with 2 * (1 << k) >= max(ncols, nrows)
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -427,6 +436,9 @@ int launch_track_quality(hipStream_t s, const QualityArgs &a);
 void launch_model_gather(hipStream_t s, const ModelArgs &a);
 void launch_model_score(hipStream_t s, const ModelArgs &a);
 void launch_model_decide(hipStream_t s, const ModelArgs &a);
+// the epipolar check (epipolar_kernels.hip) behind launch_model_gather: one score per hypothesis, the decision
+void launch_epipolar_score(hipStream_t s, const EpipolarArgs &a);
+void launch_epipolar_decide(hipStream_t s, const EpipolarArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

@@ -20,77 +20,30 @@
 //                         under the final model, scatter the outlier records through the candidate-to-record index (one 16-byte store
 //                         each) and count; thread 0 writes the 80-byte model record.
 // Batched form: blockIdx.y selects the pair from a table in device memory (ModelPair), the mechanism of QualityPair.
-#include "klt_internal.h"
+#include "consensus_primitives.h"
 
 #pragma clang fp contract(off)
 
 namespace model_kernels {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
+using namespace consensus;
 
 constexpr int GATHER_WAVES = 16, GATHER_ROUNDS = 8, GATHER_THREADS = 64 * GATHER_WAVES;
 constexpr int SCORE_WAVES = 4;
 constexpr int DECIDE_THREADS = 512;
 constexpr int SCORE_AHEAD = 4, SUM_AHEAD = 8, FINAL_AHEAD = 4;      // candidates a lane loads before it uses the first: the loops wait for L2, not for arithmetic
 
-template <bool BATCH>
-__device__ __forceinline__ ModelPair pair_of(const ModelArgs &a)
-{
-    if (!BATCH) return a.one;
-    typedef const __attribute__((address_space(4))) ModelPair *cptr;
-    const cptr c = (cptr)(a.pairs + blockIdx.y);
-    ModelPair pr;
-    pr.in = c->in; pr.out = c->out; pr.model = c->model; pr.cand = c->cand; pr.idx = c->idx; pr.scores = c->scores; pr.count = c->count;
-    return pr;
-}
-
 // 0 <= v < limit as f32 comparisons, false for NaN and the infinities
 __device__ __forceinline__ bool inside(float v, int limit) { return v >= 0.f && v < (float)limit; }
-
-__device__ __forceinline__ uint32_t mix(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// candidate number r_j of hypothesis h among m candidates
-__device__ __forceinline__ int pick(uint32_t seed, uint32_t h, uint32_t j, int m)
-{
-    return (int)__umulhi(mix(seed ^ mix(3u * h + j)), (uint32_t)m);
-}
-
-struct Cand { double px, py, qx, qy; };
-
-__device__ __forceinline__ Cand load_cand(const double *cand, int k)
-{
-    const f64x2 *c = reinterpret_cast<const f64x2 *>(cand) + 2 * (size_t)k;
-    const f64x2 p = c[0], q = c[1];
-    return Cand{p.x, p.y, q.x, q.y};
-}
-
-// U candidates k0 + stride * j + lane_or_thread, j = 0 .. U-1, all loads issued before the first is used; one beyond m is (0, 0, 0, 0), ok[j] false
-template <int U>
-__device__ __forceinline__ void load_ahead(const double *cand, int k0, int stride, int m, Cand (&c)[U], bool (&ok)[U])
-{
-#pragma unroll
-    for (int j = 0; j < U; j++) {
-        const int k = k0 + stride * j;
-        ok[j] = k < m;
-        c[j] = Cand{0., 0., 0., 0.};
-        if (ok[j]) c[j] = load_cand(cand, k);
-    }
-}
 
 struct Model { double nxx, nxy, ntx, nyx, nyy, nty, d; };
 
 // step 3 of the rule: the seven numbers of hypothesis h
 __device__ __forceinline__ Model hypothesis(const ModelPair &pr, uint32_t seed, int h, int m)
 {
-    const Cand c0 = load_cand(pr.cand, pick(seed, (uint32_t)h, 0u, m));
-    const Cand c1 = load_cand(pr.cand, pick(seed, (uint32_t)h, 1u, m));
-    const Cand c2 = load_cand(pr.cand, pick(seed, (uint32_t)h, 2u, m));
+    const Cand c0 = load_cand(pr.cand, pick<3>(seed, (uint32_t)h, 0u, m));
+    const Cand c1 = load_cand(pr.cand, pick<3>(seed, (uint32_t)h, 1u, m));
+    const Cand c2 = load_cand(pr.cand, pick<3>(seed, (uint32_t)h, 2u, m));
     const double ux = c1.px - c0.px, uy = c1.py - c0.py, vx = c2.px - c0.px, vy = c2.py - c0.py;
     const double ax = c1.qx - c0.qx, ay = c1.qy - c0.qy, bx = c2.qx - c0.qx, by = c2.qy - c0.qy;
     Model M;
@@ -124,19 +77,6 @@ __device__ __forceinline__ double threshold(const Model &M, double t2)
 {
     const double dd = M.d * M.d;
     return t2 * dd;
-}
-
-// the 64 partials of the rule, one per lane, folded into lane 0 (p[l] += p[l + w], l < w, w = 32 .. 1) and handed to every lane
-__device__ __forceinline__ double fold64(double p)
-{
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) p = p + __shfl_down(p, w);
-    return __shfl(p, 0);
-}
-
-__device__ __forceinline__ int lane_rank(unsigned long long ballot)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
 template <bool BATCH>
@@ -255,23 +195,10 @@ __global__ __launch_bounds__(DECIDE_THREADS) void model_decide_kernel(ModelArgs 
         return;
     }
     // the best hypothesis: the largest score, ties to the smallest h
-    unsigned long long key = 0;
-    for (int h = t; h < a.hypotheses; h += DECIDE_THREADS) {
-        const unsigned long long k = (unsigned long long)(unsigned)(pr.scores[h] + 1) << 32 | (0xffffffffu - (unsigned)h);
-        key = k > key ? k : key;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned lo = __shfl_down((unsigned)key, o), hi = __shfl_down((unsigned)(key >> 32), o);
-        const unsigned long long k = (unsigned long long)hi << 32 | lo;
-        key = k > key ? k : key;
-    }
-    if (lane == 0) wave_key[w] = key;
+    reduce_best_key<DECIDE_THREADS>(pr.scores, a.hypotheses, wave_key);
     if (t == 0) inlier_count = 0;
     __syncthreads();
-    key = wave_key[0];
-#pragma unroll
-    for (int i = 1; i < DECIDE_THREADS / 64; i++) key = wave_key[i] > key ? wave_key[i] : key;
+    const unsigned long long key = best_key_of<DECIDE_THREADS>(wave_key);
     const int best_score = (int)(unsigned)(key >> 32) - 1;
     const int best = (int)(0xffffffffu - (unsigned)key);
     if (best_score < a.min_inliers) {

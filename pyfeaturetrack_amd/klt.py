@@ -38,6 +38,7 @@ class kltState:
     KLT_LARGE_RESIDUE = -5
     KLT_FB_INCONSISTENT = -6          # not in the reference: rejected by the forward-backward check (tc.forwardBackwardCheck)
     KLT_MODEL_OUTLIER = -7            # not in the reference: off the frame pair's dominant affine motion (tc.motionModelCheck)
+    KLT_EPIPOLAR_OUTLIER = -8         # not in the reference: off the frame pair's fundamental matrix (tc.epipolarCheck)
 
 
 def _pyramidSigma(tc):
@@ -106,6 +107,15 @@ class KLT_TrackingContext:
         self.model_hypotheses = 256
         self.model_seed = 0
         self.model_min_inliers = 8
+        # epipolar check (not in the reference): False, or True -- the motion-model check's sibling for a camera that moves through a scene
+        # with depth: the consensus search finds the pair's fundamental matrix and every tracked feature further than epipolar_max_error px
+        # (Sampson distance) from its epipolar line is lost (KLT_EPIPOLAR_OUTLIER); KLTTrackFeatures leaves tc.epipolar_last,
+        # KLTTrackSequence's table carries ft.epipolar.  Not together with motionModelCheck.
+        self.epipolarCheck = False
+        self.epipolar_max_error = 1.0
+        self.epipolar_hypotheses = 512
+        self.epipolar_seed = 0
+        self.epipolar_min_inliers = 16
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -718,6 +728,7 @@ class KLT_FeatureTable:
     val = property(lambda self: self.rec["val"])
     quality = None            # KLTTrackSequence with tc.trackQuality: [nFrames, nFeatures] records (residue, ncc, min_eig, val)
     models = None             # KLTTrackSequence with tc.motionModelCheck: [nFrames] backend.MODEL_DTYPE records, row 0 all zero
+    epipolar = None           # KLTTrackSequence with tc.epipolarCheck: [nFrames] backend.EPIPOLAR_DTYPE records, row 0 all zero
 
     def feature(self, feat, frame):
         return _feature_of(self.rec[frame, feat])
@@ -743,6 +754,10 @@ def KLTPrintTrackingContext(tc):
     print("\n\tpyramid_last = {0}".format(tc.pyramid_last))
     print("\tpyramid_last_gradx = {0}".format(tc.pyramid_last_gradx))
     print("\tpyramid_last_grady = {0}".format(tc.pyramid_last_grady))
+    if getattr(tc, "epipolarCheck", False):          # (not in the reference: printed only when the check is on)
+        print("")
+        for name in ("epipolarCheck", "epipolar_max_error", "epipolar_hypotheses", "epipolar_seed", "epipolar_min_inliers"):
+            print("\t{0} = {1}".format(name, getattr(tc, name, None)))
     print("\n")
 
 

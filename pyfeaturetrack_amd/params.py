@@ -1,7 +1,7 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import numpy as np
 
-from ._abi import KltAffineParams, KltFbParams, KltLightParams, KltModelParams, KltParams
+from ._abi import KltAffineParams, KltEpipolarParams, KltFbParams, KltLightParams, KltModelParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -135,6 +135,41 @@ def model_params_from_tc(tc, ncols=None, nrows=None):
         raise ValueError("the motion-model check takes frames of 1 .. 65535 columns and rows")
     mp.hypotheses, mp.seed, mp.min_inliers, mp.max_error, mp.min_area = hyp, seed, inl, err, area
     return mp
+
+
+def epipolar_params_from_tc(tc, ncols=None, nrows=None):
+    """tc.epipolarCheck / tc.epipolar_max_error / tc.epipolar_hypotheses / tc.epipolar_seed / tc.epipolar_min_inliers -> klt_epipolar_params
+    for a frame of ncols x nrows: False (the default) packs mode 0, True mode 1.  All are read with defaults: a tracking context made
+    elsewhere has none of them.  ValueError -- before any device work -- for a value that is no bool, for the check together with
+    tc.motionModelCheck (one consensus check per pair: the planar one or this) or with tc.affineConsistencyCheck >= 0 (what the
+    motion-model check refuses), and for parameters klt_set_epipolar_params would refuse."""
+    on = getattr(tc, "epipolarCheck", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("tc.epipolarCheck must be True or False (got {0!r})".format(on))
+    ep = KltEpipolarParams()
+    ep.mode = 1 if on else 0
+    ep.ncols, ep.nrows = int(ncols or 0), int(nrows or 0)
+    if not ep.mode:
+        ep.hypotheses, ep.seed, ep.min_inliers, ep.max_error = 512, 0, 16, 1.0
+        return ep
+    if getattr(tc, "motionModelCheck", None) is not None:
+        raise ValueError("epipolarCheck and motionModelCheck cannot both be switched on")
+    if getattr(tc, "affineConsistencyCheck", -1) >= 0:
+        raise ValueError("epipolarCheck and affineConsistencyCheck cannot both be switched on")
+    hyp, seed = int(getattr(tc, "epipolar_hypotheses", 512)), int(getattr(tc, "epipolar_seed", 0))
+    inl, err = int(getattr(tc, "epipolar_min_inliers", 16)), float(getattr(tc, "epipolar_max_error", 1.0))
+    if not 1 <= hyp <= 65536:
+        raise ValueError("tc.epipolar_hypotheses must lie in 1 .. 65536 (got {0})".format(hyp))
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError("tc.epipolar_seed must lie in 0 .. 2**32 - 1 (got {0})".format(seed))
+    if inl < 8:
+        raise ValueError("tc.epipolar_min_inliers must be at least 8 (got {0})".format(inl))
+    if not err >= 0.0:
+        raise ValueError("tc.epipolar_max_error must be a number >= 0")
+    if ncols is not None and not (1 <= ep.ncols <= 65535 and 1 <= ep.nrows <= 65535):
+        raise ValueError("the epipolar check takes frames of 1 .. 65535 columns and rows")
+    ep.hypotheses, ep.seed, ep.min_inliers, ep.max_error = hyp, seed, inl, err
+    return ep
 
 
 def guess_records(guess, n, affine=False):

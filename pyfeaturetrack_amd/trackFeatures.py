@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import fb_params_from_tc, guess_records, light_params_from_tc, model_params_from_tc
+from .params import epipolar_params_from_tc, fb_params_from_tc, guess_records, light_params_from_tc, model_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -399,7 +399,12 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     affine motion is found among the tracks and every tracked feature further than tc.model_max_error px from it comes back lost, as
     (-1, -1, KLT_MODEL_OUTLIER); tc.model_last is then a dict A (2x2), t, valid, candidates, inliers, hypothesis.
     Works with `guess=`, tc.forwardBackwardCheck, tc.lightingCompensation and tc.trackQuality (a flagged record is not measured);
-    ValueError together with tc.affineConsistencyCheck >= 0, for another value and for parameters out of range."""
+    ValueError together with tc.affineConsistencyCheck >= 0, for another value and for parameters out of range.
+    tc.epipolarCheck = True (not in the reference): in the same place the frame pair's fundamental matrix is found among the tracks and
+    every tracked feature further than tc.epipolar_max_error px (Sampson distance) from its epipolar line comes back lost, as
+    (-1, -1, KLT_EPIPOLAR_OUTLIER); tc.epipolar_last is then the backend.EPIPOLAR_DTYPE record (backend.epipolar_matrix turns it into F
+    in pixels).  For a camera that moves through a scene with depth, where parallax is no affine motion.  Works
+    with what tc.motionModelCheck works with; ValueError together with it, with tc.affineConsistencyCheck >= 0 and for bad values."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -408,6 +413,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     light_params_from_tc(tc, guess=guess is not None)      # (ValueError for lightingCompensation with a check, a prior or a guess, likewise)
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
     model_params_from_tc(tc)                          # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
+    epipolar_params_from_tc(tc)                       # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -441,6 +447,12 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_MODEL
         ctx.set_model_params(model)
         ctx.motion_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_MODEL, nfeat)
+    # tc.epipolarCheck: the same place, the same buffers, a model record of its own (never together with the motion-model check)
+    epipolar = epipolar_params_from_tc(tc, ncols, nrows)
+    if epipolar.mode:
+        from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR
+        ctx.set_epipolar_params(epipolar)
+        ctx.epipolar_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR, nfeat)
     # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
     # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
     quality = bool(getattr(tc, "trackQuality", False))
@@ -459,6 +471,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check, guess=guess)
         if model.mode:
             ctx.motion_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_MODEL, nfeat)
+        if epipolar.mode:
+            ctx.epipolar_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR, nfeat)
         if quality:
             ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
@@ -481,6 +495,9 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
     if model.mode:                                    # one more download of 80 bytes
         from .backend import MODEL_DTYPE, model_summary
         tc.model_last = model_summary(ctx.model_download(_FB_API_MODEL) if nfeat else np.zeros(1, MODEL_DTYPE)[0])
+    if epipolar.mode:                                 # one more download of 96 bytes
+        from .backend import EPIPOLAR_DTYPE
+        tc.epipolar_last = ctx.epipolar_download(_FB_API_EPIPOLAR) if nfeat else np.zeros(1, EPIPOLAR_DTYPE)[0]
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

@@ -19,6 +19,7 @@ _FB_ROW0 = 60001
 _FB_GUESS = 65525            # ... and the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
 _FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality records, laid out like the feature table (below _FB_TABLE)
 _FBM_TABLE = 48000           # tc.motionModelCheck: a parallel table of model records, five feature records per frame (below _FBQ_TABLE)
+_FBE_TABLE = 42000           # tc.epipolarCheck: a parallel table of epipolar model records, six feature records per frame (below _FBM_TABLE)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -154,6 +155,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     tc.motionModelCheck = "affine": one motion-model check per frame behind the tracker and in front of that frame's replacement pass, which
     refills the slots it flagged (KLT_MODEL_OUTLIER); `ft.models` holds one backend.MODEL_DTYPE record per frame, row 0 all zero.  Not
     together with the affine consistency check.
+    tc.epipolarCheck = True: one epipolar check per frame in the same place (never both); the replacement pass refills the slots it flagged
+    (KLT_EPIPOLAR_OUTLIER); `ft.epipolar` holds one backend.EPIPOLAR_DTYPE record per frame, row 0 all zero.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
@@ -168,6 +171,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
     from .params import model_params_from_tc
     model_params_from_tc(tc)             # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
+    from .params import epipolar_params_from_tc
+    epipolar_params_from_tc(tc)          # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -230,15 +235,20 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     model = model_params_from_tc(tc, ncols, nrows)       # the same check behind every tracker launch, its record into a table of its own
     if model.mode:
         ctx.set_model_params(model)
+    from .params import epipolar_params_from_tc
+    epipolar = epipolar_params_from_tc(tc, ncols, nrows)     # ... or this one (never both), six records per frame in another table
+    if epipolar.mode:
+        ctx.set_epipolar_params(epipolar)
     mtables = []
+    mbase, mrecords = (_FBE_TABLE, 6) if epipolar.mode else (_FBM_TABLE, 5)
 
     def mrow_fb(k):
         ci, off = divmod(k, chunk)
         if ci == len(mtables):
-            base = _FBM_TABLE + ci * (chunk + 1)
-            ctx.featbuf_alloc(base, chunk * 5)
+            base = mbase + ci * (chunk + 1)
+            ctx.featbuf_alloc(base, chunk * mrecords)
             for j in range(chunk):
-                ctx.featbuf_view(base + 1 + j, base, j * 5, 5)
+                ctx.featbuf_view(base + 1 + j, base, j * mrecords, mrecords)
             mtables.append(base)
         return mtables[ci] + 1 + off
 
@@ -319,6 +329,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                     ctx.track_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
                 if model.mode:                       # wherever the tracker goes, in front of the quality launch and of frame j's select_begin
                     ctx.motion_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
+                if epipolar.mode:                    # likewise
+                    ctx.epipolar_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
                 if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
                     ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
@@ -424,18 +436,23 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
             ctx.featbuf_download_into(base, rec[lo:hi])
         ft.quality = rec.view(QUALITY_DTYPE)
         ft.quality[0] = 0                                        # nothing was tracked into the first frame
-    if model.mode:
-        from .backend import FEAT_DTYPE, MODEL_DTYPE
-        rec = np.zeros((nframes, 5), FEAT_DTYPE)
+    if model.mode or epipolar.mode:
+        from .backend import EPIPOLAR_DTYPE, FEAT_DTYPE, MODEL_DTYPE
+        dtype = EPIPOLAR_DTYPE if epipolar.mode else MODEL_DTYPE
+        rec = np.zeros((nframes, mrecords), FEAT_DTYPE)
         for ci, base in enumerate(mtables):
             lo = ci * chunk
             hi = min(nframes, lo + chunk)
             if hi > lo:
                 ctx.featbuf_download_into(base, rec[lo:hi])
-        ft.models = rec.view(MODEL_DTYPE).reshape(nframes)
+        records = rec.view(dtype).reshape(nframes)
         if nFeatures == 0:
-            ft.models[:] = np.zeros(1, MODEL_DTYPE)[0]           # (no list, no launch: nothing was written)
-        ft.models[0] = np.zeros(1, MODEL_DTYPE)[0]               # nothing was tracked into the first frame
+            records[:] = np.zeros(1, dtype)[0]                   # (no list, no launch: nothing was written)
+        records[0] = np.zeros(1, dtype)[0]                       # nothing was tracked into the first frame
+        if epipolar.mode:
+            ft.epipolar = records
+        else:
+            ft.models = records
     if tc.sequentialMode:
         # leave the context as the per-frame API would: the last frame's pyramids are "frame 1" of the next call
         from .trackFeatures import _pyramid_handles
