@@ -144,6 +144,12 @@ void       *klt_stream_handle(klt_ctx *ctx);                /* the context's hip
  * builds go lean does not depend on it, and the planes are the same bit for bit. */
 #define KLT_OPT_L0_LEAN_FORM 23
 #define KLT_L0_LEAN_FORM_DEFAULT 1
+/* How the tracker that makes its level-0 gradients itself (KLT_OPT_L0_LAZY_GRAD) enters level 0.  1: one fused phase makes the gradients
+ * of the template's footprint and of the first search footprint together -- the image patches of both are requested before anything waits
+ * for either, each patch row is filtered by one lane; 0: one phase per footprint, one after the other.  Footprints that a Newton step moves
+ * to another pixel are recomputed one at a time in both forms.  Same results bit for bit. */
+#define KLT_OPT_TRACK_LAZY_FORM 24
+#define KLT_TRACK_LAZY_FORM_DEFAULT 1
 #define KLT_L0_LEAN_WAVE_SEG 32     /* segment height of the wave form, rows (pyfeaturetrack_amd/_abi.py carries the same figure) */
 int klt_set_option(klt_ctx *ctx, int option, int value);
 

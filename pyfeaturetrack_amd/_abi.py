@@ -12,6 +12,8 @@ KLT_MAX_LEVELS = 8
 KLT_OPT_L0_LEAN_FORM = 23
 L0_LEAN_WAVE_COLS = 232
 L0_LEAN_WAVE_SEG = 32              # KLT_L0_LEAN_WAVE_SEG
+# how the lazy tracker enters level 0 (include/klt_gpu.h): 1 the fused phase, 0 one phase per footprint
+KLT_OPT_TRACK_LAZY_FORM = 24
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkltgpu.so")
 

@@ -368,6 +368,11 @@ int klt_set_option(klt_ctx *c, int option, int value)
         c->l0_lean_form_opt = value;
         return KLT_OK;
     }
+    if (option == KLT_OPT_TRACK_LAZY_FORM) {
+        if (value < 0 || value > 1) return fail(c, KLT_ERR_ARG, "KLT_OPT_TRACK_LAZY_FORM takes 0 or 1");
+        c->track_lazy_form = value;
+        return KLT_OK;
+    }
     if (option == KLT_OPT_TRACK_XCD_ORDER) { c->track_xcd_order = value != 0; return KLT_OK; }
     if (option == KLT_OPT_BUILD_STREAM) {
         if (!value && c->bstream) HIPCHK(c, hipStreamSynchronize(c->bstream));      // pending builds finish; their events stay valid

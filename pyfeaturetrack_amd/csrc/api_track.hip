@@ -217,7 +217,7 @@ static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nl
         TrackLazyArgs la;
         static_cast<TrackArgsBase &>(la) = a;
         for (int i = 0; i < 4; i++) { la.kg[i] = c->gauss[2].k[i]; la.kd[i] = c->deriv[2].k[i]; }
-        if (launch_track_lazy(c->stream, la)) return fail(c, KLT_ERR_STATE, "tracker launch: no lazy form for this launch");
+        if (launch_track_lazy(c->stream, la, c->track_lazy_form)) return fail(c, KLT_ERR_STATE, "tracker launch: no lazy form for this launch");
         return 0;
     }
     if (c->lightp.mode) {                                   // gain / bias tracking (klt_set_light_params): kernels of their own, features in list order

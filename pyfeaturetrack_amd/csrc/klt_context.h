@@ -200,6 +200,7 @@ struct klt_ctx {
     int l0_lean_form = 0;                     // klt_level0_lean_form: 0 not lean, 1 banded, 2 wave (that group's launch)
     uint64_t cfg_gen = 1;                     // counts the changes of the taps and of the pyramid's shape (Slot::built_cfg)
     bool track_xcd_order = true;              // KLT_OPT_TRACK_XCD_ORDER
+    int track_lazy_form = KLT_TRACK_LAZY_FORM_DEFAULT;   // KLT_OPT_TRACK_LAZY_FORM: 1 the fused level-0 entry phase of the lazy tracker, 0 two calls
     uint64_t waited_built_serial = ~0ull;     // the build event the main stream waited for last (wait_built)
     // selection scratch
     float *sel_img = nullptr, *sel_rec = nullptr, *sat = nullptr, *valmap = nullptr;   // compact image, pixel records (KLT_PIX_STRIDE)

@@ -277,7 +277,7 @@ __device__ __forceinline__ float plane_load(plane_rsrc r, unsigned byte_off)
 // ---- shared by the level-0 kernels (pyramid_kernels.hip) and the tracker's level-0 gradients on demand (track_kernels.hip): one text, so
 // that the two cannot drift apart.  (Both files switch contraction off for the whole translation unit, as the build's flags do.)
 // The reflect map for indices at most n beyond either end (frames at least as large as the halo): branch-free
-__device__ __forceinline__ int reflect_once(int i, int n)
+__host__ __device__ __forceinline__ int reflect_once(int i, int n)
 {
     return i < 0 ? -1 - i : i >= n ? 2 * n - 1 - i : i;
 }
@@ -294,7 +294,7 @@ struct TapRegs { double k[NT]; };
 // ZC (antisymmetric taps only): the centre tap is +0.0 and the centre sample is >= +0 and finite, so the first product c[0] * k[H]
 // is +0 and the first addition +0 + p equals p + 0.0 bit for bit (-0 included): the multiply is dropped, the addition kept.
 template <int NT, int SYM, bool ZC = false>
-__device__ __forceinline__ float corr_regs(const double *c /* centre */, const TapRegs<NT> &t)
+__host__ __device__ __forceinline__ float corr_regs(const double *c /* centre */, const TapRegs<NT> &t)
 {
     constexpr int H = NT / 2;
     static_assert(!ZC || SYM < 0, "centre-tap elision is for the derivative taps");
@@ -427,7 +427,8 @@ int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
 // Would launch_track take the plain 7x7 quad kernel for this launch (the one kernel with a lazy form)? ...
 bool track_lazy_capable(int window, int tree_sums, int n, int npairs);
 // ... and that form: level 0 of every pair is a compact image plane (TrackLazyArgs)
-int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a);
+// form: KLT_OPT_TRACK_LAZY_FORM (1: the template's and the first footprint's level-0 gradients in one fused phase)
+int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a, int form);
 // the gain / bias tracker (track_light_kernels.hip; klt_set_light_params mode 1): *path = 1 wave kernel, 2 quad kernel; a.order is not looked at
 int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
 // per-feature track quality (quality_kernels.hip): one klt_quality record per feature; returns -1 for an unsupported window

@@ -389,11 +389,10 @@ __device__ __forceinline__ void lazy_records(const float *plane, int nc, int nr,
         float *d = fl + LZ_P + s;
 #pragma unroll 1
         for (int j = 0; j < LZ_ROWS / 2; j++, p += 2 * LZ_PW, d += 16) {
-            double w[7];
-#pragma unroll
-            for (int i = 0; i < 7; i++) w[i] = (double)p[i];
-            d[0] = corr_regs<7, -1>(w + 3, kd);
-            d[LZ_DE] = corr_regs<7, 1>(w + 3, kg);
+            float dd, ee;
+            lazy_row_h<1>(p, kg, kd, &dd, &ee);
+            d[0] = dd;
+            d[LZ_DE] = ee;
         }
     }
     wave_lds_sync();
@@ -408,15 +407,15 @@ __device__ __forceinline__ void lazy_records(const float *plane, int nc, int nr,
             TapRegs<7> k;
             lazy_taps(k, u >= 2);
             const float *c = d + (u >> 1) * LZ_DE + 2 * (u & 1);
-            double w0[7], w1[7];
+            float c0[7], c1[7];
 #pragma unroll
             for (int j = 0; j < 7; j++) {
                 const float2 t = *reinterpret_cast<const float2 *>(c + 8 * j);
-                w0[j] = (double)t.x; w1[j] = (double)t.y;
+                c0[j] = t.x; c1[j] = t.y;
             }
             float a0, a1;
-            if (u < 2) { a0 = corr_regs<7, 1>(w0 + 3, k); a1 = corr_regs<7, 1>(w1 + 3, k); }
-            else { a0 = corr_regs<7, -1>(w0 + 3, k); a1 = corr_regs<7, -1>(w1 + 3, k); }
+            if (u < 2) { lazy_col_v<1, 1>(c0, k, &a0); lazy_col_v<1, 1>(c1, k, &a1); }
+            else { lazy_col_v<-1, 1>(c0, k, &a0); lazy_col_v<-1, 1>(c1, k, &a1); }
             // (o[] by a constant index: the loop is not unrolled, so each slot is set under its own test)
 #pragma unroll
             for (int e = 0; e < 4; e++)
@@ -431,6 +430,118 @@ __device__ __forceinline__ void lazy_records(const float *plane, int nc, int nr,
     if (need) { im = oi; gx = ox; gy = oy; }
 }
 
+// The fused entry phase of level 0 (KLT_OPT_TRACK_LAZY_FORM 1): the template's quads (corner (cx1, cy1) of plane1, for the features that
+// need1 them) and those of the first search footprint (corner (cx2, cy2) of plane2, need2) in ONE phase instead of two lazy_records calls
+// in a row -- the two patches depend on nothing of each other, so all 28 patch rows are requested before anything waits, and the wavefront
+// pays one memory round trip where the two calls pay four.
+//   loads   straight into LDS (buffer_load ... lds, 4 bytes per lane): no destination registers, one wait for both patches.  The
+//           destination of such a load is a wave-uniform base + lane x 4, so a patch row is one wave-instruction and lies as
+//           [feature][16 lanes]; lane s of a feature brings column s of the patch (14 and 15 repeat column 13) through the reflect map.
+//           A row is LZE_STRIDE floats from the next.
+//   H pass  one lane per patch row (lanes 14 and 15 of a feature idle), one round per patch: the lane reads its 14 samples once, widens each
+//           once and slides the window over the 8 footprint columns (lazy_row_h<8>), then writes 8 D and 8 E values over its own row.
+//   image   the 8 x 8 image values of a footprint are the middle of the patch rows 3 .. 10, which the H pass overwrites: the lanes of those
+//           rows set them aside ([patch][feature][8][8] behind the patches), and every lane reads its quad from there at the end -- held
+//           in registers from before the H pass they took the kernel past 128 VGPRs.
+//   V pass  one lane per footprint column of a patch, 8 + 8 lanes for the two patches, one round per filter: the lane reads its column of
+//           14 values once, widens each once and slides the window down the 8 footprint rows (lazy_col_v<., 8>) -- 14 conversions per
+//           column where a lane per pixel pair makes 14 per pair -- and writes the 8 results over the head of its column; every lane
+//           then reads the quads of its own pixels.  Each tap set is read once per pass.
+// Row stride 72 floats, a multiple of 4 (16-byte row reads) and 8 mod 32: the 16 lanes of a feature's V pass read 8 + 8 consecutive
+// floats 16 banks apart; the H pass's 16-byte row reads meet two rows per bank group (r and r + 8).
+// Every output is the corr_regs call of lazy_records on the same seven values in the same order: the same bits.
+constexpr int LZE_STRIDE = 72, LZE_PATCH = 2 * LZ_ROWS * LZE_STRIDE, LZE_FLOATS = LZE_PATCH + 2 * 4 * 64;
+
+__device__ __forceinline__ void lazy_records_entry(const float *plane1, const float *plane2, int nc, int nr, int cx1, int cy1, bool need1,
+                                                   int cx2, int cy2, bool need2, float *lds, int g, int s,
+                                                   f32x4 &t_im, f32x4 &t_gx, f32x4 &t_gy, f32x4 &s_im, f32x4 &s_gx, f32x4 &s_gy)
+{
+    typedef __attribute__((address_space(3))) float *lds_ptr;
+    // (the lane's place through an empty asm statement: the LDS addresses of the phase are made here, from it, not at the head of the
+    // kernel and held through every level -- there they cost the kernel a spilled register)
+    asm volatile("" : "+v"(s), "+v"(g));
+    // reflect_once without a comparison per case (28 rows: as selects under tests the compiler made branches of them): -1 - i for i < 0,
+    // then the smaller of a and its mirror image 2 n - 1 - a, which is a itself below n
+    auto reflect = [](int i, int n) { const int a = i ^ (i >> 31); return min(a, 2 * n - 1 - a); };
+    const int sc = s < 13 ? s : 13;
+    // (the destination through an empty asm statement: the 28 row addresses are made where they are used, not once per kernel and held)
+    lds_ptr dst = (lds_ptr)lds;
+    asm volatile("" : "+s"(dst));
+    const int xa = need1 ? cx1 - 3 : 0, ya = need1 ? cy1 - 3 : 0, xb = need2 ? cx2 - 3 : 0, yb = need2 ? cy2 - 3 : 0;
+    const plane_rsrc pa = plane_of(plane1), pb = plane_of(plane2);
+    if (__all(min(min(xa, ya), min(xb, yb)) >= 0 && max(xa, xb) + LZ_ROWS <= nc && max(ya, yb) + LZ_ROWS <= nr)) {
+        // no patch of the wavefront leaves its frame (every launch of two or more levels): row r is r rows below the first, and that
+        // distance rides in the load's scalar offset -- no vector instruction per row
+        const unsigned oa = 4u * (__umul24((unsigned)ya, (unsigned)nc) + (unsigned)(xa + sc));
+        const unsigned ob = 4u * (__umul24((unsigned)yb, (unsigned)nc) + (unsigned)(xb + sc));
+#pragma unroll
+        for (int r = 0; r < LZ_ROWS; r++) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pa, dst + r * LZE_STRIDE, 4, oa, 4 * r * nc, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pb, dst + (LZ_ROWS + r) * LZE_STRIDE, 4, ob, 4 * r * nc, 0, 0);
+        }
+    } else {
+        const unsigned ca = (unsigned)reflect(xa + sc, nc), cb = (unsigned)reflect(xb + sc, nc);
+#pragma unroll
+        for (int r = 0; r < LZ_ROWS; r++) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pa, dst + r * LZE_STRIDE, 4,
+                                                     4u * (__umul24((unsigned)reflect(ya + r, nr), (unsigned)nc) + ca), 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pb, dst + (LZ_ROWS + r) * LZE_STRIDE, 4,
+                                                     4u * (__umul24((unsigned)reflect(yb + r, nr), (unsigned)nc) + cb), 0, 0, 0);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    float *const fb = lds + 16 * g;                          // the feature's 16 floats of every row
+    const int qr = s >> 1, qh = s & 1;
+    float *const im = lds + LZE_PATCH + 64 * g;              // the feature's 8 x 8 image values, of the template (and + 256: the footprint)
+    if (s < LZ_ROWS) {
+        float4 *row = reinterpret_cast<float4 *>(fb + s * LZE_STRIDE);
+        float4 *keep = reinterpret_cast<float4 *>(im + 8 * (s - 3));
+        TapRegs<7> kg, kd;
+        lazy_taps(kg, false);
+        lazy_taps(kd, true);
+        // (both rounds unrolled: as a rolled loop the kernel kept 57 SGPRs spilled to VGPR lanes and read them back in here -- 5 us of the
+        // eight-pair launch -- and the single-pair kernel reserved scratch)
+#pragma unroll
+        for (int p = 0; p < 2; p++, row += LZ_ROWS * LZE_STRIDE / 4, keep += 64) {
+            const float4 v0 = row[0], v1 = row[1], v2 = row[2], v3 = row[3];
+            const float v[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
+            if (s >= 3 && s < 11) { keep[0] = make_float4(v[3], v[4], v[5], v[6]); keep[1] = make_float4(v[7], v[8], v[9], v[10]); }
+            float d[8], e[8];
+            lazy_row_h<8>(v, kg, kd, d, e);
+            row[0] = make_float4(d[0], d[1], d[2], d[3]); row[1] = make_float4(d[4], d[5], d[6], d[7]);
+            row[2] = make_float4(e[0], e[1], e[2], e[3]); row[3] = make_float4(e[4], e[5], e[6], e[7]);
+        }
+    }
+    wave_lds_sync();
+    {
+        // vertical pass: lane s takes footprint column s & 7 of patch s >> 3, first down D with the Gaussian taps (gradx), then down E with
+        // the derivative taps (grady): its 14 values read and widened once, the window slid down the 8 footprint rows (lazy_col_v<., 8>).
+        // The 8 results go over the first 8 rows of the column they came from, which no lane reads again.
+        float *col = fb + (s >> 3) * LZ_ROWS * LZE_STRIDE + (s & 7);
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++, col += 8) {
+            TapRegs<7> k;
+            lazy_taps(k, pl);
+            float c[LZ_ROWS], out[8];
+#pragma unroll
+            for (int j = 0; j < LZ_ROWS; j++) c[j] = col[j * LZE_STRIDE];
+            if (pl) lazy_col_v<-1, 8>(c, k, out);
+            else lazy_col_v<1, 8>(c, k, out);
+#pragma unroll
+            for (int j = 0; j < 8; j++) col[j * LZE_STRIDE] = out[j];
+        }
+    }
+    wave_lds_sync();
+    // every lane's quads: the image values set aside, gradx and grady where the vertical pass left them
+    const float *qd = fb + qr * LZE_STRIDE + 4 * qh;
+    const f32x4 i1 = *reinterpret_cast<const f32x4 *>(im + 4 * s), i2 = *reinterpret_cast<const f32x4 *>(im + 256 + 4 * s);
+    const f32x4 x1 = *reinterpret_cast<const f32x4 *>(qd), y1 = *reinterpret_cast<const f32x4 *>(qd + 8);
+    const f32x4 x2 = *reinterpret_cast<const f32x4 *>(qd + LZ_ROWS * LZE_STRIDE), y2 = *reinterpret_cast<const f32x4 *>(qd + LZ_ROWS * LZE_STRIDE + 8);
+    wave_lds_sync();
+    if (need1) { t_im = i1; t_gx = x1; t_gy = y1; }
+    if (need2) { s_im = i2; s_gx = x2; s_gy = y2; }
+}
+
 // the image values of pixels q .. q + 3 of a compact plane (the residue at a lazy level 0)
 __device__ __forceinline__ f32x4 load_plane_images(const float *plane, unsigned q)
 {
@@ -443,13 +554,14 @@ __device__ __forceinline__ f32x4 load_plane_images(const float *plane, unsigned 
 // batch flag, window, target, sum form -- which has to stay theirs alone; as a shared body under two kernel names the 15x15 kernel took
 // 48 instead of 40 bytes of scratch and four plain instantiations two more SGPRs)
 // (LAZY, the instantiations that make their level-0 gradients themselves, carry a mark of their own there for the same reason: WAVES =
-// occupancy target + LAZY_WAVES)
-constexpr int GUESS_WAVES = 8, LAZY_WAVES = 16;
+// occupancy target + LAZY_WAVES; and + ENTRY_WAVES on top for the ones whose level-0 entry is the fused phase, lazy_records_entry)
+constexpr int GUESS_WAVES = 8, LAZY_WAVES = 16, ENTRY_WAVES = 32;
 
 template <bool BATCH, int W, int WAVES = 1, bool TREE = false, bool FB = false, bool GUESS = false>
-__global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std::conditional_t<(WAVES >= LAZY_WAVES), TrackLazyArgs, TrackKernArgs<FB, GUESS>> a)
+__global__ __launch_bounds__(64, WAVES >= ENTRY_WAVES ? 4 : WAVES % GUESS_WAVES) void track_kernel_quad(std::conditional_t<(WAVES >= LAZY_WAVES), TrackLazyArgs, TrackKernArgs<FB, GUESS>> a)
 {
     constexpr bool LAZY = WAVES >= LAZY_WAVES;
+    constexpr bool ENTRY = WAVES >= ENTRY_WAVES;             // LAZY: the template and the first footprint of level 0 in one fused phase
     static_assert(GUESS == (WAVES >= GUESS_WAVES && !LAZY), "instantiations with a prior carry the mark in their occupancy target");
     static_assert(!LAZY || (W == 7 && !TREE && !FB && !GUESS), "level-0 gradients on demand: the plain 7x7 kernels only");
     static_assert(W == 7 || W == 15, "quad kernels exist for 7x7 and 15x15 windows");
@@ -537,7 +649,8 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std
             if constexpr (LAZY) {
                 if (r == 0) {
                     t_qi = f32x4{0.f, 0.f, 0.f, 0.f}; t_qgx = t_qi; t_qgy = t_qi;
-                    lazy_records(lv.i1, nc, nr, b1.ix - hw, b1.iy - hw, run, fl, s, t_qi, t_qgx, t_qgy);
+                    // (ENTRY: the first request_footprint below makes the template's quads together with the footprint's)
+                    if constexpr (!ENTRY) lazy_records(lv.i1, nc, nr, b1.ix - hw, b1.iy - hw, run, fl, s, t_qi, t_qgx, t_qgy);
                 } else {
                     load_records(lv.i1, q1, t_qi, t_qgx, t_qgy);
                 }
@@ -559,7 +672,8 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std
             // all the time at ~750 clocks each), so a request not made is time saved: 89.2 -> 86.6 us per eight-pair launch of cfg-2,
             // 131.6 -> 125.7 us at cfg-4.  7x7 only: the 15x15 kernel, at its occupancy target of five, pays for the held offset and the
             // conditional loads with 16 more bytes of scratch and goes from 38.9 to 42.4 us at cfg-3.
-            auto request_footprint = [&]() {
+            // (first: the request at the level's entry, a type that says so)
+            auto request_footprint = [&](auto first) {
                 const bool oob = (double)(x2 - (float)hw) < 0. || (float)nc - (x2 + (float)hw) < one_plus_eps ||
                                  (double)(y2 - (float)hw) < 0. || (float)nr - (y2 + (float)hw) < one_plus_eps;
                 if (iterating && oob) { status = KLT_OOB; iterating = false; }
@@ -569,7 +683,15 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std
                     if constexpr (LAZY) {
                         if (r == 0) {
                             const bool need = iterating && q != q_held;
-                            if (__any(need)) lazy_records(lv.i2, nc, nr, b2.ix - hw, b2.iy - hw, need, fl, s, s_qi, s_qgx, s_qgy);
+                            if constexpr (ENTRY && decltype(first)::value) {
+                                lazy_records_entry(lv.i1, lv.i2, nc, nr, b1.ix - hw, b1.iy - hw, run, b2.ix - hw, b2.iy - hw, need, lds, g, s,
+                                                   t_qi, t_qgx, t_qgy, s_qi, s_qgx, s_qgy);
+                                // (the weights made again behind the phase, from a position the compiler takes for another: only the
+                                // corner is held through it, six registers fewer)
+                                float xa = x2;
+                                asm volatile("" : "+v"(xa));
+                                b2 = make_bilinear(xa, y2);
+                            } else if (__any(need)) lazy_records(lv.i2, nc, nr, b2.ix - hw, b2.iy - hw, need, fl, s, s_qi, s_qgx, s_qgy);
                             if (need) q_held = q;
                         } else if (iterating && q != q_held) {
                             load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
@@ -585,7 +707,7 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std
                     load_records(lv.i2, q, s_qi, s_qgx, s_qgy);
                 }
             };
-            request_footprint();
+            request_footprint(std::true_type{});
 
             float t_i[4], t_gx[4], t_gy[4];
             sample_quad<QPR>(t_qi, b1, t_i);
@@ -643,7 +765,7 @@ __global__ __launch_bounds__(64, WAVES % GUESS_WAVES) void track_kernel_quad(std
                     it++;
                     iterating = (fabsf(dx) >= a.th || fabsf(dy) >= a.th) && it < a.max_iterations;
                 }
-                if (__any(iterating)) request_footprint();
+                if (__any(iterating)) request_footprint(std::false_type{});
             }
             if (run) { xout = x2; yout = y2; }
 
@@ -1013,7 +1135,7 @@ bool track_lazy_capable(int window, int tree_sums, int n, int npairs)
     return track_quad7_rule(window, n, npairs) && !tree_sums && n > 0 && npairs > 0;
 }
 
-int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a)
+int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a, int form)
 {
     const unsigned ny = a.pairs ? a.npairs : 1;
     if (!track_lazy_capable(a.window, a.tree_sums, a.n, (int)ny)) return -1;
@@ -1022,6 +1144,14 @@ int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a)
     const dim3 gq(a.order ? 8 * ((a.order_chunk + 3) / 4) : (a.n + 3) / 4, ny), block(64);
     // LDS: the four features' product arrays or, at level 0, their patches (the larger of the two)
     constexpr unsigned lds = (unsigned)(4 * sizeof(float) * (LZ_FLOATS > 5 * track_npad(49) ? LZ_FLOATS : 5 * track_npad(49)));
+    if (form) {
+        // ... or the two patches of the fused entry phase (which the patches of the Newton loop's recomputations fit under)
+        constexpr unsigned lds_entry = (unsigned)(sizeof(float) * LZE_FLOATS);
+        static_assert(lds_entry >= lds && lds_entry <= 10240, "sixteen wavefronts per CU");
+        if (a.pairs) klt_launch((track_kernel_quad<true, 7, 1 + LAZY_WAVES + ENTRY_WAVES>), gq, block, lds_entry, s, a);
+        else klt_launch((track_kernel_quad<false, 7, 1 + LAZY_WAVES + ENTRY_WAVES>), gq, block, lds_entry, s, a);
+        return 0;
+    }
     if (a.pairs) klt_launch((track_kernel_quad<true, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
     else klt_launch((track_kernel_quad<false, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
     return 0;

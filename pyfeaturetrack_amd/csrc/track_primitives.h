@@ -238,6 +238,36 @@ __device__ __forceinline__ void sample_quad(const f32x4 a, const Bilinear &b, fl
     }
 }
 
+// Level-0 gradients on demand (the LAZY kernels of track_kernels.hip), the arithmetic that does not depend on which lane does it: host
+// and device text, so that tests/lazy_grad_dump.cpp holds it against the oracle's gradient planes without a GPU.  Both are corr_regs on
+// seven widened values -- the FP64 expression and the operation order of the level-0 kernels without the centre-tap elision.
+// One patch row's horizontal pass: NOUT + 6 consecutive samples of the smoothed image p[0 ..] give NOUT values of each filter, centred on
+// p[3 ..]: derivative taps -> d, Gaussian taps -> e.  Every sample is widened once.
+template <int NOUT>
+__host__ __device__ __forceinline__ void lazy_row_h(const float *p, const TapRegs<7> &kg, const TapRegs<7> &kd, float *d, float *e)
+{
+    double w[NOUT + 6];
+#pragma unroll
+    for (int i = 0; i < NOUT + 6; i++) w[i] = (double)p[i];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++) {
+        d[j] = corr_regs<7, -1>(w + 3 + j, kd);
+        e[j] = corr_regs<7, 1>(w + 3 + j, kg);
+    }
+}
+
+// One footprint column's vertical pass down D (SYM = 1 with the Gaussian taps: gradx) or E (SYM = -1 with the derivative taps: grady):
+// the column's NOUT + 6 consecutive values c[0 ..] give the NOUT pixels whose rows are centred on c[3 ..].  Every value is widened once.
+template <int SYM, int NOUT>
+__host__ __device__ __forceinline__ void lazy_col_v(const float *c, const TapRegs<7> &k, float *out)
+{
+    double w[NOUT + 6];
+#pragma unroll
+    for (int j = 0; j < NOUT + 6; j++) w[j] = (double)c[j];
+#pragma unroll
+    for (int j = 0; j < NOUT; j++) out[j] = corr_regs<7, SYM>(w + 3 + j, k);
+}
+
 // The window classes of the one-feature-per-wavefront kernels (host): f(MAXK, WCT) as integral constants -- MAXK window samples per lane;
 // WCT the window size where it is known at compile time (7 and 15), 0 for any other window of n = window * window <= 1024 samples.
 template <class F>
