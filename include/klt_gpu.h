@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -54,7 +54,8 @@ enum { KLT_TRACKED = 0, KLT_NOT_FOUND = -1, KLT_SMALL_DET = -2, KLT_MAX_ITERATIO
        KLT_OOB = -4, KLT_LARGE_RESIDUE = -5,
        KLT_FB_INCONSISTENT = -6, /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */
        KLT_MODEL_OUTLIER = -7,   /* not in the reference: off the frame pair's dominant affine motion (klt_motion_check_async); lost likewise */
-       KLT_EPIPOLAR_OUTLIER = -8 /* not in the reference: off the frame pair's fundamental matrix (klt_epipolar_check_async); lost likewise */ };
+       KLT_EPIPOLAR_OUTLIER = -8, /* not in the reference: off the frame pair's fundamental matrix (klt_epipolar_check_async); lost likewise */
+       KLT_HOMOGRAPHY_OUTLIER = -9 /* not in the reference: off the frame pair's homography (klt_homography_check_async); lost likewise */ };
 
 /* selection modes, selectGoodFeatures.py:11-13 */
 enum { KLT_SELECTING_ALL = 1, KLT_REPLACING_SOME = 2 };
@@ -610,6 +611,73 @@ int klt_epipolar_check(klt_ctx *ctx, const klt_feat *in, klt_feat *out, klt_epip
 int klt_epipolar_matrix(const klt_epipolar_model *model, double F[9]);
 /* 0: no epipolar-check launch yet; 1: the last one ran as three launches on one pair, 2: on a table of pairs.  A diagnostic. */
 int klt_epipolar_check_path(klt_ctx *ctx);
+
+/* ---- homography check (not in the reference) -------------------------------------------------------------------- */
+/* The third consensus check, for a camera that ROTATES (pan / tilt, hand-held) and for any camera that looks at a PLANE (aerial nadir
+ * view, road surface, document, wall): the static scene then moves by a homography q ~ H p, whose perspective part an affine map cannot
+ * follow and for which the fundamental matrix is not unique.  A seeded consensus search over four-point hypotheses finds the pair's
+ * homography, one least-squares refit, and every tracked feature off the result becomes (-1, -1, KLT_HOMOGRAPHY_OUTLIER, aux).  It reads
+ * two feature lists and nothing else, and runs stream-ordered behind whatever wrote them.  Limits: exactly collinear correspondences
+ * fit a family of homographies: the check then flags less, never more; candidates that lie NEARLY on one line with noise on them make
+ * every four-point hypothesis ill-conditioned, and good tracks are flagged: the check wants candidates spread
+ * over the frame in both directions.  A scene with parallax (a camera that translates through depth) is NOT a homography: the check
+ * then flags most of the static tracks, and the epipolar check is the tool.
+ *
+ * THE RULE.  Inputs: lists `in` and `out` of n records and klt_homography_params.  All arithmetic is FP64, one rounding per operation,
+ * nothing contracted, in exactly the order written here; only +, -, * and comparisons: no division, no square root.
+ * Magnitudes: working coordinates lie in [-1, 1] (step 1), so every entry of a row is at most 1 in magnitude; a term of the 24 sums is at
+ * most 2 (q.x*q.x + q.y*q.y) and the sums stay below 2 n < 2^26.  null9's bounds are those of the epipolar rule, unchanged: the remaining
+ * block is rescaled in every step, |x| < 9^8 < 2^26 and h never is all zero.  u, v and w of the inlier test are then below 3 * 2^26 < 2^28,
+ * w*q.x likewise, rx and ry below 2^29 and every square and their sum below 2^60.  Nothing comes near 2^1023 or 2^-1022.
+ *  1 candidates  exactly step 1 of the epipolar rule: the same conditions, list order, cx = ncols / 2, cy = nrows / 2, s = 2^-k with k the
+ *                smallest integer with 2 * (1 << k) >= max(ncols, nrows); p = (((double)in.x - cx) * s, ((double)in.y - cy) * s), q
+ *                likewise from out.  m < min_inliers: no model (valid = 0), out untouched.
+ *  2 samples     hypothesis h takes candidates r_j = mulhi32(mix(seed ^ mix(4*h + j)), m), j = 0 .. 3 (mix, mulhi32: the motion-model rule).
+ *  3 rows        correspondence j gives rows 2j and 2j+1 of the 8x9 matrix, the coefficients of h[0 .. 8] (H row-major):
+ *                  (p.x, p.y, 1.0, 0.0, 0.0, 0.0, -(q.x*p.x), -(q.x*p.y), -q.x)
+ *                  (0.0, 0.0, 0.0, p.x, p.y, 1.0, -(q.y*p.x), -(q.y*p.y), -q.y)
+ *                one product, then its negation (exact); the zeros are +0.0.
+ *  4 null9(A)    step 4 of the epipolar rule, bit for bit.  Repeated picks leave exactly zero rows: null9 fails, no special case.
+ *  5 hypothesis  h = null9 of the eight rows of its picks; null9 fails: score -1.  With
+ *                  u = (h0*p.x + h1*p.y) + h2    v = (h3*p.x + h4*p.y) + h5    w = (h6*p.x + h7*p.y) + h8
+ *                  rx = u - w*q.x                ry = v - w*q.y
+ *                candidate k is an inlier of h iff rx*rx + ry*ry <= t2 * (w*w) (NaN fails), the forward transfer error
+ *                cross-multiplied, with t2 = ts*ts, ts = (double)max_error * s.  The score is the number of inliers; the best
+ *                hypothesis has the largest score, ties go to the smallest h.  Best score < min_inliers: valid = 0, out untouched.
+ *  6 refit, once least squares on the same rows over the inliers of the best hypothesis.  With e = (p.x, p.y, 1.0) the normal matrix is
+ *                M = [[A, 0, -Bx], [0, A, -By], [-Bx, -By, C]], 3x3 symmetric blocks, 24 sums over (i, j), i <= j:
+ *                  A[i][j] = SUM ee    Bx[i][j] = SUM q.x*ee    By[i][j] = SUM q.y*ee    C[i][j] = SUM qq*ee
+ *                with ee = e_i*e_j (one product; a factor 1.0 is exact) and qq = q.x*q.x + q.y*q.y (two products, one sum).  The term
+ *                of candidate k joins partial k mod 64 in increasing k (non-inliers are skipped), the 64 partials fold by
+ *                p[l] += p[l + w], l < w, w = 32 .. 1.  The blocks are mirrored, -Bx and -By are the negated sums, the structural zeros
+ *                are +0.0.  g = the index of the largest |h_i| of the hypothesis, ties to the smallest.  h' = null9(M without row g).
+ *                null9 succeeds: the model is h', valid = 1; otherwise the hypothesis is kept, valid = 2.  The inlier test is evaluated
+ *                once more under the final model; there is no iteration.
+ *  7 outputs     every candidate that is not an inlier of the final model becomes (-1, -1, KLT_HOMOGRAPHY_OUTLIER, out.aux) in `out`;
+ *                every other byte of `out` stays.  One klt_homography_model goes to a feature buffer of six klt_feat records: valid = 0:
+ *                h, n_inliers and hypothesis_inliers are 0, hypothesis is -1; otherwise the final model (in working coordinates), its
+ *                inlier count, the best hypothesis and its score.  n_candidates = m; pad = ncols | nrows << 16 in every record. */
+typedef struct { int32_t mode; int32_t ncols, nrows; int32_t hypotheses; uint32_t seed; int32_t min_inliers; float max_error; } klt_homography_params;
+typedef struct { double h[9]; int32_t valid, n_candidates, n_inliers, hypothesis, hypothesis_inliers, pad; } klt_homography_model;
+/* mode: 0 = off (the default), 1 = on; anything else is KLT_ERR_ARG, and so are hypotheses outside 1 .. 65536, min_inliers < 4,
+ * max_error negative or NaN, and (mode 1) ncols / nrows outside 1 .. 65535.  Defaults: 256 hypotheses, seed 0, min_inliers 8,
+ * max_error 1.0 px.  Not in the reference; DESIGN.md section 9i. */
+int klt_set_homography_params(klt_ctx *ctx, const klt_homography_params *p);
+/* The check on two resident lists, with the conventions and refusals of klt_epipolar_check_async: fb_out is rewritten in place, fb_model
+ * (allocated if needed, six records) takes the klt_homography_model.  The scratch belongs to the context and to this check alone: all
+ * three consensus checks may be on in one context. */
+int klt_homography_check_async(klt_ctx *ctx, int fb_in, int fb_out, int fb_model, int n);
+/* npairs pairs in the same launches; every fb_model distinct from every list and from each other, every fb_out from every other list. */
+int klt_homography_check_batch_async(klt_ctx *ctx, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n);
+/* synchronous, host arrays: out is rewritten, *model filled, *n_outliers (may be NULL) = the records that became KLT_HOMOGRAPHY_OUTLIER. */
+int klt_homography_check(klt_ctx *ctx, const klt_feat *in, klt_feat *out, klt_homography_model *model, int n, int *n_outliers);
+/* host only: H (row-major) in UNCENTRED pixel coordinates, q ~ H p for p in frame 1 and q in frame 2: T^-1 h T with
+ * T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]] (T^-1 holds 2^k: exact), scaled to unit Frobenius norm, with the sign that makes the
+ * third coordinate positive at the image centre (working h[8] > 0).  KLT_ERR_ARG for a null pointer, KLT_ERR_STATE for a record with
+ * valid == 0 (or one whose norm is zero or not finite). */
+int klt_homography_matrix(const klt_homography_model *model, double H[9]);
+/* 0: no homography-check launch yet; 1: the last one ran as three launches on one pair, 2: on a table of pairs.  A diagnostic. */
+int klt_homography_check_path(klt_ctx *ctx);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

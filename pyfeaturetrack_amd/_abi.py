@@ -47,6 +47,16 @@ class KltEpipolarModel(C.Structure):
                 ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
 
 
+class KltHomographyParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ncols", C.c_int32), ("nrows", C.c_int32), ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+                ("min_inliers", C.c_int32), ("max_error", C.c_float)]
+
+
+class KltHomographyModel(C.Structure):
+    _fields_ = [("h", C.c_double * 9), ("valid", C.c_int32), ("n_candidates", C.c_int32), ("n_inliers", C.c_int32),
+                ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
+
+
 class KltParams(C.Structure):
     _fields_ = [
         ("mindist", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
@@ -186,6 +196,12 @@ SYMBOLS = {
     "klt_epipolar_check": (_I, [_P, _P, _P, C.POINTER(KltEpipolarModel), _I, _PI]),
     "klt_epipolar_matrix": (_I, [C.POINTER(KltEpipolarModel), C.POINTER(C.c_double)]),
     "klt_epipolar_check_path": (_I, [_P]),
+    "klt_set_homography_params": (_I, [_P, C.POINTER(KltHomographyParams)]),
+    "klt_homography_check_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_homography_check_batch_async": (_I, [_P, _PI, _PI, _PI, _I, _I]),
+    "klt_homography_check": (_I, [_P, _P, _P, C.POINTER(KltHomographyModel), _I, _PI]),
+    "klt_homography_matrix": (_I, [C.POINTER(KltHomographyModel), C.POINTER(C.c_double)]),
+    "klt_homography_check_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltEpipolarModel, KltEpipolarParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
+                   KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
@@ -33,6 +33,10 @@ assert MODEL_DTYPE.itemsize == C.sizeof(KltMotionModel) == 5 * FEAT_DTYPE.itemsi
 EPIPOLAR_DTYPE = np.dtype([("f", np.float64, (9,)), ("valid", np.int32), ("n_candidates", np.int32), ("n_inliers", np.int32),
                            ("hypothesis", np.int32), ("hypothesis_inliers", np.int32), ("pad", np.int32)])
 assert EPIPOLAR_DTYPE.itemsize == C.sizeof(KltEpipolarModel) == 6 * FEAT_DTYPE.itemsize
+# a homography model (klt_homography_model; klt_homography_check*): likewise one record in a feature buffer of six klt_feat records
+HOMOGRAPHY_DTYPE = np.dtype([("h", np.float64, (9,)), ("valid", np.int32), ("n_candidates", np.int32), ("n_inliers", np.int32),
+                             ("hypothesis", np.int32), ("hypothesis_inliers", np.int32), ("pad", np.int32)])
+assert HOMOGRAPHY_DTYPE.itemsize == C.sizeof(KltHomographyModel) == 6 * FEAT_DTYPE.itemsize
 
 SELECTING_ALL = 1
 REPLACING_SOME = 2
@@ -47,7 +51,8 @@ _FB_API_BACK = 65528                 # backward records of a forward-backward ca
 _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
 _FB_API_MODEL = 53999                # the model record of a KLTTrackFeatures call with tc.motionModelCheck (48000 .. 53998: KLTTrackSequence's model rows)
 _FB_API_EPIPOLAR = 47999             # the model record of a KLTTrackFeatures call with tc.epipolarCheck (42000 .. 47998: KLTTrackSequence's epipolar rows)
-_FB_API_QUALITY = 59999              # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
+_FB_API_HOMOGRAPHY = 41999           # the model record of a KLTTrackFeatures call with tc.homographyCheck (36000 .. 41998: KLTTrackSequence's homography rows)
+_FB_API_QUALITY = 59999             # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
 
 
 def _dp(a):
@@ -856,6 +861,49 @@ class Context:
         """the EPIPOLAR_DTYPE record of feature buffer `fb` (what an epipolar_check*_async launch wrote there)"""
         return self.featbuf_download(fb, 6).view(EPIPOLAR_DTYPE)[0]
 
+    # ------------------------------------------------ homography check (klt_set_homography_params, klt_homography_check*)
+    def set_homography_params(self, hp=None, **kw):
+        """klt_set_homography_params: `hp` a KltHomographyParams, or its fields by name (mode, ncols, nrows, hypotheses, seed, min_inliers,
+        max_error; defaults 1, -, -, 256, 0, 8, 1.0)"""
+        if hp is None:
+            d = dict(mode=1, hypotheses=256, seed=0, min_inliers=8, max_error=1.0)
+            d.update(kw)
+            hp = KltHomographyParams(**d)
+        key = bytes(hp)
+        if key != getattr(self, "_homography_key", None):
+            self._homography_key = None
+            self._check(self._lib.klt_set_homography_params(self._h, C.byref(hp)))
+            self._homography_key = key
+
+    def homography_check(self, fl_in, fl_out):
+        """klt_homography_check: (out, model, n_outliers) -- fl_out with every tracked record off the pair's homography turned into
+        (-1, -1, KLT_HOMOGRAPHY_OUTLIER, aux), the HOMOGRAPHY_DTYPE record, and how many records that were"""
+        fl_in = np.ascontiguousarray(fl_in, FEAT_DTYPE)
+        out = np.array(fl_out, FEAT_DTYPE, order="C")
+        if len(fl_in) != len(out):
+            raise ValueError("the two lists have %d and %d records" % (len(fl_in), len(out)))
+        model = np.zeros(1, HOMOGRAPHY_DTYPE)
+        cnt = C.c_int(0)
+        self._check(self._lib.klt_homography_check(self._h, fl_in.ctypes.data, out.ctypes.data,
+                                                   C.cast(model.ctypes.data, C.POINTER(KltHomographyModel)), len(out), C.byref(cnt)))
+        return out, model[0], cnt.value
+
+    def homography_check_async(self, fb_in, fb_out, fb_model, n):
+        self._check(self._lib.klt_homography_check_async(self._h, fb_in, fb_out, fb_model, n))
+
+    def homography_check_batch_async(self, pairs, n):
+        """pairs: [(fb_in, fb_out, fb_model), ...] -- the check's launches once for all of them."""
+        cols = _columns(pairs, 3)
+        self._check(self._lib.klt_homography_check_batch_async(self._h, cols[0], cols[1], cols[2], len(pairs), n))
+
+    def homography_check_path(self):
+        """klt_homography_check_path: 0 no homography-check launch yet, 1 the last one ran on one pair, 2 on a table of pairs (a diagnostic)"""
+        return self._check(self._lib.klt_homography_check_path(self._h))
+
+    def homography_download(self, fb):
+        """the HOMOGRAPHY_DTYPE record of feature buffer `fb` (what a homography_check*_async launch wrote there)"""
+        return self.featbuf_download(fb, 6).view(HOMOGRAPHY_DTYPE)[0]
+
     def track_stats_reset(self):
         self._check(self._lib.klt_track_stats_reset(self._h))
 
@@ -1029,6 +1077,18 @@ def epipolar_matrix(model):
     return F.reshape(3, 3)
 
 
+def homography_matrix(model):
+    """klt_homography_matrix: the 3x3 homography H of a HOMOGRAPHY_DTYPE record in uncentred pixel coordinates, unit Frobenius norm,
+    q ~ H p for p in frame 1 and q in frame 2, third coordinate positive at the image centre; None for a record without a model"""
+    rec = np.zeros(1, HOMOGRAPHY_DTYPE)
+    rec[0] = model
+    H = np.zeros(9, np.float64)
+    rc = load_library().klt_homography_matrix(C.cast(rec.ctypes.data, C.POINTER(KltHomographyModel)), H.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        return None
+    return H.reshape(3, 3)
+
+
 def model_summary(model):
     """what KLTTrackFeatures leaves in tc.model_last: a dict with A (2x2), t, valid, candidates, inliers, hypothesis"""
     A, t = model_affine(model)
@@ -1036,5 +1096,5 @@ def model_summary(model):
             "hypothesis": int(model["hypothesis"])}
 
 
-__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "MODEL_DTYPE", "model_affine", "model_summary", "EPIPOLAR_DTYPE", "epipolar_matrix", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
+__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "MODEL_DTYPE", "model_affine", "model_summary", "EPIPOLAR_DTYPE", "epipolar_matrix", "HOMOGRAPHY_DTYPE", "homography_matrix", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
            "KLT_MAX_LEVELS", "KltParams"]

@@ -11,15 +11,6 @@ static ConsensusCheck epipolar_check(klt_ctx *c)
                           "the epipolar check is off (klt_set_epipolar_params mode 0)"};
 }
 
-// s = 2^-k, k the smallest integer with 2 * (1 << k) >= max(ncols, nrows)
-static double working_scale(int ncols, int nrows)
-{
-    const int big = ncols > nrows ? ncols : nrows;
-    double s = 1.0;
-    for (int k = 0; 2 * (1 << k) < big; k++) s *= 0.5;
-    return s;
-}
-
 static void fill_epipolar_args(const klt_ctx *c, int n, EpipolarArgs &e)
 {
     const klt_epipolar_params &p = c->epip;

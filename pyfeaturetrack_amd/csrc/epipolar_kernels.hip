@@ -33,22 +33,6 @@ constexpr int SCORE_WAVES = 4;
 constexpr int DECIDE_THREADS = 512;
 constexpr int SCORE_AHEAD = 4, SUM_AHEAD = 8, FINAL_AHEAD = 4;      // candidates a lane loads before it uses the first
 
-struct F9 { double f[9]; };                                          // (indexed by compile-time constants only)
-
-__device__ __forceinline__ Cand working(Cand c, double s)
-{
-    c.px = c.px * s; c.py = c.py * s; c.qx = c.qx * s; c.qy = c.qy * s;
-    return c;
-}
-
-template <int U>
-__device__ __forceinline__ void load_working(const double *cand, int k0, int stride, int m, double s, Cand (&c)[U], bool (&ok)[U])
-{
-    load_ahead<U>(cand, k0, stride, m, c, ok);
-#pragma unroll
-    for (int j = 0; j < U; j++) c[j] = working(c[j], s);
-}
-
 // step 5 of the rule: the Sampson distance, cross-multiplied
 __device__ __forceinline__ bool is_inlier(const F9 &F, double t2, const Cand &c)
 {
@@ -73,88 +57,6 @@ __device__ __forceinline__ double row_entry(const Cand &c, int col)
     const bool x = col == 0 || col == 3 || col == 6, y = col == 1 || col == 4 || col == 7;
     const double r = x ? c.px : (y ? c.py : 1.0);
     return l * r;
-}
-
-// step 4 of the rule on a matrix spread over the wavefront: `a` is A[lane >> 3][lane & 7], `a8` is A[lane >> 3][8].  All 64 lanes call
-// it together; the result and f are the same in every lane.
-__device__ __forceinline__ bool null9(double a, double a8, int lane, F9 &F)
-{
-    const int r = lane >> 3, c = lane & 7;
-    int perm = lane;                                         // lanes 0 .. 8: the column of the input that stands at position `lane`
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const bool rows = r >= k;
-        // the pivot: largest bits of |v|, then the smallest 9 row + column
-        unsigned long long kb = 0;
-        unsigned ki = 0;
-        if (rows && c >= k) { kb = (unsigned long long)__double_as_longlong(fabs(a)); ki = 127u - (unsigned)(r * 9 + c); }
-        if (rows) {
-            const unsigned long long b8 = (unsigned long long)__double_as_longlong(fabs(a8));
-            const unsigned i8 = 127u - (unsigned)(r * 9 + 8);
-            if (b8 > kb || (b8 == kb && i8 > ki)) { kb = b8; ki = i8; }
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const unsigned lo = __shfl_xor((unsigned)kb, o), hi = __shfl_xor((unsigned)(kb >> 32), o), oi = __shfl_xor(ki, o);
-            const unsigned long long ob = (unsigned long long)hi << 32 | lo;
-            if (ob > kb || (ob == kb && oi > ki)) { kb = ob; ki = oi; }
-        }
-        const int ef = __builtin_amdgcn_readfirstlane((int)(kb >> 52));
-        if (ef == 0 || ef == 0x7ff) return false;            // zero, subnormal or not finite (uniform: every lane holds the same key)
-        const int at = __builtin_amdgcn_readfirstlane((int)(127u - ki));
-        const int pr = at / 9, pc = at - 9 * pr;             // (a constant divisor: a multiplication)
-        // rows k and pr, then columns k and pc, change places
-        const int sr = r == k ? pr : (r == pr ? k : r);
-        a = __shfl(a, sr * 8 + c);
-        a8 = __shfl(a8, sr * 8 + c);
-        if (pc < 8) {
-            const int sc = c == k ? pc : (c == pc ? k : c);
-            a = __shfl(a, r * 8 + sc);
-        } else {
-            const double was = __shfl(a, r * 8 + k);
-            a = c == k ? a8 : a;
-            a8 = was;
-        }
-        perm = __shfl(perm, lane == k ? pc : (lane == pc ? k : lane));
-        // the remaining block times a power of two: the pivot P lands in 0.5 <= |P| < 1
-        const double scale = __longlong_as_double((long long)(2045 - ef) << 52);
-        if (rows && c >= k) a = a * scale;
-        if (rows) a8 = a8 * scale;
-        // A[i][j] = A[i][j] * P - A[k][j] * A[i][k]
-        const double P = __shfl(a, 9 * k), rk = __shfl(a, k * 8 + c), rk8 = __shfl(a8, k * 8), ci = __shfl(a, r * 8 + k);
-        if (r > k && c > k) {
-            const double t1 = a * P, t2 = rk * ci;
-            a = t1 - t2;
-        }
-        if (r > k) {
-            const double t1 = a8 * P, t2 = rk8 * ci;
-            a8 = t1 - t2;
-        }
-    }
-    // back-substitution: lane j <= 8 holds x[j]
-    double x = lane == 8 ? 1.0 : 0.0;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        const double aj = __shfl(a, i * 8 + c), a88 = __shfl(a8, i * 8);
-        const double aij = lane == 8 ? a88 : aj;             // lane j: A[i][j]
-        const double term = aij * x;
-        double sum = __shfl(term, i + 1);
-#pragma unroll
-        for (int j = i + 2; j <= 8; j++) {
-            const double tj = __shfl(term, j);
-            sum = sum + tj;
-        }
-        const double aii = __shfl(a, 9 * i);
-        if (lane > i) x = x * aii;
-        if (lane == i) x = -sum;
-    }
-    // f[perm[c]] = x[c]
-#pragma unroll
-    for (int t = 0; t < 9; t++) {
-        const unsigned long long who = __ballot(lane < 9 && perm == t);      // exactly one lane: perm is a permutation of 0 .. 8
-        F.f[t] = __shfl(x, __ffsll((long long)who) - 1);
-    }
-    return true;
 }
 
 // steps 2 to 4 for hypothesis h: the eight rows of its picks, one entry per lane, and their null vector

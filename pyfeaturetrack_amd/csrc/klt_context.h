@@ -11,6 +11,7 @@
 //   api_quality.hip   per-feature track quality (single pair, batched)
 //   api_model.hip     motion-model check (single pair, batched), the model record as an affine map
 //   api_epipolar.hip  epipolar check (single pair, batched), the model record as a fundamental matrix in pixels
+//   api_homography.hip homography check (single pair, batched), the model record as a homography in pixels
 //   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
@@ -304,6 +305,12 @@ struct klt_ctx {
     unsigned char *epi_scratch = nullptr;
     size_t epi_scratch_cap = 0;
     SentTable<ModelPair> epi_table;                                // klt_epipolar_check_batch_async
+    // homography check (klt_set_homography_params, klt_homography_check*): likewise, scratch and pair table of its own
+    klt_homography_params homp{0, 0, 0, 256, 0u, 8, 1.0f};
+    int hom_path = 0;                                              // klt_homography_check_path
+    unsigned char *hom_scratch = nullptr;
+    size_t hom_scratch_cap = 0;
+    SentTable<ModelPair> hom_table;                                // klt_homography_check_batch_async
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -476,8 +483,8 @@ inline int own_records(klt_ctx *c, int fb, std::initializer_list<int> others, co
 }
 
 // ---- api_model.hip
-// What the two consensus checks over feature lists (motion model: api_model.hip, epipolar: api_epipolar.hip) differ in before their
-// launches: whose scratch, how many hypotheses' scores, how many feature records the model record takes, whether the check is on and
+// What the consensus checks over feature lists (motion model: api_model.hip, epipolar: api_epipolar.hip, homography:
+// api_homography.hip) differ in before their launches: whose scratch, how many hypotheses' scores, how many feature records the model record takes, whether the check is on and
 // what to say when it is not.  consensus_prepare* hold the one copy of the refusals, of the scratch layout and of the pair descriptors.
 struct ConsensusCheck {
     unsigned char *&scratch;
@@ -489,6 +496,14 @@ struct ConsensusCheck {
 int consensus_prepare(klt_ctx *c, ConsensusCheck k, int fb_in, int fb_out, int fb_model, int n, ModelPair *one, int *go);
 int consensus_prepare_batch(klt_ctx *c, ConsensusCheck k, const int *fb_in, const int *fb_out, const int *fb_model, int npairs, int n,
                             std::vector<ModelPair> *table, int *go);
+// the working scale of the epipolar and the homography rule: s = 2^-k, k the smallest integer with 2 * (1 << k) >= max(ncols, nrows)
+inline double working_scale(int ncols, int nrows)
+{
+    const int big = ncols > nrows ? ncols : nrows;
+    double s = 1.0;
+    for (int k = 0; 2 * (1 << k) < big; k++) s *= 0.5;
+    return s;
+}
 
 // ---- api_frames.hip
 // The kernels address a plane with 32-bit BYTE offsets into a buffer descriptor of 2 GB (raw buffer operations, klt_internal.h), and the

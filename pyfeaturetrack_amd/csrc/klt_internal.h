@@ -144,6 +144,9 @@ struct EpipolarArgs {
     ModelArgs m;
     double s;                           // 2^-k, k the smallest integer with 2 * (1 << k) >= max(ncols, nrows)
 };
+// the homography check (klt_homography_check_async) takes the same arguments: ModelPair::model then points at a
+// klt_homography_model
+static_assert(sizeof(klt_homography_model) == 6 * sizeof(klt_feat), "a homography model record lives in a feature buffer of six records");
 
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
@@ -440,6 +443,9 @@ void launch_model_decide(hipStream_t s, const ModelArgs &a);
 // the epipolar check (epipolar_kernels.hip) behind launch_model_gather: one score per hypothesis, the decision
 void launch_epipolar_score(hipStream_t s, const EpipolarArgs &a);
 void launch_epipolar_decide(hipStream_t s, const EpipolarArgs &a);
+// the homography check (homography_kernels.hip) behind launch_model_gather, likewise
+void launch_homography_score(hipStream_t s, const EpipolarArgs &a);
+void launch_homography_decide(hipStream_t s, const EpipolarArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

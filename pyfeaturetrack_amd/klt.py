@@ -39,6 +39,7 @@ class kltState:
     KLT_FB_INCONSISTENT = -6          # not in the reference: rejected by the forward-backward check (tc.forwardBackwardCheck)
     KLT_MODEL_OUTLIER = -7            # not in the reference: off the frame pair's dominant affine motion (tc.motionModelCheck)
     KLT_EPIPOLAR_OUTLIER = -8         # not in the reference: off the frame pair's fundamental matrix (tc.epipolarCheck)
+    KLT_HOMOGRAPHY_OUTLIER = -9       # not in the reference: off the frame pair's homography (tc.homographyCheck)
 
 
 def _pyramidSigma(tc):
@@ -116,6 +117,15 @@ class KLT_TrackingContext:
         self.epipolar_hypotheses = 512
         self.epipolar_seed = 0
         self.epipolar_min_inliers = 16
+        # homography check (not in the reference): False, or True -- the third consensus check, for a camera that rotates and for any
+        # camera that looks at a plane: the consensus search finds the pair's homography and every tracked feature further than
+        # homography_max_error px from where it sends the feature is lost (KLT_HOMOGRAPHY_OUTLIER); KLTTrackFeatures leaves
+        # tc.homography_last, KLTTrackSequence's table carries ft.homography.  Not together with the other two.
+        self.homographyCheck = False
+        self.homography_max_error = 1.0
+        self.homography_hypotheses = 256
+        self.homography_seed = 0
+        self.homography_min_inliers = 8
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -729,6 +739,7 @@ class KLT_FeatureTable:
     quality = None            # KLTTrackSequence with tc.trackQuality: [nFrames, nFeatures] records (residue, ncc, min_eig, val)
     models = None             # KLTTrackSequence with tc.motionModelCheck: [nFrames] backend.MODEL_DTYPE records, row 0 all zero
     epipolar = None           # KLTTrackSequence with tc.epipolarCheck: [nFrames] backend.EPIPOLAR_DTYPE records, row 0 all zero
+    homography = None         # KLTTrackSequence with tc.homographyCheck: [nFrames] backend.HOMOGRAPHY_DTYPE records, row 0 all zero
 
     def feature(self, feat, frame):
         return _feature_of(self.rec[frame, feat])
@@ -757,6 +768,10 @@ def KLTPrintTrackingContext(tc):
     if getattr(tc, "epipolarCheck", False):          # (not in the reference: printed only when the check is on)
         print("")
         for name in ("epipolarCheck", "epipolar_max_error", "epipolar_hypotheses", "epipolar_seed", "epipolar_min_inliers"):
+            print("\t{0} = {1}".format(name, getattr(tc, name, None)))
+    if getattr(tc, "homographyCheck", False):        # (likewise)
+        print("")
+        for name in ("homographyCheck", "homography_max_error", "homography_hypotheses", "homography_seed", "homography_min_inliers"):
             print("\t{0} = {1}".format(name, getattr(tc, name, None)))
     print("\n")
 

@@ -1,7 +1,7 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import numpy as np
 
-from ._abi import KltAffineParams, KltEpipolarParams, KltFbParams, KltLightParams, KltModelParams, KltParams
+from ._abi import KltAffineParams, KltEpipolarParams, KltFbParams, KltHomographyParams, KltLightParams, KltModelParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -170,6 +170,43 @@ def epipolar_params_from_tc(tc, ncols=None, nrows=None):
         raise ValueError("the epipolar check takes frames of 1 .. 65535 columns and rows")
     ep.hypotheses, ep.seed, ep.min_inliers, ep.max_error = hyp, seed, inl, err
     return ep
+
+
+def homography_params_from_tc(tc, ncols=None, nrows=None):
+    """tc.homographyCheck / tc.homography_max_error / tc.homography_hypotheses / tc.homography_seed / tc.homography_min_inliers ->
+    klt_homography_params for a frame of ncols x nrows: False (the default) packs mode 0, True mode 1.  All are read with defaults: a
+    tracking context made elsewhere has none of them.  ValueError -- before any device work -- for a value that is no bool, for the check
+    together with tc.motionModelCheck or tc.epipolarCheck (one consensus check per pair) or with tc.affineConsistencyCheck >= 0 (what
+    those two refuse), and for parameters klt_set_homography_params would refuse."""
+    on = getattr(tc, "homographyCheck", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("tc.homographyCheck must be True or False (got {0!r})".format(on))
+    hp = KltHomographyParams()
+    hp.mode = 1 if on else 0
+    hp.ncols, hp.nrows = int(ncols or 0), int(nrows or 0)
+    if not hp.mode:
+        hp.hypotheses, hp.seed, hp.min_inliers, hp.max_error = 256, 0, 8, 1.0
+        return hp
+    if getattr(tc, "motionModelCheck", None) is not None:
+        raise ValueError("homographyCheck and motionModelCheck cannot both be switched on")
+    if getattr(tc, "epipolarCheck", False):
+        raise ValueError("homographyCheck and epipolarCheck cannot both be switched on")
+    if getattr(tc, "affineConsistencyCheck", -1) >= 0:
+        raise ValueError("homographyCheck and affineConsistencyCheck cannot both be switched on")
+    hyp, seed = int(getattr(tc, "homography_hypotheses", 256)), int(getattr(tc, "homography_seed", 0))
+    inl, err = int(getattr(tc, "homography_min_inliers", 8)), float(getattr(tc, "homography_max_error", 1.0))
+    if not 1 <= hyp <= 65536:
+        raise ValueError("tc.homography_hypotheses must lie in 1 .. 65536 (got {0})".format(hyp))
+    if not 0 <= seed <= 0xFFFFFFFF:
+        raise ValueError("tc.homography_seed must lie in 0 .. 2**32 - 1 (got {0})".format(seed))
+    if inl < 4:
+        raise ValueError("tc.homography_min_inliers must be at least 4 (got {0})".format(inl))
+    if not err >= 0.0:
+        raise ValueError("tc.homography_max_error must be a number >= 0")
+    if ncols is not None and not (1 <= hp.ncols <= 65535 and 1 <= hp.nrows <= 65535):
+        raise ValueError("the homography check takes frames of 1 .. 65535 columns and rows")
+    hp.hypotheses, hp.seed, hp.min_inliers, hp.max_error = hyp, seed, inl, err
+    return hp
 
 
 def guess_records(guess, n, affine=False):

@@ -124,3 +124,23 @@ def warp_frame(base, A, t=(0.0, 0.0)):
     out = (base[y0, x0] * ((1 - ax) * (1 - ay)) + base[y0, x1] * (ax * (1 - ay))
            + base[y1, x0] * ((1 - ax) * ay) + base[y1, x1] * (ax * ay))
     return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
+
+
+def warp_homography(base, H):
+    """uint8 frame whose content is `base` mapped by the homography p -> H p in pixel coordinates (3x3, row-major; periodic texture,
+    bilinear resampling): a feature at p in `base` is found at (H p)[:2] / (H p)[2].  Known answer for the homography check."""
+    h, w = base.shape
+    Hi = np.linalg.inv(np.asarray(H, np.float64).reshape(3, 3))
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    sw = Hi[2, 0] * xs + Hi[2, 1] * ys + Hi[2, 2]
+    sx = (Hi[0, 0] * xs + Hi[0, 1] * ys + Hi[0, 2]) / sw      # source position in `base`
+    sy = (Hi[1, 0] * xs + Hi[1, 1] * ys + Hi[1, 2]) / sw
+    x0 = np.floor(sx)
+    y0 = np.floor(sy)
+    ax, ay = sx - x0, sy - y0
+    x0 = x0.astype(np.int64) % w
+    y0 = y0.astype(np.int64) % h
+    x1, y1 = (x0 + 1) % w, (y0 + 1) % h
+    out = (base[y0, x0] * ((1 - ax) * (1 - ay)) + base[y0, x1] * (ax * (1 - ay))
+           + base[y1, x0] * ((1 - ax) * ay) + base[y1, x1] * (ax * ay))
+    return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)

@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import epipolar_params_from_tc, fb_params_from_tc, guess_records, light_params_from_tc, model_params_from_tc
+from .params import epipolar_params_from_tc, fb_params_from_tc, guess_records, homography_params_from_tc, light_params_from_tc, model_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -404,7 +404,13 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     every tracked feature further than tc.epipolar_max_error px (Sampson distance) from its epipolar line comes back lost, as
     (-1, -1, KLT_EPIPOLAR_OUTLIER); tc.epipolar_last is then the backend.EPIPOLAR_DTYPE record (backend.epipolar_matrix turns it into F
     in pixels).  For a camera that moves through a scene with depth, where parallax is no affine motion.  Works
-    with what tc.motionModelCheck works with; ValueError together with it, with tc.affineConsistencyCheck >= 0 and for bad values."""
+    with what tc.motionModelCheck works with; ValueError together with it, with tc.affineConsistencyCheck >= 0 and for bad values.
+    tc.homographyCheck = True (not in the reference): in the same place the frame pair's homography is found among the tracks and every
+    tracked feature further than tc.homography_max_error px from where it sends the feature comes back lost, as
+    (-1, -1, KLT_HOMOGRAPHY_OUTLIER); tc.homography_last is then the backend.HOMOGRAPHY_DTYPE record (backend.homography_matrix turns it
+    into H in pixels).  For a camera that rotates and for any camera that looks at a plane.  Works with what
+    tc.epipolarCheck works with; ValueError together with either other consensus check, with tc.affineConsistencyCheck >= 0 and for
+    bad values."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -414,6 +420,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
     model_params_from_tc(tc)                          # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
     epipolar_params_from_tc(tc)                       # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
+    homography_params_from_tc(tc)                     # (... and for tc.homographyCheck, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -453,6 +460,12 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR
         ctx.set_epipolar_params(epipolar)
         ctx.epipolar_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR, nfeat)
+    # tc.homographyCheck: likewise (never together with either of the two)
+    homography = homography_params_from_tc(tc, ncols, nrows)
+    if homography.mode:
+        from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY
+        ctx.set_homography_params(homography)
+        ctx.homography_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY, nfeat)
     # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
     # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
     quality = bool(getattr(tc, "trackQuality", False))
@@ -473,6 +486,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
             ctx.motion_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_MODEL, nfeat)
         if epipolar.mode:
             ctx.epipolar_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR, nfeat)
+        if homography.mode:
+            ctx.homography_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY, nfeat)
         if quality:
             ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
@@ -498,6 +513,9 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
     if epipolar.mode:                                 # one more download of 96 bytes
         from .backend import EPIPOLAR_DTYPE
         tc.epipolar_last = ctx.epipolar_download(_FB_API_EPIPOLAR) if nfeat else np.zeros(1, EPIPOLAR_DTYPE)[0]
+    if homography.mode:                               # likewise
+        from .backend import HOMOGRAPHY_DTYPE
+        tc.homography_last = ctx.homography_download(_FB_API_HOMOGRAPHY) if nfeat else np.zeros(1, HOMOGRAPHY_DTYPE)[0]
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

@@ -20,6 +20,7 @@ _FB_GUESS = 65525            # ... and the constant-velocity guesses of the step
 _FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality records, laid out like the feature table (below _FB_TABLE)
 _FBM_TABLE = 48000           # tc.motionModelCheck: a parallel table of model records, five feature records per frame (below _FBQ_TABLE)
 _FBE_TABLE = 42000           # tc.epipolarCheck: a parallel table of epipolar model records, six feature records per frame (below _FBM_TABLE)
+_FBH_TABLE = 36000           # tc.homographyCheck: a parallel table of homography model records, six feature records per frame (below _FBE_TABLE)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -157,6 +158,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     together with the affine consistency check.
     tc.epipolarCheck = True: one epipolar check per frame in the same place (never both); the replacement pass refills the slots it flagged
     (KLT_EPIPOLAR_OUTLIER); `ft.epipolar` holds one backend.EPIPOLAR_DTYPE record per frame, row 0 all zero.
+    tc.homographyCheck = True: one homography check per frame in the same place (never with either of the two); the replacement pass refills
+    the slots it flagged (KLT_HOMOGRAPHY_OUTLIER); `ft.homography` holds one backend.HOMOGRAPHY_DTYPE record per frame, row 0 all zero.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
@@ -173,6 +176,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     model_params_from_tc(tc)             # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
     from .params import epipolar_params_from_tc
     epipolar_params_from_tc(tc)          # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
+    from .params import homography_params_from_tc
+    homography_params_from_tc(tc)        # (... and for tc.homographyCheck, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -240,7 +245,11 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
     if epipolar.mode:
         ctx.set_epipolar_params(epipolar)
     mtables = []
-    mbase, mrecords = (_FBE_TABLE, 6) if epipolar.mode else (_FBM_TABLE, 5)
+    from .params import homography_params_from_tc
+    homography = homography_params_from_tc(tc, ncols, nrows)     # ... or this one (never two of the three), six records per frame likewise
+    if homography.mode:
+        ctx.set_homography_params(homography)
+    mbase, mrecords = (_FBH_TABLE, 6) if homography.mode else (_FBE_TABLE, 6) if epipolar.mode else (_FBM_TABLE, 5)
 
     def mrow_fb(k):
         ci, off = divmod(k, chunk)
@@ -331,6 +340,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                     ctx.motion_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
                 if epipolar.mode:                    # likewise
                     ctx.epipolar_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
+                if homography.mode:                  # likewise
+                    ctx.homography_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
                 if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
                     ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
@@ -436,9 +447,9 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
             ctx.featbuf_download_into(base, rec[lo:hi])
         ft.quality = rec.view(QUALITY_DTYPE)
         ft.quality[0] = 0                                        # nothing was tracked into the first frame
-    if model.mode or epipolar.mode:
-        from .backend import EPIPOLAR_DTYPE, FEAT_DTYPE, MODEL_DTYPE
-        dtype = EPIPOLAR_DTYPE if epipolar.mode else MODEL_DTYPE
+    if model.mode or epipolar.mode or homography.mode:
+        from .backend import EPIPOLAR_DTYPE, FEAT_DTYPE, HOMOGRAPHY_DTYPE, MODEL_DTYPE
+        dtype = HOMOGRAPHY_DTYPE if homography.mode else EPIPOLAR_DTYPE if epipolar.mode else MODEL_DTYPE
         rec = np.zeros((nframes, mrecords), FEAT_DTYPE)
         for ci, base in enumerate(mtables):
             lo = ci * chunk
@@ -449,7 +460,9 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
         if nFeatures == 0:
             records[:] = np.zeros(1, dtype)[0]                   # (no list, no launch: nothing was written)
         records[0] = np.zeros(1, dtype)[0]                       # nothing was tracked into the first frame
-        if epipolar.mode:
+        if homography.mode:
+            ft.homography = records
+        elif epipolar.mode:
             ft.epipolar = records
         else:
             ft.models = records
