@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -55,7 +55,8 @@ enum { KLT_TRACKED = 0, KLT_NOT_FOUND = -1, KLT_SMALL_DET = -2, KLT_MAX_ITERATIO
        KLT_FB_INCONSISTENT = -6, /* not in the reference: rejected by the forward-backward check (klt_track_fb_async); lost, like every negative val */
        KLT_MODEL_OUTLIER = -7,   /* not in the reference: off the frame pair's dominant affine motion (klt_motion_check_async); lost likewise */
        KLT_EPIPOLAR_OUTLIER = -8, /* not in the reference: off the frame pair's fundamental matrix (klt_epipolar_check_async); lost likewise */
-       KLT_HOMOGRAPHY_OUTLIER = -9 /* not in the reference: off the frame pair's homography (klt_homography_check_async); lost likewise */ };
+       KLT_HOMOGRAPHY_OUTLIER = -9, /* not in the reference: off the frame pair's homography (klt_homography_check_async); lost likewise */
+       KLT_CROWDED = -10          /* not in the reference: drifted within min_distance of an older track (klt_crowd_check_async); lost likewise */ };
 
 /* selection modes, selectGoodFeatures.py:11-13 */
 enum { KLT_SELECTING_ALL = 1, KLT_REPLACING_SOME = 2 };
@@ -678,6 +679,57 @@ int klt_homography_check(klt_ctx *ctx, const klt_feat *in, klt_feat *out, klt_ho
 int klt_homography_matrix(const klt_homography_model *model, double H[9]);
 /* 0: no homography-check launch yet; 1: the last one ran as three launches on one pair, 2: on a table of pairs.  A diagnostic. */
 int klt_homography_check_path(klt_ctx *ctx);
+
+/* ---- crowding check (not in the reference) ----------------------------------------------------------------------- */
+/* Selection keeps features mindist apart and the replacement pass keeps every NEW feature mindist away from the live ones; nothing keeps
+ * the live ones apart once they move (a zoom-out, a camera that backs away, two tracks that slide onto one corner).  This check drops
+ * every tracked feature that has come within min_distance of an older one: the missing half of that invariant.  It reads one feature
+ * list (and the previous step's crowd records) and no frame, and runs stream-ordered behind whatever wrote them.
+ *
+ * THE RULE (serial; the device equals it byte for byte).  Inputs: a list `out` of n records, optionally n klt_crowd records `prev` (the
+ * previous step's output), ncols, nrows and min_distance d >= 1; r = d - 1, as the minimum-distance walk of selection works with
+ * mindist - 1.
+ *  1 candidates  record i is a candidate iff out.val == KLT_TRACKED, 0 <= x < ncols and 0 <= y < nrows: f32 comparisons (NaN and the
+ *                infinities fail; -0.0 passes), made before any conversion.  Its pixel is px = (int)x, py = (int)y, by truncation, as
+ *                the reference's int(feat.x) when it stamps the live features into its feature map.
+ *  2 age in      a_i = max(prev[i].age, 0); without prev every a_i is 0.
+ *  3 order       candidates are ordered by age descending, then by list index ascending.
+ *  4 walk        in that order candidate i is CROWDED iff an earlier KEPT candidate j has |px_i - px_j| <= r and |py_i - py_j| <= r;
+ *                otherwise it is kept.  This is the reference's feature map: offered the candidates' pixels as a point list in this
+ *                order, its walk accepts exactly the kept ones.  The WINNER of a crowded candidate is the first kept candidate in the
+ *                order that covers it.
+ *  5 outputs     crowded records of `out` become (-1, -1, KLT_CROWDED, out.aux); every other record of `out` keeps its bytes.  One
+ *                klt_crowd is written per record: kept (min(a_i, INT32_MAX - 1) + 1, -1, 1, 0); crowded (0, winner's index, 2, 0);
+ *                non-candidate (0, -1, 0, 0).
+ * `age` so counts the consecutive steps a slot has been tracked: a slot that was lost, flagged by any check or refilled by the
+ * replacement pass starts again at 0; `winner` tells which track a dropped one merged into.  The crowd records go to a buffer of their
+ * own and nothing but `out` is updated in place: a step may be enqueued ahead and repeated, like the stateless tracker launches.
+ * Afterwards no two live records are within r px of each other (Chebyshev distance on integer pixels): what the replacement pass
+ * assumes of the list it stamps.
+ * The device finds the same set in rounds -- kept, if every higher-priority neighbour is crowded; crowded, if any is kept -- inside ONE
+ * workgroup per list (no workgroup ever waits for another); the number of rounds depends on the data (a chain of k candidates spaced r
+ * apart with falling ages takes k), the loop ends when no candidate is undecided. */
+typedef struct { int32_t mode; int32_t ncols, nrows; int32_t min_distance; } klt_crowd_params;
+typedef struct { int32_t age, winner, val, pad; } klt_crowd;     /* val: 0 non-candidate, 1 kept, 2 crowded */
+/* mode: 0 = off (the default), 1 = on; anything else is KLT_ERR_ARG, and so are min_distance < 1 and (mode 1) ncols / nrows outside 1 .. 65535. */
+int klt_set_crowd_params(klt_ctx *ctx, const klt_crowd_params *p);
+/* The check on a resident list: fb_out is rewritten in place, fb_prev (-1: none) holds the previous step's klt_crowd records, fb_crowd
+ * (allocated if needed; klt_crowd records live in feature buffers as klt_quality records do) takes this step's.  fb_crowd must be
+ * distinct from fb_out and fb_prev, by index and by address (KLT_ERR_ARG); lists shorter than n: KLT_ERR_STATE; mode 0: KLT_ERR_STATE
+ * with a klt_last_error text; n == 0: KLT_OK, nothing is enqueued.  Three launches, no host synchronisation; the scratch belongs to the
+ * context (KLT_ERR_NOMEM when it cannot grow, the context stays usable). */
+int klt_crowd_check_async(klt_ctx *ctx, int fb_out, int fb_prev, int fb_crowd, int n);
+/* npairs lists in the same three launches (fb_prev may be NULL: none has a previous step; or hold -1 entries); every fb_crowd distinct
+ * from every other buffer of the call, every fb_out from every other fb_out. */
+int klt_crowd_check_batch_async(klt_ctx *ctx, const int *fb_out, const int *fb_prev, const int *fb_crowd, int npairs, int n);
+/* synchronous, host arrays: out is rewritten, crowd filled, *n_crowded (may be NULL) = the records that became KLT_CROWDED. */
+int klt_crowd_check(klt_ctx *ctx, klt_feat *out, const klt_crowd *prev, klt_crowd *crowd, int n, int *n_crowded);
+/* 0: no crowd-check launch yet; 1: the last one ran on one list, 2: on a table of lists.  A diagnostic. */
+int klt_crowd_check_path(klt_ctx *ctx);
+/* The rounds the last single-list launch took (the first list's of a batch), read back from the device: synchronises.  phase_ticks (may
+ * be NULL) takes what the resolve launch's one workgroup spent grouping the candidates by cell, in the rounds and writing the records,
+ * in ticks of 10 ns.  A diagnostic; KLT_ERR_STATE before any crowd-check launch. */
+int klt_crowd_check_rounds(klt_ctx *ctx, int *rounds, int *phase_ticks);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

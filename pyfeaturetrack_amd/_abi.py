@@ -57,6 +57,14 @@ class KltHomographyModel(C.Structure):
                 ("hypothesis", C.c_int32), ("hypothesis_inliers", C.c_int32), ("pad", C.c_int32)]
 
 
+class KltCrowdParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("ncols", C.c_int32), ("nrows", C.c_int32), ("min_distance", C.c_int32)]
+
+
+class KltCrowd(C.Structure):
+    _fields_ = [("age", C.c_int32), ("winner", C.c_int32), ("val", C.c_int32), ("pad", C.c_int32)]
+
+
 class KltParams(C.Structure):
     _fields_ = [
         ("mindist", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
@@ -202,6 +210,12 @@ SYMBOLS = {
     "klt_homography_check": (_I, [_P, _P, _P, C.POINTER(KltHomographyModel), _I, _PI]),
     "klt_homography_matrix": (_I, [C.POINTER(KltHomographyModel), C.POINTER(C.c_double)]),
     "klt_homography_check_path": (_I, [_P]),
+    "klt_set_crowd_params": (_I, [_P, C.POINTER(KltCrowdParams)]),
+    "klt_crowd_check_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_crowd_check_batch_async": (_I, [_P, _PI, _PI, _PI, _I, _I]),
+    "klt_crowd_check": (_I, [_P, _P, _P, _P, _I, _PI]),
+    "klt_crowd_check_path": (_I, [_P]),
+    "klt_crowd_check_rounds": (_I, [_P, _PI, _PI]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
+                   KltCrowd, KltCrowdParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
@@ -37,6 +37,10 @@ assert EPIPOLAR_DTYPE.itemsize == C.sizeof(KltEpipolarModel) == 6 * FEAT_DTYPE.i
 HOMOGRAPHY_DTYPE = np.dtype([("h", np.float64, (9,)), ("valid", np.int32), ("n_candidates", np.int32), ("n_inliers", np.int32),
                              ("hypothesis", np.int32), ("hypothesis_inliers", np.int32), ("pad", np.int32)])
 assert HOMOGRAPHY_DTYPE.itemsize == C.sizeof(KltHomographyModel) == 6 * FEAT_DTYPE.itemsize
+# one crowd record per feature (klt_crowd; klt_crowd_check*): age = the consecutive steps the slot has been tracked, winner = the record a
+# crowded one merged into (-1 otherwise), val 0 non-candidate / 1 kept / 2 crowded; they live in feature buffers like quality records
+CROWD_DTYPE = np.dtype([("age", np.int32), ("winner", np.int32), ("val", np.int32), ("pad", np.int32)])
+assert CROWD_DTYPE.itemsize == C.sizeof(KltCrowd) == FEAT_DTYPE.itemsize
 
 SELECTING_ALL = 1
 REPLACING_SOME = 2
@@ -52,6 +56,8 @@ _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures
 _FB_API_MODEL = 53999                # the model record of a KLTTrackFeatures call with tc.motionModelCheck (48000 .. 53998: KLTTrackSequence's model rows)
 _FB_API_EPIPOLAR = 47999             # the model record of a KLTTrackFeatures call with tc.epipolarCheck (42000 .. 47998: KLTTrackSequence's epipolar rows)
 _FB_API_HOMOGRAPHY = 41999           # the model record of a KLTTrackFeatures call with tc.homographyCheck (36000 .. 41998: KLTTrackSequence's homography rows)
+_FB_API_CROWD = 35999                # crowd records of a KLTTrackFeatures call with tc.crowdingCheck (30000 .. 35998: KLTTrackSequence's crowd rows)
+_FB_API_CROWD_PREV = 29999           # ... and the ages the caller handed in (age=)
 _FB_API_QUALITY = 59999             # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
 
 
@@ -904,6 +910,59 @@ class Context:
         """the HOMOGRAPHY_DTYPE record of feature buffer `fb` (what a homography_check*_async launch wrote there)"""
         return self.featbuf_download(fb, 6).view(HOMOGRAPHY_DTYPE)[0]
 
+    # ------------------------------------------------ crowding check (klt_set_crowd_params, klt_crowd_check*)
+    def set_crowd_params(self, cp=None, **kw):
+        """klt_set_crowd_params: `cp` a KltCrowdParams, or its fields by name (mode, ncols, nrows, min_distance; defaults 1, -, -, 1)"""
+        if cp is None:
+            d = dict(mode=1, min_distance=1)
+            d.update(kw)
+            cp = KltCrowdParams(**d)
+        key = bytes(cp)
+        if key != getattr(self, "_crowd_key", None):
+            self._crowd_key = None
+            self._check(self._lib.klt_set_crowd_params(self._h, C.byref(cp)))
+            self._crowd_key = key
+
+    def crowd_check(self, fl_out, prev=None):
+        """klt_crowd_check: (out, crowd, n_crowded) -- fl_out with every tracked record that lies within min_distance of an older one
+        turned into (-1, -1, KLT_CROWDED, aux), the CROWD_DTYPE records, and how many records that were.  `prev`: the CROWD_DTYPE
+        records of the previous step (their age column counts), or None."""
+        out = np.array(fl_out, FEAT_DTYPE, order="C")
+        if prev is not None:
+            prev = np.ascontiguousarray(prev, CROWD_DTYPE)
+            if len(prev) != len(out):
+                raise ValueError("the list has %d records, prev %d" % (len(out), len(prev)))
+        crowd = np.zeros(len(out), CROWD_DTYPE)
+        cnt = C.c_int(0)
+        self._check(self._lib.klt_crowd_check(self._h, out.ctypes.data, prev.ctypes.data if prev is not None else None, crowd.ctypes.data,
+                                              len(out), C.byref(cnt)))
+        return out, crowd, cnt.value
+
+    def crowd_check_async(self, fb_out, fb_prev, fb_crowd, n):
+        """fb_prev: -1 or None = no previous step"""
+        self._check(self._lib.klt_crowd_check_async(self._h, fb_out, -1 if fb_prev is None else fb_prev, fb_crowd, n))
+
+    def crowd_check_batch_async(self, lists, n):
+        """lists: [(fb_out, fb_prev, fb_crowd), ...] (fb_prev -1: none) -- the check's launches once for all of them."""
+        cols = _columns(lists, 3)
+        self._check(self._lib.klt_crowd_check_batch_async(self._h, cols[0], cols[1], cols[2], len(lists), n))
+
+    def crowd_check_path(self):
+        """klt_crowd_check_path: 0 no crowd-check launch yet, 1 the last one ran on one list, 2 on a table of lists (a diagnostic)"""
+        return self._check(self._lib.klt_crowd_check_path(self._h))
+
+    def crowd_check_rounds(self, phases=False):
+        """klt_crowd_check_rounds: the rounds the last launch's (first) list took; waits for it (a diagnostic).  `phases`: (rounds,
+        (grouping, rounds, records) in us) -- what the resolve launch's workgroup spent where"""
+        r = C.c_int(0)
+        ticks = (C.c_int * 3)()
+        self._check(self._lib.klt_crowd_check_rounds(self._h, C.byref(r), ticks))
+        return (r.value, tuple(t * 0.01 for t in ticks)) if phases else r.value
+
+    def crowd_download(self, fb, n):
+        """n crowd records of feature buffer `fb` (what a crowd_check*_async launch wrote there)"""
+        return self.featbuf_download(fb, n).view(CROWD_DTYPE)
+
     def track_stats_reset(self):
         self._check(self._lib.klt_track_stats_reset(self._h))
 
@@ -1096,5 +1155,5 @@ def model_summary(model):
             "hypothesis": int(model["hypothesis"])}
 
 
-__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "MODEL_DTYPE", "model_affine", "model_summary", "EPIPOLAR_DTYPE", "epipolar_matrix", "HOMOGRAPHY_DTYPE", "homography_matrix", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
+__all__ = ["Context", "default_context", "context_of", "FEAT_DTYPE", "QUALITY_DTYPE", "MODEL_DTYPE", "model_affine", "model_summary", "EPIPOLAR_DTYPE", "epipolar_matrix", "HOMOGRAPHY_DTYPE", "homography_matrix", "CROWD_DTYPE", "SELECTING_ALL", "REPLACING_SOME", "KltBackendError", "KltCommTimeout", "KltOutOfMemory",
            "KLT_MAX_LEVELS", "KltParams"]

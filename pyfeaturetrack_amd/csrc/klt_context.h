@@ -12,6 +12,7 @@
 //   api_model.hip     motion-model check (single pair, batched), the model record as an affine map
 //   api_epipolar.hip  epipolar check (single pair, batched), the model record as a fundamental matrix in pixels
 //   api_homography.hip homography check (single pair, batched), the model record as a homography in pixels
+//   api_crowd.hip     crowding check (single list, batched)
 //   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
@@ -35,10 +36,10 @@ namespace kltapi {
 
 
 enum Family { F_SMOOTH_GRAD, F_PYR_REDUCE, F_GRAD, F_SMOOTH_H, F_SMOOTH_V, F_PYR_H, F_PYR_V, F_GRAD_H, F_GRAD_V, F_TRACK,
-              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_COUNT };
+              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_COUNT };
 inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_reduce", "gradients", "smooth_h", "smooth_v", "pyramid_h",
                                           "pyramid_v", "gradient_h", "gradient_v", "track", "sat_rows", "sat_cols",
-                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check"};
+                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check"};
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
@@ -311,6 +312,13 @@ struct klt_ctx {
     unsigned char *hom_scratch = nullptr;
     size_t hom_scratch_cap = 0;
     SentTable<ModelPair> hom_table;                                // klt_homography_check_batch_async
+    // crowding check (klt_set_crowd_params, klt_crowd_check*): scratch and list table of its own
+    klt_crowd_params crowdp{0, 0, 0, 1};
+    int crowd_path = 0;                                            // klt_crowd_check_path
+    unsigned char *crowd_scratch = nullptr;
+    size_t crowd_scratch_cap = 0;
+    const int *crowd_rounds = nullptr;                             // in crowd_scratch: the last launch's round count (klt_crowd_check_rounds)
+    SentTable<CrowdPair> crowd_table;                              // klt_crowd_check_batch_async
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -372,7 +380,7 @@ struct TimerScope {
         }
         // families whose scope holds ONE launch that goes through klt_launch (the order kernel in front of a tracker and the threshold
         // kernel behind the eigenvalue pass do not): timed by that dispatch's own timestamps.  Scopes with several launches keep the pair
-        stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE ||
+        stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE || fam == F_CROWD_PREPARE || fam == F_CROWD ||
                                       fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN);
         if (stamps) { g_klt_stamp_start = t.a; g_klt_stamp_stop = t.b; }      // filled by the launch itself (klt_launch)
         else hipEventRecord(t.a, st);

@@ -148,6 +148,32 @@ struct EpipolarArgs {
 // klt_homography_model
 static_assert(sizeof(klt_homography_model) == 6 * sizeof(klt_feat), "a homography model record lives in a feature buffer of six records");
 
+// one list of a crowding check (klt_crowd_check_async): the list, the previous step's crowd records (null: none),
+// this step's, and the list's part of the context's scratch.  The table of a batched launch (device memory, indexed by blockIdx.y)
+// holds these.
+static_assert(sizeof(klt_crowd) == sizeof(klt_feat), "crowd records live in feature buffers");
+struct CrowdCand { int cell, pos, age, idx; };      // cell: -1 = no candidate; pos = px | py << 16; idx: in `info` the candidate's place in its
+                                                    // cell, in `sorted` the record's number
+struct CrowdPair {
+    klt_feat *out;
+    const klt_crowd *prev;
+    klt_crowd *crowd;
+    CrowdCand *info;                    // [n]: record i as the prepare launch classified it
+    CrowdCand *sorted;                  // [n]: the m candidates, grouped by cell (row-major cell order; any order inside a cell)
+    int *cells;                         // [gx * gy]: candidates per cell
+    int *starts;                        // [gx * gy + 1]: where each cell's group begins in `sorted`; the last entry is m, the candidates
+    int *state;                         // [n]: a candidate's state, for lists longer than the resolve kernel's LDS holds
+    int *rounds;                        // [4]: the rounds the resolve kernel took; 10 ns ticks of its grouping, its rounds, its record writing
+};
+struct CrowdArgs {
+    CrowdPair one;                      // single-list launch
+    const CrowdPair *pairs;             // batched launch: npairs descriptors (`one` unused)
+    int npairs;
+    int n, ncols, nrows, r;             // r = min_distance - 1
+    int side, gx, gy;                   // square cells of `side` pixels (> r: all neighbours within 3 x 3 cells), gx x gy of them
+};
+constexpr int kCrowdLdsStates = 24576;  // lists up to this length keep pixel and state of every candidate in LDS (5 bytes each: 120 KiB)
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -446,6 +472,11 @@ void launch_epipolar_decide(hipStream_t s, const EpipolarArgs &a);
 // the homography check (homography_kernels.hip) behind launch_model_gather, likewise
 void launch_homography_score(hipStream_t s, const EpipolarArgs &a);
 void launch_homography_decide(hipStream_t s, const EpipolarArgs &a);
+// the crowding check (crowd_kernels.hip): classify the records and clear the cell counts; every candidate's place in its cell; then one
+// workgroup per list groups them by cell, resolves, writes
+void launch_crowd_prepare(hipStream_t s, const CrowdArgs &a);
+void launch_crowd_rank(hipStream_t s, const CrowdArgs &a);
+void launch_crowd_resolve(hipStream_t s, const CrowdArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

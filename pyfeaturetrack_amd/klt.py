@@ -40,6 +40,7 @@ class kltState:
     KLT_MODEL_OUTLIER = -7            # not in the reference: off the frame pair's dominant affine motion (tc.motionModelCheck)
     KLT_EPIPOLAR_OUTLIER = -8         # not in the reference: off the frame pair's fundamental matrix (tc.epipolarCheck)
     KLT_HOMOGRAPHY_OUTLIER = -9       # not in the reference: off the frame pair's homography (tc.homographyCheck)
+    KLT_CROWDED = -10                 # not in the reference: drifted within mindist of an older track (tc.crowdingCheck)
 
 
 def _pyramidSigma(tc):
@@ -126,6 +127,12 @@ class KLT_TrackingContext:
         self.homography_hypotheses = 256
         self.homography_seed = 0
         self.homography_min_inliers = 8
+        # crowding check (not in the reference): False, or True -- behind the tracker and every other check, a tracked feature that has
+        # come within crowding_min_distance (None: mindist) of an older track is lost (KLT_CROWDED): what selection and replacement
+        # guarantee of new features, kept for the live ones; KLTTrackFeatures leaves tc.crowding_last, KLTTrackSequence's table carries
+        # ft.crowd.
+        self.crowdingCheck = False
+        self.crowding_min_distance = None
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -740,6 +747,7 @@ class KLT_FeatureTable:
     models = None             # KLTTrackSequence with tc.motionModelCheck: [nFrames] backend.MODEL_DTYPE records, row 0 all zero
     epipolar = None           # KLTTrackSequence with tc.epipolarCheck: [nFrames] backend.EPIPOLAR_DTYPE records, row 0 all zero
     homography = None         # KLTTrackSequence with tc.homographyCheck: [nFrames] backend.HOMOGRAPHY_DTYPE records, row 0 all zero
+    crowd = None              # KLTTrackSequence with tc.crowdingCheck: [nFrames, nFeatures] backend.CROWD_DTYPE records, row 0 all zero
 
     def feature(self, feat, frame):
         return _feature_of(self.rec[frame, feat])
@@ -772,6 +780,10 @@ def KLTPrintTrackingContext(tc):
     if getattr(tc, "homographyCheck", False):        # (likewise)
         print("")
         for name in ("homographyCheck", "homography_max_error", "homography_hypotheses", "homography_seed", "homography_min_inliers"):
+            print("\t{0} = {1}".format(name, getattr(tc, name, None)))
+    if getattr(tc, "crowdingCheck", False):          # (likewise)
+        print("")
+        for name in ("crowdingCheck", "crowding_min_distance"):
             print("\t{0} = {1}".format(name, getattr(tc, name, None)))
     print("\n")
 

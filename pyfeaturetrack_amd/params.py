@@ -1,7 +1,7 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import numpy as np
 
-from ._abi import KltAffineParams, KltEpipolarParams, KltFbParams, KltHomographyParams, KltLightParams, KltModelParams, KltParams
+from ._abi import KltAffineParams, KltCrowdParams, KltEpipolarParams, KltFbParams, KltHomographyParams, KltLightParams, KltModelParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -207,6 +207,51 @@ def homography_params_from_tc(tc, ncols=None, nrows=None):
         raise ValueError("the homography check takes frames of 1 .. 65535 columns and rows")
     hp.hypotheses, hp.seed, hp.min_inliers, hp.max_error = hyp, seed, inl, err
     return hp
+
+
+def crowd_params_from_tc(tc, ncols=None, nrows=None):
+    """tc.crowdingCheck / tc.crowding_min_distance -> klt_crowd_params for a frame of ncols x nrows: False (the default) packs mode 0,
+    True mode 1; crowding_min_distance None (the default) means tc.mindist.  Both are read with defaults: a tracking context made
+    elsewhere has neither.  ValueError -- before any device work -- for a value that is no bool, for a distance < 1 and for the check
+    together with tc.affineConsistencyCheck >= 0 (what the other checks refuse).  It goes with everything else, lighting compensation
+    included: the check reads no frame."""
+    on = getattr(tc, "crowdingCheck", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("tc.crowdingCheck must be True or False (got {0!r})".format(on))
+    cp = KltCrowdParams()
+    cp.mode = 1 if on else 0
+    cp.ncols, cp.nrows = int(ncols or 0), int(nrows or 0)
+    cp.min_distance = 1
+    if not cp.mode:
+        return cp
+    if getattr(tc, "affineConsistencyCheck", -1) >= 0:
+        raise ValueError("crowdingCheck and affineConsistencyCheck cannot both be switched on")
+    dist = getattr(tc, "crowding_min_distance", None)
+    if dist is None:
+        dist = tc.mindist
+    if isinstance(dist, (bool, np.bool_)) or int(dist) != dist:
+        raise ValueError("tc.crowding_min_distance must be a whole number (got {0!r})".format(dist))
+    if not 1 <= int(dist) <= 0x7FFFFFFF:
+        raise ValueError("tc.crowding_min_distance must be at least 1 (got {0})".format(dist))
+    if ncols is not None and not (1 <= cp.ncols <= 65535 and 1 <= cp.nrows <= 65535):
+        raise ValueError("the crowding check takes frames of 1 .. 65535 columns and rows")
+    cp.min_distance = int(dist)
+    return cp
+
+
+def age_records(age, n):
+    """The `age=` argument of KLTTrackFeatures -> None, or n klt_crowd records whose age column holds it: an (n,) integer array-like (the
+    age column of the last call's tc.crowding_last).  ValueError for another shape or for values that are no 32-bit integers."""
+    if age is None:
+        return None
+    a = np.asarray(age)
+    if a.shape != (n,) or a.dtype.kind not in "iu":
+        raise ValueError("age must be an integer array of shape ({0},) (got {1} of {2})".format(n, a.dtype, a.shape))
+    if n and (a.min() < -0x80000000 or a.max() > 0x7FFFFFFF):
+        raise ValueError("age must hold 32-bit integers")
+    rec = np.zeros((n, 4), np.int32)
+    rec[:, 0] = a
+    return rec
 
 
 def guess_records(guess, n, affine=False):

@@ -11,7 +11,7 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import epipolar_params_from_tc, fb_params_from_tc, guess_records, homography_params_from_tc, light_params_from_tc, model_params_from_tc
+from .params import age_records, crowd_params_from_tc, epipolar_params_from_tc, fb_params_from_tc, guess_records, homography_params_from_tc, light_params_from_tc, model_params_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
@@ -383,7 +383,7 @@ def KLTPredictConstantVelocity(prev_positions, featurelist):
     return out
 
 
-def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
+def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     """trackFeatures.py:205-409 (translation model; the affine branch :347-399 calls functions the
     reference never defines).
     `guess` (not in the reference): an (n, 2) array-like of predicted frame-2 positions, one row per feature; each feature's search starts
@@ -410,7 +410,14 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     (-1, -1, KLT_HOMOGRAPHY_OUTLIER); tc.homography_last is then the backend.HOMOGRAPHY_DTYPE record (backend.homography_matrix turns it
     into H in pixels).  For a camera that rotates and for any camera that looks at a plane.  Works with what
     tc.epipolarCheck works with; ValueError together with either other consensus check, with tc.affineConsistencyCheck >= 0 and for
-    bad values."""
+    bad values.
+    tc.crowdingCheck = True (not in the reference): behind the tracker and behind any of the checks above, every tracked feature that has
+    come within tc.crowding_min_distance (None: tc.mindist) of an older track comes back lost, as (-1, -1, KLT_CROWDED): after the call
+    no two live features are closer than selection would have placed them.  `age`: an (n,) integer array, how many
+    steps each feature has been tracked (default: zeros, so list order decides which of two colliding tracks stays: the lower index).
+    tc.crowding_last is then a backend.CROWD_DTYPE array of len(featurelist) -- age (what to hand to the next call), winner (the record a
+    crowded one merged into), val (0 not tracked, 1 kept, 2 crowded).  Goes with everything but tc.affineConsistencyCheck >= 0
+    (ValueError), lighting compensation included: it reads no frame."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -421,15 +428,17 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None):
     model_params_from_tc(tc)                          # (ValueError for an unknown tc.motionModelCheck, bad parameters, or the affine check beside it, likewise)
     epipolar_params_from_tc(tc)                       # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
     homography_params_from_tc(tc)                     # (... and for tc.homographyCheck, likewise)
+    crowd_params_from_tc(tc)                          # (... and for tc.crowdingCheck, likewise)
+    age = age_records(age, len(featurelist))          # (ValueError for an `age` of another shape or kind, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
-        _track_locked(ctx, tc, img1, img2, featurelist, guess)
+        _track_locked(ctx, tc, img1, img2, featurelist, guess, age)
     if KLT_verbose >= 1:
         print("\n\t{0} features successfully tracked.".format(KLTCountRemainingFeatures(featurelist)))
 
 
-def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
+def _track_locked(ctx, tc, img1, img2, featurelist, guess=None, age=None):
     affine = tc.affineConsistencyCheck >= 0
     # forward-backward check: one fused launch (klt_track_fb_async), stateless -- it can be repeated like the plain tracker's.  A rejected
     # feature comes back as (-1, -1, KLT_FB_INCONSISTENT) and goes through the branches below like any other lost one.
@@ -466,6 +475,17 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
         from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY
         ctx.set_homography_params(homography)
         ctx.homography_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY, nfeat)
+    # tc.crowdingCheck: behind all of them and in front of the quality launch (a crowded record is then simply unmeasured), on the tracker's
+    # output buffer; the ages the caller handed in go up first, as crowd records
+    crowd = crowd_params_from_tc(tc, ncols, nrows)
+    crowd_prev = -1
+    if crowd.mode:
+        from .backend import FEAT_DTYPE, _FB_API_OUT, _FB_API_CROWD, _FB_API_CROWD_PREV
+        ctx.set_crowd_params(crowd)
+        if age is not None and nfeat:
+            ctx.featbuf_upload(_FB_API_CROWD_PREV, age.view(FEAT_DTYPE).reshape(nfeat))
+            crowd_prev = _FB_API_CROWD_PREV
+        ctx.crowd_check_async(_FB_API_OUT, crowd_prev, _FB_API_CROWD, nfeat)
     # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
     # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
     quality = bool(getattr(tc, "trackQuality", False))
@@ -488,6 +508,8 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
             ctx.epipolar_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_EPIPOLAR, nfeat)
         if homography.mode:
             ctx.homography_check_async(_FB_API_IN, _FB_API_OUT, _FB_API_HOMOGRAPHY, nfeat)
+        if crowd.mode:
+            ctx.crowd_check_async(_FB_API_OUT, crowd_prev, _FB_API_CROWD, nfeat)
         if quality:
             ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
@@ -516,6 +538,9 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None):
     if homography.mode:                               # likewise
         from .backend import HOMOGRAPHY_DTYPE
         tc.homography_last = ctx.homography_download(_FB_API_HOMOGRAPHY) if nfeat else np.zeros(1, HOMOGRAPHY_DTYPE)[0]
+    if crowd.mode:                                    # one more download of 16 bytes per feature
+        from .backend import CROWD_DTYPE
+        tc.crowding_last = ctx.crowd_download(_FB_API_CROWD, nfeat) if nfeat else np.zeros(0, CROWD_DTYPE)
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

@@ -21,6 +21,7 @@ _FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality reco
 _FBM_TABLE = 48000           # tc.motionModelCheck: a parallel table of model records, five feature records per frame (below _FBQ_TABLE)
 _FBE_TABLE = 42000           # tc.epipolarCheck: a parallel table of epipolar model records, six feature records per frame (below _FBM_TABLE)
 _FBH_TABLE = 36000           # tc.homographyCheck: a parallel table of homography model records, six feature records per frame (below _FBE_TABLE)
+_FBC_TABLE = 30000           # tc.crowdingCheck: a parallel table of crowd records, laid out like the feature table (below _FBH_TABLE)
 _MAX_FRAMES = 65535 - _FB_ROW0
 _OPT_SELECT_AFFINE_STATE = 4
 
@@ -160,6 +161,11 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     (KLT_EPIPOLAR_OUTLIER); `ft.epipolar` holds one backend.EPIPOLAR_DTYPE record per frame, row 0 all zero.
     tc.homographyCheck = True: one homography check per frame in the same place (never with either of the two); the replacement pass refills
     the slots it flagged (KLT_HOMOGRAPHY_OUTLIER); `ft.homography` holds one backend.HOMOGRAPHY_DTYPE record per frame, row 0 all zero.
+    tc.crowdingCheck = True: one crowding check per frame behind the tracker and any of the checks above, in front of the quality launch and
+    of that frame's replacement pass, which refills the slots it flagged (KLT_CROWDED): after every frame no two live features are within
+    tc.crowding_min_distance - 1 px (None: tc.mindist) of each other.  `ft.crowd` is a [frames][features] array of backend.CROWD_DTYPE
+    records -- age (the consecutive frames the slot has been tracked: the older of two colliding tracks stays), winner, val -- row k
+    computed from row k - 1 and list row k, row 0 all zero.  Not together with the affine consistency check.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     from .params import fb_params_from_tc
@@ -178,6 +184,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     epipolar_params_from_tc(tc)          # (ValueError for a tc.epipolarCheck that is no bool, bad parameters, or another check beside it, likewise)
     from .params import homography_params_from_tc
     homography_params_from_tc(tc)        # (... and for tc.homographyCheck, likewise)
+    from .params import crowd_params_from_tc
+    crowd_params_from_tc(tc)             # (... and for tc.crowdingCheck, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -261,6 +269,22 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
             mtables.append(base)
         return mtables[ci] + 1 + off
 
+    from .params import crowd_params_from_tc
+    crowd = crowd_params_from_tc(tc, ncols, nrows)       # behind all of them: one crowding check per frame, its records into a table of their own
+    if crowd.mode:
+        ctx.set_crowd_params(crowd)
+    ctables = []
+
+    def crow_fb(k):
+        ci, off = divmod(k, chunk)
+        if ci == len(ctables):
+            base = _FBC_TABLE + ci * (chunk + 1)
+            ctx.featbuf_alloc(base, chunk * nFeatures)
+            for j in range(chunk):
+                ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
+            ctables.append(base)
+        return ctables[ci] + 1 + off
+
     workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
     # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
     # colour / float frames (the frame `img.convert("F")` would be, made by the helper threads: klt_upload_f32_async takes it from there)
@@ -342,6 +366,8 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
                     ctx.epipolar_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
                 if homography.mode:                  # likewise
                     ctx.homography_check_async(row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
+                if crowd.mode:                       # behind every other check; row j - 1 of its table in (row 0: no ages yet), row j out
+                    ctx.crowd_check_async(row_fb(j), crow_fb(j - 1) if j >= 2 else -1, crow_fb(j), nFeatures)
                 if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
                     ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
@@ -447,6 +473,16 @@ def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_inges
             ctx.featbuf_download_into(base, rec[lo:hi])
         ft.quality = rec.view(QUALITY_DTYPE)
         ft.quality[0] = 0                                        # nothing was tracked into the first frame
+    if crowd.mode:
+        from .backend import CROWD_DTYPE, FEAT_DTYPE
+        rec = np.zeros((nframes, nFeatures), FEAT_DTYPE)
+        for ci, base in enumerate(ctables):
+            lo = ci * chunk
+            hi = min(nframes, lo + chunk)
+            if hi > lo and nFeatures:
+                ctx.featbuf_download_into(base, rec[lo:hi])
+        ft.crowd = rec.view(CROWD_DTYPE)
+        ft.crowd[0] = 0                                          # nothing was tracked into the first frame
     if model.mode or epipolar.mode or homography.mode:
         from .backend import EPIPOLAR_DTYPE, FEAT_DTYPE, HOMOGRAPHY_DTYPE, MODEL_DTYPE
         dtype = HOMOGRAPHY_DTYPE if homography.mode else EPIPOLAR_DTYPE if epipolar.mode else MODEL_DTYPE
