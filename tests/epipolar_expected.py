@@ -37,20 +37,32 @@ def _pow2(field):
     return np.float64(struct.unpack("<d", struct.pack("<Q", field << 52))[0])
 
 
-def null9(A):
-    """the null vector of an 8x9 matrix by the rule's division-free elimination with full pivoting, or None"""
+def _traced(trace, event):
+    if trace is not None:
+        (trace if callable(trace) else trace.append)(event)
+
+
+def null9(A, trace=None):
+    """the null vector of an 8x9 matrix by the rule's division-free elimination with full pivoting, or None.  `trace` (a list or a
+    callback; it changes nothing of the result) gets one dict per step k: the pivot's column is the ninth (`pc8`), another entry of the
+    block holds the pivot's key (`tie`), rows / columns changed places (`row_swap`, `col_swap`), and `fail`: None, or why the step gave
+    up -- "zero", "subnormal" or "nonfinite"."""
     A = np.array(A, np.float64)
     assert A.shape == (8, 9)
     perm = list(range(9))
     with np.errstate(all="ignore"):
         for k in range(8):
-            best, br, bc = -1, k, k
+            best, br, bc, ties = -1, k, k, 0
             for i in range(k, 8):
                 for j in range(k, 9):
                     b = _abs_bits(A[i, j])
                     if b > best:                    # (rows, then columns, in increasing order: the first of the largest)
-                        best, br, bc = b, i, j
+                        best, br, bc, ties = b, i, j, 0
+                    elif b == best:
+                        ties += 1
             ef = best >> 52
+            _traced(trace, dict(k=k, pc8=bc == 8, tie=ties > 0, row_swap=br != k, col_swap=bc != k,
+                                fail=None if 0 < ef < 0x7FF else "nonfinite" if ef else "subnormal" if best else "zero"))
             if ef == 0 or ef == 0x7FF:
                 return None
             A[[k, br], :] = A[[br, k], :]

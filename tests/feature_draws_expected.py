@@ -632,9 +632,10 @@ def model_facts(c):
     return facts
 
 
-def model_differ(got_out, got_model, want_out, want_model, what):
-    """None, or what differs: every byte of the model record and of `out` (the lists hold NaN coordinates, and -0 is not +0)"""
-    got_model, want_model = np.asarray(got_model, MODEL_DTYPE).reshape(1), np.asarray(want_model, MODEL_DTYPE).reshape(1)
+def model_differ(got_out, got_model, want_out, want_model, what, dtype=MODEL_DTYPE):
+    """None, or what differs: every byte of the model record (`dtype`: the check's record) and of `out` (the lists hold NaN coordinates,
+    and -0 is not +0)"""
+    got_model, want_model = np.asarray(got_model, dtype).reshape(1), np.asarray(want_model, dtype).reshape(1)
     if got_model.tobytes() != want_model.tobytes():
         return "%s: model record differs: got %r, want %r" % (what, got_model[0], want_model[0])
     if len(got_out) != len(want_out):

@@ -7,6 +7,8 @@ bit for bit.
     python3 tests/fuzz/fuzz_parity.py [--trials 40] [--seed 1] [--max-pixels 400000] [--max-n 700] [--max-side 900]
 --light / --quality / --model: gain / bias tracking, track quality and the motion-model check on the draws of
 tests/feature_draws_expected.py, against the numpy restatements of their rules.
+--epipolar / --homography / --crowd: the epipolar, the homography and the crowding check on the draws of tests/check_draws_expected.py
+(the trial functions tests/test_gpu_check_draws.py runs on its fixed tables), trial k on draw seed * 100000 + k.
 --fb / --guess / --mask: the forward-backward check, the motion prior and the selection mask on the draws of tests/draws_expected.py (the
 trial functions tests/test_gpu_draws.py runs on its fixed seed table), trial k on draw seed * 100000 + k.
 --pyramid: the level-0 pyramid kernels on the draws of tests/pyramid_expected.py (the kernel first, then a batch of frames that reaches it;
@@ -424,6 +426,32 @@ def run_feature_draws_trials(a):
     ctx.close()
 
 
+def run_check_draws_trials(a):
+    """--epipolar / --homography / --crowd: the trial functions of tests/check_draws_expected.py on fresh draws"""
+    import check_draws_expected as cd
+    ctx = Context(0)
+    t0 = time.time()
+    for k in range(a.trials):
+        seed = a.seed * 100000 + k
+        if a.crowd:
+            c = cd.crowd_case(seed)
+            bad = cd.run_crowd_trial(ctx, c)
+            f = cd.crowd_facts(c)
+            stat = "side %d, %d x %d cells (%s), candidates %r, crowded %r" % (f["side"], f["gx"], f["gy"], f["scan"], f["candidates"], f["crowded"])
+            cd.crowd_case.cache_clear()
+        else:
+            rule = "epipolar" if a.epipolar else "homography"
+            c = cd.consensus_case(rule, seed)
+            bad = cd.run_consensus_trial(ctx, c)
+            stat = "; ".join("valid %d, m %d, flagged %d, best %d" % (f["valid"], f["m"], f["flagged"], f["best"]) for f in cd.consensus_facts(c))
+            cd.consensus_case.cache_clear()
+        print("trial %3d %s  %s  %s" % (k, "ok  " if not bad else "FAIL (%s)" % bad, c["t"], stat), flush=True)
+        if bad:
+            sys.exit(1)
+    print("%d trials identical in %.0f s" % (a.trials, time.time() - t0))
+    ctx.close()
+
+
 def run_pyramid_trials(a):
     """--pyramid: run_pyramid_trial of tests/pyramid_expected.py on fresh draws"""
     import pyramid_expected as pe
@@ -483,7 +511,12 @@ def main():
     ap.add_argument("--light", action="store_true", help="gain / bias tracking on the draws of tests/feature_draws_expected.py, against the rule's restatement")
     ap.add_argument("--quality", action="store_true", help="klt_track_quality* on the quality draws of tests/feature_draws_expected.py")
     ap.add_argument("--model", action="store_true", help="klt_motion_check* on the model draws of tests/feature_draws_expected.py")
+    ap.add_argument("--epipolar", action="store_true", help="klt_epipolar_check* on the epipolar draws of tests/check_draws_expected.py, against the rule's restatement")
+    ap.add_argument("--homography", action="store_true", help="klt_homography_check* on the homography draws of tests/check_draws_expected.py")
+    ap.add_argument("--crowd", action="store_true", help="klt_crowd_check* on the crowding draws of tests/check_draws_expected.py")
     a = ap.parse_args()
+    if a.epipolar or a.homography or a.crowd:
+        return run_check_draws_trials(a)
     if a.light or a.quality or a.model:
         return run_feature_draws_trials(a)
     if a.scores:

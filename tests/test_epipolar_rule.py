@@ -171,7 +171,8 @@ def test_no_model_leaves_out_untouched():
 def test_degenerate_geometry_flags_less_never_a_kept_hypothesis():
     """valid == 2 needs a hypothesis that passes null9 while the normal equations of its inliers lose rank EXACTLY.  Attempts: a planar
     scene, a pure rotation, exactly eight candidates, eight candidates repeated.  Rounding in the 45 sums keeps every pivot of the refit
-    away from zero: each gives valid 0 or 1 (DESIGN.md section 9h says so)."""
+    away from zero: each gives valid 0 or 1.  (Exact integer positions do reach valid 2: check_draws_expected.valid2_lists, DESIGN.md
+    section 9h.)"""
     rs = np.random.RandomState(8)
     n = 200
     x, y = rs.uniform(100, 1800, n), rs.uniform(100, 1000, n)

@@ -77,7 +77,8 @@ def test_the_parallax_scene_at_1080p(ctx):
 
 def test_every_outcome_and_the_asynchronous_call(ctx):
     """valid 0 (too few candidates; every hypothesis degenerate; a best score below min_inliers) and 1 through klt_epipolar_check_async
-    on resident lists (no input is known to reach valid 2: DESIGN.md section 9h); n = 0 enqueues nothing"""
+    on resident lists (valid 2, a refit that fails, takes exact integer positions: tests/test_gpu_check_draws.py, entry `valid2`);
+    n = 0 enqueues nothing"""
     rs = np.random.RandomState(9)
     fin64, fout64, _ = parallax_n(64, NCOLS, NROWS, seed=5)
     tin, tout = translation_lists(64, NCOLS, NROWS, 3)

@@ -45,11 +45,12 @@ def mixed_lists(n, seed):
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 9, 64, 65, 600, 8193])
 def test_kernels_equal_the_rule_across_counts(ctx, n):
     """n across the four picks, one wavefront, the 64 partials and several passes of the eight-wavefront stride (8193 > 4 * 512 * 4);
-    hypotheses 1, 4 and 5 (the wavefronts of a scoring workgroup) and 257 (past one pass of the argmax); min_inliers 4 so that n = 4 can
+    hypotheses 1, 4 and 5 (the wavefronts of a scoring workgroup), 257 (inside one pass of the decide kernel's 512-thread argmax), 513 and
+    1001 (past it: the strided loop of reduce_best_key takes a second trip); min_inliers 4 so that n = 4 can
     give a model and n = 3 none; every kind of non-candidate among the 600 and the 8193"""
     fin, fout = mixed_lists(n, seed=40 + n)
     seen = set()
-    for hyp in (1, 4, 5, 257):
+    for hyp in (1, 4, 5, 257, 513, 1001):
         kw = dict(hypotheses=hyp, seed=7 * hyp, min_inliers=4 if n < 64 else 8, max_error=1.0)
         ctx.set_homography_params(ncols=NCOLS, nrows=NROWS, **kw)
         want_out, want_model = homography_check_expected(fin, fout, NCOLS, NROWS, **kw)
@@ -79,7 +80,8 @@ def test_the_rotation_scene_at_1080p(ctx):
 
 def test_every_outcome_and_the_asynchronous_call(ctx):
     """valid 0 (too few candidates; every hypothesis singular; a best score below min_inliers) and 1 through klt_homography_check_async
-    on resident lists (no input is known to reach valid 2: DESIGN.md section 9i); collinear candidates; n = 0 enqueues nothing"""
+    on resident lists (valid 2, a refit that fails, takes exact integer positions: tests/test_gpu_check_draws.py, entry `valid2`);
+    collinear candidates; n = 0 enqueues nothing"""
     rs = np.random.RandomState(9)
     fin64, fout64, _ = rotation_n(64, NCOLS, NROWS, seed=5)
     k = np.arange(40)
