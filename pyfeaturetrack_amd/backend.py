@@ -47,18 +47,31 @@ REPLACING_SOME = 2
 # the reference-shaped API's tracker reads and writes its pinned record arrays in place (klt_featbuf_map_host); KLT_MAP_RECORDS=0 in
 # the environment goes back to one copy command each way
 MAP_RECORDS = _os.environ.get("KLT_MAP_RECORDS", "1") != "0"
-# feature buffers of the reference-shaped API (the library keeps 65530 .. 65532, 65534 and 65535 for itself: the staging buffers of its
-# synchronous entry points -- klt_track*, klt_select, klt_track_quality, klt_motion_check; 65533 is the API's selection list,
-# 60000 .. 65524 KLTTrackSequence's table rows)
-_FB_API_IN, _FB_API_OUT = 65526, 65527
+# Feature-buffer ids: every id the Python layer uses, and the ones the library keeps for itself, in this one table.
+_FB_LIBRARY = (65530, 65531, 65532, 65534, 65535)   # staging buffers of the library's synchronous entry points (klt_track*, klt_select, ...)
+_FB_API_SELECT = 65533               # the selection list of the reference-shaped API while its records are not mapped (MAP_RECORDS)
+_FB_API_IN, _FB_API_OUT = 65526, 65527               # the tracker's two lists in a KLTTrackFeatures call
 _FB_API_BACK = 65528                 # backward records of a forward-backward call of that API (device memory, read back on request)
 _FB_API_GUESS = 65529                # predicted positions of a KLTTrackFeatures(..., guess=) call
-_FB_API_MODEL = 53999                # the model record of a KLTTrackFeatures call with tc.motionModelCheck (48000 .. 53998: KLTTrackSequence's model rows)
-_FB_API_EPIPOLAR = 47999             # the model record of a KLTTrackFeatures call with tc.epipolarCheck (42000 .. 47998: KLTTrackSequence's epipolar rows)
-_FB_API_HOMOGRAPHY = 41999           # the model record of a KLTTrackFeatures call with tc.homographyCheck (36000 .. 41998: KLTTrackSequence's homography rows)
-_FB_API_CROWD = 35999                # crowd records of a KLTTrackFeatures call with tc.crowdingCheck (30000 .. 35998: KLTTrackSequence's crowd rows)
+_FB_GUESS = 65525                    # KLTTrackSequence: the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
+# KLTTrackSequence's record tables (trackSequence._RecordTable): chunk ci of a table is buffer base + ci * (FB_CHUNK + 1), its FB_CHUNK rows the
+# ids behind it.  The feature table ends the call at _MAX_FRAMES; the others follow its rows.
+FB_CHUNK = 64
+_FB_TABLE = 60000                    # the feature lists, one row per frame
+_FBQ_TABLE = 54000                   # tc.trackQuality: quality records
+_FBM_TABLE, _FBE_TABLE, _FBH_TABLE = 48000, 42000, 36000        # tc.motionModelCheck, tc.epipolarCheck, tc.homographyCheck: a model record per frame
+_FBC_TABLE = 30000                   # tc.crowdingCheck: crowd records
+_MAX_FRAMES = 65535 - (_FB_TABLE + 1)
+# ... and the buffers of the same records in a KLTTrackFeatures call: the last id below the next table up
+_FB_API_QUALITY, _FB_API_MODEL, _FB_API_EPIPOLAR, _FB_API_HOMOGRAPHY, _FB_API_CROWD = 59999, 53999, 47999, 41999, 35999
 _FB_API_CROWD_PREV = 29999           # ... and the ages the caller handed in (age=)
-_FB_API_QUALITY = 59999             # quality records of a KLTTrackFeatures call with tc.trackQuality (54000 .. 59998: KLTTrackSequence's quality rows)
+# no id of a table that has grown as far as it can is a single buffer or an id of another table, and all of them lie below 65535
+_ids = [base + i for base in (_FB_TABLE, _FBQ_TABLE, _FBM_TABLE, _FBE_TABLE, _FBH_TABLE, _FBC_TABLE)
+        for i in range(_MAX_FRAMES // (FB_CHUNK + 1) * (FB_CHUNK + 1))]
+assert max(_ids) < 65535 and len(set(_ids + list(_FB_LIBRARY + (
+    _FB_API_SELECT, _FB_API_IN, _FB_API_OUT, _FB_API_BACK, _FB_API_GUESS, _FB_GUESS, _FB_API_QUALITY, _FB_API_MODEL, _FB_API_EPIPOLAR,
+    _FB_API_HOMOGRAPHY, _FB_API_CROWD, _FB_API_CROWD_PREV)))) == len(_ids) + 17
+del _ids
 
 # The three consensus checks over feature lists (DESIGN.md "what a consensus check is made of"), one row each: everything params.py,
 # the Context methods below, KLTTrackFeatures and KLTTrackSequence know of a check.  The order counts: a check refuses to be switched on
@@ -76,16 +89,17 @@ ConsensusCheck.off = property(lambda k: k.choices[0] if k.choices is not None el
 CONSENSUS_CHECKS = (
     ConsensusCheck("model", "motion-model", "motion", "motionModelCheck", (None, "affine"), "model_",
                    dict(hypotheses=256, seed=0, min_inliers=8, max_error=1.0, min_area=1.0), 3, KltModelParams, KltMotionModel, MODEL_DTYPE, 5,
-                   _FB_API_MODEL, 48000, "model_last", "models", lambda record: model_summary(record)),
+                   _FB_API_MODEL, _FBM_TABLE, "model_last", "models", lambda record: model_summary(record)),
     ConsensusCheck("epipolar", "epipolar", "epipolar", "epipolarCheck", None, "epipolar_",
                    dict(hypotheses=512, seed=0, min_inliers=16, max_error=1.0), 8, KltEpipolarParams, KltEpipolarModel, EPIPOLAR_DTYPE, 6,
-                   _FB_API_EPIPOLAR, 42000, "epipolar_last", "epipolar", None),
+                   _FB_API_EPIPOLAR, _FBE_TABLE, "epipolar_last", "epipolar", None),
     ConsensusCheck("homography", "homography", "homography", "homographyCheck", None, "homography_",
                    dict(hypotheses=256, seed=0, min_inliers=8, max_error=1.0), 4, KltHomographyParams, KltHomographyModel, HOMOGRAPHY_DTYPE, 6,
-                   _FB_API_HOMOGRAPHY, 36000, "homography_last", "homography", None),
+                   _FB_API_HOMOGRAPHY, _FBH_TABLE, "homography_last", "homography", None),
 )
 _MODEL_CHECK, _EPIPOLAR_CHECK, _HOMOGRAPHY_CHECK = CONSENSUS_CHECKS
 assert all(k.dtype.itemsize == C.sizeof(k.model_type) == k.records * FEAT_DTYPE.itemsize for k in CONSENSUS_CHECKS)
+PostTrackTargets = collections.namedtuple("PostTrackTargets", "model crowd_prev crowd quality")       # (Context.post_track_async)
 
 
 def _dp(a):
@@ -562,7 +576,7 @@ class Context:
         select_complete.  With MAP_RECORDS (the default) the feature buffer IS that pinned array -- the kernels update it in place, no
         copy either way; otherwise the list goes up first."""
         if fb is None:
-            fb = _FB_API_IN if MAP_RECORDS else 65533
+            fb = _FB_API_IN if MAP_RECORDS else _FB_API_SELECT
         if MAP_RECORDS and fb == _FB_API_IN:
             self._map_records(n, _FB_API_IN, _FB_API_OUT)
         elif mode == REPLACING_SOME:
@@ -573,7 +587,7 @@ class Context:
         """Second half: waits for the selection (klt_select_finish); the records are host_records(n)[0] itself when the buffer is
         mapped, else they come back into host_records(n)[1] with one download."""
         if fb is None:
-            fb = _FB_API_IN if MAP_RECORDS else 65533
+            fb = _FB_API_IN if MAP_RECORDS else _FB_API_SELECT
         self._check(self._lib.klt_select_finish(self._h))
         if MAP_RECORDS and fb == _FB_API_IN:
             # klt_select_finish has waited for the parallel passes' last launch -- but the sorted serial walk (no candidates at all, an
@@ -612,19 +626,26 @@ class Context:
             self._map_records(n, fb_in, fb_out)
         elif upload:
             self._check(self._lib.klt_featbuf_upload_async(self._h, fb_in, self.host_records(n)[0].ctypes.data, n))
-        if guess is not None:
-            if upload:
-                self._check(self._lib.klt_featbuf_upload(self._h, _FB_API_GUESS, guess.ctypes.data, n))
+        if guess is not None and upload:
+            self._check(self._lib.klt_featbuf_upload(self._h, _FB_API_GUESS, guess.ctypes.data, n))
+        self.track_dispatch_async(slot1, slot2, fb_in, fb_out, n, state, fb_check, None if guess is None else _FB_API_GUESS, _FB_API_BACK)
+
+    def track_dispatch_async(self, slot1, slot2, fb_in, fb_out, n, state=None, fb_check=False, fb_guess=None, fb_back=None):
+        """The tracker entry point for (state, fb_check, fb_guess), enqueued: the motion prior's with guesses in `fb_guess`, the
+        forward-backward check's with `fb_check` (or both in one), the affine check's with a `state` (params.py refuses the two others
+        beside it), else the plain tracker.  `fb_back` (None: not passed): where the forward-backward check keeps its backward records."""
+        back = () if fb_back is None else (fb_back,)
+        if fb_guess is not None:
             if fb_check:
-                self._check(self._lib.klt_track_fb_guess_async(self._h, slot1, slot2, fb_in, _FB_API_GUESS, fb_out, n, _FB_API_BACK))
+                self.track_fb_guess_async(slot1, slot2, fb_in, fb_guess, fb_out, n, *back)
             else:
-                self._check(self._lib.klt_track_guess_async(self._h, slot1, slot2, fb_in, _FB_API_GUESS, fb_out, n))
-        elif fb_check:                       # forward-backward check (never with an affine state); the backward records stay on the device
-            self._check(self._lib.klt_track_fb_async(self._h, slot1, slot2, fb_in, fb_out, n, _FB_API_BACK))
+                self.track_guess_async(slot1, slot2, fb_in, fb_guess, fb_out, n)
+        elif fb_check:                       # stateless like the plain tracker: may be enqueued ahead and repeated
+            self.track_fb_async(slot1, slot2, fb_in, fb_out, n, *back)
         elif state is None:
-            self._check(self._lib.klt_track_async(self._h, slot1, slot2, fb_in, fb_out, n))
+            self.track_async(slot1, slot2, fb_in, fb_out, n)
         else:
-            self._check(self._lib.klt_track_affine_async(self._h, slot1, slot2, fb_in, fb_out, n, state))
+            self.track_affine_async(slot1, slot2, fb_in, fb_out, n, state)
 
     def track_mark(self):
         """Marks the main stream behind the tracker just enqueued: track_complete(marked=True) then waits for THAT point, and work
@@ -808,6 +829,37 @@ class Context:
     def quality_download(self, fb, n):
         """n quality records of feature buffer `fb` (what a track_quality*_async launch wrote there)"""
         return self.featbuf_download(fb, n).view(QUALITY_DTYPE)
+
+    # ------------------------------------------------ the post-track stages (params.post_track_from_tc): one chain
+    def set_post_track_params(self, stages):
+        """the parameters of every stage that is switched on, once for a call that enqueues the chain many times (KLTTrackSequence)"""
+        for k, p in stages.consensus:
+            self._consensus_set_params(k, p, {})
+        if stages.crowd is not None:
+            self.set_crowd_params(stages.crowd)
+
+    def post_track_async(self, stages, slot1, slot2, fb_in, fb_out, n, targets, set_params=False, ages=None):
+        """What follows a tracker launch from fb_in into fb_out, enqueued in THE order: the consensus check that is switched on -- it
+        rewrites fb_out in place --, then the crowding check on fb_out, then the quality launch: a record that either check flagged is
+        simply unmeasured.  A repeated tracker is followed by the whole chain again.  `targets` (PostTrackTargets, or anything with its
+        attributes: each is read when its stage is enqueued, and only then) names the buffers written: model (None: the check's own
+        buffer of a KLTTrackFeatures call), crowd_prev (the crowd records of the step before, -1: none), crowd, quality.  `set_params`:
+        each stage's parameters are set directly in front of its launch (KLTTrackFeatures: one or two chains per call); `ages`: crowd
+        records that go up into targets.crowd_prev first."""
+        for k, p in stages.consensus:
+            if set_params:
+                self._consensus_set_params(k, p, {})
+            fb_model = targets.model
+            self._consensus_async(k, fb_in, fb_out, k.fb_api if fb_model is None else fb_model, n)
+        if stages.crowd is not None:
+            if set_params:
+                self.set_crowd_params(stages.crowd)
+            fb_prev = targets.crowd_prev
+            if ages is not None:
+                self.featbuf_upload(fb_prev, ages)
+            self.crowd_check_async(fb_out, fb_prev, targets.crowd, n)
+        if stages.quality:
+            self.track_quality_async(slot1, slot2, fb_in, fb_out, targets.quality, n)
 
     # ------------------------------------------------ the consensus checks (a row of CONSENSUS_CHECKS each): one implementation
     def _consensus_set_params(self, k, p, kw):

@@ -1,4 +1,6 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
+import collections
+
 import numpy as np
 
 from ._abi import KltAffineParams, KltCrowdParams, KltFbParams, KltLightParams, KltParams
@@ -107,7 +109,6 @@ def consensus_params_from_tc(k, tc, ncols=None, nrows=None):
     device work -- for a switch of another value, for the check together with a check of an earlier row (one consensus check per pair)
     or with tc.affineConsistencyCheck >= 0 (that check keeps per-feature state keyed on loss), and for parameters klt_set_*_params would
     refuse."""
-    from .backend import CONSENSUS_CHECKS
     value = getattr(tc, k.switch, k.off)
     if k.choices is not None:
         if not isinstance(value, (str, type(None))) or value not in k.choices:
@@ -119,6 +120,7 @@ def consensus_params_from_tc(k, tc, ncols=None, nrows=None):
     p.ncols, p.nrows = int(ncols or 0), int(nrows or 0)
     values = dict(k.defaults)
     if p.mode:
+        from .backend import CONSENSUS_CHECKS
         for other in CONSENSUS_CHECKS[:CONSENSUS_CHECKS.index(k)]:
             theirs = getattr(tc, other.switch, other.off)
             if (theirs is not None) if other.choices is not None else theirs:
@@ -196,6 +198,26 @@ def crowd_params_from_tc(tc, ncols=None, nrows=None):
         raise ValueError("the crowding check takes frames of 1 .. 65535 columns and rows")
     cp.min_distance = int(dist)
     return cp
+
+
+PostTrack = collections.namedtuple("PostTrack", "consensus crowd quality")
+NO_POST_TRACK = PostTrack((), None, False)
+
+
+def post_track_from_tc(tc, ncols=None, nrows=None):
+    """What follows every tracker launch of a call on this tracking context, as Context.post_track_async enqueues it (DESIGN.md "what a
+    post-track stage is made of"): `consensus` ((row of backend.CONSENSUS_CHECKS, its parameter struct), ...) of the checks that are
+    switched on (never two), `crowd` the klt_crowd_params of tc.crowdingCheck or None, `quality` tc.trackQuality.  Every ValueError of
+    consensus_params_from_tc (the rows in their order) and then of crowd_params_from_tc is raised here: without a frame size this is
+    the refusal pass an entry point runs before it touches the device, with one what it then uses."""
+    from .backend import CONSENSUS_CHECKS
+    consensus = ()
+    for k in CONSENSUS_CHECKS:
+        p = consensus_params_from_tc(k, tc, ncols, nrows)
+        if p.mode:
+            consensus += ((k, p),)
+    crowd = crowd_params_from_tc(tc, ncols, nrows)
+    return PostTrack(consensus, crowd if crowd.mode else None, bool(getattr(tc, "trackQuality", False)))
 
 
 def age_records(age, n):

@@ -11,8 +11,10 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import age_records, consensus_params_from_tc, crowd_params_from_tc, fb_params_from_tc, guess_records, light_params_from_tc
+from .params import age_records, fb_params_from_tc, guess_records, light_params_from_tc, post_track_from_tc
 from .backend import context_of, default_context  # noqa: F401
+from .backend import (CROWD_DTYPE, FEAT_DTYPE, QUALITY_DTYPE, PostTrackTargets, _FB_API_BACK, _FB_API_CROWD, _FB_API_CROWD_PREV, _FB_API_IN,
+                      _FB_API_OUT, _FB_API_QUALITY)
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
 from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
 from .selectGoodFeatures import _fix_window, _image_size, _slots_of, features_to_array, image_to_array
@@ -172,7 +174,6 @@ class _BackRecords:
 
     def _records(self):
         if self._rec is None:
-            from .backend import _FB_API_BACK
             if self._ctx.__dict__.get("_fb_back_serial") != self._serial:
                 raise KltBackendError("the backward records of this call were replaced by a later call with forwardBackwardCheck")
             with self._ctx.lock:
@@ -425,10 +426,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     fb_params_from_tc(tc)                             # (ValueError for the forward-backward and the affine check together, before any device work)
     light_params_from_tc(tc, guess=guess is not None)      # (ValueError for lightingCompensation with a check, a prior or a guess, likewise)
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
-    from .backend import CONSENSUS_CHECKS
-    for k in CONSENSUS_CHECKS:                        # (ValueError for a switch of a consensus check that is none, bad parameters, or another
-        consensus_params_from_tc(k, tc)               # check or the affine check beside it, likewise)
-    crowd_params_from_tc(tc)                          # (... and for tc.crowdingCheck, likewise)
+    post_track_from_tc(tc)                            # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, likewise)
     age = age_records(age, len(featurelist))          # (ValueError for an `age` of another shape or kind, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
@@ -438,13 +436,20 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
         print("\n\t{0} features successfully tracked.".format(KLTCountRemainingFeatures(featurelist)))
 
 
-def _consensus_enqueue(ctx, k, params, nfeat):
-    """the consensus check `k` (a row of backend.CONSENSUS_CHECKS) behind the tracker of a KLTTrackFeatures call, if `params` switch it on"""
-    if params.mode:
-        from .backend import _FB_API_IN, _FB_API_OUT
-        ctx._consensus_set_params(k, params, {})
-        ctx._consensus_async(k, _FB_API_IN, _FB_API_OUT, k.fb_api, nfeat)
-    return bool(params.mode)
+_TARGETS = PostTrackTargets(None, -1, _FB_API_CROWD, _FB_API_QUALITY)      # where the post-track stages of a call write; with `age=` as well:
+_TARGETS_WITH_AGES = _TARGETS._replace(crowd_prev=_FB_API_CROWD_PREV)
+
+
+def _post_track_results(ctx, tc, stages, nfeat):
+    """what the post-track stages of a call leave on the tracking context: one more download each (16 bytes per feature; 80 or 96 bytes
+    for a model record), or zeros when the list is empty and nothing was launched"""
+    if stages.quality:
+        tc.quality_last = ctx.quality_download(_FB_API_QUALITY, nfeat) if nfeat else np.zeros(0, QUALITY_DTYPE)
+    for k, _ in stages.consensus:
+        record = ctx._consensus_download(k, k.fb_api) if nfeat else np.zeros(1, k.dtype)[0]
+        setattr(tc, k.last, k.summary(record) if k.summary else record)
+    if stages.crowd is not None:
+        tc.crowding_last = ctx.crowd_download(_FB_API_CROWD, nfeat) if nfeat else np.zeros(0, CROWD_DTYPE)
 
 
 def _track_locked(ctx, tc, img1, img2, featurelist, guess=None, age=None):
@@ -465,28 +470,14 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None, age=None):
         # by the feature list object.
         state = _affine_state_of(tc, ctx, featurelist)
     ctx.track_enqueue(s1, s2, nfeat, state, fb_check=fb_check, guess=guess)
-    # tc.motionModelCheck, tc.epipolarCheck, tc.homographyCheck (never two of them): three more launches behind the tracker (and its
-    # forward-backward check), on the tracker's own two feature buffers -- the output list is rewritten in place -- with a model record of
-    # the check's own, and in front of the quality launch: a flagged record is then simply unmeasured
-    from .backend import CONSENSUS_CHECKS, _FB_API_IN, _FB_API_OUT
-    consensus = [k for k in CONSENSUS_CHECKS if _consensus_enqueue(ctx, k, consensus_params_from_tc(k, tc, ncols, nrows), nfeat)]
-    # tc.crowdingCheck: behind all of them and in front of the quality launch (a crowded record is then simply unmeasured), on the tracker's
-    # output buffer; the ages the caller handed in go up first, as crowd records
-    crowd = crowd_params_from_tc(tc, ncols, nrows)
-    crowd_prev = -1
-    if crowd.mode:
-        from .backend import FEAT_DTYPE, _FB_API_OUT, _FB_API_CROWD, _FB_API_CROWD_PREV
-        ctx.set_crowd_params(crowd)
-        if age is not None and nfeat:
-            ctx.featbuf_upload(_FB_API_CROWD_PREV, age.view(FEAT_DTYPE).reshape(nfeat))
-            crowd_prev = _FB_API_CROWD_PREV
-        ctx.crowd_check_async(_FB_API_OUT, crowd_prev, _FB_API_CROWD, nfeat)
-    # tc.trackQuality: one more launch behind the tracker (and behind its forward-backward or affine check), on the records the list held
-    # on entry and the ones it gets -- the feature buffers the tracker just read and wrote
-    quality = bool(getattr(tc, "trackQuality", False))
-    if quality:
-        from .backend import _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY
-        ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
+    # The post-track stages (Context.post_track_async has their order).  tc.motionModelCheck, tc.epipolarCheck, tc.homographyCheck (never two of
+    # them): three more launches behind the tracker (and its forward-backward check), on the tracker's own two feature buffers -- the output
+    # list is rewritten in place -- with a model record of the check's own.  tc.crowdingCheck: on the tracker's output buffer; the ages the
+    # caller handed in go up first, as crowd records.  tc.trackQuality: one more launch on the two feature buffers the tracker just read and wrote.
+    stages = post_track_from_tc(tc, ncols, nrows)
+    ages = age.view(FEAT_DTYPE).reshape(nfeat) if stages.crowd is not None and age is not None and nfeat else None
+    chain = (stages, s1, s2, _FB_API_IN, _FB_API_OUT, nfeat, _TARGETS if ages is None else _TARGETS_WITH_AGES)
+    ctx.post_track_async(*chain, set_params=True, ages=ages)
     # The device is tracking; now every byte of the frames that were taken as resident is compared with what their slots were
     # filled from.  One that differs (the same array edited in place off the lattice, ...) is sent and built now and the tracker
     # runs again on the same input records: the records that come back are those of the last launch.
@@ -497,12 +488,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None, age=None):
             again = True
     if again:
         ctx.track_enqueue(s1, s2, nfeat, state, upload=False, fb_check=fb_check, guess=guess)
-        for k in consensus:
-            ctx._consensus_async(k, _FB_API_IN, _FB_API_OUT, k.fb_api, nfeat)
-        if crowd.mode:
-            ctx.crowd_check_async(_FB_API_OUT, crowd_prev, _FB_API_CROWD, nfeat)
-        if quality:
-            ctx.track_quality_async(s1, s2, _FB_API_IN, _FB_API_OUT, _FB_API_QUALITY, nfeat)
+        ctx.post_track_async(*chain)
     # A tracking context whose last KLTTrackFeatures call was followed by KLTReplaceLostFeatures (the loop of a video script): the
     # list-independent half of that replacement -- summed-area tables and eigenvalue keys of frame 2's level 0, 50 us at 1080p -- is
     # enqueued now, behind the tracker, and runs while the host moves the columns and finds its way into the replacement call
@@ -517,15 +503,7 @@ def _track_locked(ctx, tc, img1, img2, featurelist, guess=None, age=None):
             except KltBackendError:                         # (an optimisation only: the replacement scores the frame itself then)
                 pass
     fl_out = ctx.track_complete(nfeat, marked=marked)
-    if quality:                                       # one more download of 16 bytes per feature
-        from .backend import QUALITY_DTYPE
-        tc.quality_last = ctx.quality_download(_FB_API_QUALITY, nfeat) if nfeat else np.zeros(0, QUALITY_DTYPE)
-    for k in consensus:                               # one more download of 80 or 96 bytes
-        record = ctx._consensus_download(k, k.fb_api) if nfeat else np.zeros(1, k.dtype)[0]
-        setattr(tc, k.last, k.summary(record) if k.summary else record)
-    if crowd.mode:                                    # one more download of 16 bytes per feature
-        from .backend import CROWD_DTYPE
-        tc.crowding_last = ctx.crowd_download(_FB_API_CROWD, nfeat) if nfeat else np.zeros(0, CROWD_DTYPE)
+    _post_track_results(ctx, tc, stages, nfeat)
     if fb_check:
         tc.fb_back = _BackRecords(ctx, nfeat)         # the backward records, fetched if somebody looks (nothing is copied otherwise)
     if affine:

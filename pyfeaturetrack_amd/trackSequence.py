@@ -8,28 +8,23 @@ are bit-identical to the per-frame host API loop, which the GPU tests check.
 """
 from __future__ import print_function
 
+import contextlib
+
 import numpy as np
 
-from .backend import REPLACING_SOME, SELECTING_ALL, context_of
+from ._frames import cache_of, pixels_of
+from .backend import (CROWD_DTYPE, FB_CHUNK, FEAT_DTYPE, QUALITY_DTYPE, REPLACING_SOME, SELECTING_ALL, Context, context_of,
+                      _FB_GUESS, _FB_TABLE, _FBC_TABLE, _FBQ_TABLE, _MAX_FRAMES)       # (backend.py has the table of feature-buffer ids)
 from .klt import KLT_FeatureTable
+from .params import (NO_POST_TRACK, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc,
+                     select_grid_from_tc, selection_mask_from_tc)
 from .selectGoodFeatures import _fix_window, _slots_of
 
-_FB_TABLE = 60000            # feature-buffer ids used by this module: the table, then one view per frame
-_FB_ROW0 = 60001
-_FB_GUESS = 65525            # ... and the constant-velocity guesses of the step being enqueued (tc.motionPrediction)
-_FBQ_TABLE = 54000           # tc.trackQuality: a parallel table of quality records, laid out like the feature table (below _FB_TABLE)
-# (48000, 42000, 36000: tc.motionModelCheck, tc.epipolarCheck, tc.homographyCheck -- a parallel table of model records each, five or six
-# feature records per frame: fb_table of backend.CONSENSUS_CHECKS)
-_FBC_TABLE = 30000           # tc.crowdingCheck: a parallel table of crowd records, laid out like the feature table (below those)
-_MAX_FRAMES = 65535 - _FB_ROW0
+_track_dispatch_async, _post_track_async = Context.track_dispatch_async, Context.post_track_async
 _OPT_SELECT_AFFINE_STATE = 4
-
-
 _OPT_BUILD_STREAM = 15
 _OPT_COPY_STREAMS = 20
 SEQUENCE_COPY_STREAMS = 1        # copy streams a sequence call's uploads use (the default of a context, two, is for the two frames of a pair)
-
-
 STAGER_WORKERS = 0                       # 0: by frame size (below); 1 / 2 / ...: that many helper threads
 STAGER_THREADS_FROM_BYTES = 4 << 20      # frames of this size and above are staged by two helper threads (one core copies a 4K frame in
                                          # 0.26 ms -- longer than the GPU needs for it; tools/stage_copy_probe.py)
@@ -167,328 +162,278 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     computed from row k - 1 and list row k, row 0 all zero.  Not together with the affine consistency check.
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
-    from .params import fb_params_from_tc
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
-    from .params import selection_mask_from_tc
     selection_mask_from_tc(tc)           # (TypeError for a tc.selectionMask of an unknown kind, likewise)
-    from .params import select_grid_from_tc
     grid = select_grid_from_tc(tc)       # (TypeError / ValueError for a tc.selectionGrid that is no (cell_width, cell_height, max_per_cell), likewise)
-    from .params import motion_prediction_from_tc
     motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
-    from .params import light_params_from_tc
     light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
-    from .backend import CONSENSUS_CHECKS
-    from .params import consensus_params_from_tc
-    for k in CONSENSUS_CHECKS:           # (ValueError for a switch of a consensus check that is none, bad parameters, or another check or
-        consensus_params_from_tc(k, tc)  # the affine check beside it, likewise)
-    from .params import crowd_params_from_tc
-    crowd_params_from_tc(tc)             # (... and for tc.crowdingCheck, likewise)
+    post_track_from_tc(tc)               # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, or a check beside one, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
         return _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid)
 
 
-def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid=None):
-    frames = iter(frames)
-    _fix_window(tc)
-    from ._frames import cache_of
-    cache_of(tc).keep_all_handles()     # pyramid handles somebody kept (ComputeImagePyramids, tc.pyramid_last) fetch their planes first
-    ctx.configure(tc)
-    s = list(_slots_of(tc))              # ring of three frame slots (the third is otherwise the per-frame API's selection slot)
-    cache_of(tc).forget()               # this call fills the slots itself: what the per-frame API remembers of them is void
-    ring = 3 if prefetch else 2
-    from ._frames import pixels_of
-    first = pixels_of(next(frames))
-    rows = [first]
-    nrows, ncols = first.shape
-    from .params import selection_mask_from_tc
-    # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
-    ctx.sync_select_mask(selection_mask_from_tc(tc, ncols, nrows))
-    ctx.sync_select_grid(grid)          # tc.selectionGrid, read when the call started: the first selection and every replacement
-    affine = tc.affineConsistencyCheck >= 0
-    from .params import fb_params_from_tc
-    fb_check = bool(fb_params_from_tc(tc).enabled) and not affine       # forward-backward check in every tracker step
-    from .params import motion_prediction_from_tc
-    predict = motion_prediction_from_tc(tc) == "constant_velocity"      # a motion prior for every tracker step but the first
+class _RecordTable:
+    """One device-side table of a sequence call: `records` feature records per frame, row k a feature-buffer view of its own.  The frames are
+    consumed lazily, so the table grows in chunks of `chunk` rows (a generator of unknown length works): chunk ci is feature buffer
+    base + ci * (chunk + 1), allocated with its `chunk` views -- the ids behind it -- when a row of it is first asked for.  `limit`: the call is
+    refused when the table would outgrow that many ids (the feature table's); `skip_empty`: a table of rows without records is not downloaded."""
 
-    # frames are consumed lazily; the table grows in chunks so that a generator of unknown length works
-    chunk = 64
-    tables = []                         # [(fb_table, first_row, n_rows)]
+    def __init__(self, ctx, base, records, chunk=FB_CHUNK, limit=None, skip_empty=False):
+        self.ctx, self.base, self.records, self.chunk, self.limit, self.skip_empty = ctx, base, records, chunk, limit, skip_empty
+        self.chunks = []                     # the chunks' feature buffers
 
-    def row_fb(k):
-        ci, off = divmod(k, chunk)
-        if ci == len(tables):
-            if ci * (chunk + 1) + chunk + 1 > _MAX_FRAMES:
+    def row(self, k):
+        ci, off = divmod(k, self.chunk)
+        if ci == len(self.chunks):
+            chunk, records, base = self.chunk, self.records, self.base + ci * (self.chunk + 1)
+            if self.limit is not None and ci * (chunk + 1) + chunk + 1 > self.limit:
                 raise ValueError("sequence too long for one call")
-            base = _FB_TABLE + ci * (chunk + 1)
-            ctx.featbuf_alloc(base, chunk * nFeatures)
+            self.ctx.featbuf_alloc(base, chunk * records)
             for j in range(chunk):
-                ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
-            tables.append(base)
-        return tables[ci] + 1 + off
+                self.ctx.featbuf_view(base + 1 + j, base, j * records, records)
+            self.chunks.append(base)
+        return self.chunks[ci] + 1 + off
 
-    quality = bool(getattr(tc, "trackQuality", False))   # one quality launch behind every tracker launch, into a table of its own
-    qtables = []
+    def download(self, nframes, out=None):
+        """the (nframes, records) array of klt_feat records (`out`, or a new one: rows nobody wrote are zero).  A chunk exists only once
+        a row of it was asked for, and rows are asked for only for frames that arrived: every chunk has rows to fetch."""
+        rec = np.zeros((nframes, self.records), FEAT_DTYPE) if out is None else out
+        for ci, base in enumerate(self.chunks):
+            lo = ci * self.chunk
+            hi = min(nframes, lo + self.chunk)
+            if hi > lo and (self.records or not self.skip_empty):
+                self.ctx.featbuf_download_into(base, rec[lo:hi])      # rows lo .. hi-1 are contiguous in the table: no staging copy
+        return rec
 
-    def qrow_fb(k):
-        ci, off = divmod(k, chunk)
-        if ci == len(qtables):
-            base = _FBQ_TABLE + ci * (chunk + 1)
-            ctx.featbuf_alloc(base, chunk * nFeatures)
-            for j in range(chunk):
-                ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
-            qtables.append(base)
-        return qtables[ci] + 1 + off
 
-    from .backend import CONSENSUS_CHECKS
-    from .params import consensus_params_from_tc
-    check = None                         # the consensus check that is switched on (never two of them): the same check behind every tracker
-    for k in CONSENSUS_CHECKS:           # launch, its record into a table of its own, k.records feature records per frame
-        consensus = consensus_params_from_tc(k, tc, ncols, nrows)
-        if consensus.mode:
-            ctx._consensus_set_params(k, consensus, {})
-            check = k
-    mtables = []
+class _Sequence:
+    """The state of one KLTTrackSequence call, made by its set-up: the frame slots, the post-track stages and their tables, the staging
+    buffers and the helper threads.  The drivers below enqueue the steps, and `table` brings the result back."""
 
-    def mrow_fb(k):
-        ci, off = divmod(k, chunk)
-        if ci == len(mtables):
-            base = check.fb_table + ci * (chunk + 1)
-            ctx.featbuf_alloc(base, chunk * check.records)
-            for j in range(chunk):
-                ctx.featbuf_view(base + 1 + j, base, j * check.records, check.records)
-            mtables.append(base)
-        return mtables[ci] + 1 + off
+    def __init__(self, ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid):
+        self.ctx, self.tc, self.frames, self.n, self.replace_lost, self.prefetch = ctx, tc, iter(frames), nFeatures, replace_lost, prefetch
+        _fix_window(tc)
+        cache_of(tc).keep_all_handles()     # pyramid handles somebody kept (ComputeImagePyramids, tc.pyramid_last) fetch their planes first
+        ctx.configure(tc)
+        self.s = list(_slots_of(tc))        # ring of three frame slots (the third is otherwise the per-frame API's selection slot)
+        cache_of(tc).forget()               # this call fills the slots itself: what the per-frame API remembers of them is void
+        self.ring = 3 if prefetch else 2
+        first = pixels_of(next(self.frames))
+        self.nrows, self.ncols = first.shape
+        # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
+        ctx.sync_select_mask(selection_mask_from_tc(tc, self.ncols, self.nrows))
+        ctx.sync_select_grid(grid)          # tc.selectionGrid, read when the call started: the first selection and every replacement
+        self.affine = tc.affineConsistencyCheck >= 0
+        self.fb_check = bool(fb_params_from_tc(tc).enabled) and not self.affine      # forward-backward check in every tracker step
+        self.predict = motion_prediction_from_tc(tc) == "constant_velocity"          # a motion prior for every tracker step but the first
+        # The tracker of frame k + 1 only READS the list that frame k's replacement completes, so it is enqueued before the host looks at
+        # that replacement's outcome (klt_select_finish): the GPU has it queued while the host turns around.  In the rare case that the
+        # look makes the selection rewrite the list, the tracker is enqueued once more.  Not with the affine check: it updates the
+        # per-feature state in place, so its launch cannot simply be repeated.
+        self.ahead = prefetch and replace_lost and not self.affine
+        # the post-track stages: the same chain behind every tracker launch, each stage's records into a table of its own, laid out like the feature table
+        self.stages = post_track_from_tc(tc, self.ncols, self.nrows)
+        Context.set_post_track_params(ctx, self.stages)         # (as a plain function, like the two in `track`)
+        self.check = self.stages.consensus[-1][0] if self.stages.consensus else None
+        self.rows = _RecordTable(ctx, _FB_TABLE, nFeatures, limit=_MAX_FRAMES)
+        self.quality_rows = _RecordTable(ctx, _FBQ_TABLE, nFeatures)
+        self.model_rows = _RecordTable(ctx, self.check.fb_table, self.check.records) if self.check else None
+        self.crowd_rows = _RecordTable(ctx, _FBC_TABLE, nFeatures, skip_empty=True)
+        workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
+        # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
+        # colour / float frames (the frame `img.convert("F")` would be, made by the helper threads: klt_upload_f32_async takes it from there)
+        self.stage_key = ((self.nrows, self.ncols), self.ring + 2 + workers, first.dtype)
+        stage = ctx.staging(*self.stage_key) if async_ingest and first.dtype in (np.uint8, np.float32) else None
+        self.in_flight, self.stager, self.k = [], None, 0       # staging buffers whose copy may still be running; the last frame whose step was enqueued
+        self.ingest(self.s[0], first, 0)
+        ctx.build_pyramids(self.s[0], sync=False)
+        # the initial selection follows KLTSelectGoodFeatures: the smoothed level-0 image when tc.smoothBeforeSelecting, the raw
+        # frame otherwise (selectGoodFeatures.py:183-197) -- level 0 of the pyramid is always smoothed
+        ctx.select_async(self.s[0], SELECTING_ALL, bool(tc.smoothBeforeSelecting), self.rows.row(0), nFeatures)
+        self.state = ctx.take_affine_state() if self.affine else None
+        if self.affine:
+            ctx.affine_alloc(self.state, nFeatures)
+        if stage is not None:
+            self.stager = _FrameStager(self.frames, stage, (self.nrows, self.ncols), workers=workers)
 
-    from .params import crowd_params_from_tc
-    crowd = crowd_params_from_tc(tc, ncols, nrows)       # behind all of them: one crowding check per frame, its records into a table of their own
-    if crowd.mode:
-        ctx.set_crowd_params(crowd)
-    ctables = []
-
-    def crow_fb(k):
-        ci, off = divmod(k, chunk)
-        if ci == len(ctables):
-            base = _FBC_TABLE + ci * (chunk + 1)
-            ctx.featbuf_alloc(base, chunk * nFeatures)
-            for j in range(chunk):
-                ctx.featbuf_view(base + 1 + j, base, j * nFeatures, nFeatures)
-            ctables.append(base)
-        return ctables[ci] + 1 + off
-
-    workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
-    # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
-    # colour / float frames (the frame `img.convert("F")` would be, made by the helper threads: klt_upload_f32_async takes it from there)
-    stage_key = ((nrows, ncols), ring + 2 + workers, first.dtype)
-    stage = ctx.staging(*stage_key) if async_ingest and first.dtype in (np.uint8, np.float32) else None
-    in_flight = []                          # staging buffer whose host-to-device copy may still be running
-
-    def ingest(slot, img, k, staged=False, wait=True):
-        if img.shape != (nrows, ncols):
+    def ingest(self, slot, img, k, staged=False, wait=True):
+        if img.shape != (self.nrows, self.ncols):
             from .error import KLTError
             KLTError("(KLTTrackSequence) Size of incoming image ({0} by {1}) is different from size of previous image "
-                     "({2} by {3})".format(img.shape[1], img.shape[0], ncols, nrows))
+                     "({2} by {3})".format(img.shape[1], img.shape[0], self.ncols, self.nrows))
         if staged:
             if wait:
-                ctx.upload_wait()           # the previous frame's copy has finished (kernels keep running): its buffer goes back
-                while in_flight:
-                    stager.release(in_flight.pop()[1])
-            ctx.upload_async(slot, img)
-            in_flight.append((k, img))
+                self.ctx.upload_wait()      # the previous frame's copy has finished (kernels keep running): its buffer goes back
+                while self.in_flight:
+                    self.stager.release(self.in_flight.pop()[1])
+            self.ctx.upload_async(slot, img)
+            self.in_flight.append((k, img))
         else:
-            ctx.upload(slot, img)
+            self.ctx.upload(slot, img)
 
-    def landed(k):
+    def landed(self, k):
         """frame k's selection has completed, so its pyramid was built, so its copy has left the staging buffer: the buffer goes back
         (no host wait for the copy streams -- klt_upload_wait costs the host the rest of the copy)"""
-        while in_flight and in_flight[0][0] <= k:
-            stager.release(in_flight.pop(0)[1])
+        while self.in_flight and self.in_flight[0][0] <= k:
+            self.stager.release(self.in_flight.pop(0)[1])
 
-    ingest(s[0], first, 0)
-    ctx.build_pyramids(s[0], sync=False)
-    # the initial selection follows KLTSelectGoodFeatures: the smoothed level-0 image when tc.smoothBeforeSelecting, the raw
-    # frame otherwise (selectGoodFeatures.py:183-197) -- level 0 of the pyramid is always smoothed
-    ctx.select_async(s[0], SELECTING_ALL, bool(tc.smoothBeforeSelecting), row_fb(0), nFeatures)
-    state = None
-    if affine:
-        state = ctx.take_affine_state()
-        ctx.affine_alloc(state, nFeatures)
-    k = 0
-    stager = _FrameStager(frames, stage, (nrows, ncols), workers=workers) if stage is not None else None
-    try:
-        if affine:
-            ctx.set_option(_OPT_SELECT_AFFINE_STATE, state)
-        if prefetch:
+    def next_frame(self):                    # ("staged", pinned buffer) | ("raw", array) | None at the end
+        if self.stager is not None:
+            item = self.stager.next()
+            return item if item[0] is not None else None
+        img = next(self.frames, None)
+        return None if img is None else ("raw", pixels_of(img))
+
+    def stage_frame(self, k, item):          # upload + pyramid build of frame k (enqueued only)
+        self.ingest(self.s[k % self.ring], item[1], k, staged=item[0] == "staged")
+        self.build(k)
+
+    def send(self, j):                       # frame j leaves for its slot, if there is one (no wait for the copy before it)
+        item = self.next_frame()
+        if item is not None:
+            self.ingest(self.s[j % self.ring], item[1], j, staged=item[0] == "staged", wait=False)
+        return item is not None
+
+    def build(self, j):
+        ctx, slot = self.ctx, self.s[j % self.ring]
+        ctx.build_pyramids(slot, sync=False)
+        if self.replace_lost and self.prefetch:      # ... and the list-independent half of its replacement pass, on the same stream
+            ctx.select_prepare(slot)
+
+    def track(self, j):
+        """frame j - 1 -> j: row j - 1 of the table in, row j out; behind the tracker -- wherever it goes, a repeated one included -- the
+        post-track stages, in front of frame j's replacement pass.  (The two Context methods are called as plain functions: what stands
+        in for a context in the tests has the entry points alone.)"""
+        ctx, n, row = self.ctx, self.n, self.rows.row
+        cur, prev = self.s[j % self.ring], self.s[(j - 1) % self.ring]
+        fb_guess = None
+        if self.predict and j >= 2:          # guesses from rows j - 2 and j - 1, on the same stream in front of the tracker that reads them
+            ctx.predict_cv_async(row(j - 2), row(j - 1), _FB_GUESS, n)
+            fb_guess = _FB_GUESS
+        fb_in, fb_out = row(j - 1), row(j)
+        _track_dispatch_async(ctx, prev, cur, fb_in, fb_out, n, self.state, self.fb_check, fb_guess)
+        if self.stages != NO_POST_TRACK:
+            self.j = j
+            _post_track_async(ctx, self.stages, prev, cur, fb_in, fb_out, n, self)
+
+    # Context.post_track_async's `targets` for step `j`: row j of each stage's table (a chunk of a table is allocated when its stage first
+    # asks for a row of it); the crowding check reads row j - 1 of its own table (row 0: no ages yet)
+    model = property(lambda q: q.model_rows.row(q.j))
+    crowd_prev = property(lambda q: q.crowd_rows.row(q.j - 1) if q.j >= 2 else -1)
+    crowd = property(lambda q: q.crowd_rows.row(q.j))
+    quality = property(lambda q: q.quality_rows.row(q.j))
+
+    def open(self, stack):
+        """Sets the options of the call; `stack` (an ExitStack) undoes them when it closes, and ends what the call started, in the order
+        written here -- every step on its own: a failing one must not skip the rest (the options live on the shared default context)."""
+        ctx = self.ctx
+        steps = [ctx.select_finish, self.close_stager, lambda: ctx.set_option(_OPT_COPY_STREAMS, 2)]      # (a look: only pending after an exception)
+        if self.prefetch:
+            steps.append(lambda: ctx.set_option(_OPT_BUILD_STREAM, 0))
+        if self.affine:
+            steps += [lambda: ctx.set_option(_OPT_SELECT_AFFINE_STATE, -1), lambda: ctx.release_affine_state(self.state)]
+        for step in reversed(steps):                                       # (an ExitStack runs what it was given last first)
+            stack.callback(step)
+        if self.affine:
+            ctx.set_option(_OPT_SELECT_AFFINE_STATE, self.state)
+        if self.prefetch:
             ctx.set_option(_OPT_BUILD_STREAM, 1)
         # one new frame per step: all uploads on ONE copy stream (the default, two, is for the two frames of a pair; with two, the look at
         # every other frame's selection waits twice as long -- 0.280 against 0.307 ms per 4K frame, profiles/README.md round 6)
         ctx.set_option(_OPT_COPY_STREAMS, SEQUENCE_COPY_STREAMS)
 
-        def stage_frame(k, item):                    # upload + pyramid build of frame k (enqueued only)
-            ingest(s[k % ring], item[1], k, staged=item[0] == "staged")
-            ctx.build_pyramids(s[k % ring], sync=False)
-            if replace_lost and prefetch:            # ... and the list-independent half of its replacement pass, on the same stream
-                ctx.select_prepare(s[k % ring])
+    def close_stager(self):
+        if self.stager is not None and not self.stager.close():
+            # the helper thread is still inside the caller's frame source: it may yet write one buffer of this set, so the
+            # next call must not get the same pinned memory (a fresh set is allocated instead)
+            self.ctx.staging_forget(*self.stage_key)
 
-        def next_frame():                            # ("staged", pinned buffer) | ("raw", array) | None at the end
-            if stager is not None:
-                item = stager.next()
-                return item if item[0] is not None else None
-            img = next(frames, None)
-            return None if img is None else ("raw", pixels_of(img))
+    def table(self):
+        """the KLT_FeatureTable of the frames that arrived: one download per chunk and table, straight into the arrays handed out"""
+        nframes, stages = self.k + 1, self.stages
+        ft = KLT_FeatureTable(nframes, self.n, _fill=False)
+        self.rows.download(nframes, ft.rec)
+        ft.rec["aux"] = 0
+        if stages.quality:
+            ft.quality = self.quality_rows.download(nframes).view(QUALITY_DTYPE)
+            ft.quality[0] = 0                                        # nothing was tracked into the first frame
+        if stages.crowd is not None:
+            ft.crowd = self.crowd_rows.download(nframes).view(CROWD_DTYPE)
+            ft.crowd[0] = 0                                          # nothing was tracked into the first frame
+        for check, _ in stages.consensus:
+            records = self.model_rows.download(nframes).view(check.dtype).reshape(nframes)
+            if self.n == 0:
+                records[:] = np.zeros(1, check.dtype)[0]             # (no list, no launch: nothing was written)
+            records[0] = np.zeros(1, check.dtype)[0]                 # nothing was tracked into the first frame
+            setattr(ft, check.ft, records)                           # ft.models, ft.epipolar or ft.homography
+        if self.tc.sequentialMode:
+            # leave the context as the per-frame API would: the last frame's pyramids are "frame 1" of the next call
+            from .trackFeatures import _pyramid_handles
+            tc, s = self.tc, self.s
+            last = s[(nframes - 1) % self.ring]
+            if last != s[0]:
+                self.ctx.swap_slots(s[0], last)
+            tc.pyramid_last, tc.pyramid_last_gradx, tc.pyramid_last_grady = _pyramid_handles(tc, self.ctx, s[0], self.ncols, self.nrows)
+        return ft
 
-        def track(j):                                # frame j - 1 -> j: row j - 1 of the table in, row j out
-                cur, prev = s[j % ring], s[(j - 1) % ring]
-                if affine:
-                    ctx.track_affine_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures, state)
-                elif predict and j >= 2:             # guesses from rows j - 2 and j - 1, on the same stream in front of the tracker that reads them
-                    ctx.predict_cv_async(row_fb(j - 2), row_fb(j - 1), _FB_GUESS, nFeatures)
-                    if fb_check:
-                        ctx.track_fb_guess_async(prev, cur, row_fb(j - 1), _FB_GUESS, row_fb(j), nFeatures)
-                    else:
-                        ctx.track_guess_async(prev, cur, row_fb(j - 1), _FB_GUESS, row_fb(j), nFeatures)
-                elif fb_check:                       # stateless like the plain tracker: may be enqueued ahead and repeated
-                    ctx.track_fb_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
-                else:
-                    ctx.track_async(prev, cur, row_fb(j - 1), row_fb(j), nFeatures)
-                if check:                            # wherever the tracker goes, in front of the quality launch and of frame j's select_begin
-                    ctx._consensus_async(check, row_fb(j - 1), row_fb(j), mrow_fb(j), nFeatures)
-                if crowd.mode:                       # behind every other check; row j - 1 of its table in (row 0: no ages yet), row j out
-                    ctx.crowd_check_async(row_fb(j), crow_fb(j - 1) if j >= 2 else -1, crow_fb(j), nFeatures)
-                if quality:                          # wherever the tracker goes, a repeated one included; in front of frame j's replacement
-                    ctx.track_quality_async(prev, cur, row_fb(j - 1), row_fb(j), qrow_fb(j), nFeatures)
 
-        # The tracker of frame k + 1 only READS the list that frame k's replacement completes, so it is enqueued before the host looks at
-        # that replacement's outcome (klt_select_finish): the GPU has it queued while the host turns around.  In the rare case that the
-        # look makes the selection rewrite the list, the tracker is enqueued once more.  Not with the affine check: it updates the
-        # per-feature state in place, so its launch cannot simply be repeated.
-        ahead = prefetch and replace_lost and not affine
-        if ahead:
-            # Frames are SENT two steps before their pyramid is built: frame k + 3 leaves for the slot of frame k (its other raw buffer) at the
-            # end of step k, while the tracker k -> k + 1 still reads that slot's pyramids.  Sent one step ahead, a 4K frame's 155 us copy and
-            # its build sit behind each other in front of the tracker that needs them (0.329 instead of 0.277 ms per frame, profiles/README.md).
-            def send(j):
-                item = next_frame()
-                if item is not None:
-                    ingest(s[j % ring], item[1], j, staged=item[0] == "staged", wait=False)
-                return item is not None
+def _drive_ahead(q):
+    """The steps of a call that replaces lost features and prefetches: every tracker is enqueued before the host looks at the replacement
+    in front of it (_Sequence.ahead), and frames are SENT two steps before their pyramid is built: frame k + 3 leaves for the slot of
+    frame k (its other raw buffer) at the end of step k, while the tracker k -> k + 1 still reads that slot's pyramids.  Sent one step
+    ahead, a 4K frame's 155 us copy and its build sit behind each other in front of the tracker that needs them (0.329 instead of
+    0.277 ms per frame, profiles/README.md)."""
+    ctx, s, ring, row, n = q.ctx, q.s, q.ring, q.rows.row, q.n
+    have = 0                                 # frames sent so far beyond frame 0: 1 .. have
+    for j in (1, 2):
+        if have == j - 1 and q.send(j):      # (a source that has ended is not asked again: the helper thread says so only once)
+            have = j
+    if have >= 1:
+        q.build(1)
+        q.track(1)
+    if have == 2 and q.send(3):              # into frame 0's slot, which only the tracker just enqueued still reads
+        have = 3
+    while q.k + 1 <= have:
+        q.k = k = q.k + 1
+        ctx.select_begin(s[k % ring], REPLACING_SOME, True, row(k), n)
+        if k + 1 <= have:
+            q.build(k + 1)
+            q.track(k + 1)
+        if ctx.select_finish() and k + 1 <= have:
+            q.track(k + 1)
+        if q.stager is not None:
+            q.landed(k)
+        # (after the look: a repeated tracker needs slot k's pyramids valid.  Putting the send off to behind the NEXT selection's
+        # launches -- so that the host is back at them sooner -- measured slower, 0.360 against 0.335 ms per 4K frame, 0.168 against
+        # 0.153 at 1080p: the copy's head start is worth more than the host's 25 us)
+        if have == k + 2 and q.send(k + 3):
+            have = k + 3
 
-            def build(j):
-                ctx.build_pyramids(s[j % ring], sync=False)
-                ctx.select_prepare(s[j % ring])
 
-            have = 0                                 # frames sent so far beyond frame 0: 1 .. have
-            for j in (1, 2):
-                if have == j - 1 and send(j):        # (a source that has ended is not asked again: the helper thread says so only once)
-                    have = j
-            if have >= 1:
-                build(1)
-                track(1)
-            if have == 2 and send(3):                # into frame 0's slot, which only the tracker just enqueued still reads
-                have = 3
-            while k + 1 <= have:
-                k += 1
-                ctx.select_begin(s[k % ring], REPLACING_SOME, True, row_fb(k), nFeatures)
-                if k + 1 <= have:
-                    build(k + 1)
-                    track(k + 1)
-                if ctx.select_finish() and k + 1 <= have:
-                    track(k + 1)
-                if stager is not None:
-                    landed(k)
-                # (after the look: a repeated tracker needs slot k's pyramids valid.  Putting the send off to behind the NEXT selection's
-                # launches -- so that the host is back at them sooner -- measured slower, 0.360 against 0.335 ms per 4K frame, 0.168 against
-                # 0.153 at 1080p: the copy's head start is worth more than the host's 25 us)
-                if have == k + 2 and send(k + 3):
-                    have = k + 3
-            nxt = None
-        else:
-            nxt = next_frame()
-            if nxt is not None:
-                stage_frame(1, nxt)
-        while nxt is not None:
-            k += 1
-            nxt = next_frame()
-            if not ahead:
-                track(k)
-            if replace_lost:                         # the chain first: tracker, then the replacement pass up to the host's look at it
-                ctx.select_begin(s[k % ring], REPLACING_SOME, True, row_fb(k), nFeatures)
-            if nxt is not None and prefetch:
-                stage_frame(k + 1, nxt)              # the next frame's upload, build and scores: enqueued while the GPU works on the above
-                if ahead:
-                    track(k + 1)
-            if replace_lost:
-                redo = ctx.select_finish()
-                if redo and ahead and nxt is not None:
-                    track(k + 1)
-            if nxt is not None and not prefetch:
-                stage_frame(k + 1, nxt)
-    finally:
-        # every step on its own: a failing one must not skip the rest (the options live on the shared default context)
-        try:
-            ctx.select_finish()                      # (only pending after an exception)
-        finally:
-            try:
-                if stager is not None and not stager.close():
-                    # the helper thread is still inside the caller's frame source: it may yet write one buffer of this set, so the
-                    # next call must not get the same pinned memory (a fresh set is allocated instead)
-                    ctx.staging_forget(*stage_key)
-            finally:
-                try:
-                    ctx.set_option(_OPT_COPY_STREAMS, 2)
-                    if prefetch:
-                        ctx.set_option(_OPT_BUILD_STREAM, 0)
-                finally:
-                    if affine:
-                        try:
-                            ctx.set_option(_OPT_SELECT_AFFINE_STATE, -1)
-                        finally:
-                            ctx.release_affine_state(state)
-    nframes = k + 1
-    ft = KLT_FeatureTable(nframes, nFeatures, _fill=False)
-    for ci, base in enumerate(tables):
-        lo = ci * chunk
-        hi = min(nframes, lo + chunk)
-        ctx.featbuf_download_into(base, ft.rec[lo:hi])          # rows lo .. hi-1 are contiguous in the table: no staging copy
-    ft.rec["aux"] = 0
-    if quality:
-        from .backend import FEAT_DTYPE, QUALITY_DTYPE
-        rec = np.zeros((nframes, nFeatures), FEAT_DTYPE)
-        for ci, base in enumerate(qtables):
-            lo = ci * chunk
-            hi = min(nframes, lo + chunk)
-            ctx.featbuf_download_into(base, rec[lo:hi])
-        ft.quality = rec.view(QUALITY_DTYPE)
-        ft.quality[0] = 0                                        # nothing was tracked into the first frame
-    if crowd.mode:
-        from .backend import CROWD_DTYPE, FEAT_DTYPE
-        rec = np.zeros((nframes, nFeatures), FEAT_DTYPE)
-        for ci, base in enumerate(ctables):
-            lo = ci * chunk
-            hi = min(nframes, lo + chunk)
-            if hi > lo and nFeatures:
-                ctx.featbuf_download_into(base, rec[lo:hi])
-        ft.crowd = rec.view(CROWD_DTYPE)
-        ft.crowd[0] = 0                                          # nothing was tracked into the first frame
-    if check:
-        from .backend import FEAT_DTYPE
-        rec = np.zeros((nframes, check.records), FEAT_DTYPE)
-        for ci, base in enumerate(mtables):
-            lo = ci * chunk
-            hi = min(nframes, lo + chunk)
-            if hi > lo:
-                ctx.featbuf_download_into(base, rec[lo:hi])
-        records = rec.view(check.dtype).reshape(nframes)
-        if nFeatures == 0:
-            records[:] = np.zeros(1, check.dtype)[0]             # (no list, no launch: nothing was written)
-        records[0] = np.zeros(1, check.dtype)[0]                 # nothing was tracked into the first frame
-        setattr(ft, check.ft, records)                           # ft.models, ft.epipolar or ft.homography
-    if tc.sequentialMode:
-        # leave the context as the per-frame API would: the last frame's pyramids are "frame 1" of the next call
-        from .trackFeatures import _pyramid_handles
-        last = s[(nframes - 1) % ring]
-        if last != s[0]:
-            ctx.swap_slots(s[0], last)
-        tc.pyramid_last, tc.pyramid_last_gradx, tc.pyramid_last_grady = _pyramid_handles(tc, ctx, s[0], ncols, nrows)
-    return ft
+def _drive_plain(q):
+    """The steps of every other call: tracker, replacement pass up to the host's look, the next frame's upload and build in between (`prefetch`) or behind."""
+    nxt = q.next_frame()
+    if nxt is not None:
+        q.stage_frame(1, nxt)
+    while nxt is not None:
+        q.k = k = q.k + 1
+        nxt = q.next_frame()
+        q.track(k)
+        if q.replace_lost:                   # the chain first: tracker, then the replacement pass up to the host's look at it
+            q.ctx.select_begin(q.s[k % q.ring], REPLACING_SOME, True, q.rows.row(k), q.n)
+        if nxt is not None and q.prefetch:
+            q.stage_frame(k + 1, nxt)        # the next frame's upload, build and scores: enqueued while the GPU works on the above
+        if q.replace_lost:
+            q.ctx.select_finish()
+        if nxt is not None and not q.prefetch:
+            q.stage_frame(k + 1, nxt)
+
+
+def _track_sequence_locked(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid=None):
+    q = _Sequence(ctx, tc, frames, nFeatures, replace_lost, async_ingest, prefetch, grid)
+    with contextlib.ExitStack() as stack:
+        q.open(stack)
+        (_drive_ahead if q.ahead else _drive_plain)(q)
+    return q.table()
