@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -730,6 +730,48 @@ int klt_crowd_check_path(klt_ctx *ctx);
  * be NULL) takes what the resolve launch's one workgroup spent grouping the candidates by cell, in the rounds and writing the records,
  * in ticks of 10 ns.  A diagnostic; KLT_ERR_STATE before any crowd-check launch. */
 int klt_crowd_check_rounds(klt_ctx *ctx, int *rounds, int *phase_ticks);
+
+/* ---- CLAHE ingest stage (not in the reference) ------------------------------------------------------------------- */
+/* Contrast-limited adaptive histogram equalisation of an 8-bit frame in front of the level-0 kernel: in a low-contrast frame (a dark
+ * half, a backlit scene, a thermal camera squeezed into 8 bits) the 7x7 sums of the selection sit in a few grey levels and min_eigenvalue
+ * turns away corners a person would pick.  With mode 1 every reader of a slot's raw 8-bit frame -- the level-0 launch of a build, the
+ * two-pass build, the selection on the raw frame (use_pyramid = 0) -- reads an equalised copy the slot keeps instead; the frame itself
+ * (an adopted frame is the caller's memory) is read and never written.
+ *
+ * THE RULE (integer arithmetic only; the device equals it byte for byte).  Inputs: an 8-bit frame ncols x nrows, tiles_x, tiles_y, clip_q8
+ * (the clip limit times 256, rounded; 0 = no clipping).
+ *  1 tiles     edges x_k = (k * ncols) / tiles_x, k = 0 .. tiles_x, and y_j likewise (integer division): tiles differ by at most one pixel
+ *              in size, nothing is padded.
+ *  2 per tile  (area A, 256-bin histogram h)  if clip_q8 > 0: cap = max(1, (clip_q8 * A) >> 16) in 64 bits; excess = SUM max(h[b] - cap, 0);
+ *              h[b] = min(h[b], cap) + excess / 256; with r = excess % 256 the bins (k * 256) / r, k = 0 .. r - 1, get one more each.  No
+ *              second clipping pass; the bins still sum to A.  cdf[b] = the inclusive prefix sum of h; lut[b] = (cdf[b] * 255 + A / 2) / A.
+ *  3 per axis  in doubled coordinates, C_k = x_k + x_{k+1} and P = 2 x + 1:  P < C_0: both tiles 0, w = 0, D = 1;  P >= C_{tiles_x - 1}:
+ *              both tiles tiles_x - 1, w = 0, D = 1;  otherwise with k the largest value with C_k <= P: tiles k and k + 1, w = P - C_k,
+ *              D = C_{k+1} - C_k.  (One tile on an axis: D is always 1.)
+ *  4 pixel     with v the input byte: (lut00[v] (Dx - wx) (Dy - wy) + lut10[v] wx (Dy - wy) + lut01[v] (Dx - wx) wy + lut11[v] wx wy
+ *              + (Dx Dy) / 2) / (Dx Dy): one rounding, 0 .. 255 (lut10: the tile one to the right, lut01: the tile one down).
+ * A frame is EQUALISABLE when tiles_x <= ncols, tiles_y <= nrows and the largest Dx * Dy * 255 is below 2^32 (the per-pixel division is a
+ * 32-bit one; at 3840 x 2160 this holds from 2 x 2 tiles up, and for 1 x 1); otherwise KLT_ERR_ARG, and the slot stays usable.
+ * Two launches per build (per-tile LUTs; the interpolated frame), the frames of a build's group in the same two. */
+typedef struct { int32_t mode; int32_t tiles_x, tiles_y; int32_t clip_q8; } klt_equalize_params;
+/* mode: 0 = off (the default), 1 = CLAHE; tiles_x, tiles_y in 1 .. 64; clip_q8 in 0 .. 2^20; anything else is KLT_ERR_ARG.  A change
+ * voids every slot's equalised frame and counts as a change of the taps does: every slot's next build is a full one, lean slots included.
+ * The pyramids a slot holds stay what their build made them (klt_slot_state keeps saying so): the caller rebuilds. */
+int klt_set_equalize_params(klt_ctx *ctx, const klt_equalize_params *p);
+/* A host frame (pitch bytes from row to row) in, the equalised host frame (ncols bytes from row to row) out, like klt_smooth_f32: the
+ * two kernels by name, under the context's tiles and clip limit whatever its mode says.  Synchronises.  A frame that is not equalisable:
+ * KLT_ERR_ARG. */
+int klt_equalize_u8(klt_ctx *ctx, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst);
+/* The equalised frame the slot's last build (or selection on the raw frame) read, [nrows][ncols] bytes: KLT_ERR_STATE if that was not an
+ * equalised one -- mode 0, or a new frame or new parameters since.  Synchronises. */
+int klt_download_equalized_u8(klt_ctx *ctx, int slot, uint8_t *dst);
+/* 0: the last klt_build_pyramids* enqueued no equalisation launch (mode 0, or every slot's equalised frame was still valid), 1: it did.
+ * A diagnostic, like klt_track_light_path. */
+int klt_equalize_path(klt_ctx *ctx);
+/* With mode 1, klt_build_pyramids* and the selection on the raw frame refuse an f32 slot: KLT_ERR_STATE, "equalisation takes 8-bit
+ * frames"; nothing is enqueued and the slot builds again with mode 0.  The slot's equalised frame lives in a buffer of its own, allocated
+ * when first needed (KLT_ERR_NOMEM leaves the slot as it was), freed by klt_slot_free, travelling with klt_swap_slots.  With mode 0 no
+ * launch, no allocation and no event is added to any call. */
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

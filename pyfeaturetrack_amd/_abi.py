@@ -61,6 +61,10 @@ class KltCrowdParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("ncols", C.c_int32), ("nrows", C.c_int32), ("min_distance", C.c_int32)]
 
 
+class KltEqualizeParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("clip_q8", C.c_int32)]
+
+
 class KltCrowd(C.Structure):
     _fields_ = [("age", C.c_int32), ("winner", C.c_int32), ("val", C.c_int32), ("pad", C.c_int32)]
 
@@ -216,6 +220,10 @@ SYMBOLS = {
     "klt_crowd_check": (_I, [_P, _P, _P, _P, _I, _PI]),
     "klt_crowd_check_path": (_I, [_P]),
     "klt_crowd_check_rounds": (_I, [_P, _PI, _PI]),
+    "klt_set_equalize_params": (_I, [_P, C.POINTER(KltEqualizeParams)]),
+    "klt_equalize_u8": (_I, [_P, _P, _I, _I, _I, _P]),
+    "klt_download_equalized_u8": (_I, [_P, _I, _P]),
+    "klt_equalize_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

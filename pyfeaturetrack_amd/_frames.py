@@ -70,10 +70,12 @@ class FrameKey:
     A Pillow image -- what the reference's callers pass (trackFeatures.py:165,176) -- is not converted by Pillow at all: `rows` is the
     row table of its own storage (_pil.py), which the lattice, the comparison and the staging copy read in place: 8-bit images ("L") as
     they are, colour images ("RGB" / "RGBA" / "RGBX") compared and kept as 4-byte pixels and turned into the float frame
-    `img.convert("F")` would be by klt_host_luma_rows, float images ("F") as float rows."""
+    `img.convert("F")` would be by klt_host_luma_rows, float images ("F") as float rows.
+    `eq` (tc.equalization switched on: the bytes of the call's klt_equalize_params, `equalization_tag`) is part of the kind: a slot whose
+    pyramids were built from the frame equalised under other parameters, or from the frame as it is, does not hold this image."""
     __slots__ = ("img", "size", "kind", "rows", "_arr", "_sig")
 
-    def __init__(self, img):
+    def __init__(self, img, eq=None):
         self.img = img
         self.rows = None
         if isinstance(img, np.ndarray):
@@ -81,6 +83,8 @@ class FrameKey:
         else:
             self.size, self.kind = tuple(img.size), getattr(img, "mode", "?")
             self.rows = rows_of(img)
+        if eq is not None:
+            self.kind = (self.kind, eq)
         self._arr = self._sig = None
 
     def array(self):
@@ -146,6 +150,13 @@ class FrameKey:
             _host_lib().klt_host_luma_rows(buf.ctypes.data, r.table, r.nrows, r.ncols)
         else:
             _host_lib().klt_host_copy_rows(buf.ctypes.data, r.table, r.nrows, r.row_bytes)
+
+
+def equalization_tag(tc):
+    """what FrameKey takes as `eq` for a call on this tracking context: None with tc.equalization off, else the parameters' bytes"""
+    from .params import equalize_params_from_tc
+    eq = equalize_params_from_tc(tc)
+    return bytes(eq) if eq.mode else None
 
 
 def pixels_of(img):

@@ -12,8 +12,8 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltCrowd, KltCrowdParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
-from .params import affine_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
+                   KltCrowd, KltCrowdParams, KltEqualizeParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
+from .params import affine_params_from_tc, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
 assert FEAT_DTYPE.itemsize == C.sizeof(KltFeat)
@@ -177,12 +177,51 @@ class Context:
 
     def configure(self, tc):
         light = light_params_from_tc(tc)                 # (ValueError for a combination that is not offered, before anything is set)
+        eq = equalize_params_from_tc(tc)                 # (likewise for tc.equalization and its parameters)
         self.set_params(params_from_tc(tc))
+        self.set_equalize_params(eq, only_if_on=True)
         self.set_light_params(light)
         self.set_affine_params(affine_params_from_tc(tc))
         fb = fb_params_from_tc(tc)
         if fb.enabled:
             self.set_fb_params(fb)
+
+    # ------------------------------------------------ CLAHE ingest stage (klt_set_equalize_params)
+    def set_equalize_params(self, eq=None, only_if_on=False, **kw):
+        """klt_set_equalize_params: `eq` a KltEqualizeParams, or its fields by name (mode, tiles_x, tiles_y, clip_q8; the defaults: off,
+        8 x 8 tiles, clip limit 3.0).  Sent when it differs from what the library holds.  `only_if_on`: a struct with mode 0 is sent only
+        to switch off an equalisation that is on -- a context that never had it on gets no call at all."""
+        if eq is None:
+            eq = KltEqualizeParams(int(kw.pop("mode", 0)), int(kw.pop("tiles_x", 8)), int(kw.pop("tiles_y", 8)), int(kw.pop("clip_q8", 768)))
+            assert not kw, kw
+        key = bytes(eq)
+        held = getattr(self, "_equalize_key", None)
+        if only_if_on and not eq.mode and (held is None or not KltEqualizeParams.from_buffer_copy(held).mode):
+            return
+        if key != held:
+            self._check(self._lib.klt_set_equalize_params(self._h, C.byref(eq)))
+            self._equalize_key = key
+
+    def equalize(self, img, ncols=None):
+        """klt_equalize_u8: the equalised frame of a 2-D uint8 array under the context's tiles and clip limit, whatever its mode.
+        `ncols`: the frame is the first ncols columns of `img` (whose width is then the pitch)"""
+        a = np.ascontiguousarray(img)
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("expected a 2-D uint8 image")
+        nrows, pitch = a.shape
+        out = np.empty((nrows, pitch if ncols is None else int(ncols)), np.uint8)
+        self._check(self._lib.klt_equalize_u8(self._h, a.ctypes.data, out.shape[1], nrows, pitch, out.ctypes.data))
+        return out
+
+    def download_equalized(self, slot, ncols, nrows):
+        """klt_download_equalized_u8: the equalised frame the slot's last build read"""
+        out = np.empty((nrows, ncols), np.uint8)
+        self._check(self._lib.klt_download_equalized_u8(self._h, slot, out.ctypes.data))
+        return out
+
+    def equalize_path(self):
+        """klt_equalize_path: 1 if the last build enqueued equalisation launches, 0 if not (a diagnostic)"""
+        return self._check(self._lib.klt_equalize_path(self._h))
 
     # ------------------------------------------------ gain / bias tracking (klt_set_light_params)
     def set_light_params(self, lp=None, mode=None):

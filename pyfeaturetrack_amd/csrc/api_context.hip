@@ -298,7 +298,7 @@ void klt_destroy(klt_ctx *c)
     for (void *p : c->dev_allocs) hipFree(p);
     for (hipEvent_t e : c->ring) hipEventDestroy(e);
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
-    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); }
+    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); }
     for (FeatBuf &b : c->fbs)
         if (!b.view) hipFree(b.d);
     hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg);
@@ -349,6 +349,21 @@ int klt_set_params(klt_ctx *c, const klt_params *p)
     return KLT_OK;
 }
 
+
+// CLAHE ingest stage: a change voids every slot's equalised frame and counts as a change of the taps (cfg_gen: the next build of every
+// slot is a full one).  The pyramids the slots hold stay what their builds made them
+int klt_set_equalize_params(klt_ctx *c, const klt_equalize_params *p)
+{
+    if (!c || !p) return fail(c, KLT_ERR_ARG, "null argument");
+    if (p->mode != 0 && p->mode != 1) return fail(c, KLT_ERR_ARG, "equalisation mode must be 0 (off) or 1 (CLAHE)");
+    if (p->tiles_x < 1 || p->tiles_x > 64 || p->tiles_y < 1 || p->tiles_y > 64) return fail(c, KLT_ERR_ARG, "equalisation tiles must lie in 1 .. 64");
+    if (p->clip_q8 < 0 || p->clip_q8 > (1 << 20)) return fail(c, KLT_ERR_ARG, "equalisation clip_q8 must lie in 0 .. 2^20");
+    if (std::memcmp(p, &c->eqp, sizeof(*p)) == 0) return KLT_OK;
+    c->eqp = *p;
+    for (Slot &s : c->slots) s.eq_valid = false;
+    c->cfg_gen++;
+    return KLT_OK;
+}
 
 int klt_set_option(klt_ctx *c, int option, int value)
 {
@@ -441,7 +456,7 @@ int klt_slot_free(klt_ctx *c, int slot)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     Slot &s = c->slots[slot];
-    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img);
+    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq);
     s = Slot();
     return KLT_OK;
 }

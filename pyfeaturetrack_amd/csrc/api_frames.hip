@@ -57,6 +57,7 @@ int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int p
     s->raw_kind = kind;
     s->f32_in_raw = false;
     s->pyr_valid = false;
+    s->eq_valid = false;
     return 0;
 }
 
@@ -97,6 +98,93 @@ int layout_pyramid(klt_ctx *c, Slot *s)
     return 0;
 }
 
+// ---- CLAHE ingest stage (klt_set_equalize_params; the rule: include/klt_gpu.h)
+// A frame is equalisable when the tile grid fits it and the per-pixel division is a 32-bit one: the largest Dx * Dy * 255 below 2^32,
+// Dx the largest distance of two neighbouring tile centres in doubled coordinates (1 with one tile on the axis)
+static long long widest_centre_gap(int n, int tiles)
+{
+    long long widest = 1;
+    for (int k = 0; k + 2 <= tiles; k++)           // C_{k+1} - C_k = x_{k+2} - x_k
+        widest = std::max(widest, ((long long)(k + 2) * n) / tiles - ((long long)k * n) / tiles);
+    return widest;
+}
+
+static int check_equalisable(klt_ctx *c, int nc, int nr)
+{
+    const klt_equalize_params &q = c->eqp;
+    if (q.tiles_x > nc || q.tiles_y > nr) return fail(c, KLT_ERR_ARG, "equalisation: the frame is smaller than the tile grid");
+    if (widest_centre_gap(nc, q.tiles_x) * widest_centre_gap(nr, q.tiles_y) * 255 >= (1LL << 32))
+        return fail(c, KLT_ERR_ARG, "equalisation: tiles too large for a 32-bit interpolation (the largest Dx * Dy * 255 must stay below 2^32)");
+    return 0;
+}
+
+// the bytes of a slot's equalised frame and where its LUTs begin behind it
+static size_t eq_lut_offset(int nc, int nr) { return ((size_t)nc * nr + 255) & ~(size_t)255; }
+static size_t eq_bytes(const klt_ctx *c, int nc, int nr) { return eq_lut_offset(nc, nr) + (size_t)c->eqp.tiles_x * c->eqp.tiles_y * 256; }
+
+// the two launches on `batch` frames of one size as `a` names them (src, dst, lut, src_pitch filled in by the caller)
+static int enqueue_equalize(klt_ctx *c, EqualizeArgs &a, int batch, int nc, int nr, hipStream_t st)
+{
+    a.ncols = nc; a.nrows = nr;
+    a.tiles_x = c->eqp.tiles_x; a.tiles_y = c->eqp.tiles_y; a.clip_q8 = c->eqp.clip_q8;
+    // the apply launch: every band of rows between two tile centres split until about a thousand workgroups are out, a workgroup keeping
+    // at least 4 rows of a band of average height
+    const int bands = a.tiles_y + 1;
+    int split = (1024 + bands * batch - 1) / (bands * batch);
+    const int most = std::max(1, nr / a.tiles_y / 4);
+    a.split = std::max(1, std::min(split, most));
+    const double N = (double)nc * nr * batch;
+    {
+        TimerScope t(c, F_EQ_LUT, N + 256.0 * a.tiles_x * a.tiles_y * batch, st);
+        launch_clahe_lut(st, a, batch);
+    }
+    {
+        TimerScope t(c, F_EQ_APPLY, 2 * N, st);
+        launch_clahe_apply(st, a, batch);
+    }
+    return 0;
+}
+
+// (declared in klt_context.h)
+int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched /* = nullptr */)
+{
+    if (launched) *launched = false;
+    std::vector<Slot *> todo;
+    // every refusal first: nothing is allocated or enqueued for a call that fails
+    for (int i = 0; i < n; i++) {
+        Slot *s = slots[i];
+        if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, "equalisation takes 8-bit frames");
+        if (s->eq_valid) continue;
+        if (int rc = check_equalisable(c, s->nc, s->nr)) return rc;
+        if (c->capturing) return fail(c, KLT_ERR_STATE, "a frame would have to be equalised during a stream capture");
+        todo.push_back(s);
+    }
+    for (Slot *s : todo)
+        if (int rc = ensure(c, s->eq, s->eq_cap, eq_bytes(c, s->nc, s->nr))) return rc;      // (a slot that gets none keeps eq == nullptr, eq_valid false)
+    std::vector<bool> done(todo.size(), false);
+    for (size_t i0 = 0; i0 < todo.size(); i0++) {
+        if (done[i0]) continue;
+        EqualizeArgs a;
+        std::memset(&a, 0, sizeof(a));
+        int B = 0;
+        const int nc = todo[i0]->nc, nr = todo[i0]->nr;
+        for (size_t i = i0; i < todo.size() && B < KLT_MAX_BATCH; i++)
+            if (!done[i] && todo[i]->nc == nc && todo[i]->nr == nr) {
+                Slot *s = todo[i];
+                a.src[B] = s->u8_ext ? s->u8_ext : s->u8;
+                a.dst[B] = s->eq;
+                a.lut[B] = s->eq + eq_lut_offset(nc, nr);
+                B++;
+                done[i] = true;
+            }
+        a.src_pitch = nc;
+        if (int rc = enqueue_equalize(c, a, B, nc, nr, st)) return rc;
+    }
+    for (Slot *s : todo) s->eq_valid = true;
+    if (launched) *launched = !todo.empty();
+    return 0;
+}
+
 int enqueue_smooth_raw(klt_ctx *c, Slot *s, float *dst)
 {
     const int nc = s->nc, nr = s->nr;
@@ -104,7 +192,7 @@ int enqueue_smooth_raw(klt_ctx *c, Slot *s, float *dst)
     const Taps &g = c->gauss[0];
     {
         TimerScope t(c, F_SMOOTH_H, N * ((s->raw_kind == 1 ? 1 : 4) + 4));
-        if (s->raw_kind == 1) launch_hconv_u8(c->work, raw8(s), nc, nr, c->tmpA, nullptr, nc, 1, 0, g, nullptr);
+        if (s->raw_kind == 1) launch_hconv_u8(c->work, raw8(c, s), nc, nr, c->tmpA, nullptr, nc, 1, 0, g, nullptr);
         else launch_hconv_f32(c->work, rawf(s), nc, nr, c->tmpA, nullptr, nc, 1, 0, g, nullptr);
     }
     {
@@ -381,6 +469,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     for (int i = 0; i < n; i++) {
         if (int rc = get_slot(c, slot_ids[i], &sl[i], false)) return rc;
         if (sl[i]->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
+        if (c->eqp.mode == 1 && sl[i]->raw_kind != 1) return fail(c, KLT_ERR_STATE, "equalisation takes 8-bit frames");
         for (int j = 0; j < i; j++)
             if (sl[j] == sl[i]) return fail(c, KLT_ERR_ARG, "slot listed twice");
         if (int rc = layout_pyramid(c, sl[i])) return rc;
@@ -399,6 +488,14 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         sl[i]->read_valid = false;
     }
     c->last_build_on_bstream = on_bstream ? 1 : 0;
+    // CLAHE ingest stage: the frames that have no valid equalised copy get one here, behind their uploads on the stream the build runs
+    // on; the level-0 launches below read the copies (raw8).  The mark at the end of the build covers this reader of the raw frames too.
+    c->eq_path = 0;
+    if (c->eqp.mode == 1) {
+        bool launched = false;
+        if (int rc = ensure_equalized(c, sl.data(), n, c->work, &launched)) return rc;
+        c->eq_path = launched ? 1 : 0;
+    }
     // groups of frames with the same geometry and input type share launches
     std::vector<bool> done((size_t)n, false);
     for (int i0 = 0; i0 < n; i0++) {
@@ -437,7 +534,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
             for (int b = 0; b < B && lean; b++)
                 if (int rc = ensure(c, g[b]->l0img, g[b]->l0img_cap, (size_t)s0->nc * s0->nr)) return rc;
             for (int b = 0; b < B; b++) {
-                raw[b] = g[b]->raw_kind == 1 ? (const void *)raw8(g[b]) : (const void *)rawf(g[b]);
+                raw[b] = g[b]->raw_kind == 1 ? (const void *)raw8(c, g[b]) : (const void *)rawf(g[b]);
                 rec[b] = g[b]->lv[0].img;
                 cim[b] = lean ? g[b]->l0img : cimg_of(0, b);
             }
@@ -614,6 +711,7 @@ static int upload_async(klt_ctx *c, int slot, const void *px, int ncols, int nro
     s->raw_kind = esz == 1 ? 1 : 2;
     s->f32_in_raw = esz != 1;
     s->pyr_valid = false;
+    s->eq_valid = false;
     return KLT_OK;
 }
 
@@ -660,7 +758,7 @@ int klt_device_free(klt_ctx *c, void *p)
             const uint8_t *lo = (const uint8_t *)p, *hi = lo + c->dev_alloc_bytes[i];
             for (Slot &s : c->slots)
                 if (s.u8_ext && s.u8_ext >= lo && s.u8_ext < hi) {
-                    s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.gen = 0; s.nc = s.nr = 0;
+                    s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.eq_valid = false; s.gen = 0; s.nc = s.nr = 0;
                 }
             // likewise a selection mask that lives inside it (klt_set_select_mask_device): the context has no mask any more
             if (c->mask && c->mask >= lo && c->mask < hi) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }
@@ -704,6 +802,7 @@ int klt_slot_adopt_u8(klt_ctx *c, int slot, const uint8_t *dev_px, int ncols, in
     s->raw_kind = 1;
     s->f32_in_raw = false;
     s->pyr_valid = false;
+    s->eq_valid = false;
     return KLT_OK;
 }
 
@@ -807,6 +906,56 @@ int klt_smooth_f32(klt_ctx *c, const float *src, int ncols, int nrows, const dou
     if (!c || !src || !dst || !gauss) return fail(c, KLT_ERR_ARG, "null argument");
     if (ng < 1 || ng > KLT_MAX_KERNEL_WIDTH || !(ng & 1)) return fail(c, KLT_ERR_ARG, "tap count must be odd and at most 71");
     return klt_convolve_separate_f32(c, src, ncols, nrows, gauss, ng, gauss, ng, dst);      // KLTComputeSmoothedImage, convolve.py:263
+}
+
+// ------------------------------------------------------------------------------- CLAHE ingest stage
+// the two equalisation kernels on one host frame, under the context's tiles and clip limit (whatever its mode): one allocation holds the
+// frame as the caller laid it out, the equalised frame and the LUTs
+int klt_equalize_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
+{
+    if (!c || !src || !dst) return fail(c, KLT_ERR_ARG, "null argument");
+    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols || (long long)ncols * nrows > kMaxFramePixels ||
+        (long long)pitch * nrows > 2 * kMaxFramePixels)
+        return fail(c, KLT_ERR_ARG, "bad image geometry");
+    if (int rc = check_equalisable(c, ncols, nrows)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = (size_t)ncols * nrows, src_bytes = (size_t)pitch * (nrows - 1) + ncols;
+    const size_t dst_off = (src_bytes + 255) & ~(size_t)255, lut_off = dst_off + eq_lut_offset(ncols, nrows);
+    uint8_t *d = nullptr;
+    DEVALLOC(c, d, dst_off + eq_bytes(c, ncols, nrows));
+    hipError_t e = hipMemcpyAsync(d, src, src_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        EqualizeArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.src[0] = d; a.dst[0] = d + dst_off; a.lut[0] = d + lut_off;
+        a.src_pitch = pitch;
+        enqueue_equalize(c, a, 1, ncols, nrows, c->stream);
+        e = hipMemcpyAsync(dst, d + dst_off, N, hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    hipFree(d);
+    if (e != hipSuccess) return fail(c, KLT_ERR_DEVICE, hipGetErrorString(e));
+    return KLT_OK;
+}
+
+int klt_download_equalized_u8(klt_ctx *c, int slot, uint8_t *dst)
+{
+    if (!c || !dst) return fail(c, KLT_ERR_ARG, "null argument");
+    Slot *s;
+    if (int rc = get_slot(c, slot, &s, false)) return rc;
+    if (!s->eq_valid || !s->eq) return fail(c, KLT_ERR_STATE, "the slot holds no equalised frame (mode 0, or a new frame or new parameters since its last build)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = wait_built(c, s)) return rc;                 // the equalisation may have run on the build stream
+    HIPCHK(c, hipMemcpyAsync(dst, s->eq, (size_t)s->nc * s->nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KLT_OK;
+}
+
+int klt_equalize_path(klt_ctx *c)
+{
+    if (!c) return KLT_ERR_ARG;
+    return c->eq_path;
 }
 
 int klt_gradients_f32(klt_ctx *c, const float *src, int ncols, int nrows, const double *gauss, int ng,

@@ -293,9 +293,11 @@ int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, c
     if (s->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
     if (int rc = wait_upload(c, s, c->stream)) return rc;
     if (int rc = wait_built(c, s)) return rc;              // a build of this slot may still read the raw frame's buffers
+    if (c->eqp.mode == 1)                                  // CLAHE ingest stage: the readers below take the equalised copy (raw8), made now if it is stale
+        if (int rc = ensure_equalized(c, &s, 1, c->stream)) return rc;
     bool grads_done = false;
     if (c->p.smoothBeforeSelecting && fused_smooth_ok(c)) {
-        const void *raw = s->raw_kind == 1 ? (const void *)raw8(s) : (const void *)rawf(s);
+        const void *raw = s->raw_kind == 1 ? (const void *)raw8(c, s) : (const void *)rawf(s);
         if (int rc = enqueue_fused_smooth_grad(c, 1, &raw, s->raw_kind, &c->sel_rec, nullptr, nc, nr, plan_l0(c, 1, s->raw_kind == 1 ? 0 : 1, nc, nr)))
             return rc;
         grads_done = true;
@@ -309,7 +311,7 @@ int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, c
         Taps one;
         std::memset(&one, 0, sizeof(one));
         one.n = 1; one.sym = 1; one.k[0] = 1.0;
-        launch_hconv_u8(c->stream, raw8(s), nc, nr, c->sel_img, nullptr, nc, 1, 0, one, nullptr);
+        launch_hconv_u8(c->stream, raw8(c, s), nc, nr, c->sel_img, nullptr, nc, 1, 0, one, nullptr);
         img = c->sel_img;
     }
     if (!grads_done) {

@@ -34,10 +34,10 @@ namespace kltapi {
 
 
 enum Family { F_SMOOTH_GRAD, F_PYR_REDUCE, F_GRAD, F_SMOOTH_H, F_SMOOTH_V, F_PYR_H, F_PYR_V, F_GRAD_H, F_GRAD_V, F_TRACK,
-              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_COUNT };
+              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_COUNT };
 inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_reduce", "gradients", "smooth_h", "smooth_v", "pyramid_h",
                                           "pyramid_v", "gradient_h", "gradient_v", "track", "sat_rows", "sat_cols",
-                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check"};
+                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply"};
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
@@ -88,9 +88,14 @@ struct Slot {
     uint64_t wr_serial = 0, wr_alt_serial = 0;
     int wr_lane = -1, wr_alt_lane = -1;
     bool f32_in_raw = false;          // klt_upload_f32_async: the f32 frame lives in the alternating raw buffers (`u8`, 4 bytes per pixel), not in `f32`
+    // klt_set_equalize_params, mode 1: the equalised copy of the 8-bit frame (nc x nr bytes, rounded up to 256) with the per-tile LUTs
+    // it was made from behind it, allocated when first needed.  eq_valid: it was made from the frame the slot holds now -- this upload or
+    // adoption -- under the parameters the context holds now (a new frame, klt_slot_free or new parameters clear it)
+    uint8_t *eq = nullptr;
+    size_t eq_cap = 0;                // bytes
+    bool eq_valid = false;
 };
 
-inline const uint8_t *raw8(const Slot *s) { return s->u8_ext ? s->u8_ext : s->u8; }
 inline const float *rawf(const Slot *s) { return s->f32_in_raw ? reinterpret_cast<const float *>(s->u8) : s->f32; }
 
 struct FeatBuf { klt_feat *d = nullptr; int cap = 0; bool view = false; hipEvent_t comm_done = nullptr; /* last collective that touched it */ };
@@ -168,6 +173,8 @@ using namespace kltapi;      // (this header is for the api_*.hip files only)
 
 struct klt_ctx {
     int device = -1;
+    klt_equalize_params eqp{0, 8, 8, 768};    // CLAHE ingest stage (klt_set_equalize_params): off; 8 x 8 tiles, clip limit 3.0
+    int eq_path = 0;                          // klt_equalize_path: the last build enqueued equalisation launches
     hipStream_t stream = nullptr;     // uploads, pyramid build, selection, tracker
     hipStream_t cstream = nullptr;    // asynchronous frame ingest from pinned host memory (created on first use)
     // ... and more copy streams: consecutive uploads go round-robin over all of them, i.e. over several DMA engines (2 MB frames: 44 GB/s
@@ -340,6 +347,10 @@ struct klt_ctx {
 
 namespace kltapi {
 
+// the 8-bit frame a slot's readers take: the caller's device memory (adopted), the slot's own raw buffer, or -- CLAHE switched on -- the
+// equalised copy (ensure_equalized has made it)
+inline const uint8_t *raw8(const klt_ctx *c, const Slot *s) { return c->eqp.mode == 1 ? s->eq : (s->u8_ext ? s->u8_ext : s->u8); }
+
 int fail(klt_ctx *c, int code, const std::string &msg);      // sets the context's message, returns `code`
 
 #define HIPCHK(c, call)                                                                              \
@@ -377,7 +388,7 @@ struct TimerScope {
         // families whose scope holds ONE launch that goes through klt_launch (the order kernel in front of a tracker and the threshold
         // kernel behind the eigenvalue pass do not): timed by that dispatch's own timestamps.  Scopes with several launches keep the pair
         stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE || fam == F_CROWD_PREPARE || fam == F_CROWD ||
-                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN);
+                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY);
         if (stamps) { g_klt_stamp_start = t.a; g_klt_stamp_stop = t.b; }      // filled by the launch itself (klt_launch)
         else hipEventRecord(t.a, st);
     }
@@ -503,6 +514,10 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
 L0Plan plan_l0(const klt_ctx *c, int batch, int kind, int nc, int nr, bool uniform = true, bool want_hred = false, bool want_lean = false);
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
+// CLAHE switched on (klt_ctx::eqp.mode == 1): the 8-bit frames of these slots that have no valid equalised copy get one, enqueued on
+// `st` (behind the frames' uploads: the caller has waited for them there) -- the slots of one frame size in the same two launches.
+// KLT_ERR_STATE for an f32 slot, KLT_ERR_ARG for a frame the tile grid does not fit, KLT_ERR_NOMEM; *launched (optional): something was enqueued
+int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched = nullptr);
 // KLT_OPT_L0_LAZY_GRAD: whoever reads lv[0].img / .gx / .gy of a built slot calls this first.  The records of a lean slot are made from its
 // compact image by the gradient launch of the levels >= 1, on the main stream behind the slot's build (wait_built); a caller that
 // enqueues on the build stream is ordered behind it.  `asked` (every reader but the tracker's own fallback): the slot's next build is full.

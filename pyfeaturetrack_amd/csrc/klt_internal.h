@@ -174,6 +174,18 @@ struct CrowdArgs {
 };
 constexpr int kCrowdLdsStates = 24576;  // lists up to this length keep pixel and state of every candidate in LDS (5 bytes each: 120 KiB)
 
+// the two launches of an equalisation (equalize_kernels.hip) on up to KLT_MAX_BATCH 8-bit frames of one size: the
+// frames (src_pitch bytes from row to row, read only), their equalised copies (ncols bytes from row to row, 16-byte aligned) and a LUT
+// buffer per frame (tiles_x * tiles_y * 256 bytes, 16-byte aligned: written by the first launch, read by the second)
+struct EqualizeArgs {
+    const uint8_t *src[KLT_MAX_BATCH];
+    uint8_t *dst[KLT_MAX_BATCH];
+    uint8_t *lut[KLT_MAX_BATCH];
+    int ncols, nrows, src_pitch;
+    int tiles_x, tiles_y, clip_q8;
+    int split;                          // apply launch: workgroups per band of rows between two tile centres
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -477,6 +489,9 @@ void launch_homography_decide(hipStream_t s, const EpipolarArgs &a);
 void launch_crowd_prepare(hipStream_t s, const CrowdArgs &a);
 void launch_crowd_rank(hipStream_t s, const CrowdArgs &a);
 void launch_crowd_resolve(hipStream_t s, const CrowdArgs &a);
+// CLAHE (equalize_kernels.hip): the per-tile LUTs, then the interpolated frame; `batch` frames each
+void launch_clahe_lut(hipStream_t s, const EqualizeArgs &a, int batch);
+void launch_clahe_apply(hipStream_t s, const EqualizeArgs &a, int batch);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

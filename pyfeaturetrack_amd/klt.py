@@ -133,6 +133,13 @@ class KLT_TrackingContext:
         # ft.crowd.
         self.crowdingCheck = False
         self.crowding_min_distance = None
+        # CLAHE ingest stage (not in the reference): None, or "clahe" -- every 8-bit frame is equalised on the device in front of the
+        # pyramid build and of the selection (contrast-limited adaptive histogram equalisation: clahe_tiles tiles across and down,
+        # clahe_clip_limit times the mean bin, None or 0 = no clipping).  For low-contrast frames: a dark half, a
+        # backlit scene, a thermal camera squeezed into 8 bits.  KLTEqualizeImage(tc, img) returns the frame the tracker then sees.
+        self.equalization = None
+        self.clahe_tiles = (8, 8)
+        self.clahe_clip_limit = 3.0
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -784,6 +791,10 @@ def KLTPrintTrackingContext(tc):
     if getattr(tc, "crowdingCheck", False):          # (likewise)
         print("")
         for name in ("crowdingCheck", "crowding_min_distance"):
+            print("\t{0} = {1}".format(name, getattr(tc, name, None)))
+    if getattr(tc, "equalization", None) is not None:          # (likewise)
+        print("")
+        for name in ("equalization", "clahe_tiles", "clahe_clip_limit"):
             print("\t{0} = {1}".format(name, getattr(tc, name, None)))
     print("\n")
 

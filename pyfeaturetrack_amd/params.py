@@ -1,9 +1,10 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import collections
+import numbers
 
 import numpy as np
 
-from ._abi import KltAffineParams, KltCrowdParams, KltFbParams, KltLightParams, KltParams
+from ._abi import KltAffineParams, KltCrowdParams, KltEqualizeParams, KltFbParams, KltLightParams, KltParams
 from .convolve import _computeKernels
 from .klt_util import KLTComputeSmoothSigma
 
@@ -198,6 +199,68 @@ def crowd_params_from_tc(tc, ncols=None, nrows=None):
         raise ValueError("the crowding check takes frames of 1 .. 65535 columns and rows")
     cp.min_distance = int(dist)
     return cp
+
+
+EQUALIZATIONS = (None, "clahe")
+
+
+def equalize_params_from_tc(tc):
+    """tc.equalization (None, the default: mode 0; "clahe": mode 1) / tc.clahe_tiles ((8, 8): tiles across, tiles down) /
+    tc.clahe_clip_limit (3.0; None or 0: no clipping) -> klt_equalize_params, clip_q8 the limit times 256, rounded.  All three are read
+    with defaults: a tracking context made elsewhere has none of them.  ValueError -- before any device work -- for another switch value
+    and, with the switch on, for tiles that are no pair of integers in 1 .. 64 and for a limit that is not finite, is negative or is
+    above 4096 (switched off, the struct packs mode 0 and the defaults, as the other extensions' do)."""
+    mode = getattr(tc, "equalization", None)
+    if mode is None:                                        # (switched off: the other two are not looked at, the struct packs the defaults)
+        return KltEqualizeParams(0, 8, 8, 768)
+    if not isinstance(mode, str) or mode not in EQUALIZATIONS:
+        raise ValueError("tc.equalization must be None or 'clahe' (got {0!r})".format(mode))
+    tiles = getattr(tc, "clahe_tiles", (8, 8))
+    try:
+        values = tuple(tiles)
+    except TypeError:
+        values = None
+    if isinstance(tiles, (str, bytes)) or values is None or len(values) != 2 or not all(
+            isinstance(v, numbers.Integral) and not isinstance(v, (bool, np.bool_)) and 1 <= v <= 64 for v in values):
+        raise ValueError("tc.clahe_tiles must be (tiles_x, tiles_y), two integers in 1 .. 64 (got {0!r})".format(tiles))
+    limit = getattr(tc, "clahe_clip_limit", 3.0)
+    if limit is None:
+        limit = 0.0
+    if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, numbers.Real) or not 0.0 <= float(limit) <= 4096.0:      # (NaN fails)
+        raise ValueError("tc.clahe_clip_limit must be None or a number in 0 .. 4096 (got {0!r})".format(limit))
+    return KltEqualizeParams(1, int(values[0]), int(values[1]), int(round(float(limit) * 256.0)))
+
+
+def equalisable(ncols, nrows, tiles_x, tiles_y):
+    """include/klt_gpu.h, "CLAHE ingest stage": the tile grid fits the frame and the per-pixel division is a 32-bit one"""
+    if tiles_x > ncols or tiles_y > nrows:
+        return False
+    widest = 1
+    for n, t in ((ncols, tiles_x), (nrows, tiles_y)):
+        widest *= max([((k + 2) * n) // t - (k * n) // t for k in range(t - 1)] or [1])
+    return widest * 255 < 2 ** 32
+
+
+def equalization_for_frames(tc, *imgs):
+    """The klt_equalize_params of a call on these frames (equalize_params_from_tc).  Switched on, a ValueError that names tc.equalization
+    -- before any device work -- for a frame that is not a single-channel 8-bit image (a float array, a colour or "F" Pillow image) and
+    for a frame the tile grid does not fit."""
+    eq = equalize_params_from_tc(tc)
+    if eq.mode:
+        for img in imgs:
+            if isinstance(img, np.ndarray):
+                ok, (nrows, ncols) = img.dtype == np.uint8 and img.ndim == 2, img.shape[:2]
+                what = "a {0} array of {1} dimensions".format(img.dtype, img.ndim)
+            else:
+                ok, (ncols, nrows) = getattr(img, "mode", None) == "L", img.size
+                what = "an image of mode {0!r}".format(getattr(img, "mode", None))
+            if not ok:
+                raise ValueError("tc.equalization = 'clahe' takes single-channel 8-bit frames (a 2-D uint8 array or a Pillow image of "
+                                 "mode 'L'), not {0}".format(what))
+            if not equalisable(ncols, nrows, eq.tiles_x, eq.tiles_y):
+                raise ValueError("tc.equalization = 'clahe': a {0} by {1} frame does not take tc.clahe_tiles = ({2}, {3}) (more tiles "
+                                 "than pixels, or tiles too large for the 32-bit interpolation)".format(ncols, nrows, eq.tiles_x, eq.tiles_y))
+    return eq
 
 
 PostTrack = collections.namedtuple("PostTrack", "consensus crowd quality")

@@ -175,6 +175,8 @@ def _KLTSelectGoodFeatures(tc, img, nFeatures, mode, featurelist=None):
     mask = selection_mask_from_tc(tc, ncols, nrows)     # (TypeError / ValueError before any device work)
     from .params import select_grid_from_tc
     grid = select_grid_from_tc(tc)                      # (likewise)
+    from .params import equalization_for_frames
+    equalization_for_frames(tc, img)                    # (ValueError for tc.equalization on a frame it does not take, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                      # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -199,7 +201,8 @@ def _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask=None, grid=N
         # smoothed again; a new one goes to the slot the next KLTTrackFeatures call will look for it in (frame 1 -- or frame 2 while
         # sequential mode keeps the last frame in slot 1) and gets its whole pyramid, which that call then does not build.
         frames = cache_of(tc)
-        key = FrameKey(img)
+        from ._frames import equalization_tag
+        key = FrameKey(img, equalization_tag(tc))
         slot = frames.find(key, slots[:2], ctx)
         if slot is None:
             slot = slots[1] if (tc.sequentialMode and tc.pyramid_last is not None) else slots[0]
@@ -296,6 +299,29 @@ def KLTSelectGoodFeatures(tc, img, nFeatures):
     if KLT_verbose >= 1:
         print("\n\t{0} features found.\n".format(KLTCountRemainingFeatures(fl)))
     return fl
+
+
+def KLTEqualizeImage(tc, img):
+    """Not in the reference: the frame the tracker sees with tc.equalization = "clahe" -- `img` (a 2-D uint8 array or a Pillow image of mode
+    "L") equalised on the device under tc.clahe_tiles and tc.clahe_clip_limit, whatever tc.equalization says -- as a uint8 array
+    (DESIGN.md section 9l).  ValueError for another kind of image and for a frame the tile grid does not fit.
+    Not a pure query of the device context: the tiles and the clip limit are SET on it (klt_set_equalize_params; klt_equalize_u8 takes
+    the context's).  Where they differ from what it held, every slot's equalised frame is void and every slot's next build is a full one
+    (lean slots included), as after a change of tc.clahe_tiles between two KLT* calls.  Results do not change -- built pyramids stay,
+    and the frame cache goes by the parameters a slot was built under -- but a loop that calls this between tracking calls with other
+    parameters than the tracking context's own pays an equalisation per frame it would not pay otherwise."""
+    import types
+    from ._frames import pixels_of
+    from .params import equalization_for_frames, equalize_params_from_tc
+    on = types.SimpleNamespace(equalization="clahe", clahe_tiles=getattr(tc, "clahe_tiles", (8, 8)),
+                               clahe_clip_limit=getattr(tc, "clahe_clip_limit", 3.0))
+    eq = equalization_for_frames(on, img)               # (the refusals of a call with the switch on)
+    eq.mode = equalize_params_from_tc(tc).mode          # (what is sent keeps the tracking context's own switch)
+    ctx = context_of(tc)
+    with ctx.lock:
+        ctx.settle_deferred()
+        ctx.set_equalize_params(eq)
+        return ctx.equalize(pixels_of(img))
 
 
 def KLTReplaceLostFeatures(tc, img, featurelist):

@@ -11,12 +11,12 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import age_records, fb_params_from_tc, guess_records, light_params_from_tc, post_track_from_tc
+from .params import age_records, equalization_for_frames, fb_params_from_tc, guess_records, light_params_from_tc, post_track_from_tc
 from .backend import context_of, default_context  # noqa: F401
 from .backend import (CROWD_DTYPE, FEAT_DTYPE, QUALITY_DTYPE, PostTrackTargets, _FB_API_BACK, _FB_API_CROWD, _FB_API_CROWD_PREV, _FB_API_IN,
                       _FB_API_OUT, _FB_API_QUALITY)
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
-from ._frames import FrameKey, KLTForgetFrames, cache_of, settle_frames  # noqa: F401
+from ._frames import FrameKey, KLTForgetFrames, cache_of, equalization_tag, settle_frames  # noqa: F401
 from .selectGoodFeatures import _fix_window, _image_size, _slots_of, features_to_array, image_to_array
 # the reference binds the name at import (trackFeatures.py:7 `from selectGoodFeatures import KLT_verbose`): this module has its own
 # switch, and setting selectGoodFeatures.KLT_verbose later does not reach it
@@ -245,6 +245,7 @@ def _prepare_pair(tc, ctx, img1, img2, speculate=False):
     if frames.handles and not ctx.configured_for(tc):
         frames.keep_all_handles()                     # new parameters void every pyramid of the context: kept handles fetch theirs first
     ctx.configure(tc)
+    eq_tag = equalization_tag(tc)                 # tc.equalization: part of what a slot must hold to count as holding the image
     s1, s2, _ = _slots_of(tc)
     doubts = []
     sure = frames.trusting() or not speculate
@@ -274,7 +275,7 @@ def _prepare_pair(tc, ctx, img1, img2, speculate=False):
             from .error import KLTError
             KLTError("(KLTTrackFeatures) Size of incoming image ({0} by {1}) is different from size of previous image "
                      "({2} by {3})".format(ncols, nrows, tc.pyramid_last.ncols[0], tc.pyramid_last.nrows[0]))
-        k2 = FrameKey(img2)
+        k2 = FrameKey(img2, eq_tag)
         at2, doubt2 = locate(k2, (s2,))
         if at2 is None:
             frames.send(ctx, s2, k2)
@@ -288,7 +289,7 @@ def _prepare_pair(tc, ctx, img1, img2, speculate=False):
     else:
         # A slot that already holds exactly the pixels of one of the two images (every byte compared -- _frames.py) keeps it: the
         # reference converts and rebuilds both on every call, example1's ping-pong (example1.py:53-56) the same two 200 times.
-        k1, k2 = FrameKey(img1), FrameKey(img2)
+        k1, k2 = FrameKey(img1, eq_tag), FrameKey(img2, eq_tag)
         (at1, doubt1), (at2, doubt2) = locate(k1, (s1, s2)), locate(k2, (s1, s2))
         if at1 == s2 or at2 == s1:                    # the pair arrives the other way round (or shifted by one frame)
             ctx.swap_slots(s1, s2)
@@ -418,7 +419,11 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     steps each feature has been tracked (default: zeros, so list order decides which of two colliding tracks stays: the lower index).
     tc.crowding_last is then a backend.CROWD_DTYPE array of len(featurelist) -- age (what to hand to the next call), winner (the record a
     crowded one merged into), val (0 not tracked, 1 kept, 2 crowded).  Goes with everything but tc.affineConsistencyCheck >= 0
-    (ValueError), lighting compensation included: it reads no frame."""
+    (ValueError), lighting compensation included: it reads no frame.
+    tc.equalization = "clahe" (not in the reference): both frames are equalised on the device in front of their pyramid builds
+    (tc.clahe_tiles, tc.clahe_clip_limit), in both modes and with every other switch; the frames must be
+    single-channel 8-bit images the tile grid fits (ValueError).  A frame a slot holds equalised under other parameters, or as it is, is
+    built again; in sequential mode the pyramid kept from the last call stays what that call built."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -428,6 +433,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     guess = guess_records(guess, len(featurelist), tc.affineConsistencyCheck >= 0)      # (ValueError likewise)
     post_track_from_tc(tc)                            # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, likewise)
     age = age_records(age, len(featurelist))          # (ValueError for an `age` of another shape or kind, likewise)
+    equalization_for_frames(tc, img1, img2)           # (ValueError for tc.equalization on frames it does not take, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()

@@ -16,7 +16,7 @@ from ._frames import cache_of, pixels_of
 from .backend import (CROWD_DTYPE, FB_CHUNK, FEAT_DTYPE, QUALITY_DTYPE, REPLACING_SOME, SELECTING_ALL, Context, context_of,
                       _FB_GUESS, _FB_TABLE, _FBC_TABLE, _FBQ_TABLE, _MAX_FRAMES)       # (backend.py has the table of feature-buffer ids)
 from .klt import KLT_FeatureTable
-from .params import (NO_POST_TRACK, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc,
+from .params import (NO_POST_TRACK, equalization_for_frames, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc,
                      select_grid_from_tc, selection_mask_from_tc)
 from .selectGoodFeatures import _fix_window, _slots_of
 
@@ -160,6 +160,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     tc.crowding_min_distance - 1 px (None: tc.mindist) of each other.  `ft.crowd` is a [frames][features] array of backend.CROWD_DTYPE
     records -- age (the consecutive frames the slot has been tracked: the older of two colliding tracks stays), winner, val -- row k
     computed from row k - 1 and list row k, row 0 all zero.  Not together with the affine consistency check.
+    tc.equalization = "clahe": every frame is equalised on the device in front of its pyramid build (tc.clahe_tiles, tc.clahe_clip_limit;
+    DESIGN.md section 9l); the clip must then be of single-channel 8-bit frames the tile grid fits (ValueError).
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
@@ -168,6 +170,7 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     motion_prediction_from_tc(tc)        # (ValueError for an unknown tc.motionPrediction, or one together with the affine check, likewise)
     light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
     post_track_from_tc(tc)               # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, or a check beside one, likewise)
+    equalize_params_from_tc(tc)          # (ValueError for an unknown tc.equalization or parameters out of range, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -222,6 +225,9 @@ class _Sequence:
         self.ring = 3 if prefetch else 2
         first = pixels_of(next(self.frames))
         self.nrows, self.ncols = first.shape
+        # tc.equalization = "clahe": every frame is equalised in front of its build (the library's side of ctx.configure); the clip must
+        # be of 8-bit frames the tile grid fits (ValueError; `ingest` holds the later frames to it)
+        self.equalized = bool(equalization_for_frames(tc, first).mode)
         # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
         ctx.sync_select_mask(selection_mask_from_tc(tc, self.ncols, self.nrows))
         ctx.sync_select_grid(grid)          # tc.selectionGrid, read when the call started: the first selection and every replacement
@@ -259,6 +265,8 @@ class _Sequence:
             self.stager = _FrameStager(self.frames, stage, (self.nrows, self.ncols), workers=workers)
 
     def ingest(self, slot, img, k, staged=False, wait=True):
+        if self.equalized and (img.dtype != np.uint8 or img.ndim != 2):
+            raise ValueError("tc.equalization = 'clahe' takes single-channel 8-bit frames; frame {0} of the clip is not one".format(k))
         if img.shape != (self.nrows, self.ncols):
             from .error import KLTError
             KLTError("(KLTTrackSequence) Size of incoming image ({0} by {1}) is different from size of previous image "
