@@ -926,10 +926,10 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
 // its VALU issue time (profiles/README.md); here a WAVEFRONT owns a strip and walks it down a segment of rows on its own.
 //   Lane l owns the four columns x0 - 12 + 4 l ... + 3 of the strip at x0 = 232 * strip: lanes 3..60 are the strip's 232 output
 //   columns, lanes 0-2 and 61-63 the 12-column halo of the 21-tap reduction.  Per row: the lane's raw quad (requested PD rows ahead,
-//   held in registers), the samples left and right of it from the neighbouring lanes (ds_bpermute), the horizontal smoothing of the four
+//   held in registers), the samples left and right of it from the neighbouring lanes (a whole-wavefront DPP shift), the horizontal smoothing of the four
 //   columns into a rotating window of the last NS H-smoothed rows in registers (the row loop is unrolled NS times, so the window's
 //   indices are compile-time; kept widened for 5 taps, f32 and widened at use for 9), the vertical smoothing from the window, one
-//   16-byte store to the compact plane, and the same quad into a 1 KB row of LDS that only this wavefront touches, from which the lane
+//   16-byte store to the compact plane, and the same quad into a padded row of LDS (LW_ROW) that only this wavefront touches, from which the lane
 //   reads the rest of its 21-sample window (quads l - 2 .. l + 2 and the first sample of l + 3) for the H1 sample at column 4 l + 2 of
 //   its quad.  One wavefront's LDS operations complete in order: s_waitcnt is all that orders the row's store and its loads.
 // The NS - 1 rows above a segment are H-smoothed again (stage 1 only).  Rows go through the reflect map on the row index.  The first and
@@ -938,6 +938,21 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
 // hreduce_pair's sum), so the same values (header of this file).  The host takes it for frames of >= 256 columns and >= NS rows: one
 // reflection brings every index inside (columns reach 245 past the last strip's first, rows NS / 2 past either end).
 constexpr int LW_COLS = 232, LW_HALO = 12, LW_WAVES = 4;         // output columns of a strip, halo columns a side, wavefronts per workgroup
+// Wavefronts per SIMD the wave kernel asks the compiler for (its own constant: KLT_L0_WAVES bounds smooth_grad_rb and
+// smooth_grad_stream).  All four instantiations fit 96 VGPRs without scratch under a bound of four and of five alike, so a SIMD holds five
+// of them either way and the 9 x 34 x 16 = 4896 units of a sixteen-frame 1080p launch are resident at once (5120 slots;
+// tests/test_l0_wave_regs.py holds the figure).  The bound itself stays four: the headline did not pass its gate with five
+// (profiles/README.md).
+#ifndef KLT_L0_WAVE_PER_SIMD
+#define KLT_L0_WAVE_PER_SIMD 4
+#endif
+// A wavefront's LDS row: two quads of padding, the 64 quads of the lanes, two quads and one float of padding (kept a multiple of four
+// floats).  Lane l reads quads l - 2 .. l + 2 and the first float of quad l + 3 at constant offsets from ONE per-lane address, without a
+// clamp.  INVARIANT: nothing ever writes the padding, and only the six halo lanes (0 - 2, 61 - 63) can read it -- lanes 0 and 1 on the
+// left, 61 - 63 on the right -- whose H1 sample is never stored (out_lane); an output lane's window 4 l - 8 .. 4 l + 12 lies inside
+// quads 1 .. 63.  Whatever an earlier workgroup left in the padding therefore reaches no result.
+constexpr int LW_PAD_L = 8, LW_PAD_R = 12, LW_ROW = LW_PAD_L + 256 + LW_PAD_R;
+static_assert(LW_PAD_L >= 8 && LW_PAD_R >= 9 && LW_ROW % 4 == 0, "padding of the H1 window's reads");
 
 // The raw samples of one row and lane in flight: the RawQuad register of the aligned path, four zero-extended bytes of a u8 edge strip
 template <typename TIn, bool EDGE> struct WaveRaw { typedef typename RawQuad<TIn>::reg reg; };
@@ -946,13 +961,17 @@ __device__ __forceinline__ uint32_t wave_quad(uint4 e) { return e.x | e.y << 8 |
 __device__ __forceinline__ uint32_t wave_quad(uint32_t w) { return w; }
 __device__ __forceinline__ float4 wave_quad(float4 v) { return v; }
 
-__device__ __forceinline__ float lane_read(int lane_b /* 4 x source lane */, float v)
+// The value of lane l - 1 (UP = false) or l + 1 (UP = true) of the wavefront: a whole-wavefront DPP shift, which needs no index register
+// and no LDS queue slot (ds_bpermute needs both).  Lane 0 has no lane below it and lane 63 none above: they get 0 (bound_ctrl), in samples
+// that only reach columns of halo lanes which no stored output reads (lean_wave_segment).
+template <bool UP> __device__ __forceinline__ uint32_t lane_next(uint32_t v)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(lane_b, __builtin_bit_cast(int, v)));
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, UP ? 0x130 /* wave_shl:1 */ : 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
 }
+template <bool UP> __device__ __forceinline__ float lane_next(float v) { return __builtin_bit_cast(float, lane_next<UP>(__builtin_bit_cast(uint32_t, v))); }
 
 template <typename TIn, int NS, bool EDGE>
-__device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float *const wrow /* 2 x 256 floats of this wavefront */, const int b,
+__device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float *const wrow /* 2 x LW_ROW floats of this wavefront */, const int b,
                                                   const int nc, const int nr, const int x0, const int s0, const int ylim)
 {
     constexpr int rs = NS / 2, PD = NS % 3 == 0 ? 3 : NS;        // rows in flight: a divisor of the unroll count
@@ -978,10 +997,8 @@ __device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float
         xo[0] = (unsigned)cx * (unsigned)sizeof(TIn);
     }
     const unsigned xn = (unsigned)(EDGE ? reflect_once(cx + 4, nc) : cx + 4) * (unsigned)sizeof(TIn);
-    const int prev_b = 4 * max(lane - 1, 0), next_b = 4 * min(lane + 1, 63);
-    // LDS: quads l - 2, l - 1, l + 1, l + 2 and the first float of l + 3 (clamped: the halo lanes' H1 samples are not stored)
-    const int q_m2 = 4 * max(lane - 2, 0), q_m1 = 4 * max(lane - 1, 0), q_p1 = 4 * min(lane + 1, 63), q_p2 = 4 * min(lane + 2, 63),
-              q_p3 = 4 * min(lane + 3, 63);
+    // LDS: the lane's address in a padded row is that of quad l - 2; its own quad is two quads on (layout and invariant: LW_ROW above)
+    float *const wlane = wrow + 4 * lane;
     const int T = ylim - s0 + 2 * rs;                            // H-smoothed rows of the segment: step t makes frame row s0 - rs + t
 
     auto request = [&](int t, raw_t &q, float &nx) {
@@ -1025,13 +1042,13 @@ __device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float
             if (t + PD < T) request(t + PD, pre[u % PD], nxt[u % PD]);
             float4 mid = quad_f32(w), lo, hi;
             if constexpr (U8) {
-                lo = unpack_u8x4((uint32_t)__builtin_amdgcn_ds_bpermute(prev_b, (int)w));
-                hi = unpack_u8x4((uint32_t)__builtin_amdgcn_ds_bpermute(next_b, (int)w));
+                lo = unpack_u8x4(lane_next<false>(w));
+                hi = unpack_u8x4(lane_next<true>(w));
             } else {
-                lo.x = rs > 3 ? lane_read(prev_b, mid.x) : 0.f; lo.y = rs > 2 ? lane_read(prev_b, mid.y) : 0.f;
-                lo.z = rs > 1 ? lane_read(prev_b, mid.z) : 0.f; lo.w = lane_read(prev_b, mid.w);
-                hi.x = lane_read(next_b, mid.x); hi.y = rs > 1 ? lane_read(next_b, mid.y) : 0.f;
-                hi.z = rs > 2 ? lane_read(next_b, mid.z) : 0.f; hi.w = rs > 3 ? lane_read(next_b, mid.w) : 0.f;
+                lo.x = rs > 3 ? lane_next<false>(mid.x) : 0.f; lo.y = rs > 2 ? lane_next<false>(mid.y) : 0.f;
+                lo.z = rs > 1 ? lane_next<false>(mid.z) : 0.f; lo.w = lane_next<false>(mid.w);
+                hi.x = lane_next<true>(mid.x); hi.y = rs > 1 ? lane_next<true>(mid.y) : 0.f;
+                hi.z = rs > 2 ? lane_next<true>(mid.z) : 0.f; hi.w = rs > 3 ? lane_next<true>(mid.w) : 0.f;
             }
             if constexpr (NXT) if (lane == 63) hi.x = nx;
             // ---- horizontal smoothing of the four columns -> the window's slot u
@@ -1065,26 +1082,34 @@ __device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float
                 }
             }
             // ---- the H1 sample at column cx + 2: the row through this wavefront's LDS slot (by row parity), then the 21-tap sum
-            float *const slot = wrow + (t & 1) * 256;
+            float *const slot = wlane + (t & 1) * LW_ROW;        // (quad l - 2 of the row's slot)
             f32x4 cq;
             cq.x = c[0]; cq.y = c[1]; cq.z = c[2]; cq.w = c[3];
-            *(lds_quad_ptr)(slot + 4 * lane) = cq;
+            *(lds_quad_ptr)(slot + 8) = cq;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const f32x4 qa = *(lds_quad_ptr)(slot + q_m2), qb = *(lds_quad_ptr)(slot + q_m1), qd = *(lds_quad_ptr)(slot + q_p1),
-                        qe = *(lds_quad_ptr)(slot + q_p2);
-            const float qf = *(lds_f32_ptr)(slot + q_p3);
-            double m[NR];
-            m[0] = (double)qa.x; m[1] = (double)qa.y; m[2] = (double)qa.z; m[3] = (double)qa.w;
-            m[4] = (double)qb.x; m[5] = (double)qb.y; m[6] = (double)qb.z; m[7] = (double)qb.w;
-            m[8] = (double)c[0]; m[9] = (double)c[1]; m[10] = (double)c[2]; m[11] = (double)c[3];
-            m[12] = (double)qd.x; m[13] = (double)qd.y; m[14] = (double)qd.z; m[15] = (double)qd.w;
-            m[16] = (double)qe.x; m[17] = (double)qe.y; m[18] = (double)qe.z; m[19] = (double)qe.w;
-            m[20] = (double)qf;
-            double acc = m[HR] * kr.k[HR];                       // (hreduce_pair's sum at the centre m[HR])
-#pragma unroll
-            for (int jj = -HR; jj < 0; jj++) acc = acc + (m[HR + jj] + m[HR - jj]) * kr.k[HR + jj];
+            // hreduce_pair's sum at the centre m[HR] of the window m[0 .. 20] = quads l - 2, l - 1, c, l + 1, l + 2 and the first sample of
+            // l + 3: the samples are read and widened in the order the sum takes them, the centre, then (m[0], m[20]) ... (m[9], m[11]),
+            // in three stages so that a third of the window is live at a time (same operations, same order, same roundings; the LDS reads are
+            // volatile and keep their order, and the scheduler leaves the widenings with their stage: no scheduling barrier is needed)
+            auto pair = [&](double acc, float lo_s, float hi_s, int j) { return acc + ((double)lo_s + (double)hi_s) * kr.k[j]; };
+            double acc = (double)c[2] * kr.k[HR];
+            {
+                const f32x4 qa = *(lds_quad_ptr)(slot), qe = *(lds_quad_ptr)(slot + 16);
+                const float qf = *(lds_f32_ptr)(slot + 20);
+                acc = pair(acc, qa.x, qf, 0);
+                acc = pair(acc, qa.y, qe.w, 1);
+                acc = pair(acc, qa.z, qe.z, 2);
+                acc = pair(acc, qa.w, qe.y, 3);
+                const f32x4 qb = *(lds_quad_ptr)(slot + 4), qd = *(lds_quad_ptr)(slot + 12);
+                acc = pair(acc, qb.x, qe.x, 4);
+                acc = pair(acc, qb.y, qd.w, 5);
+                acc = pair(acc, qb.z, qd.z, 6);
+                acc = pair(acc, qb.w, qd.y, 7);
+                acc = pair(acc, c[0], qd.x, 8);
+                acc = pair(acc, c[1], c[3], 9);
+            }
             const int xg = cx / 4;
             if (out_lane && (!EDGE || xg < h1_nc)) plane_store(h1, 4u * ((unsigned)y * (unsigned)h1_nc + (unsigned)xg), (float)acc);
         }
@@ -1094,9 +1119,9 @@ __device__ __forceinline__ void lean_wave_segment(const SmoothGradArgs &a, float
 // grid = ceil(units / 4) workgroups of four wavefronts; unit = (frame * nsegs + segment) * nstrips + strip, any four units to a workgroup
 // (a wavefront per SIMD).  `a` stays the first parameter, as for smooth_grad_stream.
 template <typename TIn, int NS>
-__global__ __launch_bounds__(64 * LW_WAVES, KLT_L0_WAVES) void smooth_grad_lean_wave(SmoothGradArgs a, int seg_h, int nstrips, int nsegs, int nunits)
+__global__ __launch_bounds__(64 * LW_WAVES, KLT_L0_WAVE_PER_SIMD) void smooth_grad_lean_wave(SmoothGradArgs a, int seg_h, int nstrips, int nsegs, int nunits)
 {
-    __shared__ __attribute__((aligned(16))) float lds[LW_WAVES * 2 * 256];
+    __shared__ __attribute__((aligned(16))) float lds[LW_WAVES * 2 * LW_ROW];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int unit = blockIdx.x * LW_WAVES + wave;
     if (unit >= nunits) return;
@@ -1107,8 +1132,8 @@ __global__ __launch_bounds__(64 * LW_WAVES, KLT_L0_WAVES) void smooth_grad_lean_
     const int ylim = min(s0 + seg_h, nr);
     // every column the strip reads inside the frame, its quads aligned
     const bool inside = (nc & 3) == 0 && x0 >= LW_HALO && x0 + LW_COLS + LW_HALO + (NS / 2 > 3 ? 4 : 0) <= nc && x0 / 4 + LW_COLS / 4 <= a.h1_nc;
-    if (inside) lean_wave_segment<TIn, NS, false>(a, lds + wave * 512, b, nc, nr, x0, s0, ylim);
-    else lean_wave_segment<TIn, NS, true>(a, lds + wave * 512, b, nc, nr, x0, s0, ylim);
+    if (inside) lean_wave_segment<TIn, NS, false>(a, lds + wave * (2 * LW_ROW), b, nc, nr, x0, s0, ylim);
+    else lean_wave_segment<TIn, NS, true>(a, lds + wave * (2 * LW_ROW), b, nc, nr, x0, s0, ylim);
 }
 
 // The f32-rounded horizontal result is kept in LDS as the double it widens to (one widening per sample instead of one
