@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path / klt_set_remap / klt_remap_u8 / klt_download_remapped_u8 / klt_remap_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
@@ -772,6 +772,45 @@ int klt_equalize_path(klt_ctx *ctx);
  * frames"; nothing is enqueued and the slot builds again with mode 0.  The slot's equalised frame lives in a buffer of its own, allocated
  * when first needed (KLT_ERR_NOMEM leaves the slot as it was), freed by klt_slot_free, travelling with klt_swap_slots.  With mode 0 no
  * launch, no allocation and no event is added to any call. */
+
+/* ---- Remap ingest stage (not in the reference) -------------------------------------------------------------------- */
+/* A fixed-point remap with bilinear interpolation of an 8-bit frame in front of the level-0 kernel -- lens undistortion, stereo
+ * rectification, fisheye to pinhole, a rotated camera mount: the epipolar and the homography check assume a pinhole camera, and on a
+ * wide-angle lens they flag good tracks toward the frame's edges.  With a map set every reader of a slot's raw 8-bit frame -- the level-0
+ * launch of a build, the two-pass build, the selection on the raw frame (use_pyramid = 0), the CLAHE stage -- reads a remapped copy the
+ * slot keeps instead; the frame itself (an adopted frame is the caller's memory) is read and never written.  With both ingest stages on
+ * the order is remap, then CLAHE.
+ *
+ * THE RULE (integer arithmetic only; the device equals it byte for byte).  Inputs: an 8-bit source frame ncols x nrows; a map of the
+ * same ncols x nrows that holds for each destination pixel two int32 values mx, my: the source position in 1/256 px, pixel centres at
+ * integers (KLT's coordinates).  Any int32 value is legal.
+ *  1 clamp     X = min(max(mx, 0), (ncols - 1) * 256), Y = min(max(my, 0), (nrows - 1) * 256): edge replication, not a fill colour (a
+ *              fill would draw a curved black border that the selection takes for corners).
+ *  2 split     x0 = X >> 8, fx = X & 255, x1 = min(x0 + 1, ncols - 1); y0, fy, y1 likewise.
+ *  3 pixel     out = ((256 - fx) (256 - fy) p00 + fx (256 - fy) p10 + (256 - fx) fy p01 + fx fy p11 + 32768) >> 16 in unsigned 32 bits,
+ *              p10 the pixel at (x1, y0), p01 at (x0, y1).  The largest sum is 65536 * 255 + 32768; the weights sum to 65536, so a
+ *              constant frame stays constant under every map.
+ * The destination has the shape of the source (a map that changes the frame size is not offered).  The clamp is done on the device for
+ * every entry: no map content makes a read outside the source rows.  One launch per build, the frames of the build in it. */
+/* The context's one map: two planes of ncols * nrows int32 (row-major, ncols entries from row to row), copied to the device before the
+ * call returns.  NULL, NULL switches the stage off (the default; the sizes are then not looked at); one NULL, or a size outside
+ * 1 .. 65535, is KLT_ERR_ARG.  A new map -- also the same values again -- or none voids every slot's remapped and equalised frame and
+ * counts as a change of the taps does: every slot's next build is a full one.  The pyramids a slot holds stay what their build made
+ * them: the caller rebuilds.  Synchronises. */
+int klt_set_remap(klt_ctx *ctx, const int32_t *map_x, const int32_t *map_y, int ncols, int nrows);
+/* A host frame (pitch bytes from row to row) in, the remapped host frame (ncols bytes from row to row) out: the kernel by name under
+ * the context's map, whatever else is set.  Synchronises.  No map set: KLT_ERR_STATE; a size that is not the map's: KLT_ERR_ARG. */
+int klt_remap_u8(klt_ctx *ctx, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst);
+/* The remapped frame the slot's last build (or selection on the raw frame) read, [nrows][ncols] bytes: KLT_ERR_STATE if that was not a
+ * remapped one -- no map set, or a new frame or a new map since.  Synchronises. */
+int klt_download_remapped_u8(klt_ctx *ctx, int slot, uint8_t *dst);
+/* 0: the last klt_build_pyramids* enqueued no remap launch (no map set, or every slot's remapped frame was still valid), 1: it did. */
+int klt_remap_path(klt_ctx *ctx);
+/* With a map set, klt_build_pyramids* and the selection on the raw frame refuse an f32 slot (KLT_ERR_STATE, "remapping takes 8-bit
+ * frames") and a slot whose frame is not of the map's size (KLT_ERR_ARG, naming both sizes); nothing is enqueued, and the slot builds
+ * again with no map or a fitting one.  The slot's remapped frame lives in a buffer of its own, allocated when first needed (KLT_ERR_NOMEM
+ * leaves the slot as it was), freed by klt_slot_free, travelling with klt_swap_slots.  With no map set no launch, no allocation and no
+ * event is added to any call. */
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

@@ -224,6 +224,10 @@ SYMBOLS = {
     "klt_equalize_u8": (_I, [_P, _P, _I, _I, _I, _P]),
     "klt_download_equalized_u8": (_I, [_P, _I, _P]),
     "klt_equalize_path": (_I, [_P]),
+    "klt_set_remap": (_I, [_P, _P, _P, _I, _I]),
+    "klt_remap_u8": (_I, [_P, _P, _I, _I, _I, _P]),
+    "klt_download_remapped_u8": (_I, [_P, _I, _P]),
+    "klt_remap_path": (_I, [_P]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -159,6 +159,15 @@ def equalization_tag(tc):
     return bytes(eq) if eq.mode else None
 
 
+def ingest_tag(tc):
+    """what FrameKey takes as `eq` for a call on this tracking context, both ingest stages counted: `equalization_tag` with tc.remap
+    off, else that tag paired with the table's serial -- a slot built under another table, or under none, does not hold the image"""
+    from .params import remap_from_tc
+    table = remap_from_tc(tc)
+    eq = equalization_tag(tc)
+    return eq if table is None else (eq, "remap", table.serial)
+
+
 def pixels_of(img):
     """the image as a uint8 / float32 array of its own (`image_to_array`; a Pillow image is copied / converted out of its row table)"""
     key = FrameKey(img)

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
                    KltCrowd, KltCrowdParams, KltEqualizeParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
-from .params import affine_params_from_tc, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, taps_from_params
+from .params import affine_params_from_tc, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, remap_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
 assert FEAT_DTYPE.itemsize == C.sizeof(KltFeat)
@@ -178,8 +178,10 @@ class Context:
     def configure(self, tc):
         light = light_params_from_tc(tc)                 # (ValueError for a combination that is not offered, before anything is set)
         eq = equalize_params_from_tc(tc)                 # (likewise for tc.equalization and its parameters)
+        remap = remap_from_tc(tc)                        # (likewise for tc.remap)
         self.set_params(params_from_tc(tc))
         self.set_equalize_params(eq, only_if_on=True)
+        self.sync_remap(remap)
         self.set_light_params(light)
         self.set_affine_params(affine_params_from_tc(tc))
         fb = fb_params_from_tc(tc)
@@ -222,6 +224,52 @@ class Context:
     def equalize_path(self):
         """klt_equalize_path: 1 if the last build enqueued equalisation launches, 0 if not (a diagnostic)"""
         return self._check(self._lib.klt_equalize_path(self._h))
+
+    # ------------------------------------------------ remap ingest stage (klt_set_remap)
+    def set_remap(self, map_x=None, map_y=None):
+        """klt_set_remap: two int32 arrays of one 2-D shape (nrows, ncols), source positions in 1/256 px; None, None switches the stage off"""
+        if map_x is None and map_y is None:
+            self._check(self._lib.klt_set_remap(self._h, None, None, 0, 0))
+        elif map_x is None or map_y is None:
+            raise ValueError("both planes of the map, or neither")
+        else:
+            mx, my = np.ascontiguousarray(map_x, np.int32), np.ascontiguousarray(map_y, np.int32)
+            if mx.ndim != 2 or mx.shape != my.shape:
+                raise ValueError("expected two 2-D arrays of one shape")
+            self._check(self._lib.klt_set_remap(self._h, mx.ctypes.data, my.ctypes.data, mx.shape[1], mx.shape[0]))
+        self._remap_set, self._remap_serial = map_x is not None, None      # (a map sent by hand is no table's)
+
+    def sync_remap(self, table):
+        """tc.remap as the call found it (params.remap_from_tc: a KLT_RemapTable or None): the map goes to the library only when the
+        table's serial is not the one the context holds, None only to switch off a map that is set -- a context that never had one gets
+        no call at all."""
+        if table is None:
+            if getattr(self, "_remap_set", False):
+                self.set_remap()
+        elif not getattr(self, "_remap_set", False) or getattr(self, "_remap_serial", None) != table.serial:
+            self.set_remap(table.map_x, table.map_y)
+            self._remap_serial = table.serial
+
+    def remap(self, img, ncols=None):
+        """klt_remap_u8: the remapped frame of a 2-D uint8 array under the context's map.  `ncols`: the frame is the first ncols columns
+        of `img` (whose width is then the pitch)"""
+        a = np.ascontiguousarray(img)
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("expected a 2-D uint8 image")
+        nrows, pitch = a.shape
+        out = np.empty((nrows, pitch if ncols is None else int(ncols)), np.uint8)
+        self._check(self._lib.klt_remap_u8(self._h, a.ctypes.data, out.shape[1], nrows, pitch, out.ctypes.data))
+        return out
+
+    def download_remapped(self, slot, ncols, nrows):
+        """klt_download_remapped_u8: the remapped frame the slot's last build read"""
+        out = np.empty((nrows, ncols), np.uint8)
+        self._check(self._lib.klt_download_remapped_u8(self._h, slot, out.ctypes.data))
+        return out
+
+    def remap_path(self):
+        """klt_remap_path: 1 if the last build enqueued a remap launch, 0 if not (a diagnostic)"""
+        return self._check(self._lib.klt_remap_path(self._h))
 
     # ------------------------------------------------ gain / bias tracking (klt_set_light_params)
     def set_light_params(self, lp=None, mode=None):

@@ -298,10 +298,10 @@ void klt_destroy(klt_ctx *c)
     for (void *p : c->dev_allocs) hipFree(p);
     for (hipEvent_t e : c->ring) hipEventDestroy(e);
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
-    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); }
+    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm); }
     for (FeatBuf &b : c->fbs)
         if (!b.view) hipFree(b.d);
-    hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg);
+    hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg); hipFree(c->rmp.d);
     hipFree(c->sel_img); hipFree(c->sel_rec); hipFree(c->sat); hipFree(c->valmap);
     for (auto &e : c->pre) hipFree(e.keys);
     hipFree(c->sat_pre);
@@ -361,6 +361,36 @@ int klt_set_equalize_params(klt_ctx *c, const klt_equalize_params *p)
     if (std::memcmp(p, &c->eqp, sizeof(*p)) == 0) return KLT_OK;
     c->eqp = *p;
     for (Slot &s : c->slots) s.eq_valid = false;
+    c->cfg_gen++;
+    return KLT_OK;
+}
+
+// Remap ingest stage: the context's one map.  A new map (or none) voids every slot's remapped and equalised frame and counts as a change
+// of the taps (cfg_gen), like new equalisation parameters.  The upload is synchronous: the host arrays are the caller's again on return.
+int klt_set_remap(klt_ctx *c, const int32_t *map_x, const int32_t *map_y, int ncols, int nrows)
+{
+    if (!c) return KLT_ERR_ARG;
+    if ((map_x == nullptr) != (map_y == nullptr)) return fail(c, KLT_ERR_ARG, "remap: both planes of the map, or neither");
+    if (!map_x && !c->rmp.d) return KLT_OK;                 // off, and it was off: nothing changes
+    if (map_x && (ncols < 1 || ncols > 65535 || nrows < 1 || nrows > 65535)) return fail(c, KLT_ERR_ARG, "remap: the map's sizes must lie in 1 .. 65535");
+    if (map_x && (long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "remap: map too large (2^27 entries or more: no frame of that size is taken)");
+    if (c->capturing) return fail(c, KLT_ERR_STATE, "the map cannot change during a stream capture");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = sync_all(c)) return rc;                    // a launch may still read the old map
+    int32_t *d = nullptr;
+    size_t plane = 0;
+    if (map_x) {
+        const size_t N = (size_t)ncols * nrows;
+        plane = (N + 63) & ~(size_t)63;
+        DEVALLOC(c, d, 2 * plane * sizeof(int32_t));       // (KLT_ERR_NOMEM: the context keeps the map it had)
+        hipError_t e = hipMemcpy(d, map_x, N * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + plane, map_y, N * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); return fail(c, KLT_ERR_DEVICE, hipGetErrorString(e)); }
+    }
+    hipFree(c->rmp.d);
+    c->rmp.d = d; c->rmp.plane = plane;
+    c->rmp.nc = d ? ncols : 0; c->rmp.nr = d ? nrows : 0;
+    for (Slot &s : c->slots) s.rm_valid = s.eq_valid = false;
     c->cfg_gen++;
     return KLT_OK;
 }
@@ -456,7 +486,7 @@ int klt_slot_free(klt_ctx *c, int slot)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     Slot &s = c->slots[slot];
-    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq);
+    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm);
     s = Slot();
     return KLT_OK;
 }

@@ -57,7 +57,7 @@ int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int p
     s->raw_kind = kind;
     s->f32_in_raw = false;
     s->pyr_valid = false;
-    s->eq_valid = false;
+    s->eq_valid = s->rm_valid = false;
     return 0;
 }
 
@@ -95,6 +95,57 @@ int layout_pyramid(klt_ctx *c, Slot *s)
     }
     s->nlev = L;
     s->ss = ss;
+    return 0;
+}
+
+// ---- remap ingest stage (klt_set_remap; the rule: include/klt_gpu.h)
+// what a slot must be for the context's map: an 8-bit frame of the map's size
+static int check_remappable(klt_ctx *c, const Slot *s)
+{
+    if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, "remapping takes 8-bit frames");
+    if (s->nc != c->rmp.nc || s->nr != c->rmp.nr)
+        return fail(c, KLT_ERR_ARG, "remapping: the frame is " + std::to_string(s->nc) + " by " + std::to_string(s->nr) + ", the map " +
+                                        std::to_string(c->rmp.nc) + " by " + std::to_string(c->rmp.nr));
+    return 0;
+}
+
+// the launch on a.batch frames of the map's size as `a` names them (src, dst, src_pitch filled in by the caller)
+static void enqueue_remap(klt_ctx *c, RemapArgs &a, hipStream_t st)
+{
+    a.map_x = c->rmp.d; a.map_y = c->rmp.d + c->rmp.plane;
+    a.ncols = c->rmp.nc; a.nrows = c->rmp.nr;
+    TimerScope t(c, F_REMAP, (double)a.ncols * a.nrows * (8.0 + 2.0 * a.batch), st);
+    launch_remap(st, a);
+}
+
+// (declared in klt_context.h)
+int ensure_remapped(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched /* = nullptr */)
+{
+    if (launched) *launched = false;
+    std::vector<Slot *> todo;
+    // every refusal first: nothing is allocated or enqueued for a call that fails
+    for (int i = 0; i < n; i++) {
+        Slot *s = slots[i];
+        if (int rc = check_remappable(c, s)) return rc;
+        if (s->rm_valid) continue;
+        if (c->capturing) return fail(c, KLT_ERR_STATE, "a frame would have to be remapped during a stream capture");
+        todo.push_back(s);
+    }
+    for (Slot *s : todo)
+        if (int rc = ensure(c, s->rm, s->rm_cap, (size_t)s->nc * s->nr)) return rc;      // (a slot that gets none keeps rm == nullptr, rm_valid false)
+    for (size_t i0 = 0; i0 < todo.size(); i0 += KLT_MAX_BATCH) {      // (one size: the map's)
+        RemapArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.batch = (int)std::min(todo.size() - i0, (size_t)KLT_MAX_BATCH);
+        for (int b = 0; b < a.batch; b++) {
+            a.src[b] = frame8(todo[i0 + b]);
+            a.dst[b] = todo[i0 + b]->rm;
+        }
+        a.src_pitch = c->rmp.nc;
+        enqueue_remap(c, a, st);
+    }
+    for (Slot *s : todo) { s->rm_valid = true; s->eq_valid = false; }      // (an equalised copy is one of the remapped frame)
+    if (launched) *launched = !todo.empty();
     return 0;
 }
 
@@ -171,7 +222,7 @@ int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool
         for (size_t i = i0; i < todo.size() && B < KLT_MAX_BATCH; i++)
             if (!done[i] && todo[i]->nc == nc && todo[i]->nr == nr) {
                 Slot *s = todo[i];
-                a.src[B] = s->u8_ext ? s->u8_ext : s->u8;
+                a.src[B] = c->rmp.d ? s->rm : frame8(s);     // (a map set: the caller has run ensure_remapped in front)
                 a.dst[B] = s->eq;
                 a.lut[B] = s->eq + eq_lut_offset(nc, nr);
                 B++;
@@ -469,6 +520,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     for (int i = 0; i < n; i++) {
         if (int rc = get_slot(c, slot_ids[i], &sl[i], false)) return rc;
         if (sl[i]->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
+        if (c->rmp.d) { if (int rc = check_remappable(c, sl[i])) return rc; }
         if (c->eqp.mode == 1 && sl[i]->raw_kind != 1) return fail(c, KLT_ERR_STATE, "equalisation takes 8-bit frames");
         for (int j = 0; j < i; j++)
             if (sl[j] == sl[i]) return fail(c, KLT_ERR_ARG, "slot listed twice");
@@ -490,7 +542,13 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     c->last_build_on_bstream = on_bstream ? 1 : 0;
     // CLAHE ingest stage: the frames that have no valid equalised copy get one here, behind their uploads on the stream the build runs
     // on; the level-0 launches below read the copies (raw8).  The mark at the end of the build covers this reader of the raw frames too.
-    c->eq_path = 0;
+    // Remap ingest stage: in front of it on the same stream -- with both on, the equalised copy is one of the remapped frame.
+    c->eq_path = c->rm_path = 0;
+    if (c->rmp.d) {
+        bool launched = false;
+        if (int rc = ensure_remapped(c, sl.data(), n, c->work, &launched)) return rc;
+        c->rm_path = launched ? 1 : 0;
+    }
     if (c->eqp.mode == 1) {
         bool launched = false;
         if (int rc = ensure_equalized(c, sl.data(), n, c->work, &launched)) return rc;
@@ -711,7 +769,7 @@ static int upload_async(klt_ctx *c, int slot, const void *px, int ncols, int nro
     s->raw_kind = esz == 1 ? 1 : 2;
     s->f32_in_raw = esz != 1;
     s->pyr_valid = false;
-    s->eq_valid = false;
+    s->eq_valid = s->rm_valid = false;
     return KLT_OK;
 }
 
@@ -758,7 +816,7 @@ int klt_device_free(klt_ctx *c, void *p)
             const uint8_t *lo = (const uint8_t *)p, *hi = lo + c->dev_alloc_bytes[i];
             for (Slot &s : c->slots)
                 if (s.u8_ext && s.u8_ext >= lo && s.u8_ext < hi) {
-                    s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.eq_valid = false; s.gen = 0; s.nc = s.nr = 0;
+                    s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.eq_valid = s.rm_valid = false; s.gen = 0; s.nc = s.nr = 0;
                 }
             // likewise a selection mask that lives inside it (klt_set_select_mask_device): the context has no mask any more
             if (c->mask && c->mask >= lo && c->mask < hi) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }
@@ -802,7 +860,7 @@ int klt_slot_adopt_u8(klt_ctx *c, int slot, const uint8_t *dev_px, int ncols, in
     s->raw_kind = 1;
     s->f32_in_raw = false;
     s->pyr_valid = false;
-    s->eq_valid = false;
+    s->eq_valid = s->rm_valid = false;
     return KLT_OK;
 }
 
@@ -956,6 +1014,59 @@ int klt_equalize_path(klt_ctx *c)
 {
     if (!c) return KLT_ERR_ARG;
     return c->eq_path;
+}
+
+// ------------------------------------------------------------------------------- remap ingest stage
+// the remap kernel on one host frame under the context's map: one allocation holds the frame as the caller laid it out and the remapped frame
+int klt_remap_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
+{
+    if (!c || !src || !dst) return fail(c, KLT_ERR_ARG, "null argument");
+    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols || (long long)ncols * nrows > kMaxFramePixels ||
+        (long long)pitch * nrows > 2 * kMaxFramePixels)
+        return fail(c, KLT_ERR_ARG, "bad image geometry");
+    if (!c->rmp.d) return fail(c, KLT_ERR_STATE, "no map set (klt_set_remap)");
+    if (ncols != c->rmp.nc || nrows != c->rmp.nr)
+        return fail(c, KLT_ERR_ARG, "remapping: the frame is " + std::to_string(ncols) + " by " + std::to_string(nrows) + ", the map " +
+                                        std::to_string(c->rmp.nc) + " by " + std::to_string(c->rmp.nr));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = (size_t)ncols * nrows, src_bytes = (size_t)pitch * (nrows - 1) + ncols;
+    const size_t dst_off = (src_bytes + 255) & ~(size_t)255;
+    uint8_t *d = nullptr;
+    DEVALLOC(c, d, dst_off + N);
+    hipError_t e = hipMemcpyAsync(d, src, src_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        RemapArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.src[0] = d; a.dst[0] = d + dst_off;
+        a.src_pitch = pitch;
+        a.batch = 1;
+        enqueue_remap(c, a, c->stream);
+        e = hipMemcpyAsync(dst, d + dst_off, N, hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    hipFree(d);
+    if (e != hipSuccess) return fail(c, KLT_ERR_DEVICE, hipGetErrorString(e));
+    return KLT_OK;
+}
+
+int klt_download_remapped_u8(klt_ctx *c, int slot, uint8_t *dst)
+{
+    if (!c || !dst) return fail(c, KLT_ERR_ARG, "null argument");
+    Slot *s;
+    if (int rc = get_slot(c, slot, &s, false)) return rc;
+    if (!s->rm_valid || !s->rm) return fail(c, KLT_ERR_STATE, "the slot holds no remapped frame (no map set, or a new frame or a new map since its last build)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = wait_built(c, s)) return rc;                 // the remap may have run on the build stream
+    HIPCHK(c, hipMemcpyAsync(dst, s->rm, (size_t)s->nc * s->nr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KLT_OK;
+}
+
+int klt_remap_path(klt_ctx *c)
+{
+    if (!c) return KLT_ERR_ARG;
+    return c->rm_path;
 }
 
 int klt_gradients_f32(klt_ctx *c, const float *src, int ncols, int nrows, const double *gauss, int ng,

@@ -34,10 +34,10 @@ namespace kltapi {
 
 
 enum Family { F_SMOOTH_GRAD, F_PYR_REDUCE, F_GRAD, F_SMOOTH_H, F_SMOOTH_V, F_PYR_H, F_PYR_V, F_GRAD_H, F_GRAD_V, F_TRACK,
-              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_COUNT };
+              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_REMAP, F_COUNT };
 inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_reduce", "gradients", "smooth_h", "smooth_v", "pyramid_h",
                                           "pyramid_v", "gradient_h", "gradient_v", "track", "sat_rows", "sat_cols",
-                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply"};
+                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply", "remap"};
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
@@ -94,6 +94,12 @@ struct Slot {
     uint8_t *eq = nullptr;
     size_t eq_cap = 0;                // bytes
     bool eq_valid = false;
+    // klt_set_remap: the remapped copy of the 8-bit frame (nc x nr bytes), allocated when first needed.  rm_valid: it was made from the
+    // frame the slot holds now under the map the context holds now (cleared wherever eq_valid is -- new equalisation parameters
+    // excepted, they leave it -- and by a new map)
+    uint8_t *rm = nullptr;
+    size_t rm_cap = 0;                // bytes
+    bool rm_valid = false;
 };
 
 inline const float *rawf(const Slot *s) { return s->f32_in_raw ? reinterpret_cast<const float *>(s->u8) : s->f32; }
@@ -175,6 +181,10 @@ struct klt_ctx {
     int device = -1;
     klt_equalize_params eqp{0, 8, 8, 768};    // CLAHE ingest stage (klt_set_equalize_params): off; 8 x 8 tiles, clip limit 3.0
     int eq_path = 0;                          // klt_equalize_path: the last build enqueued equalisation launches
+    // remap ingest stage (klt_set_remap): the context's one map, two planes of nc * nr int32 in one allocation (x first; the y plane
+    // begins on a 256-byte boundary), uploaded synchronously by the set call and freed with the context.  d == nullptr: the stage is off
+    struct RemapTable { int32_t *d = nullptr; size_t plane = 0; /* int32 from x to y */ int nc = 0, nr = 0; } rmp;
+    int rm_path = 0;                          // klt_remap_path: the last build enqueued a remap launch
     hipStream_t stream = nullptr;     // uploads, pyramid build, selection, tracker
     hipStream_t cstream = nullptr;    // asynchronous frame ingest from pinned host memory (created on first use)
     // ... and more copy streams: consecutive uploads go round-robin over all of them, i.e. over several DMA engines (2 MB frames: 44 GB/s
@@ -347,9 +357,11 @@ struct klt_ctx {
 
 namespace kltapi {
 
-// the 8-bit frame a slot's readers take: the caller's device memory (adopted), the slot's own raw buffer, or -- CLAHE switched on -- the
-// equalised copy (ensure_equalized has made it)
-inline const uint8_t *raw8(const klt_ctx *c, const Slot *s) { return c->eqp.mode == 1 ? s->eq : (s->u8_ext ? s->u8_ext : s->u8); }
+// the 8-bit frame a slot holds as it came: the caller's device memory (adopted) or the slot's own raw buffer
+inline const uint8_t *frame8(const Slot *s) { return s->u8_ext ? s->u8_ext : s->u8; }
+// the 8-bit frame a slot's readers take: the equalised copy with CLAHE switched on (ensure_equalized has made it), else the remapped
+// copy with a map set (ensure_remapped has made it), else the frame as it came
+inline const uint8_t *raw8(const klt_ctx *c, const Slot *s) { return c->eqp.mode == 1 ? s->eq : (c->rmp.d ? s->rm : frame8(s)); }
 
 int fail(klt_ctx *c, int code, const std::string &msg);      // sets the context's message, returns `code`
 
@@ -388,7 +400,7 @@ struct TimerScope {
         // families whose scope holds ONE launch that goes through klt_launch (the order kernel in front of a tracker and the threshold
         // kernel behind the eigenvalue pass do not): timed by that dispatch's own timestamps.  Scopes with several launches keep the pair
         stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE || fam == F_CROWD_PREPARE || fam == F_CROWD ||
-                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY);
+                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY || fam == F_REMAP);
         if (stamps) { g_klt_stamp_start = t.a; g_klt_stamp_stop = t.b; }      // filled by the launch itself (klt_launch)
         else hipEventRecord(t.a, st);
     }
@@ -518,6 +530,10 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
 // `st` (behind the frames' uploads: the caller has waited for them there) -- the slots of one frame size in the same two launches.
 // KLT_ERR_STATE for an f32 slot, KLT_ERR_ARG for a frame the tile grid does not fit, KLT_ERR_NOMEM; *launched (optional): something was enqueued
 int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched = nullptr);
+// A map set (klt_ctx::rmp.d): the 8-bit frames of these slots that have no valid remapped copy get one, enqueued on `st` like the
+// equalised copies, in front of them -- the slots of a call in one launch per KLT_MAX_BATCH.  KLT_ERR_STATE for an f32 slot, KLT_ERR_ARG
+// for a frame whose size is not the map's, KLT_ERR_NOMEM; *launched (optional): something was enqueued
+int ensure_remapped(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched = nullptr);
 // KLT_OPT_L0_LAZY_GRAD: whoever reads lv[0].img / .gx / .gy of a built slot calls this first.  The records of a lean slot are made from its
 // compact image by the gradient launch of the levels >= 1, on the main stream behind the slot's build (wait_built); a caller that
 // enqueues on the build stream is ordered behind it.  `asked` (every reader but the tracker's own fallback): the slot's next build is full.

@@ -186,6 +186,17 @@ struct EqualizeArgs {
     int split;                          // apply launch: workgroups per band of rows between two tile centres
 };
 
+// the launch of a remap (remap_kernels.hip) on `batch` (up to KLT_MAX_BATCH) 8-bit frames of one size under one
+// map: the frames (src_pitch bytes from row to row, read only), their remapped copies (ncols bytes from row to row, 16-byte aligned) and
+// the map as two planes of ncols * nrows int32 (1/256 px, any value; 16-byte aligned)
+struct RemapArgs {
+    const uint8_t *src[KLT_MAX_BATCH];
+    uint8_t *dst[KLT_MAX_BATCH];
+    const int32_t *map_x, *map_y;
+    int ncols, nrows, src_pitch;
+    int batch;
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -492,6 +503,8 @@ void launch_crowd_resolve(hipStream_t s, const CrowdArgs &a);
 // CLAHE (equalize_kernels.hip): the per-tile LUTs, then the interpolated frame; `batch` frames each
 void launch_clahe_lut(hipStream_t s, const EqualizeArgs &a, int batch);
 void launch_clahe_apply(hipStream_t s, const EqualizeArgs &a, int batch);
+// remap (remap_kernels.hip): the a.batch frames in one launch
+void launch_remap(hipStream_t s, const RemapArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

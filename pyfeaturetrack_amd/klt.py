@@ -140,6 +140,13 @@ class KLT_TrackingContext:
         self.equalization = None
         self.clahe_tiles = (8, 8)
         self.clahe_clip_limit = 3.0
+        # Remap ingest stage (not in the reference): None, or a KLT_RemapTable (KLTCreateRemap, KLTUndistortMap) -- every 8-bit frame is
+        # remapped on the device in front of the pyramid build and of the selection, and in front of the equalisation (a fixed-point
+        # bilinear remap: lens undistortion, stereo rectification, fisheye to pinhole, a rotated mount).  Features
+        # then live in the rectified frame, where the epipolar and the homography check's pinhole model holds.  KLTRemapImage(tc, img)
+        # returns the frame the tracker then sees, KLTRemapValidMask(table) a tc.selectionMask that keeps the selection off replicated
+        # edges, KLTRemapSourcePositions(table, x, y) where rectified positions lie in the incoming frame.
+        self.remap = None
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()
@@ -796,6 +803,9 @@ def KLTPrintTrackingContext(tc):
         print("")
         for name in ("equalization", "clahe_tiles", "clahe_clip_limit"):
             print("\t{0} = {1}".format(name, getattr(tc, name, None)))
+    if getattr(tc, "remap", None) is not None:                 # (likewise)
+        shape = getattr(tc.remap, "shape", None)
+        print("\n\tremap = a {0} by {1} table (serial {2})".format(shape[1], shape[0], tc.remap.serial) if shape else "\n\tremap = {0!r}".format(tc.remap))
     print("\n")
 
 

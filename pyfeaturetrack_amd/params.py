@@ -1,5 +1,6 @@
 """KLT_TrackingContext -> klt_params (include/klt_gpu.h) and the three tap sets."""
 import collections
+import itertools
 import numbers
 
 import numpy as np
@@ -261,6 +262,152 @@ def equalization_for_frames(tc, *imgs):
                 raise ValueError("tc.equalization = 'clahe': a {0} by {1} frame does not take tc.clahe_tiles = ({2}, {3}) (more tiles "
                                  "than pixels, or tiles too large for the 32-bit interpolation)".format(ncols, nrows, eq.tiles_x, eq.tiles_y))
     return eq
+
+
+# ---------------------------------------------------------------------------------------------- remap ingest stage
+_remap_serials = itertools.count(1)
+_INT32_MIN, _INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+class KLT_RemapTable:
+    """A remap for tc.remap (include/klt_gpu.h, "Remap ingest stage"): map_x, map_y -- int32 arrays of shape (nrows, ncols), for each
+    pixel of the rectified frame its source position in 1/256 px -- frozen (writeable = False), with a process-wide serial number: the
+    device context compares serials, not 16 MB of map, on every call.  Made by KLTCreateRemap / KLTUndistortMap."""
+    __slots__ = ("map_x", "map_y", "serial")
+
+    def __init__(self, map_x, map_y):
+        ax, ay = np.asarray(map_x), np.asarray(map_y)
+        for a in (ax, ay):
+            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+                raise TypeError("a remap takes integer arrays (source positions in 1/256 px), not {0}".format(a.dtype))
+        if ax.ndim != 2 or ay.ndim != 2 or ax.shape != ay.shape:
+            raise ValueError("a remap takes two 2-D arrays of one shape (got {0} and {1})".format(ax.shape, ay.shape))
+        if not (1 <= ax.shape[0] <= 65535 and 1 <= ax.shape[1] <= 65535):
+            raise ValueError("a remap takes frames of 1 .. 65535 columns and rows")
+        for a in (ax, ay):
+            if a.size and (int(a.min()) < _INT32_MIN or int(a.max()) > _INT32_MAX):
+                raise ValueError("a remap's entries must fit 32 bits")
+        self.map_x, self.map_y = (np.array(a, dtype=np.int32, order="C") for a in (ax, ay))      # (copies)
+        self.map_x.setflags(write=False)
+        self.map_y.setflags(write=False)
+        self.serial = next(_remap_serials)
+
+    @property
+    def shape(self):
+        return self.map_x.shape
+
+    def __setattr__(self, name, value):
+        if hasattr(self, "serial"):                         # (the serial is set last)
+            raise AttributeError("a KLT_RemapTable is immutable")
+        object.__setattr__(self, name, value)
+
+
+def KLTCreateRemap(map_x, map_y):
+    """Not in the reference: a KLT_RemapTable from two 2-D integer arrays of one shape (nrows, ncols) -- for each pixel of the frame the
+    tracker is to see, the position in the incoming frame it is read from, in 1/256 px, pixel centres at integers; any int32 value is
+    legal (positions outside the frame read the nearest edge pixel).  The arrays are copied.  TypeError for float arrays, ValueError for
+    shapes that differ."""
+    return KLT_RemapTable(map_x, map_y)
+
+
+def _distort(x, y, dist):
+    """forward Brown-Conrady: normalised pinhole coordinates -> normalised distorted coordinates"""
+    k1, k2, p1, p2, k3 = dist
+    r2 = x * x + y * y
+    radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    return (x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x),
+            y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)
+
+
+def _camera(matrix, what):
+    k = np.asarray(matrix, np.float64)
+    if k.shape != (3, 3) or not np.isfinite(k).all() or k[0, 0] == 0.0 or k[1, 1] == 0.0:
+        raise ValueError("{0} must be a finite 3 x 3 matrix with non-zero focal lengths".format(what))
+    return k[0, 0], k[1, 1], k[0, 2], k[1, 2]
+
+
+def KLTUndistortMap(ncols, nrows, camera_matrix, dist_coeffs, new_camera_matrix=None):
+    """Not in the reference: the KLT_RemapTable that undoes a lens's distortion.  Host numpy in FP64, the forward Brown-Conrady model
+    with coefficients (k1, k2, p1, p2[, k3]) -- no iteration: a pixel (u, v) of the rectified frame under new_camera_matrix (None: the
+    camera matrix) is normalised, x = (u - cx') / fx', y = (v - cy') / fy'; distorted, r2 = x x + y y, radial = 1 + k1 r2 + k2 r2^2 +
+    k3 r2^3, xd = x radial + 2 p1 x y + p2 (r2 + 2 x x), yd = y radial + p1 (r2 + 2 y y) + 2 p2 x y; and projected with the camera
+    matrix, us = fx xd + cx, vs = fy yd + cy (the matrices' focal lengths and principal point are read, a skew is not).  Entries are
+    rint(256 us), rint(256 vs), clipped to int32."""
+    ncols, nrows = int(ncols), int(nrows)
+    if not (1 <= ncols <= 65535 and 1 <= nrows <= 65535):
+        raise ValueError("a remap takes frames of 1 .. 65535 columns and rows")
+    dist = np.asarray(dist_coeffs, np.float64).ravel()
+    if dist.size not in (4, 5) or not np.isfinite(dist).all():
+        raise ValueError("dist_coeffs must be (k1, k2, p1, p2) or (k1, k2, p1, p2, k3), finite")
+    dist = np.concatenate([dist, np.zeros(5 - dist.size)])
+    fx, fy, cx, cy = _camera(camera_matrix, "camera_matrix")
+    nfx, nfy, ncx, ncy = (fx, fy, cx, cy) if new_camera_matrix is None else _camera(new_camera_matrix, "new_camera_matrix")
+    v, u = np.mgrid[0:nrows, 0:ncols].astype(np.float64)
+    xd, yd = _distort((u - ncx) / nfx, (v - ncy) / nfy, dist)
+    entries = [np.clip(np.rint(256.0 * s), _INT32_MIN, _INT32_MAX).astype(np.int64) for s in (fx * xd + cx, fy * yd + cy)]
+    return KLT_RemapTable(entries[0], entries[1])
+
+
+def _table(table):
+    if not isinstance(table, KLT_RemapTable):
+        raise TypeError("expected a KLT_RemapTable (KLTCreateRemap, KLTUndistortMap), got {0!r}".format(type(table).__name__))
+    return table
+
+
+def KLTRemapValidMask(table, margin=0):
+    """Not in the reference: a uint8 array for tc.selectionMask -- 1 where the map's (unclamped) source position lies inside the frame
+    by `margin` px on both axes, 0 where the remapped frame shows replicated edge pixels (or comes within `margin` of them)."""
+    t = _table(table)
+    nrows, ncols = t.shape
+    m = int(round(float(margin) * 256.0))
+    ok = (t.map_x >= m) & (t.map_x <= (ncols - 1) * 256 - m) & (t.map_y >= m) & (t.map_y <= (nrows - 1) * 256 - m)
+    return ok.astype(np.uint8)
+
+
+def KLTRemapSourcePositions(table, x, y):
+    """Not in the reference: where positions of the rectified frame (what the tracker reports with tc.remap set) lie in the incoming
+    frame -- the map read bilinearly at (x, y) in FP64, in px; positions outside the frame read the map's edge.  At whole positions
+    these are the map's entries over 256."""
+    t = _table(table)
+    nrows, ncols = t.shape
+    x, y = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64))
+    xc, yc = np.clip(x, 0.0, ncols - 1.0), np.clip(y, 0.0, nrows - 1.0)
+    x0, y0 = np.floor(xc).astype(np.int64), np.floor(yc).astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, ncols - 1), np.minimum(y0 + 1, nrows - 1)
+    ax, ay = xc - x0, yc - y0
+    out = []
+    for m in (t.map_x, t.map_y):
+        m = m.astype(np.float64)
+        out.append(((1.0 - ax) * (1.0 - ay) * m[y0, x0] + ax * (1.0 - ay) * m[y0, x1] + (1.0 - ax) * ay * m[y1, x0] + ax * ay * m[y1, x1]) / 256.0)
+    return out[0], out[1]
+
+
+def remap_from_tc(tc):
+    """tc.remap (None, the default: the stage is off) -> the KLT_RemapTable of the call, or None.  Read with a default: a tracking context
+    made elsewhere has no such attribute.  TypeError -- before any device work -- for anything else."""
+    table = getattr(tc, "remap", None)
+    if table is not None and not isinstance(table, KLT_RemapTable):
+        raise TypeError("tc.remap must be None or a KLT_RemapTable (KLTCreateRemap, KLTUndistortMap), got {0!r}".format(type(table).__name__))
+    return table
+
+
+def remap_for_frames(tc, *imgs):
+    """The KLT_RemapTable of a call on these frames (remap_from_tc), or None.  Switched on, a ValueError that names tc.remap -- before any
+    device work -- for a frame that is not a single-channel 8-bit image and for a frame whose shape is not the table's."""
+    table = remap_from_tc(tc)
+    if table is not None:
+        for img in imgs:
+            if isinstance(img, np.ndarray):
+                ok, shape = img.dtype == np.uint8 and img.ndim == 2, tuple(img.shape[:2])
+                what = "a {0} array of {1} dimensions".format(img.dtype, img.ndim)
+            else:
+                ok, shape = getattr(img, "mode", None) == "L", (img.size[1], img.size[0])
+                what = "an image of mode {0!r}".format(getattr(img, "mode", None))
+            if not ok:
+                raise ValueError("tc.remap takes single-channel 8-bit frames (a 2-D uint8 array or a Pillow image of mode 'L'), not {0}".format(what))
+            if shape != table.shape:
+                raise ValueError("tc.remap: the frame is {0} by {1}, the table {2} by {3}".format(shape[1], shape[0], table.shape[1], table.shape[0]))
+    return table
 
 
 PostTrack = collections.namedtuple("PostTrack", "consensus crowd quality")

@@ -175,8 +175,9 @@ def _KLTSelectGoodFeatures(tc, img, nFeatures, mode, featurelist=None):
     mask = selection_mask_from_tc(tc, ncols, nrows)     # (TypeError / ValueError before any device work)
     from .params import select_grid_from_tc
     grid = select_grid_from_tc(tc)                      # (likewise)
-    from .params import equalization_for_frames
+    from .params import equalization_for_frames, remap_for_frames
     equalization_for_frames(tc, img)                    # (ValueError for tc.equalization on a frame it does not take, likewise)
+    remap_for_frames(tc, img)                           # (TypeError / ValueError for tc.remap, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                      # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -201,8 +202,8 @@ def _select_locked(ctx, tc, img, nFeatures, mode, featurelist, mask=None, grid=N
         # smoothed again; a new one goes to the slot the next KLTTrackFeatures call will look for it in (frame 1 -- or frame 2 while
         # sequential mode keeps the last frame in slot 1) and gets its whole pyramid, which that call then does not build.
         frames = cache_of(tc)
-        from ._frames import equalization_tag
-        key = FrameKey(img, equalization_tag(tc))
+        from ._frames import ingest_tag
+        key = FrameKey(img, ingest_tag(tc))
         slot = frames.find(key, slots[:2], ctx)
         if slot is None:
             slot = slots[1] if (tc.sequentialMode and tc.pyramid_last is not None) else slots[0]
@@ -322,6 +323,27 @@ def KLTEqualizeImage(tc, img):
         ctx.settle_deferred()
         ctx.set_equalize_params(eq)
         return ctx.equalize(pixels_of(img))
+
+
+from .params import KLT_RemapTable, KLTCreateRemap, KLTRemapSourcePositions, KLTRemapValidMask, KLTUndistortMap  # noqa: E402,F401  (the remap ingest stage's host side)
+
+
+def KLTRemapImage(tc, img):
+    """Not in the reference: the frame the tracker sees with tc.remap set -- `img` (a 2-D uint8 array or a Pillow image of mode "L", of
+    the table's shape) remapped on the device under the table (klt_remap_u8: the kernel by name), as a uint8 array (DESIGN.md section
+    9m); with tc.equalization on as well the tracker sees KLTEqualizeImage of this.  ValueError with tc.remap None, for another kind of
+    image and for a frame whose shape is not the table's.  The table is SET on the device context where it holds another (as any KLT*
+    call with this tracking context does)."""
+    from ._frames import pixels_of
+    from .params import remap_for_frames
+    table = remap_for_frames(tc, img)
+    if table is None:
+        raise ValueError("tc.remap is None: there is no map to remap the frame under")
+    ctx = context_of(tc)
+    with ctx.lock:
+        ctx.settle_deferred()
+        ctx.sync_remap(table)
+        return ctx.remap(pixels_of(img))
 
 
 def KLTReplaceLostFeatures(tc, img, featurelist):

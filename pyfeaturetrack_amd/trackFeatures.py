@@ -11,12 +11,12 @@ from . import selectGoodFeatures as _sgf
 import numpy as np
 
 from ._abi import KltBackendError
-from .params import age_records, equalization_for_frames, fb_params_from_tc, guess_records, light_params_from_tc, post_track_from_tc
+from .params import age_records, equalization_for_frames, fb_params_from_tc, guess_records, light_params_from_tc, post_track_from_tc, remap_for_frames
 from .backend import context_of, default_context  # noqa: F401
 from .backend import (CROWD_DTYPE, FEAT_DTYPE, QUALITY_DTYPE, PostTrackTargets, _FB_API_BACK, _FB_API_CROWD, _FB_API_CROWD_PREV, _FB_API_IN,
                       _FB_API_OUT, _FB_API_QUALITY)
 from .klt import KLTCountRemainingFeatures, kltState, shared_store  # noqa: F401
-from ._frames import FrameKey, KLTForgetFrames, cache_of, equalization_tag, settle_frames  # noqa: F401
+from ._frames import FrameKey, KLTForgetFrames, cache_of, equalization_tag, ingest_tag, settle_frames  # noqa: F401
 from .selectGoodFeatures import _fix_window, _image_size, _slots_of, features_to_array, image_to_array
 # the reference binds the name at import (trackFeatures.py:7 `from selectGoodFeatures import KLT_verbose`): this module has its own
 # switch, and setting selectGoodFeatures.KLT_verbose later does not reach it
@@ -245,7 +245,7 @@ def _prepare_pair(tc, ctx, img1, img2, speculate=False):
     if frames.handles and not ctx.configured_for(tc):
         frames.keep_all_handles()                     # new parameters void every pyramid of the context: kept handles fetch theirs first
     ctx.configure(tc)
-    eq_tag = equalization_tag(tc)                 # tc.equalization: part of what a slot must hold to count as holding the image
+    eq_tag = ingest_tag(tc)                       # tc.equalization, tc.remap: part of what a slot must hold to count as holding the image
     s1, s2, _ = _slots_of(tc)
     doubts = []
     sure = frames.trusting() or not speculate
@@ -423,7 +423,11 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     tc.equalization = "clahe" (not in the reference): both frames are equalised on the device in front of their pyramid builds
     (tc.clahe_tiles, tc.clahe_clip_limit), in both modes and with every other switch; the frames must be
     single-channel 8-bit images the tile grid fits (ValueError).  A frame a slot holds equalised under other parameters, or as it is, is
-    built again; in sequential mode the pyramid kept from the last call stays what that call built."""
+    built again; in sequential mode the pyramid kept from the last call stays what that call built.
+    tc.remap = a KLT_RemapTable (not in the reference): both frames are remapped on the device in front of their pyramid builds, and in
+    front of the equalisation, in both modes and with every other switch; features live in the rectified frame.
+    The frames must be single-channel 8-bit images of the table's shape (ValueError).  A frame a slot holds under another table, or as
+    it is, is built again."""
     if KLT_verbose >= 1:
         ncols, nrows = _image_size(img1)
         print("(KLT) Tracking {0} features in a {1} by {2} image...  ".format(
@@ -434,6 +438,7 @@ def KLTTrackFeatures(tc, img1, img2, featurelist, guess=None, age=None):
     post_track_from_tc(tc)                            # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, likewise)
     age = age_records(age, len(featurelist))          # (ValueError for an `age` of another shape or kind, likewise)
     equalization_for_frames(tc, img1, img2)           # (ValueError for tc.equalization on frames it does not take, likewise)
+    remap_for_frames(tc, img1, img2)                  # (TypeError / ValueError for tc.remap, likewise)
     ctx = context_of(tc)
     with ctx.lock:                                    # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()

@@ -16,7 +16,7 @@ from ._frames import cache_of, pixels_of
 from .backend import (CROWD_DTYPE, FB_CHUNK, FEAT_DTYPE, QUALITY_DTYPE, REPLACING_SOME, SELECTING_ALL, Context, context_of,
                       _FB_GUESS, _FB_TABLE, _FBC_TABLE, _FBQ_TABLE, _MAX_FRAMES)       # (backend.py has the table of feature-buffer ids)
 from .klt import KLT_FeatureTable
-from .params import (NO_POST_TRACK, equalization_for_frames, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc,
+from .params import (NO_POST_TRACK, equalization_for_frames, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc, remap_for_frames, remap_from_tc,
                      select_grid_from_tc, selection_mask_from_tc)
 from .selectGoodFeatures import _fix_window, _slots_of
 
@@ -162,6 +162,8 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     computed from row k - 1 and list row k, row 0 all zero.  Not together with the affine consistency check.
     tc.equalization = "clahe": every frame is equalised on the device in front of its pyramid build (tc.clahe_tiles, tc.clahe_clip_limit;
     DESIGN.md section 9l); the clip must then be of single-channel 8-bit frames the tile grid fits (ValueError).
+    tc.remap = a KLT_RemapTable: every frame is remapped on the device in front of its pyramid build and of the equalisation (DESIGN.md
+    section 9m); the clip must then be of single-channel 8-bit frames of the table's shape (ValueError).
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
@@ -171,6 +173,7 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     light_params_from_tc(tc, sequence=True)      # (ValueError: tc.lightingCompensation is offered by KLTTrackFeatures alone)
     post_track_from_tc(tc)               # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, or a check beside one, likewise)
     equalize_params_from_tc(tc)          # (ValueError for an unknown tc.equalization or parameters out of range, likewise)
+    remap_from_tc(tc)                    # (TypeError for a tc.remap that is no KLT_RemapTable, likewise)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -228,6 +231,8 @@ class _Sequence:
         # tc.equalization = "clahe": every frame is equalised in front of its build (the library's side of ctx.configure); the clip must
         # be of 8-bit frames the tile grid fits (ValueError; `ingest` holds the later frames to it)
         self.equalized = bool(equalization_for_frames(tc, first).mode)
+        # tc.remap: likewise every frame is remapped in front of its build; 8-bit frames of the table's shape (ValueError)
+        self.remapped = remap_for_frames(tc, first) is not None
         # tc.selectionMask: one static mask for the first selection and every replacement of the clip (ValueError for another shape)
         ctx.sync_select_mask(selection_mask_from_tc(tc, self.ncols, self.nrows))
         ctx.sync_select_grid(grid)          # tc.selectionGrid, read when the call started: the first selection and every replacement
@@ -267,6 +272,8 @@ class _Sequence:
     def ingest(self, slot, img, k, staged=False, wait=True):
         if self.equalized and (img.dtype != np.uint8 or img.ndim != 2):
             raise ValueError("tc.equalization = 'clahe' takes single-channel 8-bit frames; frame {0} of the clip is not one".format(k))
+        if self.remapped and (img.dtype != np.uint8 or img.ndim != 2):
+            raise ValueError("tc.remap takes single-channel 8-bit frames; frame {0} of the clip is not one".format(k))
         if img.shape != (self.nrows, self.ncols):
             from .error import KLTError
             KLTError("(KLTTrackSequence) Size of incoming image ({0} by {1}) is different from size of previous image "
