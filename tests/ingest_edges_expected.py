@@ -1,0 +1,499 @@
+"""TEST INFRASTRUCTURE ONLY -- the edge tables of the two ingest stages (CLAHE: csrc/equalize_kernels.hip; remap: csrc/remap_kernels.hip):
+named cases at the bounds of the kernels' loops and of their 32-bit arithmetic, the functions that say which class of those loops and
+bounds a case reaches (plain Python, computed from the case alone), the frames, seeded draws, and copies of the two rules
+(tests/equalize_expected.py, tests/remap_expected.py) that can be evaluated in bands of rows and with one wrong step each.
+
+The class functions mirror the kernels' constants below; tests/test_ingest_edges_rule.py reads them out of the sources and compares."""
+from collections import namedtuple
+from functools import lru_cache
+
+import numpy as np
+
+import equalize_expected as ee
+import remap_expected as re_
+
+# csrc/equalize_kernels.hip, enqueue_equalize (csrc/api_frames.hip), csrc/remap_kernels.hip
+LUT_THREADS, HIST_COPIES, APPLY_THREADS = 1024, 16, 256
+SPLIT_TARGET, SPLIT_ROWS = 1024, 4
+PIECE, PIECES_ACROSS, GROUP_ROWS = 4, 16, 16
+MAX_BATCH = 32
+INT32_MIN, INT32_MAX = re_.INT32_MIN, re_.INT32_MAX
+BAND = 128
+
+CLAHE_WRONG = ("bins_mod_2_16", "excess_mod_2_16", "clip_product_mod_2_32", "cap_without_max", "remainder_to_first_bins",
+               "remainder_255_shifted", "numerator_mod_2_32", "product_wrapped_int32", "tie_downward", "centre_counted_with_gt",
+               "edges_from_floor_width")
+REMAP_WRONG = ("clamp_to_n", "no_min", "round_32767", "fx_fy_exchanged", "clamp_after_shift")
+
+
+# ------------------------------------------------------------------------------------------------------------------ CLAHE: the rule
+def _edges(n, tiles, wrong=None):
+    if wrong == "edges_from_floor_width":
+        return np.arange(tiles + 1, dtype=np.int64) * (n // tiles)
+    return (np.arange(tiles + 1, dtype=np.int64) * n) // tiles
+
+
+def _centres(n, tiles, wrong=None):
+    e = _edges(n, tiles, wrong)
+    return e[:-1] + e[1:]
+
+
+def _axis(n, tiles, wrong=None):
+    """ee.axis_weights with the edges and the comparison open to a wrong step"""
+    c = _centres(n, tiles, wrong)
+    p = 2 * np.arange(n, dtype=np.int64) + 1
+    count = np.searchsorted(c, p, side="left" if wrong == "centre_counted_with_gt" else "right")
+    inner = (count >= 1) & (count < tiles)
+    k = np.clip(count - 1, 0, tiles - 1)
+    first = np.where(count == 0, 0, k)
+    second = np.where(inner, k + 1, first)
+    k2 = np.minimum(k + 1, tiles - 1)
+    return first, second, np.where(inner, p - c[k], 0), np.where(inner, c[k2] - c[k], 1)
+
+
+def tile_values(hist, area, clip_q8, wrong=None):
+    """step 2 of the rule on one tile's 256 bin counts -> (lut, what the clip did: cap, excess; the largest numerator)"""
+    h = np.array(hist, np.int64)
+    if wrong == "bins_mod_2_16":
+        h %= 1 << 16
+    cap = excess = 0
+    if clip_q8 > 0:
+        product = clip_q8 * area
+        if wrong == "clip_product_mod_2_32":
+            product %= 1 << 32
+        cap = product >> 16
+        if wrong != "cap_without_max":
+            cap = max(1, cap)
+        excess = int(np.maximum(h - cap, 0).sum())
+        if wrong == "excess_mod_2_16":
+            excess %= 1 << 16
+        h = np.minimum(h, cap) + excess // 256
+        r = excess % 256
+        if r:
+            if wrong == "remainder_to_first_bins":
+                h[:r] += 1
+            elif wrong == "remainder_255_shifted" and r == 255:
+                h[(np.arange(r, dtype=np.int64) * 256) // r + 1] += 1
+            else:
+                h[(np.arange(r, dtype=np.int64) * 256) // r] += 1
+    num = np.cumsum(h) * 255 + area // 2
+    largest = int(num.max())
+    if wrong == "numerator_mod_2_32":
+        num %= 1 << 32
+    return num // area, cap, excess, largest
+
+
+def clahe(img, tiles_x, tiles_y, clip_q8, band=BAND, wrong=None, stats=None):
+    """ee.clahe, the interpolation evaluated `band` rows at a time (None: all at once); `wrong`: one step of CLAHE_WRONG done wrongly;
+    `stats`: a dict that receives what the class functions report of the arithmetic"""
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim == 2
+    nrows, ncols = img.shape
+    assert ee.equalisable(ncols, nrows, tiles_x, tiles_y)
+    xe, ye = _edges(ncols, tiles_x, wrong), _edges(nrows, tiles_y, wrong)
+    lut = np.zeros((tiles_y, tiles_x, 256), np.int64)
+    tiles = []
+    for j in range(tiles_y):
+        for i in range(tiles_x):
+            tile = img[ye[j]:ye[j + 1], xe[i]:xe[i + 1]]
+            hist = np.bincount(tile.ravel(), minlength=256)
+            lut[j, i], cap, excess, largest = tile_values(hist, tile.size, clip_q8, wrong)
+            tiles.append(dict(area=int(tile.size), bin=int(hist.max()), cap=int(cap), excess=int(excess), numerator=largest))
+    x0, x1, wx, dx = _axis(ncols, tiles_x, wrong)
+    y0, y1, wy, dy = _axis(nrows, tiles_y, wrong)
+    X0, X1, WX, DX = x0[None, :], x1[None, :], wx[None, :], dx[None, :]
+    out = np.empty((nrows, ncols), np.uint8)
+    product = 0
+    rounding = set()
+    for a in range(0, nrows, band or nrows):
+        b = min(nrows, a + (band or nrows))
+        v = img[a:b].astype(np.intp)
+        Y0, Y1, WY, DY = y0[a:b, None], y1[a:b, None], wy[a:b, None], dy[a:b, None]
+        terms = [lut[Y0, X0, v] * (DX - WX) * (DY - WY), lut[Y0, X1, v] * WX * (DY - WY), lut[Y1, X0, v] * (DX - WX) * WY,
+                 lut[Y1, X1, v] * WX * WY]
+        if wrong == "product_wrapped_int32":
+            terms = [((t + (1 << 31)) % (1 << 32)) - (1 << 31) for t in terms]
+        d = DX * DY
+        s = terms[0] + terms[1] + terms[2] + terms[3]
+        q = (s + ((d - 1) // 2 if wrong == "tie_downward" else d // 2)) // d
+        if stats is not None:
+            product = max(product, max(int(t.max()) for t in terms))
+            rem = s - (s // d) * d
+            turn = d - d // 2                                  # the smallest remainder that rounds up
+            for what, hit in (("at the turn", rem == turn), ("below the turn", rem == turn - 1)):
+                for parity, of in (("even D", d % 2 == 0), ("odd D", d % 2 == 1)):
+                    if (hit & of).any():
+                        rounding.add("%s, %s" % (what, parity))
+        if wrong is None:
+            assert q.min() >= 0 and q.max() <= 255
+        out[a:b] = q.astype(np.uint8)
+    if stats is not None:
+        stats.update(tiles=tiles, single_product=product, rounding=sorted(rounding))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ CLAHE: the cases
+# maker: "random" / "two_bin" / "constant" / "noise" (seeded), "large_noise" / "large_constant" (the module's one large frame, cut)
+ClaheCase = namedtuple("ClaheCase", "ncols nrows pitch tiles_x tiles_y clip_q8 maker seed")
+LARGE = (4096, 4200)                                         # (ncols, nrows) of the one large frame
+
+
+@lru_cache(maxsize=None)
+def large_noise():
+    f = np.random.RandomState(4096).randint(0, 256, (LARGE[1], LARGE[0]), dtype=np.uint8)
+    f.setflags(write=False)
+    return f
+
+
+def noise_frame(ncols, nrows, seed):
+    return np.random.RandomState(seed).randint(0, 256, (nrows, ncols), dtype=np.uint8)
+
+
+def clahe_frame(case):
+    if case.maker == "random":
+        return ee.random_frame(case.ncols, case.nrows, case.seed)
+    if case.maker == "two_bin":
+        return ee.two_bin_frame(case.ncols, case.nrows, case.seed)
+    if case.maker == "constant":
+        return ee.constant_frame(case.ncols, case.nrows)
+    if case.maker == "noise":
+        return noise_frame(case.ncols, case.nrows, case.seed)
+    if case.maker == "large_noise":
+        return large_noise()[:case.nrows, :case.ncols]
+    assert case.maker == "large_constant", case.maker
+    return np.full((case.nrows, case.ncols), 77, np.uint8)
+
+
+def _clahe_edges():
+    t = {}
+    # the LUT kernel's strided loop: one tile, per_row 1 (frames one pixel wide) and 2; the pitches walk `mis` through all 16 values
+    for ncols, nrows in ((1, 1024), (1, 1025), (16, 1025), (16, 2049)):
+        for extra in (0, 1, 13):
+            t["lut_%dx%d_p%d" % (ncols, nrows, ncols + extra)] = ClaheCase(ncols, nrows, ncols + extra, 1, 1, 768, "noise", nrows + extra)
+    t["lut_16x1025_clip_2_20"] = ClaheCase(16, 1025, 16, 1, 1, 1 << 20, "two_bin", 5)
+    # counts at and above 2^16 in one tile
+    for clip_q8 in (0, 1, 768, 1 << 20):
+        t["count_256x257_constant_c%d" % clip_q8] = ClaheCase(256, 257, 256, 1, 1, clip_q8, "constant", 0)
+        t["count_256x257_two_bin_c%d" % clip_q8] = ClaheCase(256, 257, 256, 1, 1, clip_q8, "two_bin", 5)
+        t["count_256x256_constant_c%d" % clip_q8] = ClaheCase(256, 256, 256, 1, 1, clip_q8, "constant", 0)
+    # the redistribution: a constant tile of area 272 under a cap c has excess 272 - c
+    for name, clip_q8 in (("r0", 3856), ("r1", 3615), ("r255", 4097), ("r15", 256)):
+        t["redist_16x17_%s" % name] = ClaheCase(16, 17, 16, 1, 1, clip_q8, "constant", 0)
+    t["redist_16x17_cap_from_max"] = ClaheCase(16, 17, 16, 1, 1, 1, "two_bin", 5)      # (1 * 272) >> 16 = 0: the cap is max(1, 0)
+    t["redist_16x17_no_excess"] = ClaheCase(16, 17, 16, 1, 1, 1 << 20, "noise", 3)
+    t["redist_67x45_3x2_two_bin"] = ClaheCase(67, 45, 67, 3, 2, 768, "two_bin", 7)
+    # the benchmark's shape
+    t["real_1920x1080_random"] = ClaheCase(1920, 1080, 1920, 8, 8, 768, "random", 3)
+    t["real_1920x1080_noise"] = ClaheCase(1920, 1080, 1920, 8, 8, 768, "noise", 9)
+    # the apply kernel's loops
+    t["apply_1040x36_1x2"] = ClaheCase(1040, 36, 1040, 1, 2, 768, "random", 4)
+    for tiles_x in (1, 2, 16, 17, 64):
+        t["apply_130x20_tx%d" % tiles_x] = ClaheCase(130, 20, 130, tiles_x, 2, 768, "random", tiles_x)
+    t["apply_64x9_one_pixel_tiles"] = ClaheCase(64, 9, 64, 64, 3, 768, "noise", 6)
+    t["apply_40x5_rows_are_tiles"] = ClaheCase(40, 5, 40, 2, 5, 768, "random", 8)
+    t["apply_3x3_all_one_pixel"] = ClaheCase(3, 3, 3, 3, 3, 0, "noise", 2)
+    # the extents
+    t["extent_65535x1_64x1"] = ClaheCase(65535, 1, 65535, 64, 1, 768, "noise", 11)
+    t["extent_1x65535_1x64"] = ClaheCase(1, 65535, 1, 1, 64, 768, "noise", 12)
+    t["extent_65535x2_1x2"] = ClaheCase(65535, 2, 65535, 1, 2, 768, "noise", 13)
+    # the 32-bit bounds: the one large frame
+    t["large_a_4096x4112_2x2"] = ClaheCase(4096, 4112, 4096, 2, 2, 768, "large_noise", 0)
+    t["large_c_4096x4200_1x1_noise"] = ClaheCase(4096, 4200, 4096, 1, 1, 768, "large_noise", 0)
+    t["large_c_4096x4200_1x1_constant"] = ClaheCase(4096, 4200, 4096, 1, 1, 768, "large_constant", 0)
+    t["large_d_4096x4200_1x2"] = ClaheCase(4096, 4200, 4096, 1, 2, 768, "large_noise", 0)
+    t["large_d_4096x4200_2x1"] = ClaheCase(4096, 4200, 4096, 2, 1, 768, "large_noise", 0)
+    return t
+
+
+CLAHE_EDGES = _clahe_edges()
+LARGE_ENTRIES = tuple(n for n in CLAHE_EDGES if n.startswith("large_"))
+# (ncols, nrows, tiles_x, tiles_y) the library refuses ("tiles too large"): one row, one column more than large_a
+CLAHE_REFUSED = ((4096, 4113, 2, 2), (4097, 4112, 2, 2))
+
+
+@lru_cache(maxsize=None)
+def clahe_reference(name):
+    """(the rule's bytes, the statistics of its arithmetic, seconds the rule took) of a named entry, computed once"""
+    import time
+    case = CLAHE_EDGES[name]
+    frame = clahe_frame(case)
+    stats = {}
+    t0 = time.time()
+    out = clahe(frame, case.tiles_x, case.tiles_y, case.clip_q8, stats=stats)
+    out.setflags(write=False)
+    return out, stats, time.time() - t0
+
+
+# ---------------------------------------------------------------------------------------------------------- CLAHE: the class functions
+def _trips(items, lanes):
+    return -(-items // lanes)
+
+
+def clahe_split(nrows, tiles_y, batch=1):
+    """enqueue_equalize: (split, the bound that set it: "1024" -- about a thousand workgroups -- or "rows" -- 4 rows a workgroup)"""
+    bands = tiles_y + 1
+    split = (SPLIT_TARGET + bands * batch - 1) // (bands * batch)
+    most = max(1, nrows // tiles_y // SPLIT_ROWS)
+    return max(1, min(split, most)), ("1024" if split <= most else "rows")
+
+
+def clahe_classes(case, stats, base_align=0, batch=1):
+    """which class of every loop and bound of the two kernels `case` reaches.  `stats`: what `clahe(..., stats=)` collected;
+    `base_align`: the source's first byte modulo 16"""
+    nc, nr, Tx, Ty = case.ncols, case.nrows, case.tiles_x, case.tiles_y
+    xe, ye = _edges(nc, Tx), _edges(nr, Ty)
+    w, h = np.diff(xe), np.diff(ye)
+    out = {}
+    out["lut_trips"] = _trips(int((((w.max() + 30) >> 4) * h.max())), LUT_THREADS)
+    out["lut_items"] = int(((w.max() + 30) >> 4) * h.max())
+    tiles = stats["tiles"]
+    out["largest_bin"] = max(t["bin"] for t in tiles)
+    out["largest_area"] = max(t["area"] for t in tiles)
+    out["clip"] = [(t["cap"], t["excess"], t["excess"] >> 8, t["excess"] % 256) for t in tiles]
+    out["clip_product_64bit"] = case.clip_q8 * out["largest_area"] >= 1 << 32
+    out["numerator_64bit"] = max(t["numerator"] for t in tiles) >= 1 << 32
+    rows = np.arange(nr, dtype=np.int64)
+    out["mis"] = sorted({int(m) for x in xe[:-1] for m in np.unique((base_align + rows * case.pitch + x) & 15)})
+    out["split"], out["split_bound"] = clahe_split(nr, Ty, batch)
+    cy = _centres(nr, Ty)
+    band_edges = np.concatenate([[0], cy >> 1, [nr]])
+    band_rows = np.diff(band_edges)
+    per_row = (nc + 30) >> 4
+    most_rows = 0
+    for rows_in_band in band_rows:
+        parts = (int(rows_in_band) * np.arange(out["split"] + 1, dtype=np.int64)) // out["split"]
+        most_rows = max(most_rows, int(np.diff(parts).max()))
+    out["apply_trips"] = _trips(per_row * most_rows, APPLY_THREADS)
+    out["empty_bands"] = int((band_rows == 0).sum())
+    out["lut_copy_trips"] = _trips(Tx * 16, APPLY_THREADS)
+    out["tiles_x_class"] = "below 16" if Tx < 16 else "16" if Tx == 16 else "above 16"
+    # the apply kernel's pieces are cut on the destination's address: rows of ncols bytes behind a 16-byte aligned base
+    cx = _centres(nc, Tx)
+    crossed, sides = set(), set()
+    for mis in np.unique((rows * nc) & 15):
+        first = np.arange(-int(mis), nc, 16, dtype=np.int64)
+        xs, xl = np.maximum(first, 0), np.minimum(first + 15, nc - 1)
+        n = np.searchsorted(cx, 2 * xl + 1, side="right") - np.searchsorted(cx, 2 * xs + 1, side="right")
+        crossed |= {min(int(v), 2) for v in n}
+        t = ((xs + 1) * Tx - 1) // nc
+        sides |= {"right" if v else "left" for v in (2 * xs + 1 >= cx[t])}
+    out["centres_per_piece"] = sorted(crossed)
+    out["first_pixel_side"] = sorted(sides)
+    gap = [int(np.diff(c).max()) if len(c) > 1 else 1 for c in (cx, cy)]
+    out["dxdy255"] = gap[0] * gap[1] * 255
+    out["single_product"] = stats["single_product"]
+    out["rounding"] = stats["rounding"]                      # remainders `sum - q * D` equal to D - (D >> 1) and to that minus one
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ remap: the rule
+def remap(frame, mx, my, wrong=None, stats=None):
+    """re_.remap with one step of REMAP_WRONG done wrongly (a wrong step that reads outside the frame raises IndexError)"""
+    frame, mx, my = np.asarray(frame), np.asarray(mx), np.asarray(my)
+    assert frame.dtype == np.uint8 and frame.ndim == 2 and mx.shape == frame.shape == my.shape
+    assert mx.dtype == np.int32 and my.dtype == np.int32
+    nrows, ncols = frame.shape
+    mx, my = mx.astype(np.int64), my.astype(np.int64)
+    if wrong == "clamp_after_shift":
+        x0, fx, y0, fy = np.clip(mx >> 8, 0, ncols - 1), mx & 255, np.clip(my >> 8, 0, nrows - 1), my & 255
+    else:
+        top = (ncols * 256, nrows * 256) if wrong == "clamp_to_n" else ((ncols - 1) * 256, (nrows - 1) * 256)
+        X, Y = np.clip(mx, 0, top[0]), np.clip(my, 0, top[1])
+        x0, fx, y0, fy = X >> 8, X & 255, Y >> 8, Y & 255
+    if wrong == "no_min":
+        x1, y1 = x0 + 1, y0 + 1
+    else:
+        x1, y1 = np.minimum(x0 + 1, ncols - 1), np.minimum(y0 + 1, nrows - 1)
+    if wrong == "fx_fy_exchanged":
+        fx, fy = fy, fx
+    p = frame.astype(np.int64)
+    s = (256 - fx) * (256 - fy) * p[y0, x0] + fx * (256 - fy) * p[y0, x1] + (256 - fx) * fy * p[y1, x0] + fx * fy * p[y1, x1]
+    if stats is not None:
+        low = s & 0xffff
+        stats.update(tie_8000=bool((low == 0x8000).any()), tie_7fff=bool((low == 0x7fff).any()),
+                     edge_pair=bool(ncols >= 2 and (x0 == ncols - 1).any()))
+    return ((s + (32767 if wrong == "round_32767" else 32768)) >> 16).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------------ remap: the cases
+def lattice_values(n):
+    """the clamp's edges on an axis of n pixels"""
+    return [INT32_MIN, -257, -256, -1, 0, 1, 255, 256, 257, (n - 1) * 256 - 1, (n - 1) * 256, (n - 1) * 256 + 1, INT32_MAX]
+
+
+def clamp_class(v, n):
+    """the first entry of lattice_values(n) that `v` equals, 13 for any other value"""
+    values = lattice_values(n)
+    return values.index(int(v)) if int(v) in values else 13
+
+
+def lattice_map(ncols, nrows):
+    """the 169 pairs of lattice values in runs of 8 destination pixels: every run holds a whole aligned piece of 4, the runs at a row's
+    two ends its ragged pieces; the pair moves on by one from run to run and from row to row"""
+    y, x = np.mgrid[0:nrows, 0:ncols]
+    combo = (y + x // 8) % 169
+    vx, vy = np.array(lattice_values(ncols), np.int64), np.array(lattice_values(nrows), np.int64)
+    return vx[combo % 13].astype(np.int32), vy[combo // 13].astype(np.int32)
+
+
+# map: a name of re_.MAPS, "lattice", "shift_frac" (dx 2.37, dy 0.41: both replicated edges stay out of a frame one row high),
+# "half_shift" (dx = dy = 0.5); frame: "noise" / "two_level"
+RemapCase = namedtuple("RemapCase", "ncols nrows pitch map frame seed")
+
+
+def remap_frame(case):
+    if case.frame == "two_level":
+        return re_.two_level_frame(case.ncols, case.nrows, case.seed)
+    assert case.frame == "noise", case.frame
+    return noise_frame(case.ncols, case.nrows, case.seed)
+
+
+def remap_map(case):
+    nc, nr = case.ncols, case.nrows
+    if case.map == "lattice":
+        return lattice_map(nc, nr)
+    if case.map == "shift_frac":
+        return re_.shift_map(nc, nr, 2.37, 0.41)
+    if case.map == "half_shift":
+        return re_.shift_map(nc, nr, 0.5, 0.5)
+    if case.map == "wild":
+        return re_.wild_map(nc, nr, case.seed)
+    return re_.MAPS[case.map](nc, nr)
+
+
+def _remap_edges():
+    t = {}
+    for ncols in list(range(1, 10)) + list(range(63, 70)) + list(range(127, 132)):
+        for extra in (0, 1):
+            t["cut_%dx8_p%d" % (ncols, ncols + extra)] = RemapCase(ncols, 8, ncols + extra, "wild", "noise", ncols + extra)
+    for ncols in (67, 2, 1):
+        for frame in ("two_level", "noise"):
+            t["lattice_%dx169_%s" % (ncols, frame)] = RemapCase(ncols, 169, ncols, "lattice", frame, 5)
+    for ncols, nrows in ((65535, 1), (1, 65535), (2, 65535), (3, 40000)):
+        for m in ("transpose", "wild", "shift_frac"):
+            t["extent_%dx%d_%s" % (ncols, nrows, m)] = RemapCase(ncols, nrows, ncols, m, "noise", 21)
+    t["real_1920x1080_barrel"] = RemapCase(1920, 1080, 1920, "barrel", "noise", 22)
+    t["real_1920x1080_rotation"] = RemapCase(1920, 1080, 1920, "rotation", "noise", 23)
+    t["tie_64x48_half_shift"] = RemapCase(64, 48, 64, "half_shift", "two_level", 5)
+    t["tie_640x480_both"] = RemapCase(640, 480, 640, "shift_frac", "noise", TIE_SEED)
+    return t
+
+
+TIE_SEED = 0                                                 # (found by a search over seeds: see test_ingest_edges_rule.py)
+REMAP_EDGES = _remap_edges()
+# the entries of both tables that hold the benchmark's frame size (the issue names them; every other entry outside LARGE_ENTRIES stays
+# below 1 100 000 pixels)
+REAL_ENTRIES = ("real_1920x1080_random", "real_1920x1080_noise", "real_1920x1080_barrel", "real_1920x1080_rotation")
+
+
+@lru_cache(maxsize=None)
+def remap_reference(name):
+    """(frame, (mx, my), the rule's bytes, statistics) of a named entry, computed once"""
+    case = REMAP_EDGES[name]
+    frame, (mx, my) = remap_frame(case), remap_map(case)
+    stats = {}
+    out = remap(frame, mx, my, stats=stats)
+    assert np.array_equal(out, re_.remap(frame, mx, my))
+    for a in (frame, mx, my, out):
+        a.setflags(write=False)
+    return frame, (mx, my), out, stats
+
+
+def remap_classes(ncols, nrows, mx, my, stats):
+    """which class of the kernel's piece cut, clamp and rounding a frame of that size under that map reaches"""
+    out = {}
+    cuts, narrow = set(), set()
+    per_row = (ncols + 2 * (PIECE - 1)) // PIECE
+    for y in range(min(nrows, 4)):                           # (row & 3 has the period 4 in y)
+        r = (y * ncols) & 3
+        first = [PIECE * j - r for j in range(per_row)]
+        live = [(max(-f, 0), min(ncols - f, PIECE)) for f in first if min(ncols - f, PIECE) > max(-f, 0)]
+        cuts.add((r, live[0][0], live[-1][1]))
+        if ncols < PIECE:
+            narrow.add("one piece" if len(live) == 1 else "straddles two")
+    out["cuts"], out["narrow"] = sorted(cuts), sorted(narrow)
+    out["kernel"] = "remap_kernel<true>" if ncols >= 2 else "remap_kernel<false>"
+    out["grid"] = (-(-per_row // PIECES_ACROSS), -(-nrows // GROUP_ROWS))
+    vx, vy = lattice_values(ncols), lattice_values(nrows)
+    cx = np.full(mx.shape, 13, np.int64)
+    cy = np.full(my.shape, 13, np.int64)
+    for k in range(12, -1, -1):                              # (downwards: the first equal entry names the class)
+        cx[mx == vx[k]] = k
+        cy[my == vy[k]] = k
+    both = (cx < 13) & (cy < 13)
+    combo = cx * 13 + cy
+    out["clamp_pairs"] = {(int(c) // 13, int(c) % 13) for c in np.unique(combo[both])}
+    # which pairs stand on a whole piece and which on a ragged one (a piece: 4 pixels cut where the index counted from the frame's first
+    # pixel is a multiple of 4, inside one row)
+    flat = np.arange(ncols * nrows, dtype=np.int64).reshape(nrows, ncols)
+    start = flat - (flat & 3)
+    row0 = (flat // ncols) * ncols
+    whole = (start >= row0) & (start + PIECE <= row0 + ncols)
+    out["clamp_pairs_whole"] = {(int(c) // 13, int(c) % 13) for c in np.unique(combo[both & whole])}
+    out["clamp_pairs_ragged"] = {(int(c) // 13, int(c) % 13) for c in np.unique(combo[both & ~whole])}
+    out["edge_pair"], out["tie_8000"], out["tie_7fff"] = stats["edge_pair"], stats["tie_8000"], stats["tie_7fff"]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the draws
+DRAW_SEEDS = tuple(range(12))
+CLIPS = (0, 1, 256, 768, 10240, 1 << 20)
+
+
+def clahe_draw(seed):
+    """(frame, tiles_x, tiles_y, clip_q8, pitch): frames up to 700 x 500; the even seeds draw a coarse tile grid on a frame of at least
+    300 x 250, so that a tile has more than 1024 pieces"""
+    rs = np.random.RandomState(3000 + seed)
+    while True:
+        if seed % 2 == 0:
+            ncols, nrows = int(rs.randint(300, 701)), int(rs.randint(250, 501))
+            tiles_x, tiles_y = int(rs.randint(1, 7)), int(rs.randint(1, 4))
+            if (((ncols + tiles_x - 1) // tiles_x + 30) >> 4) * ((nrows + tiles_y - 1) // tiles_y) <= LUT_THREADS:
+                continue
+        else:
+            ncols, nrows = int(rs.randint(1, 701)), int(rs.randint(1, 501))
+            tiles_x, tiles_y = int(rs.randint(1, min(64, ncols) + 1)), int(rs.randint(1, min(64, nrows) + 1))
+        if ee.equalisable(ncols, nrows, tiles_x, tiles_y):
+            break
+    picks = CLIPS + (int(rs.randint(1, 1 << 20)),)
+    clip_q8 = int(picks[int(rs.randint(0, len(picks)))])
+    pitch = ncols + int(rs.choice([0, 0, 1, 13, 16]))
+    kind = int(rs.randint(0, 3))
+    frame = (ee.random_frame(ncols, nrows, seed), ee.two_bin_frame(ncols, nrows, seed), noise_frame(ncols, nrows, seed))[kind]
+    return frame, tiles_x, tiles_y, clip_q8, pitch
+
+
+def remap_draw(seed):
+    """(frame, (mx, my), pitch, name of the map): frames up to 700 x 500, the map's entries overlaid with the clamp's lattice at a drawn
+    step"""
+    rs = np.random.RandomState(4000 + seed)
+    ncols, nrows = int(rs.randint(1, 701)), int(rs.randint(1, 501))
+    name = sorted(re_.MAPS)[int(rs.randint(0, len(re_.MAPS)))]
+    if name == "shift":
+        m = re_.shift_map(ncols, nrows, float(rs.uniform(-9, 9)), float(rs.uniform(-9, 9)))
+    elif name == "rotation":
+        m = re_.rotation_map(ncols, nrows, float(rs.uniform(-180, 180)))
+    elif name == "wild":
+        m = re_.wild_map(ncols, nrows, seed)
+    else:
+        m = re_.MAPS[name](ncols, nrows)
+    mx, my = np.array(m[0], np.int32), np.array(m[1], np.int32)
+    step = int(rs.randint(3, 41))
+    at = np.arange(0, ncols * nrows, step)
+    k = np.arange(at.size) + int(rs.randint(0, 169))
+    mx.ravel()[at] = np.array(lattice_values(ncols), np.int64)[k % 13].astype(np.int32)
+    my.ravel()[at] = np.array(lattice_values(nrows), np.int64)[(k // 13) % 13].astype(np.int32)
+    pitch = ncols + int(rs.choice([0, 0, 1, 13, 16]))
+    kind = int(rs.randint(0, 3))
+    frame = (noise_frame(ncols, nrows, seed), re_.two_level_frame(ncols, nrows, seed), re_.textured_frame(ncols, nrows, seed))[kind]
+    return frame, (mx, my), pitch, name
+
+
+# ------------------------------------------------------------------------------------------------------------- frames for the slots
+def slot_frame(ncols, nrows, k):
+    """the frame of slot k: seeded by the slot, no two alike -- texture with a dark half (so the equalisation has work) and noise"""
+    yy, xx = np.mgrid[0:nrows, 0:ncols]
+    rs = np.random.RandomState(500 + k)
+    f = 90 + 50 * np.sin(xx / (5.0 + k % 7) + k) * np.cos(yy / (9.0 + k % 5)) + rs.normal(0, 10, (nrows, ncols))
+    f[:, : ncols // 2] = f[:, : ncols // 2] * 0.3 + 5
+    return np.clip(f, 0, 255).astype(np.uint8)
