@@ -131,7 +131,7 @@ int klt_debug_graph(klt_ctx *c, int op)
     if (!c) return KLT_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     auto forget = [&]() {
-        for (Slot &s : c->slots) { s.upload_pending = s.built_pending = s.read_valid = s.consumed_valid = s.consumed_alt_valid = false; }
+        for (Slot &s : c->slots) { s.upload_pending = s.built_pending = s.read_valid = s.raw.consumed_valid = s.raw_alt.consumed_valid = false; }
         c->ring_serial += kEventRing;                 // every event handed out so far counts as re-used: nobody waits for it any more
         c->last_build_on_bstream = -1;                // the next build on the build stream orders itself behind the main stream
         c->waited_built_serial = ~0ull;

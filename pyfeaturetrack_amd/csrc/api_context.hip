@@ -187,7 +187,7 @@ int mark_consumed(klt_ctx *c, Slot *const *slots, int n, hipStream_t reader)
     uint64_t serial;
     if (int rc = fresh_event(c, &e, &serial)) return rc;
     HIPCHK(c, hipEventRecord(e, reader));
-    for (int i = 0; i < n; i++) { slots[i]->ev_consumed = e; slots[i]->consumed_serial = serial; slots[i]->consumed_valid = true; }
+    for (int i = 0; i < n; i++) { RawBuffer &r = slots[i]->raw; r.ev_consumed = e; r.consumed_serial = serial; r.consumed_valid = true; }
     return 0;
 }
 
@@ -298,7 +298,7 @@ void klt_destroy(klt_ctx *c)
     for (void *p : c->dev_allocs) hipFree(p);
     for (hipEvent_t e : c->ring) hipEventDestroy(e);
     if (c->ev_sel) hipEventDestroy(c->ev_sel);
-    for (Slot &s : c->slots) { hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm); }
+    for (Slot &s : c->slots) { hipFree(s.raw.u8); hipFree(s.raw_alt.u8); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm); }
     for (FeatBuf &b : c->fbs)
         if (!b.view) hipFree(b.d);
     hipFree(c->tmpA); hipFree(c->tmpB); hipFree(c->h1); hipFree(c->cimg); hipFree(c->rmp.d);
@@ -360,7 +360,7 @@ int klt_set_equalize_params(klt_ctx *c, const klt_equalize_params *p)
     if (p->clip_q8 < 0 || p->clip_q8 > (1 << 20)) return fail(c, KLT_ERR_ARG, "equalisation clip_q8 must lie in 0 .. 2^20");
     if (std::memcmp(p, &c->eqp, sizeof(*p)) == 0) return KLT_OK;
     c->eqp = *p;
-    for (Slot &s : c->slots) s.eq_valid = false;
+    for (Slot &s : c->slots) void_copies_from(s, INGEST_EQUALIZE);
     c->cfg_gen++;
     return KLT_OK;
 }
@@ -390,7 +390,7 @@ int klt_set_remap(klt_ctx *c, const int32_t *map_x, const int32_t *map_y, int nc
     hipFree(c->rmp.d);
     c->rmp.d = d; c->rmp.plane = plane;
     c->rmp.nc = d ? ncols : 0; c->rmp.nr = d ? nrows : 0;
-    for (Slot &s : c->slots) s.rm_valid = s.eq_valid = false;
+    for (Slot &s : c->slots) void_copies_from(s, INGEST_REMAP);
     c->cfg_gen++;
     return KLT_OK;
 }
@@ -486,7 +486,7 @@ int klt_slot_free(klt_ctx *c, int slot)
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = sync_all(c)) return rc;
     Slot &s = c->slots[slot];
-    hipFree(s.u8); hipFree(s.u8_alt); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm);
+    hipFree(s.raw.u8); hipFree(s.raw_alt.u8); hipFree(s.f32); hipFree(s.planes); hipFree(s.l0img); hipFree(s.eq); hipFree(s.rm);
     s = Slot();
     return KLT_OK;
 }

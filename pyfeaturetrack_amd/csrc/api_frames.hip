@@ -1,5 +1,6 @@
 // api_frames.hip -- frames on their way in and the pyramids built from them: taps, uploads (synchronous, asynchronous from pinned memory on
-// the copy streams, adoption of frames already in device memory), pinned / device memory for callers without a HIP binding, the launch
+// the copy streams, adoption of frames already in device memory), pinned / device memory for callers without a HIP binding, the ingest
+// chain in front of every reader of a raw 8-bit frame (remap, then CLAHE: ensure_ingested; its device-free rules: ingest_rule.h), the launch
 // sequence of the pyramid build (klt_build_pyramids*), the stand-alone convolutions and the read-back of planes.
 #include "klt_context.h"
 
@@ -26,38 +27,65 @@ void make_taps(const double *k, int n, Taps &t)
 }
 
 
+// ---- a slot takes or loses a frame
+// (declared in klt_context.h) the one place that clears the flags of a slot's copies
+void void_copies_from(Slot &s, IngestStage stage)
+{
+    if (stage <= INGEST_FRAME) s.pyr_valid = false;
+    if (stage <= INGEST_REMAP) s.rm_valid = false;       // (so, while a stage is on, no copy behind a stale copy of it is valid)
+    s.eq_valid = false;
+}
+
+void Slot::take_frame(int ncols, int nrows, int kind, bool in_raw)
+{
+    nc = ncols;
+    nr = nrows;
+    raw_kind = kind;
+    f32_in_raw = in_raw;
+    void_copies_from(*this, INGEST_FRAME);
+}
+
+void Slot::drop_frame()
+{
+    u8_ext = nullptr;
+    gen = 0;
+    take_frame(0, 0, 0, f32_in_raw);                     // (kind 0: none)
+}
+
+// a rule's answer (ingest_rule.h: the text of a refusal, or null) as a return code
+static int refuse_arg(klt_ctx *c, const char *why) { return why ? fail(c, KLT_ERR_ARG, why) : 0; }
+
+// What every entry point that brings a frame asks first: its pointers (`pointers`: none of them null), then the geometry it takes -- sides
+// of 1 .. 65535 pixels and the rest of frame_geometry_refusal
+static int check_frame(klt_ctx *c, bool pointers, int ncols, int nrows, int pitch, FrameUse use)
+{
+    if (!c || !pointers) return fail(c, KLT_ERR_ARG, "null argument");
+    return refuse_arg(c, frame_geometry_refusal(ncols, nrows, pitch, use));
+}
+
 int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int pitch, int kind)
 {
-    if (!c || !px) return fail(c, KLT_ERR_ARG, "null argument");
-    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols)
-        return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
+    if (int rc = check_frame(c, px != nullptr, ncols, nrows, pitch, FRAME_UPLOADED)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     Slot *s;
     if (int rc = get_slot(c, slot, &s, true)) return rc;
     if (s->upload_pending) {
-        HIPCHK(c, hipStreamSynchronize(c->cstream));
-        for (hipStream_t x : c->cextra) if (x) HIPCHK(c, hipStreamSynchronize(x));
+        if (int rc = klt_upload_wait(c)) return rc;
         s->upload_pending = false;
     }
     if (int rc = wait_built(c, s)) return rc;                 // a build on the build stream may still read the old frame
     const size_t px_count = (size_t)ncols * nrows;
     s->u8_ext = nullptr;
-    if (kind == 1) { if (int rc = ensure(c, s->u8, s->u8_cap, px_count)) return rc; }
+    if (kind == 1) { if (int rc = ensure(c, s->raw.u8, s->raw.cap, px_count)) return rc; }
     else { if (int rc = ensure(c, s->f32, s->f32_cap, px_count)) return rc; }
     const size_t esz = kind == 1 ? 1 : sizeof(float);
-    void *dst = kind == 1 ? (void *)s->u8 : (void *)s->f32;
+    void *dst = kind == 1 ? (void *)s->raw.u8 : (void *)s->f32;
     if (pitch == ncols) HIPCHK(c, hipMemcpyAsync(dst, px, px_count * esz, hipMemcpyHostToDevice, c->stream));
     else HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)ncols * esz, px, (size_t)pitch * esz, (size_t)ncols * esz, nrows,
                                     hipMemcpyHostToDevice, c->stream));
     // pageable host memory: the copy above is staged before returning, but make it explicit
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    s->nc = ncols;
-    s->nr = nrows;
-    s->raw_kind = kind;
-    s->f32_in_raw = false;
-    s->pyr_valid = false;
-    s->eq_valid = s->rm_valid = false;
+    s->take_frame(ncols, nrows, kind, false);
     return 0;
 }
 
@@ -98,92 +126,63 @@ int layout_pyramid(klt_ctx *c, Slot *s)
     return 0;
 }
 
-// ---- remap ingest stage (klt_set_remap; the rule: include/klt_gpu.h)
-// what a slot must be for the context's map: an 8-bit frame of the map's size
-static int check_remappable(klt_ctx *c, const Slot *s)
+// slots of one frame size share a launch (for_each_group, ingest_rule.h: KLT_MAX_BATCH at a time)
+static bool same_size(const Slot *a, const Slot *b) { return a->nc == b->nc && a->nr == b->nr; }
+
+// ---- the ingest chain: remap (klt_set_remap), then CLAHE (klt_set_equalize_params); the rules: include/klt_gpu.h, DESIGN.md 9l and 9m
+// What a stage is to the chain's skeleton (ensure_ingested), to the host-frame calls (host_frame_through) and to the downloads
+struct IngestStep {
+    IngestStage stage, reads;         // the point of the chain it makes, and the one whose output (ingest_output) it reads
+    uint8_t *Slot::*buf;              // the slot's copy behind this stage, ...
+    size_t Slot::*cap;                // ... its capacity in bytes ...
+    bool Slot::*valid;                // ... and whether it was made from the frame the slot holds under what the context holds now
+    int klt_ctx::*path;               // klt_remap_path / klt_equalize_path
+    // the stage's own refusals: of a frame that is not an 8-bit one, of a launch during a stream capture, and of a frame's size --
+    // when_stale: only where a launch would be needed (a valid copy is not examined again)
+    const char *not_u8, *in_capture;
+    int (*check)(klt_ctx *, int nc, int nr);
+    bool when_stale;
+    size_t (*bytes)(const klt_ctx *, int nc, int nr);      // of the copy, with whatever the stage keeps behind it
+    // the launches, under their timing families, on `batch` frames of nc x nr pixels whose rows lie src_pitch bytes apart
+    void (*enqueue)(klt_ctx *, const uint8_t *const *src, int src_pitch, uint8_t *const *dst, int batch, int nc, int nr, hipStream_t);
+};
+
+// what a frame must be for the context's map: of the map's size
+static int check_remappable(klt_ctx *c, int nc, int nr)
 {
-    if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, "remapping takes 8-bit frames");
-    if (s->nc != c->rmp.nc || s->nr != c->rmp.nr)
-        return fail(c, KLT_ERR_ARG, "remapping: the frame is " + std::to_string(s->nc) + " by " + std::to_string(s->nr) + ", the map " +
+    if (nc != c->rmp.nc || nr != c->rmp.nr)
+        return fail(c, KLT_ERR_ARG, "remapping: the frame is " + std::to_string(nc) + " by " + std::to_string(nr) + ", the map " +
                                         std::to_string(c->rmp.nc) + " by " + std::to_string(c->rmp.nr));
     return 0;
 }
 
-// the launch on a.batch frames of the map's size as `a` names them (src, dst, src_pitch filled in by the caller)
-static void enqueue_remap(klt_ctx *c, RemapArgs &a, hipStream_t st)
+static size_t remap_bytes(const klt_ctx *, int nc, int nr) { return (size_t)nc * nr; }
+
+static void enqueue_remap(klt_ctx *c, const uint8_t *const *src, int src_pitch, uint8_t *const *dst, int batch, int nc, int nr, hipStream_t st)
 {
+    RemapArgs a{};
+    for (int b = 0; b < batch; b++) { a.src[b] = src[b]; a.dst[b] = dst[b]; }
+    a.batch = batch; a.src_pitch = src_pitch;
     a.map_x = c->rmp.d; a.map_y = c->rmp.d + c->rmp.plane;
-    a.ncols = c->rmp.nc; a.nrows = c->rmp.nr;
-    TimerScope t(c, F_REMAP, (double)a.ncols * a.nrows * (8.0 + 2.0 * a.batch), st);
+    a.ncols = nc; a.nrows = nr;                            // (the map's size: check_remappable)
+    TimerScope t(c, F_REMAP, (double)nc * nr * (8.0 + 2.0 * batch), st);
     launch_remap(st, a);
 }
 
-// (declared in klt_context.h)
-int ensure_remapped(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched /* = nullptr */)
-{
-    if (launched) *launched = false;
-    std::vector<Slot *> todo;
-    // every refusal first: nothing is allocated or enqueued for a call that fails
-    for (int i = 0; i < n; i++) {
-        Slot *s = slots[i];
-        if (int rc = check_remappable(c, s)) return rc;
-        if (s->rm_valid) continue;
-        if (c->capturing) return fail(c, KLT_ERR_STATE, "a frame would have to be remapped during a stream capture");
-        todo.push_back(s);
-    }
-    for (Slot *s : todo)
-        if (int rc = ensure(c, s->rm, s->rm_cap, (size_t)s->nc * s->nr)) return rc;      // (a slot that gets none keeps rm == nullptr, rm_valid false)
-    for (size_t i0 = 0; i0 < todo.size(); i0 += KLT_MAX_BATCH) {      // (one size: the map's)
-        RemapArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.batch = (int)std::min(todo.size() - i0, (size_t)KLT_MAX_BATCH);
-        for (int b = 0; b < a.batch; b++) {
-            a.src[b] = frame8(todo[i0 + b]);
-            a.dst[b] = todo[i0 + b]->rm;
-        }
-        a.src_pitch = c->rmp.nc;
-        enqueue_remap(c, a, st);
-    }
-    for (Slot *s : todo) { s->rm_valid = true; s->eq_valid = false; }      // (an equalised copy is one of the remapped frame)
-    if (launched) *launched = !todo.empty();
-    return 0;
-}
+// what a frame must be for the context's tile grid (equalisable_refusal, ingest_rule.h)
+static int check_equalisable(klt_ctx *c, int nc, int nr) { return refuse_arg(c, equalisable_refusal(nc, nr, c->eqp.tiles_x, c->eqp.tiles_y)); }
 
-// ---- CLAHE ingest stage (klt_set_equalize_params; the rule: include/klt_gpu.h)
-// A frame is equalisable when the tile grid fits it and the per-pixel division is a 32-bit one: the largest Dx * Dy * 255 below 2^32,
-// Dx the largest distance of two neighbouring tile centres in doubled coordinates (1 with one tile on the axis)
-static long long widest_centre_gap(int n, int tiles)
-{
-    long long widest = 1;
-    for (int k = 0; k + 2 <= tiles; k++)           // C_{k+1} - C_k = x_{k+2} - x_k
-        widest = std::max(widest, ((long long)(k + 2) * n) / tiles - ((long long)k * n) / tiles);
-    return widest;
-}
+static size_t equalize_bytes(const klt_ctx *c, int nc, int nr) { return eq_bytes(nc, nr, c->eqp.tiles_x, c->eqp.tiles_y); }
 
-static int check_equalisable(klt_ctx *c, int nc, int nr)
+// the two launches; a frame's LUTs lie behind its equalised copy (eq_lut_offset)
+static void enqueue_equalize(klt_ctx *c, const uint8_t *const *src, int src_pitch, uint8_t *const *dst, int batch, int nc, int nr, hipStream_t st)
 {
-    const klt_equalize_params &q = c->eqp;
-    if (q.tiles_x > nc || q.tiles_y > nr) return fail(c, KLT_ERR_ARG, "equalisation: the frame is smaller than the tile grid");
-    if (widest_centre_gap(nc, q.tiles_x) * widest_centre_gap(nr, q.tiles_y) * 255 >= (1LL << 32))
-        return fail(c, KLT_ERR_ARG, "equalisation: tiles too large for a 32-bit interpolation (the largest Dx * Dy * 255 must stay below 2^32)");
-    return 0;
-}
-
-// the bytes of a slot's equalised frame and where its LUTs begin behind it
-static size_t eq_lut_offset(int nc, int nr) { return ((size_t)nc * nr + 255) & ~(size_t)255; }
-static size_t eq_bytes(const klt_ctx *c, int nc, int nr) { return eq_lut_offset(nc, nr) + (size_t)c->eqp.tiles_x * c->eqp.tiles_y * 256; }
-
-// the two launches on `batch` frames of one size as `a` names them (src, dst, lut, src_pitch filled in by the caller)
-static int enqueue_equalize(klt_ctx *c, EqualizeArgs &a, int batch, int nc, int nr, hipStream_t st)
-{
+    EqualizeArgs a{};
+    for (int b = 0; b < batch; b++) { a.src[b] = src[b]; a.dst[b] = dst[b]; a.lut[b] = dst[b] + eq_lut_offset(nc, nr); }
+    a.src_pitch = src_pitch;
     a.ncols = nc; a.nrows = nr;
     a.tiles_x = c->eqp.tiles_x; a.tiles_y = c->eqp.tiles_y; a.clip_q8 = c->eqp.clip_q8;
-    // the apply launch: every band of rows between two tile centres split until about a thousand workgroups are out, a workgroup keeping
-    // at least 4 rows of a band of average height
-    const int bands = a.tiles_y + 1;
-    int split = (1024 + bands * batch - 1) / (bands * batch);
-    const int most = std::max(1, nr / a.tiles_y / 4);
-    a.split = std::max(1, std::min(split, most));
+    a.split = eq_apply_split(nr, a.tiles_y, batch);
     const double N = (double)nc * nr * batch;
     {
         TimerScope t(c, F_EQ_LUT, N + 256.0 * a.tiles_x * a.tiles_y * batch, st);
@@ -193,46 +192,85 @@ static int enqueue_equalize(klt_ctx *c, EqualizeArgs &a, int batch, int nc, int 
         TimerScope t(c, F_EQ_APPLY, 2 * N, st);
         launch_clahe_apply(st, a, batch);
     }
+}
+
+// The two stages, in the order they run
+static const IngestStep kRemapStep = {INGEST_REMAP, INGEST_FRAME, &Slot::rm, &Slot::rm_cap, &Slot::rm_valid, &klt_ctx::rm_path, "remapping takes 8-bit frames",
+                                      "a frame would have to be remapped during a stream capture", check_remappable, false, remap_bytes, enqueue_remap};
+static const IngestStep kEqualizeStep = {INGEST_EQUALIZE, INGEST_REMAP, &Slot::eq, &Slot::eq_cap, &Slot::eq_valid, &klt_ctx::eq_path, "equalisation takes 8-bit frames",
+                                         "a frame would have to be equalised during a stream capture", check_equalisable, true, equalize_bytes, enqueue_equalize};
+
+// those of them that are switched on
+static int steps_on(const klt_ctx *c, const IngestStep *on[2])
+{
+    int n = 0;
+    if (c->rmp.d) on[n++] = &kRemapStep;
+    if (c->eqp.mode == 1) on[n++] = &kEqualizeStep;
+    return n;
+}
+
+static int step_refusal(klt_ctx *c, const IngestStep &step, const Slot *s, bool stale)
+{
+    if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, step.not_u8);
+    return stale || !step.when_stale ? step.check(c, s->nc, s->nr) : 0;
+}
+
+// (declared in klt_context.h) each stage reads the output of the last stage in front of it that is switched on
+const uint8_t *ingest_output(const klt_ctx *c, const Slot *s, IngestStage upto)
+{
+    const IngestStep *on[2];
+    const uint8_t *out = frame8(s);
+    for (int k = 0, steps = steps_on(c, on); k < steps && on[k]->stage <= upto; k++) out = s->*on[k]->buf;
+    return out;
+}
+
+// (declared in klt_context.h)
+int ingest_refusal(klt_ctx *c, const Slot *s)
+{
+    const IngestStep *on[2];
+    for (int k = 0, steps = steps_on(c, on); k < steps; k++)
+        if (int rc = step_refusal(c, *on[k], s, false)) return rc;
     return 0;
 }
 
 // (declared in klt_context.h)
-int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched /* = nullptr */)
+int ensure_ingested(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool of_build /* = false */)
 {
-    if (launched) *launched = false;
-    std::vector<Slot *> todo;
-    // every refusal first: nothing is allocated or enqueued for a call that fails
-    for (int i = 0; i < n; i++) {
-        Slot *s = slots[i];
-        if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, "equalisation takes 8-bit frames");
-        if (s->eq_valid) continue;
-        if (int rc = check_equalisable(c, s->nc, s->nr)) return rc;
-        if (c->capturing) return fail(c, KLT_ERR_STATE, "a frame would have to be equalised during a stream capture");
-        todo.push_back(s);
+    const IngestStep *on[2];
+    const int steps = steps_on(c, on);
+    if (!steps) return 0;
+    // 1. every refusal of every stage, stage by stage; todo: (stage, slot) wherever the slot's copy behind the stage is stale, in that
+    // order (void_copies_from keeps a copy behind a stale one stale as well; the test below does not lean on it)
+    std::vector<std::pair<const IngestStep *, Slot *>> todo;
+    for (int k = 0; k < steps; k++)
+        for (int i = 0; i < n; i++) {
+            Slot *s = slots[i];
+            const bool stale = !(s->*on[k]->valid) || (k > 0 && !(s->*on[k - 1]->valid));      // (its own flag, or its source is made anew)
+            if (int rc = step_refusal(c, *on[k], s, stale)) return rc;
+            if (stale && c->capturing) return fail(c, KLT_ERR_STATE, on[k]->in_capture);
+            if (stale) todo.push_back({on[k], s});
+        }
+    // 2. every allocation (a slot that gets none keeps a null pointer and its cleared flag)
+    for (auto &[step, s] : todo)
+        if (int rc = ensure(c, s->*step->buf, s->*step->cap, step->bytes(c, s->nc, s->nr))) return rc;
+    // 3. the launches: the stale slots of one stage and one frame size together (a map set: every frame has the map's size)
+    for_each_group(todo.data(), todo.size(), [](const auto &a, const auto &b) { return a.first == b.first && same_size(a.second, b.second); },
+                   [&](const auto *g, int B) {
+        const IngestStep &step = *g[0].first;
+        const Slot *s0 = g[0].second;
+        const uint8_t *src[KLT_MAX_BATCH];
+        uint8_t *dst[KLT_MAX_BATCH];
+        for (int b = 0; b < B; b++) { src[b] = ingest_output(c, g[b].second, step.reads); dst[b] = g[b].second->*step.buf; }
+        step.enqueue(c, src, s0->nc, dst, B, s0->nc, s0->nr, st);
+        return 0;
+    });
+    // 4. the flags: a stage's new copy is valid, the copies behind it are stale until their own stage has run (and has: it comes later in
+    // todo); the build has cleared both paths before the call
+    for (auto &[step, s] : todo) {
+        void_copies_from(*s, step->stage);
+        s->*step->valid = true;
+        if (of_build) c->*step->path = 1;
     }
-    for (Slot *s : todo)
-        if (int rc = ensure(c, s->eq, s->eq_cap, eq_bytes(c, s->nc, s->nr))) return rc;      // (a slot that gets none keeps eq == nullptr, eq_valid false)
-    std::vector<bool> done(todo.size(), false);
-    for (size_t i0 = 0; i0 < todo.size(); i0++) {
-        if (done[i0]) continue;
-        EqualizeArgs a;
-        std::memset(&a, 0, sizeof(a));
-        int B = 0;
-        const int nc = todo[i0]->nc, nr = todo[i0]->nr;
-        for (size_t i = i0; i < todo.size() && B < KLT_MAX_BATCH; i++)
-            if (!done[i] && todo[i]->nc == nc && todo[i]->nr == nr) {
-                Slot *s = todo[i];
-                a.src[B] = c->rmp.d ? s->rm : frame8(s);     // (a map set: the caller has run ensure_remapped in front)
-                a.dst[B] = s->eq;
-                a.lut[B] = s->eq + eq_lut_offset(nc, nr);
-                B++;
-                done[i] = true;
-            }
-        a.src_pitch = nc;
-        if (int rc = enqueue_equalize(c, a, B, nc, nr, st)) return rc;
-    }
-    for (Slot *s : todo) s->eq_valid = true;
-    if (launched) *launched = !todo.empty();
     return 0;
 }
 
@@ -362,24 +400,18 @@ int ensure_level0_records(klt_ctx *c, Slot *const *slots, int n, bool asked /* =
     if (todo.empty()) return 0;
     hipStream_t const caller = c->work;
     // slots of one frame size share a launch, KLT_MAX_BATCH at a time
-    std::vector<bool> done(todo.size(), false);
-    for (size_t i0 = 0; i0 < todo.size(); i0++) {
-        if (done[i0]) continue;
+    const int rc_groups = for_each_group(todo.data(), todo.size(), same_size, [&](Slot *const *g, int B) {
         const float *img[KLT_MAX_BATCH];
         float *rec[KLT_MAX_BATCH];
-        std::vector<Slot *> g;
-        for (size_t i = i0; i < todo.size() && g.size() < (size_t)KLT_MAX_BATCH; i++)
-            if (!done[i] && todo[i]->nc == todo[i0]->nc && todo[i]->nr == todo[i0]->nr) {
-                img[g.size()] = todo[i]->l0img; rec[g.size()] = todo[i]->lv[0].img;
-                g.push_back(todo[i]);
-                done[i] = true;
-            }
+        for (int b = 0; b < B; b++) { img[b] = g[b]->l0img; rec[b] = g[b]->lv[0].img; }
         c->work = c->stream;
-        const int rc = enqueue_fused_grad(c, (int)g.size(), img, rec, todo[i0]->nc, todo[i0]->nr);
+        const int rc = enqueue_fused_grad(c, B, img, rec, g[0]->nc, g[0]->nr);
         c->work = caller;
         if (rc) return rc;
-        for (Slot *s : g) s->rec0_valid = true;
-    }
+        for (int b = 0; b < B; b++) g[b]->rec0_valid = true;
+        return 0;
+    });
+    if (rc_groups) return rc_groups;
     if (caller != c->stream) {                               // a reader on the build stream: behind the launch just enqueued
         hipEvent_t e;
         if (int rc2 = fresh_event(c, &e)) return rc2;
@@ -520,8 +552,7 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
     for (int i = 0; i < n; i++) {
         if (int rc = get_slot(c, slot_ids[i], &sl[i], false)) return rc;
         if (sl[i]->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
-        if (c->rmp.d) { if (int rc = check_remappable(c, sl[i])) return rc; }
-        if (c->eqp.mode == 1 && sl[i]->raw_kind != 1) return fail(c, KLT_ERR_STATE, "equalisation takes 8-bit frames");
+        if (int rc = ingest_refusal(c, sl[i])) return rc;
         for (int j = 0; j < i; j++)
             if (sl[j] == sl[i]) return fail(c, KLT_ERR_ARG, "slot listed twice");
         if (int rc = layout_pyramid(c, sl[i])) return rc;
@@ -540,32 +571,15 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
         sl[i]->read_valid = false;
     }
     c->last_build_on_bstream = on_bstream ? 1 : 0;
-    // CLAHE ingest stage: the frames that have no valid equalised copy get one here, behind their uploads on the stream the build runs
-    // on; the level-0 launches below read the copies (raw8).  The mark at the end of the build covers this reader of the raw frames too.
-    // Remap ingest stage: in front of it on the same stream -- with both on, the equalised copy is one of the remapped frame.
+    // The ingest stages: the frames that have no valid copy of a stage that is on get one here, behind their uploads on the stream the
+    // build runs on; the level-0 launches below read the chain's output (raw8).  The mark at the end of the build covers these readers
+    // of the raw frames too.
     c->eq_path = c->rm_path = 0;
-    if (c->rmp.d) {
-        bool launched = false;
-        if (int rc = ensure_remapped(c, sl.data(), n, c->work, &launched)) return rc;
-        c->rm_path = launched ? 1 : 0;
-    }
-    if (c->eqp.mode == 1) {
-        bool launched = false;
-        if (int rc = ensure_equalized(c, sl.data(), n, c->work, &launched)) return rc;
-        c->eq_path = launched ? 1 : 0;
-    }
+    if (int rc = ensure_ingested(c, sl.data(), n, c->work, true)) return rc;
     // groups of frames with the same geometry and input type share launches
-    std::vector<bool> done((size_t)n, false);
-    for (int i0 = 0; i0 < n; i0++) {
-        if (done[i0]) continue;
-        std::vector<Slot *> g;
-        for (int i = i0; i < n && (int)g.size() < KLT_MAX_BATCH; i++)
-            if (!done[i] && sl[i]->nc == sl[i0]->nc && sl[i]->nr == sl[i0]->nr && sl[i]->raw_kind == sl[i0]->raw_kind &&
-                wants_lean(c, sl[i]) == wants_lean(c, sl[i0])) {
-                g.push_back(sl[i]);
-                done[i] = true;
-            }
-        const int B = (int)g.size();
+    auto same_launch = [c](const Slot *a, const Slot *b) { return same_size(a, b) && a->raw_kind == b->raw_kind && wants_lean(c, a) == wants_lean(c, b); };
+    const int rc_groups = for_each_group(sl.data(), sl.size(), same_launch, [&](Slot *const *members, int B) {
+        const std::vector<Slot *> g(members, members + B);
         Slot *s0 = g[0];
         const void *raw[KLT_MAX_BATCH];
         float *rec[KLT_MAX_BATCH], *cim[KLT_MAX_BATCH];
@@ -617,7 +631,9 @@ int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n)
             s->lazy_read = s->rec0_asked = false;
             s->built_nc = s->nc; s->built_nr = s->nr; s->built_cfg = c->cfg_gen;
         }
-    }
+        return 0;
+    });
+    if (rc_groups) return rc_groups;
     // the next asynchronous copy into these slots waits for this build
     if (int rc = mark_consumed(c, sl.data(), n, c->work)) return rc;
     if (on_bstream) { if (int rc = leave_build_stream(c, sl)) return rc; }
@@ -707,9 +723,7 @@ int klt_host_free(klt_ctx *c, void *p)
 // pitch in pixels)
 static int upload_async(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int pitch, size_t esz)
 {
-    if (!c || !px) return fail(c, KLT_ERR_ARG, "null argument");
-    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols) return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
+    if (int rc = check_frame(c, px != nullptr, ncols, nrows, pitch, FRAME_UPLOADED)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t attr;                           // the source must be pinned: a pageable copy would be staged synchronously
     if (hipPointerGetAttributes(&attr, px) != hipSuccess || attr.type != hipMemoryTypeHost) {
@@ -722,54 +736,43 @@ static int upload_async(klt_ctx *c, int slot, const void *px, int ncols, int nro
     const hipStream_t cs = lane == 0 ? c->cstream : c->cextra[lane - 1];
     Slot *s;
     if (int rc = get_slot(c, slot, &s, true)) return rc;
-    const size_t px_count = (size_t)ncols * nrows * esz;      // bytes: the raw buffers are byte buffers (`u8_cap` counts bytes)
+    const size_t px_count = (size_t)ncols * nrows * esz;      // bytes
     // write into the buffer the build before last read (normally long finished: poll, block only if it is not)
     s->u8_ext = nullptr;
-    std::swap(s->u8, s->u8_alt);
-    std::swap(s->u8_cap, s->u8_alt_cap);
-    std::swap(s->ev_consumed, s->ev_consumed_alt);
-    std::swap(s->consumed_serial, s->consumed_alt_serial);
-    std::swap(s->consumed_valid, s->consumed_alt_valid);
-    std::swap(s->ev_wr, s->ev_wr_alt);
-    std::swap(s->wr_serial, s->wr_alt_serial);
-    std::swap(s->wr_lane, s->wr_alt_lane);
-    if (int rc = ensure(c, s->u8, s->u8_cap, px_count)) return rc;
-    if (s->wr_lane >= 0 && s->wr_lane != lane) {
+    std::swap(s->raw, s->raw_alt);
+    RawBuffer &r = s->raw;
+    if (int rc = ensure(c, r.u8, r.cap, px_count)) return rc;
+    if (r.wr_lane >= 0 && r.wr_lane != lane) {
         // an earlier copy into this very buffer went through another copy stream (a slot uploaded twice without a build in between, an
         // upload abandoned by klt_slot_adopt_u8): this one is ordered behind it -- a copy-stream event, normally long complete
-        if (event_live(c, s->wr_serial)) HIPCHK(c, hipStreamWaitEvent(cs, s->ev_wr, 0));
-        else HIPCHK(c, hipStreamSynchronize(s->wr_lane == 0 ? c->cstream : c->cextra[s->wr_lane - 1]));
+        if (event_live(c, r.wr_serial)) HIPCHK(c, hipStreamWaitEvent(cs, r.ev_wr, 0));
+        else HIPCHK(c, hipStreamSynchronize(r.wr_lane == 0 ? c->cstream : c->cextra[r.wr_lane - 1]));
     }
-    if (s->consumed_valid) {
-        if (!event_live(c, s->consumed_serial)) {
+    if (r.consumed_valid) {
+        if (!event_live(c, r.consumed_serial)) {
             // the event has been re-used since: wait for the reading streams themselves (a build on the build stream reads raw frames too)
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (c->bstream) HIPCHK(c, hipStreamSynchronize(c->bstream));
         } else {
             // poll: the build in question is at most a few launches from done, and hipEventSynchronize wakes the host 50-100 us late --
             // long enough for the queues to run dry behind it (tools/ingest_probe.py: 246 us per pair with the blocking wait)
-            hipError_t q = hipEventQuery(s->ev_consumed);
+            hipError_t q = hipEventQuery(r.ev_consumed);
             for (long spins = 0; q == hipErrorNotReady; spins++) {
                 (void)hipGetLastError();                          // ("not ready" must not surface in a later hipGetLastError check)
-                if (spins > 2000000) { HIPCHK(c, hipEventSynchronize(s->ev_consumed)); q = hipSuccess; break; }   // (seconds: something else is wrong)
-                q = hipEventQuery(s->ev_consumed);
+                if (spins > 2000000) { HIPCHK(c, hipEventSynchronize(r.ev_consumed)); q = hipSuccess; break; }   // (seconds: something else is wrong)
+                q = hipEventQuery(r.ev_consumed);
             }
             if (q != hipSuccess) return fail(c, KLT_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(q));
         }
-        s->consumed_valid = false;
+        r.consumed_valid = false;
     }
-    if (pitch == ncols) HIPCHK(c, hipMemcpyAsync(s->u8, px, px_count, hipMemcpyHostToDevice, cs));
-    else HIPCHK(c, hipMemcpy2DAsync(s->u8, (size_t)ncols * esz, px, (size_t)pitch * esz, (size_t)ncols * esz, nrows, hipMemcpyHostToDevice, cs));
+    if (pitch == ncols) HIPCHK(c, hipMemcpyAsync(r.u8, px, px_count, hipMemcpyHostToDevice, cs));
+    else HIPCHK(c, hipMemcpy2DAsync(r.u8, (size_t)ncols * esz, px, (size_t)pitch * esz, (size_t)ncols * esz, nrows, hipMemcpyHostToDevice, cs));
     if (int rc = fresh_event(c, &s->ev_upload, &s->upload_serial)) return rc;
     HIPCHK(c, hipEventRecord(s->ev_upload, cs));
     s->upload_pending = true;
-    s->ev_wr = s->ev_upload; s->wr_serial = s->upload_serial; s->wr_lane = lane;
-    s->nc = ncols;
-    s->nr = nrows;
-    s->raw_kind = esz == 1 ? 1 : 2;
-    s->f32_in_raw = esz != 1;
-    s->pyr_valid = false;
-    s->eq_valid = s->rm_valid = false;
+    r.ev_wr = s->ev_upload; r.wr_serial = s->upload_serial; r.wr_lane = lane;
+    s->take_frame(ncols, nrows, esz == 1 ? 1 : 2, esz != 1);
     return KLT_OK;
 }
 
@@ -815,9 +818,7 @@ int klt_device_free(klt_ctx *c, void *p)
             // smaller than the adopted frame and holds an older image); slots adopted from other memory keep theirs
             const uint8_t *lo = (const uint8_t *)p, *hi = lo + c->dev_alloc_bytes[i];
             for (Slot &s : c->slots)
-                if (s.u8_ext && s.u8_ext >= lo && s.u8_ext < hi) {
-                    s.u8_ext = nullptr; s.raw_kind = 0; s.pyr_valid = false; s.eq_valid = s.rm_valid = false; s.gen = 0; s.nc = s.nr = 0;
-                }
+                if (s.u8_ext && s.u8_ext >= lo && s.u8_ext < hi) s.drop_frame();
             // likewise a selection mask that lives inside it (klt_set_select_mask_device): the context has no mask any more
             if (c->mask && c->mask >= lo && c->mask < hi) { c->mask = nullptr; c->mask_nc = c->mask_nr = 0; }
             hipFree(p);
@@ -839,10 +840,7 @@ int klt_device_write(klt_ctx *c, void *dst, const void *src, size_t bytes)
 
 int klt_slot_adopt_u8(klt_ctx *c, int slot, const uint8_t *dev_px, int ncols, int nrows, int pitch)
 {
-    if (!c || !dev_px) return fail(c, KLT_ERR_ARG, "null argument");
-    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535) return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if (pitch != ncols) return fail(c, KLT_ERR_ARG, "an adopted frame must have contiguous rows (pitch == ncols): it is read in place");
-    if ((long long)ncols * nrows > kMaxFramePixels) return fail(c, KLT_ERR_ARG, "frame too large (2^27 pixels or more: a plane of pixel records must stay below 2 GB)");
+    if (int rc = check_frame(c, dev_px != nullptr, ncols, nrows, pitch, FRAME_ADOPTED)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, dev_px) != hipSuccess || attr.type != hipMemoryTypeDevice) {
@@ -855,12 +853,7 @@ int klt_slot_adopt_u8(klt_ctx *c, int slot, const uint8_t *dev_px, int ncols, in
     // previous frame through its own pointer and is unaffected; a pending asynchronous upload into the slot is abandoned
     s->upload_pending = false;
     s->u8_ext = dev_px;
-    s->nc = ncols;
-    s->nr = nrows;
-    s->raw_kind = 1;
-    s->f32_in_raw = false;
-    s->pyr_valid = false;
-    s->eq_valid = s->rm_valid = false;
+    s->take_frame(ncols, nrows, 1, false);
     return KLT_OK;
 }
 
@@ -966,29 +959,22 @@ int klt_smooth_f32(klt_ctx *c, const float *src, int ncols, int nrows, const dou
     return klt_convolve_separate_f32(c, src, ncols, nrows, gauss, ng, gauss, ng, dst);      // KLTComputeSmoothedImage, convolve.py:263
 }
 
-// ------------------------------------------------------------------------------- CLAHE ingest stage
-// the two equalisation kernels on one host frame, under the context's tiles and clip limit (whatever its mode): one allocation holds the
-// frame as the caller laid it out, the equalised frame and the LUTs
-int klt_equalize_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
+// ------------------------------------------------------------------------------- the ingest stages by name
+// One host frame through one stage, whatever else the context has switched on: one allocation holds the frame as the caller laid it out
+// and, from the next 256-byte boundary on, what the stage writes (step.bytes); the stage's ncols * nrows bytes come back.  Synchronises.
+static int host_frame_through(klt_ctx *c, const IngestStep &step, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
 {
-    if (!c || !src || !dst) return fail(c, KLT_ERR_ARG, "null argument");
-    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols || (long long)ncols * nrows > kMaxFramePixels ||
-        (long long)pitch * nrows > 2 * kMaxFramePixels)
-        return fail(c, KLT_ERR_ARG, "bad image geometry");
-    if (int rc = check_equalisable(c, ncols, nrows)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = (size_t)ncols * nrows, src_bytes = (size_t)pitch * (nrows - 1) + ncols;
-    const size_t dst_off = (src_bytes + 255) & ~(size_t)255, lut_off = dst_off + eq_lut_offset(ncols, nrows);
+    const size_t dst_off = (src_bytes + 255) & ~(size_t)255;
     uint8_t *d = nullptr;
-    DEVALLOC(c, d, dst_off + eq_bytes(c, ncols, nrows));
+    DEVALLOC(c, d, dst_off + step.bytes(c, ncols, nrows));
     hipError_t e = hipMemcpyAsync(d, src, src_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        EqualizeArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.src[0] = d; a.dst[0] = d + dst_off; a.lut[0] = d + lut_off;
-        a.src_pitch = pitch;
-        enqueue_equalize(c, a, 1, ncols, nrows, c->stream);
-        e = hipMemcpyAsync(dst, d + dst_off, N, hipMemcpyDeviceToHost, c->stream);
+        const uint8_t *from = d;
+        uint8_t *to = d + dst_off;
+        step.enqueue(c, &from, pitch, &to, 1, ncols, nrows, c->stream);
+        e = hipMemcpyAsync(dst, to, N, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipGetLastError();
@@ -997,17 +983,31 @@ int klt_equalize_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pi
     return KLT_OK;
 }
 
-int klt_download_equalized_u8(klt_ctx *c, int slot, uint8_t *dst)
+// the copy behind a stage that the slot's last build (or selection on the raw frame) read; `none`: the refusal where it holds none
+static int download_stage_copy(klt_ctx *c, const IngestStep &step, int slot, uint8_t *dst, const char *none)
 {
     if (!c || !dst) return fail(c, KLT_ERR_ARG, "null argument");
     Slot *s;
     if (int rc = get_slot(c, slot, &s, false)) return rc;
-    if (!s->eq_valid || !s->eq) return fail(c, KLT_ERR_STATE, "the slot holds no equalised frame (mode 0, or a new frame or new parameters since its last build)");
+    if (!(s->*step.valid) || !(s->*step.buf)) return fail(c, KLT_ERR_STATE, none);
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = wait_built(c, s)) return rc;                 // the equalisation may have run on the build stream
-    HIPCHK(c, hipMemcpyAsync(dst, s->eq, (size_t)s->nc * s->nr, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = wait_built(c, s)) return rc;                 // the stage may have run on the build stream
+    HIPCHK(c, hipMemcpyAsync(dst, s->*step.buf, (size_t)s->nc * s->nr, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KLT_OK;
+}
+
+// the two equalisation kernels under the context's tiles and clip limit (whatever its mode)
+int klt_equalize_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
+{
+    if (int rc = check_frame(c, src && dst, ncols, nrows, pitch, FRAME_HOST)) return rc;
+    if (int rc = check_equalisable(c, ncols, nrows)) return rc;
+    return host_frame_through(c, kEqualizeStep, src, ncols, nrows, pitch, dst);
+}
+
+int klt_download_equalized_u8(klt_ctx *c, int slot, uint8_t *dst)
+{
+    return download_stage_copy(c, kEqualizeStep, slot, dst, "the slot holds no equalised frame (mode 0, or a new frame or new parameters since its last build)");
 }
 
 int klt_equalize_path(klt_ctx *c)
@@ -1016,51 +1016,18 @@ int klt_equalize_path(klt_ctx *c)
     return c->eq_path;
 }
 
-// ------------------------------------------------------------------------------- remap ingest stage
-// the remap kernel on one host frame under the context's map: one allocation holds the frame as the caller laid it out and the remapped frame
+// the remap kernel under the context's map
 int klt_remap_u8(klt_ctx *c, const uint8_t *src, int ncols, int nrows, int pitch, uint8_t *dst)
 {
-    if (!c || !src || !dst) return fail(c, KLT_ERR_ARG, "null argument");
-    if (ncols <= 0 || nrows <= 0 || ncols > 65535 || nrows > 65535 || pitch < ncols || (long long)ncols * nrows > kMaxFramePixels ||
-        (long long)pitch * nrows > 2 * kMaxFramePixels)
-        return fail(c, KLT_ERR_ARG, "bad image geometry");
+    if (int rc = check_frame(c, src && dst, ncols, nrows, pitch, FRAME_HOST)) return rc;
     if (!c->rmp.d) return fail(c, KLT_ERR_STATE, "no map set (klt_set_remap)");
-    if (ncols != c->rmp.nc || nrows != c->rmp.nr)
-        return fail(c, KLT_ERR_ARG, "remapping: the frame is " + std::to_string(ncols) + " by " + std::to_string(nrows) + ", the map " +
-                                        std::to_string(c->rmp.nc) + " by " + std::to_string(c->rmp.nr));
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = (size_t)ncols * nrows, src_bytes = (size_t)pitch * (nrows - 1) + ncols;
-    const size_t dst_off = (src_bytes + 255) & ~(size_t)255;
-    uint8_t *d = nullptr;
-    DEVALLOC(c, d, dst_off + N);
-    hipError_t e = hipMemcpyAsync(d, src, src_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        RemapArgs a;
-        std::memset(&a, 0, sizeof(a));
-        a.src[0] = d; a.dst[0] = d + dst_off;
-        a.src_pitch = pitch;
-        a.batch = 1;
-        enqueue_remap(c, a, c->stream);
-        e = hipMemcpyAsync(dst, d + dst_off, N, hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    hipFree(d);
-    if (e != hipSuccess) return fail(c, KLT_ERR_DEVICE, hipGetErrorString(e));
-    return KLT_OK;
+    if (int rc = check_remappable(c, ncols, nrows)) return rc;
+    return host_frame_through(c, kRemapStep, src, ncols, nrows, pitch, dst);
 }
 
 int klt_download_remapped_u8(klt_ctx *c, int slot, uint8_t *dst)
 {
-    if (!c || !dst) return fail(c, KLT_ERR_ARG, "null argument");
-    Slot *s;
-    if (int rc = get_slot(c, slot, &s, false)) return rc;
-    if (!s->rm_valid || !s->rm) return fail(c, KLT_ERR_STATE, "the slot holds no remapped frame (no map set, or a new frame or a new map since its last build)");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = wait_built(c, s)) return rc;                 // the remap may have run on the build stream
-    HIPCHK(c, hipMemcpyAsync(dst, s->rm, (size_t)s->nc * s->nr, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return KLT_OK;
+    return download_stage_copy(c, kRemapStep, slot, dst, "the slot holds no remapped frame (no map set, or a new frame or a new map since its last build)");
 }
 
 int klt_remap_path(klt_ctx *c)

@@ -293,10 +293,7 @@ int select_planes(klt_ctx *c, Slot *s, int use_pyramid, const float **img_out, c
     if (s->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
     if (int rc = wait_upload(c, s, c->stream)) return rc;
     if (int rc = wait_built(c, s)) return rc;              // a build of this slot may still read the raw frame's buffers
-    if (c->rmp.d)                                          // remap ingest stage: likewise, in front (with both on the equalised copy is one of the remapped frame)
-        if (int rc = ensure_remapped(c, &s, 1, c->stream)) return rc;
-    if (c->eqp.mode == 1)                                  // CLAHE ingest stage: the readers below take the equalised copy (raw8), made now if it is stale
-        if (int rc = ensure_equalized(c, &s, 1, c->stream)) return rc;
+    if (int rc = ensure_ingested(c, &s, 1, c->stream)) return rc;      // the ingest stages: the readers below take the chain's output (raw8), made now where it is stale
     bool grads_done = false;
     if (c->p.smoothBeforeSelecting && fused_smooth_ok(c)) {
         const void *raw = s->raw_kind == 1 ? (const void *)raw8(c, s) : (const void *)rawf(s);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "klt_internal.h"
+#include "ingest_rule.h"
 
 struct klt_ctx;
 
@@ -41,12 +42,30 @@ inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_redu
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
+// One of a slot's two alternating raw buffers with everything that orders work on it (Slot::raw, Slot::raw_alt: an asynchronous upload
+// exchanges the two whole)
+struct RawBuffer {
+    uint8_t *u8 = nullptr;
+    size_t cap = 0;                   // bytes
+    hipEvent_t ev_consumed = nullptr; // last kernel on `stream` that read the raw frame in it
+    uint64_t consumed_serial = 0;     // when the ring handed that event out (event_live)
+    bool consumed_valid = false;
+    // last asynchronous copy INTO the buffer (consecutive uploads go round-robin over the copy streams: the next copy into the same
+    // buffer may be issued on another stream and must wait for this one)
+    hipEvent_t ev_wr = nullptr;
+    uint64_t wr_serial = 0;
+    int wr_lane = -1;
+};
+
+// The points of the ingest chain in their order: the frame as it came, its remapped copy (klt_set_remap), its equalised copy
+// (klt_set_equalize_params).  A stage reads the output of the last stage in front of it that is switched on (ingest_output)
+enum IngestStage { INGEST_FRAME, INGEST_REMAP, INGEST_EQUALIZE };
+
 struct Slot {
     int nc = 0, nr = 0;
     int raw_kind = 0;                 // 0 none, 1 u8, 2 f32
-    uint8_t *u8 = nullptr;
     float *f32 = nullptr;
-    size_t u8_cap = 0, f32_cap = 0;   // pixels
+    size_t f32_cap = 0;               // pixels
     float *planes = nullptr;          // 3 pyramids, level-concatenated
     size_t planes_cap = 0;            // floats
     Level lv[KLT_MAX_LEVELS];
@@ -64,8 +83,7 @@ struct Slot {
     uint64_t built_cfg = 0;           // the slot to a full build
     uint64_t gen = 0;                // which build filled the pyramids (unique per build; travels with klt_swap_slots)
     hipEvent_t ev_upload = nullptr;   // asynchronous ingest: frame copy finished (the build waits for it)
-    hipEvent_t ev_consumed = nullptr; // last kernel on `stream` that read the raw frame u8
-    uint64_t upload_serial = 0, consumed_serial = 0, consumed_alt_serial = 0;   // when the ring handed those events out (event_live)
+    uint64_t upload_serial = 0;       // when the ring handed that event out (event_live)
     hipEvent_t ev_built = nullptr;    // KLT_OPT_BUILD_STREAM: end of the build that filled this slot's pyramids (recorded on the build stream)
     uint64_t built_serial = 0;
     bool built_pending = false;       // the main stream has not waited for ev_built yet
@@ -73,21 +91,13 @@ struct Slot {
     hipEvent_t ev_read = nullptr;     // last tracker launch on the main stream that reads this slot's pyramids (a build on the build
     uint64_t read_serial = 0;         // stream waits for it; selections synchronise before they return and need no mark)
     bool read_valid = false;
-    bool upload_pending = false, consumed_valid = false;
+    bool upload_pending = false;
     // asynchronous ingest alternates between two raw buffers so that a copy never has to wait (on the device) for
     // kernels still reading the previous frame: making the copy stream wait on a compute-stream event blocks the
     // HOST for the duration of the queued work on this runtime (measured 150-800 us per step)
-    uint8_t *u8_alt = nullptr;
-    size_t u8_alt_cap = 0;
+    RawBuffer raw, raw_alt;           // the buffer that holds (or is receiving) the slot's frame, and the other one
     const uint8_t *u8_ext = nullptr;  // klt_slot_adopt_u8: the frame IS this caller-owned device buffer (read in place, never written or freed here)
-    hipEvent_t ev_consumed_alt = nullptr;
-    bool consumed_alt_valid = false;
-    // last asynchronous copy INTO each raw buffer (consecutive uploads go round-robin over the copy streams: the next copy into the
-    // same buffer may be issued on another stream and must wait for this one)
-    hipEvent_t ev_wr = nullptr, ev_wr_alt = nullptr;
-    uint64_t wr_serial = 0, wr_alt_serial = 0;
-    int wr_lane = -1, wr_alt_lane = -1;
-    bool f32_in_raw = false;          // klt_upload_f32_async: the f32 frame lives in the alternating raw buffers (`u8`, 4 bytes per pixel), not in `f32`
+    bool f32_in_raw = false;          // klt_upload_f32_async: the f32 frame lives in the alternating raw buffers (`raw.u8`, 4 bytes per pixel), not in `f32`
     // klt_set_equalize_params, mode 1: the equalised copy of the 8-bit frame (nc x nr bytes, rounded up to 256) with the per-tile LUTs
     // it was made from behind it, allocated when first needed.  eq_valid: it was made from the frame the slot holds now -- this upload or
     // adoption -- under the parameters the context holds now (a new frame, klt_slot_free or new parameters clear it)
@@ -95,14 +105,16 @@ struct Slot {
     size_t eq_cap = 0;                // bytes
     bool eq_valid = false;
     // klt_set_remap: the remapped copy of the 8-bit frame (nc x nr bytes), allocated when first needed.  rm_valid: it was made from the
-    // frame the slot holds now under the map the context holds now (cleared wherever eq_valid is -- new equalisation parameters
-    // excepted, they leave it -- and by a new map)
+    // frame the slot holds now under the map the context holds now.  What clears the two flags: void_copies_from, nothing else
     uint8_t *rm = nullptr;
     size_t rm_cap = 0;                // bytes
     bool rm_valid = false;
+    // a frame arrives (every upload, adoption) / the slot holds no frame any more (api_frames.hip)
+    void take_frame(int ncols, int nrows, int kind, bool in_raw);
+    void drop_frame();
 };
 
-inline const float *rawf(const Slot *s) { return s->f32_in_raw ? reinterpret_cast<const float *>(s->u8) : s->f32; }
+inline const float *rawf(const Slot *s) { return s->f32_in_raw ? reinterpret_cast<const float *>(s->raw.u8) : s->f32; }
 
 struct FeatBuf { klt_feat *d = nullptr; int cap = 0; bool view = false; hipEvent_t comm_done = nullptr; /* last collective that touched it */ };
 
@@ -358,10 +370,11 @@ struct klt_ctx {
 namespace kltapi {
 
 // the 8-bit frame a slot holds as it came: the caller's device memory (adopted) or the slot's own raw buffer
-inline const uint8_t *frame8(const Slot *s) { return s->u8_ext ? s->u8_ext : s->u8; }
-// the 8-bit frame a slot's readers take: the equalised copy with CLAHE switched on (ensure_equalized has made it), else the remapped
-// copy with a map set (ensure_remapped has made it), else the frame as it came
-inline const uint8_t *raw8(const klt_ctx *c, const Slot *s) { return c->eqp.mode == 1 ? s->eq : (c->rmp.d ? s->rm : frame8(s)); }
+inline const uint8_t *frame8(const Slot *s) { return s->u8_ext ? s->u8_ext : s->raw.u8; }
+// the slot's 8-bit frame behind the stages of the chain up to and including `upto` that are switched on (api_frames.hip: the chain)
+const uint8_t *ingest_output(const klt_ctx *c, const Slot *s, IngestStage upto);
+// the 8-bit frame a slot's readers take: the output of the whole chain (ensure_ingested has made it)
+inline const uint8_t *raw8(const klt_ctx *c, const Slot *s) { return ingest_output(c, s, INGEST_EQUALIZE); }
 
 int fail(klt_ctx *c, int code, const std::string &msg);      // sets the context's message, returns `code`
 
@@ -510,10 +523,7 @@ inline int own_records(klt_ctx *c, int fb, std::initializer_list<int> others, co
 }
 
 // ---- api_frames.hip
-// The kernels address a plane with 32-bit BYTE offsets into a buffer descriptor of 2 GB (raw buffer operations, klt_internal.h), and the
-// largest plane is the record plane of level 0 with 12 bytes per pixel: a frame must stay below 2^27 pixels (1.5 GB of records).
-// 2^27 - 1 pixels is a 16 384 x 8 191 frame; the largest frame of the test suite is 7680 x 4320.
-constexpr long long kMaxFramePixels = (1LL << 27) - 1;
+// (kMaxFramePixels, the bound on a frame: ingest_rule.h)
 void make_taps(const double *k, int n, Taps &t);
 int upload_raw(klt_ctx *c, int slot, const void *px, int ncols, int nrows, int pitch, int kind);
 int layout_pyramid(klt_ctx *c, Slot *s);
@@ -526,14 +536,18 @@ int enqueue_fused_smooth_grad(klt_ctx *c, int batch, const void *const *raw, int
 L0Plan plan_l0(const klt_ctx *c, int batch, int kind, int nc, int nr, bool uniform = true, bool want_hred = false, bool want_lean = false);
 int enqueue_fused_grad(klt_ctx *c, int batch, const float *const *img, float *const *rec, int nc, int nr, bool u8_input = false);
 int build_pyramids_batch(klt_ctx *c, const int *slot_ids, int n);
-// CLAHE switched on (klt_ctx::eqp.mode == 1): the 8-bit frames of these slots that have no valid equalised copy get one, enqueued on
-// `st` (behind the frames' uploads: the caller has waited for them there) -- the slots of one frame size in the same two launches.
-// KLT_ERR_STATE for an f32 slot, KLT_ERR_ARG for a frame the tile grid does not fit, KLT_ERR_NOMEM; *launched (optional): something was enqueued
-int ensure_equalized(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched = nullptr);
-// A map set (klt_ctx::rmp.d): the 8-bit frames of these slots that have no valid remapped copy get one, enqueued on `st` like the
-// equalised copies, in front of them -- the slots of a call in one launch per KLT_MAX_BATCH.  KLT_ERR_STATE for an f32 slot, KLT_ERR_ARG
-// for a frame whose size is not the map's, KLT_ERR_NOMEM; *launched (optional): something was enqueued
-int ensure_remapped(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool *launched = nullptr);
+// The ingest chain in front of every reader of a slot's raw frame: the 8-bit frames of these slots that have no valid copy of a stage
+// that is switched on get one, enqueued on `st` (behind the frames' uploads: the caller has waited for them there), remap before CLAHE,
+// the slots of one frame size in the same launches, KLT_MAX_BATCH at a time.  Every refusal of every stage comes before the first
+// allocation, every allocation before the first launch: a call that fails has enqueued nothing and leaves the slots' copies and flags as
+// they were.  KLT_ERR_STATE for an f32 slot or a launch during a stream capture, KLT_ERR_ARG for a frame a stage does not take,
+// KLT_ERR_NOMEM.  of_build: klt_remap_path / klt_equalize_path become 1 for the stages that launch (the build has cleared both)
+int ensure_ingested(klt_ctx *c, Slot *const *slots, int n, hipStream_t st, bool of_build = false);
+// ... and the refusals of one slot that hold whether or not anything would be launched (the build asks in front of layout_pyramid)
+int ingest_refusal(klt_ctx *c, const Slot *s);
+// Something changed at `stage` of the chain: the copies of `s` from there on are stale (a new frame: everything, the pyramids included;
+// a new map: the remapped and the equalised copy; new equalisation parameters: the equalised copy)
+void void_copies_from(Slot &s, IngestStage stage);
 // KLT_OPT_L0_LAZY_GRAD: whoever reads lv[0].img / .gx / .gy of a built slot calls this first.  The records of a lean slot are made from its
 // compact image by the gradient launch of the levels >= 1, on the main stream behind the slot's build (wait_built); a caller that
 // enqueues on the build stream is ordered behind it.  `asked` (every reader but the tracker's own fallback): the slot's next build is full.

@@ -242,6 +242,15 @@ def equalisable(ncols, nrows, tiles_x, tiles_y):
     return widest * 255 < 2 ** 32
 
 
+def _frame_class(img):
+    """What the ingest stages ask of a frame: (it is a single-channel 8-bit image -- a 2-D uint8 array or a Pillow image of mode 'L' --,
+    its shape (nrows, ncols) if it is one -- of any other array whatever leads its shape, which may be less --, what to call it in a
+    refusal)"""
+    if isinstance(img, np.ndarray):
+        return img.dtype == np.uint8 and img.ndim == 2, tuple(img.shape[:2]), "a {0} array of {1} dimensions".format(img.dtype, img.ndim)
+    return getattr(img, "mode", None) == "L", (img.size[1], img.size[0]), "an image of mode {0!r}".format(getattr(img, "mode", None))
+
+
 def equalization_for_frames(tc, *imgs):
     """The klt_equalize_params of a call on these frames (equalize_params_from_tc).  Switched on, a ValueError that names tc.equalization
     -- before any device work -- for a frame that is not a single-channel 8-bit image (a float array, a colour or "F" Pillow image) and
@@ -249,15 +258,11 @@ def equalization_for_frames(tc, *imgs):
     eq = equalize_params_from_tc(tc)
     if eq.mode:
         for img in imgs:
-            if isinstance(img, np.ndarray):
-                ok, (nrows, ncols) = img.dtype == np.uint8 and img.ndim == 2, img.shape[:2]
-                what = "a {0} array of {1} dimensions".format(img.dtype, img.ndim)
-            else:
-                ok, (ncols, nrows) = getattr(img, "mode", None) == "L", img.size
-                what = "an image of mode {0!r}".format(getattr(img, "mode", None))
+            ok, shape, what = _frame_class(img)
             if not ok:
                 raise ValueError("tc.equalization = 'clahe' takes single-channel 8-bit frames (a 2-D uint8 array or a Pillow image of "
                                  "mode 'L'), not {0}".format(what))
+            nrows, ncols = shape
             if not equalisable(ncols, nrows, eq.tiles_x, eq.tiles_y):
                 raise ValueError("tc.equalization = 'clahe': a {0} by {1} frame does not take tc.clahe_tiles = ({2}, {3}) (more tiles "
                                  "than pixels, or tiles too large for the 32-bit interpolation)".format(ncols, nrows, eq.tiles_x, eq.tiles_y))
@@ -397,12 +402,7 @@ def remap_for_frames(tc, *imgs):
     table = remap_from_tc(tc)
     if table is not None:
         for img in imgs:
-            if isinstance(img, np.ndarray):
-                ok, shape = img.dtype == np.uint8 and img.ndim == 2, tuple(img.shape[:2])
-                what = "a {0} array of {1} dimensions".format(img.dtype, img.ndim)
-            else:
-                ok, shape = getattr(img, "mode", None) == "L", (img.size[1], img.size[0])
-                what = "an image of mode {0!r}".format(getattr(img, "mode", None))
+            ok, shape, what = _frame_class(img)
             if not ok:
                 raise ValueError("tc.remap takes single-channel 8-bit frames (a 2-D uint8 array or a Pillow image of mode 'L'), not {0}".format(what))
             if shape != table.shape:

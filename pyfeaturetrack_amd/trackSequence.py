@@ -270,10 +270,9 @@ class _Sequence:
             self.stager = _FrameStager(self.frames, stage, (self.nrows, self.ncols), workers=workers)
 
     def ingest(self, slot, img, k, staged=False, wait=True):
-        if self.equalized and (img.dtype != np.uint8 or img.ndim != 2):
-            raise ValueError("tc.equalization = 'clahe' takes single-channel 8-bit frames; frame {0} of the clip is not one".format(k))
-        if self.remapped and (img.dtype != np.uint8 or img.ndim != 2):
-            raise ValueError("tc.remap takes single-channel 8-bit frames; frame {0} of the clip is not one".format(k))
+        for on, setting in ((self.equalized, "tc.equalization = 'clahe'"), (self.remapped, "tc.remap")):
+            if on and (img.dtype != np.uint8 or img.ndim != 2):
+                raise ValueError("{0} takes single-channel 8-bit frames; frame {1} of the clip is not one".format(setting, k))
         if img.shape != (self.nrows, self.ncols):
             from .error import KLTError
             KLTError("(KLTTrackSequence) Size of incoming image ({0} by {1}) is different from size of previous image "

@@ -12,7 +12,7 @@ import numpy as np
 import equalize_expected as ee
 import remap_expected as re_
 
-# csrc/equalize_kernels.hip, enqueue_equalize (csrc/api_frames.hip), csrc/remap_kernels.hip
+# csrc/equalize_kernels.hip, eq_apply_split and for_each_group (csrc/ingest_rule.h), csrc/remap_kernels.hip
 LUT_THREADS, HIST_COPIES, APPLY_THREADS = 1024, 16, 256
 SPLIT_TARGET, SPLIT_ROWS = 1024, 4
 PIECE, PIECES_ACROSS, GROUP_ROWS = 4, 16, 16
@@ -487,6 +487,21 @@ def remap_draw(seed):
     kind = int(rs.randint(0, 3))
     frame = (noise_frame(ncols, nrows, seed), re_.two_level_frame(ncols, nrows, seed), re_.textured_frame(ncols, nrows, seed))[kind]
     return frame, (mx, my), pitch, name
+
+
+# ------------------------------------------------------------------------------------------------------------------ the grouping
+def groups(keys, most=MAX_BATCH):
+    """for_each_group (csrc/ingest_rule.h): the indices of `keys` gathered into launches -- in first-appearance order, at most `most`
+    equal keys to a group, the next equal one opening a group where it stands"""
+    out, done = [], [False] * len(keys)
+    for i0, first in enumerate(keys):
+        if done[i0]:
+            continue
+        members = [i for i in range(i0, len(keys)) if not done[i] and keys[i] == first][:most]
+        for i in members:
+            done[i] = True
+        out.append(members)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------- frames for the slots

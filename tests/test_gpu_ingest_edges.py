@@ -281,6 +281,75 @@ def _adopted_16(ctx, plain, stages):
         ctx.device_free(dev)
 
 
+# ---- a call that the SECOND stage refuses enqueues nothing and leaves the slots' copies as they were (ensure_ingested: every refusal of
+# every stage in front of the first allocation and the first launch)
+SMALL = (40, 30)
+STAGE_FAMILIES = ("remap", "equalize_lut", "equalize_apply")
+GRID_REFUSAL = "error -1: equalisation: the frame is smaller than the tile grid"
+NO_REMAPPED, NO_EQUALISED = "error -3: the slot holds no remapped frame", "error -3: the slot holds no equalised frame"
+
+
+def _grid_past_the_frame(ctx, count):
+    """a map for 40 x 30 and a tile grid 64 wide, which 40 columns do not fit; `count` slots uploaded -> (the frames remapped, then
+    equalised under 3 x 2 tiles)"""
+    raw = [ie.slot_frame(SMALL[0], SMALL[1], 160 + k) for k in range(count)]
+    mx, my = re_.rotation_map(SMALL[0], SMALL[1], MAP[1])
+    remapped = [re_.remap(f, mx, my) for f in raw]
+    ctx.set_remap(mx, my)
+    ctx.set_equalize_params(mode=1, tiles_x=64, tiles_y=2, clip_q8=768)
+    for k in range(count):
+        ctx.upload(k, raw[k])
+    return remapped, [ee.clahe(f, 3, 2, 768) for f in remapped]
+
+
+def _refused(ctx, call, message, slots):
+    """`call` raises with `message`, no stage family shows a launch, and no slot holds a copy afterwards"""
+    from pyfeaturetrack_amd._abi import KltBackendError
+    ctx.timing_enable(True)
+    try:
+        with pytest.raises(KltBackendError, match=message):
+            call()
+        times = {t["name"]: t["launches"] for t in ctx.timing_read()}
+    finally:
+        ctx.timing_enable(False)
+    assert not any(times.get(f) for f in STAGE_FAMILIES), times
+    for k in slots:
+        with pytest.raises(KltBackendError, match=NO_REMAPPED):
+            ctx.download_remapped(k, *SMALL)
+        with pytest.raises(KltBackendError, match=NO_EQUALISED):
+            ctx.download_equalized(k, *SMALL)
+
+
+def _refused_build(ctx, plain):
+    remapped, want = _grid_past_the_frame(ctx, 2)
+    _refused(ctx, lambda: ctx.build_pyramids_batch([0, 1], sync=True), GRID_REFUSAL, (0, 1))
+    # a frame of another size beside them: the first stage's refusal, and nothing enqueued for slot 0 either
+    ctx.upload(2, ie.slot_frame(NC, NR, 162))
+    _refused(ctx, lambda: ctx.build_pyramids_batch([0, 2], sync=True), "error -1: remapping: the frame is 67 by 45, the map 40 by 30", (0, 1))
+    ctx.set_equalize_params(mode=1, tiles_x=3, tiles_y=2, clip_q8=768)
+    times = _launches(ctx, (0, 1))
+    assert [times.get(f) for f in STAGE_FAMILIES] == [1, 1, 1] and ctx.remap_path() == 1 and ctx.equalize_path() == 1, times
+    for k, planes in zip((0, 1), _plain_planes(plain, want)):
+        _same_bytes(ctx.download_remapped(k, *SMALL), remapped[k], "klt_download_remapped_u8 of slot %d" % k)
+        _same_bytes(ctx.download_equalized(k, *SMALL), want[k], "klt_download_equalized_u8 of slot %d" % k)
+        _same_planes(_planes(ctx, k), planes, "slot %d" % k)
+
+
+def _refused_selection(ctx, plain):
+    tc = make_tc(levels=1, ss=2, window=3)                   # (the default border leaves no candidate in a frame this small)
+    ctx.configure(tc)
+    plain.configure(tc)
+    remapped, want = _grid_past_the_frame(ctx, 1)
+    _refused(ctx, lambda: ctx.select(0, 40, use_pyramid=False), GRID_REFUSAL, (0,))
+    ctx.set_equalize_params(mode=1, tiles_x=3, tiles_y=2, clip_q8=768)
+    got, placed = ctx.select(0, 40, use_pyramid=False)
+    plain.upload(0, want[0])
+    exp, placed_exp = plain.select(0, 40, use_pyramid=False)
+    assert placed == placed_exp and placed > 0 and got.tobytes() == exp.tobytes()
+    _same_bytes(ctx.download_remapped(0, *SMALL), remapped[0], "the remapped frame the selection read")
+    _same_bytes(ctx.download_equalized(0, *SMALL), want[0], "the equalised frame the selection read")
+
+
 SLOT_CASES = {
     "remap_33_slots": lambda c, p: _remap_33(c, p),
     "clahe_33_and_3_slots_clip_768": lambda c, p: _clahe_36(c, p, 768),
@@ -293,6 +362,8 @@ SLOT_CASES = {
     "adopted_16_residues_clahe": lambda c, p: _adopted_16(c, p, ("clahe",)),
     "adopted_16_residues_remap": lambda c, p: _adopted_16(c, p, ("remap",)),
     "adopted_16_residues_remap_then_clahe": lambda c, p: _adopted_16(c, p, ("remap", "clahe")),
+    "second_stage_refusal_enqueues_nothing": lambda c, p: _refused_build(c, p),
+    "second_stage_refusal_enqueues_nothing_selection": lambda c, p: _refused_selection(c, p),
 }
 
 

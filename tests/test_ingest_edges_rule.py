@@ -29,17 +29,20 @@ def test_the_kernels_constants_are_the_sources():
     assert "for (int i = tid; i < Tx * 16; i += APPLY_THREADS) {" in eq
     assert "const int t = (int)((((unsigned)xs + 1u) * (unsigned)Tx - 1u) / (unsigned)nc);" in eq
     api = (CSRC / "api_frames.hip").read_text()
-    body = api[api.index("static int enqueue_equalize"):api.index("int ensure_equalized")]
-    assert "int split = (%d + bands * batch - 1) / (bands * batch);" % ie.SPLIT_TARGET in body
-    assert "const int most = std::max(1, nr / a.tiles_y / %d);" % ie.SPLIT_ROWS in body
-    assert "a.split = std::max(1, std::min(split, most));" in body and "const int bands = a.tiles_y + 1;" in body
+    rule = (CSRC / "ingest_rule.h").read_text()                  # (the host rules of the ingest path; api_frames.hip launches by them)
+    body = rule[rule.index("inline int eq_apply_split"):rule.index("// ---- grouping")]
+    assert "const int split = (%d + bands * batch - 1) / (bands * batch);" % ie.SPLIT_TARGET in body
+    assert "const int most = std::max(1, nrows / tiles_y / %d);" % ie.SPLIT_ROWS in body
+    assert "return std::max(1, std::min(split, most));" in body and "const int bands = tiles_y + 1;" in body
+    assert api.count("a.split = eq_apply_split(nr, a.tiles_y, batch);") == 1
     rm = (CSRC / "remap_kernels.hip").read_text()
     assert int(re.search(r"constexpr int PIECE = (\d+);", rm).group(1)) == ie.PIECE
     assert int(re.search(r"constexpr int PIECES_ACROSS = (\d+);", rm).group(1)) == ie.PIECES_ACROSS
     assert int(re.search(r"constexpr int WAVE_ROWS = \d+, GROUP_ROWS = (\d+);", rm).group(1)) == ie.GROUP_ROWS
     assert "const int per_row = (a.ncols + 2 * (PIECE - 1)) / PIECE;" in rm and "if (a.ncols >= 2) klt_launch(remap_kernel<true>" in rm
     assert int(re.search(r"constexpr int KLT_MAX_BATCH = (\d+);", (CSRC / "l0_plan.h").read_text()).group(1)) == ie.MAX_BATCH
-    assert "for (size_t i0 = 0; i0 < todo.size(); i0 += KLT_MAX_BATCH) {" in api and "i < todo.size() && B < KLT_MAX_BATCH; i++)" in api
+    assert "T group[KLT_MAX_BATCH];" in rule and "i < n && count < KLT_MAX_BATCH; i++)" in rule
+    assert api.count("return a.first == b.first && same_size(a.second, b.second);") == 1    # the stages' launches: one stage, one size
     # the split of the shapes the table is built around
     assert ie.clahe_split(1025, 1) == (256, "rows") and ie.clahe_split(2049, 1) == (512, "1024") and ie.clahe_split(1080, 8) == (33, "rows")
     assert ie.clahe_split(36, 2) == (4, "rows") and ie.clahe_split(65535, 64) == (16, "1024")
