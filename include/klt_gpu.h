@@ -35,7 +35,8 @@ extern "C" {
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
                                    * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path / klt_set_remap / klt_remap_u8 / klt_download_remapped_u8 / klt_remap_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
-                                   * klt_select_score_path and klt_download_prepared_keys, read-only diagnostic entries) */
+                                   * klt_select_score_path, klt_select_pick_path and klt_download_prepared_keys, read-only diagnostic
+                                   * entries) */
 #define KLT_MAX_KERNEL_WIDTH 71   /* convolve.py:28 */
 #define KLT_MAX_LEVELS 8
 
@@ -924,6 +925,22 @@ int klt_download_prepared_keys(klt_ctx *ctx, int slot, uint64_t *dst, size_t cap
 #define KLT_SCORE_PIPELINE 1        /* *rows, *cols: sat_rows_pipe / sat_cols_pipe */
 #define KLT_SCORE_FUSED_KEYS 2      /* *cols only: cols_eigen_pipe, the column pass and the eigenvalue keys in one launch (klt_select_prepare_async) */
 int klt_select_score_path(klt_ctx *ctx, int *rows, int *cols);
+/* Diagnostic, read-only: how the last COMPLETED selection (klt_select, klt_select_async, klt_select_begin_async + klt_select_finish) got
+ * from the eigenvalue keys to the list, recorded where the decisions are taken; nothing is enqueued.  KLT_ERR_STATE before the first, and
+ * while a selection is pending.  Every path gives the same list -- the tests use this to know that the code they were written for ran. */
+typedef struct klt_select_pick {
+    int32_t walk;            /* 0: sorted serial walk; 1: parallel minimum-distance passes */
+    int32_t order;           /* 0: the greedy walk alone; 1: accepted candidates ranked by counting; 2: accepted keys sorted, then walked */
+    int32_t cut;             /* 1: the top-K prefilter was planned (more than 262144 candidates and a target below half of them) */
+    int32_t attempts;        /* 1, or 2: the cut's candidates ran out and the selection was repeated with every candidate */
+    int32_t passes;          /* parallel: minimum-distance passes launched, both attempts; serial: 0 */
+    int32_t looks;           /* parallel: times the host looked at the outcome; serial: 0 */
+    int32_t instantiation;   /* parallel: 9 (the radius compiled in) or 0 (any radius); serial: 0 */
+    int32_t pass_lds;        /* parallel: dynamic LDS bytes of a pass; serial: 0 */
+    int32_t grid;            /* cell grid of the greedy walk, where one ran: 0 in LDS, 1 in global memory */
+    int32_t sparse;          /* parallel: 1 when the later passes took several tiles per workgroup (a replacement behind the cut) */
+} klt_select_pick;
+int klt_select_pick_path(klt_ctx *ctx, klt_select_pick *out);
 
 /* ---- standalone convolutions (host buffers in / out, synchronous) ---------------------------- */
 /* _convolveSeparate(imgin, horiz_kernel, vert_kernel), convolve.py:208-219 (SciPy branch: scipy.ndimage.convolve1d along axis 1, then

@@ -100,6 +100,11 @@ class KltSelectGrid(C.Structure):
     _fields_ = [("cell_width", C.c_int32), ("cell_height", C.c_int32), ("max_per_cell", C.c_int32)]
 
 
+class KltSelectPick(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("walk", "order", "cut", "attempts", "passes", "looks", "instantiation", "pass_lds", "grid",
+                                         "sparse")]
+
+
 class KltAffineRec(C.Structure):
     _fields_ = [("aff_x", C.c_float), ("aff_y", C.c_float), ("Axx", C.c_float), ("Ayx", C.c_float), ("Axy", C.c_float),
                 ("Ayy", C.c_float), ("valid", C.c_int32), ("pad", C.c_int32)]
@@ -244,6 +249,7 @@ SYMBOLS = {
     "klt_set_score_override": (_I, [_P, _P, _I]),
     "klt_download_prepared_keys": (_I, [_P, _I, _P, C.c_size_t, _PI, _PI]),
     "klt_select_score_path": (_I, [_P, _PI, _PI]),
+    "klt_select_pick_path": (_I, [_P, _P]),
     "klt_download_sorted_candidates": (_I, [_P, _P, _P, _P, _I, _PI]),
     "klt_smooth_f32": (_I, [_P, _P, _I, _I, C.POINTER(C.c_double), _I, _P]),
     "klt_convolve_separate_f32": (_I, [_P, _P, _I, _I, C.POINTER(C.c_double), _I, C.POINTER(C.c_double), _I, _P]),

@@ -869,6 +869,16 @@ class Context:
         self._check(self._lib.klt_select_score_path(self._h, C.byref(rows), C.byref(cols)))
         return rows.value, cols.value
 
+    def select_pick_path(self):
+        """klt_select_pick_path: how the last completed selection got from the keys to the list, as a dict -- walk 0 serial / 1 parallel;
+        order 0 greedy walk only / 1 ranked by counting / 2 accepted keys sorted and walked; cut 0 / 1 prefilter planned; attempts 1 / 2;
+        passes launched; host looks; instantiation 9 / 0; pass_lds bytes; grid 0 LDS / 1 global; sparse 0 / 1.  A diagnostic: every path
+        gives the same list."""
+        from ._abi import KltSelectPick
+        p = KltSelectPick()
+        self._check(self._lib.klt_select_pick_path(self._h, C.byref(p)))
+        return {k: int(getattr(p, k)) for k, _ in KltSelectPick._fields_}
+
     def sorted_candidates(self, n):
         val = np.empty(n, np.float32)
         x = np.empty(n, np.int32)

@@ -108,7 +108,7 @@ int select_job_rounds(klt_ctx *c, SelectJob &j)
 {
     {
         TimerScope t(c, F_NMS, (double)j.n * 16);
-        for (int r = 0; r < j.rounds_per_look; r++, j.round++)
+        for (int r = 0; r < j.rounds_per_look; r++, j.round++, j.passes++)
             if (const int e = launch_mis_round(c->stream, j.ma, j.round))
                 return fail(c, KLT_ERR_DEVICE, std::string("minimum-distance pass: ") + hipGetErrorString((hipError_t)e));
     }
@@ -166,8 +166,10 @@ int select_job_finish(klt_ctx *c, SelectJob &j)
         if (j.mode == KLT_REPLACING_SOME) needed += 1;
         c->mis_rounds_hint = needed < 2 ? 2 : (needed > 32 ? 32 : needed);
         c->sorted_keys = j.by_rank ? nullptr : c->keys2; c->sorted_count = j.by_rank ? 0 : (int)j.np2;
-        // ran out of accepted candidates although the prefilter dropped some: repeat with every candidate
-        if (j.filtered && res[1] && info[1] < info[2]) {
+        // ran out of accepted candidates although the prefilter dropped some: repeat with every candidate.  info[3] is mis_init_kernel's
+        // word "the threshold bin kept a valid key out" -- exact, where info[1] and info[2] count the histogram's sample only (a sample
+        // that lies wholly at or above the bin says nothing of the keys it did not see)
+        if (j.filtered && res[1] && info[3]) {
             if (int rc = restore_list(c, j.fl, j.n)) return rc;
             j.attempt = 1;
             if (int rc = select_job_start(c, j)) return rc;
@@ -178,6 +180,9 @@ int select_job_finish(klt_ctx *c, SelectJob &j)
     }
     if (j.pre) j.pre->gen = 0;                                       // a score set is used once
     HIPCHK(c, hipGetLastError());
+    // klt_select_pick_path
+    c->pick = klt_select_pick{1, j.by_rank ? 1 : 2, j.prefilter ? 1 : 0, j.attempt + 1, j.passes, looks, j.ma.R == 9 ? 9 : 0,
+                              (int32_t)mis_pass_lds(j.ma), j.pa.grid_in_lds ? 0 : 1, j.ma.sparse};
     return looks > 1 ? 1 : KLT_OK;
 }
 
@@ -457,7 +462,7 @@ int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa
     ma.keys = pl.pre ? pl.pre->keys : c->keys; ma.seed = pl.pre ? sa.seedmap : nullptr; ma.seed_stamp = c->seed_stamp; ma.ncols = sa.ncols;
     ma.st = c->mis_st; ma.list = c->mis_list; ma.cnt = base + cnt.lists;
     ma.remaining = base + cnt.remaining; ma.acc_cnt = base + cnt.tile_accepted; ma.acc_cap = tile_cap;
-    ma.acc_keys = c->mis_tile_keys; ma.info = j.info_d;
+    ma.acc_keys = c->mis_tile_keys; ma.info = j.info_d; ma.cut_dropped = j.info_d + 3;
     ma.nx = nx; ma.ny = ny; ma.R = R; ma.stage = 1; ma.bx = sa.bx; ma.by = sa.by; ma.step = sa.step;
     ma.sparse = mode == KLT_REPLACING_SOME && pl.prefilter ? 1 : 0;
     j.pa = na;                                          // placement: the accepted candidates never exclude each other
@@ -492,6 +497,7 @@ int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArg
 {
     const int n = na.nfeat;
     if (qa) c->grid_path = 2;
+    c->pick = klt_select_pick{0, 0, pl.prefilter ? 1 : 0, 1, 0, 0, 0, 0, na.grid_in_lds ? 0 : 1, 0};      // klt_select_pick_path
     const long long ncand = (long long)sa.nx * sa.ny, npow2 = sa.npow2;
     // top-K prefilter: sort only the candidates the greedy walk can plausibly reach (one small D2H read-back)
     if (pl.prefilter) {
@@ -520,6 +526,7 @@ int serial_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa, NmsArg
         if (!(res[1] && kept < valid)) { HIPCHK(c, hipGetLastError()); return KLT_OK; }
         // the kept candidates ran out before the list was full: restore the list and take the full sort
         if (int rc = restore_list(c, na.fl, n)) return rc;
+        c->pick.attempts = 2;
     }
     { TimerScope t(c, F_SORT, (double)npow2 * 16); launch_sort_desc(c->stream, c->keys, (int)npow2); }
     if (int rc = run_nms(c, na, c->keys, (int)(ncand < npow2 ? ncand : npow2), qa, sa.ncols, sa.nrows)) return rc;
@@ -791,6 +798,15 @@ int klt_select_score_path(klt_ctx *c, int *rows, int *cols)
     if (c->score_rows_path < 0 || c->score_cols_path < 0) return fail(c, KLT_ERR_STATE, "no summed-area tables have been built yet");
     if (rows) *rows = c->score_rows_path;
     if (cols) *cols = c->score_cols_path;
+    return KLT_OK;
+}
+
+int klt_select_pick_path(klt_ctx *c, klt_select_pick *out)
+{
+    if (!c || !out) return fail(c, KLT_ERR_ARG, "null argument");
+    if (c->sel_job) return fail(c, KLT_ERR_STATE, "a selection is pending: klt_select_finish first");
+    if (c->pick.walk < 0) return fail(c, KLT_ERR_STATE, "no selection has completed yet");
+    *out = c->pick;
     return KLT_OK;
 }
 

@@ -177,6 +177,7 @@ struct SelectJob {
     size_t zero_n = 0;
     long long bound = 0, np2 = 0, ncand = 0, target = 0;
     int n = 0, mode = 0, rounds_per_look = 0, attempt = 0, round = 0, look = 0;
+    int passes = 0;                           // passes launched, both attempts (klt_select_pick_path)
     bool by_rank = false, prefilter = false, filtered = false;
     bool quota = false;                       // a grid is set (klt_set_select_grid): qa, and the frame the cells lie on
     QuotaArgs qa{};
@@ -278,6 +279,7 @@ struct klt_ctx {
     int mis_rounds_hint = 6;
     int sat_variant = 1;                      // 1: step-synchronous wavefront pipelines (sat_pipeline.hip), 0: barrier-coupled SAT kernels
     int score_rows_path = -1, score_cols_path = -1;   // klt_select_score_path: KLT_SCORE_* of the tables' row / column pass last enqueued (-1: none yet)
+    klt_select_pick pick{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // klt_select_pick_path: how the last completed selection picked (walk -1: none yet)
     unsigned *readback = nullptr;             // pinned scratch for small results
     float *score_override = nullptr;          // test hook (klt_set_score_override)
     size_t score_override_cap = 0;

@@ -253,6 +253,7 @@ struct MisArgs {
     unsigned *acc_cnt;                // [tiles] how many of them
     int acc_cap;
     const unsigned *info;             // info[0] = lowest key bin that takes part (top-K prefilter)
+    unsigned *cut_dropped;            // set to 1 by mis_init when that bin keeps a valid key out of the passes (info[3]: the histogram is a sample)
     int nx, ny, R /* exclusion radius in cells */, stage /* 1: stage tile + halo in LDS */;
     int bx, by, step;                 // pixel position of cell (i, j) = (bx + i * step, by + j * step)
     const uint8_t *seed;              // optional: [nrows][ncols] squares of the live features and the selection mask's zeros (pixels holding seed_stamp); keys were scored WITHOUT it
@@ -446,6 +447,7 @@ int  launch_nms(hipStream_t s, const NmsArgs &a);   // returns 0 or a hipError_t
 void launch_key_threshold(hipStream_t s, const unsigned long long *keys, int n, unsigned target, unsigned *hist, unsigned *info);
 int  mis_tiles(int nx, int ny);
 size_t mis_stage_bytes(int R);
+size_t mis_pass_lds(const MisArgs &a);               // dynamic LDS of a pass: the staged tiles + the tile's accepted candidates
 void launch_mis_init(hipStream_t s, const MisArgs &a);
 int  launch_mis_round(hipStream_t s, const MisArgs &a, int round);   // returns 0 or a hipError_t
 void launch_mis_compact(hipStream_t s, const MisArgs &a, unsigned long long *out, unsigned *out_count);

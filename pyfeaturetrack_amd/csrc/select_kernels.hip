@@ -378,7 +378,8 @@ __global__ __launch_bounds__(1024) void key_threshold_kernel(const unsigned *__r
 
 // Eigenvalues, keys, and -- for the parallel minimum-distance passes -- the histogram behind the prefilter threshold in the
 // same launch: every 4th workgroup histograms its keys (an estimate is enough: the threshold only saves work, any value
-// is correct); key_threshold_kernel turns it into the threshold bin.  a.hist == nullptr: keys only.
+// is correct -- as long as the repeat does not rest on the sample's counts: mis_init_kernel reports what the bin really
+// dropped); key_threshold_kernel turns it into the threshold bin.  a.hist == nullptr: keys only.
 __global__ __launch_bounds__(256) void eigen_hist_kernel(SelectArgs a)
 {
     __shared__ unsigned h[HIST_BINS];
@@ -779,14 +780,19 @@ __global__ __launch_bounds__(MIS_T) void mis_init_kernel(MisArgs a)
     }
 #pragma unroll
     for (int u = 0; u < U; u++) key[u] = inside[u] && key[u] ? a.keys[pcell[u]] : 0ull;
+    bool dropped = false;
 #pragma unroll
     for (int u = 0; u < U; u++) {
         const int p = pcell[u];
         const bool keep = key[u] != 0ull && key_bin(key[u]) >= thr;
+        dropped |= key[u] != 0ull && !keep;
         if (inside[u]) a.st[p] = keep ? klt_key_bits(key[u]) : 0u;
         const unsigned slot = wave_compact_slot(keep, &s_cursor, lane);
         if (keep) list[slot] = (uint32_t)p;
     }
+    // the cut kept a valid key of this tile out of the passes: what the repeat with every candidate rests on (the histogram behind the cut
+    // is a sample, and its counts say nothing about the keys it did not see).  A plain store of 1, like "something is left" in a pass.
+    if (__ballot(dropped) != 0ull && lane == 0) *a.cut_dropped = 1u;
     __syncthreads();
     if (threadIdx.x == 0) a.cnt[tile] = s_cursor;
 }
@@ -1566,9 +1572,14 @@ static int launch_mis_round_t(hipStream_t s, const MisArgs &a, int round, size_t
     return 0;
 }
 
+size_t mis_pass_lds(const MisArgs &a)
+{
+    return (a.stage ? mis_stage_bytes(a.R) : 0) + (((size_t)a.acc_cap * sizeof(unsigned short) + 15) & ~(size_t)15);
+}
+
 int launch_mis_round(hipStream_t s, const MisArgs &a, int round)
 {
-    const size_t lds = (a.stage ? mis_stage_bytes(a.R) : 0) + (((size_t)a.acc_cap * sizeof(unsigned short) + 15) & ~(size_t)15);
+    const size_t lds = mis_pass_lds(a);
     return a.R == 9 ? launch_mis_round_t<9>(s, a, round, lds) : launch_mis_round_t<0>(s, a, round, lds);
 }
 
