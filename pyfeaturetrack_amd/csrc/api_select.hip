@@ -67,6 +67,17 @@ int enqueue_quota_live(klt_ctx *c, const QuotaArgs &qa, bool rounds, const klt_f
     return 0;
 }
 
+// the greedy walk over na.keys: the cell grid cleared first where it lives in global memory, the live counts first where there is a quota
+int enqueue_walk(klt_ctx *c, const NmsArgs &na, const QuotaArgs *qa, int ncols, int nrows)
+{
+    if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
+    TimerScope t(c, F_NMS, (double)na.nfeat * 16);
+    if (qa)
+        if (int rc = enqueue_quota_live(c, *qa, false, na.fl, na.nfeat, na.overwrite_all != 0, ncols, nrows)) return rc;
+    if (const int e = launch_nms(c->stream, na, qa)) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
+    return 0;
+}
+
 // start of an attempt: free slots + snapshot of the list, scores / histogram / cut (attempt 0) or "every candidate" (attempt 1), tile lists
 int select_job_start(klt_ctx *c, SelectJob &j)
 {
@@ -115,23 +126,18 @@ int select_job_rounds(klt_ctx *c, SelectJob &j)
     j.look = j.round < 64 ? j.round : 64;                        // the last `look` passes
     const unsigned *rem_d = j.ma.remaining + j.round - j.look;
     launch_mis_compact(c->stream, j.ma, c->keys2, j.acc_count_d);
-    if (j.by_rank && j.quota) {
-        // the accepted candidates beyond their cell's room leave keys2 before the rest is ranked and placed
-        TimerScope t(c, F_NMS, (double)j.n * 16 + (double)j.bound * 8 * (j.qa.q + 1));
-        if (int rc = enqueue_quota_live(c, j.qa, true, j.fl, j.n, j.pa.overwrite_all != 0, j.ncols, j.nrows)) return rc;
-        launch_quota_filter(c->stream, c->keys2, j.acc_count_d, (int)j.bound, j.qa, c->quota_buf, j.qa.cells, quota_nkept(j.qa));
-        launch_mis_place_quota(c->stream, j.pa, j.acc_count_d, quota_nkept(j.qa), j.rank_d, j.nfill_d, (int)j.bound, c->readback, rem_d, j.look,
-                               j.info_d);
-    } else if (j.by_rank) {
-        TimerScope t(c, F_NMS, (double)j.n * 16);
-        launch_mis_place(c->stream, j.pa, j.acc_count_d, j.rank_d, j.nfill_d, (int)j.bound, c->readback, rem_d, j.look, j.info_d);
+    if (j.by_rank) {
+        TimerScope t(c, F_NMS, (double)j.n * 16 + (j.quota ? (double)j.bound * 8 * (j.qa.q + 1) : 0.0));
+        if (j.quota) {
+            // the accepted candidates beyond their cell's room leave keys2 before the rest is ranked and placed
+            if (int rc = enqueue_quota_live(c, j.qa, true, j.fl, j.n, j.pa.overwrite_all != 0, j.ncols, j.nrows)) return rc;
+            launch_quota_filter(c->stream, c->keys2, j.acc_count_d, (int)j.bound, j.qa, c->quota_buf, j.qa.cells, quota_nkept(j.qa));
+        }
+        launch_mis_place(c->stream, j.pa, j.acc_count_d, j.quota ? quota_nkept(j.qa) : nullptr, j.rank_d, j.nfill_d, (int)j.bound, c->readback,
+                         rem_d, j.look, j.info_d);
     } else {
         { TimerScope t(c, F_SORT, (double)j.np2 * 16); launch_sort_desc(c->stream, c->keys2, (int)j.np2); }
-        TimerScope t(c, F_NMS, (double)j.n * 16);
-        if (j.quota)
-            if (int rc = enqueue_quota_live(c, j.qa, false, j.fl, j.n, j.pa.overwrite_all != 0, j.ncols, j.nrows)) return rc;
-        const int e = j.quota ? launch_nms_quota(c->stream, j.pa, j.qa) : launch_nms(c->stream, j.pa);
-        if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
+        if (int rc = enqueue_walk(c, j.pa, j.quota ? &j.qa : nullptr, j.ncols, j.nrows)) return rc;      // (j.pa's cell grid is one word in LDS)
         launch_mis_results(c->stream, c->readback, rem_d, j.look, j.info_d, c->placed_d);
     }
     // the host's look waits for THIS point of the stream, not for the stream: a caller may enqueue work that only reads the list (the next
@@ -477,18 +483,12 @@ int begin_parallel_selection(klt_ctx *c, const SelPlan &pl, const SelectArgs &sa
     return KLT_OK;
 }
 
-// the greedy walk over sorted `keys`, the cell grid cleared first where it lives in global memory
+// the greedy walk over sorted `keys`
 int run_nms(klt_ctx *c, NmsArgs &na, const unsigned long long *keys, int nkeys, const QuotaArgs *qa, int ncols, int nrows)
 {
     na.keys = keys;
     na.nkeys = nkeys;
-    if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
-    TimerScope t(c, F_NMS, (double)na.nfeat * 16);
-    if (qa)
-        if (int rc = enqueue_quota_live(c, *qa, false, na.fl, na.nfeat, na.overwrite_all != 0, ncols, nrows)) return rc;
-    const int e = qa ? launch_nms_quota(c->stream, na, *qa) : launch_nms(c->stream, na);
-    if (e) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
-    return 0;
+    return enqueue_walk(c, na, qa, ncols, nrows);
 }
 
 // ---- sorted serial walk (KLT_OPT_SELECT_PARALLEL_NMS = 0, or an exclusion square too large for the LDS tile).  Leaves the
@@ -743,7 +743,7 @@ int klt_min_distance_walk(klt_ctx *c, const uint64_t *keys, int nkeys, int ncols
     if (int rc = make_nms_args(c, c->fbs[fb].d, n, overwrite_all != 0, d, ncols, nrows, na)) return rc;
     if (!na.grid_in_lds) HIPCHK(c, hipMemsetAsync(c->grid, 0, (size_t)na.gw * na.gh * sizeof(uint32_t), c->stream));
     na.keys = c->keys2; na.nkeys = nkeys + 1;
-    if (const int e = launch_nms(c->stream, na)) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
+    if (const int e = launch_nms(c->stream, na, nullptr)) return fail(c, KLT_ERR_DEVICE, std::string("nms launch: ") + hipGetErrorString((hipError_t)e));
     c->sorted_keys = nullptr; c->sorted_count = 0;
     if (int rc = klt_featbuf_download(c, fb, inout, n)) return rc;
     if (n_placed) HIPCHK(c, hipMemcpy(n_placed, c->placed_d, sizeof(int), hipMemcpyDeviceToHost));

@@ -233,8 +233,8 @@ struct NmsArgs {
     int nkeys, nfeat, overwrite_all, d /* mindist-1 */, cell, gw, gh, grid_in_lds;
 };
 
-// per-cell quota of the selector (klt_set_select_grid): the cell of pixel (x, y) is (y / ch) * gw + x / cw.  A second kernel argument of the
-// quota kernels only: NmsArgs and the kernels that take it alone stay as they are.
+// per-cell quota of the selector (klt_set_select_grid): the cell of pixel (x, y) is (y / ch) * gw + x / cw.  An argument of the quota
+// kernels only: the walk under a quota takes NmsArgs followed by it (select_kernels.hip), the walk without one NmsArgs alone.
 struct QuotaArgs {
     unsigned *live;          // [gw * gh] features each cell holds: the list's live records, plus (the walk) the features placed so far
     int cw, ch, gw, q;       // cell size in pixels, cells per row, max_per_cell
@@ -443,7 +443,7 @@ void launch_eigen(hipStream_t s, const SelectArgs &a);
 void launch_sort_desc(hipStream_t s, unsigned long long *keys, int npow2);
 void launch_topk_prefilter(hipStream_t s, const unsigned long long *keys, int n, unsigned target, unsigned *hist,
                            unsigned *info /* [0] bin, [1] kept (histogram), [2] valid, [3] compaction counter */, unsigned long long *out);
-int  launch_nms(hipStream_t s, const NmsArgs &a);   // returns 0 or a hipError_t
+int  launch_nms(hipStream_t s, const NmsArgs &a, const QuotaArgs *g);   // the greedy walk, under a quota when g is given; returns 0 or a hipError_t
 void launch_key_threshold(hipStream_t s, const unsigned long long *keys, int n, unsigned target, unsigned *hist, unsigned *info);
 int  mis_tiles(int nx, int ny);
 size_t mis_stage_bytes(int R);
@@ -459,7 +459,8 @@ void launch_eigen_hist(hipStream_t s, const SelectArgs &a);
 // histogram (every 4th block of 256 keys, as eigen_hist_kernel samples) of the keys outside the seed map, then the threshold
 void launch_mask_hist(hipStream_t s, const SelectArgs &a);
 void launch_mis_results(hipStream_t s, unsigned *host_out, const unsigned *rem, int look, const unsigned *info, const int *placed);
-void launch_mis_place(hipStream_t s, const NmsArgs &a, const unsigned *count, unsigned *rank, const int *nfill, int bound,
+// nkept: null, or the keys went through launch_quota_filter (zero keys are skipped, *nkept of them are not zero)
+void launch_mis_place(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill, int bound,
                       unsigned *host_out, const unsigned *rem, int look, const unsigned *info);
 void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int n, float *val, int *x, int *y);
 // ---- per-cell quota (klt_set_select_grid)
@@ -470,10 +471,6 @@ void launch_quota_live(hipStream_t s, const klt_feat *fl, int nfeat, int ncols, 
 // words, zeroed by the caller, like *nkept; g.q <= KLT_QUOTA_MAX_ROUNDS
 void launch_quota_filter(hipStream_t s, unsigned long long *keys, const unsigned *count, int bound, const QuotaArgs &g,
                          unsigned long long *thr, int ncells, unsigned *nkept);
-// launch_mis_place over filtered keys (zero keys are skipped, *nkept of them are not zero)
-void launch_mis_place_quota(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill,
-                            int bound, unsigned *host_out, const unsigned *rem, int look, const unsigned *info);
-int  launch_nms_quota(hipStream_t s, const NmsArgs &a, const QuotaArgs &g);   // the greedy walk under a quota; returns 0 or a hipError_t
 
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
 int launch_track(hipStream_t s, const TrackArgs &a);

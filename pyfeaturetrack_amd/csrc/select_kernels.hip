@@ -608,8 +608,159 @@ __device__ __forceinline__ void mark_not_found(klt_feat *fl, int slot)
     fl[slot] = ft;
 }
 
+// The walk under a per-cell quota (klt_set_select_grid, QUOTA): a candidate accepted by distance marks the cell grid and blocks the later
+// lanes near it whatever its cell holds; it takes a slot, and room, only while its cell has room left.  The room of a batch of 64
+// survivors: what the cell had when the batch began (g.live, which the batch's placed features are added to behind it) minus the lanes
+// of the same cell placed before this one.  The kernel argument is one struct per QUOTA value: the plain walk receives NmsArgs alone.
+struct NmsQuotaArgs : NmsArgs { QuotaArgs g; };
+template <bool QUOTA>
+using NmsKernArgs = std::conditional_t<QUOTA, NmsQuotaArgs, NmsArgs>;
+
+__device__ __forceinline__ int quota_cell(const QuotaArgs &g, int x, int y)
+{
+    const int cx = g.cw == 1 ? x : (int)klt_div_by_magic((unsigned)x, g.cw_magic);
+    const int cy = g.ch == 1 ? y : (int)klt_div_by_magic((unsigned)y, g.ch_magic);
+    return cy * g.gw + cx;
+}
+
+// room left in a cell; the count is read from L2 (the walk adds to it between two reads)
+__device__ __forceinline__ int quota_left(const QuotaArgs &g, int cell)
+{
+    const unsigned held = __hip_atomic_load(&g.live[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return held < (unsigned)g.q ? (int)((unsigned)g.q - held) : 0;
+}
+
+// The slots that may be filled when the list is not overwritten, in list order (selectGoodFeatures.py:109-110): the slots whose feature
+// is lost.  a.slots[k] = index of the k-th fillable slot; returns how many there are.  Every thread of the workgroup calls.
+__device__ __forceinline__ int list_free_slots(const NmsArgs &a, int *scan, int *s_nfill, int tid)
+{
+    const int per = (a.nfeat + NMS_T - 1) / NMS_T, lo = tid * per, hi = min(lo + per, a.nfeat);
+    int cnt = 0;
+    for (int i = lo; i < hi; i++) cnt += a.fl[i].val < 0;
+    scan[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < NMS_T; off <<= 1) {          // Hillis-Steele inclusive scan
+        const int v = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    int k = scan[tid] - cnt;
+    for (int i = lo; i < hi; i++)
+        if (a.fl[i].val < 0) a.slots[k++] = i;
+    if (tid == NMS_T - 1) *s_nfill = scan[tid];
+    __syncthreads();
+    return *s_nfill;
+}
+
+// Steps 1 and 2 on one super-batch: the candidates that pass the first test go to surv[] in rank order; returns how many.
+// ended: some thread held a zero key -- everything after it is padding.  Every thread of the workgroup calls.
+template <bool LDSGRID, bool QUOTA>
+__device__ __forceinline__ int first_test_compact(const NmsKernArgs<QUOTA> &a, const uint32_t *grid, unsigned long long cur,
+                                                  unsigned long long *surv, int *wave_cnt, int lane, int wave, int &ended)
+{
+    const bool valid = cur != 0ull;
+    const int x = klt_key_x(cur), y = klt_key_y(cur);
+    bool ok = valid;
+    if constexpr (QUOTA) {
+        if (valid) ok = a.d >= 0 ? grid_free<LDSGRID>(grid, a, x, y) : quota_left(a.g, quota_cell(a.g, x, y)) > 0;
+    } else {
+        if (valid && a.d >= 0) ok = grid_free<LDSGRID>(grid, a, x, y);
+    }
+    const unsigned long long m = __ballot(ok);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    ended = __syncthreads_or(!valid);
+    int offset = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < NMS_T / 64; w++) {
+        const int c = wave_cnt[w];
+        offset += w < wave ? c : 0;
+        total += c;
+    }
+    if (ok) surv[offset + __popcll(m & ((1ull << lane) - 1ull))] = cur;
+    __syncthreads();
+    return total;
+}
+
+// an accepted candidate in the cell grid: it blocks what comes after it within the exclusion square
 template <bool LDSGRID>
-__global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
+__device__ __forceinline__ void grid_mark(uint32_t *grid, const NmsArgs &a, int x, int y)
+{
+    const uint32_t code = (((uint32_t)x << 16) | (uint32_t)y) + 1u;
+    uint32_t *cellp = &grid[cell_of(y, a) * a.gw + cell_of(x, a)];
+    if (LDSGRID) *cellp = code;
+    else __hip_atomic_store(cellp, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Step 3 on one batch of 64 survivors, one per lane of wave 0 (k = 0: none): `placed` slots are taken and at most nfill may be;
+// returns how many this batch takes.  retest: earlier batches of the super-batch are in the grid and were not there for the first test.
+template <bool LDSGRID, bool QUOTA>
+__device__ __forceinline__ int resolve_batch(const NmsKernArgs<QUOTA> &a, uint32_t *grid, unsigned long long k, bool retest, int placed,
+                                             int nfill, int lane)
+{
+    const int sx = klt_key_x(k), sy = klt_key_y(k);
+    bool is_free = k != 0ull;
+    if (retest && is_free && a.d >= 0) is_free = grid_free<LDSGRID>(grid, a, sx, sy);
+    int qc = -1, left = 0;                           // QUOTA: the lane's cell and the room it had when the batch began
+    if constexpr (QUOTA) {
+        if (is_free) { qc = quota_cell(a.g, sx, sy); left = quota_left(a.g, qc); }
+    }
+    unsigned long long mask = __ballot(is_free), accepted = 0ull, taken = 0ull;       // accepted by distance; of those, the ones that take a slot
+    int room = nfill - placed;
+    if constexpr (!QUOTA) {
+        if (a.d < 0) {                   // nothing excludes anything: the first `room` free lanes are accepted
+            const bool take = ((mask >> lane) & 1ull) && __popcll(mask & ((1ull << lane) - 1ull)) < room;
+            accepted = __ballot(take);
+            mask = 0ull;
+        }
+    }
+    // rank order = lane order: the first free lane is accepted and blocks the later lanes near it
+    while (mask != 0ull && room > 0) {
+        const int l = __ffsll((long long)mask) - 1;
+        accepted |= 1ull << l;
+        if constexpr (!QUOTA) room--;
+        mask &= ~(1ull << l);
+        if constexpr (QUOTA) {
+            const int cell_l = __builtin_amdgcn_readlane(qc, l), left_l = __builtin_amdgcn_readlane(left, l);
+            const unsigned long long same = __ballot(qc == cell_l);
+            if (__popcll(taken & same) < left_l) { taken |= 1ull << l; room--; }
+        }
+        if (a.d >= 0) {
+            const int ax = __builtin_amdgcn_readlane(sx, l), ay = __builtin_amdgcn_readlane(sy, l);
+            mask &= ~__ballot(abs(sx - ax) <= a.d && abs(sy - ay) <= a.d);
+        }
+    }
+    if constexpr (!QUOTA) {
+        taken = accepted;
+        if ((accepted >> lane) & 1ull) {
+            const int rank = placed + __popcll(accepted & ((1ull << lane) - 1ull));
+            fill_slot(a, a.overwrite_all ? rank : a.slots[rank], k);
+            if (a.d >= 0) grid_mark<LDSGRID>(grid, a, sx, sy);
+        }
+    } else {
+        if (((accepted >> lane) & 1ull) && a.d >= 0) grid_mark<LDSGRID>(grid, a, sx, sy);
+        if ((taken >> lane) & 1ull) {
+            const int rank = placed + __popcll(taken & ((1ull << lane) - 1ull));
+            fill_slot(a, a.overwrite_all ? rank : a.slots[rank], k);
+            __hip_atomic_fetch_add(&a.g.live[qc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    return __popcll(taken);
+}
+
+// the end of the walk (wave 0): the slots the candidates did not reach, and the outcome
+__device__ __forceinline__ void walk_tail(const NmsArgs &a, int placed, bool list_full, int lane)
+{
+    if (!list_full && a.overwrite_all)                         // candidates exhausted
+        for (int i = placed + lane; i < a.nfeat; i += 64) mark_not_found(a.fl, i);
+    if (lane == 0 && a.placed_out) {
+        a.placed_out[0] = placed;
+        a.placed_out[1] = list_full ? 0 : 1;      // 1: the walk ran out of candidates before the list was full
+    }
+}
+
+template <bool LDSGRID, bool QUOTA>
+__global__ __launch_bounds__(NMS_T) void nms_kernel(NmsKernArgs<QUOTA> a)
 {
     extern __shared__ uint32_t lds_grid[];
     __shared__ unsigned long long surv[NMS_T];
@@ -621,29 +772,7 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
     if (LDSGRID)
         for (int i = tid; i < a.gw * a.gh; i += NMS_T) grid[i] = 0u;
     if (tid == 0) s_stop = 0;
-
-    // slots that may be filled, in list order (selectGoodFeatures.py:109-110): every slot when overwriting,
-    // otherwise the slots whose feature is lost.  a.slots[k] = index of the k-th fillable slot.
-    int nfill = a.nfeat;
-    if (!a.overwrite_all) {
-        const int per = (a.nfeat + NMS_T - 1) / NMS_T, lo = tid * per, hi = min(lo + per, a.nfeat);
-        int cnt = 0;
-        for (int i = lo; i < hi; i++) cnt += a.fl[i].val < 0;
-        scan[tid] = cnt;
-        __syncthreads();
-        for (int off = 1; off < NMS_T; off <<= 1) {          // Hillis-Steele inclusive scan
-            const int v = tid >= off ? scan[tid - off] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        int k = scan[tid] - cnt;
-        for (int i = lo; i < hi; i++)
-            if (a.fl[i].val < 0) a.slots[k++] = i;
-        if (tid == NMS_T - 1) s_nfill = scan[tid];
-        __syncthreads();
-        nfill = s_nfill;
-    }
+    const int nfill = a.overwrite_all ? a.nfeat : list_free_slots(a, scan, &s_nfill, tid);      // overwriting: every slot, in order
     __syncthreads();
 
     int placed = 0;                               // meaningful in wave 0 only
@@ -653,74 +782,23 @@ __global__ __launch_bounds__(NMS_T) void nms_kernel(NmsArgs a)
         const unsigned long long cur = key;
         const int nxt = pos + NMS_T + tid;
         key = nxt < a.nkeys ? a.keys[nxt] : 0ull;                 // prefetch the next super-batch
-        const bool valid = cur != 0ull;
-        const int x = klt_key_x(cur), y = klt_key_y(cur);
-        bool ok = valid;
-        if (valid && a.d >= 0) ok = grid_free<LDSGRID>(grid, a, x, y);
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) wave_cnt[wave] = __popcll(m);
-        const int ended = __syncthreads_or(!valid);               // a zero key: everything after it is padding
-        int offset = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < NMS_T / 64; w++) {
-            const int c = wave_cnt[w];
-            offset += w < wave ? c : 0;
-            total += c;
-        }
-        if (ok) surv[offset + __popcll(m & ((1ull << lane) - 1ull))] = cur;
-        __syncthreads();
+        int ended;
+        const int total = first_test_compact<LDSGRID, QUOTA>(a, grid, cur, surv, wave_cnt, lane, wave, ended);
         if (wave == 0) {
             for (int base = 0; base < total && !list_full; base += 64) {
                 const unsigned long long k = base + lane < total ? surv[base + lane] : 0ull;
-                const int sx = klt_key_x(k), sy = klt_key_y(k);
-                bool is_free = k != 0ull;
-                if (base > 0 && is_free && a.d >= 0) is_free = grid_free<LDSGRID>(grid, a, sx, sy);
-                unsigned long long mask = __ballot(is_free), accepted = 0ull;
-                int room = nfill - placed;
-                if (a.d < 0) {                   // nothing excludes anything: the first `room` free lanes are accepted
-                    const bool take = ((mask >> lane) & 1ull) && __popcll(mask & ((1ull << lane) - 1ull)) < room;
-                    accepted = __ballot(take);
-                    mask = 0ull;
-                }
-                // rank order = lane order: the first free lane is accepted and blocks the later lanes near it
-                while (mask != 0ull && room > 0) {
-                    const int l = __ffsll((long long)mask) - 1;
-                    accepted |= 1ull << l;
-                    room--;
-                    mask &= ~(1ull << l);
-                    if (a.d >= 0) {
-                        const int ax = __builtin_amdgcn_readlane(sx, l), ay = __builtin_amdgcn_readlane(sy, l);
-                        mask &= ~__ballot(abs(sx - ax) <= a.d && abs(sy - ay) <= a.d);
-                    }
-                }
-                if ((accepted >> lane) & 1ull) {
-                    const int rank = placed + __popcll(accepted & ((1ull << lane) - 1ull));
-                    const int slot = a.overwrite_all ? rank : a.slots[rank];
-                    fill_slot(a, slot, k);
-                    if (a.d >= 0) {
-                        const uint32_t code = (((uint32_t)sx << 16) | (uint32_t)sy) + 1u;
-                        uint32_t *cellp = &grid[cell_of(sy, a) * a.gw + cell_of(sx, a)];
-                        if (LDSGRID) *cellp = code;
-                        else __hip_atomic_store(cellp, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                placed += __popcll(accepted);
+                placed += resolve_batch<LDSGRID, QUOTA>(a, grid, k, base > 0, placed, nfill, lane);
                 if (placed >= nfill) list_full = true;                            // :112
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                // the next batch, and the next first test, read the grid -- and under a quota g.live, which lives in global memory
+                if constexpr (QUOTA) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             }
             if (lane == 0 && (list_full || ended)) s_stop = 1;
         }
         __syncthreads();
         if (s_stop) break;
     }
-    if (wave == 0) {
-        if (!list_full && a.overwrite_all)                         // candidates exhausted
-            for (int i = placed + lane; i < a.nfeat; i += 64) mark_not_found(a.fl, i);
-        if (lane == 0 && a.placed_out) {
-            a.placed_out[0] = placed;
-            a.placed_out[1] = list_full ? 0 : 1;      // 1: the walk ran out of candidates before the list was full
-        }
-    }
+    if (wave == 0) walk_tail(a, placed, list_full, lane);
 }
 
 // ------------------------------------------------------------------ minimum distance without the serial walk
@@ -1246,19 +1324,26 @@ __global__ __launch_bounds__(RANK_T) void mis_rank_kernel(const unsigned long lo
     }
 }
 
-__global__ __launch_bounds__(256) void mis_place_kernel(NmsArgs a, const unsigned *__restrict__ count, const unsigned *__restrict__ rank,
-                                                        const int *__restrict__ nfill_in, unsigned *host_out, const unsigned *rem, int look,
-                                                        const unsigned *info)
+// Rank placement: accepted key i goes to the free slot of its rank.  FILTERED: the keys went through the quota filter (quota_round_kernel)
+// -- the zero keys are skipped (mis_rank_kernel counted none of them as greater than anything) and *nkept keys are left.  The count
+// argument is one struct per FILTERED value, so that the plain kernel receives nothing it does not read.
+struct PlaceCount { const unsigned *count; };
+struct PlaceCountFiltered : PlaceCount { const unsigned *nkept; };
+template <bool FILTERED>
+__global__ __launch_bounds__(256) void mis_place_kernel(NmsArgs a, std::conditional_t<FILTERED, PlaceCountFiltered, PlaceCount> c,
+                                                        const unsigned *__restrict__ rank, const int *__restrict__ nfill_in, unsigned *host_out,
+                                                        const unsigned *rem, int look, const unsigned *info)
 {
-    const int n = (int)*count, nfill = *nfill_in;
-    const int placed = min(n, nfill);
+    const int n = (int)*c.count, nfill = *nfill_in;
+    int left = n;
+    if constexpr (FILTERED) left = (int)*c.nkept;
+    const int placed = min(left, nfill);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
         const int r = (int)rank[i];
         if (r < nfill) {
             const unsigned long long k = a.keys[i];
-            const int slot = a.overwrite_all ? r : a.slots[r];
-            fill_slot(a, slot, k);
+            if (!FILTERED || k != 0ull) fill_slot(a, a.overwrite_all ? r : a.slots[r], k);
         }
     }
     if (a.overwrite_all)                                           // candidates exhausted
@@ -1283,20 +1368,8 @@ __global__ void unpack_candidates_kernel(const unsigned long long *__restrict__ 
 
 // ------------------------------------------------------------------ per-cell quota (klt_set_select_grid)
 // The members of the accepted sequence A (what the walk accepts by distance, in rank order) that are kept are the first cap(cell) of
-// each cell, cap(cell) = max(q - live(cell), 0); everything else about A -- who excludes whom -- is as without a grid.
-__device__ __forceinline__ int quota_cell(const QuotaArgs &g, int x, int y)
-{
-    const int cx = g.cw == 1 ? x : (int)klt_div_by_magic((unsigned)x, g.cw_magic);
-    const int cy = g.ch == 1 ? y : (int)klt_div_by_magic((unsigned)y, g.ch_magic);
-    return cy * g.gw + cx;
-}
-
-// room left in a cell; the count is read from L2 (the walk adds to it between two reads)
-__device__ __forceinline__ int quota_left(const QuotaArgs &g, int cell)
-{
-    const unsigned held = __hip_atomic_load(&g.live[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return held < (unsigned)g.q ? (int)((unsigned)g.q - held) : 0;
-}
+// each cell, cap(cell) = max(q - live(cell), 0); everything else about A -- who excludes whom -- is as without a grid.  (quota_cell and
+// quota_left stand in front of the walk, which uses them under a quota.)
 
 // live(cell): list records with val >= 0 whose position lies inside the frame (f32 comparisons: a NaN fails), counted in the cell of
 // ((int)x, (int)y).  A sum: the order the additions arrive in does not matter.
@@ -1343,147 +1416,6 @@ __global__ __launch_bounds__(256) void quota_round_kernel(unsigned long long *__
             if (i < n) keys[i] = kept ? k & ~QUOTA_KEPT : 0ull;
             const unsigned long long m = __ballot(kept);
             if ((threadIdx.x & 63) == 0 && m) atomicAdd(nkept, (unsigned)__popcll(m));
-        }
-    }
-}
-
-// mis_place_kernel over filtered keys: the zero keys are skipped (mis_rank_kernel counted none of them as greater than anything), and
-// *nkept keys are left
-__global__ __launch_bounds__(256) void mis_place_quota_kernel(NmsArgs a, const unsigned *__restrict__ count, const unsigned *__restrict__ nkept,
-                                                              const unsigned *__restrict__ rank, const int *__restrict__ nfill_in,
-                                                              unsigned *host_out, const unsigned *rem, int look, const unsigned *info)
-{
-    const int n = (int)*count, nfill = *nfill_in;
-    const int placed = min((int)*nkept, nfill);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        const unsigned long long k = a.keys[i];
-        const int r = (int)rank[i];
-        if (k != 0ull && r < nfill) fill_slot(a, a.overwrite_all ? r : a.slots[r], k);
-    }
-    if (a.overwrite_all)                                           // the kept candidates ran out
-        for (int s = placed + i; s < a.nfeat; s += gridDim.x * 256) mark_not_found(a.fl, s);
-    if (i == 0 && a.placed_out) {
-        a.placed_out[0] = placed;
-        a.placed_out[1] = placed < nfill ? 1 : 0;
-    }
-    if (blockIdx.x == 0) write_results(host_out, rem, look, info, placed, placed < nfill ? 1 : 0);
-}
-
-// nms_kernel under a quota.  A candidate accepted by distance marks the cell grid and blocks the later lanes near it whatever its cell
-// holds; it takes a slot, and room, only while its cell has room left.  The room of a batch of 64 survivors: what the cell had when the
-// batch began (g.live, which the batch's placed features are added to behind it) minus the lanes of the same cell placed before this one.
-// Without a minimum distance (d < 0) a candidate of a full cell has no effect at all and is dropped with the first test; the one-shot
-// "first `room` free lanes" of nms_kernel becomes the same lane-by-lane loop, which stops when the list is full.
-template <bool LDSGRID>
-__global__ __launch_bounds__(NMS_T) void nms_quota_kernel(NmsArgs a, QuotaArgs g)
-{
-    extern __shared__ uint32_t lds_grid[];
-    __shared__ unsigned long long surv[NMS_T];
-    __shared__ int wave_cnt[NMS_T / 64];
-    __shared__ int scan[NMS_T];
-    __shared__ int s_stop, s_nfill;
-    uint32_t *grid = LDSGRID ? lds_grid : a.grid_global;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (LDSGRID)
-        for (int i = tid; i < a.gw * a.gh; i += NMS_T) grid[i] = 0u;
-    if (tid == 0) s_stop = 0;
-
-    // the fillable slots in list order, as in nms_kernel
-    int nfill = a.nfeat;
-    if (!a.overwrite_all) {
-        const int per = (a.nfeat + NMS_T - 1) / NMS_T, lo = min(tid * per, a.nfeat), hi = min(lo + per, a.nfeat);
-        int cnt = 0;
-        for (int i = lo; i < hi; i++) cnt += a.fl[i].val < 0;
-        scan[tid] = cnt;
-        __syncthreads();
-        for (int off = 1; off < NMS_T; off <<= 1) {
-            const int v = tid >= off ? scan[tid - off] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        int k = scan[tid] - cnt;
-        for (int i = lo; i < hi; i++)
-            if (a.fl[i].val < 0) a.slots[k++] = i;
-        if (tid == NMS_T - 1) s_nfill = scan[tid];
-        __syncthreads();
-        nfill = s_nfill;
-    }
-    __syncthreads();
-
-    int placed = 0;                               // meaningful in wave 0 only
-    bool list_full = nfill == 0;
-    unsigned long long key = tid < a.nkeys ? a.keys[tid] : 0ull;
-    for (int pos = 0; pos < a.nkeys && nfill > 0; pos += NMS_T) {
-        const unsigned long long cur = key;
-        const int nxt = pos + NMS_T + tid;
-        key = nxt < a.nkeys ? a.keys[nxt] : 0ull;
-        const bool valid = cur != 0ull;
-        const int x = klt_key_x(cur), y = klt_key_y(cur);
-        bool ok = valid;
-        if (valid) ok = a.d >= 0 ? grid_free<LDSGRID>(grid, a, x, y) : quota_left(g, quota_cell(g, x, y)) > 0;
-        const unsigned long long m = __ballot(ok);
-        if (lane == 0) wave_cnt[wave] = __popcll(m);
-        const int ended = __syncthreads_or(!valid);
-        int offset = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < NMS_T / 64; w++) {
-            const int c = wave_cnt[w];
-            offset += w < wave ? c : 0;
-            total += c;
-        }
-        if (ok) surv[offset + __popcll(m & ((1ull << lane) - 1ull))] = cur;
-        __syncthreads();
-        if (wave == 0) {
-            for (int base = 0; base < total && !list_full; base += 64) {
-                const unsigned long long k = base + lane < total ? surv[base + lane] : 0ull;
-                const int sx = klt_key_x(k), sy = klt_key_y(k);
-                bool is_free = k != 0ull;
-                if (base > 0 && is_free && a.d >= 0) is_free = grid_free<LDSGRID>(grid, a, sx, sy);
-                const int qc = is_free ? quota_cell(g, sx, sy) : -1;
-                const int left = is_free ? quota_left(g, qc) : 0;
-                unsigned long long mask = __ballot(is_free), accepted = 0ull, taken = 0ull;
-                int room = nfill - placed;
-                // rank order = lane order: the first free lane is accepted and blocks the later lanes near it
-                while (mask != 0ull && room > 0) {
-                    const int l = __ffsll((long long)mask) - 1;
-                    accepted |= 1ull << l;
-                    mask &= ~(1ull << l);
-                    const int cell_l = __builtin_amdgcn_readlane(qc, l), left_l = __builtin_amdgcn_readlane(left, l);
-                    const unsigned long long same = __ballot(qc == cell_l);
-                    if (__popcll(taken & same) < left_l) { taken |= 1ull << l; room--; }
-                    if (a.d >= 0) {
-                        const int ax = __builtin_amdgcn_readlane(sx, l), ay = __builtin_amdgcn_readlane(sy, l);
-                        mask &= ~__ballot(abs(sx - ax) <= a.d && abs(sy - ay) <= a.d);
-                    }
-                }
-                if (((accepted >> lane) & 1ull) && a.d >= 0) {
-                    const uint32_t code = (((uint32_t)sx << 16) | (uint32_t)sy) + 1u;
-                    uint32_t *cellp = &grid[cell_of(sy, a) * a.gw + cell_of(sx, a)];
-                    if (LDSGRID) *cellp = code;
-                    else __hip_atomic_store(cellp, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if ((taken >> lane) & 1ull) {
-                    const int rank = placed + __popcll(taken & ((1ull << lane) - 1ull));
-                    fill_slot(a, a.overwrite_all ? rank : a.slots[rank], k);
-                    __hip_atomic_fetch_add(&g.live[qc], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                placed += __popcll(taken);
-                if (placed >= nfill) list_full = true;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // the next batch (and the next first test) reads g.live and the grid
-            }
-            if (lane == 0 && (list_full || ended)) s_stop = 1;
-        }
-        __syncthreads();
-        if (s_stop) break;
-    }
-    if (wave == 0) {
-        if (!list_full && a.overwrite_all)                         // candidates exhausted
-            for (int i = placed + lane; i < a.nfeat; i += 64) mark_not_found(a.fl, i);
-        if (lane == 0 && a.placed_out) {
-            a.placed_out[0] = placed;
-            a.placed_out[1] = list_full ? 0 : 1;
         }
     }
 }
@@ -1629,14 +1561,17 @@ void launch_mis_results(hipStream_t s, unsigned *host_out, const unsigned *rem, 
     hipLaunchKernelGGL(mis_results_kernel, dim3(1), dim3(64), 0, s, host_out, rem, look, info, placed);
 }
 
-// keys[0 .. *count) unsorted accepted candidates, *count <= bound; rank[] zeroed by the caller
-void launch_mis_place(hipStream_t s, const NmsArgs &a, const unsigned *count, unsigned *rank, const int *nfill, int bound,
+// keys[0 .. *count) unsorted accepted candidates, *count <= bound; rank[] zeroed by the caller.  nkept: null, or the keys went through
+// launch_quota_filter, which left *nkept of them
+void launch_mis_place(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill, int bound,
                       unsigned *host_out, const unsigned *rem, int look, const unsigned *info)
 {
     const int chunks = (bound + RANK_T - 1) / RANK_T;
     hipLaunchKernelGGL(mis_rank_kernel, dim3(chunks < RANK_GX ? chunks : RANK_GX, chunks < RANK_GY ? chunks : RANK_GY), dim3(RANK_T), 0, s,
                        a.keys, count, rank);
-    hipLaunchKernelGGL(mis_place_kernel, dim3((bound + 255) / 256), dim3(256), 0, s, a, count, rank, nfill, host_out, rem, look, info);
+    const dim3 grid((bound + 255) / 256);
+    if (nkept) hipLaunchKernelGGL(mis_place_kernel<true>, grid, dim3(256), 0, s, a, PlaceCountFiltered{{count}, nkept}, rank, nfill, host_out, rem, look, info);
+    else hipLaunchKernelGGL(mis_place_kernel<false>, grid, dim3(256), 0, s, a, PlaceCount{count}, rank, nfill, host_out, rem, look, info);
 }
 
 void launch_sort_desc(hipStream_t s, unsigned long long *keys, int n)
@@ -1650,17 +1585,23 @@ void launch_sort_desc(hipStream_t s, unsigned long long *keys, int n)
     }
 }
 
-int launch_nms(hipStream_t s, const NmsArgs &a)
+template <bool QUOTA>
+static int launch_walk(hipStream_t s, const NmsKernArgs<QUOTA> &a)
 {
     if (a.grid_in_lds) {
         const size_t lds = (size_t)a.gw * a.gh * sizeof(uint32_t);
-        hipError_t e = hipFuncSetAttribute((const void *)nms_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void *)nms_kernel<true, QUOTA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(nms_kernel<true>, dim3(1), dim3(NMS_T), lds, s, a);
+        hipLaunchKernelGGL((nms_kernel<true, QUOTA>), dim3(1), dim3(NMS_T), lds, s, a);
     } else {
-        hipLaunchKernelGGL(nms_kernel<false>, dim3(1), dim3(NMS_T), 0, s, a);
+        hipLaunchKernelGGL((nms_kernel<false, QUOTA>), dim3(1), dim3(NMS_T), 0, s, a);
     }
     return 0;
+}
+
+int launch_nms(hipStream_t s, const NmsArgs &a, const QuotaArgs *g)
+{
+    return g ? launch_walk<true>(s, NmsQuotaArgs{a, *g}) : launch_walk<false>(s, a);
 }
 
 void launch_unpack_candidates(hipStream_t s, const unsigned long long *keys, int n, float *val, int *x, int *y)
@@ -1681,26 +1622,4 @@ void launch_quota_filter(hipStream_t s, unsigned long long *keys, const unsigned
     const size_t most = (size_t)(bound > ncells ? bound : ncells);
     const dim3 grid(clamp_grid((most + 255) / 256, 384));
     for (int r = 0; r <= g.q; r++) hipLaunchKernelGGL(quota_round_kernel, grid, dim3(256), 0, s, keys, count, g, thr, ncells, r, nkept);
-}
-
-void launch_mis_place_quota(hipStream_t s, const NmsArgs &a, const unsigned *count, const unsigned *nkept, unsigned *rank, const int *nfill,
-                            int bound, unsigned *host_out, const unsigned *rem, int look, const unsigned *info)
-{
-    const int chunks = (bound + RANK_T - 1) / RANK_T;
-    hipLaunchKernelGGL(mis_rank_kernel, dim3(chunks < RANK_GX ? chunks : RANK_GX, chunks < RANK_GY ? chunks : RANK_GY), dim3(RANK_T), 0, s,
-                       a.keys, count, rank);
-    hipLaunchKernelGGL(mis_place_quota_kernel, dim3((bound + 255) / 256), dim3(256), 0, s, a, count, nkept, rank, nfill, host_out, rem, look, info);
-}
-
-int launch_nms_quota(hipStream_t s, const NmsArgs &a, const QuotaArgs &g)
-{
-    if (a.grid_in_lds) {
-        const size_t lds = (size_t)a.gw * a.gh * sizeof(uint32_t);
-        hipError_t e = hipFuncSetAttribute((const void *)nms_quota_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(nms_quota_kernel<true>, dim3(1), dim3(NMS_T), lds, s, a, g);
-    } else {
-        hipLaunchKernelGGL(nms_quota_kernel<false>, dim3(1), dim3(NMS_T), 0, s, a, g);
-    }
-    return 0;
 }

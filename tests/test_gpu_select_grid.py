@@ -238,6 +238,29 @@ def test_768x512_walk_behind_the_prefilter():
         assert g.c.select_grid_path() == PATH_WALK
 
 
+def test_512x260_quota_walk_with_the_cell_grid_in_global_memory():
+    """mindist 2: a cell grid of 256 x 130 words = 133 120 bytes, just past the 131 072 the walk keeps in LDS -- the walk under a quota with
+    its cell grid in global memory, and before a grid is set the plain walk on the same frame"""
+    ncols, nrows, grid, mindist = 512, 260, (64, 52, 40), 2
+    assert grid_dims(ncols, nrows, grid) == (8, 5) and (ncols // mindist) * (nrows // mindist) * 4 == 133120 > 131072
+    assert len(members(ncols, nrows, mindist=mindist)) == 19491
+    does_not_fill = expected(ncols, nrows, 2000, grid, mindist=mindist)[1]
+    assert found(does_not_fill) == 1600 and live_counts(does_not_fill, ncols, nrows, grid).max() == 40, "every cell at its cap of 40"
+    fills = expected(ncols, nrows, 1000, grid, mindist=mindist)[1]
+    assert found(fills) == 1000
+    start, replaced = expected(ncols, nrows, 2000, grid, REPLACING_SOME, mindist=mindist)
+    assert (start["val"] < 0).sum() == 667 and (replaced["val"] < 0).sum() == 130
+    with Ctx(ncols, nrows, WALK, mindist=mindist) as g:
+        check(g.select(2000), plain(ncols, nrows, 2000, mindist=mindist)[0], "no grid: the plain walk")
+        pick = g.c.select_pick_path()
+        assert pick["walk"] == 0 and pick["grid"] == 1 and g.candidates() < PREFILTER_FROM
+        g.c.set_select_grid(grid)
+        for n, mode, first, want in ((2000, SELECTING_ALL, None, does_not_fill), (1000, SELECTING_ALL, None, fills),
+                                     (2000, REPLACING_SOME, start, replaced)):
+            check(g.select(n, mode, first), want, (n, mode))
+            assert g.c.select_grid_path() == PATH_WALK and g.c.select_pick_path()["grid"] == 1
+
+
 # ---- composition and state -----------------------------------------------------------------------------------------------------------
 def test_mask_and_grid_compose():
     ncols, nrows, n, grid = 320, 240, 100, (64, 48, 3)
