@@ -88,6 +88,8 @@ int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<S
 
 }  // namespace kltapi
 
+int g_track_variant = getenv("KLT_TRACK_VARIANT") ? atoi(getenv("KLT_TRACK_VARIANT")) : 4;      // KLT_OPT_TRACK_VARIANT: read by launch_pairs and nowhere else
+
 extern "C" {
 
 static void fill_track_params(const klt_ctx *c, const Slot *s1, TrackArgs &a, int n)
@@ -118,9 +120,8 @@ static void fill_fb_params(const klt_ctx *c, TrackArgs &a)
 // order of pair A's rows.  A single-pair launch on a list seen for the FIRST time takes the context's shared order instead (refreshed every
 // 64 launches): the rows of a sequence's feature table are all new buffers holding nearly the same
 // positions, and an order kernel per frame would buy nothing; the second launch on the same buffer gives it its own entry.
-static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<const klt_feat *> &ins)
+static int set_track_order(klt_ctx *c, TrackArgs &a, int n, int chunk, const std::vector<const klt_feat *> &ins)
 {
-    if (!c->track_xcd_order || n < 64) return 0;
     const int npairs = (int)ins.size();
     klt_ctx::BatchOrder *bo = cache_find(c->batch_orders, [&](const klt_ctx::BatchOrder &e) { return e.in == ins; });
     if (npairs == 1) {
@@ -142,7 +143,7 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
     if (int rc = ensure(c, bo->order, bo->cap, (size_t)n * npairs)) return rc;
     if (bo->cap != cap_before) bo->n = -1;               // a new buffer holds no order yet
     a.order = bo->order;
-    a.order_chunk = (n + 7) / 8;
+    a.order_chunk = chunk;
     a.order_refresh = (bo->n != n || bo->age >= 64) ? 1 : 0;
     if (a.order_refresh) { bo->n = n; bo->age = 0; }
     bo->age++;
@@ -150,7 +151,7 @@ static int set_track_order(klt_ctx *c, TrackArgs &a, int n, const std::vector<co
 }
 
 // lazy: level 0 is the two slots' compact images (TrackLazyArgs; the kernels do not look at that level's gradient pointers)
-static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv, bool lazy = false)
+static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv, bool lazy)
 {
     for (int l = 0; l < s1->nlev; l++) {
         level_planes(s1, s2, l, lv[l].i1, lv[l].gx1, lv[l].gy1, lv[l].i2, lv[l].gx2, lv[l].gy2);
@@ -160,24 +161,6 @@ static void fill_levels(const Slot *s1, const Slot *s2, TrackLevel *lv, bool laz
         lv[0].i1 = s1->l0img; lv[0].i2 = s2->l0img;
         lv[0].gx1 = lv[0].gy1 = lv[0].gx2 = lv[0].gy2 = nullptr;
     }
-}
-
-// KLT_OPT_L0_LAZY_GRAD, a plain tracker launch of `npairs` pairs on `slots`: *capable = the launch has a lazy form (track_lazy_capable, 7-tap
-// gradient filters), *lazy = it has and every slot holds a compact level-0 image.  Otherwise the slots without level-0 records get them
-// here (one launch per KLT_MAX_BATCH slots); the fallback of a launch that has a lazy form is not held against the slots.
-static int settle_level0(klt_ctx *c, const TrackArgsBase &a, int npairs, Slot *const *slots, int nslots, bool *capable, bool *lazy)
-{
-    *capable = track_lazy_capable(a.window, a.tree_sums, a.n, npairs) && merged_grad_ok(c);
-    bool all = *capable;
-    for (int i = 0; i < nslots; i++) all = all && slots[i]->l0img_valid;
-    *lazy = all;
-    return all ? 0 : ensure_level0_records(c, slots, nslots, !*capable);
-}
-
-// ... and once the launch is out: a launch that has a lazy form leaves its mark on the slots it read (their next build may be lean)
-static void mark_lazy_read(Slot *const *slots, int nslots, bool capable)
-{
-    for (int i = 0; i < nslots && capable; i++) slots[i]->lazy_read = true;
 }
 
 // what a forward-backward launch asks of a pair's three feature buffers (fb_back: a buffer or -1)
@@ -205,27 +188,80 @@ static int guess_records(klt_ctx *c, int fb_guess, int fb_out, int fb_back, int 
     return own_records(c, fb_guess, {fb_out, fb_back}, kGuessNotDistinct);
 }
 
-// the tracker launch of `npairs` pairs of `nlev` levels under its timer (guess: the kernels that start from a predicted position)
-// lazy: the plain 7x7 quad kernels that read level 0 as compact images (settle_level0)
-static int enqueue_track(klt_ctx *c, const TrackGuessArgs &a, int npairs, int nlev, bool guess = false, bool lazy = false)
+// A batched launch's descriptor table on the device.  It is uploaded only when none of the tables kept there holds it (found by hash; at
+// most 256 tables, the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order
+// protects the launch that read the replaced table
+static int upload_pair_table(klt_ctx *c, const std::vector<TrackPairDesc> &table, const TrackPairDesc **dev)
 {
-    const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
-    // (a lazy level 0 reads the 14 x 14 image patch around a footprint, 4 bytes per pixel, instead of the footprint's records)
-    const double foot0 = lazy ? 4.0 * 14 * 14 : foot;
-    TimerScope t(c, F_TRACK, (double)npairs * a.n * (foot * 2 * (nlev - 1) + foot0 * 2 + 32), c->stream);   // refined by the caller from klt_track_stats
-    if (lazy) {
-        TrackLazyArgs la;
-        static_cast<TrackArgsBase &>(la) = a;
-        for (int i = 0; i < 4; i++) { la.kg[i] = c->gauss[2].k[i]; la.kd[i] = c->deriv[2].k[i]; }
-        if (launch_track_lazy(c->stream, la, c->track_lazy_form)) return fail(c, KLT_ERR_STATE, "tracker launch: no lazy form for this launch");
-        return 0;
+    const size_t bytes = table.size() * sizeof(TrackPairDesc);
+    uint64_t hash = 1469598103934665603ull;
+    const unsigned char *raw = reinterpret_cast<const unsigned char *>(table.data());
+    for (size_t i = 0; i < bytes; i++) hash = (hash ^ raw[i]) * 1099511628211ull;
+    klt_ctx::BatchTable *bt = cache_find(c->batch_tables, [&](const klt_ctx::BatchTable &e) {
+        return e.hash == hash && e.host.size() == table.size() && std::memcmp(e.host.data(), table.data(), bytes) == 0;
+    });
+    if (!bt) {
+        bt = cache_place(c->batch_tables, klt_ctx::kBatchTables);
+        if (int rc = ensure(c, bt->dev, bt->cap, table.size())) return rc;
+        HIPCHK(c, hipMemcpyAsync(bt->dev, table.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        bt->host = table;
+        bt->hash = hash;
     }
-    if (c->lightp.mode) {                                   // gain / bias tracking (klt_set_light_params): kernels of their own, features in list order
-        if (launch_track_light(c->stream, a, &c->light_path)) return fail(c, KLT_ERR_ARG, "unsupported window size");
-        return 0;
-    }
-    if (guess ? launch_track_guess(c->stream, a) : launch_track(c->stream, a)) return fail(c, KLT_ERR_ARG, "unsupported window size");
+    bt->used = ++c->batch_clock;
+    *dev = bt->dev;
     return 0;
+}
+
+// The back half of every tracker entry point, from the launch's parameters to the marks on its slots: one request, one plan (plan_track,
+// track_plan.h), and every step reads off the plan.  slots: those of the pairs, two each, built and of one size (check_pair).  table: a
+// batched launch's descriptors with their lists filled in, or null for a single pair, whose lists are in `a`.
+static int launch_pairs(klt_ctx *c, TrackGuessArgs &a, Slot *const *slots, int npairs, int n, bool fb, bool guess, std::vector<TrackPairDesc> *table)
+{
+    const int nslots = 2 * npairs, nlev = slots[0]->nlev;
+    fill_track_params(c, slots[0], a, n);
+    TrackRequest q = {};
+    q.window = a.window; q.n = n; q.batched = table != nullptr; q.npairs = npairs;
+    q.fb = fb; q.guess = guess; q.light = c->lightp.mode != 0; q.tree_sums = c->track_tree_sums; q.variant = g_track_variant;
+    q.order = c->track_xcd_order && n >= 64 && !q.light; q.order_chunk = (n + 7) / 8;
+    q.grad7 = merged_grad_ok(c); q.lazy_form = c->track_lazy_form;
+    q.all_compact = true;
+    for (int i = 0; i < nslots; i++) q.all_compact = q.all_compact && slots[i]->l0img_valid;
+    const TrackPlan plan = plan_track(q);
+    if (plan.refusal) return fail(c, KLT_ERR_ARG, plan.refusal);
+    // KLT_OPT_L0_LAZY_GRAD: the slots without level-0 records get them here (one launch per KLT_MAX_BATCH slots); the fallback of a
+    // launch that has a lazy form is not held against the slots
+    if (plan.need_records)
+        if (int rc = ensure_level0_records(c, slots, nslots, !plan.lazy_capable)) return rc;
+    if (table) {
+        for (int i = 0; i < npairs; i++) fill_levels(slots[2 * i], slots[2 * i + 1], (*table)[i].lv, plan.lazy);
+        if (int rc = upload_pair_table(c, *table, &a.pairs)) return rc;
+        a.npairs = npairs;
+    } else {
+        fill_levels(slots[0], slots[1], a.lv, plan.lazy);
+    }
+    if (fb) fill_fb_params(c, a);
+    if (plan.uses_order) {
+        // one permutation per pair, kept with the set of input lists (see set_track_order)
+        std::vector<const klt_feat *> ins((size_t)npairs);
+        for (int i = 0; i < npairs; i++) ins[i] = table ? (*table)[i].in : a.in;
+        if (int rc = set_track_order(c, a, n, q.order_chunk, ins)) return rc;
+    }
+    {
+        const double foot = 12.0 * (c->p.window_width + 1) * (c->p.window_width + 1);
+        // (a lazy level 0 reads the 14 x 14 image patch around a footprint, 4 bytes per pixel, instead of the footprint's records)
+        const double foot0 = plan.lazy ? 4.0 * 14 * 14 : foot;
+        TimerScope t(c, F_TRACK, (double)npairs * n * (foot * 2 * (nlev - 1) + foot0 * 2 + 32), c->stream);   // refined by the caller from klt_track_stats
+        launch_track(c->stream, plan, a, c->gauss[2].k, c->deriv[2].k);
+    }
+    if (plan.light_path) c->light_path = plan.light_path;
+    // a launch that has a lazy form leaves its mark on the slots it read (their next build may be lean)
+    for (int i = 0; i < nslots && plan.lazy_capable; i++) slots[i]->lazy_read = true;
+    if (c->collect_stats)
+        for (int i = 0; i < npairs; i++)
+            launch_track_stats(c->stream, table ? (*table)[i].in : a.in, table ? (*table)[i].out : a.out, n, nlev, c->stats_d);
+    if (int rc = mark_read(c, slots, nslots)) return rc;
+    HIPCHK(c, hipGetLastError());
+    return KLT_OK;
 }
 
 // klt_track_async (fb == false) and klt_track_fb_async (fb == true; fb_back = the buffer of the backward records or -1); guess == true:
@@ -242,9 +278,9 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
     if (guess)
         if (int rc = check_guess_buffer(c, fb_guess, fb_out, fb ? fb_back : -1)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    Slot *s1, *s2;
-    const bool plain = !fb && !guess && !c->lightp.mode;     // the launches with a lazy form look after level 0 themselves (settle_level0)
-    if (int rc = check_pair(c, slot1, slot2, &s1, &s2, plain)) return rc;
+    Slot *both[2];
+    // (a launch that may have a lazy form looks after level 0 itself, launch_pairs; any other gets its records here, slot by slot)
+    if (int rc = check_pair(c, slot1, slot2, &both[0], &both[1], track_lazy_rule(fb, guess, c->lightp.mode != 0))) return rc;
     if (int rc = lists_set(c, {fb_in}, n, false)) return rc;
     FeatBuf *bo;
     if (fb && fb_back >= 0)                                  // (may grow c->fbs: before any pointer into it is taken)
@@ -255,24 +291,8 @@ static int track_single(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out,
     if (guess)
         if (int rc = guess_records(c, fb_guess, fb_out, fb ? fb_back : -1, n, &a.guess)) return rc;
     a.in = c->fbs[fb_in].d; a.out = bo->d;
-    fill_track_params(c, s1, a, n);
-    bool lazy = false, capable = false;
-    Slot *const both[2] = {s1, s2};
-    if (plain)
-        if (int rc = settle_level0(c, a, 1, both, 2, &capable, &lazy)) return rc;
-    fill_levels(s1, s2, a.lv, lazy);
-    if (fb) {
-        fill_fb_params(c, a);
-        a.back = fb_back >= 0 ? c->fbs[fb_back].d : nullptr;
-    }
-    if (!c->lightp.mode)
-        if (int rc = set_track_order(c, a, n, std::vector<const klt_feat *>{a.in})) return rc;
-    if (int rc = enqueue_track(c, a, 1, s1->nlev, guess, lazy)) return rc;
-    mark_lazy_read(both, 2, capable);
-    if (c->collect_stats) launch_track_stats(c->stream, a.in, a.out, n, s1->nlev, c->stats_d);
-    if (int rc = mark_read_pair(c, s1, s2)) return rc;
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
+    if (fb && fb_back >= 0) a.back = c->fbs[fb_back].d;
+    return launch_pairs(c, a, both, 1, n, fb, guess, nullptr);
 }
 
 int klt_track_async(klt_ctx *c, int slot1, int slot2, int fb_in, int fb_out, int n)
@@ -362,7 +382,6 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
         if (fb && fb_back && fb_back[i] >= 0)
             if (int rc = get_fb(c, fb_back[i], n > 0 ? n : 1, &bo)) return rc;
     }
-    const bool plain = !fb && !fb_guess && !c->lightp.mode;  // the launches with a lazy form look after level 0 themselves (settle_level0)
     for (int i = 0; i < npairs; i++) {
         if (int rc = batch_pair(c, slot1[i], slot2[i], true, used, true)) return rc;
         if (int rc = lists_set(c, {fb_in[i]}, n, false)) return rc;
@@ -376,46 +395,7 @@ static int track_batch(klt_ctx *c, const int *slot1, const int *slot2, const int
     }
     TrackGuessArgs a;
     std::memset(&a, 0, sizeof(a));
-    fill_track_params(c, used[0], a, n);
-    bool lazy = false, capable = false;
-    if (plain) { if (int rc = settle_level0(c, a, npairs, used.data(), (int)used.size(), &capable, &lazy)) return rc; }
-    else if (int rc = ensure_level0_records(c, used.data(), (int)used.size())) return rc;      // (no lazy form: the records, one launch for all)
-    for (int i = 0; i < npairs; i++) fill_levels(used[2 * i], used[2 * i + 1], table[i].lv, lazy);
-    // the descriptor table is uploaded only when none of the tables kept on the device holds it (found by hash; at most 256 tables,
-    // the least recently used one is replaced).  Pageable source: the runtime stages it before returning; stream order protects the
-    // launch that read the replaced table
-    uint64_t hash = 1469598103934665603ull;
-    {
-        const unsigned char *bytes = reinterpret_cast<const unsigned char *>(table.data());
-        for (size_t i = 0; i < table.size() * sizeof(TrackPairDesc); i++) hash = (hash ^ bytes[i]) * 1099511628211ull;
-    }
-    klt_ctx::BatchTable *bt = cache_find(c->batch_tables, [&](const klt_ctx::BatchTable &e) {
-        return e.hash == hash && e.host.size() == table.size() && std::memcmp(e.host.data(), table.data(), table.size() * sizeof(TrackPairDesc)) == 0;
-    });
-    if (!bt) {
-        bt = cache_place(c->batch_tables, klt_ctx::kBatchTables);
-        if (int rc = ensure(c, bt->dev, bt->cap, (size_t)npairs)) return rc;
-        HIPCHK(c, hipMemcpyAsync(bt->dev, table.data(), (size_t)npairs * sizeof(TrackPairDesc), hipMemcpyHostToDevice, c->stream));
-        bt->host = table;
-        bt->hash = hash;
-    }
-    bt->used = ++c->batch_clock;
-    a.pairs = bt->dev;
-    a.npairs = npairs;
-    if (fb) fill_fb_params(c, a);
-    if (!c->lightp.mode) {
-        // one permutation per pair, kept with the set of input lists (see set_track_order)
-        std::vector<const klt_feat *> ins((size_t)npairs);
-        for (int i = 0; i < npairs; i++) ins[i] = table[i].in;
-        if (int rc = set_track_order(c, a, n, ins)) return rc;
-    }
-    if (int rc = enqueue_track(c, a, npairs, used[0]->nlev, fb_guess != nullptr, lazy)) return rc;
-    mark_lazy_read(used.data(), (int)used.size(), capable);
-    if (c->collect_stats)
-        for (int i = 0; i < npairs; i++) launch_track_stats(c->stream, table[i].in, table[i].out, n, used[0]->nlev, c->stats_d);
-    if (int rc = mark_read(c, used.data(), (int)used.size())) return rc;
-    HIPCHK(c, hipGetLastError());
-    return KLT_OK;
+    return launch_pairs(c, a, used.data(), npairs, n, fb, fb_guess != nullptr, &table);
 }
 
 int klt_track_batch_async(klt_ctx *c, const int *slot1, const int *slot2, const int *fb_in, const int *fb_out, int npairs, int n)

@@ -7,6 +7,7 @@
 
 #include "klt_gpu.h"
 #include "l0_plan.h"                  // Taps, KLT_MAX_BATCH, the level-0 launch plan
+#include "track_plan.h"               // the tracker launch plan, track_npad
 
 struct SmoothGradArgs {
     const void *raw[KLT_MAX_BATCH];   // u8 or f32 frame (or, for gradients only, the compact level image)
@@ -360,7 +361,7 @@ __host__ __device__ __forceinline__ float corr_regs(const double *c /* centre */
     return (float)acc;
 }
 
-extern int g_track_variant;         // tracker kernels: 4 (default) quad-load kernels where they apply, 0 always track_kernel
+extern int g_track_variant;         // KLT_OPT_TRACK_VARIANT (read by the tracker's request builder alone, api_track.hip): 4 (default) quad-load kernels where they apply, 0 always track_kernel
 size_t pyr_reduce_lds_bytes(int ss, int ntaps);
 // the kernel, form and grid that plan_level0 (l0_plan.h) chose for these arguments: a lean plan writes the smoothed image to the compact
 // planes a.cimg and nothing to a.rec, a plan with hred writes the H1 planes a.h1 as well
@@ -473,15 +474,11 @@ void launch_quota_filter(hipStream_t s, unsigned long long *keys, const unsigned
                          unsigned long long *thr, int ncells, unsigned *nkept);
 
 void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, int n, int nlevels, unsigned long long *stats);
-int launch_track(hipStream_t s, const TrackArgs &a);
-int launch_track_guess(hipStream_t s, const TrackGuessArgs &a);
-// Would launch_track take the plain 7x7 quad kernel for this launch (the one kernel with a lazy form)? ...
-bool track_lazy_capable(int window, int tree_sums, int n, int npairs);
-// ... and that form: level 0 of every pair is a compact image plane (TrackLazyArgs)
-// form: KLT_OPT_TRACK_LAZY_FORM (1: the template's and the first footprint's level-0 gradients in one fused phase)
-int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a, int form);
-// the gain / bias tracker (track_light_kernels.hip; klt_set_light_params mode 1): *path = 1 wave kernel, 2 quad kernel; a.order is not looked at
-int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path);
+// the kernel, form, grid and LDS that plan_track (track_plan.h) chose for these arguments, behind track_order_kernel where the plan takes a
+// feature order and a.order_refresh asks for a new one.  A lazy plan reads level 0 of every pair as a compact image plane (TrackLazyArgs)
+// under the gradient taps kg / kd; a gain / bias plan goes to the kernels of track_light_kernels.hip, through the second function
+void launch_track(hipStream_t s, const TrackPlan &plan, const TrackGuessArgs &a, const double *kg, const double *kd);
+void launch_track_light_kernel(hipStream_t s, const TrackPlan &plan, const TrackArgsBase &a);
 // per-feature track quality (quality_kernels.hip): one klt_quality record per feature; returns -1 for an unsupported window
 int launch_track_quality(hipStream_t s, const QualityArgs &a);
 // the motion-model check (model_kernels.hip), three launches in stream order: candidates, one score per hypothesis, the decision

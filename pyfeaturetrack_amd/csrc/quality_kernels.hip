@@ -162,7 +162,8 @@ static int launch_quality_t(hipStream_t s, const QualityArgs &a)
     if (a.window < 3 || !(a.window & 1) || n > 1024) return -1;
     const unsigned lds = (unsigned)(track_npad(n) * sizeof(float));
     const dim3 grid(a.n, BATCH ? a.npairs : 1), block(64);
-    for_window_class(a.window, [&](auto maxk, auto wct) {
+    const TrackWindowClass wc = track_window_class(a.window);
+    for_window_class(wc.maxk, wc.wct, [&](auto maxk, auto wct) {
         klt_launch((quality_eigen_kernel<maxk.value, wct.value, BATCH>), grid, block, lds, s, a);
     });
     return 0;

@@ -964,39 +964,22 @@ void launch_track_stats(hipStream_t s, const klt_feat *in, const klt_feat *out, 
     hipLaunchKernelGGL(track_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, s, in, out, n, nlevels, stats);
 }
 
-// Tracker kernels: track_kernel_quad (7x7 windows with lists of 2048 features and more: four features per wavefront; 15x15
-// windows: one feature per wavefront; one 16-byte load per lane, image and footprint), track_kernel (one feature per wavefront,
-// one sample per lane and round: every other window, short 7x7 lists).  All give bit-identical records.
-// KLT_OPT_TRACK_VARIANT = 0 (or KLT_TRACK_VARIANT=0 in the environment) forces track_kernel: the plain fallback the parity
-// tests compare the quad kernel with.  The measured-slower generations in between (prefetching, per-sample loads with four
-// features per wavefront, one pixel per lane) are recorded in profiles/README.md and live in the git history.
-int g_track_variant = getenv("KLT_TRACK_VARIANT") ? atoi(getenv("KLT_TRACK_VARIANT")) : 4;
+// Tracker kernels: track_kernel_quad (7x7 windows with long lists: four features per wavefront; 15x15 windows: one feature per
+// wavefront; one 16-byte load per lane, image and footprint), track_kernel (one feature per wavefront, one sample per lane and round:
+// every other window, short 7x7 lists).  All give bit-identical records.  Which of them a launch takes, with which grid and LDS:
+// plan_track (track_plan.h).  The measured-slower generations in between (prefetching, per-sample loads with four features per
+// wavefront, one pixel per lane) are recorded in profiles/README.md and live in the git history.
+static_assert(LZ_FLOATS == TRACK_LAZY_FLOATS && LZE_FLOATS == TRACK_LAZY_ENTRY_FLOATS, "the plan's LDS sizes are these kernels'");
 
-// FB: the forward-backward kernels (klt_track_fb_async), chosen by the same rules; they have no tree-sum form
-// GUESS: the kernels with a motion prior (klt_track_guess*), chosen by the same rules again
-// Does a launch take the 7x7 quad kernel?  (short 7x7 lists keep one feature per wavefront: with a few hundred features the launch is pure
-// latency, which four features in lock step lengthen)
-static bool track_quad7_rule(int window, int n, int npairs)
-{
-    return g_track_variant != 0 && window == 7 && (long long)n * npairs >= 2048;
-}
-
-template <bool BATCH, bool FB, bool GUESS, class Args>
-static int launch_track_t(hipStream_t s, const Args &a)
+// The instantiation a plan names, of the plain (FB, GUESS false), forward-backward and motion-prior kernels
+template <bool BATCH, bool FB, bool GUESS>
+static void launch_track_t(hipStream_t s, const TrackPlan &p, const TrackGuessArgs &a)
 {
     const TrackKernArgs<FB, GUESS> &ka = a;              // what the kernels take: the plain ones not the forward-backward fields, only those with a prior the guess list
-    const int n = a.window * a.window;
-    if (n > 1024) return -1;
-    const size_t lds = track_lds_bytes(n);
-    const unsigned ny = BATCH ? a.npairs : 1;
-    const dim3 block(64);
-    // the permutation is (re)computed here whenever the caller asks for it, whichever kernel consumes it
-    if (a.order && a.order_refresh)
-        hipLaunchKernelGGL(track_order_kernel, dim3(ny), dim3(ORDER_T), 0, s, a.in, BATCH ? a.pairs : nullptr, a.n, a.order);
-    // (short 7x7 lists keep one feature per wavefront: with a few hundred features the launch is pure latency, which four
-    // features in lock step lengthen)
-    if (track_quad7_rule(a.window, a.n, (int)ny)) {
-        const dim3 gq(a.order ? 8 * ((a.order_chunk + 3) / 4) : (a.n + 3) / 4, ny);
+    const dim3 grid(p.gx, p.gy), block(64);
+    const unsigned lds = (unsigned)p.lds;
+    constexpr int GW = GUESS ? GUESS_WAVES : 0;
+    if (p.family == TRACK_FAMILY_QUAD7) {
         // (occupancy targets 5 / 6 for this kernel -- 96 / 80 VGPRs with 84 / 172 bytes of scratch per lane instead of 122 VGPRs -- were
         // measured again in round 3 on eight-pair launches, 10 000 wavefronts, where a fifth resident wavefront per SIMD could hide
         // latency: 112 / 199 us per launch against 87.5, cfg-4's 32-pair shard 0.535 / 0.687 ms against 0.495.  A scratch reload is a
@@ -1004,28 +987,30 @@ static int launch_track_t(hipStream_t s, const Args &a)
         // the extra wavefront was meant to hide.)
         // (the forward-backward instantiation is left without a cap as well -- an occupancy target of two is none for a kernel of 138
         // VGPRs, which three wavefronts per SIMD fit; its registers and scratch are in DESIGN.md section 9a)
-        constexpr int GW = GUESS ? GUESS_WAVES : 0;
-        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 7, 2 + GW, false, true, GUESS>), gq, block, (unsigned)(4 * lds), s, ka);
-        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, true, false, GUESS>), gq, block, 0u, s, ka);
-        else klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, false, false, GUESS>), gq, block, (unsigned)(4 * lds), s, ka);
-        return 0;
-    }
-    if (g_track_variant != 0 && a.window == 15) {
-        const dim3 gq(a.order ? 8 * a.order_chunk : a.n, ny);
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 7, 2 + GW, false, true, GUESS>), grid, block, lds, s, ka);
+        else if (p.tree) klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, true, false, GUESS>), grid, block, lds, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 7, 1 + GW, false, false, GUESS>), grid, block, lds, s, ka);
+    } else if (p.family == TRACK_FAMILY_QUAD15) {
         // occupancy target 5 (96 VGPRs, 40 bytes of scratch per lane instead of 107 VGPRs): the 5000 wavefronts of cfg-3 are then
         // resident at once instead of in two rounds -- 57.9 -> 49.3 us.  (The 7x7 kernel loses from the same cap, see above.)
         // (forward-backward: occupancy target 4 -- 123 VGPRs, 36 bytes of scratch; at 5 the two passes' state costs 152 bytes of scratch per lane)
-        constexpr int GW = GUESS ? GUESS_WAVES : 0;
-        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 15, 4 + GW, false, true, GUESS>), gq, block, (unsigned)lds, s, ka);
-        else if (a.tree_sums) klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, true, false, GUESS>), gq, block, 0u, s, ka);
-        else klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, false, false, GUESS>), gq, block, (unsigned)lds, s, ka);
-        return 0;
+        if constexpr (FB) klt_launch((track_kernel_quad<BATCH, 15, 4 + GW, false, true, GUESS>), grid, block, lds, s, ka);
+        else if (p.tree) klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, true, false, GUESS>), grid, block, lds, s, ka);
+        else klt_launch((track_kernel_quad<BATCH, 15, 5 + GW, false, false, GUESS>), grid, block, lds, s, ka);
+    } else {
+        for_window_class(p.maxk, p.wct, [&](auto maxk, auto wct) {
+            klt_launch((track_kernel<maxk.value, wct.value, BATCH, FB, GUESS>), grid, block, lds, s, ka);
+        });
     }
-    const dim3 grid(a.order ? 8 * a.order_chunk : a.n, ny);
-    for_window_class(a.window, [&](auto maxk, auto wct) {
-        klt_launch((track_kernel<maxk.value, wct.value, BATCH, FB, GUESS>), grid, block, (unsigned)lds, s, ka);
-    });
-    return 0;
+}
+
+// ... and of the plain 7x7 quad kernels that read level 0 as compact images
+template <bool BATCH>
+static void launch_track_lazy_t(hipStream_t s, const TrackPlan &p, const TrackLazyArgs &a)
+{
+    const dim3 grid(p.gx, p.gy), block(64);
+    if (p.entry) klt_launch((track_kernel_quad<BATCH, 7, 1 + LAZY_WAVES + ENTRY_WAVES>), grid, block, (unsigned)p.lds, s, a);
+    else klt_launch((track_kernel_quad<BATCH, 7, 1 + LAZY_WAVES>), grid, block, (unsigned)p.lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1118,49 +1103,23 @@ void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, c
                        small, th, max_iterations, res);
 }
 
-int launch_track(hipStream_t s, const TrackArgs &a)
+// The tracker launch that plan_track (track_plan.h) chose for these arguments; it decides nothing.  kg, kd: the taps of the two gradient
+// filters as TrackLazyArgs carries them (read by a lazy plan alone).  The feature order is (re)computed here whenever the arguments ask
+// for it, whichever kernel consumes it.
+void launch_track(hipStream_t s, const TrackPlan &p, const TrackGuessArgs &a, const double *kg, const double *kd)
 {
-    if (a.n <= 0) return 0;
-    if (a.fb) {
-        if (a.pairs) return a.npairs > 0 ? launch_track_t<true, true, false>(s, a) : 0;
-        return launch_track_t<false, true, false>(s, a);
+    if (!p.launch || p.refusal) return;
+    if (p.uses_order && a.order_refresh)
+        hipLaunchKernelGGL(track_order_kernel, dim3(p.gy), dim3(ORDER_T), 0, s, a.in, p.batched ? a.pairs : nullptr, a.n, a.order);
+    if (p.rule == TRACK_RULE_LIGHT) return launch_track_light_kernel(s, p, a);
+    if (p.lazy) {
+        TrackLazyArgs la;
+        static_cast<TrackArgsBase &>(la) = a;
+        for (int i = 0; i < 4; i++) { la.kg[i] = kg[i]; la.kd[i] = kd[i]; }
+        return p.batched ? launch_track_lazy_t<true>(s, p, la) : launch_track_lazy_t<false>(s, p, la);
     }
-    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false, false>(s, a) : 0;
-    return launch_track_t<false, false, false>(s, a);
-}
-
-// (the rule of launch_track_t for the plain 7x7 quad kernel with the reference-order sums)
-bool track_lazy_capable(int window, int tree_sums, int n, int npairs)
-{
-    return track_quad7_rule(window, n, npairs) && !tree_sums && n > 0 && npairs > 0;
-}
-
-int launch_track_lazy(hipStream_t s, const TrackLazyArgs &a, int form)
-{
-    const unsigned ny = a.pairs ? a.npairs : 1;
-    if (!track_lazy_capable(a.window, a.tree_sums, a.n, (int)ny)) return -1;
-    if (a.order && a.order_refresh)
-        hipLaunchKernelGGL(track_order_kernel, dim3(ny), dim3(ORDER_T), 0, s, a.in, a.pairs ? a.pairs : nullptr, a.n, a.order);
-    const dim3 gq(a.order ? 8 * ((a.order_chunk + 3) / 4) : (a.n + 3) / 4, ny), block(64);
-    // LDS: the four features' product arrays or, at level 0, their patches (the larger of the two)
-    constexpr unsigned lds = (unsigned)(4 * sizeof(float) * (LZ_FLOATS > 5 * track_npad(49) ? LZ_FLOATS : 5 * track_npad(49)));
-    if (form) {
-        // ... or the two patches of the fused entry phase (which the patches of the Newton loop's recomputations fit under)
-        constexpr unsigned lds_entry = (unsigned)(sizeof(float) * LZE_FLOATS);
-        static_assert(lds_entry >= lds && lds_entry <= 10240, "sixteen wavefronts per CU");
-        if (a.pairs) klt_launch((track_kernel_quad<true, 7, 1 + LAZY_WAVES + ENTRY_WAVES>), gq, block, lds_entry, s, a);
-        else klt_launch((track_kernel_quad<false, 7, 1 + LAZY_WAVES + ENTRY_WAVES>), gq, block, lds_entry, s, a);
-        return 0;
-    }
-    if (a.pairs) klt_launch((track_kernel_quad<true, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
-    else klt_launch((track_kernel_quad<false, 7, 1 + LAZY_WAVES>), gq, block, lds, s, a);
-    return 0;
-}
-
-int launch_track_guess(hipStream_t s, const TrackGuessArgs &a)
-{
-    if (a.n <= 0) return 0;
-    if (a.fb) return a.pairs ? -1 : launch_track_t<false, true, true>(s, a);        // (no batched entry point takes a prior and the check together)
-    if (a.pairs) return a.npairs > 0 ? launch_track_t<true, false, true>(s, a) : 0;
-    return launch_track_t<false, false, true>(s, a);
+    if (p.fb && p.guess) return launch_track_t<false, true, true>(s, p, a);      // (single-pair: no batched entry point takes a prior and the check together)
+    if (p.fb) return p.batched ? launch_track_t<true, true, false>(s, p, a) : launch_track_t<false, true, false>(s, p, a);
+    if (p.guess) return p.batched ? launch_track_t<true, false, true>(s, p, a) : launch_track_t<false, false, true>(s, p, a);
+    return p.batched ? launch_track_t<true, false, false>(s, p, a) : launch_track_t<false, false, false>(s, p, a);
 }

@@ -498,34 +498,20 @@ __global__ __launch_bounds__(64) void track_light_quad(TrackArgsBase a)
 }
 
 template <bool BATCH>
-static int launch_track_light_t(hipStream_t s, const TrackArgsBase &a, int *path)
+static void launch_track_light_t(hipStream_t s, const TrackPlan &p, const TrackArgsBase &a)
 {
-    const int n = a.window * a.window;
-    if (n > 1024) return -1;
-    const size_t lds = track_lds_bytes(n);
-    const unsigned ny = BATCH ? a.npairs : 1;
-    const dim3 block(64);
-    // the plain tracker's rule (launch_track_t of track_kernels.hip): 7x7 lists of 2048 features and more per launch take four features
-    // per wavefront; KLT_OPT_TRACK_VARIANT = 0 forces the wave kernel.  15x15 windows use the wave kernel.
-    if (g_track_variant != 0 && a.window == 7 && (long long)a.n * ny >= 2048) {
-        klt_launch((track_light_quad<BATCH>), dim3((a.n + 3) / 4, ny), block, (unsigned)(4 * lds), s, a);
-        *path = 2;
-        return 0;
-    }
-    const dim3 grid(a.n, ny);
-    for_window_class(a.window, [&](auto maxk, auto wct) {
-        klt_launch((track_light_kernel<maxk.value, wct.value, BATCH>), grid, block, (unsigned)lds, s, a);
+    const dim3 grid(p.gx, p.gy), block(64);
+    if (p.family == TRACK_FAMILY_QUAD7) return klt_launch((track_light_quad<BATCH>), grid, block, (unsigned)p.lds, s, a);
+    for_window_class(p.maxk, p.wct, [&](auto maxk, auto wct) {
+        klt_launch((track_light_kernel<maxk.value, wct.value, BATCH>), grid, block, (unsigned)p.lds, s, a);
     });
-    *path = 1;
-    return 0;
 }
 
 }  // namespace track_kernel_light
 
-// The tracker launch under klt_set_light_params mode 1; *path = 1 wave kernel, 2 quad kernel.  Returns -1 for an unsupported window.
-int launch_track_light(hipStream_t s, const TrackArgsBase &a, int *path)
+// The instantiation that a plan under klt_set_light_params mode 1 names (launch_track of track_kernels.hip calls this; the kernels stay in
+// this file for their symbols' sake)
+void launch_track_light_kernel(hipStream_t s, const TrackPlan &p, const TrackArgsBase &a)
 {
-    if (a.n <= 0) return 0;
-    if (a.pairs) return a.npairs > 0 ? track_kernel_light::launch_track_light_t<true>(s, a, path) : 0;
-    return track_kernel_light::launch_track_light_t<false>(s, a, path);
+    return p.batched ? track_kernel_light::launch_track_light_t<true>(s, p, a) : track_kernel_light::launch_track_light_t<false>(s, p, a);
 }

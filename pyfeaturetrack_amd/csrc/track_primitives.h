@@ -63,9 +63,7 @@ __device__ __forceinline__ bool solve_step(float gxx, float gxy, float gyy, floa
     return det < small;
 }
 
-// 16-byte aligned sub-arrays: the five product arrays of a window of n samples in LDS
-__host__ __device__ constexpr int track_npad(int n) { return (n + 3) & ~3; }
-__host__ __device__ constexpr size_t track_lds_bytes(int n) { return 5 * (size_t)track_npad(n) * sizeof(float); }
+// (track_npad, the 16-byte aligned length of one of a window's five product arrays in LDS: track_plan.h)
 
 // One product array added in the reference's row-major order (sequential f32 adds, trackFeaturesUtils.pyx:263-267, :296-302), read
 // from LDS 16 bytes at a time: N terms, N known at compile time (a window size known at run time only: a plain loop over the terms).
@@ -268,19 +266,18 @@ __host__ __device__ __forceinline__ void lazy_col_v(const float *c, const TapReg
     for (int j = 0; j < NOUT; j++) out[j] = corr_regs<7, SYM>(w + 3 + j, k);
 }
 
-// The window classes of the one-feature-per-wavefront kernels (host): f(MAXK, WCT) as integral constants -- MAXK window samples per lane;
-// WCT the window size where it is known at compile time (7 and 15), 0 for any other window of n = window * window <= 1024 samples.
+// A window class of the one-feature-per-wavefront kernels (host; track_window_class of track_plan.h has the table) as integral
+// constants: f(MAXK, WCT)
 template <class F>
-inline void for_window_class(int window, F &&f)
+inline void for_window_class(int maxk, int wct, F &&f)
 {
     using std::integral_constant;
-    const int n = window * window;
-    if (window == 7) f(integral_constant<int, 1>{}, integral_constant<int, 7>{});
-    else if (window == 15) f(integral_constant<int, 4>{}, integral_constant<int, 15>{});
-    else if (n <= 64) f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
-    else if (n <= 128) f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
-    else if (n <= 256) f(integral_constant<int, 4>{}, integral_constant<int, 0>{});
-    else if (n <= 512) f(integral_constant<int, 8>{}, integral_constant<int, 0>{});
+    if (wct == 7) f(integral_constant<int, 1>{}, integral_constant<int, 7>{});
+    else if (wct == 15) f(integral_constant<int, 4>{}, integral_constant<int, 15>{});
+    else if (maxk == 1) f(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+    else if (maxk == 2) f(integral_constant<int, 2>{}, integral_constant<int, 0>{});
+    else if (maxk == 4) f(integral_constant<int, 4>{}, integral_constant<int, 0>{});
+    else if (maxk == 8) f(integral_constant<int, 8>{}, integral_constant<int, 0>{});
     else f(integral_constant<int, 16>{}, integral_constant<int, 0>{});
 }
 

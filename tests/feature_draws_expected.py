@@ -40,7 +40,7 @@ FEATURE_API_SEEDS = [0, 1, 2, 3]                # (even: a selection grid, odd: 
 
 
 def window_class(window):
-    """(MAXK, WCT) of for_window_class (track_primitives.h): the kernel instantiation a window takes"""
+    """(MAXK, WCT) of track_window_class (track_plan.h): the kernel instantiation a window takes"""
     n = window * window
     if window in (7, 15):
         return (1, 7) if window == 7 else (4, 15)

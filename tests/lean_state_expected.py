@@ -1,6 +1,6 @@
 """KLT_OPT_L0_LAZY_GRAD: the host's rule for a context's pyramid slots restated in plain Python, no GPU -- which builds go out lean
-(wants_lean, the grouping of a batch: api_frames.hip; the plan's `lean`: l0_plan.h), which tracker launches have a lazy form (track_lazy_capable,
-settle_level0, mark_lazy_read: track_kernels.hip, api_track.hip) and who makes level-0 records on demand (ensure_level0_records and its
+(wants_lean, the grouping of a batch: api_frames.hip; the plan's `lean`: l0_plan.h), which tracker launches have a lazy form (plan_track's
+`lazy_capable` and `lazy`: track_plan.h; launch_pairs: api_track.hip) and who makes level-0 records on demand (ensure_level0_records and its
 ten call sites).  For a sequence of operations the model predicts
   * after every build, what klt_level0_lean and klt_level0_lean_form say (the last group, as the context reports it);
   * for every call, the launches of family "gradients" (klt_timing_read): those of a build's levels >= 1 -- one merged launch per group
@@ -17,7 +17,7 @@ from test_gpu_l0_lean_wave import goes_lean
 
 MAX_BATCH = 32                   # KLT_MAX_BATCH
 WORKGROUPS = 2048                # the streaming kernels' grid bound (L0S_MIN_WGS, L0W_MIN_WGS)
-QUAD_MIN = 2048                  # features x pairs from which the 7x7 quad tracker runs (track_quad7_rule)
+QUAD_MIN = 2048                  # features x pairs from which the 7x7 quad tracker runs (TRACK_QUAD7_MIN)
 OPT_TRACK_VARIANT, OPT_BUILD_STREAM, OPT_TRACK_TREE_SUMS, OPT_L0_STREAM, OPT_L0_LAZY_GRAD, OPT_L0_LEAN_FORM = 11, 15, 18, 21, 22, 23
 LEVELS, SS = 3, 4
 BORDER = 120                     # make_tc(levels=3, ss=4): KLTUpdateTCBorder's border, windows 7 (and, kept, 9)
@@ -183,7 +183,7 @@ class Model:
         return self.variant != 0 and self.window == 7 and n * npairs >= QUAD_MIN and not self.tree_sums and n > 0 and npairs > 0
 
     def track_plain(self, ids, n, npairs, kind):
-        """settle_level0 and mark_lazy_read of a plain launch on `ids` (a slot may be listed more than once)"""
+        """launch_pairs, its records on demand and its marks, for a plain launch on `ids` (a slot may be listed more than once)"""
         capable = self.lazy_capable(n, npairs)
         launches = 0
         if not (capable and all(self.slots[k].l0img_valid for k in ids)):

@@ -126,9 +126,11 @@ def test_constants_are_the_sources():
     plan = src("pyfeaturetrack_amd", "csrc", "l0_plan.h")
     assert re.search(r"L0S_MIN_WGS = (\d+), L0W_MIN_WGS = (\d+)", plan).groups() == (str(L.WORKGROUPS),) * 2
     assert int(re.search(r"constexpr int KLT_MAX_BATCH = (\d+);", plan).group(1)) == L.MAX_BATCH
-    trk = src("pyfeaturetrack_amd", "csrc", "track_kernels.hip")
-    assert int(re.search(r"return g_track_variant != 0 && window == 7 && \(long long\)n \* npairs >= (\d+);", trk).group(1)) == L.QUAD_MIN
-    assert re.search(r"return track_quad7_rule\(window, n, npairs\) && !tree_sums && n > 0 && npairs > 0;", trk)
+    trk = src("pyfeaturetrack_amd", "csrc", "track_plan.h")
+    assert int(re.search(r"constexpr long long TRACK_QUAD7_MIN = (\d+);", trk).group(1)) == L.QUAD_MIN
+    assert re.search(r"const bool quad7 = q\.variant != 0 && wc\.wct == 7 && \(long long\)q\.n \* ny >= TRACK_QUAD7_MIN;", trk)
+    # (over a sweep of launches: tests/test_track_plan_rule.py holds plan_track's lazy_capable against Model.lazy_capable)
+    assert re.search(r"p\.lazy_capable = track_lazy_rule\(q\.fb, q\.guess, q\.light\) && quad7 && !q\.tree_sums && q\.n > 0 && ny > 0 && q\.grad7;", trk)
     frames = src("pyfeaturetrack_amd", "csrc", "api_frames.hip")
     assert "return c->l0_lazy_grad == 1 && s->lazy_read && !s->rec0_asked && s->built_nc == s->nc && s->built_nr == s->nr && s->built_cfg == c->cfg_gen;" in frames
     assert "B * (s0->nlev - 1) <= KLT_MAX_BATCH" in frames      # the merged gradient launch of a build's levels >= 1
