@@ -33,7 +33,7 @@ extern "C" {
 
 #define KLT_ABI_VERSION 11        /* (unchanged by the forward-backward entry points, by the selection mask and by the motion prior:
                                    * klt_set_fb_params / klt_track_fb* / klt_set_select_mask* / klt_track_guess* / klt_track_fb_guess_async /
-                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path / klt_set_remap / klt_remap_u8 / klt_download_remapped_u8 / klt_remap_path are purely additive, no
+                                   * klt_predict_cv_async / klt_set_light_params / klt_track_light_path / klt_set_select_grid / klt_select_grid_path / klt_track_quality* / klt_set_model_params / klt_motion_check* / klt_motion_model_affine / klt_set_epipolar_params / klt_epipolar_check* / klt_epipolar_matrix / klt_set_homography_params / klt_homography_check* / klt_homography_matrix / klt_set_crowd_params / klt_crowd_check* / klt_set_equalize_params / klt_equalize_u8 / klt_download_equalized_u8 / klt_equalize_path / klt_set_remap / klt_remap_u8 / klt_download_remapped_u8 / klt_remap_path / klt_set_descriptor_params / klt_describe* / klt_set_match_params / klt_match* / klt_match_path are purely additive, no
                                    * existing struct or signature moved; klt_params stays as it is; nor by klt_level0_path,
                                    * klt_select_score_path, klt_select_pick_path and klt_download_prepared_keys, read-only diagnostic
                                    * entries) */
@@ -812,6 +812,70 @@ int klt_remap_path(klt_ctx *ctx);
  * again with no map or a fitting one.  The slot's remapped frame lives in a buffer of its own, allocated when first needed (KLT_ERR_NOMEM
  * leaves the slot as it was), freed by klt_slot_free, travelling with klt_swap_slots.  With no map set no launch, no allocation and no
  * event is added to any call. */
+
+/* ---- descriptors (not in the reference) --------------------------------------------------------------------------- */
+/* A 256-bit binary descriptor per feature from the 8-bit frame a slot holds, and a brute-force Hamming matcher over two descriptor sets:
+ * what gives a feature an identity that survives a gap (an occlusion, a second camera, a revisited place).  Both rules are integer-only;
+ * the device output equals their numpy restatement (tests/describe_expected.py) byte for byte.
+ *
+ * RULE 1, THE DESCRIPTOR.  Inputs: F, the ncols x nrows 8-bit frame that is the output of the slot's ingest chain (remapped, then
+ * equalised, when those stages are on); a list of klt_feat; mode: 1 upright, 2 steered.
+ *   1. centre    a feature is DESCRIBABLE when val >= 0, x and y are finite and, with cx = floor((double)x + 0.5), cy likewise,
+ *                0 <= cx < ncols and 0 <= cy < nrows.  Every other record is all zero (val = 0).
+ *   2. pixels    P(u, v) = F[clamp(cy + v, 0, nrows - 1)][clamp(cx + u, 0, ncols - 1)]: edges are replicated, as in the remap stage, so
+ *                every describable feature gets a descriptor on any frame size, 1 x 1 included.
+ *   3. pattern   256 tests (ax, ay, bx, by), generated once on the host and never typed in: state s = 0x9E3779B9 (uint32); a draw is
+ *                s = s * 1664525 + 1013904223 (mod 2^32) with value ((s >> 16) % 27) - 13; draw ax, ay, bx, by in that order; discard
+ *                the four if ax^2 + ay^2 > 169, or bx^2 + by^2 > 169, or (ax, ay) == (bx, by), or the test or its swap (bx, by, ax, ay)
+ *                is in the list already; stop at 256 tests (1892 draws).
+ *   4. orientation (mode 2; mode 1 has k = 0)  m10 = SUM u P(u, v), m01 = SUM v P(u, v) over u^2 + v^2 <= 225, 64-bit integers; k is the
+ *                smallest index in 0 .. 31 that maximises m10 C[k] + m01 S[k], C[k] = round(16384 cos(2 pi k / 32)) =
+ *                16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0, -3196, -6270, -9102, -11585, -13623, -15137, -16069,
+ *                -16384, -16069, -15137, -13623, -11585, -9102, -6270, -3196, 0, 3196, 6270, 9102, 11585, 13623, 15137, 16069
+ *                and S[k] = C[(k + 24) % 32].  No libm call on either side of the comparison.
+ *   5. steering  for k != 0 both points of every test are rotated: x' = (x C[k] - y S[k] + 8192) >> 14, y' = (x S[k] + y C[k] + 8192) >> 14,
+ *                arithmetic shifts (floor).  No rotated coordinate exceeds 13 in magnitude: with the box of step 6 every read lies in
+ *                the 31 x 31 patch around the centre, as does the orientation disc.
+ *   6. bit       B(u, v) = the sum of P over the 5 x 5 box centred at (u, v) (at most 6375); bit t is 1 iff B(a'_t) < B(b'_t), and is
+ *                bit t & 31 of bits[t >> 5].
+ *   7. record    klt_descriptor, 48 bytes = three klt_feat records: val 1 described / 0 not; orientation = k; cx, cy the centre.  It
+ *                lives in a feature buffer of 3 n records, the way quality and model records live in feature buffers.
+ *
+ * RULE 2, THE MATCH.  Inputs: nq query records, nt train records, klt_match_params.  Train record j is a CANDIDATE of query i when both
+ * have val == 1 and, with radius > 0, |cx_i - cx_j| <= radius and |cy_i - cy_j| <= radius.  d(i, j) = popcount of the XOR of the 256
+ * bits; best = the candidate of least d, a tie to the lowest j; second = the least d over the candidates other than best, 257 when there
+ * is none.  The outcome, decided in the order of these val codes:
+ *   0  the query is not described (train = -1, distance = second = 0);
+ *   2  no candidate (train = -1, distance = second = 257);
+ *   3  distance > max_distance;
+ *   4  ratio on, and not distance * ratio_den < second * ratio_num (64-bit arithmetic, strict);
+ *   5  cross-check on, and the best QUERY of train record `best` -- found by the same rule with the roles exchanged, ties to the lowest
+ *      query index -- is not i;
+ *   1  matched.
+ * Codes 1, 3, 4 and 5 carry train = best and the two distances found.  One `struct klt_match` record (16 bytes, one klt_feat) per query. */
+typedef struct { uint32_t bits[8]; int32_t val, orientation, cx, cy; } klt_descriptor;
+typedef struct { int32_t mode; } klt_descriptor_params;                      /* 1 upright (default), 2 steered */
+typedef struct { int32_t max_distance, ratio_num, ratio_den, cross_check, radius; } klt_match_params;
+struct klt_match { int32_t train, distance, second, val; };      /* (a tag, not a typedef: klt_match is also the synchronous call) */
+int klt_set_descriptor_params(klt_ctx *ctx, const klt_descriptor_params *p);      /* another mode: KLT_ERR_ARG */
+/* Describes the n records of fb_in on the slot's 8-bit frame into fb_desc (3 n feature records, allocated if needed).  The frame is read
+ * the way the selection on the raw frame reads it: behind its upload, behind a build that still reads it, through the ingest chain.  No
+ * pyramid is needed.  Refused before anything is allocated or enqueued: a slot without a frame and an f32 slot ("descriptors take 8-bit
+ * frames"): KLT_ERR_STATE; fb_desc the same buffer as fb_in, by index or by address, and n < 0: KLT_ERR_ARG; fb_in short of n records:
+ * KLT_ERR_STATE.  n == 0: KLT_OK, nothing enqueued.  A failed allocation is KLT_ERR_NOMEM and the context stays usable. */
+int klt_describe_async(klt_ctx *ctx, int slot, int fb_in, int fb_desc, int n);
+int klt_describe(klt_ctx *ctx, int slot, const klt_feat *in, klt_descriptor *out, int n);      /* synchronous, host arrays */
+/* max_distance 0 .. 256 (default 64); ratio_num == 0 switches the ratio test off, else 0 < ratio_num <= ratio_den <= 65535 (default
+ * 4 / 5); cross_check 0 or 1 (default 1); radius >= 0, 0 = no gate (default).  Anything else: KLT_ERR_ARG. */
+int klt_set_match_params(klt_ctx *ctx, const klt_match_params *p);
+/* fb_query holds nq descriptors (3 nq feature records), fb_train nt; fb_match (nq feature records, allocated if needed) must be distinct
+ * from both, by index and by address (KLT_ERR_ARG); fb_query may be fb_train.  nq == 0 enqueues nothing; nt == 0 gives every described
+ * query val = 2.  The partial results of the train set's ranges go through scratch the context owns and grows (KLT_ERR_NOMEM). */
+int klt_match_async(klt_ctx *ctx, int fb_query, int nq, int fb_train, int nt, int fb_match);
+int klt_match(klt_ctx *ctx, const klt_descriptor *q, int nq, const klt_descriptor *t, int nt, struct klt_match *out);      /* synchronous, host arrays */
+/* Diagnostic, read-only: *splits = how many ranges the train set of the last match was cut into (decided from nq and nt alone; every
+ * cut gives the same records).  KLT_ERR_STATE before the first match. */
+int klt_match_path(klt_ctx *ctx, int *splits);
 
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither

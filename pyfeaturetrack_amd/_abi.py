@@ -65,6 +65,23 @@ class KltEqualizeParams(C.Structure):
     _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("clip_q8", C.c_int32)]
 
 
+class KltDescriptor(C.Structure):
+    _fields_ = [("bits", C.c_uint32 * 8), ("val", C.c_int32), ("orientation", C.c_int32), ("cx", C.c_int32), ("cy", C.c_int32)]
+
+
+class KltDescriptorParams(C.Structure):
+    _fields_ = [("mode", C.c_int32)]
+
+
+class KltMatchParams(C.Structure):
+    _fields_ = [("max_distance", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("cross_check", C.c_int32),
+                ("radius", C.c_int32)]
+
+
+class KltMatch(C.Structure):
+    _fields_ = [("train", C.c_int32), ("distance", C.c_int32), ("second", C.c_int32), ("val", C.c_int32)]
+
+
 class KltCrowd(C.Structure):
     _fields_ = [("age", C.c_int32), ("winner", C.c_int32), ("val", C.c_int32), ("pad", C.c_int32)]
 
@@ -233,6 +250,13 @@ SYMBOLS = {
     "klt_remap_u8": (_I, [_P, _P, _I, _I, _I, _P]),
     "klt_download_remapped_u8": (_I, [_P, _I, _P]),
     "klt_remap_path": (_I, [_P]),
+    "klt_set_descriptor_params": (_I, [_P, C.POINTER(KltDescriptorParams)]),
+    "klt_describe_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_describe": (_I, [_P, _I, _P, _P, _I]),
+    "klt_set_match_params": (_I, [_P, C.POINTER(KltMatchParams)]),
+    "klt_match_async": (_I, [_P, _I, _I, _I, _I, _I]),
+    "klt_match": (_I, [_P, _P, _I, _P, _I, _P]),
+    "klt_match_path": (_I, [_P, _PI]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
-                   KltCrowd, KltCrowdParams, KltEqualizeParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
+                   KltCrowd, KltCrowdParams, KltDescriptor, KltDescriptorParams, KltMatch, KltMatchParams, KltEqualizeParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, remap_from_tc, taps_from_params
 
 FEAT_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("val", np.int32), ("aux", np.int32)])
@@ -41,6 +41,12 @@ assert HOMOGRAPHY_DTYPE.itemsize == C.sizeof(KltHomographyModel) == 6 * FEAT_DTY
 # crowded one merged into (-1 otherwise), val 0 non-candidate / 1 kept / 2 crowded; they live in feature buffers like quality records
 CROWD_DTYPE = np.dtype([("age", np.int32), ("winner", np.int32), ("val", np.int32), ("pad", np.int32)])
 assert CROWD_DTYPE.itemsize == C.sizeof(KltCrowd) == FEAT_DTYPE.itemsize
+# a descriptor (klt_descriptor; klt_describe*): one record in three klt_feat records of a feature buffer; a match record (klt_match;
+# klt_match*): one klt_feat record per query
+DESCRIPTOR_DTYPE = np.dtype([("bits", np.uint32, (8,)), ("val", np.int32), ("orientation", np.int32), ("cx", np.int32), ("cy", np.int32)])
+assert DESCRIPTOR_DTYPE.itemsize == C.sizeof(KltDescriptor) == 3 * FEAT_DTYPE.itemsize
+MATCH_DTYPE = np.dtype([("train", np.int32), ("distance", np.int32), ("second", np.int32), ("val", np.int32)])
+assert MATCH_DTYPE.itemsize == C.sizeof(KltMatch) == FEAT_DTYPE.itemsize
 
 SELECTING_ALL = 1
 REPLACING_SOME = 2
@@ -65,12 +71,16 @@ _MAX_FRAMES = 65535 - (_FB_TABLE + 1)
 # ... and the buffers of the same records in a KLTTrackFeatures call: the last id below the next table up
 _FB_API_QUALITY, _FB_API_MODEL, _FB_API_EPIPOLAR, _FB_API_HOMOGRAPHY, _FB_API_CROWD = 59999, 53999, 47999, 41999, 35999
 _FB_API_CROWD_PREV = 29999           # ... and the ages the caller handed in (age=)
+# KLTDescribeFeatures: the list and its descriptors; KLTMatchDescriptors: the two descriptor sets and the match records
+_FB_API_DESCRIBE_IN, _FB_API_DESCRIBE = 29998, 29997
+_FB_API_MATCH_QUERY, _FB_API_MATCH_TRAIN, _FB_API_MATCH = 29996, 29995, 29994
 # no id of a table that has grown as far as it can is a single buffer or an id of another table, and all of them lie below 65535
 _ids = [base + i for base in (_FB_TABLE, _FBQ_TABLE, _FBM_TABLE, _FBE_TABLE, _FBH_TABLE, _FBC_TABLE)
         for i in range(_MAX_FRAMES // (FB_CHUNK + 1) * (FB_CHUNK + 1))]
 assert max(_ids) < 65535 and len(set(_ids + list(_FB_LIBRARY + (
     _FB_API_SELECT, _FB_API_IN, _FB_API_OUT, _FB_API_BACK, _FB_API_GUESS, _FB_GUESS, _FB_API_QUALITY, _FB_API_MODEL, _FB_API_EPIPOLAR,
-    _FB_API_HOMOGRAPHY, _FB_API_CROWD, _FB_API_CROWD_PREV)))) == len(_ids) + 17
+    _FB_API_HOMOGRAPHY, _FB_API_CROWD, _FB_API_CROWD_PREV, _FB_API_DESCRIBE_IN, _FB_API_DESCRIBE, _FB_API_MATCH_QUERY, _FB_API_MATCH_TRAIN,
+    _FB_API_MATCH)))) == len(_ids) + 22
 del _ids
 
 # The three consensus checks over feature lists (DESIGN.md "what a consensus check is made of"), one row each: everything params.py,
@@ -926,6 +936,69 @@ class Context:
     def quality_download(self, fb, n):
         """n quality records of feature buffer `fb` (what a track_quality*_async launch wrote there)"""
         return self.featbuf_download(fb, n).view(QUALITY_DTYPE)
+
+    # ------------------------------------------------ descriptors and their matcher (klt_describe*, klt_match*)
+    def set_descriptor_params(self, mode=1):
+        """klt_set_descriptor_params: 1 upright (the default), 2 steered by the patch's orientation"""
+        self._check(self._lib.klt_set_descriptor_params(self._h, C.byref(KltDescriptorParams(int(mode)))))
+
+    def describe_async(self, slot, fb_in, fb_desc, n):
+        self._check(self._lib.klt_describe_async(self._h, slot, fb_in, fb_desc, n))
+
+    def describe(self, slot, fl, sync_entry=False):
+        """A DESCRIPTOR_DTYPE array, record i the descriptor of fl[i] on the 8-bit frame the slot holds (behind its ingest stages).
+        sync_entry: through klt_describe and the library's staging buffers instead of the Python layer's own two."""
+        fl = np.ascontiguousarray(fl, FEAT_DTYPE)
+        n = len(fl)
+        if sync_entry:
+            out = np.zeros(n, DESCRIPTOR_DTYPE)
+            self._check(self._lib.klt_describe(self._h, slot, fl.ctypes.data, out.ctypes.data, n))
+            return out
+        if n:
+            self.featbuf_upload(_FB_API_DESCRIBE_IN, fl)
+        self.describe_async(slot, _FB_API_DESCRIBE_IN, _FB_API_DESCRIBE, n)
+        return self.descriptor_download(_FB_API_DESCRIBE, n)
+
+    def descriptor_upload(self, fb, desc):
+        desc = np.ascontiguousarray(desc, DESCRIPTOR_DTYPE)
+        self.featbuf_upload(fb, desc.view(FEAT_DTYPE))
+
+    def descriptor_download(self, fb, n):
+        """n descriptors of feature buffer `fb` (its first 3 n records)"""
+        if n == 0:
+            return np.zeros(0, DESCRIPTOR_DTYPE)
+        return self.featbuf_download(fb, 3 * n).view(DESCRIPTOR_DTYPE)
+
+    def set_match_params(self, max_distance=64, ratio_num=4, ratio_den=5, cross_check=1, radius=0):
+        """klt_set_match_params (the defaults are the library's)"""
+        p = KltMatchParams(int(max_distance), int(ratio_num), int(ratio_den), int(cross_check), int(radius))
+        self._check(self._lib.klt_set_match_params(self._h, C.byref(p)))
+
+    def match_async(self, fb_query, nq, fb_train, nt, fb_match):
+        self._check(self._lib.klt_match_async(self._h, fb_query, nq, fb_train, nt, fb_match))
+
+    def match(self, query, train, sync_entry=False):
+        """A MATCH_DTYPE array, one record per query descriptor, under the parameters the context holds (set_match_params)"""
+        query = np.ascontiguousarray(query, DESCRIPTOR_DTYPE)
+        train = np.ascontiguousarray(train, DESCRIPTOR_DTYPE)
+        nq, nt = len(query), len(train)
+        if sync_entry:
+            out = np.zeros(nq, MATCH_DTYPE)
+            self._check(self._lib.klt_match(self._h, query.ctypes.data, nq, train.ctypes.data, nt, out.ctypes.data))
+            return out
+        if nq == 0:
+            return np.zeros(0, MATCH_DTYPE)
+        self.descriptor_upload(_FB_API_MATCH_QUERY, query)
+        if nt:
+            self.descriptor_upload(_FB_API_MATCH_TRAIN, train)
+        self.match_async(_FB_API_MATCH_QUERY, nq, _FB_API_MATCH_TRAIN, nt, _FB_API_MATCH)
+        return self.featbuf_download(_FB_API_MATCH, nq).view(MATCH_DTYPE)
+
+    def match_path(self):
+        """klt_match_path: how many ranges the train set of the last match was cut into"""
+        splits = C.c_int(0)
+        self._check(self._lib.klt_match_path(self._h, C.byref(splits)))
+        return splits.value
 
     # ------------------------------------------------ the post-track stages (params.post_track_from_tc): one chain
     def set_post_track_params(self, stages):

@@ -11,6 +11,7 @@
 //   api_quality.hip   per-feature track quality (single pair, batched)
 //   api_consensus.hip the consensus checks -- motion model, epipolar, homography -- (single pair, batched), their model records in pixels
 //   api_crowd.hip     crowding check (single list, batched)
+//   api_describe.hip  binary descriptors of a slot's 8-bit frame and their Hamming matcher
 //   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
@@ -35,10 +36,10 @@ namespace kltapi {
 
 
 enum Family { F_SMOOTH_GRAD, F_PYR_REDUCE, F_GRAD, F_SMOOTH_H, F_SMOOTH_V, F_PYR_H, F_PYR_V, F_GRAD_H, F_GRAD_V, F_TRACK,
-              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_REMAP, F_COUNT };
+              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_REMAP, F_DESCRIBE, F_MATCH, F_MATCH_RESOLVE, F_COUNT };
 inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_reduce", "gradients", "smooth_h", "smooth_v", "pyramid_h",
                                           "pyramid_v", "gradient_h", "gradient_v", "track", "sat_rows", "sat_cols",
-                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply", "remap"};
+                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply", "remap", "describe", "match", "match_resolve"};
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
@@ -346,6 +347,14 @@ struct klt_ctx {
     size_t crowd_scratch_cap = 0;
     const int *crowd_rounds = nullptr;                             // in crowd_scratch: the last launch's round count (klt_crowd_check_rounds)
     SentTable<CrowdPair> crowd_table;                              // klt_crowd_check_batch_async
+    // descriptors and their matcher (api_describe.hip): the parameters, the pattern in device memory (sent with the first describe
+    // launch), the partial results of a match's ranges (forward, then backward) and the cut of the last match (0: none yet)
+    klt_descriptor_params descp{1};
+    klt_match_params matchp{64, 4, 5, 1, 0};
+    int8_t *desc_pattern = nullptr;
+    int4 *match_part = nullptr;
+    size_t match_part_cap = 0;
+    int match_splits = 0;                                          // klt_match_path
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -415,7 +424,7 @@ struct TimerScope {
         // families whose scope holds ONE launch that goes through klt_launch (the order kernel in front of a tracker and the threshold
         // kernel behind the eigenvalue pass do not): timed by that dispatch's own timestamps.  Scopes with several launches keep the pair
         stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE || fam == F_CROWD_PREPARE || fam == F_CROWD ||
-                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY || fam == F_REMAP);
+                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY || fam == F_REMAP || fam == F_DESCRIBE || fam == F_MATCH || fam == F_MATCH_RESOLVE);
         if (stamps) { g_klt_stamp_start = t.a; g_klt_stamp_stop = t.b; }      // filled by the launch itself (klt_launch)
         else hipEventRecord(t.a, st);
     }

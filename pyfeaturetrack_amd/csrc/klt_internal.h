@@ -198,6 +198,36 @@ struct RemapArgs {
     int batch;
 };
 
+// the describe launch (describe_kernels.hip): the slot's 8-bit frame (ncols bytes from row to row), the list, the
+// descriptor records (in a feature buffer of 3 n records), the pattern (256 tests of four int8, 4-byte aligned) and the cosine table
+static_assert(sizeof(klt_descriptor) == 3 * sizeof(klt_feat) && alignof(klt_descriptor) == alignof(klt_feat), "a descriptor lives in three feature records");
+static_assert(sizeof(struct klt_match) == sizeof(klt_feat) && alignof(struct klt_match) == alignof(klt_feat), "match records live in feature buffers");
+struct DescribeArgs {
+    const uint8_t *frame;
+    const klt_feat *in;
+    klt_descriptor *out;
+    const int8_t *pattern;
+    int n, ncols, nrows;
+    short cs[32];                       // C[k]; S[k] = C[(k + 24) & 31]
+};
+
+// a match launch (match_kernels.hip): every record of `a` (na of them, one per lane) against the range blockIdx.y of `b` (nb records cut
+// into `splits` ranges, describe_rule.h: match_range); part[split * na + i] = (best distance, best index or -1, second distance, 0)
+struct MatchArgs {
+    const klt_descriptor *a, *b;
+    int4 *part;
+    int na, nb, splits, radius;
+};
+// ... and its resolve launch: the forward partial results (nq x splits), the backward ones when the cross-check is on (nt x rsplits,
+// else null), the parameters, one klt_match per query
+struct MatchResolveArgs {
+    const klt_descriptor *q;
+    const int4 *fwd, *bwd;
+    struct klt_match *out;
+    int nq, nt, splits, rsplits;
+    klt_match_params p;
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -501,6 +531,10 @@ void launch_clahe_lut(hipStream_t s, const EqualizeArgs &a, int batch);
 void launch_clahe_apply(hipStream_t s, const EqualizeArgs &a, int batch);
 // remap (remap_kernels.hip): the a.batch frames in one launch
 void launch_remap(hipStream_t s, const RemapArgs &a);
+// descriptors and their matcher (describe_kernels.hip, match_kernels.hip)
+void launch_describe(hipStream_t s, const DescribeArgs &a, int mode);
+void launch_match(hipStream_t s, const MatchArgs &a);
+void launch_match_resolve(hipStream_t s, const MatchResolveArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

@@ -147,6 +147,11 @@ class KLT_TrackingContext:
         # returns the frame the tracker then sees, KLTRemapValidMask(table) a tc.selectionMask that keeps the selection off replicated
         # edges, KLTRemapSourcePositions(table, x, y) where rectified positions lie in the incoming frame.
         self.remap = None
+        # Descriptors (not in the reference): KLTDescribeFeatures(tc, img, featurelist) gives every feature a
+        # 256-bit binary descriptor of the frame the tracker sees, KLTMatchDescriptors(tc, query, train) matches two sets by Hamming
+        # distance -- an identity that survives an occlusion.  False: upright descriptors (what a tracker's small frame-to-frame
+        # rotations want); True: steered by the patch's orientation (one of 32 bins), for sets related by an in-plane rotation.
+        self.descriptorOrientation = False
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

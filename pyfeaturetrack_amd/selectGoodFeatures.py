@@ -326,6 +326,7 @@ def KLTEqualizeImage(tc, img):
 
 
 from .params import KLT_RemapTable, KLTCreateRemap, KLTRemapSourcePositions, KLTRemapValidMask, KLTUndistortMap  # noqa: E402,F401  (the remap ingest stage's host side)
+from .describeFeatures import KLT_DescriptorList, KLTDescribeFeatures, KLTMatchDescriptors  # noqa: E402,F401  (descriptors: DESIGN.md section 9n)
 
 
 def KLTRemapImage(tc, img):
