@@ -207,7 +207,9 @@ int klt_host_sample_rows(const uint8_t *const *rows, int nrows, int ncols, int y
 int klt_host_luma_rows(float *dst, const uint8_t *const *rows, int nrows, int ncols);
 /* Frames that are ALREADY in device memory (a hardware decoder's output, a clip kept resident): the slot's frame becomes this caller-owned
  * buffer -- read in place by the next build / selection of the slot, never copied, written or freed by the library (zero-copy
- * ingest).  pitch must equal ncols.  Host-only call: nothing is enqueued; the buffer must hold the frame already and stay unchanged until
+ * ingest).  pitch must equal ncols.  The address needs no alignment: a frame may start at any byte (frame k of a clip at clip + k * size,
+ * or behind a header of any length); frames on a multiple of 4 bytes whose width is divisible by 4 take the level-0 kernels' 4-byte
+ * loads, every other frame is read byte by byte, with the same planes.  Host-only call: nothing is enqueued; the buffer must hold the frame already and stay unchanged until
  * the work that reads it has completed (klt_sync, or the download of what was computed from it).  The next upload into the slot ends the
  * adoption.  klt_device_alloc / klt_device_write / klt_device_free give callers without a HIP binding of their own (Python) such memory:
  * owned by the context, freed with it. */

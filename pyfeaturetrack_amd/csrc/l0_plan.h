@@ -20,6 +20,22 @@ struct Taps {
 
 constexpr int KLT_MAX_BATCH = 32;   // frames per fused pyramid launch (pointer tables travel in the kernarg segment)
 
+#if defined(__HIPCC__)
+#define KLT_RULE_HD __host__ __device__
+#else
+#define KLT_RULE_HD
+#endif
+
+// May a level-0 kernel read the frame at `addr` (rows of `ncols` elements of `elem_bytes`, no padding) four elements to a load?  Only
+// where every quad of every row then sits on a multiple of its own size: a width divisible by 4 AND a first byte on a multiple of
+// 4 * elem_bytes (4 for u8 frames, 16 for f32 frames).  An adopted frame (klt_slot_adopt_u8) may start at any byte, so the width alone
+// does not tell; frames that miss either half are read element by element.  The one home of this rule: every raw-frame quad load of
+// pyramid_kernels.hip asks here, per frame of a batch (tests/test_l0_plan_rule.py sweeps it without a GPU).
+KLT_RULE_HD inline bool raw_quads_aligned(uintptr_t addr, int ncols, int elem_bytes)
+{
+    return ncols % 4 == 0 && addr % (uintptr_t)(4 * elem_bytes) == 0;
+}
+
 // What the decision depends on, and nothing else
 struct L0Request {
     int ncols, nrows;       // the largest entry (grid extent)

@@ -299,22 +299,28 @@ template <> struct RawQuad<float> { typedef float4 reg; };
 __device__ __forceinline__ float4 quad_f32(uint32_t w) { return unpack_u8x4(w); }
 __device__ __forceinline__ float4 quad_f32(float4 v) { return v; }
 
-// Is the block of H rows x WQ quads at frame position (y0, x0) inside the frame, its quads aligned?
-template <int H, int WQ>
-__device__ __forceinline__ bool raw_block_interior(int nc, int nr, int y0, int x0)
+// Is the block of H rows x WQ quads at frame position (y0, x0) inside the frame, its quads aligned (raw_quads_aligned, l0_plan.h: by the
+// frame's own address, which for an adopted frame is any byte)?  Workgroup-uniform scalar work.
+template <int H, int WQ, typename TIn>
+__device__ __forceinline__ bool raw_block_interior(const TIn *raw, int nc, int nr, int y0, int x0)
 {
-    return (nc & 3) == 0 && x0 >= 0 && x0 + 4 * WQ <= nc && y0 >= 0 && y0 + H <= nr;
+    return raw_quads_aligned(reinterpret_cast<uintptr_t>(raw), nc, (int)sizeof(TIn)) && x0 >= 0 && x0 + 4 * WQ <= nc && y0 >= 0 && y0 + H <= nr;
 }
 
 // Stage 0: the raw block of H rows x WQ quads at frame position (y0, x0) -> registers; w[u] = quad tid + u NTHR of the block, row-major
 // (clamped: the last threads repeat the last quad).  Converting to f32 and storing to LDS is the caller's.  The frame must be large
 // enough that one reflection brings every index of the block inside.
-template <typename TIn, int H, int WQ, int NTHR>
+// QUADS: who has asked raw_quads_aligned about the frame's address.  BY_ADDRESS: nobody, the block asks (the tiled kernels: once per
+// workgroup).  ADDRESS_TESTED / NEVER: the streaming kernels, which ask once per workgroup in front of their band loop and fold the
+// answer into their EDGE instantiation (smooth_grad_stream): its blocks read element by element whatever the frame, the others'
+// by the width and the block's position alone -- no address bits are held across the bands.
+enum { RAW_QUADS_NEVER, RAW_QUADS_ADDRESS_TESTED, RAW_QUADS_BY_ADDRESS };
+template <typename TIn, int H, int WQ, int NTHR, int QUADS = RAW_QUADS_BY_ADDRESS>
 __device__ __forceinline__ void load_raw_block(const TIn *raw, int nc, int nr, int y0, int x0, int tid,
                                                typename RawQuad<TIn>::reg (&w)[(H * WQ + NTHR - 1) / NTHR])
 {
     constexpr int N0 = H * WQ, U0 = (N0 + NTHR - 1) / NTHR;
-    if (raw_block_interior<H, WQ>(nc, nr, y0, x0)) {
+    if (QUADS != RAW_QUADS_NEVER && raw_block_interior<H, WQ>(QUADS == RAW_QUADS_BY_ADDRESS ? raw : (const TIn *)nullptr, nc, nr, y0, x0)) {
         // Blocks inside the frame (most of them): every load of the thread is issued before the first one is used.  A loop
         // that waits for each of its 3-4 loads in turn costs 2.2 of the 9 us a workgroup of the tiled kernel lives.
         const plane_rsrc rawp = plane_of(raw);
@@ -506,8 +512,9 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
         constexpr int W0 = SMOOTH ? AQ : BQ, H0 = SMOOTH ? RH : IH, X0 = SMOOTH ? -(HB + 4) : -HB, Y0 = -(R + rs);
         float *const dst = SMOOTH ? A : C;
         constexpr int N0 = H0 * W0, U0 = (N0 + NTHR - 1) / NTHR;
+        const bool quads = raw_quads_aligned(reinterpret_cast<uintptr_t>(raw), nc, (int)sizeof(TIn));   // block-uniform, outside the loops
         // tiles whose halo lies inside the frame, and frame-edge tiles of frames large enough that one reflection brings every index inside
-        if (raw_block_interior<H0, W0>(nc, nr, ty0 + Y0, tx0 + X0) || (nc >= 2 * TW && nr >= 2 * TH_)) {
+        if (raw_block_interior<H0, W0>(raw, nc, nr, ty0 + Y0, tx0 + X0) || (nc >= 2 * TW && nr >= 2 * TH_)) {
             typename RawQuad<TIn>::reg w[U0];
             load_raw_block<TIn, H0, W0, NTHR>(raw, nc, nr, ty0 + Y0, tx0 + X0, tid, w);
 #pragma unroll
@@ -522,7 +529,7 @@ __device__ __forceinline__ void smooth_grad_rb_tile(const SmoothGradArgs &a, flo
             const int x = tx0 + X0 + 4 * q;
             const TIn *row = raw + (size_t)gy * nc;
             float4 v;
-            if (x >= 0 && x + 3 < nc && (nc & 3) == 0) {          // aligned quad: one 4- or 16-byte load
+            if (quads && x >= 0 && x + 3 < nc) {                  // aligned quad: one 4- or 16-byte load
                 if constexpr (sizeof(TIn) == 1) v = unpack_u8x4(*reinterpret_cast<const uint32_t *>(row + x));
                 else v = *reinterpret_cast<const float4 *>(row + x);
             } else if (x >= 0 && x + 3 < nc) {
@@ -718,6 +725,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
                                                const int cbase, const int s0, const int ylim, const int par, uint32_t (&pre)[l0_stream_pre_regs<TW, SB>()])
 {
     constexpr bool PF = sizeof(TIn) == 1;                       // u8: raw rows fetched one band ahead
+    constexpr int RQ = EDGE ? RAW_QUADS_NEVER : RAW_QUADS_ADDRESS_TESTED;   // (smooth_grad_stream has asked about the frame's address)
     STREAM_CLK_START;
     constexpr int NTHR = 256, NG = 7, ND = 7;
     using L = StreamLds<NS, TW, SB>;
@@ -750,7 +758,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
 #pragma unroll
             for (int u = 0; u < U0; u++) w[u] = pre[u];
         } else {
-            load_raw_block<TIn, NA, AQ, NTHR>(raw, nc, nr, cbase + rs + ALO, tx0 + X0, tid, w);
+            load_raw_block<TIn, NA, AQ, NTHR, RQ>(raw, nc, nr, cbase + rs + ALO, tx0 + X0, tid, w);
         }
         if (!PRO) __syncthreads();                               // the previous band's stage 4 has read DE
 #pragma unroll
@@ -771,7 +779,7 @@ __device__ __forceinline__ void l0_stream_band(const SmoothGradArgs &a, float *c
     STREAM_MARK(0);
     if constexpr (PF) {
         if (PRO || cbase - 3 + SB < ylim)                        // the A rows of the next steady band
-            load_raw_block<uint8_t, SB, AQ, NTHR>(raw, nc, nr, (PRO ? s0 + 3 : cbase + SB) + rs, tx0 + X0, threadIdx.x, pre);
+            load_raw_block<uint8_t, SB, AQ, NTHR, RQ>(raw, nc, nr, (PRO ? s0 + 3 : cbase + SB) + rs, tx0 + X0, threadIdx.x, pre);
     }
     {
         TapRegs<NS> ks;
@@ -912,7 +920,13 @@ __global__ __launch_bounds__(256, KLT_L0_WAVES) void smooth_grad_stream(SmoothGr
     const int nc = a.dim_c[b] ? a.dim_c[b] : a.ncols, nr = a.dim_r[b] ? a.dim_r[b] : a.nrows;
     if (tx0 >= nc || s0 >= nr) return;
     const int ylim = min(s0 + seg_h, nr);
-    const bool inside = tx0 + TW <= nc && tx0 / 4 + TW / 4 <= a.h1_nc;
+    // A frame of a width divisible by 4 whose address is off its quads' alignment (an adopted frame starts at any byte: raw_quads_aligned,
+    // l0_plan.h) takes the EDGE instantiation for every strip: that one never loads a quad.  For every other frame EDGE strips read
+    // element by element as it is (h1_nc = nc / 4, so a strip is EDGE where tx0 + TW > 4 (nc / 4): its raw block, 16 columns wider a
+    // side, leaves the frame or the width is no multiple of 4), and the other strips decide by the width alone, as they always have.
+    // Asked here, once per workgroup, so that the band loop holds nothing for it.
+    const bool off_quads = nc % 4 == 0 && !raw_quads_aligned(reinterpret_cast<uintptr_t>(a.raw[b]), nc, (int)sizeof(TIn));
+    const bool inside = tx0 + TW <= nc && tx0 / 4 + TW / 4 <= a.h1_nc && !off_quads;
     STAGE_MARK(0);
     if (inside) l0_stream_segment<TIn, NS, TW, SB, ZC, false, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
     else l0_stream_segment<TIn, NS, TW, SB, ZC, true, LEAN>(a, lds, nc, nr, tx0, s0, ylim);
@@ -1130,8 +1144,8 @@ __global__ __launch_bounds__(64 * LW_WAVES, KLT_L0_WAVE_PER_SIMD) void smooth_gr
     const int x0 = strip * LW_COLS, s0 = seg * seg_h;
     if (x0 >= nc || s0 >= nr) return;
     const int ylim = min(s0 + seg_h, nr);
-    // every column the strip reads inside the frame, its quads aligned
-    const bool inside = (nc & 3) == 0 && x0 >= LW_HALO && x0 + LW_COLS + LW_HALO + (NS / 2 > 3 ? 4 : 0) <= nc && x0 / 4 + LW_COLS / 4 <= a.h1_nc;
+    // every column the strip reads inside the frame, its quads aligned (by this frame's own address: wavefront-uniform)
+    const bool inside = raw_quads_aligned(reinterpret_cast<uintptr_t>(a.raw[b]), nc, (int)sizeof(TIn)) && x0 >= LW_HALO && x0 + LW_COLS + LW_HALO + (NS / 2 > 3 ? 4 : 0) <= nc && x0 / 4 + LW_COLS / 4 <= a.h1_nc;
     if (inside) lean_wave_segment<TIn, NS, false>(a, lds + wave * (2 * LW_ROW), b, nc, nr, x0, s0, ylim);
     else lean_wave_segment<TIn, NS, true>(a, lds + wave * (2 * LW_ROW), b, nc, nr, x0, s0, ylim);
 }

@@ -3,7 +3,8 @@
 //   T <name> <n> <sym> <k0> ... <kn-1>       defines a tap set (hex floats), in the order the library keeps them
 //   R <ncols> <nrows> <batch> <kind> <uniform> <smooth> <ggauss> <gderiv> <reduce> <ss> <fuse_hreduce> <l0_stream> <lean_form_opt>
 //     <want_hred> <want_lean> <rb_th> <l0_seg> <wide_wgs>      one request (tap sets by name, then the three tuning hooks; 0 = default)
-// One line of `field=value` pairs per request, every field of the plan.
+//   Q <addr> <ncols> <elem_bytes>             raw_quads_aligned: may a frame at that address be read four elements to a load
+// One line of `field=value` pairs per request, every field of the plan; one line `quads=0|1` per Q.
 #include <cstdio>
 #include <map>
 #include <string>
@@ -21,6 +22,13 @@ int main()
             for (int i = 0; i < t.n; i++)
                 if (scanf("%la", &t.k[i]) != 1) return 2;
             taps[name[0]] = t;
+            continue;
+        }
+        if (tag[0] == 'Q') {
+            unsigned long long addr;
+            int ncols, elem_bytes;
+            if (scanf("%llu %d %d", &addr, &ncols, &elem_bytes) != 3) return 2;
+            printf("quads=%d\n", (int)raw_quads_aligned((uintptr_t)addr, ncols, elem_bytes));
             continue;
         }
         L0Request q = {};

@@ -5,12 +5,16 @@ takes_wave, test_gpu_l0_lean.takes_geometry -- each left as it is.  Drift betwee
 where klt_level0_path disagrees on a GPU.
 
 The restatements speak about builds at subsampling 4 with more than one level and 5 or 9 smoothing taps; the sweep also holds launches
-outside that (subsampling 2, one level, 7 smoothing taps), where the answer is expected_path's alone and nothing streams or goes lean."""
+outside that (subsampling 2, one level, 7 smoothing taps), where the answer is expected_path's alone and nothing streams or goes lean.
+
+raw_quads_aligned, the rule in the same header for the quad loads of a caller's frame (an adopted frame starts at any byte), is swept through
+the same program against a one-line numpy restatement."""
 import functools
 import itertools
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import test_gpu_l0_lean as lean_mod
@@ -125,10 +129,16 @@ def build_sweep():
 
 
 @pytest.fixture(scope="module")
-def answers(tmp_path_factory):
+def dump_exe(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("l0_plan") / "l0_plan_dump")
     subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(REPO, "include"),
                     "-I" + os.path.join(REPO, "pyfeaturetrack_amd", "csrc"), os.path.join(REPO, "tests", "l0_plan_dump.cpp"), "-o", exe], check=True)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def answers(dump_exe):
+    exe = dump_exe
     sw = build_sweep()
     r = subprocess.run([exe], input="\n".join(sw.lines) + "\n", capture_output=True, text=True, check=True)
     plans = [{k: int(v) for k, v in (f.split("=") for f in line.split())} for line in r.stdout.splitlines()]
@@ -221,3 +231,18 @@ def test_the_experiment_hooks(answers):
     p = got["KLT_L0_SEG wave 50"]
     assert (p["lean_form"], p["seg"], p["nsegs"], p["units"], p["gx"]) == (2, 50, 22, 9 * 22 * 16, 9 * 22 * 4)
     assert (got["KLT_L0_WIDE_WGS"]["path"], got["KLT_L0_WIDE_WGS"]["gz"]) == (STREAM_WIDE_NO_CENTRE, 9)
+
+
+def test_quad_loads_go_by_the_address_and_the_width(dump_exe):
+    """raw_quads_aligned over every residue of 16 of the address (on several bases, one past 2^32), every ncols % 4 (on several widths) and
+    both element sizes: true exactly where the width is a multiple of 4 and the address one of 4 elements"""
+    asked = [(base + r, nc + c, eb) for base in (0, 1 << 20, (1 << 33) + 4096, (1 << 47) - 16) for r in range(16)
+             for nc in (4, 64, 1920) for c in range(4) for eb in (1, 4)]
+    r = subprocess.run([dump_exe], input="".join("Q %d %d %d\n" % q for q in asked), capture_output=True, text=True, check=True)
+    got = np.array([int(line.split("=")[1]) for line in r.stdout.splitlines()], bool)
+    addr, ncols, eb = (np.array(v, np.uint64) for v in zip(*asked))
+    want = (ncols % 4 == 0) & (addr % (4 * eb) == 0)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    # both answers for either element size, and the u8 and f32 answers differ where the address is a multiple of 4 and not of 16
+    assert {(int(e), bool(g)) for e, g in zip(eb, got)} == {(1, False), (1, True), (4, False), (4, True)}
+    assert any(g and e == 1 and a % 16 for a, e, g in zip(addr, eb, got))
