@@ -879,6 +879,60 @@ int klt_match(klt_ctx *ctx, const klt_descriptor *q, int nq, const klt_descripto
  * cut gives the same records).  KLT_ERR_STATE before the first match. */
 int klt_match_path(klt_ctx *ctx, int *splits);
 
+/* ---- track identities (not in the reference) ----------------------------------------------------------------------- */
+/* A persistent track id for every slot of every list of a sequence, and re-acquisition of lost tracks: what a lost track leaves behind
+ * (descriptor, id, the step it was last seen) goes into a ring bank in device memory; every step the newly selected features are matched
+ * against the bank (rule 2 above, cross-check always on) and inherit the old id on a match.  Everything is enqueued on the context's
+ * stream; no call here synchronises except the three diagnostics.  Integer-only; the device output (ident rows, bank, state) equals
+ * the numpy restatement (tests/reacquire_expected.py) byte for byte.
+ *
+ * STATE per context: the step counter k, next_id, the ring head h, a bank of C = capacity entries, the descriptors P of the previous list.
+ *
+ * BEGIN (list L0 of n records on the slot's frame):  I0[s] = {s, 0, 0, 2} where L0[s].val >= 0, else {-1, 0, 0, 0}; next_id = n, h = 0,
+ * k = 0, every bank entry all zero; P = the descriptors of L0 (rule 1 in the context's descriptor mode).
+ *
+ * STEP k >= 1 (list Lk -- after tracking, checks and replacement --, the previous ident row I(k-1), frame k in the slot):
+ *   1. Q = the descriptors of Lk on frame k.
+ *   2. classes   slot s is CONTINUED when I(k-1)[s].val != 0 and Lk[s].val == 0; FRESH when Lk[s].val >= 0 and it is not continued; LOST
+ *                when I(k-1)[s].val != 0 and it is not continued.  A refilled slot is both lost and fresh.
+ *   3. expire    a valid bank entry with k - last_seen - 1 > max_gap becomes all zero.
+ *   4. deposit   the lost slots with P[s].val == 1, in slot order, ranks r = 0 .. L-1: entry (h + r) & (C-1) = {P[s], I(k-1)[s].id,
+ *                last_seen = k-1, valid = 1, pad = 0}; the outcome is that of writing all L in order (L > C: only ranks >= L - C are
+ *                written); then h = (h + L) & (C-1).
+ *   5. match     rule 2 with cross_check = 1: the queries are the C bank entries in position order (an entry that is not valid counts as
+ *                not described), the train set is the fresh slots' Q records in slot order.
+ *   6. assign    bank entry i with outcome 1 and train slot s: Ik[s] = {bank[i].id, k - bank[i].last_seen - 1, distance, 3}, and the
+ *                entry becomes all zero.  The cross-check makes this conflict-free: entry i is matched only when the best query of its
+ *                train record is i, and that is one value per train record.  The other fresh slots, in slot order with rank r:
+ *                {next_id + r, 0, 0, 2}; next_id += their number.  Continued slots: {I(k-1)[s].id, 0, 0, 1}.  All others: {-1, 0, 0, 0}.
+ *   7. P = Q.
+ * Deposits come before the match: a track the tracker dropped and the replacement pass selected again in the same step gets its id back
+ * with gap = 0. */
+typedef struct { int32_t id, gap, distance, val; } klt_ident;      /* val: 0 no track (id = -1), 1 continued, 2 new, 3 re-acquired */
+typedef struct { klt_descriptor d; int32_t id, last_seen, valid, pad; } klt_bank_entry;      /* 64 bytes */
+typedef struct { int32_t capacity, max_gap, max_distance, ratio_num, ratio_den, radius; } klt_reacquire_params;
+/* k, h and next_id after the last begin / step; the valid bank entries; the fresh slots and the deposited (lost and described) slots
+ * of the last step */
+struct klt_reacquire_state { int32_t k, h, next_id, valid, fresh, lost; };      /* (a tag, as klt_match is: the name is also the call) */
+/* capacity a power of two in 1 .. 4096 (default 1024); max_gap >= 0 (default 30); max_distance, ratio_num, ratio_den, radius as
+ * klt_set_match_params takes them (defaults 64, 4 / 5, 24).  Anything else: KLT_ERR_ARG.  New parameters end the sequence in progress:
+ * the next call must be a begin. */
+int klt_set_reacquire_params(klt_ctx *ctx, const klt_reacquire_params *p);
+/* fb_list holds the n >= 1 records of the list, the slot its frame (read as klt_describe_async reads it, and refused as it refuses);
+ * fb_ident (n feature records, allocated if needed) receives the klt_ident row.  Every refusal comes before the first allocation --
+ * klt_describe_async's; fb_ident the same buffer as fb_list (or, in a step, fb_ident_prev), by index or by address, n < 1:
+ * KLT_ERR_ARG; a step without a begin, with another n than the begin's, fb_ident_prev short of n records: KLT_ERR_STATE -- and every
+ * allocation before the first launch; a failed one is KLT_ERR_NOMEM and the call can be repeated.  All memory is taken by the begin call:
+ * a step allocates nothing, so steps may be captured into a graph. */
+int klt_reacquire_begin_async(klt_ctx *ctx, int slot, int fb_list, int fb_ident, int n);
+int klt_reacquire_step_async(klt_ctx *ctx, int slot, int fb_list, int fb_ident_prev, int fb_ident, int n);
+/* Diagnostics.  The first two synchronise the context's stream; KLT_ERR_STATE before the first begin.  `entries` receives capacity
+ * klt_bank_entry records.  klt_reacquire_path: *launches = the launches the last begin (2) or step (5) enqueued, 0 = none yet; a
+ * context that never calls a begin makes exactly the calls it made before. */
+int klt_reacquire_state(klt_ctx *ctx, struct klt_reacquire_state *state);
+int klt_reacquire_download_bank(klt_ctx *ctx, void *entries);
+int klt_reacquire_path(klt_ctx *ctx, int *launches);
+
 /* ---- affine consistency check (BASELINE cfg-3) -- PARITY UNPINNED ------------------------- */
 /* The reference calls _am_trackFeatureAffine / _am_getSubFloatImage at trackFeatures.py:347-399 but defines neither
  * (NameError): the call site pins the interface, upstream KLT 1.3.4 the behaviour.

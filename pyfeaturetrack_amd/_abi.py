@@ -82,6 +82,23 @@ class KltMatch(C.Structure):
     _fields_ = [("train", C.c_int32), ("distance", C.c_int32), ("second", C.c_int32), ("val", C.c_int32)]
 
 
+class KltIdent(C.Structure):
+    _fields_ = [("id", C.c_int32), ("gap", C.c_int32), ("distance", C.c_int32), ("val", C.c_int32)]
+
+
+class KltBankEntry(C.Structure):
+    _fields_ = [("d", KltDescriptor), ("id", C.c_int32), ("last_seen", C.c_int32), ("valid", C.c_int32), ("pad", C.c_int32)]
+
+
+class KltReacquireParams(C.Structure):
+    _fields_ = [("capacity", C.c_int32), ("max_gap", C.c_int32), ("max_distance", C.c_int32), ("ratio_num", C.c_int32),
+                ("ratio_den", C.c_int32), ("radius", C.c_int32)]
+
+
+class KltReacquireState(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("k", "h", "next_id", "valid", "fresh", "lost")]
+
+
 class KltCrowd(C.Structure):
     _fields_ = [("age", C.c_int32), ("winner", C.c_int32), ("val", C.c_int32), ("pad", C.c_int32)]
 
@@ -257,6 +274,12 @@ SYMBOLS = {
     "klt_match_async": (_I, [_P, _I, _I, _I, _I, _I]),
     "klt_match": (_I, [_P, _P, _I, _P, _I, _P]),
     "klt_match_path": (_I, [_P, _PI]),
+    "klt_set_reacquire_params": (_I, [_P, C.POINTER(KltReacquireParams)]),
+    "klt_reacquire_begin_async": (_I, [_P, _I, _I, _I, _I]),
+    "klt_reacquire_step_async": (_I, [_P, _I, _I, _I, _I, _I]),
+    "klt_reacquire_state": (_I, [_P, C.POINTER(KltReacquireState)]),
+    "klt_reacquire_download_bank": (_I, [_P, _P]),
+    "klt_reacquire_path": (_I, [_P, _PI]),
     "klt_set_affine_params": (_I, [_P, C.POINTER(KltAffineParams)]),
     "klt_affine_alloc": (_I, [_P, _I, _I]),
     "klt_affine_download": (_I, [_P, _I, _P, _I]),

@@ -12,6 +12,7 @@ import threading
 import numpy as np
 
 from ._abi import (KLT_MAX_LEVELS, KltAffineRec, KltFbParams, KltLightParams, KltSelectGrid, KltBackendError, KltCommTimeout, KltOutOfMemory, KltFeat, KltKernelTime, KltParams,
+                   KltBankEntry, KltIdent, KltReacquireParams, KltReacquireState,
                    KltCrowd, KltCrowdParams, KltDescriptor, KltDescriptorParams, KltMatch, KltMatchParams, KltEqualizeParams, KltEpipolarModel, KltEpipolarParams, KltHomographyModel, KltHomographyParams, KltModelParams, KltMotionModel, KltQuality, KltTrackStats, load_library)
 from .params import affine_params_from_tc, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, params_from_tc, remap_from_tc, taps_from_params
 
@@ -47,6 +48,14 @@ DESCRIPTOR_DTYPE = np.dtype([("bits", np.uint32, (8,)), ("val", np.int32), ("ori
 assert DESCRIPTOR_DTYPE.itemsize == C.sizeof(KltDescriptor) == 3 * FEAT_DTYPE.itemsize
 MATCH_DTYPE = np.dtype([("train", np.int32), ("distance", np.int32), ("second", np.int32), ("val", np.int32)])
 assert MATCH_DTYPE.itemsize == C.sizeof(KltMatch) == FEAT_DTYPE.itemsize
+# an ident record (klt_ident; klt_reacquire_*): one klt_feat record per slot, val 0 no track / 1 continued / 2 new / 3 re-acquired; an
+# entry of the bank of lost tracks and the counters, as the two synchronous diagnostics return them
+IDENT_DTYPE = np.dtype([("id", np.int32), ("gap", np.int32), ("distance", np.int32), ("val", np.int32)])
+assert IDENT_DTYPE.itemsize == C.sizeof(KltIdent) == FEAT_DTYPE.itemsize
+BANK_DTYPE = np.dtype([("d", DESCRIPTOR_DTYPE), ("id", np.int32), ("last_seen", np.int32), ("valid", np.int32), ("pad", np.int32)])
+assert BANK_DTYPE.itemsize == C.sizeof(KltBankEntry) == 64
+REACQUIRE_STATE_DTYPE = np.dtype([(k, np.int32) for k in ("k", "h", "next_id", "valid", "fresh", "lost")])
+assert REACQUIRE_STATE_DTYPE.itemsize == C.sizeof(KltReacquireState)
 
 SELECTING_ALL = 1
 REPLACING_SOME = 2
@@ -74,13 +83,18 @@ _FB_API_CROWD_PREV = 29999           # ... and the ages the caller handed in (ag
 # KLTDescribeFeatures: the list and its descriptors; KLTMatchDescriptors: the two descriptor sets and the match records
 _FB_API_DESCRIBE_IN, _FB_API_DESCRIBE = 29998, 29997
 _FB_API_MATCH_QUERY, _FB_API_MATCH_TRAIN, _FB_API_MATCH = 29996, 29995, 29994
+# track identities: KLTUpdateIdentities' list and its two alternating ident rows; the two descriptor buffers the library keeps for
+# itself (klt_reacquire_*: P and Q); KLTTrackSequence's table of ident rows (tc.reacquireLost)
+_FB_API_IDENT_IN, _FB_API_IDENT = 29993, (29992, 29989)
+_FB_LIBRARY_REACQUIRE = (29990, 29991)
+_FBI_TABLE = 24000
 # no id of a table that has grown as far as it can is a single buffer or an id of another table, and all of them lie below 65535
-_ids = [base + i for base in (_FB_TABLE, _FBQ_TABLE, _FBM_TABLE, _FBE_TABLE, _FBH_TABLE, _FBC_TABLE)
+_ids = [base + i for base in (_FB_TABLE, _FBQ_TABLE, _FBM_TABLE, _FBE_TABLE, _FBH_TABLE, _FBC_TABLE, _FBI_TABLE)
         for i in range(_MAX_FRAMES // (FB_CHUNK + 1) * (FB_CHUNK + 1))]
-assert max(_ids) < 65535 and len(set(_ids + list(_FB_LIBRARY + (
+assert max(_ids) < 65535 and len(set(_ids + list(_FB_LIBRARY + _FB_LIBRARY_REACQUIRE + _FB_API_IDENT + (
     _FB_API_SELECT, _FB_API_IN, _FB_API_OUT, _FB_API_BACK, _FB_API_GUESS, _FB_GUESS, _FB_API_QUALITY, _FB_API_MODEL, _FB_API_EPIPOLAR,
     _FB_API_HOMOGRAPHY, _FB_API_CROWD, _FB_API_CROWD_PREV, _FB_API_DESCRIBE_IN, _FB_API_DESCRIBE, _FB_API_MATCH_QUERY, _FB_API_MATCH_TRAIN,
-    _FB_API_MATCH)))) == len(_ids) + 22
+    _FB_API_MATCH, _FB_API_IDENT_IN)))) == len(_ids) + 27
 del _ids
 
 # The three consensus checks over feature lists (DESIGN.md "what a consensus check is made of"), one row each: everything params.py,
@@ -999,6 +1013,44 @@ class Context:
         splits = C.c_int(0)
         self._check(self._lib.klt_match_path(self._h, C.byref(splits)))
         return splits.value
+
+    # ------------------------------------------------ track identities (klt_reacquire_*)
+    def set_reacquire_params(self, capacity=1024, max_gap=30, max_distance=64, ratio_num=4, ratio_den=5, radius=24):
+        """klt_set_reacquire_params (the defaults are the library's); ends the sequence in progress"""
+        p = KltReacquireParams(int(capacity), int(max_gap), int(max_distance), int(ratio_num), int(ratio_den), int(radius))
+        self._check(self._lib.klt_set_reacquire_params(self._h, C.byref(p)))
+
+    def reacquire_begin_async(self, slot, fb_list, fb_ident, n):
+        self._check(self._lib.klt_reacquire_begin_async(self._h, slot, fb_list, fb_ident, n))
+
+    def reacquire_step_async(self, slot, fb_list, fb_ident_prev, fb_ident, n):
+        self._check(self._lib.klt_reacquire_step_async(self._h, slot, fb_list, fb_ident_prev, fb_ident, n))
+
+    def ident_download(self, fb, n):
+        """n ident records of feature buffer `fb`"""
+        return self.featbuf_download(fb, n).view(IDENT_DTYPE)
+
+    def reacquire_state(self):
+        """klt_reacquire_state (synchronous): a REACQUIRE_STATE_DTYPE scalar -- k, h, next_id, the valid bank entries, the fresh and the
+        deposited slots of the last step"""
+        st = KltReacquireState()
+        self._check(self._lib.klt_reacquire_state(self._h, C.byref(st)))
+        out = np.zeros((), REACQUIRE_STATE_DTYPE)
+        for k in REACQUIRE_STATE_DTYPE.names:
+            out[k] = getattr(st, k)
+        return out
+
+    def reacquire_bank(self, capacity):
+        """klt_reacquire_download_bank (synchronous): the `capacity` entries of the bank as a BANK_DTYPE array"""
+        out = np.zeros(int(capacity), BANK_DTYPE)
+        self._check(self._lib.klt_reacquire_download_bank(self._h, out.ctypes.data))
+        return out
+
+    def reacquire_path(self):
+        """klt_reacquire_path: the launches the last begin (2) or step (5) enqueued; 0: none yet"""
+        launches = C.c_int(-1)
+        self._check(self._lib.klt_reacquire_path(self._h, C.byref(launches)))
+        return launches.value
 
     # ------------------------------------------------ the post-track stages (params.post_track_from_tc): one chain
     def set_post_track_params(self, stages):

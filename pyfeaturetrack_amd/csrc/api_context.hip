@@ -306,7 +306,7 @@ void klt_destroy(klt_ctx *c)
     for (auto &e : c->pre) hipFree(e.keys);
     hipFree(c->sat_pre);
     hipFree(c->keys); hipFree(c->seedmap); hipFree(c->mask_own); hipFree(c->quota_buf); hipFree(c->grid); hipFree(c->nms_slots); for (auto &bt : c->batch_tables) hipFree(bt.dev); for (auto &bo : c->batch_orders) hipFree(bo.order); hipFree(c->shared_order.order); hipFree(c->keys2); hipFree(c->topk_hist); hipFree(c->fl_snapshot); hipFree(c->mis_st); hipFree(c->mis_list); hipFree(c->mis_cnt); hipFree(c->score_override); hipFree(c->mis_tile_keys);
-    for (AffState &a : c->aff) { hipFree(a.rec); hipFree(a.tpl); } hipFree(c->placed_d); hipFree(c->stats_d); hipFree(c->quality_table.dev); for (ConsensusState &k : c->consensus) { hipFree(k.scratch); hipFree(k.table.dev); } hipFree(c->crowd_scratch); hipFree(c->crowd_table.dev); hipFree(c->desc_pattern); hipFree(c->match_part);
+    for (AffState &a : c->aff) { hipFree(a.rec); hipFree(a.tpl); } hipFree(c->placed_d); hipFree(c->stats_d); hipFree(c->quality_table.dev); for (ConsensusState &k : c->consensus) { hipFree(k.scratch); hipFree(k.table.dev); } hipFree(c->crowd_scratch); hipFree(c->crowd_table.dev); hipFree(c->desc_pattern); hipFree(c->match_part); hipFree(c->reacq_mem);
     for (Timed &t : c->pending) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     for (hipEvent_t e : c->pool) hipEventDestroy(e);
     if (c->stream) hipStreamDestroy(c->stream);

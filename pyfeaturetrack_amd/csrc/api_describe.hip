@@ -12,13 +12,6 @@ const char *const kDescNotDistinct = "fb_desc must be distinct from fb_in";
 const char *const kMatchNoBuffer = "fb_match must be a feature buffer";
 const char *const kMatchNotDistinct = "fb_match must be distinct from fb_query and fb_train";
 
-bool match_params_ok(const klt_match_params &p)
-{
-    if (p.max_distance < 0 || p.max_distance > 256) return false;
-    if (p.ratio_num != 0 && !(0 < p.ratio_num && p.ratio_num <= p.ratio_den && p.ratio_den <= 65535)) return false;
-    return (p.cross_check == 0 || p.cross_check == 1) && p.radius >= 0;
-}
-
 // the pattern in device memory: generated and sent once per context (a synchronous copy of 1 KB)
 int ensure_pattern(klt_ctx *c)
 {
@@ -48,9 +41,19 @@ int klt_set_descriptor_params(klt_ctx *c, const klt_descriptor_params *p)
     return KLT_OK;
 }
 
-int klt_describe_async(klt_ctx *c, int slot, int fb_in, int fb_desc, int n)
+}  // extern "C"
+
+namespace kltapi {
+
+bool match_params_ok(const klt_match_params &p)
 {
-    if (!c) return KLT_ERR_ARG;
+    if (p.max_distance < 0 || p.max_distance > 256) return false;
+    if (p.ratio_num != 0 && !(0 < p.ratio_num && p.ratio_num <= p.ratio_den && p.ratio_den <= 65535)) return false;
+    return (p.cross_check == 0 || p.cross_check == 1) && p.radius >= 0;
+}
+
+int describe_refusals(klt_ctx *c, int slot, int fb_in, int fb_desc, int n, Slot **out)
+{
     if (n < 0) return fail(c, KLT_ERR_ARG, "negative feature count");
     if (n > kMaxDescribed) return fail(c, KLT_ERR_ARG, "too many features to describe in one call");
     if (int rc = own_index(c, fb_desc, {fb_in}, kDescNoBuffer, kDescNotDistinct)) return rc;
@@ -60,9 +63,14 @@ int klt_describe_async(klt_ctx *c, int slot, int fb_in, int fb_desc, int n)
     if (s->raw_kind == 0) return fail(c, KLT_ERR_STATE, "slot has no frame");
     if (s->raw_kind != 1) return fail(c, KLT_ERR_STATE, "descriptors take 8-bit frames");
     if (int rc = ingest_refusal(c, s)) return rc;
+    *out = s;
     if (n == 0) return KLT_OK;
     if (int rc = lists_set(c, {fb_in}, n)) return rc;
-    if (int rc = own_records(c, fb_desc, {fb_in}, kDescNotDistinct)) return rc;
+    return own_records(c, fb_desc, {fb_in}, kDescNotDistinct);
+}
+
+int describe_enqueue(klt_ctx *c, Slot *s, int fb_in, int fb_desc, int n)
+{
     // allocations: the pattern, the descriptor records (may grow c->fbs: before any pointer into it is taken), the chain's copies
     if (int rc = ensure_pattern(c)) return rc;
     FeatBuf *bd;
@@ -86,6 +94,19 @@ int klt_describe_async(klt_ctx *c, int slot, int fb_in, int fb_desc, int n)
     if (int rc = mark_consumed(c, &s, 1, c->stream)) return rc;
     HIPCHK(c, hipGetLastError());
     return KLT_OK;
+}
+
+}  // namespace kltapi
+
+extern "C" {
+
+int klt_describe_async(klt_ctx *c, int slot, int fb_in, int fb_desc, int n)
+{
+    if (!c) return KLT_ERR_ARG;
+    Slot *s;
+    if (int rc = describe_refusals(c, slot, fb_in, fb_desc, n, &s)) return rc;
+    if (n == 0) return KLT_OK;
+    return describe_enqueue(c, s, fb_in, fb_desc, n);
 }
 
 int klt_describe(klt_ctx *c, int slot, const klt_feat *in, klt_descriptor *out, int n)

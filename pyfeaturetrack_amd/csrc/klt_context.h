@@ -12,6 +12,7 @@
 //   api_consensus.hip the consensus checks -- motion model, epipolar, homography -- (single pair, batched), their model records in pixels
 //   api_crowd.hip     crowding check (single list, batched)
 //   api_describe.hip  binary descriptors of a slot's 8-bit frame and their Hamming matcher
+//   api_reacquire.hip track identities over a sequence: the bank of lost tracks and their re-acquisition
 //   api_affine.hip    affine consistency check and its per-feature state
 //   api_comm.hip      the multi-GPU entry points (RCCL itself: comm.hip)
 //   api_compat.hip    the reference's literal native boundary (one call = one wavefront), the HIP-graph experiment
@@ -36,10 +37,12 @@ namespace kltapi {
 
 
 enum Family { F_SMOOTH_GRAD, F_PYR_REDUCE, F_GRAD, F_SMOOTH_H, F_SMOOTH_V, F_PYR_H, F_PYR_V, F_GRAD_H, F_GRAD_V, F_TRACK,
-              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_REMAP, F_DESCRIBE, F_MATCH, F_MATCH_RESOLVE, F_COUNT };
+              F_SAT_ROWS, F_SAT_COLS, F_EIGEN, F_SORT, F_NMS, F_SEED, F_AFFINE, F_CROWD_PREPARE, F_CROWD, F_EQ_LUT, F_EQ_APPLY, F_REMAP, F_DESCRIBE, F_MATCH, F_MATCH_RESOLVE,
+              F_REACQ_CLASSIFY, F_REACQ_BANK, F_REACQ_FRESH, F_REACQ_ASSIGN, F_COUNT };
 inline const char *const kFamilyName[F_COUNT] = {"smooth_grad_l0", "pyramid_reduce", "gradients", "smooth_h", "smooth_v", "pyramid_h",
                                           "pyramid_v", "gradient_h", "gradient_v", "track", "sat_rows", "sat_cols",
-                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply", "remap", "describe", "match", "match_resolve"};
+                                          "eigen_keys", "sort", "nms", "seed_map", "affine_check", "crowd_prepare", "crowd_check", "equalize_lut", "equalize_apply", "remap", "describe", "match", "match_resolve",
+                                          "reacquire_classify", "reacquire_bank", "reacquire_fresh", "reacquire_assign"};
 
 struct Level { int nc = 0, nr = 0; float *img = nullptr, *gx = nullptr, *gy = nullptr; };
 
@@ -125,6 +128,8 @@ struct AffState { klt_affine_rec *rec = nullptr; float *tpl = nullptr; int n = 0
 // arrays -- the list in, the list out, the backward records, the guesses, and the private record buffer of klt_track_quality (quality
 // records) and klt_motion_check (the model record).  One set serves them all, the last one two of them: every synchronous entry point
 // has downloaded what it wants before it returns, so no two of them are ever in flight on these buffers.
+// ... and the two descriptor buffers of the track identities (P and Q, exchanged every step: api_reacquire.hip)
+constexpr int kFbReacqDesc[2] = {29991, 29990};
 constexpr int kFbSyncIn = 65534, kFbSyncOut = 65535, kFbSyncBack = 65532, kFbSyncGuess = 65531, kFbSyncOwn = 65530;
 
 // The descriptor table of a batched launch that stays on the device and is sent again only when it differs (send_if_changed)
@@ -355,6 +360,13 @@ struct klt_ctx {
     int4 *match_part = nullptr;
     size_t match_part_cap = 0;
     int match_splits = 0;                                          // klt_match_path
+    // track identities (api_reacquire.hip): the parameters; one allocation made by the begin call (bank, counters, the dense fresh list,
+    // the two sets of nearest-neighbour results) for the begin's n and capacity; the step counter; which of the two descriptor buffers
+    // (kFbReacqDesc) holds P; the launches of the last begin / step (klt_reacquire_path)
+    klt_reacquire_params reacqp{1024, 30, 64, 4, 5, 24};
+    unsigned char *reacq_mem = nullptr;
+    size_t reacq_mem_cap = 0;
+    int reacq_n = -1, reacq_capacity = 0, reacq_k = 0, reacq_cur = 0, reacq_path = 0;      // reacq_n < 0: no sequence begun
     std::vector<AffState> aff;
     int select_aff_state = -1;
     int *placed_d = nullptr;
@@ -424,7 +436,8 @@ struct TimerScope {
         // families whose scope holds ONE launch that goes through klt_launch (the order kernel in front of a tracker and the threshold
         // kernel behind the eigenvalue pass do not): timed by that dispatch's own timestamps.  Scopes with several launches keep the pair
         stamps = c->timing_stamps && (fam == F_SMOOTH_GRAD || fam == F_PYR_REDUCE || fam == F_GRAD || fam == F_TRACK || fam == F_AFFINE || fam == F_CROWD_PREPARE || fam == F_CROWD ||
-                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY || fam == F_REMAP || fam == F_DESCRIBE || fam == F_MATCH || fam == F_MATCH_RESOLVE);
+                                      fam == F_SAT_ROWS || fam == F_SAT_COLS || fam == F_EIGEN || fam == F_EQ_LUT || fam == F_EQ_APPLY || fam == F_REMAP || fam == F_DESCRIBE || fam == F_MATCH || fam == F_MATCH_RESOLVE ||
+                                      fam == F_REACQ_CLASSIFY || fam == F_REACQ_BANK || fam == F_REACQ_FRESH || fam == F_REACQ_ASSIGN);
         if (stamps) { g_klt_stamp_start = t.a; g_klt_stamp_stop = t.b; }      // filled by the launch itself (klt_launch)
         else hipEventRecord(t.a, st);
     }
@@ -580,6 +593,13 @@ int count_live(const klt_feat *f, int n);
 // and held against the first pair's frame size (and level count, if `same_levels`)
 int batch_arguments(klt_ctx *c, std::initializer_list<const int *> columns, int npairs, int n);
 int batch_pair(klt_ctx *c, int slot1, int slot2, bool same_levels, std::vector<Slot *> &used, bool lazy_ok = false);
+
+// ---- api_describe.hip
+// klt_describe_async in its two halves, for a caller with allocations of its own to place between them (api_reacquire.hip): every
+// refusal (nothing is allocated or enqueued; *s = the slot), then the allocations followed by the launch
+int describe_refusals(klt_ctx *c, int slot, int fb_in, int fb_desc, int n, Slot **s);
+int describe_enqueue(klt_ctx *c, Slot *s, int fb_in, int fb_desc, int n);
+bool match_params_ok(const klt_match_params &p);             // what klt_set_match_params takes
 
 // ---- api_select.hip
 // the three summed-area tables of a gradient pair (goodFeaturesUtils.pyx:49-51); rows_only: the column pass is left to the caller

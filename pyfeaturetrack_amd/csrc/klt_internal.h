@@ -228,6 +228,27 @@ struct MatchResolveArgs {
     klt_match_params p;
 };
 
+// track identities (reacquire_kernels.hip).  What the context keeps in device memory for them: the bank, the
+// counters (kReacq* words of `state`), the dense list of the step's fresh slots (their Q records and slot indices) and the two sets of
+// nearest-neighbour results (one int4 per bank entry, one per fresh record: best distance, best index or -1, second distance, 0)
+static_assert(sizeof(klt_ident) == sizeof(klt_feat) && alignof(klt_ident) == alignof(klt_feat), "ident records live in feature buffers");
+static_assert(sizeof(klt_bank_entry) == 64, "a bank entry is four 16-byte pieces");
+enum { kReacqNextId, kReacqHead, kReacqValid, kReacqFresh, kReacqLost, kReacqStateWords = 8 };
+constexpr int kReacqBlock = 256, kReacqWaves = kReacqBlock / 64;
+struct ReacquireArgs {
+    const klt_feat *list;               // Lk
+    const klt_ident *prev;              // I(k-1) (null in a begin)
+    klt_ident *ident;                   // Ik
+    const klt_descriptor *p, *q;        // P, Q
+    klt_bank_entry *bank;
+    int *state;
+    klt_descriptor *fresh_desc;
+    int *fresh_slot;
+    int4 *bank_best, *fresh_best;
+    int n, k, capacity, max_gap;
+    klt_match_params mp;                // (cross_check is not read: always on)
+};
+
 struct AffineArgs {
     const klt_feat *in;      // records before the translation tracker (frame-1 positions)
     klt_feat *out;           // records after it (updated in place)
@@ -535,6 +556,12 @@ void launch_remap(hipStream_t s, const RemapArgs &a);
 void launch_describe(hipStream_t s, const DescribeArgs &a, int mode);
 void launch_match(hipStream_t s, const MatchArgs &a);
 void launch_match_resolve(hipStream_t s, const MatchResolveArgs &a);
+// track identities (reacquire_kernels.hip): the begin launch; a step's classify / deposit / compact launch, its two nearest-neighbour
+// launches (bank entries against fresh records: the rule's queries; fresh records against bank entries: the cross-check) and its assign launch
+void launch_reacquire_begin(hipStream_t s, const ReacquireArgs &a);
+void launch_reacquire_classify(hipStream_t s, const ReacquireArgs &a);
+void launch_reacquire_nearest(hipStream_t s, const ReacquireArgs &a, bool of_bank);
+void launch_reacquire_assign(hipStream_t s, const ReacquireArgs &a);
 void launch_predict_cv(hipStream_t s, const klt_feat *prev, const klt_feat *cur, klt_feat *guess, int n);
 void launch_extract_patch(hipStream_t s, const float *img, int nc, int nr, float x, float y, int w, float *patch, int *bad);
 void launch_track_iterate(hipStream_t s, const float *t_gx, const float *t_gy, const float *t_i, const float *i2, const float *gx2,

@@ -152,6 +152,17 @@ class KLT_TrackingContext:
         # distance -- an identity that survives an occlusion.  False: upright descriptors (what a tracker's small frame-to-frame
         # rotations want); True: steered by the patch's orientation (one of 32 bins), for sets related by an in-plane rotation.
         self.descriptorOrientation = False
+        # Track identities (not in the reference): with reacquireLost = True KLTTrackSequence returns `ft.ident`, a
+        # persistent track id per slot and frame, and KLTUpdateIdentities(tc, img, featurelist) gives the same for the per-frame loop.  A
+        # lost track leaves descriptor and id in a bank of reacquire_capacity entries (a power of two, at most 4096) on the device; a newly
+        # selected feature within reacquire_radius pixels of it (None: anywhere) that matches it mutually within reacquire_max_gap frames
+        # -- Hamming distance at most reacquire_max_distance, ratio test reacquire_ratio (None: off) -- inherits the id.
+        self.reacquireLost = False
+        self.reacquire_radius = 24
+        self.reacquire_max_gap = 30
+        self.reacquire_capacity = 1024
+        self.reacquire_max_distance = 64
+        self.reacquire_ratio = (4, 5)
 
         self.KLTChangeTCPyramid(15)
         self.KLTUpdateTCBorder()

@@ -202,6 +202,35 @@ def crowd_params_from_tc(tc, ncols=None, nrows=None):
     return cp
 
 
+def reacquire_params_from_tc(tc):
+    """tc.reacquireLost (False, the default) and, for the track identities it switches on, tc.reacquire_radius (24; None: no gate),
+    tc.reacquire_max_gap (30), tc.reacquire_capacity (1024: a power of two in 1 .. 4096), tc.reacquire_max_distance (64) and
+    tc.reacquire_ratio ((4, 5); None: off) -> None when the switch is off, else the six integers of klt_reacquire_params as a dict.
+    All are read with defaults: a tracking context made elsewhere has none of them.  TypeError / ValueError -- before any device work
+    -- for anything the library would refuse."""
+    from .describeFeatures import match_params
+    on = getattr(tc, "reacquireLost", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("tc.reacquireLost must be True or False (got {0!r})".format(on))
+    if not on:
+        return None
+
+    def integer(name, default):
+        v = getattr(tc, name, default)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Integral):
+            raise TypeError("tc.{0} must be an integer (got {1!r})".format(name, v))
+        return int(v)
+    capacity, max_gap = integer("reacquire_capacity", 1024), integer("reacquire_max_gap", 30)
+    if not (1 <= capacity <= 4096 and capacity & (capacity - 1) == 0):
+        raise ValueError("tc.reacquire_capacity must be a power of two in 1 .. 4096 (got {0})".format(capacity))
+    if not 0 <= max_gap <= 2 ** 31 - 1:
+        raise ValueError("tc.reacquire_max_gap must be at least 0 (got {0})".format(max_gap))
+    m = match_params(getattr(tc, "reacquire_max_distance", 64), getattr(tc, "reacquire_ratio", (4, 5)), True,
+                     getattr(tc, "reacquire_radius", 24))
+    return dict(capacity=capacity, max_gap=max_gap, max_distance=m["max_distance"], ratio_num=m["ratio_num"], ratio_den=m["ratio_den"],
+                radius=m["radius"])
+
+
 EQUALIZATIONS = (None, "clahe")
 
 

@@ -327,6 +327,7 @@ def KLTEqualizeImage(tc, img):
 
 from .params import KLT_RemapTable, KLTCreateRemap, KLTRemapSourcePositions, KLTRemapValidMask, KLTUndistortMap  # noqa: E402,F401  (the remap ingest stage's host side)
 from .describeFeatures import KLT_DescriptorList, KLTDescribeFeatures, KLTMatchDescriptors  # noqa: E402,F401  (descriptors: DESIGN.md section 9n)
+from .trackIdentities import KLTResetIdentities, KLTUpdateIdentities  # noqa: E402,F401  (track identities: DESIGN.md section 9o)
 
 
 def KLTRemapImage(tc, img):

@@ -13,10 +13,10 @@ import contextlib
 import numpy as np
 
 from ._frames import cache_of, pixels_of
-from .backend import (CROWD_DTYPE, FB_CHUNK, FEAT_DTYPE, QUALITY_DTYPE, REPLACING_SOME, SELECTING_ALL, Context, context_of,
-                      _FB_GUESS, _FB_TABLE, _FBC_TABLE, _FBQ_TABLE, _MAX_FRAMES)       # (backend.py has the table of feature-buffer ids)
+from .backend import (CROWD_DTYPE, FB_CHUNK, FEAT_DTYPE, IDENT_DTYPE, QUALITY_DTYPE, REPLACING_SOME, SELECTING_ALL, Context, context_of,
+                      _FB_GUESS, _FB_TABLE, _FBC_TABLE, _FBI_TABLE, _FBQ_TABLE, _MAX_FRAMES)       # (backend.py has the table of feature-buffer ids)
 from .klt import KLT_FeatureTable
-from .params import (NO_POST_TRACK, equalization_for_frames, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc, remap_for_frames, remap_from_tc,
+from .params import (NO_POST_TRACK, equalization_for_frames, equalize_params_from_tc, fb_params_from_tc, light_params_from_tc, motion_prediction_from_tc, post_track_from_tc, reacquire_params_from_tc, remap_for_frames, remap_from_tc,
                      select_grid_from_tc, selection_mask_from_tc)
 from .selectGoodFeatures import _fix_window, _slots_of
 
@@ -164,6 +164,12 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     DESIGN.md section 9l); the clip must then be of single-channel 8-bit frames the tile grid fits (ValueError).
     tc.remap = a KLT_RemapTable: every frame is remapped on the device in front of its pyramid build and of the equalisation (DESIGN.md
     section 9m); the clip must then be of single-channel 8-bit frames of the table's shape (ValueError).
+    tc.reacquireLost = True: every slot of every frame gets a persistent track id, and a lost track whose corner is selected again within
+    tc.reacquire_max_gap frames gets its old id back (tc.reacquire_radius, tc.reacquire_capacity,
+    tc.reacquire_max_distance, tc.reacquire_ratio, tc.descriptorOrientation).  `ft.ident` is a [frames][features] array of
+    backend.IDENT_DTYPE records -- id, gap (frames the track was away), distance (Hamming, of the match), val 0 no track / 1 continued /
+    2 new / 3 re-acquired -- row k computed on the device from list row k as the replacement pass left it, ident row k - 1 and frame k;
+    nothing is added to the host's look per frame.  The clip must be of single-channel 8-bit frames (ValueError).
     `prefetch`: the pyramids of frame k+1 are built on a second HIP stream (KLT_OPT_BUILD_STREAM) while frame k is tracked and its
     lost features are replaced -- same results, the frames then live in a ring of three slots."""
     fb_params_from_tc(tc)                # (ValueError for the forward-backward and the affine check together, before any device work)
@@ -174,6 +180,9 @@ def KLTTrackSequence(tc, frames, nFeatures, replace_lost=True, async_ingest=True
     post_track_from_tc(tc)               # (ValueError for a consensus check's or tc.crowdingCheck's switch or parameters, or a check beside one, likewise)
     equalize_params_from_tc(tc)          # (ValueError for an unknown tc.equalization or parameters out of range, likewise)
     remap_from_tc(tc)                    # (TypeError for a tc.remap that is no KLT_RemapTable, likewise)
+    if reacquire_params_from_tc(tc) is not None:     # (TypeError / ValueError for the switches of the track identities, likewise)
+        from .describeFeatures import descriptor_mode_from_tc
+        descriptor_mode_from_tc(tc)
     ctx = context_of(tc)
     with ctx.lock:                       # one KLT* call at a time per device context (backend.default_context)
         ctx.settle_deferred()
@@ -252,6 +261,15 @@ class _Sequence:
         self.quality_rows = _RecordTable(ctx, _FBQ_TABLE, nFeatures)
         self.model_rows = _RecordTable(ctx, self.check.fb_table, self.check.records) if self.check else None
         self.crowd_rows = _RecordTable(ctx, _FBC_TABLE, nFeatures, skip_empty=True)
+        # tc.reacquireLost: an ident row per frame in a table of its own; the clip must be of 8-bit frames (`ingest` holds the later ones to it)
+        self.reacquire = reacquire_params_from_tc(tc) if nFeatures > 0 else None
+        self.ident_rows = _RecordTable(ctx, _FBI_TABLE, nFeatures, skip_empty=True)
+        if self.reacquire is not None:
+            from .describeFeatures import _describable_frame, descriptor_mode_from_tc
+            _describable_frame(first)
+            ctx.set_descriptor_params(descriptor_mode_from_tc(tc))
+            ctx.set_reacquire_params(**self.reacquire)
+            ctx.__dict__.pop("_ident_owner", None)     # (the context's one sequence is this call's now: KLTUpdateIdentities begins anew)
         workers = STAGER_WORKERS or (2 if first.nbytes >= STAGER_THREADS_FROM_BYTES else 1)
         # frames k+1 .. k+3 on their way, one being filled by each helper thread, one spare; uint8 buffers for 8-bit frames, float32 ones for
         # colour / float frames (the frame `img.convert("F")` would be, made by the helper threads: klt_upload_f32_async takes it from there)
@@ -263,6 +281,8 @@ class _Sequence:
         # the initial selection follows KLTSelectGoodFeatures: the smoothed level-0 image when tc.smoothBeforeSelecting, the raw
         # frame otherwise (selectGoodFeatures.py:183-197) -- level 0 of the pyramid is always smoothed
         ctx.select_async(self.s[0], SELECTING_ALL, bool(tc.smoothBeforeSelecting), self.rows.row(0), nFeatures)
+        if self.reacquire is not None:
+            ctx.reacquire_begin_async(self.s[0], self.rows.row(0), self.ident_rows.row(0), nFeatures)
         self.state = ctx.take_affine_state() if self.affine else None
         if self.affine:
             ctx.affine_alloc(self.state, nFeatures)
@@ -273,6 +293,9 @@ class _Sequence:
         for on, setting in ((self.equalized, "tc.equalization = 'clahe'"), (self.remapped, "tc.remap")):
             if on and (img.dtype != np.uint8 or img.ndim != 2):
                 raise ValueError("{0} takes single-channel 8-bit frames; frame {1} of the clip is not one".format(setting, k))
+        if self.reacquire is not None and k > 0:
+            from .describeFeatures import _describable_frame
+            _describable_frame(img)
         if img.shape != (self.nrows, self.ncols):
             from .error import KLTError
             KLTError("(KLTTrackSequence) Size of incoming image ({0} by {1}) is different from size of previous image "
@@ -332,6 +355,13 @@ class _Sequence:
             self.j = j
             _post_track_async(ctx, self.stages, prev, cur, fb_in, fb_out, n, self)
 
+    def identify(self, k):
+        """tc.reacquireLost: the identity step of frame k, enqueued once list row k is final -- behind the post-track chain, or behind the
+        replacement pass's last launch (the host has looked: klt_select_finish), on the stream both run on -- and before frame k's slot
+        is given to a later frame.  It reads row k and never writes it: the tracker of step k + 1, repeated or not, is unaffected."""
+        if self.reacquire is not None:
+            self.ctx.reacquire_step_async(self.s[k % self.ring], self.rows.row(k), self.ident_rows.row(k - 1), self.ident_rows.row(k), self.n)
+
     # Context.post_track_async's `targets` for step `j`: row j of each stage's table (a chunk of a table is allocated when its stage first
     # asks for a row of it); the crowding check reads row j - 1 of its own table (row 0: no ages yet)
     model = property(lambda q: q.model_rows.row(q.j))
@@ -376,6 +406,8 @@ class _Sequence:
         if stages.crowd is not None:
             ft.crowd = self.crowd_rows.download(nframes).view(CROWD_DTYPE)
             ft.crowd[0] = 0                                          # nothing was tracked into the first frame
+        if self.reacquire is not None:
+            ft.ident = self.ident_rows.download(nframes).view(IDENT_DTYPE)
         for check, _ in stages.consensus:
             records = self.model_rows.download(nframes).view(check.dtype).reshape(nframes)
             if self.n == 0:
@@ -417,6 +449,7 @@ def _drive_ahead(q):
             q.track(k + 1)
         if ctx.select_finish() and k + 1 <= have:
             q.track(k + 1)
+        q.identify(k)                        # (row k is final; before frame k + 3 is sent into this frame's slot)
         if q.stager is not None:
             q.landed(k)
         # (after the look: a repeated tracker needs slot k's pyramids valid.  Putting the send off to behind the NEXT selection's
@@ -441,6 +474,7 @@ def _drive_plain(q):
             q.stage_frame(k + 1, nxt)        # the next frame's upload, build and scores: enqueued while the GPU works on the above
         if q.replace_lost:
             q.ctx.select_finish()
+        q.identify(k)
         if nxt is not None and not q.prefetch:
             q.stage_frame(k + 1, nxt)
 
